@@ -16,6 +16,12 @@ One JSON line on rank 0.  roofline.achieved uses SURVEY.md 8(d)'s algorithmic by
 B = 0.25*L/(L-K+1) + 2*E (E = 24/32/48 B reference node), times the k-mers of pass 1, divided by the HIP-event
 time of pass 1's kernels on the library's stream (sdt_gpu_kernel_time; the locality pipeline is three kernels --
 scatter, split, count -- every k-mer goes through all of them, so their times add).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own (N = 1):
+the TRACK_FIRST configuration and the PCIe-inclusive rate (--extras), the CPU baseline on the reference binary or the
+oracle port with the kmerFreq comparison (--cpu-sample, --cpu-p8) and the whole-pregraph e2e leg (--e2e); without --full
+those fields are null.  --dump-outputs DIR writes what the last timed step returned (rank 0): kmerfreq.npy = the 257
+bins of mark_and_hist, counts.npy = [k-mers counted, distinct nodes, linear nodes], both float64.
 """
 from __future__ import annotations
 
@@ -267,16 +273,19 @@ def main():
     ap.add_argument("--err", type=float, default=0.002)
     ap.add_argument("--sigma", type=float, default=2.0, help="log-normal sigma of the expression weights (SURVEY C5: 2.5)")
     ap.add_argument("--d", type=int, default=0, help="-d: also run the low-coverage filter (k_delow) in every step")
-    ap.add_argument("--cpu-sample", type=int, default=8_000_000, help="reads timed on the CPU baseline (0 = skip); the default keeps the reference at ~25 s of wall clock on 16 cores")
-    ap.add_argument("--cpu-p8", action="store_true", help="cpu_baseline: also time the reference with its default -p 8")
-    ap.add_argument("--e2e", type=int, default=1, help="N=1: let the reference finish its whole pregraph on the CPU sample, run sdt-pregraph on "
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: --extras, the CPU baseline and the e2e leg "
+                                                        "(off: a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-sample", type=int, default=8_000_000, help="--full: reads timed on the CPU baseline (0 = skip); the default keeps the reference at ~25 s of wall clock on 16 cores")
+    ap.add_argument("--cpu-p8", action="store_true", help="--full, cpu_baseline: also time the reference with its default -p 8")
+    ap.add_argument("--e2e", type=int, default=1, help="--full, N=1: let the reference finish its whole pregraph on the CPU sample, run sdt-pregraph on "
                                                        "the same config and compare the five files (0 = skip: the reference is stopped at *.kmerFreq)")
     ap.add_argument("--est-distinct", type=int, default=0)
     ap.add_argument("--pipeline", choices=["auto", "direct", "superkmer"], default="auto",
                     help="pass-1 kernel family: 'direct' = one device atomic per occurrence (k_count_reads); 'superkmer' = "
                          "minimizer buckets of super-k-mers counted in LDS (k_sk_*); 'auto' = the library's default")
     ap.add_argument("--track-first", action="store_true", help="SDT_FLAG_TRACK_FIRST: what the five-file pipeline runs with")
-    ap.add_argument("--extras", type=int, default=1, help="N=1: also time the TRACK_FIRST configuration and the PCIe-inclusive "
+    ap.add_argument("--extras", type=int, default=1, help="--full, N=1: also time the TRACK_FIRST configuration and the PCIe-inclusive "
                                                           "rate through sdt_gpu_push_reads (0 = skip)")
     ap.add_argument("--force-sharded", action="store_true", help="run the N>1 code path even with one rank")
     ap.add_argument("--own-reads", action="store_true",
@@ -434,6 +443,11 @@ def main():
     (kmers, nodes, linear, hist), dt = timed(g, args.steps, args.warmup)
     assert kmers == kmers_total, f"processed {kmers} k-mers, expected {kmers_total}"
     assert int(hist.sum()) == nodes, "kmerFreq bins do not add up to the node count"
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results as a caller of the path receives them (all-reduced over the ranks); counts < 2^53: exact in float64
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "kmerfreq.npy"), np.asarray(hist, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "counts.npy"), np.array([kmers, nodes, linear], dtype=np.float64))
     stage_ms, sk_counters = g.stage_times()
     kms, launches, _ = g.kernel_time(reset=True)
     log("table slots:", g.table_slots())
@@ -511,10 +525,10 @@ def main():
                            "note": "ms = sum over this rank's exchanges of the time between the two events around each grouped send/recv "
                                    "(payload + metas in one group); per link = bytes to one peer / that time; xGMI peak ~153 GB/s per "
                                    "link and direction"}
-    # ---- extras (N = 1): the configuration the five-file pipeline runs with, and the rate from host buffers ----
+    # ---- extras (--full, N = 1): the configuration the five-file pipeline runs with, and the rate from host buffers ----
     out["track_first"] = None
     out["pcie_inclusive"] = None
-    if world == 1 and not sharded_path and args.extras and not args.track_first:
+    if args.full and world == 1 and not sharded_path and args.extras and not args.track_first:
         g.close()
         g = None
         try:
@@ -602,7 +616,7 @@ def main():
                                              "three runs; frac_of_h2d_bound = time of the bare copy of the same bytes / time of the run: 1.0 = the link is the limit"}
         except Exception as e:
             log("pcie extra failed:", repr(e))
-    if rank == 0 and world == 1 and not sharded_path and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and not sharded_path and args.cpu_sample > 0:
         try:
             def gpu_hist(m):
                 """257 bins of the first m reads of the workload, by the kernels the step above ran"""

@@ -691,6 +691,34 @@ def test_bench_two_ranks_on_one_device_equal_one_rank(pkg, tmp_path):
         assert a["config"][k] == b["config"][k], k
 
 
+def test_bench_dump_outputs_hold_the_last_step(pkg, tmp_path):
+    """bench.py --dump-outputs DIR: kmerfreq.npy holds the 257 bins the result line's kmerfreq_sha1 hashes, counts.npy its k-mer, node
+    and linear-node counts (float64); a second run with the same arguments writes the same arrays; a plain run (no --full) leaves the
+    legs that take runs of their own null"""
+    import hashlib
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--reads", "1000000", "--T", "2000", "--steps", "2", "--warmup", "1"]
+    got = []
+    for i in range(2):
+        d = tmp_path / f"dump{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + ["--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads(r.stdout.strip().splitlines()[-1])
+        hist, counts = np.load(d / "kmerfreq.npy"), np.load(d / "counts.npy")
+        assert hist.dtype == np.float64 and hist.shape == (257,) and counts.dtype == np.float64
+        assert hashlib.sha1(hist.astype(np.int64).tobytes()).hexdigest() == j["config"]["kmerfreq_sha1"]
+        assert counts.tolist() == [j["config"]["kmers"], j["config"]["distinct_nodes"], j["config"]["linear_nodes"]]
+        assert j["steps"] == 2 and j["ms_per_step"] > 0
+        assert all(j[k] is None for k in ("track_first", "pcie_inclusive", "cpu_baseline", "e2e"))
+        got.append((hist, counts))
+    assert (got[0][0] == got[1][0]).all() and (got[0][1] == got[1][1]).all()
+
+
 def py_minor_out_dry(keys_int, l, rf, cnt, K, threshold):
     """removeMinorOut's junction test (cutTipPreGraph.c:591-1010, 1012-1076) restated on Python ints:
     {junction index: [8 neighbour entries]} for the junctions that would cut, and the set of neighbours to cut"""

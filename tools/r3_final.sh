@@ -14,5 +14,5 @@ bash tools/pmc_sq.sh $O/sq --est-distinct 809675638
 python3 tools/pmc_sq_summary.py $O/sq 24000000000 $O/sq_pass1_200M_k31.json > $O/sq_summary.txt 2>&1
 find $O/sq -name "pass_*" -type d | xargs rm -rf
 mkdir -p profiles/r3 && cp $O/pmc_pass1_200M_k31.json profiles/r3/pmc_pass1_200M_k31.json      # bench.py reads the traffic from here
-timeout 900 python bench.py > $O/bench_default_200M_k31.json 2> $O/bench_default_200M_k31.err
+timeout 900 python bench.py --full > $O/bench_default_200M_k31.json 2> $O/bench_default_200M_k31.err
 tail -1 $O/bench_default_200M_k31.json | cut -c1-300

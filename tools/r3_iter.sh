@@ -5,7 +5,7 @@ O=gpurun_out/r3_iter; mkdir -p $O
 timeout 60 python bench.py --reads 5000000 --cpu-sample 0 --extras 0 --steps 1 --warmup 0 2>&1 | grep "stage ms" | cut -c1-110 || { echo "5M run failed/slow"; exit 1; }
 timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_fullsize.py -x -q -m gpu -k "golden or node_table or saturation or hot or growth or edge_cases or device_resident or first_occurrence or wide_key or seq_scatter or fullsize or c2 or c4" > $O/pytest.log 2>&1
 tail -3 $O/pytest.log
-timeout 300 python bench.py --cpu-sample 0 ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --cpu-sample 0 ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err
 grep "stage ms" $O/bench.err | tail -2
 python3 - <<'E'
 import json

@@ -4,7 +4,7 @@
 # with -p <all cores> AND its default -p 8, with the reference's own "time spent on hash reads".  usage: r3_matrix.sh <out dir>
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.." || exit 1
 O=${1:-gpurun_out/r3_matrix}; mkdir -p $O
-run() { name=$1; shift; timeout ${MATRIX_TIMEOUT:-900} python bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err; python3 - $O/bench_$name.json $name <<'E'
+run() { name=$1; shift; timeout ${MATRIX_TIMEOUT:-900} python bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err; python3 - $O/bench_$name.json $name <<'E'
 import json, sys
 try:
     j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

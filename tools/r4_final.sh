@@ -12,9 +12,9 @@ python3 tools/pmc_pipeline_summary.py $O/pmc200 200000000 150 31 1 $O/pmc_pass1_
 cp $O/pmc200/kernel_stats.csv $O/kernel_stats_bench_200M_k31.csv 2>/dev/null; cp $O/pmc200/bench_under_rocprof.json $O/bench_under_rocprof_200M_k31.json 2>/dev/null
 find $O/pmc200 -name "pass_*" -type d | xargs rm -rf
 mkdir -p profiles/r4 && cp $O/pmc_pass1_200M_k31.json profiles/r4/pmc_pass1_200M_k31.json      # bench.py reads the traffic from here
-timeout 900 python bench.py > $O/bench_default_200M_k31.json 2> $O/bench_default_200M_k31.err
+timeout 900 python bench.py --full > $O/bench_default_200M_k31.json 2> $O/bench_default_200M_k31.err
 tail -1 $O/bench_default_200M_k31.json | cut -c1-300
-run() { name=$1; shift; timeout 600 python bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err; tail -1 $O/bench_$name.json | cut -c1-160; }
+run() { name=$1; shift; timeout 600 python bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err; tail -1 $O/bench_$name.json | cut -c1-160; }
 run K23_100bp_200M --reads 200000000 --read-len 100 --K 23 --cpu-sample 4000000
 run K63_250bp_50M --reads 50000000 --read-len 250 --K 63 --cpu-sample 2000000
 run K95_250bp_50M --reads 50000000 --read-len 250 --K 95 --cpu-sample 2000000 --extras 0

@@ -16,12 +16,12 @@ if [ "$1" = "a" ]; then
   python3 tools/pmc_pipeline_summary.py $O/pmc200log 200000000 150 31 1 $O/pmc_nodelog_200M_k31.json
   cp $O/pmc200log/kernel_stats.csv $O/kernel_stats_bench_200M_k31_nodelog.csv 2>/dev/null
   find $O/pmc200log -name "pass_*" -type d | xargs rm -rf
-  SDT_TIMING=1 timeout 900 python bench.py > $O/bench_default_200M_k31.json 2> $O/bench_default_200M_k31.err
+  SDT_TIMING=1 timeout 900 python bench.py --full > $O/bench_default_200M_k31.json 2> $O/bench_default_200M_k31.err
   tail -1 $O/bench_default_200M_k31.json | cut -c1-300
-  SDT_PASS1_TABLE=log timeout 600 python bench.py --cpu-sample 0 > $O/bench_nodelog_200M_k31.json 2> $O/bench_nodelog_200M_k31.err
+  SDT_PASS1_TABLE=log timeout 600 python bench.py --full --cpu-sample 0 > $O/bench_nodelog_200M_k31.json 2> $O/bench_nodelog_200M_k31.err
   tail -1 $O/bench_nodelog_200M_k31.json | cut -c1-200
 else
-  run() { name=$1; shift; timeout 700 python bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err; python3 - $O/bench_$name.json $name <<'E'
+  run() { name=$1; shift; timeout 700 python bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err; python3 - $O/bench_$name.json $name <<'E'
 import json, sys
 try:
     j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/r6_job1
 mkdir -p $O
-timeout 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -c 3000 $O/bench_default.json
 timeout 600 python3 tools/overlap_probe.py --masks > $O/overlap_probe.json 2> $O/overlap_probe.err
 cat $O/overlap_probe.json; tail -5 $O/overlap_probe.err
