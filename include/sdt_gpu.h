@@ -290,6 +290,14 @@ int sdt_gpu_minor_out_dry(sdt_ctx *ctx, double threshold, uint64_t *records, uin
  *                   open addressing over index_slots = 2^m >= 2n 32-bit words, home slot = mix_key(4-word k-mer) &
  *                   (slots-1), linear probing, value = node index + 1, 0 = empty), filled by the device from its node index. */
 int sdt_gpu_build_host_index(sdt_ctx *ctx, uint32_t *index, uint64_t index_slots);
+/*   build_host_index64: the same with 64-bit entries (value = node index + 1), for graphs past 2^32 - 2 nodes.
+ * Node indices of the graph phases (set_node_index, layout_apply, layout_on_device number the nodes) take one of two forms,
+ * fixed when the nodes are numbered: 32-bit below 2^32 - 16 nodes, 64-bit past that or when the caller asked for it.
+ *   set_graph_index_bits: 0 = by node count (the default), 64 = the 64-bit form at the next numbering.
+ *   graph_index_bits:     32 or 64, the form of the numbering in effect (before one: the form the next one takes). */
+int sdt_gpu_build_host_index64(sdt_ctx *ctx, uint64_t *index, uint64_t index_slots);
+int sdt_gpu_set_graph_index_bits(sdt_ctx *ctx, int bits);
+int sdt_gpu_graph_index_bits(const sdt_ctx *ctx);
 /*   edge_ports:     kmer2edges' walks (node2edge.c:46-191): for every node that is neither linear nor deleted one
  *                   record of 17 words -- node index, then for each of its 8 ports (right links 0..3 on the stored
  *                   strand, left links 0..3 on the reverse strand) the index of the first non-linear node the chain

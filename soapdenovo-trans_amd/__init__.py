@@ -71,6 +71,9 @@ _ABI = [
                                          _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_edge_ports", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_build_host_index", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64]),
+    ("sdt_gpu_build_host_index64", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64]),
+    ("sdt_gpu_set_graph_index_bits", _c.c_int, [_c.c_void_p, _c.c_int]),
+    ("sdt_gpu_graph_index_bits", _c.c_int, [_c.c_void_p]),
     ("sdt_gpu_layout_sorted_keys", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_layout_apply", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64]),
     ("sdt_gpu_layout_on_device", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(_c.c_uint64)]),

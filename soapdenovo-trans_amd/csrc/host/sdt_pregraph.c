@@ -454,15 +454,20 @@ static int dev_index_hook(graph_t *g, void *user)
 	const double t0 = now_ms();
 	if (dev_mirror_sync(g) != 0) exit(1);
 	const double t1 = now_ms();
-	if (g->index64)
-		return 1;                                                        /* a graph past 2^32 nodes: the host builds its 64-bit index */
 	uint64_t cap = 1024;
 	while (cap < 2 * g->n + 2) cap <<= 1;
-	g->index = (uint32_t *)malloc(cap * sizeof(uint32_t));
-	g->index_mask = cap - 1;
-	if (!g->index || sdt_gpu_build_host_index(D->gpu, g->index, cap) != SDT_OK) {
-		fprintf(stderr, "sdt_gpu_build_host_index: %s\n", sdt_gpu_last_error());
-		exit(1);
+	if (g->index64) {                                                    /* a graph past 2^32 nodes: 64-bit entries (calloc'ed by graph.c) */
+		if (sdt_gpu_build_host_index64(D->gpu, g->index64, g->index_mask + 1) != SDT_OK) {
+			fprintf(stderr, "sdt_gpu_build_host_index64: %s\n", sdt_gpu_last_error());
+			exit(1);
+		}
+	} else {
+		g->index = (uint32_t *)malloc(cap * sizeof(uint32_t));
+		g->index_mask = cap - 1;
+		if (!g->index || sdt_gpu_build_host_index(D->gpu, g->index, cap) != SDT_OK) {
+			fprintf(stderr, "sdt_gpu_build_host_index: %s\n", sdt_gpu_last_error());
+			exit(1);
+		}
 	}
 	if (sdt_env("SDT_TIMING")) fprintf(stderr, "[graph]      node order to the device %.1f ms, index built + copied back %.1f ms\n", t1 - t0, now_ms() - t1);
 	return 0;
@@ -852,16 +857,24 @@ int main(int argc, char **argv)
 		const int nwk = sdt_gpu_key_words(gpu), nwv = max_k <= 31 ? 1 : (max_k <= 63 ? 2 : 4);
 		if (sdt_gpu_export_nodes(gpu, NULL, NULL, NULL, NULL, NULL, 0, &n) != SDT_OK) { fprintf(stderr, "%s\n", sdt_gpu_last_error()); return 1; }
 		/* Past 2^32 - 16 nodes (the reference's sets are 64-bit: inc/newhash.h:79-88 `ubyte8 size, count, max`) the device's graph phases
-		 * are out -- their walk records, component labels, layout ranks and edge records carry 32-bit node indices -- and the documented
-		 * fallback takes over: the nodes go to the host in one export, the host replays the layout, builds its 64-bit index
-		 * (graph_t.index64) and runs cutting and kmer2edges on its threads; pass 1 and the second read pass stay on the device (they
-		 * address the table by key).  SDT_NODE_LIMIT moves the threshold so that the tests can take this path on a golden case. */
+		 * take their 64-bit node indices (sdt_gpu_set_graph_index_bits; the library would pick them by node count anyway): layout,
+		 * cutting and edges stay on the device, and the host's look-up index gets 64-bit entries (graph.c, from the device).  Where the
+		 * host route is taken anyway (--host-walks, --host-map, -p > 256, SDT_HOST_LAYOUT) the host replays the layout, builds its 64-bit
+		 * index itself and runs cutting and kmer2edges on its threads.  SDT_NODE_LIMIT moves the threshold so that the tests can take
+		 * these paths on a golden case. */
 		const uint64_t node_limit = sdt_test_env("SDT_NODE_LIMIT") ? strtoull(sdt_test_env("SDT_NODE_LIMIT"), NULL, 10) : 0xFFFFFFF0ULL;
 		if ((gpus > 1 ? nodes : n) >= node_limit) {
-			if (!g_quiet) fprintf(stderr, "[sdt-pregraph] %llu nodes: past the 32-bit node indices of the device's graph phases; layout, cutting and edges run on the host\n",
-			                      (unsigned long long)(gpus > 1 ? nodes : n));
-			host_walks = 1;
-			graph_force_wide_index = 1;
+			const int device_route = !host_map && !host_walks && threads <= 256 && !sdt_test_env("SDT_HOST_LAYOUT");
+			if (device_route) {
+				if (sdt_gpu_set_graph_index_bits(gpu, 64) != SDT_OK) { fprintf(stderr, "sdt_gpu_set_graph_index_bits: %s\n", sdt_gpu_last_error()); return 1; }
+				if (!g_quiet) fprintf(stderr, "[sdt-pregraph] %llu nodes: past the 32-bit node indices; the device runs layout, cutting and edges with 64-bit node indices\n",
+				                      (unsigned long long)(gpus > 1 ? nodes : n));
+			} else {
+				if (!g_quiet) fprintf(stderr, "[sdt-pregraph] %llu nodes: past the 32-bit node indices of the device's graph phases; layout, cutting and edges run on the host\n",
+				                      (unsigned long long)(gpus > 1 ? nodes : n));
+				host_walks = 1;
+				graph_force_wide_index = 1;
+			}
 		}
 		uint64_t *keys, *first = NULL;
 		uint32_t *ll, *rf, *cnt;
@@ -949,7 +962,7 @@ int main(int argc, char **argv)
 				return 0;
 			}
 			n = nodes;                                            /* all shards */
-			const int device_layout = !host_map && !host_walks && threads <= 256 && n < node_limit && !sdt_test_env("SDT_HOST_LAYOUT");
+			const int device_layout = !host_map && !host_walks && threads <= 256 && !sdt_test_env("SDT_HOST_LAYOUT");
 			keys_in_device = device_layout;
 			if (device_layout) {
 				/* the shards go straight into rank 0's device table (it then lays the whole graph out like a single-GPU run: below);
@@ -995,7 +1008,7 @@ int main(int argc, char **argv)
 			}
 			}
 		}
-		if ((gpus == 1 || keys_in_device) && !host_map && !host_walks && threads <= 256 && n < node_limit && !sdt_test_env("SDT_HOST_LAYOUT")) {
+		if ((gpus == 1 || keys_in_device) && !host_map && !host_walks && threads <= 256 && !sdt_test_env("SDT_HOST_LAYOUT")) {
 			/* the visiting order with the device: it sorts the nodes by (set, first occurrence) and sends the keys, the host
 			 * replays the probing of every set (graph_replay_order), the device numbers the nodes and sends them in that order */
 			keys = (uint64_t *)malloc((n + 1) * (size_t)nwk * 8);

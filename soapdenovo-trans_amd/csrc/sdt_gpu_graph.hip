@@ -5,45 +5,11 @@
 //   dry runs    the read-only halves of removeMinorOut / removeSingleTips / removeMinorTips (cutTipPreGraph.c) and of
 //               kmer2edges (node2edge.c), labelled with the connected components the ordered commits may run side by side
 //               (union-find over node indices), sorted by (component, node)
+// The phases that hold node indices are templates over the index form (sdt_graph_phases.hpp): the 32-bit form is instantiated
+// here, the 64-bit one in sdt_gpu_graph64.hip; the entry points pick the form the numbering fixed.
 // gfx950 only; no CPU fallback.  The context is seen through sdti::GraphView (sdt_internal.hpp).
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <rocprim/rocprim.hpp>
+#include "sdt_graph_phases.hpp"
 
-#include "sdt_internal.hpp"
-
-using namespace sdt;
-
-#include "sdt_append.cuh"
-#include "sdt_graph_kernels.cuh"
-
-using sdti::fail;
-using sdti::GraphView;
-
-struct sdti::GraphExt {
-	uint64_t *d_sval = nullptr;       // rank in (set, first-occurrence) order -> table slot   (layout_sorted_keys .. layout_apply)
-	uint64_t n_sorted = 0;
-	uint64_t *d_slot_of = nullptr;    // node index (visiting order) -> table slot
-	uint64_t n_nodes = 0;
-	uint64_t *d_result = nullptr;     // records of the last labelled dry run, waiting for sdt_gpu_fetch_records
-	uint64_t result_words = 0;
-	uint64_t result_labelled = 0;     // the first so many of them are sorted by (component, node)
-	int result_stride = 0;
-	uint64_t *d_wnode = nullptr;      // nodes the last sdt_gpu_minor_out_commit wrote, waiting for sdt_gpu_fetch_written
-	uint32_t *d_wl = nullptr, *d_wr = nullptr;
-	uint64_t n_written = 0;
-	uint64_t *d_skipped = nullptr;    // records of the components that commit left to the host, waiting for sdt_gpu_fetch_skipped
-	uint64_t n_skipped = 0;
-	bool mo_pending = false;          // between sdt_gpu_minor_out_commit_begin and _finish: what the launched kernels work on
-	uint8_t *mo_dirty = nullptr;
-	unsigned long long *mo_cnt = nullptr;
-	uint32_t *mo_recidx = nullptr, *mo_cstart = nullptr;
-	unsigned char *d_seq = nullptr;   // bases of the edges of sdt_gpu_build_edges, waiting for sdt_gpu_fetch_edge_bases
-	uint64_t seq_bytes = 0;
-	uint64_t *d_pw = nullptr;         // path word of every node after sdt_gpu_build_edges (taken by sdt_gpu_load_paths)
-	uint64_t pw_n = 0;
-};
 
 void sdti::graph_ext_free(GraphExt *gx)
 {
@@ -64,6 +30,36 @@ void sdti::graph_ext_free(GraphExt *gx)
 	delete gx;
 }
 
+int graph_choose_form(sdti::GraphExt *gx, uint64_t n)
+{
+	gx->wide = gx->want_bits == 64 || n >= 0xFFFFFFF0ULL;
+	gx->base = 0;
+	// (SDT_NODE_BASE: test hook -- the 64-bit form numbers the nodes from this base, so that a node index cut to 32 bits anywhere on
+	// the device changes the output of a small input)
+	const char *b = sdt_test_env("SDT_NODE_BASE");
+	if (gx->wide && b && *b) gx->base = strtoull(b, nullptr, 0);
+	if (gx->base + n >= (1ULL << 55))
+		return fail(SDT_EINVAL, "node indices %llu .. %llu do not fit the 56-bit fields of the records", (unsigned long long)gx->base, (unsigned long long)(gx->base + n));
+	return SDT_OK;
+}
+
+// node indices of records that leave the device are host array positions: base + position -> position (SDT_NODE_BASE only).
+// stride 3 (tip walks): node | info << 56, end node, label; stride 14 (minor out): node, 8 x (neighbour << 1 | smaller) or ~0,
+// 4 count words, label
+static void rebase_records(uint64_t *rec, uint64_t nrec, int stride, uint64_t base)
+{
+	const uint64_t M = 0x00FFFFFFFFFFFFFFULL;
+	for (uint64_t r = 0; r < nrec; r++) {
+		uint64_t *R = rec + r * (uint64_t)stride;
+		R[0] = (R[0] & ~M) | ((R[0] & M) - base);
+		if (stride == 3) R[1] -= base;
+		else for (int q = 1; q <= 8; q++) if (R[q] != ~0ULL) R[q] -= 2 * base;
+		R[stride - 1] -= base;
+	}
+}
+
+uint64_t sdti::graph_node_base(const GraphExt *gx) { return gx ? gx->base : 0; }
+
 uint64_t *sdti::graph_take_path_words(GraphExt *gx, uint64_t n)
 {
 	if (!gx || !gx->d_pw || gx->pw_n != n) return nullptr;
@@ -71,77 +67,6 @@ uint64_t *sdti::graph_take_path_words(GraphExt *gx, uint64_t n)
 	gx->d_pw = nullptr;
 	gx->pw_n = 0;
 	return p;
-}
-
-static sdti::GraphExt *ext_of(const GraphView &v)
-{
-	if (!*v.gx) *v.gx = new sdti::GraphExt();
-	return *v.gx;
-}
-
-#define LAUNCH_NW(v, kernel, grid, ...)                                                                                      \
-	do {                                                                                                                     \
-		if ((v).nw == 1) hipLaunchKernelGGL(kernel<1>, dim3(grid), dim3(TPB), 0, (v).stream, sdti::table_of<1>(v), __VA_ARGS__);      \
-		else if ((v).nw == 2) hipLaunchKernelGGL(kernel<2>, dim3(grid), dim3(TPB), 0, (v).stream, sdti::table_of<2>(v), __VA_ARGS__); \
-		else hipLaunchKernelGGL(kernel<4>, dim3(grid), dim3(TPB), 0, (v).stream, sdti::table_of<4>(v), __VA_ARGS__);                  \
-	} while (0)
-
-// every device buffer of a call in one place: freed when the call returns, whatever the path
-struct Scratch {
-	void *p[96] = {};
-	int n = 0;
-	template <class T> hipError_t alloc(T **out, size_t bytes)
-	{
-		void *q = nullptr;
-		if (n == (int)(sizeof p / sizeof p[0])) { *out = nullptr; return hipErrorOutOfMemory; }
-		const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-		if (e == hipSuccess) p[n++] = q;
-		*out = (T *)q;
-		return e;
-	}
-	void *release(void *q)                                    // the caller keeps q
-	{
-		for (int i = 0; i < n; i++) if (p[i] == q) p[i] = nullptr;
-		return q;
-	}
-	~Scratch() { for (int i = 0; i < n; i++) if (p[i]) (void)hipFree(p[i]); }
-};
-
-#define GCHK(expr) do { hipError_t e9_ = (expr); if (e9_ != hipSuccess) return fail(e9_ == hipErrorOutOfMemory ? SDT_ENOMEM : SDT_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e9_), __FILE__, __LINE__); } while (0)
-
-// device-wide sort of (key, value) pairs by the key bits [0, end_bit): rocPRIM's radix sort ping-pongs between the caller's input and
-// output arrays (double buffers: the INPUT arrays are scratch afterwards), so its own temporary storage stays small -- with separate
-// in / out arrays it asked for as much again as the pairs (10 GiB at 678 M nodes, from the driver)
-template <class V>
-static int sort_pairs(const GraphView &v, uint64_t *k_in, uint64_t *k_out, V *v_in, V *v_out, uint64_t n, unsigned end_bit)
-{
-	rocprim::double_buffer<uint64_t> dk(k_in, k_out);
-	rocprim::double_buffer<V> dv(v_in, v_out);
-	size_t tmp_bytes = 0;
-	GCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, dk, dv, (size_t)n, 0u, end_bit, v.stream));
-	void *tmp = nullptr;
-	GCHK(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
-	hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, dk, dv, (size_t)n, 0u, end_bit, v.stream);
-	if (e == hipSuccess && dk.current() != k_out) e = hipMemcpyAsync(k_out, dk.current(), n * sizeof(uint64_t), hipMemcpyDeviceToDevice, v.stream);
-	if (e == hipSuccess && dv.current() != v_out) e = hipMemcpyAsync(v_out, dv.current(), n * sizeof(V), hipMemcpyDeviceToDevice, v.stream);
-	const hipError_t e2 = hipStreamSynchronize(v.stream);
-	(void)hipFree(tmp);
-	if (e != hipSuccess || e2 != hipSuccess) return fail(SDT_EHIP, "radix sort of %llu pairs: %s", (unsigned long long)n, hipGetErrorString(e != hipSuccess ? e : e2));
-	return SDT_OK;
-}
-
-template <class T>
-static int exclusive_scan(const GraphView &v, const T *in, T *out, uint64_t n)
-{
-	size_t tmp_bytes = 0;
-	GCHK(rocprim::exclusive_scan(nullptr, tmp_bytes, in, out, T(0), (size_t)n, rocprim::plus<T>(), v.stream));
-	void *tmp = nullptr;
-	GCHK(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
-	const hipError_t e = rocprim::exclusive_scan(tmp, tmp_bytes, in, out, T(0), (size_t)n, rocprim::plus<T>(), v.stream);
-	const hipError_t e2 = hipStreamSynchronize(v.stream);
-	(void)hipFree(tmp);
-	if (e != hipSuccess || e2 != hipSuccess) return fail(SDT_EHIP, "prefix sum over %llu items: %s", (unsigned long long)n, hipGetErrorString(e != hipSuccess ? e : e2));
-	return SDT_OK;
 }
 
 
@@ -176,49 +101,6 @@ int sdti::sort_arcs_for_output(hipStream_t stream, int cu_count, uint32_t *d_fro
 	return SDT_OK;
 }
 
-// ---- records appended in chunks per wave (sdt_append.cuh): storage, and packing into one dense array ---------------------
-struct ApBuf {
-	uint64_t *chunks = nullptr;
-	uint32_t *fill = nullptr, *off = nullptr;
-	unsigned long long *cursor = nullptr;
-	uint64_t cap_chunks = 0;
-	int stride = 0;
-};
-static ApOut ap_out(const ApBuf &B) { return ApOut{B.cursor, B.cap_chunks, B.fill, nullptr}; }
-// room for `records` records of `stride` words (a closed chunk holds more than AP_CH - 64 records, every wave has one open chunk)
-static int ap_alloc(Scratch &S, const GraphView &v, ApBuf &B, uint64_t records, int stride)
-{
-	B.cap_chunks = records / (AP_CH - 64) + 1 + (uint64_t)v.cu_count * 8 * (TPB / 64);
-	B.stride = stride;
-	GCHK(S.alloc(&B.chunks, B.cap_chunks * AP_CH * (size_t)stride * 8));
-	GCHK(S.alloc(&B.fill, (B.cap_chunks + 1) * 4)); GCHK(S.alloc(&B.off, (B.cap_chunks + 1) * 4)); GCHK(S.alloc(&B.cursor, 8));
-	GCHK(hipMemsetAsync(B.fill, 0, (B.cap_chunks + 1) * 4, v.stream));
-	GCHK(hipMemsetAsync(B.cursor, 0, 8, v.stream));
-	return SDT_OK;
-}
-static void ap_free(Scratch &S, ApBuf &B)
-{
-	(void)hipFree(S.release(B.chunks)); (void)hipFree(S.release(B.fill)); (void)hipFree(S.release(B.off)); (void)hipFree(S.release(B.cursor));
-	B = ApBuf();
-}
-// the records of chunks [0, n_chunks) packed in chunk order into a new array (the caller's Scratch owns it); *n_split = the records
-// of the chunks before split_chunk (what an earlier kernel wrote)
-static int ap_compact(Scratch &S, const GraphView &v, const ApBuf &B, uint64_t n_chunks, uint64_t split_chunk, uint64_t **out, uint64_t *n_out, uint64_t *n_split)
-{
-	if (n_chunks > B.cap_chunks) return fail(SDT_ESTATE, "records in chunks: %llu chunks taken, room for %llu", (unsigned long long)n_chunks, (unsigned long long)B.cap_chunks);
-	const int rc = exclusive_scan<uint32_t>(v, B.fill, B.off, n_chunks + 1);          // (fill[n_chunks] is 0: off[n_chunks] = all records)
-	if (rc != SDT_OK) return rc;
-	uint32_t tot = 0, spl = 0;
-	GCHK(hipMemcpy(&tot, B.off + n_chunks, 4, hipMemcpyDeviceToHost));
-	GCHK(hipMemcpy(&spl, B.off + (split_chunk < n_chunks ? split_chunk : n_chunks), 4, hipMemcpyDeviceToHost));
-	GCHK(S.alloc(out, ((size_t)tot + 1) * (size_t)B.stride * 8));
-	if (n_chunks) hipLaunchKernelGGL(k_ap_compact, dim3(sdti::scan_grid(v.cu_count, n_chunks * AP_CH)), dim3(256), 0, v.stream, B.chunks, B.fill, B.off,
-	                                 (unsigned long long)n_chunks, B.stride, *out);
-	GCHK(hipGetLastError());
-	*n_out = tot;
-	if (n_split) *n_split = spl;
-	return SDT_OK;
-}
 
 // ---- the whole layout on the device: sort, replay of the probing (fixed point per growth), numbering ---------------------
 #include <math.h>
@@ -267,8 +149,9 @@ extern "C" int sdt_gpu_layout_on_device(sdt_ctx *c, int p, int nw_variant, int s
 	if (!v.d_first) return fail(SDT_ESTATE, "first-occurrence ordinals were not tracked: init with SDT_FLAG_TRACK_FIRST");
 	if (p < 1 || p > 256) return fail(SDT_EINVAL, "layout on the device: 1..256 sets, asked for %d", p);
 	if (nw_variant < v.nw || nw_variant > 4) return fail(SDT_EINVAL, "a %d-word variant cannot hold %d-word keys", nw_variant, v.nw);
-	if (n >= 0xFFFFFFF0ULL) return fail(SDT_EINVAL, "layout on the device: 32-bit ranks, %llu nodes", (unsigned long long)n);
 	sdti::GraphExt *gx = ext_of(v);
+	rc = graph_choose_form(gx, n);                           // (the ranks of the numbering below: 32-bit below 2^32 - 16 nodes, else 64-bit)
+	if (rc != SDT_OK) return rc;
 	if (gx->d_sval) { (void)hipFree(gx->d_sval); gx->d_sval = nullptr; gx->n_sorted = 0; }
 	Scratch S;
 	const uint64_t m = n ? n : 1;
@@ -333,7 +216,7 @@ extern "C" int sdt_gpu_layout_on_device(sdt_ctx *c, int p, int nw_variant, int s
 	tick("schedule made");
 	// ---- buffers
 	unsigned long long *tab[2], *d_time, *d_saved, *d_list[2], *d_pre;
-	uint32_t *d_home, *d_occ, *d_rank;
+	uint32_t *d_home, *d_occ;
 	RpSet *d_sets;
 	unsigned int *d_flags;
 	RpRound *d_round;
@@ -475,15 +358,13 @@ extern "C" int sdt_gpu_layout_on_device(sdt_ctx *c, int p, int nw_variant, int s
 	(void)hipFree(S.release(tab[cur ^ 1])); (void)hipFree(S.release(d_time)); (void)hipFree(S.release(d_home_slot));
 	(void)hipFree(S.release(d_saved)); (void)hipFree(S.release(d_list[0])); (void)hipFree(S.release(d_list[1]));
 	uint64_t *d_order;
-	GCHK(S.alloc(&d_occ, (slot_total + 1) * 4)); GCHK(S.alloc(&d_rank, (slot_total + 1) * 4)); GCHK(S.alloc(&d_order, m * 8));
+	GCHK(S.alloc(&d_occ, (slot_total + 1) * 4)); GCHK(S.alloc(&d_order, m * 8));
 	hipLaunchKernelGGL(k_rp_slots, grid(slot_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, 1, qbits, (const unsigned long long *)nullptr, tab[cur], d_occ);
 	GCHK(hipGetLastError());
-	rc = exclusive_scan<uint32_t>(v, d_occ, d_rank, slot_total);
+	rc = gx->wide ? sdti::layout_order<Ix64>(v, d_sets, d_pre, p, tab[cur], d_occ, slot_total, d_order)
+	              : sdti::layout_order<Ix32>(v, d_sets, d_pre, p, tab[cur], d_occ, slot_total, d_order);
 	if (rc != SDT_OK) return rc;
-	hipLaunchKernelGGL(k_rp_order, grid(slot_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, tab[cur], d_occ, d_rank, d_order);
-	GCHK(hipGetLastError());
-	GCHK(hipStreamSynchronize(v.stream));
-	(void)hipFree(S.release(tab[cur])); (void)hipFree(S.release(d_occ)); (void)hipFree(S.release(d_rank)); (void)hipFree(S.release(d_home));
+	(void)hipFree(S.release(tab[cur])); (void)hipFree(S.release(d_occ)); (void)hipFree(S.release(d_home));
 	if (timing) fprintf(stderr, "[device]     layout: order extracted at %.1f ms\n", now_ms() - t_call);
 	// ---- number the nodes (as sdt_gpu_layout_apply)
 	if (*v.d_idx) { (void)hipFree(*v.d_idx); *v.d_idx = nullptr; }
@@ -495,8 +376,8 @@ extern "C" int sdt_gpu_layout_on_device(sdt_ctx *c, int p, int nw_variant, int s
 	uint64_t *d_idx, *d_slot_of;
 	GCHK(S.alloc(&d_idx, v.slots * 8)); GCHK(S.alloc(&d_slot_of, m * 8));
 	GCHK(hipMemsetAsync(d_idx, 0xFF, v.slots * 8, v.stream));
-	hipLaunchKernelGGL(k_layout_apply, dim3(sdti::scan_grid(v.cu_count, m)), dim3(TPB), 0, v.stream, v1s, d_order, n, d_idx, d_slot_of, v.d_stats);
-	GCHK(hipGetLastError());
+	rc = gx->wide ? sdti::layout_number(v, ix64_of(gx), v1s, d_order, n, d_idx, d_slot_of) : sdti::layout_number(v, Ix32(), v1s, d_order, n, d_idx, d_slot_of);
+	if (rc != SDT_OK) return rc;
 	rc = sdti::sync_stats(c);
 	if (rc != SDT_OK) return fail(SDT_ESTATE, "layout on the device: %llu positions of the order are not ranks", (unsigned long long)v.h_stats->probe_fail);
 	*v.d_idx = (uint64_t *)S.release(d_idx);
@@ -568,6 +449,8 @@ int sdt_gpu_layout_apply(sdt_ctx *c, const uint64_t *order, uint64_t n)
 	sdti::GraphExt *gx = ext_of(v);
 	if (!gx->d_sval || gx->n_sorted != n) return fail(SDT_ESTATE, "call sdt_gpu_layout_sorted_keys first (it sorted %llu nodes, the order has %llu)", (unsigned long long)gx->n_sorted, (unsigned long long)n);
 	HIPCHK(hipSetDevice(v.device));
+	int rc = graph_choose_form(gx, n);
+	if (rc != SDT_OK) return rc;
 	if (*v.d_idx) { (void)hipFree(*v.d_idx); *v.d_idx = nullptr; }
 	*v.idx_slots = *v.idx_n = 0;
 	if (gx->d_slot_of) { (void)hipFree(gx->d_slot_of); gx->d_slot_of = nullptr; gx->n_nodes = 0; }
@@ -576,10 +459,10 @@ int sdt_gpu_layout_apply(sdt_ctx *c, const uint64_t *order, uint64_t n)
 	const uint64_t m = n ? n : 1;
 	GCHK(S.alloc(&d_order, m * 8)); GCHK(S.alloc(&d_idx, v.slots * 8)); GCHK(S.alloc(&d_slot_of, m * 8));
 	GCHK(hipMemsetAsync(d_idx, 0xFF, v.slots * 8, v.stream));
-	int rc = sdti::h2d_big(v.copy_stream, d_order, order, n * 8);
+	rc = sdti::h2d_big(v.copy_stream, d_order, order, n * 8);
 	if (rc != SDT_OK) return rc;
-	hipLaunchKernelGGL(k_layout_apply, dim3(sdti::scan_grid(v.cu_count, m)), dim3(TPB), 0, v.stream, gx->d_sval, d_order, n, d_idx, d_slot_of, v.d_stats);
-	GCHK(hipGetLastError());
+	rc = gx->wide ? sdti::layout_number(v, ix64_of(gx), gx->d_sval, d_order, n, d_idx, d_slot_of) : sdti::layout_number(v, Ix32(), gx->d_sval, d_order, n, d_idx, d_slot_of);
+	if (rc != SDT_OK) return rc;
 	rc = sdti::sync_stats(c);
 	if (rc != SDT_OK) return fail(SDT_EINVAL, "layout order: %llu entries are not ranks below %llu", (unsigned long long)v.h_stats->probe_fail, (unsigned long long)n);
 	*v.d_idx = (uint64_t *)S.release(d_idx);
@@ -661,125 +544,16 @@ int sdt_gpu_update_nodes_by_index(sdt_ctx *c, const uint64_t *node, const uint32
 	return SDT_OK;
 }
 
-// ---- labelled dry runs ------------------------------------------------------------------------------------------------
-// label the first n_label records (stride words each, node in the low 56 bits of word 0, label into word stride - 1) with the
-// roots of `parent`, sort them by (label, node) and leave all n records in gx->d_result
-static int label_sort_keep(sdt_ctx *c, const GraphView &v, uint32_t *parent, uint64_t *d_rec, uint64_t n, uint64_t n_label, int stride)
-{
-	sdti::GraphExt *gx = ext_of(v);
-	if (gx->d_result) { (void)hipFree(gx->d_result); gx->d_result = nullptr; gx->result_words = 0; }
-	Scratch S;
-	uint64_t *k0, *k1, *d_out;
-	uint32_t *p0, *p1;
-	const uint64_t m = n_label ? n_label : 1;
-	GCHK(S.alloc(&k0, m * 8)); GCHK(S.alloc(&k1, m * 8)); GCHK(S.alloc(&p0, m * 4)); GCHK(S.alloc(&p1, m * 4));
-	GCHK(S.alloc(&d_out, (n ? n : 1) * (size_t)stride * 8));
-	if (n_label) {
-		hipLaunchKernelGGL(k_uf_label, dim3(sdti::scan_grid(v.cu_count, n_label)), dim3(TPB), 0, v.stream, parent, d_rec, n_label, stride, stride - 1, k0, p0);
-		GCHK(hipGetLastError());
-		const int rc = sort_pairs<uint32_t>(v, k0, k1, p0, p1, n_label, 64);
-		if (rc != SDT_OK) return rc;
-		hipLaunchKernelGGL(k_gather_records, dim3(sdti::scan_grid(v.cu_count, n_label * stride)), dim3(TPB), 0, v.stream, d_rec, p1, n_label, stride, d_out);
-		GCHK(hipGetLastError());
-	}
-	if (n > n_label) {                                        // (the records behind the sorted ones keep their order; they get their label too)
-		hipLaunchKernelGGL(k_uf_label_only, dim3(sdti::scan_grid(v.cu_count, n - n_label)), dim3(TPB), 0, v.stream, parent, d_rec, n_label, n, stride, stride - 1);
-		GCHK(hipGetLastError());
-		GCHK(hipMemcpyAsync(d_out + n_label * stride, d_rec + n_label * stride, (n - n_label) * (size_t)stride * 8, hipMemcpyDeviceToDevice, v.stream));
-	}
-	GCHK(hipStreamSynchronize(v.stream));
-	(void)c;
-	gx->d_result = (uint64_t *)S.release(d_out);
-	gx->result_words = n * (uint64_t)stride;
-	gx->result_labelled = n_label;
-	gx->result_stride = stride;
-	return SDT_OK;
-}
-
+// ---- labelled dry runs, the minor-out commit, kmer2edges: entry points of the templates of sdt_graph_phases.hpp ------------
 int sdt_gpu_tip_walks_labelled(sdt_ctx *c, int thin, int cut_len, uint64_t *n_records)
 {
 	if (!c || !n_records) return fail(SDT_EINVAL, "NULL argument");
 	const GraphView v = sdti::graph_view(c);
 	if (!*v.d_idx || *v.idx_slots != v.slots) return fail(SDT_ESTATE, "call sdt_gpu_layout_apply (or sdt_gpu_set_node_index) first");
-	const uint64_t nn = *v.idx_n;
-	if (nn >= 0xFFFFFFF0ULL) return fail(SDT_EINVAL, "component labels are 32-bit node indices: %llu nodes", (unsigned long long)nn);
+	sdti::GraphExt *gx = ext_of(v);
+	if (!gx->wide && *v.idx_n >= 0xFFFFFFF0ULL) return fail(SDT_ESTATE, "%llu nodes numbered in the 32-bit form", (unsigned long long)*v.idx_n);
 	HIPCHK(hipSetDevice(v.device));
-	Scratch S;
-	uint32_t *parent;
-	unsigned long long *d_cur, h = 0;
-	GCHK(S.alloc(&parent, (nn + 1) * 4)); GCHK(S.alloc(&d_cur, 8));
-	hipLaunchKernelGGL(k_uf_init, dim3(sdti::scan_grid(v.cu_count, nn + 1)), dim3(TPB), 0, v.stream, parent, nn + 1);
-	const int g = sdti::scan_grid(v.cu_count, v.slots);
-	uint64_t cap = nn / 8 + 4096;
-	uint64_t *d_rec = nullptr;
-	ApBuf B;
-	for (int attempt = 0; attempt < 2; attempt++) {
-		// the dead ends first (a list of slots), then one lane per walk
-		unsigned long long *d_list, *d_lcur, n_lchunks = 0;
-		const unsigned long long l_chunks = cap / (AP_CH - 64) + 1 + (unsigned long long)v.cu_count * 8 * (TPB / 64);
-		GCHK(S.alloc(&d_list, l_chunks * AP_CH * 8)); GCHK(S.alloc(&d_lcur, 8));
-		GCHK(hipMemsetAsync(d_lcur, 0, 8, v.stream));
-		int rc = ap_alloc(S, v, B, cap, 3);
-		if (rc != SDT_OK) return rc;
-		LAUNCH_NW(v, k_tip_starts, g, thin, d_list, ApOut{d_lcur, l_chunks, nullptr, d_list});
-		GCHK(hipGetLastError());
-		GCHK(hipMemcpyAsync(&n_lchunks, d_lcur, 8, hipMemcpyDeviceToHost, v.stream));
-		GCHK(hipStreamSynchronize(v.stream));
-		if (n_lchunks <= l_chunks) {
-			const unsigned long long n_list = n_lchunks * AP_CH;
-			LAUNCH_NW(v, k_tip_walks_list, sdti::scan_grid(v.cu_count, n_list), *v.d_idx, v.K, thin, cut_len, d_list, n_list, v.d_stats, B.chunks, 3, ap_out(B));
-			GCHK(hipGetLastError());
-			GCHK(hipMemcpyAsync(&h, B.cursor, 8, hipMemcpyDeviceToHost, v.stream));
-			rc = sdti::sync_stats(c);
-			if (rc != SDT_OK) return fail(SDT_ESTATE, "sdt_gpu_tip_walks_labelled: %llu walks left the graph", (unsigned long long)v.h_stats->probe_fail);
-		}
-		(void)hipFree(S.release(d_list)); (void)hipFree(S.release(d_lcur));
-		if (n_lchunks <= l_chunks && h <= B.cap_chunks) break;
-		if (attempt) return fail(SDT_ESTATE, "sdt_gpu_tip_walks_labelled: the number of walks changed between two runs");
-		ap_free(S, B);
-		cap = (n_lchunks > l_chunks ? n_lchunks : h) * AP_CH;          // (every walk has a start: the starts bound the records)
-	}
-	{
-		uint64_t n_rec = 0;
-		const int rc = ap_compact(S, v, B, h, h, &d_rec, &n_rec, nullptr);
-		if (rc != SDT_OK) return rc;
-		GCHK(hipStreamSynchronize(v.stream));
-		ap_free(S, B);
-		h = n_rec;
-	}
-	// components: removeSingleTips -- tip and end node of every walk; removeMinorTips -- the chains a walk can cross
-	if (thin) {
-		if (h) hipLaunchKernelGGL(k_uf_records, dim3(sdti::scan_grid(v.cu_count, h)), dim3(TPB), 0, v.stream, parent, d_rec, (uint64_t)h, 3, 1, 2, 0);
-	} else {
-		// every live port of every node that is neither linear nor deleted: listed, then walked one lane per port
-		unsigned long long *d_list = nullptr, *d_lcur, n_lchunks = 0;
-		GCHK(S.alloc(&d_lcur, 8));
-		unsigned long long l_chunks = nn / (AP_CH - 64) + 1 + (unsigned long long)v.cu_count * 8 * (TPB / 64);
-		for (int attempt = 0; attempt < 2; attempt++) {
-			GCHK(S.alloc(&d_list, l_chunks * AP_CH * 8));
-			GCHK(hipMemsetAsync(d_lcur, 0, 8, v.stream));
-			LAUNCH_NW(v, k_port_starts, g, d_list, ApOut{d_lcur, l_chunks, nullptr, d_list});
-			GCHK(hipGetLastError());
-			GCHK(hipMemcpyAsync(&n_lchunks, d_lcur, 8, hipMemcpyDeviceToHost, v.stream));
-			GCHK(hipStreamSynchronize(v.stream));
-			if (n_lchunks <= l_chunks) break;
-			if (attempt) return fail(SDT_ESTATE, "sdt_gpu_tip_walks_labelled: the number of ports changed between two runs");
-			(void)hipFree(S.release(d_list));
-			l_chunks = n_lchunks;
-		}
-		const unsigned long long n_list = n_lchunks * AP_CH;
-		if (n_list) LAUNCH_NW(v, k_port_union_list, sdti::scan_grid(v.cu_count, n_list), *v.d_idx, v.K, cut_len, d_list, n_list, parent, v.d_stats);
-		GCHK(hipGetLastError());
-		GCHK(hipStreamSynchronize(v.stream));
-		(void)hipFree(S.release(d_list)); (void)hipFree(S.release(d_lcur));
-	}
-	GCHK(hipGetLastError());
-	int rc = sdti::sync_stats(c);
-	if (rc != SDT_OK) return fail(SDT_ESTATE, "sdt_gpu_tip_walks_labelled: %llu chains left the graph", (unsigned long long)v.h_stats->probe_fail);
-	rc = label_sort_keep(c, v, parent, d_rec, h, h, 3);
-	if (rc != SDT_OK) return rc;
-	*n_records = h;
-	return SDT_OK;
+	return gx->wide ? sdti::tip_walks_labelled(c, ix64_of(gx), thin, cut_len, n_records) : sdti::tip_walks_labelled(c, Ix32(), thin, cut_len, n_records);
 }
 
 int sdt_gpu_minor_out_labelled(sdt_ctx *c, double threshold, uint64_t *n_junctions, uint64_t *n_records)
@@ -787,73 +561,13 @@ int sdt_gpu_minor_out_labelled(sdt_ctx *c, double threshold, uint64_t *n_junctio
 	if (!c || !n_junctions || !n_records) return fail(SDT_EINVAL, "NULL argument");
 	const GraphView v = sdti::graph_view(c);
 	if (!*v.d_idx || *v.idx_slots != v.slots) return fail(SDT_ESTATE, "call sdt_gpu_layout_apply (or sdt_gpu_set_node_index) first");
-	const uint64_t nn = *v.idx_n;
-	if (nn >= 0xFFFFFFF0ULL) return fail(SDT_EINVAL, "component labels are 32-bit node indices: %llu nodes", (unsigned long long)nn);
+	sdti::GraphExt *gx = ext_of(v);
+	if (!gx->wide && *v.idx_n >= 0xFFFFFFF0ULL) return fail(SDT_ESTATE, "%llu nodes numbered in the 32-bit form", (unsigned long long)*v.idx_n);
 	HIPCHK(hipSetDevice(v.device));
-	Scratch S;
-	uint32_t *parent;
-	uint8_t *d_need, *d_flag;
-	unsigned long long *d_cur, h1 = 0, h2 = 0;
-	GCHK(S.alloc(&parent, (nn + 1) * 4)); GCHK(S.alloc(&d_cur, 8));
-	GCHK(S.alloc(&d_need, nn + 1)); GCHK(S.alloc(&d_flag, nn + 1));
-	hipLaunchKernelGGL(k_uf_init, dim3(sdti::scan_grid(v.cu_count, nn + 1)), dim3(TPB), 0, v.stream, parent, nn + 1);
-	const int g = sdti::scan_grid(v.cu_count, v.slots);
-	// (one node in twenty has a record in the transcriptome jobs measured; the chunks add a third: room for one in sixteen, a second
-	// attempt with what the first one counted otherwise)
-	uint64_t cap = nn / 16 + 4096;
-	uint64_t *d_rec = nullptr;
-	ApBuf B;
-	for (int attempt = 0; attempt < 2; attempt++) {
-		int rc = ap_alloc(S, v, B, cap, 14);
-		if (rc != SDT_OK) return rc;
-		GCHK(hipMemsetAsync(d_need, 0, nn + 1, v.stream));
-		GCHK(hipMemsetAsync(d_flag, 0, nn + 1, v.stream));
-		LAUNCH_NW(v, k_minor_out_junctions, g, *v.d_idx, v.K, threshold, d_need, d_flag, B.chunks, 0ULL, (unsigned long long *)nullptr, v.d_stats, 14, ap_out(B));
-		GCHK(hipGetLastError());
-		GCHK(hipMemcpyAsync(&h1, B.cursor, 8, hipMemcpyDeviceToHost, v.stream));
-		LAUNCH_NW(v, k_minor_out_candidates, g, *v.d_idx, v.K, d_need, d_flag, B.chunks, 0ULL, (unsigned long long *)nullptr, v.d_stats, 14, ap_out(B));
-		GCHK(hipGetLastError());
-		GCHK(hipMemcpyAsync(&h2, B.cursor, 8, hipMemcpyDeviceToHost, v.stream));
-		rc = sdti::sync_stats(c);
-		if (rc != SDT_OK) return fail(SDT_ESTATE, "sdt_gpu_minor_out_labelled: %llu links point at k-mers that are not nodes", (unsigned long long)v.h_stats->probe_fail);
-		if (h2 <= B.cap_chunks) break;
-		if (attempt) return fail(SDT_ESTATE, "sdt_gpu_minor_out_labelled: the number of records changed between two runs");
-		ap_free(S, B);
-		cap = h2 * AP_CH;
-	}
-	{
-		// (h1, h2 are chunk counts so far: the junctions' chunks come first, packing keeps the chunk order)
-		uint64_t n_rec = 0, n_junc = 0;
-		const int rc = ap_compact(S, v, B, h2, h1, &d_rec, &n_rec, &n_junc);
-		if (rc != SDT_OK) return rc;
-		GCHK(hipStreamSynchronize(v.stream));
-		ap_free(S, B);
-		h1 = n_junc; h2 = n_rec;
-	}
-	// a visit reads and writes its junction, the junction's neighbours and the neighbours of those it may cut: unite every record's
-	// node with its eight neighbours (junction records and the records of the neighbours to cut alike)
-	if (h2) hipLaunchKernelGGL(k_uf_records, dim3(sdti::scan_grid(v.cu_count, h2)), dim3(TPB), 0, v.stream, parent, d_rec, (uint64_t)h2, 14, 1, 9, 1);
-	GCHK(hipGetLastError());
-	const int rc = label_sort_keep(c, v, parent, d_rec, h2, h1, 14);
-	if (rc != SDT_OK) return rc;
-	*n_junctions = h1;
-	*n_records = h2;
-	return SDT_OK;
+	return gx->wide ? sdti::minor_out_labelled(c, ix64_of(gx), threshold, n_junctions, n_records) : sdti::minor_out_labelled(c, Ix32(), threshold, n_junctions, n_records);
 }
 
-// removeMinorOut's commit on the records sdt_gpu_minor_out_labelled left on the device (they stay there: sdt_gpu_fetch_records still
-// works afterwards).  One lane walks a component, at about a microsecond per dependent access (most are first touches of a node:
-// HBM latency); components of more than max_component visits are left alone -- their records wait for sdt_gpu_fetch_skipped, the
-// host's threads are the better place for them.  Two halves, so that the host can work on those while the device walks the rest:
-// _begin finds the components, gathers the records of the long ones and LAUNCHES the visits; _finish waits, re-marks and lists
-// the written nodes.
-static void mo_pending_free(sdti::GraphExt *gx)
-{
-	for (void **q : {(void **)&gx->mo_dirty, (void **)&gx->mo_cnt, (void **)&gx->mo_recidx, (void **)&gx->mo_cstart})
-		if (*q) { (void)hipFree(*q); *q = nullptr; }
-	gx->mo_pending = false;
-}
-
+// removeMinorOut's commit on the records sdt_gpu_minor_out_labelled left on the device (sdt_graph_phases.hpp; _finish below)
 int sdt_gpu_minor_out_commit_begin(sdt_ctx *c, double threshold, uint64_t max_component, uint64_t *largest, uint64_t *n_skipped, uint64_t *n_skipped_records)
 {
 	if (!c || !largest || !n_skipped || !n_skipped_records) return fail(SDT_EINVAL, "NULL argument");
@@ -861,119 +575,14 @@ int sdt_gpu_minor_out_commit_begin(sdt_ctx *c, double threshold, uint64_t max_co
 	sdti::GraphExt *gx = ext_of(v);
 	if (!gx->d_slot_of || !*v.d_idx || *v.idx_slots != v.slots || *v.idx_n != gx->n_nodes) return fail(SDT_ESTATE, "call sdt_gpu_layout_apply first");
 	if (!gx->d_result || gx->result_stride != 14) return fail(SDT_ESTATE, "call sdt_gpu_minor_out_labelled first (its records must still be on the device)");
-	const uint64_t nn = gx->n_nodes, nj = gx->result_labelled, nr = gx->result_words / 14;
-	if (nn >= 0xFFFFFFF0ULL || nr >= 0xFFFFFFF0ULL) return fail(SDT_EINVAL, "commit on the device: 32-bit record and node indices");
+	const uint64_t nn = gx->n_nodes, nr = gx->result_words / 14;
+	if (nr >= 0xFFFFFFF0ULL) return fail(SDT_EINVAL, "commit on the device: 32-bit record indices, %llu records", (unsigned long long)nr);
+	if (!gx->wide && nn >= 0xFFFFFFF0ULL) return fail(SDT_ESTATE, "%llu nodes numbered in the 32-bit form", (unsigned long long)nn);
 	HIPCHK(hipSetDevice(v.device));
-	*largest = *n_skipped = *n_skipped_records = 0;
-	const bool timing = sdt_env("SDT_TIMING") != nullptr;
-	struct timespec ts0_; clock_gettime(CLOCK_MONOTONIC, &ts0_);
-	const double t_call = ts0_.tv_sec * 1e3 + ts0_.tv_nsec * 1e-6;
-	auto tick = [&](const char *what) {              // (SDT_TIMING: where the call's time goes, on stderr; waits for the stream)
-		if (!timing) return;
-		(void)hipStreamSynchronize(v.stream);
-		struct timespec t_;
-		clock_gettime(CLOCK_MONOTONIC, &t_);
-		fprintf(stderr, "[device]       commit: %s at %.1f ms\n", what, t_.tv_sec * 1e3 + t_.tv_nsec * 1e-6 - t_call);
-	};
-	if (gx->mo_pending) { (void)hipStreamSynchronize(v.stream); mo_pending_free(gx); }
-	if (gx->d_wnode) { (void)hipFree(gx->d_wnode); gx->d_wnode = nullptr; }
-	if (gx->d_wl) { (void)hipFree(gx->d_wl); gx->d_wl = nullptr; }
-	if (gx->d_wr) { (void)hipFree(gx->d_wr); gx->d_wr = nullptr; }
-	if (gx->d_skipped) { (void)hipFree(gx->d_skipped); gx->d_skipped = nullptr; }
-	gx->n_written = gx->n_skipped = 0;
-	Scratch S;
-	uint32_t *flag, *rank, *cstart, *recidx;
-	uint8_t *dirty;
-	unsigned long long *d_cnt, h_largest = 0;                    // d_cnt: off, errors, marked, written, largest
-	GCHK(S.alloc(&d_cnt, 5 * 8));
-	GCHK(hipMemsetAsync(d_cnt, 0, 5 * 8, v.stream));
-	GCHK(S.alloc(&recidx, (nn + 1) * 4)); GCHK(S.alloc(&dirty, nn + 1));
-	GCHK(hipMemsetAsync(dirty, 0, nn + 1, v.stream));
-	tick("buffers");
-	if (!nj) {                                                   // nothing to visit: _finish reports zeros
-		GCHK(S.alloc(&cstart, 8));
-		gx->mo_dirty = (uint8_t *)S.release(dirty); gx->mo_cnt = (unsigned long long *)S.release(d_cnt);
-		gx->mo_recidx = (uint32_t *)S.release(recidx); gx->mo_cstart = (uint32_t *)S.release(cstart);
-		gx->mo_pending = true;
-		return SDT_OK;
-	}
-	uint64_t ncomp = 0;
-	{
-	// (the temporaries of this block are let go BEFORE the visits are launched: freeing a block waits for the device, and at the
-	// end of the call that would be a wait for the visits -- the host would start on the long components a quarter of a second late)
-	Scratch T;
-	GCHK(T.alloc(&flag, (nj + 1) * 4)); GCHK(T.alloc(&rank, (nj + 1) * 4));
-	hipLaunchKernelGGL(k_mo_comp_flags, dim3(sdti::scan_grid(v.cu_count, nj + 1)), dim3(TPB), 0, v.stream, gx->d_result, nj, 14, flag);
-	GCHK(hipGetLastError());
-	int rc = exclusive_scan<uint32_t>(v, flag, rank, nj + 1);                   // rank[nj] = number of components
-	if (rc != SDT_OK) return rc;
-	uint32_t ncomp32 = 0;
-	GCHK(hipMemcpyAsync(&ncomp32, rank + nj, 4, hipMemcpyDeviceToHost, v.stream));
-	GCHK(hipStreamSynchronize(v.stream));
-	ncomp = ncomp32;
-	GCHK(S.alloc(&cstart, (ncomp + 1) * 4));
-	hipLaunchKernelGGL(k_mo_comp_starts, dim3(sdti::scan_grid(v.cu_count, nj)), dim3(TPB), 0, v.stream, flag, rank, nj, cstart);
-	GCHK(hipGetLastError());
-	const uint32_t nj32 = (uint32_t)nj;
-	GCHK(hipMemcpyAsync(cstart + ncomp, &nj32, 4, hipMemcpyHostToDevice, v.stream));
-	hipLaunchKernelGGL(k_mo_comp_largest, dim3(sdti::scan_grid(v.cu_count, ncomp)), dim3(TPB), 0, v.stream, cstart, ncomp, d_cnt + 4);
-	GCHK(hipGetLastError());
-	GCHK(hipMemcpyAsync(&h_largest, d_cnt + 4, 8, hipMemcpyDeviceToHost, v.stream));
-	GCHK(hipMemsetAsync(recidx, 0, (nn + 1) * 4, v.stream));
-	hipLaunchKernelGGL(k_mo_recidx, dim3(sdti::scan_grid(v.cu_count, nr)), dim3(TPB), 0, v.stream, gx->d_result, nr, 14, recidx);
-	GCHK(hipGetLastError());
-	GCHK(hipStreamSynchronize(v.stream));
-	*largest = h_largest;
-	tick("components + record index");
-	if (h_largest > max_component) {
-		// the records of the components that are left alone: their junction records in order, then the records of the neighbours
-		// they may cut (the host's commit finds the neighbours of a cut node there instead of looking them up)
-		uint32_t *sel, *pos, *size_of, *sel2, *pos2, nsk = 0, nsk2 = 0;
-		GCHK(T.alloc(&sel, (nj + 1) * 4)); GCHK(T.alloc(&pos, (nj + 1) * 4));
-		hipLaunchKernelGGL(k_mo_skipped_sel, dim3(sdti::scan_grid(v.cu_count, nj + 1)), dim3(TPB), 0, v.stream, flag, rank, cstart, nj, max_component, sel);
-		GCHK(hipGetLastError());
-		rc = exclusive_scan<uint32_t>(v, sel, pos, nj + 1);
-		if (rc != SDT_OK) return rc;
-		GCHK(hipMemcpyAsync(&nsk, pos + nj, 4, hipMemcpyDeviceToHost, v.stream));
-		const uint64_t nc = nr - nj;
-		GCHK(T.alloc(&size_of, (nn + 1) * 4)); GCHK(T.alloc(&sel2, (nc + 1) * 4)); GCHK(T.alloc(&pos2, (nc + 1) * 4));
-		GCHK(hipMemsetAsync(size_of, 0, (nn + 1) * 4, v.stream));
-		hipLaunchKernelGGL(k_mo_label_sizes, dim3(sdti::scan_grid(v.cu_count, ncomp)), dim3(TPB), 0, v.stream, gx->d_result, 14, cstart, ncomp, size_of);
-		GCHK(hipGetLastError());
-		hipLaunchKernelGGL(k_mo_skipped_sel2, dim3(sdti::scan_grid(v.cu_count, nc + 1)), dim3(TPB), 0, v.stream, gx->d_result, 14, nj, nr, size_of, max_component, sel2);
-		GCHK(hipGetLastError());
-		rc = exclusive_scan<uint32_t>(v, sel2, pos2, nc + 1);
-		if (rc != SDT_OK) return rc;
-		GCHK(hipMemcpyAsync(&nsk2, pos2 + nc, 4, hipMemcpyDeviceToHost, v.stream));
-		GCHK(hipStreamSynchronize(v.stream));
-		uint64_t *sk;
-		GCHK(S.alloc(&sk, ((uint64_t)nsk + nsk2 + 1) * 14 * 8));
-		hipLaunchKernelGGL(k_mo_skipped_gather, dim3(sdti::scan_grid(v.cu_count, nj * 14)), dim3(TPB), 0, v.stream, gx->d_result, 14, sel, pos, nj, sk);
-		GCHK(hipGetLastError());
-		if (nc) hipLaunchKernelGGL(k_mo_skipped_gather, dim3(sdti::scan_grid(v.cu_count, nc * 14)), dim3(TPB), 0, v.stream, gx->d_result + nj * 14, 14, sel2, pos2, nc, sk + (uint64_t)nsk * 14);
-		GCHK(hipGetLastError());
-		GCHK(hipStreamSynchronize(v.stream));                // (sdt_gpu_fetch_skipped copies on the other stream)
-		gx->d_skipped = (uint64_t *)S.release(sk);
-		gx->n_skipped = (uint64_t)nsk + nsk2;
-		*n_skipped = nsk;
-		*n_skipped_records = (uint64_t)nsk + nsk2;
-		tick("long components gathered");
-	}
-	}
-	// the visits and the re-marking: launched, not waited for
-	{
-		const uint64_t blocks = (ncomp + TPB - 1) / TPB;
-		const int g = (int)(blocks < (uint64_t)v.cu_count * 32 ? (blocks ? blocks : 1) : (uint64_t)v.cu_count * 32);
-		LAUNCH_NW(v, k_mo_commit, g, gx->d_slot_of, v.K, threshold, gx->d_result, 14, cstart, ncomp, recidx, dirty, d_cnt, max_component);
-		GCHK(hipGetLastError());
-	}
-	LAUNCH_NW(v, k_mo_mark, sdti::scan_grid(v.cu_count, nn), gx->d_slot_of, nn, dirty, d_cnt);
-	GCHK(hipGetLastError());
-	gx->mo_dirty = (uint8_t *)S.release(dirty); gx->mo_cnt = (unsigned long long *)S.release(d_cnt);
-	gx->mo_recidx = (uint32_t *)S.release(recidx); gx->mo_cstart = (uint32_t *)S.release(cstart);
-	gx->mo_pending = true;
-	return SDT_OK;
+	return gx->wide ? sdti::minor_out_commit_begin(c, ix64_of(gx), threshold, max_component, largest, n_skipped, n_skipped_records)
+	                : sdti::minor_out_commit_begin(c, Ix32(), threshold, max_component, largest, n_skipped, n_skipped_records);
 }
+
 
 int sdt_gpu_minor_out_commit_finish(sdt_ctx *c, uint64_t *off, uint64_t *linear, uint64_t *n_written)
 {
@@ -987,7 +596,7 @@ int sdt_gpu_minor_out_commit_finish(sdt_ctx *c, uint64_t *off, uint64_t *linear,
 	unsigned long long h_cnt[5] = {0, 0, 0, 0, 0};
 	GCHK(hipMemcpyAsync(h_cnt, gx->mo_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, v.stream));
 	GCHK(hipStreamSynchronize(v.stream));
-	if (h_cnt[1]) { mo_pending_free(gx); return fail(SDT_ESTATE, "sdt_gpu_minor_out_commit: %llu cuts found no record of the node they cut", h_cnt[1]); }
+	if (h_cnt[1]) { sdti::mo_pending_free(gx); return fail(SDT_ESTATE, "sdt_gpu_minor_out_commit: %llu cuts found no record of the node they cut", h_cnt[1]); }
 	const uint64_t nw = h_cnt[3];
 	Scratch S;
 	unsigned long long *d_cur;
@@ -1000,7 +609,7 @@ int sdt_gpu_minor_out_commit_finish(sdt_ctx *c, uint64_t *off, uint64_t *linear,
 		GCHK(hipGetLastError());
 	}
 	GCHK(hipStreamSynchronize(v.stream));
-	mo_pending_free(gx);
+	sdti::mo_pending_free(gx);
 	gx->d_wnode = (uint64_t *)S.release(wn); gx->d_wl = (uint32_t *)S.release(wl); gx->d_wr = (uint32_t *)S.release(wr);
 	gx->n_written = nw;
 	*off = h_cnt[0];
@@ -1026,6 +635,7 @@ int sdt_gpu_fetch_skipped(sdt_ctx *c, uint64_t *dst, uint64_t n_records)
 	HIPCHK(hipSetDevice(v.device));
 	int rc = SDT_OK;
 	if (n_records) rc = sdti::d2h_big(v.copy_stream, dst, gx->d_skipped, n_records * 14 * 8);
+	if (rc == SDT_OK && gx->base) rebase_records(dst, n_records, 14, gx->base);
 	// (no hipFree here: freeing waits for the device, and the visits of _begin may be running -- _begin / the context let go of it)
 	return rc;
 }
@@ -1049,79 +659,17 @@ int sdt_gpu_fetch_written(sdt_ctx *c, uint64_t *node, uint32_t *l_links, uint32_
 	return rc;
 }
 
-// ---- kmer2edges on the device (node2edge.c:46-561) ----------------------------------------------------------------------
+
+// ---- kmer2edges on the device (node2edge.c:46-561; sdt_graph_phases.hpp) ------------------------------------------------
 int sdt_gpu_build_edges(sdt_ctx *c, uint64_t *n_edges, uint64_t *num_ed, uint64_t *n_bases)
 {
 	if (!c || !n_edges || !num_ed || !n_bases) return fail(SDT_EINVAL, "NULL argument");
 	const GraphView v = sdti::graph_view(c);
 	sdti::GraphExt *gx = ext_of(v);
 	if (!gx->d_slot_of || !*v.d_idx || *v.idx_slots != v.slots || *v.idx_n != gx->n_nodes) return fail(SDT_ESTATE, "call sdt_gpu_layout_apply first");
-	const uint64_t n = gx->n_nodes;
-	if (n >= 0xFFFFFFF0ULL) return fail(SDT_EINVAL, "edge building on the device: 32-bit node indices, %llu nodes", (unsigned long long)n);
+	if (!gx->wide && gx->n_nodes >= 0xFFFFFFF0ULL) return fail(SDT_ESTATE, "%llu nodes numbered in the 32-bit form", (unsigned long long)gx->n_nodes);
 	HIPCHK(hipSetDevice(v.device));
-	if (gx->d_result) { (void)hipFree(gx->d_result); gx->d_result = nullptr; gx->result_words = 0; }
-	if (gx->d_seq) { (void)hipFree(gx->d_seq); gx->d_seq = nullptr; gx->seq_bytes = 0; }
-	if (gx->d_pw) { (void)hipFree(gx->d_pw); gx->d_pw = nullptr; gx->pw_n = 0; }
-	Scratch S;
-	const uint64_t m = n ? n : 1;
-	uint32_t *flag, *srank, *start_node;
-	uint64_t *pw;
-	unsigned int *d_asym;
-	GCHK(S.alloc(&flag, (m + 1) * 4)); GCHK(S.alloc(&srank, (m + 1) * 4)); GCHK(S.alloc(&pw, m * 8)); GCHK(S.alloc(&d_asym, 4));
-	GCHK(hipMemsetAsync(flag, 0, (m + 1) * 4, v.stream));
-	GCHK(hipMemsetAsync(d_asym, 0, 4, v.stream));
-	LAUNCH_NW(v, k_edge_starts, sdti::scan_grid(v.cu_count, m), gx->d_slot_of, n, flag, pw);
-	GCHK(hipGetLastError());
-	int rc = exclusive_scan<uint32_t>(v, flag, srank, n + 1);                  // srank[n] = number of start nodes
-	if (rc != SDT_OK) return rc;
-	uint32_t nstarts = 0;
-	GCHK(hipMemcpy(&nstarts, srank + n, 4, hipMemcpyDeviceToHost));
-	const uint64_t nports = (uint64_t)nstarts * 8;
-	PortRec *ports;
-	uint32_t *w_edge, *w_id, *e_scan, *id_scan;
-	uint64_t *w_len, *len_scan;
-	GCHK(S.alloc(&start_node, ((uint64_t)nstarts + 1) * 4)); GCHK(S.alloc(&ports, (nports + 1) * sizeof(PortRec)));
-	GCHK(S.alloc(&w_edge, (nports + 1) * 4)); GCHK(S.alloc(&w_id, (nports + 1) * 4)); GCHK(S.alloc(&w_len, (nports + 1) * 8));
-	GCHK(S.alloc(&e_scan, (nports + 1) * 4)); GCHK(S.alloc(&id_scan, (nports + 1) * 4)); GCHK(S.alloc(&len_scan, (nports + 1) * 8));
-	GCHK(hipMemsetAsync(w_edge + nports, 0, 4, v.stream)); GCHK(hipMemsetAsync(w_id + nports, 0, 4, v.stream)); GCHK(hipMemsetAsync(w_len + nports, 0, 8, v.stream));
-	hipLaunchKernelGGL(k_edge_start_nodes, dim3(sdti::scan_grid(v.cu_count, m)), dim3(TPB), 0, v.stream, flag, srank, n, start_node);
-	if (nports) LAUNCH_NW(v, k_edge_ports_ordered, sdti::scan_grid(v.cu_count, nports), *v.d_idx, gx->d_slot_of, start_node, nports, v.K, n + 1, ports, v.d_stats);
-	GCHK(hipGetLastError());
-	rc = sdti::sync_stats(c);
-	if (rc != SDT_OK) return fail(SDT_ESTATE, "sdt_gpu_build_edges: %llu chains leave the graph or never end", (unsigned long long)v.h_stats->probe_fail);
-	if (nports) hipLaunchKernelGGL(k_edge_emit, dim3(sdti::scan_grid(v.cu_count, nports)), dim3(TPB), 0, v.stream, ports, start_node, flag, srank, nports, w_edge, w_id, w_len, d_asym);
-	GCHK(hipGetLastError());
-	unsigned int asym = 0;
-	GCHK(hipMemcpyAsync(&asym, d_asym, 4, hipMemcpyDeviceToHost, v.stream));
-	GCHK(hipStreamSynchronize(v.stream));
-	if (asym) return fail(SDT_ESTATE, "sdt_gpu_build_edges: a chain does not lead back to the port it was entered from (build the edges sequentially)");
-	rc = exclusive_scan<uint32_t>(v, w_edge, e_scan, nports + 1);
-	if (rc == SDT_OK) rc = exclusive_scan<uint32_t>(v, w_id, id_scan, nports + 1);
-	if (rc == SDT_OK) rc = exclusive_scan<uint64_t>(v, w_len, len_scan, nports + 1);
-	if (rc != SDT_OK) return rc;
-	uint32_t ne = 0, ids = 0;
-	uint64_t nb = 0;
-	GCHK(hipMemcpy(&ne, e_scan + nports, 4, hipMemcpyDeviceToHost));
-	GCHK(hipMemcpy(&ids, id_scan + nports, 4, hipMemcpyDeviceToHost));
-	GCHK(hipMemcpy(&nb, len_scan + nports, 8, hipMemcpyDeviceToHost));
-	const int RW = 4 + 2 * v.nw;
-	uint64_t *erec;
-	unsigned char *seq;
-	GCHK(S.alloc(&erec, ((uint64_t)ne + 1) * RW * 8)); GCHK(S.alloc(&seq, nb + 16));
-	if (nports) LAUNCH_NW(v, k_edge_stamp, sdti::scan_grid(v.cu_count, nports), *v.d_idx, gx->d_slot_of, v.K, ports, start_node, nports, w_edge, e_scan, id_scan, len_scan, pw, seq, erec, v.d_stats);
-	GCHK(hipGetLastError());
-	rc = sdti::sync_stats(c);
-	if (rc != SDT_OK) return fail(SDT_ESTATE, "sdt_gpu_build_edges: %llu chains changed between the two walks", (unsigned long long)v.h_stats->probe_fail);
-	gx->d_result = (uint64_t *)S.release(erec);
-	gx->result_words = (uint64_t)ne * RW;
-	gx->d_seq = (unsigned char *)S.release(seq);
-	gx->seq_bytes = nb;
-	gx->d_pw = (uint64_t *)S.release(pw);
-	gx->pw_n = n;
-	*n_edges = ne;
-	*num_ed = ids;
-	*n_bases = nb;
-	return SDT_OK;
+	return gx->wide ? sdti::build_edges(c, ix64_of(gx), n_edges, num_ed, n_bases) : sdti::build_edges(c, Ix32(), n_edges, num_ed, n_bases);
 }
 
 int sdt_gpu_fetch_edge_bases(sdt_ctx *c, char *dst, uint64_t nbytes)
@@ -1148,6 +696,7 @@ int sdt_gpu_fetch_records(sdt_ctx *c, uint64_t *dst, uint64_t nwords)
 	HIPCHK(hipSetDevice(v.device));
 	int rc = SDT_OK;
 	if (nwords) rc = sdti::d2h_big(v.copy_stream, dst, gx->d_result, nwords * 8);
+	if (rc == SDT_OK && gx->result_nodes && gx->base) rebase_records(dst, nwords / gx->result_stride, gx->result_stride, gx->base);
 	if (gx->d_result) (void)hipFree(gx->d_result);
 	gx->d_result = nullptr;
 	gx->result_words = 0;
@@ -1177,15 +726,14 @@ int sdt_gpu_set_node_index(sdt_ctx *c, const uint64_t *keys, uint64_t n)
 	(*v.idx_slots) = (*v.idx_n) = 0;
 	HIPCHK(hipMalloc((void **)&(*v.d_idx), v.slots * sizeof(uint64_t)));
 	HIPCHK(hipMemsetAsync((*v.d_idx), 0xFF, v.slots * sizeof(uint64_t), v.stream));
-	uint64_t *d_k = nullptr;
-	int rc = upload_keys(c, keys, n, &d_k);
+	sdti::GraphExt *gx = ext_of(v);
+	int rc = graph_choose_form(gx, n);
 	if (rc != SDT_OK) return rc;
-	const int g = sdti::scan_grid(v.cu_count, n ? n : 1);
-	if (v.nw == 1) hipLaunchKernelGGL(k_set_index<1>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<1>(v), d_k, n, (*v.d_idx), v.d_stats);
-	else if (v.nw == 2) hipLaunchKernelGGL(k_set_index<2>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<2>(v), d_k, n, (*v.d_idx), v.d_stats);
-	else hipLaunchKernelGGL(k_set_index<4>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<4>(v), d_k, n, (*v.d_idx), v.d_stats);
-	hipError_t le = hipGetLastError();
-	rc = le == hipSuccess ? sdti::sync_stats(c) : fail(SDT_EHIP, "k_set_index: %s", hipGetErrorString(le));
+	uint64_t *d_k = nullptr;
+	rc = upload_keys(c, keys, n, &d_k);
+	if (rc != SDT_OK) return rc;
+	rc = gx->wide ? sdti::set_index(v, ix64_of(gx), d_k, n) : sdti::set_index(v, Ix32(), d_k, n);
+	if (rc == SDT_OK) rc = sdti::sync_stats(c);
 	(void)hipFree(d_k);
 	if (rc != SDT_OK)
 		return fail(SDT_ESTATE, "sdt_gpu_set_node_index: %llu nodes are not in the table", (unsigned long long)v.h_stats->probe_fail);
@@ -1231,6 +779,7 @@ int sdt_gpu_tip_walks(sdt_ctx *c, int thin, int cut_len, uint64_t *end_idx, uint
 {
 	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
 	const GraphView v = sdti::graph_view(c);
+	if (ext_of(v)->base) return fail(SDT_ESTATE, "%s reads host positions straight from the node index: no node base (SDT_NODE_BASE)", "sdt_gpu_tip_walks");
 	if (!c || !end_idx || !info)
 		return fail(SDT_EINVAL, "NULL argument");
 	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
@@ -1265,6 +814,7 @@ int sdt_gpu_minor_out_dry(sdt_ctx *c, double threshold, uint64_t *records, uint6
 {
 	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
 	const GraphView v = sdti::graph_view(c);
+	if (ext_of(v)->base) return fail(SDT_ESTATE, "%s reads host positions straight from the node index: no node base (SDT_NODE_BASE)", "sdt_gpu_minor_out_dry");
 	if (!c || (!records && max_records) || !n_junctions || !n_records)
 		return fail(SDT_EINVAL, "NULL argument");
 	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
@@ -1318,6 +868,29 @@ done:
 	return ret;
 }
 
+}  // extern "C"
+
+// the host's look-up index with entries E (32- or 64-bit), built on the device in the form of the numbering and copied to `index`
+template <class E>
+static int host_index_entries(sdt_ctx *c, const GraphView &v, E *index, uint64_t index_slots)
+{
+	(void)c;
+	sdti::GraphExt *gx = ext_of(v);
+	E *d_index = nullptr;
+	HIPCHK(hipMalloc((void **)&d_index, index_slots * sizeof(E)));
+	hipError_t e = hipMemsetAsync(d_index, 0, index_slots * sizeof(E), v.stream);
+	int rc = SDT_OK;
+	if (e == hipSuccess) rc = gx->wide ? sdti::host_index(v, ix64_of(gx), d_index, index_slots - 1) : sdti::host_index(v, Ix32(), d_index, index_slots - 1);
+	if (e == hipSuccess && rc == SDT_OK) e = hipStreamSynchronize(v.stream);
+	if (e == hipSuccess && rc == SDT_OK) rc = sdti::d2h_big(v.copy_stream, index, d_index, index_slots * sizeof(E));      // (pageable destination of gigabytes: staged copies)
+	(void)hipFree(d_index);
+	if (e != hipSuccess)
+		return fail(SDT_EHIP, "building the host index: %s", hipGetErrorString(e));
+	return rc;
+}
+
+extern "C" {
+
 int sdt_gpu_build_host_index(sdt_ctx *c, uint32_t *index, uint64_t index_slots)
 {
 	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
@@ -1331,29 +904,43 @@ int sdt_gpu_build_host_index(sdt_ctx *c, uint32_t *index, uint64_t index_slots)
 	if ((*v.idx_n) >= 0xFFFFFFFEULL)
 		return fail(SDT_EINVAL, "%llu nodes do not fit 32-bit index entries", (unsigned long long)(*v.idx_n));
 	HIPCHK(hipSetDevice(v.device));
-	unsigned int *d_index = nullptr;
-	HIPCHK(hipMalloc((void **)&d_index, index_slots * sizeof(unsigned int)));
-	hipError_t e = hipMemsetAsync(d_index, 0, index_slots * sizeof(unsigned int), v.stream);
-	if (e == hipSuccess) {
-		const int g = sdti::scan_grid(v.cu_count, v.slots);
-		if (v.nw == 1) hipLaunchKernelGGL(k_build_host_index<1>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<1>(v), (*v.d_idx), d_index, index_slots - 1);
-		else if (v.nw == 2) hipLaunchKernelGGL(k_build_host_index<2>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<2>(v), (*v.d_idx), d_index, index_slots - 1);
-		else hipLaunchKernelGGL(k_build_host_index<4>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<4>(v), (*v.d_idx), d_index, index_slots - 1);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
-	int rc = SDT_OK;
-	if (e == hipSuccess) rc = sdti::d2h_big(v.copy_stream, index, d_index, index_slots * sizeof(unsigned int));      // (pageable destination of gigabytes: staged copies)
-	(void)hipFree(d_index);
-	if (e != hipSuccess)
-		return fail(SDT_EHIP, "sdt_gpu_build_host_index: %s", hipGetErrorString(e));
-	return rc;
+	return host_index_entries<unsigned int>(c, v, index, index_slots);
+}
+
+int sdt_gpu_build_host_index64(sdt_ctx *c, uint64_t *index, uint64_t index_slots)
+{
+	if (!c || !index) return fail(SDT_EINVAL, "NULL argument");
+	const GraphView v = sdti::graph_view(c);
+	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
+		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
+	if (index_slots < 2 * (*v.idx_n) || (index_slots & (index_slots - 1)))
+		return fail(SDT_EINVAL, "index_slots must be a power of two >= 2 x nodes");
+	HIPCHK(hipSetDevice(v.device));
+	return host_index_entries<unsigned long long>(c, v, (unsigned long long *)index, index_slots);
+}
+
+int sdt_gpu_set_graph_index_bits(sdt_ctx *c, int bits)
+{
+	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
+	if (bits != 0 && bits != 64) return fail(SDT_EINVAL, "graph index bits: 0 (by node count) or 64, asked for %d", bits);
+	ext_of(sdti::graph_view(c))->want_bits = bits;
+	return SDT_OK;
+}
+
+int sdt_gpu_graph_index_bits(const sdt_ctx *c)
+{
+	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
+	const GraphView v = sdti::graph_view((sdt_ctx *)c);
+	const sdti::GraphExt *gx = ext_of(v);
+	if (*v.d_idx) return gx->wide ? 64 : 32;                  // (numbered: the form of that numbering; before: the one asked for)
+	return gx->want_bits == 64 ? 64 : 32;
 }
 
 int sdt_gpu_edge_ports(sdt_ctx *c, uint64_t *records, uint64_t max_records, uint64_t *n_records)
 {
 	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
 	const GraphView v = sdti::graph_view(c);
+	if (ext_of(v)->base) return fail(SDT_ESTATE, "%s reads host positions straight from the node index: no node base (SDT_NODE_BASE)", "sdt_gpu_edge_ports");
 	if (!c || (!records && max_records) || !n_records)
 		return fail(SDT_EINVAL, "NULL argument");
 	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
@@ -1390,6 +977,7 @@ int sdt_gpu_tip_walks_compact(sdt_ctx *c, int thin, int cut_len, uint64_t *recor
 {
 	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
 	const GraphView v = sdti::graph_view(c);
+	if (ext_of(v)->base) return fail(SDT_ESTATE, "%s reads host positions straight from the node index: no node base (SDT_NODE_BASE)", "sdt_gpu_tip_walks_compact");
 	if (!c || (!records && max_records) || !n_records)
 		return fail(SDT_EINVAL, "NULL argument");
 	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)

@@ -4,6 +4,26 @@
 #pragma once
 
 // ---------------------------------------------------------------------------------------------------------------
+// Node-index forms of the graph phases (the parameter IX of the kernels and host functions that hold node indices):
+//   Ix32  every graph below 2^32 - 16 nodes: 32-bit parent[] / labels / ranks / start nodes, no base
+//   Ix64  past that (or on request, sdt_gpu_set_graph_index_bits): 64-bit ones; under the test hook SDT_NODE_BASE the node
+//         numbered at position i is stored as base + i everywhere on the device, so that a truncation to 32 bits shows
+// Per-node arrays are addressed by ix.pos(node) = node - base.  Counts of records, components, edges and arcs stay 32-bit.
+// (the non-template kernels of this header are static: sdt_gpu_graph.hip and sdt_gpu_graph64.hip both include it)
+// ---------------------------------------------------------------------------------------------------------------
+struct Ix32 {
+	using T = uint32_t;
+	__host__ __device__ static constexpr uint64_t base() { return 0; }
+	__host__ __device__ static constexpr uint64_t pos(uint64_t node) { return node; }
+};
+struct Ix64 {
+	using T = unsigned long long;
+	uint64_t b;
+	__host__ __device__ uint64_t base() const { return b; }
+	__host__ __device__ uint64_t pos(uint64_t node) const { return node - b; }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // Graph-cleaning dry runs on the device (cutTipPreGraph.c).  The host owns the ORDER (layout replay, ordered commit
 // of the few visits that write); what it needs from a sweep is the read-only part -- the walks -- and those are
 // table look-ups, which this chip does at tens of G/s.  The device table mirrors the host graph: the host sends
@@ -15,9 +35,9 @@ template <int NW> __device__ inline bool find_slot(const Table<NW> &tbl, const K
 	return table_find<NW>(tbl, k, slot_out);         // (either layout of the node table: sdt_table.cuh)
 }
 
-template <int NW>
-__global__ __launch_bounds__(TPB) void k_set_index(Table<NW> tbl, const uint64_t *__restrict__ keys, uint64_t n,
-                                                   uint64_t *__restrict__ idx, Stats *stats)
+template <int NW, class IX = Ix32>
+static __global__ __launch_bounds__(TPB) void k_set_index(Table<NW> tbl, const uint64_t *__restrict__ keys, uint64_t n,
+                                                   uint64_t *__restrict__ idx, Stats *stats, IX ix = IX())
 {
 	uint32_t failed = 0;
 	for (uint64_t i = blockIdx.x * (uint64_t)TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TPB) {
@@ -26,7 +46,7 @@ __global__ __launch_bounds__(TPB) void k_set_index(Table<NW> tbl, const uint64_t
 		for (int w = 0; w < NW; w++)
 			k.w[w] = keys[i * NW + w];
 		uint64_t slot;
-		if (find_slot<NW>(tbl, k, slot)) idx[slot] = i;
+		if (find_slot<NW>(tbl, k, slot)) idx[slot] = ix.base() + i;
 		else failed++;
 	}
 	if (failed)
@@ -35,7 +55,7 @@ __global__ __launch_bounds__(TPB) void k_set_index(Table<NW> tbl, const uint64_t
 
 // links + flags of the given nodes as the host has them now (count is never changed by the cleaning passes)
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_update_nodes(Table<NW> tbl, const uint64_t *__restrict__ keys,
+static __global__ __launch_bounds__(TPB) void k_update_nodes(Table<NW> tbl, const uint64_t *__restrict__ keys,
                                                       const uint32_t *__restrict__ l_links, const uint32_t *__restrict__ r_flags,
                                                       uint64_t n, Stats *stats)
 {
@@ -151,7 +171,7 @@ template <int NW> __device__ inline Key<NW> key_mask_of(int K)
 }
 
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_tip_walks(Table<NW> tbl, const uint64_t *__restrict__ idx, int K, int thin, int cut_len,
+static __global__ __launch_bounds__(TPB) void k_tip_walks(Table<NW> tbl, const uint64_t *__restrict__ idx, int K, int thin, int cut_len,
                                                    uint64_t *__restrict__ end_out, uint8_t *__restrict__ info_out, Stats *stats,
                                                    uint64_t *__restrict__ rec = nullptr, unsigned long long max_rec = 0,
                                                    unsigned long long *cursor = nullptr, int rec_stride = 2)
@@ -190,7 +210,7 @@ __global__ __launch_bounds__(TPB) void k_tip_walks(Table<NW> tbl, const uint64_t
 // at 678 M nodes).  k_tip_starts lists the dead ends (their slots, in chunks: sdt_append.cuh), k_tip_walks_list gives every lane of a
 // wave a walk of its own.
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_tip_starts(Table<NW> tbl, int thin, unsigned long long *__restrict__ list, ApOut ap)
+static __global__ __launch_bounds__(TPB) void k_tip_starts(Table<NW> tbl, int thin, unsigned long long *__restrict__ list, ApOut ap)
 {
 	__shared__ WaveApp s_app[TPB / 64];
 	ap_init(s_app);
@@ -210,7 +230,7 @@ __global__ __launch_bounds__(TPB) void k_tip_starts(Table<NW> tbl, int thin, uns
 }
 
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_tip_walks_list(Table<NW> tbl, const uint64_t *__restrict__ idx, int K, int thin, int cut_len,
+static __global__ __launch_bounds__(TPB) void k_tip_walks_list(Table<NW> tbl, const uint64_t *__restrict__ idx, int K, int thin, int cut_len,
                                                         const unsigned long long *__restrict__ list, unsigned long long n_list, Stats *stats,
                                                         uint64_t *__restrict__ rec, int rec_stride, ApOut ap)
 {
@@ -281,11 +301,11 @@ __device__ inline void neighbours_of(const Table<NW> &tbl, const uint64_t *__res
 		}
 }
 
-template <int NW>
-__global__ __launch_bounds__(TPB) void k_minor_out_junctions(Table<NW> tbl, const uint64_t *__restrict__ idx, int K, double threshold,
+template <int NW, class IX = Ix32>
+static __global__ __launch_bounds__(TPB) void k_minor_out_junctions(Table<NW> tbl, const uint64_t *__restrict__ idx, int K, double threshold,
                                                              uint8_t *__restrict__ need, uint8_t *__restrict__ flagged,
                                                              uint64_t *__restrict__ rec, unsigned long long max_rec, unsigned long long *cursor,
-                                                             Stats *stats, int rec_stride = 9, ApOut ap = ApOut{nullptr, 0, nullptr, nullptr})
+                                                             Stats *stats, int rec_stride = 9, ApOut ap = ApOut{nullptr, 0, nullptr, nullptr}, IX ix = IX())
 {
 	__shared__ WaveApp s_app[TPB / 64];
 	ap_init(s_app);
@@ -319,14 +339,14 @@ __global__ __launch_bounds__(TPB) void k_minor_out_junctions(Table<NW> tbl, cons
 			for (int b = 0; b < 4; b++) {
 				const int c = (int)cnt[side * 4 + b];
 				if (nb[side * 4 + b] != ~0ULL && c && (double)c / best < threshold) {
-					need[nb[side * 4 + b] >> 1] = 1;
+					need[ix.pos(nb[side * 4 + b] >> 1)] = 1;
 					any = true;
 				}
 			}
 		}
 		if (!any) continue;
 		const uint64_t me = idx[s];
-		flagged[me] = 1;
+		flagged[ix.pos(me)] = 1;
 		unsigned long long r;
 		if (ap.cursor) r = ap_append(s_app, ap);
 		else { r = atomicAdd(cursor, 1ULL); if (r >= max_rec) r = AP_NONE; }
@@ -345,11 +365,11 @@ __global__ __launch_bounds__(TPB) void k_minor_out_junctions(Table<NW> tbl, cons
 }
 
 // neighbours of the flagged neighbours (isolate() walks them), unless the node already has a junction record
-template <int NW>
-__global__ __launch_bounds__(TPB) void k_minor_out_candidates(Table<NW> tbl, const uint64_t *__restrict__ idx, int K,
+template <int NW, class IX = Ix32>
+static __global__ __launch_bounds__(TPB) void k_minor_out_candidates(Table<NW> tbl, const uint64_t *__restrict__ idx, int K,
                                                               const uint8_t *__restrict__ need, const uint8_t *__restrict__ flagged,
                                                               uint64_t *__restrict__ rec, unsigned long long max_rec, unsigned long long *cursor,
-                                                              Stats *stats, int rec_stride = 9, ApOut ap = ApOut{nullptr, 0, nullptr, nullptr})
+                                                              Stats *stats, int rec_stride = 9, ApOut ap = ApOut{nullptr, 0, nullptr, nullptr}, IX ix = IX())
 {
 	__shared__ WaveApp s_app[TPB / 64];
 	ap_init(s_app);
@@ -365,7 +385,7 @@ __global__ __launch_bounds__(TPB) void k_minor_out_candidates(Table<NW> tbl, con
 		const Entry<NW> e = tbl.ent[s];
 		if (e.key[0] == KEY_EMPTY) continue;
 		const uint64_t me = idx[s];
-		if (!need[me] || flagged[me]) continue;
+		if (!need[ix.pos(me)] || flagged[ix.pos(me)]) continue;
 		uint64_t nb[8];
 		uint32_t cnt[8];
 		neighbours_of<NW>(tbl, idx, e, K, mask, nb, cnt, missing);
@@ -388,7 +408,8 @@ __global__ __launch_bounds__(TPB) void k_minor_out_candidates(Table<NW> tbl, con
 
 
 // the host's own look-up index over its node array (csrc/host/graph/graph.c: open addressing on mix_key of the
-// 4-word k-mer, 32-bit value = node index + 1), built here because the device already knows every node's index
+// 4-word k-mer, value = node index + 1 in 32-bit entries E, or 64-bit ones past 2^32 nodes), built here because the device
+// already knows every node's index
 __device__ inline uint64_t host_mix_key4(const uint64_t w[4])
 {
 	uint64_t h = 0x9E3779B97F4A7C15ULL;
@@ -400,9 +421,9 @@ __device__ inline uint64_t host_mix_key4(const uint64_t w[4])
 	return h;
 }
 
-template <int NW>
-__global__ __launch_bounds__(TPB) void k_build_host_index(Table<NW> tbl, const uint64_t *__restrict__ idx, unsigned int *__restrict__ index,
-                                                          uint64_t index_mask)
+template <int NW, class IX = Ix32, class E = unsigned int>
+static __global__ __launch_bounds__(TPB) void k_build_host_index(Table<NW> tbl, const uint64_t *__restrict__ idx, E *__restrict__ index,
+                                                          uint64_t index_mask, IX ix = IX())
 {
 	const uint64_t slots = tbl.slots();
 	for (uint64_t s = blockIdx.x * (uint64_t)TPB + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * TPB) {
@@ -411,8 +432,8 @@ __global__ __launch_bounds__(TPB) void k_build_host_index(Table<NW> tbl, const u
 #pragma unroll
 		for (int i = 0; i < NW; i++) w[4 - NW + i] = tbl.ent[s].key[i];
 		uint64_t h = host_mix_key4(w) & index_mask;
-		const unsigned int v = (unsigned int)(idx[s] + 1);
-		while (atomicCAS(&index[h], 0u, v) != 0u) h = (h + 1) & index_mask;
+		const E v = (E)(ix.pos(idx[s]) + 1);
+		while (atomicCAS(&index[h], (E)0, v) != (E)0) h = (h + 1) & index_mask;
 	}
 }
 
@@ -428,7 +449,7 @@ __global__ __launch_bounds__(TPB) void k_build_host_index(Table<NW> tbl, const u
 // Record = 17 words: node index, then per port (far node index or ~0, length | far_port << 32 | bal_edge << 40).
 // ---------------------------------------------------------------------------------------------------------------
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_edge_ports(Table<NW> tbl, const uint64_t *__restrict__ idx, int K, uint64_t max_steps,
+static __global__ __launch_bounds__(TPB) void k_edge_ports(Table<NW> tbl, const uint64_t *__restrict__ idx, int K, uint64_t max_steps,
                                                     uint64_t *__restrict__ rec, unsigned long long max_rec, unsigned long long *cursor, Stats *stats)
 {
 	const uint64_t slots = tbl.slots();
@@ -515,7 +536,7 @@ __device__ inline void crc_table_to_lds(int32_t *s_crc)
 
 // sort key = set << 56 | first-occurrence ordinal (< 2^56), value = table slot
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_layout_keys(Table<NW> tbl, uint32_t p, int nw_variant, uint64_t *__restrict__ skey,
+static __global__ __launch_bounds__(TPB) void k_layout_keys(Table<NW> tbl, uint32_t p, int nw_variant, uint64_t *__restrict__ skey,
                                                      uint64_t *__restrict__ sval, unsigned long long max_nodes, unsigned long long *cursor, Stats *stats)
 {
 	__shared__ int32_t s_crc[256];
@@ -561,7 +582,7 @@ __global__ __launch_bounds__(TPB) void k_layout_keys(Table<NW> tbl, uint32_t p, 
 }
 
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_layout_gather_keys(Table<NW> tbl, const uint64_t *__restrict__ sval, uint64_t n, uint64_t *__restrict__ keys)
+static __global__ __launch_bounds__(TPB) void k_layout_gather_keys(Table<NW> tbl, const uint64_t *__restrict__ sval, uint64_t n, uint64_t *__restrict__ keys)
 {
 	for (uint64_t i = blockIdx.x * (uint64_t)TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TPB) {
 		const Entry<NW> *e = tbl.ent + sval[i];
@@ -571,7 +592,7 @@ __global__ __launch_bounds__(TPB) void k_layout_gather_keys(Table<NW> tbl, const
 }
 
 // set_start[s] = first rank whose set is >= s (s = 0..p)
-__global__ void k_layout_set_starts(const uint64_t *__restrict__ skey, uint64_t n, uint32_t p, uint64_t *__restrict__ set_start)
+static __global__ void k_layout_set_starts(const uint64_t *__restrict__ skey, uint64_t n, uint32_t p, uint64_t *__restrict__ set_start)
 {
 	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
 	if (s > p) return;
@@ -584,15 +605,16 @@ __global__ void k_layout_set_starts(const uint64_t *__restrict__ skey, uint64_t 
 }
 
 // order[v] = rank of the node at visiting position v: number the nodes, remember their slots
-__global__ __launch_bounds__(TPB) void k_layout_apply(const uint64_t *__restrict__ sval, const uint64_t *__restrict__ order, uint64_t n,
-                                                      uint64_t *__restrict__ idx, uint64_t *__restrict__ slot_of, Stats *stats)
+template <class IX>
+static __global__ __launch_bounds__(TPB) void k_layout_apply(const uint64_t *__restrict__ sval, const uint64_t *__restrict__ order, uint64_t n,
+                                                      uint64_t *__restrict__ idx, uint64_t *__restrict__ slot_of, Stats *stats, IX ix)
 {
 	uint32_t bad = 0;
 	for (uint64_t v = blockIdx.x * (uint64_t)TPB + threadIdx.x; v < n; v += (uint64_t)gridDim.x * TPB) {
 		const uint64_t r = order[v];
 		if (r >= n) { bad++; continue; }
 		const uint64_t s = sval[r];
-		idx[s] = v;
+		idx[s] = ix.base() + v;
 		slot_of[v] = s;
 	}
 	if (bad) atomicAdd(&stats->probe_fail, (unsigned long long)bad);
@@ -600,7 +622,7 @@ __global__ __launch_bounds__(TPB) void k_layout_apply(const uint64_t *__restrict
 
 // the nodes in visiting order, kmer_t-shaped (as k_export)
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_export_ordered(Table<NW> tbl, const uint64_t *__restrict__ slot_of, uint64_t v0, uint64_t n,
+static __global__ __launch_bounds__(TPB) void k_export_ordered(Table<NW> tbl, const uint64_t *__restrict__ slot_of, uint64_t v0, uint64_t n,
                                                         uint64_t *__restrict__ keys, uint32_t *__restrict__ l_links,
                                                         uint32_t *__restrict__ r_flags, uint32_t *__restrict__ count)
 {
@@ -623,7 +645,7 @@ __global__ __launch_bounds__(TPB) void k_export_ordered(Table<NW> tbl, const uin
 
 // links + flags of the nodes the host wrote, addressed by node index (no keys cross the link, no look-ups)
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_update_by_index(Table<NW> tbl, const uint64_t *__restrict__ slot_of, uint64_t n_nodes,
+static __global__ __launch_bounds__(TPB) void k_update_by_index(Table<NW> tbl, const uint64_t *__restrict__ slot_of, uint64_t n_nodes,
                                                          const uint64_t *__restrict__ node, const uint32_t *__restrict__ l_links,
                                                          const uint32_t *__restrict__ r_flags, uint64_t n, Stats *stats)
 {
@@ -647,7 +669,7 @@ __global__ __launch_bounds__(TPB) void k_update_by_index(Table<NW> tbl, const ui
 // may cut.  A visit reads and writes only nodes of its own component, so components commute; inside one the visits run in
 // record order = the reference's visiting order.  One lane per component.
 // ===============================================================================================================
-__global__ __launch_bounds__(TPB) void k_mo_comp_flags(const uint64_t *__restrict__ rec, uint64_t nj, int stride, uint32_t *__restrict__ flag)
+static __global__ __launch_bounds__(TPB) void k_mo_comp_flags(const uint64_t *__restrict__ rec, uint64_t nj, int stride, uint32_t *__restrict__ flag)
 {
 	for (uint64_t r = blockIdx.x * (uint64_t)TPB + threadIdx.x; r <= nj; r += (uint64_t)gridDim.x * TPB)
 		flag[r] = r < nj && (r == 0 || rec[r * stride + stride - 1] != rec[(r - 1) * stride + stride - 1]);
@@ -655,14 +677,14 @@ __global__ __launch_bounds__(TPB) void k_mo_comp_flags(const uint64_t *__restric
 
 // cstart[c] = first record of component c (rank = exclusive scan of the flags; cstart[ncomp] = nj is written by the host side);
 // largest[0] = the largest component
-__global__ __launch_bounds__(TPB) void k_mo_comp_starts(const uint32_t *__restrict__ flag, const uint32_t *__restrict__ rank, uint64_t nj,
+static __global__ __launch_bounds__(TPB) void k_mo_comp_starts(const uint32_t *__restrict__ flag, const uint32_t *__restrict__ rank, uint64_t nj,
                                                         uint32_t *__restrict__ cstart)
 {
 	for (uint64_t r = blockIdx.x * (uint64_t)TPB + threadIdx.x; r < nj; r += (uint64_t)gridDim.x * TPB)
 		if (flag[r]) cstart[rank[r]] = (uint32_t)r;
 }
 
-__global__ __launch_bounds__(TPB) void k_mo_comp_largest(const uint32_t *__restrict__ cstart, uint64_t ncomp, unsigned long long *largest)
+static __global__ __launch_bounds__(TPB) void k_mo_comp_largest(const uint32_t *__restrict__ cstart, uint64_t ncomp, unsigned long long *largest)
 {
 	unsigned long long m = 0;
 	for (uint64_t c = blockIdx.x * (uint64_t)TPB + threadIdx.x; c < ncomp; c += (uint64_t)gridDim.x * TPB) {
@@ -673,10 +695,11 @@ __global__ __launch_bounds__(TPB) void k_mo_comp_largest(const uint32_t *__restr
 }
 
 // recidx[node] = 1 + the record that lists the node's neighbours (junction records and the records of the neighbours to cut)
-__global__ __launch_bounds__(TPB) void k_mo_recidx(const uint64_t *__restrict__ rec, uint64_t nr, int stride, uint32_t *__restrict__ recidx)
+template <class IX>
+static __global__ __launch_bounds__(TPB) void k_mo_recidx(const uint64_t *__restrict__ rec, uint64_t nr, int stride, uint32_t *__restrict__ recidx, IX ix)
 {
 	for (uint64_t r = blockIdx.x * (uint64_t)TPB + threadIdx.x; r < nr; r += (uint64_t)gridDim.x * TPB)
-		recidx[rec[r * stride]] = (uint32_t)r + 1u;
+		recidx[ix.pos(rec[r * stride])] = (uint32_t)r + 1u;
 }
 
 // a lane re-reads what it (and only it, during this kernel) wrote: real loads and stores every time, but no cache-bypassing scope --
@@ -692,10 +715,11 @@ template <int NW> __device__ inline uint32_t mo_first_base(const Entry<NW> *e, i
 }
 
 // isolate(q) (cuttip.c): q is deleted, every neighbour forgets its link to q and has its `linear` re-derived
-template <int NW>
+template <int NW, class IX>
 __device__ inline void mo_isolate(const Table<NW> &tbl, const uint64_t *__restrict__ slot_of, int K, const uint64_t *__restrict__ rec, int stride,
-                                  const uint32_t *__restrict__ recidx, uint8_t *__restrict__ dirty, uint64_t q, uint32_t &errors)
+                                  const uint32_t *__restrict__ recidx, uint8_t *__restrict__ dirty, uint64_t q, uint32_t &errors, IX ix)
 {
+	q = ix.pos(q);                                   // (from here on a position: q and x address the per-node arrays only)
 	const uint64_t sq = slot_of[q];
 	Entry<NW> *eq = tbl.ent + sq;
 	const uint32_t ch_last = (uint32_t)eq->key[NW - 1] & 3u, ch_first = mo_first_base<NW>(eq, K);
@@ -713,7 +737,7 @@ __device__ inline void mo_isolate(const Table<NW> &tbl, const uint64_t *__restri
 			if (!(((side == 0 ? vq : vq >> 24) >> (6 * b)) & 63u)) continue;
 			const uint64_t nb = Q[1 + side * 4 + b];
 			if (nb == ~0ULL) { errors++; continue; }
-			const uint64_t x = nb >> 1, sx = slot_of[x];
+			const uint64_t x = ix.pos(nb >> 1), sx = slot_of[x];
 			const bool sm = (nb & 1u) != 0;
 			// unlink_next(x, last base of q, sm) for q's left neighbours, unlink_prev(y, first base of q, sm) for its right ones
 			int drop;                                    // field of val to clear: 0..3 left links, 4..7 right links
@@ -729,11 +753,11 @@ __device__ inline void mo_isolate(const Table<NW> &tbl, const uint64_t *__restri
 		}
 }
 
-template <int NW>
-__global__ __launch_bounds__(TPB) void k_mo_commit(Table<NW> tbl, const uint64_t *__restrict__ slot_of, int K, double threshold,
+template <int NW, class IX>
+static __global__ __launch_bounds__(TPB) void k_mo_commit(Table<NW> tbl, const uint64_t *__restrict__ slot_of, int K, double threshold,
                                                    const uint64_t *__restrict__ rec, int stride, const uint32_t *__restrict__ cstart, uint64_t ncomp,
                                                    const uint32_t *__restrict__ recidx, uint8_t *__restrict__ dirty, unsigned long long *counters,
-                                                   uint64_t max_component)
+                                                   uint64_t max_component, IX ix)
 {
 	unsigned long long off = 0;
 	uint32_t errors = 0;
@@ -743,7 +767,7 @@ __global__ __launch_bounds__(TPB) void k_mo_commit(Table<NW> tbl, const uint64_t
 #pragma unroll 1
 		for (uint32_t r = cstart[c]; r < r1; r++) {
 			const uint64_t *R = rec + (uint64_t)r * stride;
-			const uint64_t sn = slot_of[R[0]];
+			const uint64_t sn = slot_of[ix.pos(R[0])];
 			const uint64_t *pv = &tbl.ent[sn].val;
 			if (mo_ld(&tbl.aux[sn]) & (AUX_LINEAR | AUX_DELETED)) continue;
 			const uint64_t v0 = mo_ld(pv);
@@ -771,7 +795,7 @@ __global__ __launch_bounds__(TPB) void k_mo_commit(Table<NW> tbl, const uint64_t
 						off++;
 						const uint64_t nb = R[1 + side * 4 + b];
 						if (nb == ~0ULL) { errors++; continue; }
-						mo_isolate<NW>(tbl, slot_of, K, rec, stride, recidx, dirty, nb >> 1, errors);
+						mo_isolate<NW, IX>(tbl, slot_of, K, rec, stride, recidx, dirty, nb >> 1, errors, ix);
 					}
 				}
 			}
@@ -783,7 +807,7 @@ __global__ __launch_bounds__(TPB) void k_mo_commit(Table<NW> tbl, const uint64_t
 
 // the junction records of the components k_mo_commit left alone, in order: sel[r] = 1 for them (rank = exclusive scan of the start
 // flags: the component of record r is rank[r] + flag[r] - 1), then gathered to the positions an exclusive scan of sel gives
-__global__ __launch_bounds__(TPB) void k_mo_skipped_sel(const uint32_t *__restrict__ flag, const uint32_t *__restrict__ rank, const uint32_t *__restrict__ cstart,
+static __global__ __launch_bounds__(TPB) void k_mo_skipped_sel(const uint32_t *__restrict__ flag, const uint32_t *__restrict__ rank, const uint32_t *__restrict__ cstart,
                                                         uint64_t nj, uint64_t max_component, uint32_t *__restrict__ sel)
 {
 	for (uint64_t r = blockIdx.x * (uint64_t)TPB + threadIdx.x; r <= nj; r += (uint64_t)gridDim.x * TPB) {
@@ -796,7 +820,7 @@ __global__ __launch_bounds__(TPB) void k_mo_skipped_sel(const uint32_t *__restri
 	}
 }
 
-__global__ __launch_bounds__(TPB) void k_mo_skipped_gather(const uint64_t *__restrict__ rec, int stride, const uint32_t *__restrict__ sel,
+static __global__ __launch_bounds__(TPB) void k_mo_skipped_gather(const uint64_t *__restrict__ rec, int stride, const uint32_t *__restrict__ sel,
                                                            const uint32_t *__restrict__ pos, uint64_t nj, uint64_t *__restrict__ out)
 {
 	for (uint64_t w = blockIdx.x * (uint64_t)TPB + threadIdx.x; w < nj * (uint64_t)stride; w += (uint64_t)gridDim.x * TPB) {
@@ -806,24 +830,26 @@ __global__ __launch_bounds__(TPB) void k_mo_skipped_gather(const uint64_t *__res
 }
 
 // size_of[label] = visits of the component with that label
-__global__ __launch_bounds__(TPB) void k_mo_label_sizes(const uint64_t *__restrict__ rec, int stride, const uint32_t *__restrict__ cstart, uint64_t ncomp,
-                                                        uint32_t *__restrict__ size_of)
+template <class IX>
+static __global__ __launch_bounds__(TPB) void k_mo_label_sizes(const uint64_t *__restrict__ rec, int stride, const uint32_t *__restrict__ cstart, uint64_t ncomp,
+                                                        uint32_t *__restrict__ size_of, IX ix)
 {
 	for (uint64_t c = blockIdx.x * (uint64_t)TPB + threadIdx.x; c < ncomp; c += (uint64_t)gridDim.x * TPB)
-		size_of[rec[(uint64_t)cstart[c] * stride + stride - 1]] = cstart[c + 1] - cstart[c];
+		size_of[ix.pos(rec[(uint64_t)cstart[c] * stride + stride - 1])] = cstart[c + 1] - cstart[c];
 }
 
 // the neighbour records [nj, nr) that belong to components left to the host
-__global__ __launch_bounds__(TPB) void k_mo_skipped_sel2(const uint64_t *__restrict__ rec, int stride, uint64_t nj, uint64_t nr, const uint32_t *__restrict__ size_of,
-                                                         uint64_t max_component, uint32_t *__restrict__ sel)
+template <class IX>
+static __global__ __launch_bounds__(TPB) void k_mo_skipped_sel2(const uint64_t *__restrict__ rec, int stride, uint64_t nj, uint64_t nr, const uint32_t *__restrict__ size_of,
+                                                         uint64_t max_component, uint32_t *__restrict__ sel, IX ix)
 {
 	for (uint64_t r = blockIdx.x * (uint64_t)TPB + threadIdx.x; r <= nr - nj; r += (uint64_t)gridDim.x * TPB)
-		sel[r] = r < nr - nj && (uint64_t)size_of[rec[(nj + r) * stride + stride - 1]] > max_component;
+		sel[r] = r < nr - nj && (uint64_t)size_of[ix.pos(rec[(nj + r) * stride + stride - 1])] > max_component;
 }
 
 // mark_linear over the nodes the commit wrote (cuttip.c: mark_linear_dirty) + their number
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_mo_mark(Table<NW> tbl, const uint64_t *__restrict__ slot_of, uint64_t nn, const uint8_t *__restrict__ dirty,
+static __global__ __launch_bounds__(TPB) void k_mo_mark(Table<NW> tbl, const uint64_t *__restrict__ slot_of, uint64_t nn, const uint8_t *__restrict__ dirty,
                                                  unsigned long long *counters)
 {
 	unsigned long long marked = 0, written = 0;
@@ -845,7 +871,7 @@ __global__ __launch_bounds__(TPB) void k_mo_mark(Table<NW> tbl, const uint64_t *
 
 // the written nodes as (index, l_links, r_links | linear << 24 | deleted << 25): what sdt_gpu_update_nodes_by_index takes, the other way
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_mo_emit(Table<NW> tbl, const uint64_t *__restrict__ slot_of, uint64_t nn, const uint8_t *__restrict__ dirty,
+static __global__ __launch_bounds__(TPB) void k_mo_emit(Table<NW> tbl, const uint64_t *__restrict__ slot_of, uint64_t nn, const uint8_t *__restrict__ dirty,
                                                  unsigned long long *cursor, uint64_t cap, uint64_t *__restrict__ node, uint32_t *__restrict__ l_links,
                                                  uint32_t *__restrict__ r_flags)
 {
@@ -880,69 +906,99 @@ __global__ __launch_bounds__(TPB) void k_mo_emit(Table<NW> tbl, const uint64_t *
 // still leads up the same tree; the per-XCD L2s are not coherent, so parent[] is read with device-scope atomic loads and
 // written with device-scope CAS only -- those resolve at the memory side.
 // ===============================================================================================================
-__device__ inline uint32_t uf_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// Node indices and parent[] entries are IX::T (base + position under Ix64); parent[] itself is addressed by position.
+template <class T> __device__ inline T uf_load(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ inline uint32_t uf_find(uint32_t *parent, uint32_t x)
+template <class IX>
+__device__ inline typename IX::T uf_find(typename IX::T *parent, typename IX::T x, IX ix)
 {
+	using T = typename IX::T;
 	for (;;) {
-		const uint32_t p = uf_load(parent + x);
+		const T p = uf_load(parent + ix.pos(x));
 		if (p == x) return x;
-		const uint32_t gp = uf_load(parent + p);
-		if (gp != p) atomicCAS(parent + x, p, gp);          // path halving
+		const T gp = uf_load(parent + ix.pos(p));
+		if (gp != p) atomicCAS(parent + ix.pos(x), p, gp);      // path halving
 		x = p;
 	}
 }
 
-__device__ inline void uf_union(uint32_t *parent, uint32_t a, uint32_t b)
+template <class IX>
+__device__ inline void uf_union(typename IX::T *parent, typename IX::T a, typename IX::T b, IX ix)
 {
+	using T = typename IX::T;
 	for (;;) {
-		a = uf_find(parent, a);
-		b = uf_find(parent, b);
+		a = uf_find(parent, a, ix);
+		b = uf_find(parent, b, ix);
 		if (a == b) return;
-		if (a < b) { const uint32_t t = a; a = b; b = t; }   // the larger root goes under the smaller
-		if (atomicCAS(parent + a, a, b) == a) return;
+		if (a < b) { const T t = a; a = b; b = t; }         // the larger root goes under the smaller
+		if (atomicCAS(parent + ix.pos(a), a, b) == a) return;
 	}
 }
 
-__global__ __launch_bounds__(TPB) void k_uf_init(uint32_t *__restrict__ parent, uint64_t n)
+template <class IX>
+static __global__ __launch_bounds__(TPB) void k_uf_init(typename IX::T *__restrict__ parent, uint64_t n, IX ix)
 {
-	for (uint64_t i = blockIdx.x * (uint64_t)TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TPB) parent[i] = (uint32_t)i;
+	for (uint64_t i = blockIdx.x * (uint64_t)TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TPB) parent[i] = (typename IX::T)(ix.base() + i);
 }
 
 // records of `stride` words: word 0 = node (low 56 bits); unite the node with the node indices found in words [w0, w1), each
 // shifted right by `shift` (an entry of ~0 is no node)
-__global__ __launch_bounds__(TPB) void k_uf_records(uint32_t *parent, const uint64_t *__restrict__ rec, uint64_t n, int stride, int w0, int w1, int shift)
+template <class IX>
+static __global__ __launch_bounds__(TPB) void k_uf_records(typename IX::T *parent, const uint64_t *__restrict__ rec, uint64_t n, int stride, int w0, int w1, int shift, IX ix)
 {
+	using T = typename IX::T;
 	for (uint64_t r = blockIdx.x * (uint64_t)TPB + threadIdx.x; r < n; r += (uint64_t)gridDim.x * TPB) {
-		const uint32_t me = (uint32_t)(rec[r * stride] & 0x00FFFFFFFFFFFFFFULL);
+		const T me = (T)(rec[r * stride] & 0x00FFFFFFFFFFFFFFULL);
 		for (int w = w0; w < w1; w++) {
 			const uint64_t x = rec[r * stride + w];
-			if (x != ~0ULL) uf_union(parent, me, (uint32_t)(x >> shift));
+			if (x != ~0ULL) uf_union(parent, me, (T)(x >> shift), ix);
 		}
 	}
 }
 
-// label word of every record = root of its node; sort key = label << 32 | node
-__global__ __launch_bounds__(TPB) void k_uf_label(uint32_t *parent, uint64_t *__restrict__ rec, uint64_t n, int stride, int label_word,
+// label word of every record = root of its node; sort key = label << 32 | node (Ix32)
+static __global__ __launch_bounds__(TPB) void k_uf_label(uint32_t *parent, uint64_t *__restrict__ rec, uint64_t n, int stride, int label_word,
                                                   uint64_t *__restrict__ skey, uint32_t *__restrict__ sval)
 {
 	for (uint64_t r = blockIdx.x * (uint64_t)TPB + threadIdx.x; r < n; r += (uint64_t)gridDim.x * TPB) {
 		const uint32_t me = (uint32_t)(rec[r * stride] & 0x00FFFFFFFFFFFFFFULL);
-		const uint32_t root = uf_find(parent, me);
+		const uint32_t root = uf_find(parent, me, Ix32());
 		rec[r * stride + label_word] = root;
 		skey[r] = ((uint64_t)root << 32) | me;
 		sval[r] = (uint32_t)r;
 	}
 }
 
-// label word of records that are not sorted (the neighbours to cut behind the junction records)
-__global__ __launch_bounds__(TPB) void k_uf_label_only(uint32_t *parent, uint64_t *__restrict__ rec, uint64_t r0, uint64_t n, int stride, int label_word)
+// Ix64: two 64-bit fields do not fit one key -- label word = root, sort key = node; a stable sort by the node, then a stable sort by
+// the label of the records in that order (k_uf_label_keys) gives the order by (label, node)
+static __global__ __launch_bounds__(TPB) void k_uf_label_wide(unsigned long long *parent, uint64_t *__restrict__ rec, uint64_t n, int stride, int label_word,
+                                                       uint64_t *__restrict__ skey, uint32_t *__restrict__ sval, Ix64 ix)
 {
-	for (uint64_t r = r0 + blockIdx.x * (uint64_t)TPB + threadIdx.x; r < n; r += (uint64_t)gridDim.x * TPB)
-		rec[r * stride + label_word] = uf_find(parent, (uint32_t)(rec[r * stride] & 0x00FFFFFFFFFFFFFFULL));
+	for (uint64_t r = blockIdx.x * (uint64_t)TPB + threadIdx.x; r < n; r += (uint64_t)gridDim.x * TPB) {
+		const unsigned long long me = rec[r * stride] & 0x00FFFFFFFFFFFFFFULL;
+		rec[r * stride + label_word] = uf_find(parent, me, ix);
+		skey[r] = me;
+		sval[r] = (uint32_t)r;
+	}
 }
 
-__global__ __launch_bounds__(TPB) void k_gather_records(const uint64_t *__restrict__ rec, const uint32_t *__restrict__ perm, uint64_t n, int stride,
+static __global__ __launch_bounds__(TPB) void k_uf_label_keys(const uint64_t *__restrict__ rec, const uint32_t *__restrict__ perm, uint64_t n, int stride,
+                                                       int label_word, uint64_t *__restrict__ skey)
+{
+	for (uint64_t i = blockIdx.x * (uint64_t)TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TPB)
+		skey[i] = rec[(uint64_t)perm[i] * stride + label_word];
+}
+
+// label word of records that are not sorted (the neighbours to cut behind the junction records)
+template <class IX>
+static __global__ __launch_bounds__(TPB) void k_uf_label_only(typename IX::T *parent, uint64_t *__restrict__ rec, uint64_t r0, uint64_t n, int stride, int label_word, IX ix)
+{
+	using T = typename IX::T;
+	for (uint64_t r = r0 + blockIdx.x * (uint64_t)TPB + threadIdx.x; r < n; r += (uint64_t)gridDim.x * TPB)
+		rec[r * stride + label_word] = uf_find(parent, (T)(rec[r * stride] & 0x00FFFFFFFFFFFFFFULL), ix);
+}
+
+static __global__ __launch_bounds__(TPB) void k_gather_records(const uint64_t *__restrict__ rec, const uint32_t *__restrict__ perm, uint64_t n, int stride,
                                                         uint64_t *__restrict__ out)
 {
 	const uint64_t total = n * (uint64_t)stride;
@@ -957,7 +1013,7 @@ __global__ __launch_bounds__(TPB) void k_gather_records(const uint64_t *__restri
 // (in two steps, as the tip walks: k_port_starts lists slot << 3 | port for every live port of such a node, k_port_union_list
 // gives every lane one port to walk)
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_port_starts(Table<NW> tbl, unsigned long long *__restrict__ list, ApOut ap)
+static __global__ __launch_bounds__(TPB) void k_port_starts(Table<NW> tbl, unsigned long long *__restrict__ list, ApOut ap)
 {
 	__shared__ WaveApp s_app[TPB / 64];
 	ap_init(s_app);
@@ -976,9 +1032,10 @@ __global__ __launch_bounds__(TPB) void k_port_starts(Table<NW> tbl, unsigned lon
 	ap_finish_mark(s_app, ap);
 }
 
-template <int NW>
-__global__ __launch_bounds__(TPB) void k_port_union_list(Table<NW> tbl, const uint64_t *__restrict__ idx, int K, int max_linear,
-                                                         const unsigned long long *__restrict__ list, unsigned long long n_list, uint32_t *parent, Stats *stats)
+template <int NW, class IX>
+static __global__ __launch_bounds__(TPB) void k_port_union_list(Table<NW> tbl, const uint64_t *__restrict__ idx, int K, int max_linear,
+                                                         const unsigned long long *__restrict__ list, unsigned long long n_list, typename IX::T *parent, Stats *stats,
+                                                         IX ix)
 {
 	const Key<NW> mask = key_mask_of<NW>(K);
 	uint32_t missing = 0;
@@ -1007,7 +1064,7 @@ __global__ __launch_bounds__(TPB) void k_port_union_list(Table<NW> tbl, const ui
 			b = sm ? first_link((ov >> 24) & 0xFFFFFFu) : (first_link(ov & 0xFFFFFFu) ^ 2u);
 			word = key_next_masked<NW>(word, b, mask);
 		}
-		if (ok) uf_union(parent, (uint32_t)idx[s], (uint32_t)idx[os]);
+		if (ok) uf_union(parent, (typename IX::T)idx[s], (typename IX::T)idx[os], ix);
 	}
 	if (missing) atomicAdd(&stats->probe_fail, (unsigned long long)missing);
 }
@@ -1029,7 +1086,7 @@ __global__ __launch_bounds__(TPB) void k_port_union_list(Table<NW> tbl, const ui
 constexpr uint64_t GP_SKIP = 1, GP_LINEAR = 2;       // = PATH_SKIP / PATH_LINEAR of sdt_map_kernels.cuh
 
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_edge_starts(Table<NW> tbl, const uint64_t *__restrict__ slot_of, uint64_t n, uint32_t *__restrict__ flag,
+static __global__ __launch_bounds__(TPB) void k_edge_starts(Table<NW> tbl, const uint64_t *__restrict__ slot_of, uint64_t n, uint32_t *__restrict__ flag,
                                                      uint64_t *__restrict__ pw)
 {
 	for (uint64_t v = blockIdx.x * (uint64_t)TPB + threadIdx.x; v < n; v += (uint64_t)gridDim.x * TPB) {
@@ -1042,25 +1099,27 @@ __global__ __launch_bounds__(TPB) void k_edge_starts(Table<NW> tbl, const uint64
 
 struct PortRec { uint64_t far, meta; };              // far node index (~0: no link), length | far_port << 32 | bal_edge << 40
 
-__global__ __launch_bounds__(TPB) void k_edge_start_nodes(const uint32_t *__restrict__ flag, const uint32_t *__restrict__ srank, uint64_t n,
-                                                           uint32_t *__restrict__ start_node)
+// (srank = exclusive scan of flag over the node positions; start_node[] holds node indices: base + position)
+template <class IX>
+static __global__ __launch_bounds__(TPB) void k_edge_start_nodes(const uint32_t *__restrict__ flag, const typename IX::T *__restrict__ srank, uint64_t n,
+                                                          typename IX::T *__restrict__ start_node, IX ix)
 {
 	for (uint64_t v = blockIdx.x * (uint64_t)TPB + threadIdx.x; v < n; v += (uint64_t)gridDim.x * TPB)
-		if (flag[v]) start_node[srank[v]] = (uint32_t)v;
+		if (flag[v]) start_node[srank[v]] = (typename IX::T)(ix.base() + v);
 }
 
 // one lane per PORT of a start node (rank r of the node among the start nodes, port p: record r * 8 + p): every lane of a wave walks
-template <int NW>
-__global__ __launch_bounds__(TPB) void k_edge_ports_ordered(Table<NW> tbl, const uint64_t *__restrict__ idx, const uint64_t *__restrict__ slot_of,
-                                                            const uint32_t *__restrict__ start_node, uint64_t nports, int K,
-                                                            uint64_t max_steps, PortRec *__restrict__ ports, Stats *stats)
+template <int NW, class IX>
+static __global__ __launch_bounds__(TPB) void k_edge_ports_ordered(Table<NW> tbl, const uint64_t *__restrict__ idx, const uint64_t *__restrict__ slot_of,
+                                                            const typename IX::T *__restrict__ start_node, uint64_t nports, int K,
+                                                            uint64_t max_steps, PortRec *__restrict__ ports, Stats *stats, IX ix)
 {
 	const Key<NW> mask = key_mask_of<NW>(K);
 	const int tb = 2 * (K - 1);
 	uint32_t missing = 0;
 	for (uint64_t g = blockIdx.x * (uint64_t)TPB + threadIdx.x; g < nports; g += (uint64_t)gridDim.x * TPB) {
 		const int p = (int)(g & 7u);
-		const Entry<NW> e = tbl.ent[slot_of[start_node[g >> 3]]];
+		const Entry<NW> e = tbl.ent[slot_of[ix.pos(start_node[g >> 3])]];
 		uint64_t far = ~0ULL, meta = 0;
 		const bool live = p < 4 ? ((e.val >> (24 + 6 * p)) & 63u) != 0 : ((e.val >> (6 * (p - 4))) & 63u) != 0;
 		if (live) {
@@ -1105,9 +1164,10 @@ __global__ __launch_bounds__(TPB) void k_edge_ports_ordered(Table<NW> tbl, const
 // one thread per port: does it emit its edge?  (the first of the two ends in visiting order; node2edge.c's zeroing of the far
 // link is what keeps the other end quiet.)  asym: a far port whose own walk does not come back here -- the host then builds the
 // edges the reference's sequential way.
-__global__ __launch_bounds__(TPB) void k_edge_emit(const PortRec *__restrict__ ports, const uint32_t *__restrict__ start_node, const uint32_t *__restrict__ flag,
-                                                   const uint32_t *__restrict__ srank, uint64_t nports, uint32_t *__restrict__ w_edge,
-                                                   uint32_t *__restrict__ w_id, uint64_t *__restrict__ w_len, unsigned int *asym)
+template <class IX>
+static __global__ __launch_bounds__(TPB) void k_edge_emit(const PortRec *__restrict__ ports, const typename IX::T *__restrict__ start_node, const uint32_t *__restrict__ flag,
+                                                   const typename IX::T *__restrict__ srank, uint64_t nports, uint32_t *__restrict__ w_edge,
+                                                   uint32_t *__restrict__ w_id, uint64_t *__restrict__ w_len, unsigned int *asym, IX ix)
 {
 	for (uint64_t rp = blockIdx.x * (uint64_t)TPB + threadIdx.x; rp < nports; rp += (uint64_t)gridDim.x * TPB) {
 		const PortRec P = ports[rp];
@@ -1116,8 +1176,8 @@ __global__ __launch_bounds__(TPB) void k_edge_emit(const PortRec *__restrict__ p
 			const uint64_t v = start_node[rp >> 3];
 			const uint32_t p = (uint32_t)(rp & 7), fp = (uint32_t)(P.meta >> 32) & 0xFFu;
 			emit = 1;
-			if (flag[P.far]) {
-				const PortRec Q = ports[(uint64_t)srank[P.far] * 8 + fp];
+			if (flag[ix.pos(P.far)]) {
+				const PortRec Q = ports[(uint64_t)srank[ix.pos(P.far)] * 8 + fp];
 				if (Q.far != ~0ULL) {
 					if (!(Q.far == v && ((uint32_t)(Q.meta >> 32) & 0xFFu) == p)) atomicOr(asym, 1u);
 					emit = (v < P.far || (v == P.far && p <= fp)) ? 1u : 0u;
@@ -1130,12 +1190,12 @@ __global__ __launch_bounds__(TPB) void k_edge_emit(const PortRec *__restrict__ p
 	}
 }
 
-template <int NW>
-__global__ __launch_bounds__(TPB) void k_edge_stamp(Table<NW> tbl, const uint64_t *__restrict__ idx, const uint64_t *__restrict__ slot_of, int K,
-                                                    const PortRec *__restrict__ ports, const uint32_t *__restrict__ start_node, uint64_t nports,
+template <int NW, class IX>
+static __global__ __launch_bounds__(TPB) void k_edge_stamp(Table<NW> tbl, const uint64_t *__restrict__ idx, const uint64_t *__restrict__ slot_of, int K,
+                                                    const PortRec *__restrict__ ports, const typename IX::T *__restrict__ start_node, uint64_t nports,
                                                     const uint32_t *__restrict__ w_edge, const uint32_t *__restrict__ e_scan, const uint32_t *__restrict__ id_scan,
                                                     const uint64_t *__restrict__ len_scan, uint64_t *__restrict__ pw, unsigned char *__restrict__ seq,
-                                                    uint64_t *__restrict__ erec, Stats *stats)
+                                                    uint64_t *__restrict__ erec, Stats *stats, IX ix)
 {
 	Key<NW> mask;
 #pragma unroll
@@ -1151,7 +1211,7 @@ __global__ __launch_bounds__(TPB) void k_edge_stamp(Table<NW> tbl, const uint64_
 		const uint64_t length = P.meta & 0xFFFFFFFFULL, cnt = length + 1;
 		const uint32_t bal = (uint32_t)(P.meta >> 40) & 1u, id = 1u + id_scan[rp];
 		const uint64_t e = e_scan[rp], off = len_scan[rp];
-		const uint64_t v = start_node[rp >> 3];
+		const uint64_t v = ix.pos(start_node[rp >> 3]);
 		const int p = (int)(rp & 7);
 		const Entry<NW> first = tbl.ent[slot_of[v]];
 		Key<NW> me;
@@ -1177,7 +1237,7 @@ __global__ __launch_bounds__(TPB) void k_edge_stamp(Table<NW> tbl, const uint64_
 			const uint64_t ov = tbl.ent[os].val;
 			if (!bal && i < cnt / 2) symbol += idsum;
 			else symbol += (long long)((ov & 63u) + ((ov >> 6) & 63u) + ((ov >> 12) & 63u) + ((ov >> 18) & 63u));
-			pw[idx[os]] = GP_LINEAR | ((uint64_t)(sm ? bal + 1u : 1u - bal) << 2) | ((uint64_t)(sm ? id : id + bal) << 32);
+			pw[ix.pos(idx[os])] = GP_LINEAR | ((uint64_t)(sm ? bal + 1u : 1u - bal) << 2) | ((uint64_t)(sm ? id : id + bal) << 32);
 			b = sm ? first_link((ov >> 24) & 0xFFFFFFu) : (first_link(ov & 0xFFFFFFu) ^ 2u);
 			word = key_next_masked<NW>(word, b, mask);
 		}
@@ -1266,7 +1326,7 @@ __device__ inline bool rp_insert(unsigned long long *tab, uint32_t size, uint32_
 
 // homes of ids [a, b) of every set for a table of size `mod` (pre = exclusive prefix of b - a over the sets)
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_rp_home(const uint64_t *__restrict__ keys, const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre,
+static __global__ __launch_bounds__(TPB) void k_rp_home(const uint64_t *__restrict__ keys, const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre,
                                                  int p, int rehash, uint32_t *__restrict__ home)
 {
 	const unsigned long long total = pre[p];
@@ -1278,7 +1338,7 @@ __global__ __launch_bounds__(TPB) void k_rp_home(const uint64_t *__restrict__ ke
 	}
 }
 
-__global__ __launch_bounds__(TPB) void k_rp_put(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int p,
+static __global__ __launch_bounds__(TPB) void k_rp_put(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int p,
                                                 const uint32_t *__restrict__ home, unsigned long long *__restrict__ tab, unsigned int *fail)
 {
 	const unsigned long long total = pre[p];
@@ -1294,7 +1354,7 @@ __global__ __launch_bounds__(TPB) void k_rp_put(const RpSet *__restrict__ sets, 
 // reads times and homes in slot order -- the insertion itself is the only random access of a round)
 //   k_rp_rehash_init: time (q, 0) and the home in the NEW geometry of the entry at every old slot
 template <int NW>
-__global__ __launch_bounds__(TPB) void k_rp_rehash_init(const uint64_t *__restrict__ keys, const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre,
+static __global__ __launch_bounds__(TPB) void k_rp_rehash_init(const uint64_t *__restrict__ keys, const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre,
                                                         int p, const unsigned long long *__restrict__ told, unsigned long long *__restrict__ t_slot,
                                                         uint32_t *__restrict__ home_slot)
 {
@@ -1327,7 +1387,7 @@ struct RpRound {
 	unsigned int pad;
 };
 
-__global__ __launch_bounds__(TPB) void k_rp_ins_all(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int p, int qbits,
+static __global__ __launch_bounds__(TPB) void k_rp_ins_all(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int p, int qbits,
                                                     const unsigned long long *__restrict__ told, unsigned long long *tnew,
                                                     const uint32_t *__restrict__ home_slot, const unsigned long long *__restrict__ t, RpRound *st)
 {
@@ -1358,7 +1418,7 @@ __device__ inline void rp_eval(const RpSet &S, int s, unsigned long long g, unsi
 	else atomicOr(&st->flags, 8u);
 }
 
-__global__ __launch_bounds__(TPB) void k_rp_eval_all(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int p, int qbits,
+static __global__ __launch_bounds__(TPB) void k_rp_eval_all(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int p, int qbits,
                                                      const unsigned long long *__restrict__ told, const unsigned long long *tnew,
                                                      const uint32_t *__restrict__ home_slot, unsigned long long *t,
                                                      unsigned long long *next_list, unsigned long long cap_chunks, RpRound *st)
@@ -1378,7 +1438,7 @@ __global__ __launch_bounds__(TPB) void k_rp_eval_all(const RpSet *__restrict__ s
 }
 
 // take the listed stretches out of the table: the words go to saved[] (same index as the slot), the slots are emptied
-__global__ __launch_bounds__(TPB) void k_rp_collect(const RpSet *__restrict__ sets, unsigned long long *tnew, unsigned long long *__restrict__ saved,
+static __global__ __launch_bounds__(TPB) void k_rp_collect(const RpSet *__restrict__ sets, unsigned long long *tnew, unsigned long long *__restrict__ saved,
                                                     unsigned long long *list, unsigned long long n_list, RpRound *st)
 {
 	for (unsigned long long k = blockIdx.x * (unsigned long long)TPB + threadIdx.x; k < n_list; k += (unsigned long long)gridDim.x * TPB) {
@@ -1400,7 +1460,7 @@ __global__ __launch_bounds__(TPB) void k_rp_collect(const RpSet *__restrict__ se
 	}
 }
 
-__global__ __launch_bounds__(TPB) void k_rp_ins_list(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int qbits,
+static __global__ __launch_bounds__(TPB) void k_rp_ins_list(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int qbits,
                                                      unsigned long long *tnew, const unsigned long long *__restrict__ saved,
                                                      const uint32_t *__restrict__ home_slot, const unsigned long long *__restrict__ t,
                                                      const unsigned long long *__restrict__ list, unsigned long long n_list, RpRound *st)
@@ -1422,7 +1482,7 @@ __global__ __launch_bounds__(TPB) void k_rp_ins_list(const RpSet *__restrict__ s
 }
 
 // the old slots inside the re-arranged stretches are the only ones whose evaluation can have changed
-__global__ __launch_bounds__(TPB) void k_rp_eval_list(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int qbits,
+static __global__ __launch_bounds__(TPB) void k_rp_eval_list(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int qbits,
                                                       const unsigned long long *__restrict__ told, const unsigned long long *tnew,
                                                       const uint32_t *__restrict__ home_slot, unsigned long long *t,
                                                       const unsigned long long *__restrict__ list, unsigned long long n_list,
@@ -1448,7 +1508,7 @@ __global__ __launch_bounds__(TPB) void k_rp_eval_list(const RpSet *__restrict__ 
 
 // over the NEW slots (pre = exclusive prefix of size): mode 0 = after a growth: the old slot in the word -> the entry (id + 1, from the
 // old table), 1 = flag occupied slots for the final order
-__global__ __launch_bounds__(TPB) void k_rp_slots(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int p, int mode, int qbits,
+static __global__ __launch_bounds__(TPB) void k_rp_slots(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int p, int mode, int qbits,
                                                   const unsigned long long *__restrict__ told, unsigned long long *__restrict__ tab, uint32_t *__restrict__ occ)
 {
 	const unsigned long long total = pre[p], qmask = (1ULL << qbits) - 1ULL;
@@ -1463,9 +1523,10 @@ __global__ __launch_bounds__(TPB) void k_rp_slots(const RpSet *__restrict__ sets
 }
 
 // order[v] = rank of the node at visiting position v: the sets one after the other, inside a set the table's slots in order
-__global__ __launch_bounds__(TPB) void k_rp_order(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int p,
+template <class R>
+static __global__ __launch_bounds__(TPB) void k_rp_order(const RpSet *__restrict__ sets, const unsigned long long *__restrict__ pre, int p,
                                                   const unsigned long long *__restrict__ tab, const uint32_t *__restrict__ occ,
-                                                  const uint32_t *__restrict__ rank, uint64_t *__restrict__ order)
+                                                  const R *__restrict__ rank, uint64_t *__restrict__ order)
 {
 	const unsigned long long total = pre[p];
 	for (unsigned long long g = blockIdx.x * (unsigned long long)TPB + threadIdx.x; g < total; g += (unsigned long long)gridDim.x * TPB) {
@@ -1479,15 +1540,15 @@ __global__ __launch_bounds__(TPB) void k_rp_order(const RpSet *__restrict__ sets
 
 
 // ---- the arcs of the second read pass in the order of *.preArc (output_arcs, prlRead2path.c:454-505) --------------------------
-__global__ __launch_bounds__(TPB) void k_arc_keys(const uint64_t *__restrict__ first, uint64_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ perm)
+static __global__ __launch_bounds__(TPB) void k_arc_keys(const uint64_t *__restrict__ first, uint64_t n, uint64_t *__restrict__ key, uint32_t *__restrict__ perm)
 {
 	for (uint64_t i = blockIdx.x * (uint64_t)TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TPB) { key[i] = ~first[i]; perm[i] = (uint32_t)i; }
 }
-__global__ __launch_bounds__(TPB) void k_arc_from_of(const uint32_t *__restrict__ from, const uint32_t *__restrict__ perm, uint64_t n, uint32_t *__restrict__ key)
+static __global__ __launch_bounds__(TPB) void k_arc_from_of(const uint32_t *__restrict__ from, const uint32_t *__restrict__ perm, uint64_t n, uint32_t *__restrict__ key)
 {
 	for (uint64_t i = blockIdx.x * (uint64_t)TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TPB) key[i] = from[perm[i]];
 }
-__global__ __launch_bounds__(TPB) void k_arc_gather(const uint32_t *__restrict__ perm, uint64_t n, const uint32_t *__restrict__ f, const uint32_t *__restrict__ t,
+static __global__ __launch_bounds__(TPB) void k_arc_gather(const uint32_t *__restrict__ perm, uint64_t n, const uint32_t *__restrict__ f, const uint32_t *__restrict__ t,
                                                     const uint32_t *__restrict__ m, const uint64_t *__restrict__ o, uint32_t *__restrict__ f2,
                                                     uint32_t *__restrict__ t2, uint32_t *__restrict__ m2, uint64_t *__restrict__ o2)
 {

@@ -2,7 +2,8 @@
 //   sdt_gpu.hip        pass 1 (direct kernel family, locality pipeline), table scans, second read pass, multi-GPU, map stage
 //   sdt_mem.hip        device memory: the arena behind every hipMalloc / hipFree of the library
 //   sdt_gpu_graph.hip  graph phases on the device mirror: layout (visiting order), dry runs of the cutting passes with
-//                      the components of their commits, port walks of kmer2edges
+//                      the components of their commits, port walks of kmer2edges (32-bit node indices; sdt_gpu_graph64.hip: the
+//                      same phases with 64-bit ones, sdt_graph_phases.hpp: what the two share)
 // The context itself (struct sdt_ctx) stays private to sdt_gpu.hip; the graph unit sees it through GraphView.
 #pragma once
 #include "sdt_knobs.h"
@@ -40,6 +41,8 @@ struct GraphExt;                   // state of the graph unit, owned by the cont
 void graph_ext_free(GraphExt *gx);
 // the path words sdt_gpu_build_edges left on the device (n words, one per node index), or nullptr; the caller frees them
 uint64_t *graph_take_path_words(GraphExt *gx, uint64_t n);
+// node index of position 0 in the node index (d_idx): 0, but under the test hook SDT_NODE_BASE in the 64-bit form
+uint64_t graph_node_base(const GraphExt *gx);
 
 struct GraphView {
 	int device, K, nw, cu_count;

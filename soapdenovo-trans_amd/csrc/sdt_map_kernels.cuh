@@ -262,13 +262,13 @@ static __global__ __launch_bounds__(TPB) void k_export_arcs(const ArcEnt *__rest
 // k_set_paths when the device already knows each node's host index (sdt_gpu_set_node_index): no keys, no probing
 template <int NW>
 __global__ __launch_bounds__(TPB) void k_set_paths_by_index(Table<NW> tbl, const uint64_t *__restrict__ idx, const uint64_t *__restrict__ info, uint64_t n,
-                                                            Stats *stats)
+                                                            Stats *stats, uint64_t base)
 {
 	const uint64_t slots = tbl.slots();
 	uint32_t failed = 0;
 	for (uint64_t s = blockIdx.x * (uint64_t)TPB + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * TPB) {
 		if (tbl.ent[s].key[0] == KEY_EMPTY) continue;
-		const uint64_t i = idx[s];
+		const uint64_t i = idx[s] - base;                     // (node index -> position: base = 0 but under SDT_NODE_BASE)
 		if (i < n) tbl.ent[s].val = info[i];
 		else failed++;
 	}
