@@ -417,6 +417,49 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
                                uint64_t max_read_len, const void *d_align_len, int align_len_all, void *d_read_info,
                                void *d_hits, uint64_t max_hits, uint64_t *nhits);
 
+/* ---- read-only questions to the counted table ------------------------------------------------------------
+ * search_kmerset (newhash.c:239-283) has no counterpart in pass 1 itself: the reference calls it from the later phases
+ * (prlRead2path.c:363-394, cutTipPreGraph.c, node2edge.c), always with the smaller of a k-mer and its reverse complement.
+ *   search_kmers:   a batch of n k-mers; keys = n x key_words() words, most significant first, the k-mer as the caller has
+ *                   it (either strand, K bases right-aligned, the bits above them 0).  For query i:
+ *                     status[i]   bit 0 found | bit 1 the query is the larger strand, i.e. the node is stored as its reverse
+ *                                 complement (set whether or not the node exists)
+ *                     count[i], l_links[i], r_flags[i]   the words sdt_gpu_export_nodes gives for the node -- kmer_t.count,
+ *                                 l_links, r_links:24 | linear << 24 | deleted << 25 | single << 27 -- as the STORED node has
+ *                                 them (never swapped to the query's strand); 0 when the node does not exist.
+ *                   Any output array may be NULL.  Host pointers; blocks.  _device: device pointers, asynchronous on the
+ *                   context's stream.
+ *   profile_reads:  the k-mer coverage of every read of a batch (packed as for sdt_gpu_push_reads): out[i] for read i.
+ *                     kmers   len - K + 1 for len >= K, else 0 and every other field 0.  (NOT pass 1's len >= K + 1 rule,
+ *                             prlHashReads.c:592: a profile is about the read, not about what was inserted.)
+ *                     found   k-mers whose node exists;  solid: k-mers with count >= min_count (min_count == 0: all of them)
+ *                     min, median, max   over ALL kmers counts, a k-mer without a node counting 0; median = the lower median,
+ *                             element (kmers - 1) / 2 in ascending order
+ *                   _device: buffers already on the device; max_read_len bounds the longest read (it sizes the LDS strip).  A
+ *                   longer read gets kmers = 0xFFFFFFFF (other fields 0) and the call returns SDT_EINVAL; the call waits for
+ *                   the kernel to know.
+ *   profile_kept_reads: the same for the reads kept in HBM (SDT_FLAG_KEEP_READS / sdt_gpu_keep_reads): out[] is indexed by
+ *                   READ ORDINAL (sdt_gpu_set_read_ordinal: base + i * stride of each kept batch), so interleaved paired
+ *                   files land in the reference's stream order (prlHashReads.c:493-567).  out_capacity records; *nreads =
+ *                   reads profiled.  Records of ordinals that no kept read has are left untouched.  SDT_EFULL, nothing
+ *                   written, when a kept read's ordinal is >= out_capacity.
+ * Allowed once sdt_gpu_finish_count has returned and for as long as the counters exist: after delow, mark_and_hist, layout or
+ * cutting calls the answers describe the table as it is then.  SDT_ESTATE: batches pushed or counted and not yet drained; after
+ * sdt_gpu_load_paths / sdt_gpu_import_paths (the counters hold path words); after sdt_gpu_release_table; on a
+ * SDT_FLAG_CONTIG_INDEX context; on a context with a communicator (a shard cannot tell "absent" from "another rank's
+ * bucket").  n == 0 / nreads == 0: SDT_OK, nothing touched.  The calls never write the table. */
+typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
+int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
+                         uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
+int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
+                                void *d_count, void *d_l_links, void *d_r_flags, void *d_status);
+int sdt_gpu_profile_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                          uint64_t nreads, uint32_t min_count, sdt_read_cov *out);
+int sdt_gpu_profile_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                                 uint64_t max_read_len, uint32_t min_count, void *d_out);
+int sdt_gpu_profile_kept_reads(sdt_ctx *ctx, uint32_t min_count, sdt_read_cov *out, uint64_t out_capacity,
+                               uint64_t *nreads);
+
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */
 uint64_t sdt_gpu_table_slots(const sdt_ctx *ctx);

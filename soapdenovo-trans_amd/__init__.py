@@ -117,8 +117,17 @@ _ABI = [
     ("sdt_comm_selftest_shm", _c.c_int, [_c.c_char_p, _c.c_int, _c.c_int, _c.c_int]),
     ("sdt_gpu_import_nodes", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64]),
     ("sdt_gpu_keep_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64]),
+    ("sdt_gpu_search_kmers", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_search_kmers_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_profile_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p]),
+    ("sdt_gpu_profile_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_uint32, _c.c_void_p]),
+    ("sdt_gpu_profile_kept_reads", _c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
+
+# sdt_read_cov (include/sdt_gpu.h): one record per read of a k-mer coverage profile
+READ_COV_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "found", "solid", "min", "median", "max")])
+COV_TOO_LONG = 0xFFFFFFFF
 
 _lib = None
 
@@ -503,6 +512,43 @@ class PregraphGPU:
         buf = np.zeros(max(nb.value, 1), dtype=np.uint8)
         self._check(self.lib.sdt_gpu_fetch_edge_bases(self._ctx, _ptr(buf), nb.value))
         return rec, buf[: nb.value].tobytes(), ids.value
+
+    # -- read-only questions to the counted table (search_kmerset, newhash.c:239-283)
+    def search_kmers(self, keys):
+        """keys uint64[n, nw], either strand -> (count, l_links, r_flags uint32[n], status uint8[n]: bit 0 found, bit 1 stored as
+        the reverse complement of the query); the words are the stored node's, as export_nodes gives them"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, self.nw)
+        n = len(keys)
+        count, l_links, r_flags = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+        status = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.sdt_gpu_search_kmers(self._ctx, _ptr(keys), n, _ptr(count), _ptr(l_links), _ptr(r_flags), _ptr(status)))
+        return count, l_links, r_flags, status
+
+    def search_kmers_device(self, d_keys, n: int, d_count=None, d_l_links=None, d_r_flags=None, d_status=None):
+        """device buffers (torch tensors or addresses); asynchronous on the context's stream"""
+        self._check(self.lib.sdt_gpu_search_kmers_device(self._ctx, _ptr(d_keys), n, _ptr(d_count), _ptr(d_l_links), _ptr(d_r_flags), _ptr(d_status)))
+
+    def profile_reads(self, words, offsets, min_count: int = 0) -> np.ndarray:
+        """-> READ_COV_DTYPE[nreads]: kmers, found, solid (count >= min_count), min, median (lower), max of every read's k-mer counts"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        out = np.zeros(n, dtype=READ_COV_DTYPE)
+        self._check(self.lib.sdt_gpu_profile_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, min_count, _ptr(out)))
+        return out
+
+    def profile_reads_device(self, d_words, d_offsets, nreads: int, max_read_len: int, min_count: int, d_out):
+        """device buffers; d_out holds nreads records of 24 bytes"""
+        self._check(self.lib.sdt_gpu_profile_reads_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, max_read_len, min_count, _ptr(d_out)))
+
+    def profile_kept_reads(self, total_reads: int, min_count: int = 0, out: np.ndarray = None):
+        """the reads kept in HBM, indexed by read ordinal -> (READ_COV_DTYPE[total_reads], reads profiled)"""
+        if out is None:
+            out = np.zeros(total_reads, dtype=READ_COV_DTYPE)
+        assert out.dtype == READ_COV_DTYPE and out.flags.c_contiguous and len(out) >= total_reads
+        n = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_profile_kept_reads(self._ctx, min_count, _ptr(out), total_reads, ctypes.byref(n)))
+        return out, n.value
 
     def set_read_ordinal(self, base: int, stride: int = 1):
         self._check(self.lib.sdt_gpu_set_read_ordinal(self._ctx, base, stride))

@@ -1,0 +1,260 @@
+/* sdt_kmers.c -- ask the counted node table: the same ingest as sdt-pregraph (library config, library order, truncation, paired
+ * interleave and its read ordinals: libcfg.c, readstream.c, seqio.c), pass 1 on the device, optionally `-d`, then
+ *
+ *   sdt-kmers profile -s lib.cfg -K k [-p threads] [-d d] [-c min_count] -o prefix
+ *       prefix.readCov: one line per read in stream order:  kmers found solid min median max   (sdt_gpu_profile_kept_reads)
+ *   sdt-kmers query   -s lib.cfg -K k [-p threads] [-d d] -q kmers.txt [-o out.tsv]
+ *       per input line:  <kmer> <found 0|1> <strand +|-> <count> <l: A C T G> <r: A C T G> <linear> <deleted>   (sdt_gpu_search_kmers,
+ *       the batch form of search_kmerset, newhash.c:239-283; links as the STORED node has them, strand - = stored as the reverse
+ *       complement of the query)
+ *
+ * The query file is read and checked before the device is touched. */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <stdint.h>
+#include <getopt.h>
+#include "../sdt_knobs.h"
+#include "libcfg.h"
+#include "seqio.h"
+#include "readstream.h"
+#include "../../../include/sdt_gpu.h"
+
+#define SDT_MAX_K 127
+
+static void usage(void)
+{
+	fprintf(stderr,
+	        "usage: sdt-kmers profile -s lib.cfg -K k [-p threads] [-d d] [-c min_count] -o prefix\n"
+	        "           -> prefix.readCov, one line per read in stream order: kmers found solid min median max\n"
+	        "       sdt-kmers query   -s lib.cfg -K k [-p threads] [-d d] -q kmers.txt [-o out.tsv]\n"
+	        "           -> per line of kmers.txt: kmer found strand count l_A l_C l_T l_G r_A r_C r_T r_G linear deleted\n"
+	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
+}
+
+/* pooled batches (pinned buffers, seqio.h) are pushed asynchronously, as sdt-pregraph does */
+#define PUSH_DEPTH 12
+static struct { int slot[PUSH_DEPTH]; uint64_t ticket[PUSH_DEPTH]; int head, n; } g_inflight;
+
+static int inflight_retire(sdt_ctx *gpu, int down_to)
+{
+	while (g_inflight.n > down_to) {
+		if (sdt_gpu_push_wait(gpu, g_inflight.ticket[g_inflight.head]) != SDT_OK) { fprintf(stderr, "sdt_gpu_push_wait: %s\n", sdt_gpu_last_error()); return -1; }
+		sdt_pool_release(g_inflight.slot[g_inflight.head]);
+		g_inflight.head = (g_inflight.head + 1) % PUSH_DEPTH;
+		g_inflight.n--;
+	}
+	return 0;
+}
+
+typedef struct { sdt_ctx *gpu; unsigned long long reads; } push_state;
+
+static int push_batch(void *user, const sdt_batch *b, uint64_t ord_base, uint64_t ord_stride)
+{
+	push_state *st = (push_state *)user;
+	st->reads += b->nreads;
+	if (!b->nreads) return 0;
+	sdt_gpu_set_read_ordinal(st->gpu, ord_base, ord_stride);
+	if (b->pool_slot >= 0) {
+		uint64_t ticket = 0;
+		const int rc = b->fixed_len ? sdt_gpu_push_reads_fixed_async(st->gpu, b->words, b->nwords, b->nreads, b->fixed_len, &ticket)
+		                            : sdt_gpu_push_reads_async(st->gpu, b->words, b->nwords, b->offsets, b->nreads, &ticket);
+		if (rc != SDT_OK) { fprintf(stderr, "sdt_gpu_push_reads_async: %s\n", sdt_gpu_last_error()); return -1; }
+		if (inflight_retire(st->gpu, PUSH_DEPTH - 1) != 0) return -1;
+		const int at = (g_inflight.head + g_inflight.n) % PUSH_DEPTH;
+		g_inflight.slot[at] = b->pool_slot;
+		g_inflight.ticket[at] = ticket;
+		g_inflight.n++;
+		sdt_pool_take(b->pool_slot);
+		return 0;
+	}
+	if (sdt_gpu_push_reads(st->gpu, b->words, b->nwords, b->offsets, b->nreads) != SDT_OK) {
+		fprintf(stderr, "sdt_gpu_push_reads: %s\n", sdt_gpu_last_error());
+		return -1;
+	}
+	return 0;
+}
+
+static char *put_u32(char *p, uint32_t v, char sep)
+{
+	char t[10];
+	int n = 0;
+	do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
+	while (n) *p++ = t[--n];
+	*p++ = sep;
+	return p;
+}
+
+/* prefix.readCov: "kmers found solid min median max" per read (8 M reads are 180 MB of digits: formatted by hand into a block buffer) */
+static int write_read_cov(const char *path, const sdt_read_cov *cov, unsigned long long n)
+{
+	FILE *fo = fopen(path, "w");
+	if (!fo) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path); return -1; }
+	enum { BLOCK = 1 << 20, LINE_MAX_BYTES = 6 * 11 };
+	char *buf = (char *)malloc(BLOCK), *p = buf;
+	int ok = buf != NULL;
+	for (unsigned long long i = 0; ok && i < n; i++) {
+		p = put_u32(p, cov[i].kmers, ' ');
+		p = put_u32(p, cov[i].found, ' ');
+		p = put_u32(p, cov[i].solid, ' ');
+		p = put_u32(p, cov[i].min, ' ');
+		p = put_u32(p, cov[i].median, ' ');
+		p = put_u32(p, cov[i].max, '\n');
+		if (p - buf > BLOCK - LINE_MAX_BYTES) { ok = fwrite(buf, 1, (size_t)(p - buf), fo) == (size_t)(p - buf); p = buf; }
+	}
+	if (ok && p != buf) ok = fwrite(buf, 1, (size_t)(p - buf), fo) == (size_t)(p - buf);
+	free(buf);
+	if (fclose(fo) != 0) ok = 0;
+	if (!ok) fprintf(stderr, "sdt-kmers: write to %s failed\n", path);
+	return ok ? 0 : -1;
+}
+
+typedef struct { char **text; uint64_t *keys; uint64_t n, cap; } query_set;
+
+/* one k-mer per line, letters ACGT (either case), exactly K of them; blank lines are skipped.  Base codes A0 C1 T2 G3. */
+static int load_queries(const char *path, int K, int nw, query_set *q)
+{
+	FILE *fi = fopen(path, "r");
+	if (!fi) { fprintf(stderr, "sdt-kmers: cannot open %s\n", path); return 2; }
+	char *line = NULL;
+	size_t cap = 0;
+	unsigned long long lineno = 0;
+	memset(q, 0, sizeof *q);
+	while (getline(&line, &cap, fi) >= 0) {
+		lineno++;
+		size_t len = strlen(line);
+		while (len && (line[len - 1] == '\n' || line[len - 1] == '\r' || line[len - 1] == ' ' || line[len - 1] == '\t')) line[--len] = 0;
+		if (!len) continue;
+		if (len != (size_t)K) {
+			fprintf(stderr, "sdt-kmers: %s line %llu: the k-mer has %zu letters, K is %d\n", path, lineno, len, K);
+			fclose(fi);
+			return 2;
+		}
+		if (q->n == q->cap) {
+			q->cap = q->cap ? 2 * q->cap : 1024;
+			q->text = (char **)realloc(q->text, q->cap * sizeof(char *));
+			q->keys = (uint64_t *)realloc(q->keys, q->cap * (size_t)nw * sizeof(uint64_t));
+			if (!q->text || !q->keys) { fprintf(stderr, "sdt-kmers: out of memory\n"); fclose(fi); return 1; }
+		}
+		uint64_t *key = q->keys + q->n * (size_t)nw;
+		memset(key, 0, (size_t)nw * sizeof(uint64_t));
+		for (int i = 0; i < K; i++) {
+			int code;
+			switch (line[i]) {
+			case 'A': case 'a': code = 0; break;
+			case 'C': case 'c': code = 1; break;
+			case 'T': case 't': code = 2; break;
+			case 'G': case 'g': code = 3; break;
+			default:
+				fprintf(stderr, "sdt-kmers: %s line %llu: '%c' at position %d is not one of ACGT\n", path, lineno, line[i], i + 1);
+				fclose(fi);
+				return 2;
+			}
+			const int bit = 2 * (K - 1 - i);                     /* first base in the most significant pair, words most significant first */
+			key[nw - 1 - bit / 64] |= (uint64_t)code << (bit % 64);
+		}
+		q->text[q->n++] = strdup(line);
+	}
+	free(line);
+	fclose(fi);
+	return 0;
+}
+
+int main(int argc, char **argv)
+{
+	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0)) { usage(); return 255; }
+	const int do_query = strcmp(argv[1], "query") == 0;
+	char cfgfile[4096] = "", outname[4096] = "", qfile[4096] = "";
+	int K = 23, threads = 8, d = 0, max_k = 0, device = 0, c;
+	unsigned long min_count = 0;
+	static struct option longopts[] = {{"max-k", required_argument, 0, 1000}, {"device", required_argument, 0, 1001}, {0, 0, 0, 0}};
+	argv++; argc--;
+	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:", longopts, NULL)) != -1) {
+		switch (c) {
+		case 's': snprintf(cfgfile, sizeof cfgfile, "%s", optarg); break;
+		case 'o': snprintf(outname, sizeof outname, "%s", optarg); break;
+		case 'q': snprintf(qfile, sizeof qfile, "%s", optarg); break;
+		case 'K': K = atoi(optarg); break;
+		case 'p': threads = atoi(optarg) > 0 ? atoi(optarg) : 1; break;
+		case 'd': d = atoi(optarg) >= 0 ? atoi(optarg) : 0; break;           /* pregraph.c:159 */
+		case 'c': min_count = strtoul(optarg, NULL, 10); break;
+		case 1000: max_k = atoi(optarg); break;
+		case 1001: device = atoi(optarg); break;
+		default: usage(); return 255;
+		}
+	}
+	if (!cfgfile[0] || (do_query ? !qfile[0] : !outname[0])) { usage(); return 255; }
+	if (max_k == 0) max_k = K <= 31 ? 31 : SDT_MAX_K;
+	if (d > 127) d = (signed char)d;                                         /* deLowKmer is a char */
+	/* pregraph.c:38-59 */
+	if (K % 2 == 0) { K++; printf("K should be an odd number\n"); }
+	if (K < 13) { K = 13; printf("K should not be less than 13\n"); }
+	else if (K > max_k) K = max_k;
+	const int nw = K <= 31 ? 1 : (K <= 63 ? 2 : 4);
+
+	query_set qs;
+	memset(&qs, 0, sizeof qs);
+	if (do_query) {
+		const int rq = load_queries(qfile, K, nw, &qs);
+		if (rq != 0) return rq;
+	}
+	sdt_cfg cfg;
+	if (sdt_cfg_load(cfgfile, &cfg) != 0) return 255;
+	const int max_read_len = cfg.max_rd_len ? cfg.max_rd_len : 100;         /* prlHashReads.c:361-364 */
+
+	sdt_ctx *gpu = NULL;
+	if (sdt_gpu_init(&gpu, device, K, 0, do_query ? 0u : SDT_FLAG_KEEP_READS) != SDT_OK) {
+		fprintf(stderr, "sdt_gpu_init: %s\n", sdt_gpu_last_error());
+		return 1;
+	}
+	push_state st = {gpu, 0};
+	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
+	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : threads;
+	sdt_pool_enable(sdt_gpu_host_alloc, sdt_gpu_host_free, parse_threads + PUSH_DEPTH + 8);
+	int rc = sdt_stream_reads(&cfg, max_read_len, parse_threads > 0 ? parse_threads : 1, chunk, 0, push_batch, &st, NULL);
+	if (rc == 0 && inflight_retire(gpu, 0) != 0) rc = -1;
+	sdt_pool_disable();
+	if (rc != 0) { sdt_gpu_destroy(gpu); return 1; }
+	uint64_t kmers = 0, nodes = 0, removed = 0;
+	if (sdt_gpu_finish_count(gpu, &kmers, &nodes) != SDT_OK) { fprintf(stderr, "sdt_gpu_finish_count: %s\n", sdt_gpu_last_error()); return 1; }
+	printf("%llu reads, %llu nodes allocated, %llu kmer in reads\n", st.reads, (unsigned long long)nodes, (unsigned long long)kmers);
+	if (d && sdt_gpu_delow(gpu, d, &removed) != SDT_OK) { fprintf(stderr, "sdt_gpu_delow: %s\n", sdt_gpu_last_error()); return 1; }
+	if (d) printf("%llu kmer removed\n", (unsigned long long)removed);
+
+	if (!do_query) {
+		char path[4200];
+		snprintf(path, sizeof path, "%s.readCov", outname);
+		sdt_read_cov *cov = (sdt_read_cov *)calloc(st.reads ? st.reads : 1, sizeof(sdt_read_cov));
+		if (!cov) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", st.reads); return 1; }
+		uint64_t got = 0;
+		if (sdt_gpu_profile_kept_reads(gpu, (uint32_t)min_count, cov, st.reads, &got) != SDT_OK) {
+			fprintf(stderr, "sdt_gpu_profile_kept_reads: %s\n", sdt_gpu_last_error());
+			return 1;
+		}
+		if (got != st.reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu profiled\n", st.reads, (unsigned long long)got); return 1; }
+		if (write_read_cov(path, cov, st.reads) != 0) return 1;
+		printf("%llu reads profiled into %s\n", st.reads, path);
+		free(cov);
+	} else {
+		/* `linear` is thread_mark's flag (prlHashReads.c:911-967): marked on the table as it is now */
+		int64_t hist[257];
+		uint64_t linear = 0;
+		if (sdt_gpu_mark_and_hist(gpu, hist, &linear) != SDT_OK) { fprintf(stderr, "sdt_gpu_mark_and_hist: %s\n", sdt_gpu_last_error()); return 1; }
+		const uint64_t n = qs.n, m = n ? n : 1;
+		uint32_t *cnt = (uint32_t *)calloc(m, 4), *ll = (uint32_t *)calloc(m, 4), *rf = (uint32_t *)calloc(m, 4);
+		uint8_t *stt = (uint8_t *)calloc(m, 1);
+		if (!cnt || !ll || !rf || !stt) { fprintf(stderr, "sdt-kmers: out of memory\n"); return 1; }
+		if (sdt_gpu_search_kmers(gpu, qs.keys, n, cnt, ll, rf, stt) != SDT_OK) { fprintf(stderr, "sdt_gpu_search_kmers: %s\n", sdt_gpu_last_error()); return 1; }
+		FILE *fo = outname[0] ? fopen(outname, "w") : stdout;
+		if (!fo) { fprintf(stderr, "sdt-kmers: cannot write %s\n", outname); return 1; }
+		for (uint64_t i = 0; i < n; i++)
+			fprintf(fo, "%s\t%d\t%c\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", qs.text[i], stt[i] & 1, (stt[i] & 2) ? '-' : '+', cnt[i],
+			        ll[i] & 63u, (ll[i] >> 6) & 63u, (ll[i] >> 12) & 63u, (ll[i] >> 18) & 63u,
+			        rf[i] & 63u, (rf[i] >> 6) & 63u, (rf[i] >> 12) & 63u, (rf[i] >> 18) & 63u, (rf[i] >> 24) & 1u, (rf[i] >> 25) & 1u);
+		if (fo != stdout && fclose(fo) != 0) { fprintf(stderr, "sdt-kmers: write to %s failed\n", outname); return 1; }
+		free(cnt); free(ll); free(rf); free(stt);
+	}
+	sdt_gpu_destroy(gpu);
+	sdt_cfg_free(&cfg);
+	return 0;
+}

@@ -4,6 +4,7 @@
 //   sdt_sharded.hip   multi-GPU: the exchange of level-1 chunks between the ranks, communicator glue
 //   sdt_pass2.hip     second read pass (prlRead2edge): path words, patch table, k_map_reads, arcs
 //   sdt_mapstage.hip  the map stage (prlContig2nodes / prlRead2Ctg)
+//   sdt_search.hip    read-only questions to the counted table: batch k-mer search, per-read k-mer coverage
 //   sdt_gpu_graph.hip the graph phases (own view of the context: sdt_internal.hpp GraphView)
 // Not part of the ABI: nothing here is visible to a caller of libsdt_gpu.so.
 #pragma once
@@ -150,6 +151,12 @@ struct sdt_ctx {
 	size_t ab_cap[5] = {0, 0, 0, 0, 0};
 	unsigned long long *d_hit_cursor = nullptr;
 	bool index_final = false;            // k_finalize_contig_index has run: look-ups only from here on
+	// k-mer search and read profiles (sdt_search.hip): the high halves of the counts past 65 535 as a small hash keyed by slot,
+	// valid for one state of the table (hi_mode < 0: to be collected again -- every call that can move or count a node says so)
+	uint64_t *d_hi = nullptr;
+	uint64_t hi_slots = 0;
+	int hi_mode = -1;
+	unsigned long long *d_cov_flags = nullptr;      // [0] reads longer than promised, [1] slots with a high half
 	// timing
 	std::vector<EventPair> ev;
 	size_t ev_used = 0;
@@ -176,6 +183,9 @@ inline size_t entry_bytes(int nw) { return nw == 1 ? sizeof(Entry<1>) : nw == 2 
 
 inline int scan_grid(const sdt_ctx *c, uint64_t items) { return sdti::scan_grid(c->cu_count, items); }
 
+
+// the table is about to change (nodes counted, moved or replaced): what sdt_search.hip derived from it is stale
+inline void search_cache_drop(sdt_ctx *c) { c->hi_mode = -1; }
 
 inline int env_int(const char *name, int dflt) { const char *v = getenv(name); return v && *v ? atoi(v) : dflt; }
 inline int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }

@@ -12,6 +12,7 @@
 //   k_mark_hist<NW>       thread_mark    (prlHashReads.c:911-967) + per-thread kmerFreq bins
 //   k_export<NW>          compaction of the table into kmer_t-shaped arrays (inc/newhash.h:65-77)
 //   k_rehash<NW>          table growth (the analogue of encap_kmerset, newhash.c:293-409)
+//   (k_search_kmers / k_profile_reads, the read-only look-ups of search_kmerset, newhash.c:239-283: sdt_search.hip)
 #include "sdt_ctx.hpp"
 #include "sdt_pipeline.hpp"
 #include "sdt_table_kernels.cuh"
@@ -143,6 +144,7 @@ int grow_table(sdt_ctx *c, uint64_t need_nodes)
 	// (any number of slots: what the nodes need at the load a fresh table is sized for, at least half as many again as before)
 	uint64_t slots = flat_slots_for(need_nodes);
 	if (slots < c->slots + c->slots / 2) slots = c->slots + c->slots / 2;
+	search_cache_drop(c);
 	void *ent = nullptr;
 	uint32_t *aux = nullptr;
 	uint64_t *first = nullptr;
@@ -342,6 +344,8 @@ int sdt_gpu_destroy(sdt_ctx *c)
 	if (c->d_ctg_len) (void)hipFree(c->d_ctg_len);
 	if (c->d_ctg_twin) (void)hipFree(c->d_ctg_twin);
 	if (c->d_hit_cursor) (void)hipFree(c->d_hit_cursor);
+	if (c->d_hi) (void)hipFree(c->d_hi);
+	if (c->d_cov_flags) (void)hipFree(c->d_cov_flags);
 	for (int i = 0; i < 5; i++) if (c->ab[i]) (void)hipFree(c->ab[i]);
 	sk_free(c);
 	shard_free(c);
@@ -364,6 +368,7 @@ int sdt_gpu_reset(sdt_ctx *c)
 	if (rc != SDT_OK)
 		return rc;
 	HIPCHK(hipMemsetAsync(c->d_stats, 0, sizeof(Stats), c->stream));
+	search_cache_drop(c);
 	c->sk.l2_in_total = 0;
 	c->sk.stream_flushes = 0;
 	c->sk.exchanged = false;
@@ -461,6 +466,7 @@ static int launch_count(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_o
 		return SDT_OK;
 	if (max_read_len < (uint64_t)c->K + 1)
 		return SDT_OK;                               // no read can hold a k-mer (prlHashReads.c:592)
+	search_cache_drop(c);
 	const int mtw = tile_words_for(max_read_len);
 	const size_t smem = tile_smem_bytes(mtw);
 	if (smem > 64 * 1024)
@@ -868,6 +874,7 @@ int sdt_gpu_release_table(sdt_ctx *c)
 	HIPCHK(hipSetDevice(c->device));
 	int rc = sdti::release_pass1(c);                 // drains pass 1; the pools go back
 	if (rc != SDT_OK) return rc;
+	search_cache_drop(c);
 	HIPCHK(hipStreamSynchronize(c->stream));
 	if (c->d_ent) (void)hipFree(c->d_ent);
 	if (c->d_aux) (void)hipFree(c->d_aux);
@@ -920,6 +927,7 @@ int sdt_gpu_import_nodes(sdt_ctx *c, const uint64_t *keys, const uint32_t *l_lin
 	HIPCHK(hipSetDevice(c->device));
 	int rc = sync_stats(c);
 	if (rc != SDT_OK) return rc;
+	search_cache_drop(c);
 	if ((double)(c->distinct_known + n) > (double)c->slots * MAX_LOAD) {
 		rc = grow_table(c, c->distinct_known + n);
 		if (rc != SDT_OK) return rc;

@@ -51,6 +51,7 @@ int sdt_gpu_load_paths(sdt_ctx *c, const uint64_t *keys, const uint64_t *path_wo
 	}
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->stream));
+	search_cache_drop(c);                            // the counters make way for the path words
 	uint64_t *d_k = nullptr, *d_i = nullptr;
 	if (n) {
 		if (!by_index) HIPCHK(hipMalloc((void **)&d_k, n * c->nw * sizeof(uint64_t)));
@@ -151,6 +152,7 @@ int sdt_gpu_import_paths(sdt_ctx *c, const uint64_t *keys, const uint64_t *path_
 	HIPCHK(hipSetDevice(c->device));
 	int rc = sync_stats(c);
 	if (rc != SDT_OK) return rc;
+	search_cache_drop(c);
 	// the table of this rank's shard makes way (the reads kept for the second pass stay): an empty flat table with room for the graph
 	if (c->d_idx) { (void)hipFree(c->d_idx); c->d_idx = nullptr; c->idx_slots = c->idx_n = 0; }
 	const uint64_t want = flat_slots_for(n);
