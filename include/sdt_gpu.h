@@ -250,7 +250,9 @@ int sdt_gpu_release_table(sdt_ctx *ctx);
  * search1kmerPlus (:575-615) and the arc counting (:190-241,415-430) over the kept reads; export_arcs returns
  * every arc with its multiplicity and the ordinal of its first appearance ((read ordinal << 16) | item index):
  * per from-edge the reference prints arcs most-recent-first-appearance first (:427-428,472-496) -- the arrays come in that order
- * (from ascending, first appearance descending) since round 5. */
+ * (from ascending, first appearance descending) since round 5.
+ * SDT_ESTATE from load_paths / import_paths: a key that is not in the table / a key twice (the message says how many).  The nodes
+ * that were found have their path words by then, but the context is not poisoned: the same call with the right keys succeeds. */
 int sdt_gpu_load_paths(sdt_ctx *ctx, const uint64_t *keys, const uint64_t *path_words, uint64_t n,
                        const uint64_t *patch_keys, const uint64_t *patch_info, uint64_t npatch, uint64_t num_ed);
 int sdt_gpu_map_reads(sdt_ctx *ctx, uint64_t *reads_processed, uint64_t *arcs);

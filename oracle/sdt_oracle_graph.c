@@ -705,6 +705,53 @@ uint64_t sdto_read2edge(sdto_sets *S, const uint8_t *codes, const uint64_t *offs
 	return narcs;
 }
 
+/* ---- the state sdto_read2edge works from, node by node and patch entry by patch entry: a test reads it back after
+ * sdto_write_edges, or sets one of its own making (every node a chosen class and label) and runs sdto_read2edge on that ---- */
+
+/* what kmer2edges leaves in a node for the second read pass: l_links = edge id (all 32 bits), twin, inEdge */
+void sdto_node_set_edge(sdto_sets *S, const uint64_t key4[4], uint32_t l_links, int twin, int in_edge)
+{
+	sdto_node *n = node_of(S, key4);
+	n->l_links = l_links;
+	n->pad = (uint8_t)((twin & 3) | (in_edge ? 4 : 0));
+}
+
+void sdto_node_get_edge(sdto_sets *S, const uint64_t key4[4], uint32_t *l_links, int *twin, int *in_edge)
+{
+	const sdto_node *n = node_of(S, key4);
+	*l_links = n->l_links;
+	*twin = ND_TWIN(n);
+	*in_edge = ND_INEDGE(n);
+}
+
+/* one entry of KmerSetsPatch: the canonical (K+1)-mer of a length-1 edge -> edge id, twin */
+void sdto_patch_put(sdto_sets *S, const uint64_t key4[4], uint32_t edge, int twin)
+{
+	sdto_kmer k;
+	memcpy(k.w, key4, sizeof k.w);
+	patch_put(S, &k, edge, twin);
+}
+
+uint64_t sdto_patch_count(const sdto_sets *S) { return S->patch_n; }
+
+/* every patch entry (table order) into arrays of sdto_patch_count() entries; returns how many there are */
+uint64_t sdto_patch_export(const sdto_sets *S, uint64_t *keys4, uint32_t *edge, uint8_t *twin)
+{
+	const sdto_patch *t = (const sdto_patch *)S->patch;
+	uint64_t n = 0;
+	for (uint64_t i = 0; t && i < S->patch_cap; i++) {
+		if (!t[i].used) continue;
+		memcpy(keys4 + 4 * n, t[i].key.w, 32);
+		edge[n] = t[i].edge;
+		twin[n] = t[i].twin;
+		n++;
+	}
+	return n;
+}
+
+void sdto_set_num_ed(sdto_sets *S, uint64_t num_ed) { S->num_ed = num_ed; }
+uint64_t sdto_get_num_ed(const sdto_sets *S) { return S->num_ed; }
+
 uint64_t sdto_write_vertex(const sdto_sets *S, const char *path)
 {
 	FILE *fp = fopen(path, "w");

@@ -553,6 +553,76 @@ class PregraphGPU:
     def set_read_ordinal(self, base: int, stride: int = 1):
         self._check(self.lib.sdt_gpu_set_read_ordinal(self._ctx, base, stride))
 
+    # -- pass 2: reads -> edge paths -> arcs (prlRead2edge); see include/sdt_gpu.h for the path word and the patch table
+    def _patch_args(self, patch_keys, patch_info):
+        if patch_keys is None or len(patch_keys) == 0:
+            return None, None, 0
+        patch_keys = np.ascontiguousarray(patch_keys, dtype=np.uint64).reshape(-1, self.nw)
+        patch_info = np.ascontiguousarray(patch_info, dtype=np.uint64)
+        assert len(patch_keys) == len(patch_info)
+        return patch_keys, patch_info, len(patch_info)
+
+    def load_paths(self, keys, path_words, patch_keys=None, patch_info=None, num_ed: int = 0, n: int = None):
+        """keys None: path_words[i] belongs to node i of set_node_index / layout_apply; path_words None as well: the path words
+        build_edges left on the device, for the n nodes of the numbering (default: all of them)"""
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, self.nw)
+        if path_words is not None:
+            path_words = np.ascontiguousarray(path_words, dtype=np.uint64)
+            assert keys is None or len(keys) == len(path_words)
+            n = len(path_words)
+        elif n is None:
+            n = getattr(self, "_nidx", 0)
+        pk, pi, npatch = self._patch_args(patch_keys, patch_info)
+        self._check(self.lib.sdt_gpu_load_paths(self._ctx, _ptr(keys), _ptr(path_words), n, _ptr(pk), _ptr(pi), npatch, num_ed))
+
+    def map_reads(self):
+        """-> (kept reads the pass went over, distinct arcs)"""
+        reads, arcs = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_map_reads(self._ctx, ctypes.byref(reads), ctypes.byref(arcs)))
+        self._narcs = arcs.value
+        return reads.value, arcs.value
+
+    def export_arcs(self, max_arcs: int = None):
+        """-> (from, to, mult uint32[n], first uint64[n]) in *.preArc's order; max_arcs: the capacity to offer (default: what the
+        last map_reads counted)"""
+        if max_arcs is None:
+            max_arcs = self._narcs
+        m = max(max_arcs, 1)
+        fr, to, mult = (np.zeros(m, dtype=np.uint32) for _ in range(3))
+        first = np.zeros(m, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_export_arcs(self._ctx, _ptr(fr), _ptr(to), _ptr(mult), _ptr(first), max_arcs, ctypes.byref(n)))
+        return fr[: n.value], to[: n.value], mult[: n.value], first[: n.value]
+
+    def export_paths(self):
+        """-> (keys uint64[n, nw], path_words uint64[n]) of every node, after load_paths"""
+        n = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_export_paths(self._ctx, None, None, 0, ctypes.byref(n)))
+        m = max(n.value, 1)
+        keys = np.zeros((m, self.nw), dtype=np.uint64)
+        words = np.zeros(m, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_export_paths(self._ctx, _ptr(keys), _ptr(words), m, ctypes.byref(n)))
+        return keys[: n.value], words[: n.value]
+
+    def import_paths(self, keys, path_words, patch_keys=None, patch_info=None, num_ed: int = 0):
+        """the whole graph into a context that holds (its share of) the reads: the table it had makes way"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, self.nw)
+        path_words = np.ascontiguousarray(path_words, dtype=np.uint64)
+        assert len(keys) == len(path_words)
+        pk, pi, npatch = self._patch_args(patch_keys, patch_info)
+        self._check(self.lib.sdt_gpu_import_paths(self._ctx, _ptr(keys), _ptr(path_words), len(path_words), _ptr(pk), _ptr(pi), npatch,
+                                                  num_ed))
+
+    def keep_reads(self, words: np.ndarray, offsets: np.ndarray):
+        """keep a batch resident for map_reads without counting it (ordinals from set_read_ordinal, as for a push)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_keep_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), offsets.size - 1))
+
+    def release_table(self):
+        self._check(self.lib.sdt_gpu_release_table(self._ctx))
+
     # -- introspection
     def table_slots(self) -> int:
         return self.lib.sdt_gpu_table_slots(self._ctx)

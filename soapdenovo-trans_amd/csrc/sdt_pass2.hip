@@ -94,8 +94,18 @@ int sdt_gpu_load_paths(sdt_ctx *c, const uint64_t *keys, const uint64_t *path_wo
 	HIPCHK(hipMalloc((void **)&c->d_arcs, slots * sizeof(ArcEnt)));
 	c->arc_slots = slots;
 	rc = sync_stats(c);
-	if (rc != SDT_OK)
-		return fail(SDT_ESTATE, "sdt_gpu_load_paths: %llu nodes are not in the table", (unsigned long long)c->h_stats->probe_fail);
+	if (rc != SDT_OK) {
+		// The counter is this call's (a probe that failed in pass 1 ended pass 1: sdt_gpu_finish_count reports it); left set it
+		// would fail every later look at the counters, a correct sdt_gpu_load_paths / sdt_gpu_import_paths included.
+		const unsigned long long missing = c->h_stats->probe_fail;
+		if (missing) {
+			c->h_stats->probe_fail = 0;
+			HIPCHK(hipMemsetAsync(&c->d_stats->probe_fail, 0, sizeof(unsigned long long), c->stream));
+			HIPCHK(hipStreamSynchronize(c->stream));
+			return fail(SDT_ESTATE, "sdt_gpu_load_paths: %llu nodes are not in the table", missing);
+		}
+		return rc;
+	}
 	c->paths_loaded = true;
 	return SDT_OK;
 }

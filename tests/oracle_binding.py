@@ -109,6 +109,24 @@ def lib():
     L.sdto_write_edges.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.sdto_read2edge.restype = C.c_uint64
     L.sdto_read2edge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p]
+    L.sdto_kmer_plus.restype = Kmer
+    L.sdto_kmer_plus.argtypes = [Kmer, C.c_int]
+    L.sdto_rc_kplus1.restype = Kmer
+    L.sdto_rc_kplus1.argtypes = [Kmer, C.c_int, C.c_int]
+    L.sdto_node_set_edge.restype = None
+    L.sdto_node_set_edge.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int]
+    L.sdto_node_get_edge.restype = None
+    L.sdto_node_get_edge.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.sdto_patch_put.restype = None
+    L.sdto_patch_put.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
+    L.sdto_patch_count.restype = C.c_uint64
+    L.sdto_patch_count.argtypes = [C.c_void_p]
+    L.sdto_patch_export.restype = C.c_uint64
+    L.sdto_patch_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sdto_set_num_ed.restype = None
+    L.sdto_set_num_ed.argtypes = [C.c_void_p, C.c_uint64]
+    L.sdto_get_num_ed.restype = C.c_uint64
+    L.sdto_get_num_ed.argtypes = [C.c_void_p]
     L.sdto_edge_port.restype = C.c_int
     L.sdto_edge_port.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     _lib = L
@@ -192,6 +210,73 @@ class Oracle:
 
     def write_vertex(self, path):
         return self.L.sdto_write_vertex(self.h, path.encode())
+
+    # the state read2edge works from, piece by piece (oracle/sdt_oracle.h): a test reads it back after write_edges or sets its own
+    def node_set_edge(self, key_row, l_links, twin, in_edge):
+        """what kmer2edges leaves in a node: edge id (all 32 bits of l_links), twin, inEdge.  After node_set, which masks l_links."""
+        k = self._key4(key_row)
+        self.L.sdto_node_set_edge(self.h, k.ctypes.data, int(l_links), int(twin), int(in_edge))
+
+    def node_get_edge(self, key_row):
+        """-> (l_links, twin, inEdge)"""
+        k, l, t, e = self._key4(key_row), C.c_uint32(), C.c_int(), C.c_int()
+        self.L.sdto_node_get_edge(self.h, k.ctypes.data, C.byref(l), C.byref(t), C.byref(e))
+        return l.value, t.value, e.value
+
+    def set_node_states(self, keys4, linear, deleted, l_links, twin, in_edge):
+        """node_set (links 0: the second read pass reads none) + node_set_edge for every row of keys4 uint64[n, 4]"""
+        keys4 = np.ascontiguousarray(keys4, dtype=np.uint64).reshape(-1, 4)
+        a = keys4.ctypes.data
+        ns, ne, h = self.L.sdto_node_set, self.L.sdto_node_set_edge, self.h
+        for i, (li, de, ll, tw, ie) in enumerate(zip(linear.tolist(), deleted.tolist(), l_links.tolist(), twin.tolist(), in_edge.tolist())):
+            ns(h, a + 32 * i, 0, 0, li, de)
+            ne(h, a + 32 * i, ll, tw, ie)
+
+    def get_node_states(self):
+        """every node in export order -> (keys4, linear, deleted, l_links, twin, inEdge)"""
+        keys4, _, _, _, fl = self.export()
+        keys4 = np.ascontiguousarray(keys4)
+        n = len(keys4)
+        ll, tw, ie = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        for i in range(n):
+            ll[i], tw[i], ie[i] = self.node_get_edge(keys4[i])
+        return keys4, fl & 1, fl >> 1 & 1, ll, tw, ie
+
+    def patch_put(self, key_row, edge, twin):
+        """one (K+1)-mer of the patch table: key = the canonical (K+1)-mer (kmer_plus / rc_kplus1), 4 words or the last nw"""
+        k = self._key4(key_row)
+        self.L.sdto_patch_put(self.h, k.ctypes.data, int(edge), int(twin))
+
+    def patch_export(self):
+        """-> (keys4 uint64[n, 4], edge uint32[n], twin uint8[n])"""
+        n = self.L.sdto_patch_count(self.h)
+        keys = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        edge, twin = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint8)
+        assert self.L.sdto_patch_export(self.h, keys.ctypes.data, edge.ctypes.data, twin.ctypes.data) == n
+        return keys[:n], edge[:n], twin[:n]
+
+    def set_num_ed(self, num_ed):
+        self.L.sdto_set_num_ed(self.h, int(num_ed))
+
+    def num_ed(self):
+        return self.L.sdto_get_num_ed(self.h)
+
+    def canonical_kplus1(self, prev_words4, ch):
+        """the (K+1)-mer prev + ch as the second read pass looks it up: (canonical key as 4 words, 1 when prev + ch itself is the
+        smaller strand) -- kmer_plus, rc_kplus1 (with the K = 127 quirk) and kmer_smaller of the oracle itself"""
+        wp = self.L.sdto_kmer_plus(Kmer.of(prev_words4), int(ch))
+        bal = self.L.sdto_rc_kplus1(wp, self.K, self.nw)
+        return (wp.tup(), 1) if self.L.sdto_kmer_smaller(wp, bal) else (bal.tup(), 0)
+
+    def read2edge_arcs(self, codes, offs, path):
+        """read2edge, and the *.preArc it wrote parsed: (arcs the call counted, [(from, to, mult), ...] in file order)"""
+        n = self.read2edge(codes, offs, path)
+        arcs = []
+        with open(path) as f:
+            for line in f:
+                t = line.split()
+                arcs += [(int(t[0]), int(t[i]), int(t[i + 1])) for i in range(1, len(t), 2)]
+        return n, arcs
 
     # read-only probes of the cleaning passes (oracle/sdt_oracle_graph.c): the device dry runs are compared with them.
     # Keys are rows of 4 uint64, most significant first (the export layout).

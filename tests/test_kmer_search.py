@@ -446,13 +446,13 @@ def test_state_errors(pkg, synth):
         g.profile_reads_device(d_w, d_o, n, 100, 0, out)
         assert (out.cpu().numpy().view(np.uint32)[:, 0] == 100 - K + 1).all()
         # path words in place of the counters
-        g._check(g.lib.sdt_gpu_load_paths(g._ctx, None, None, 0, None, None, 0, 0))
+        g.load_paths(None, None, None, None, 0)
         assert_state_error(pkg, g, words, offs)
     # the table released
     with pkg.PregraphGPU(K, est_distinct=1 << 16, flags=pkg.SDT_FLAG_KEEP_READS) as g:
         g.push_reads(words, offs)
         g.finish_count()
-        g._check(g.lib.sdt_gpu_release_table(g._ctx))
+        g.release_table()
         assert_state_error(pkg, g, words, offs)
     # reads were not kept
     with pkg.PregraphGPU(K, est_distinct=1 << 16) as g:
