@@ -449,8 +449,42 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  * cutting calls the answers describe the table as it is then.  SDT_ESTATE: batches pushed or counted and not yet drained; after
  * sdt_gpu_load_paths / sdt_gpu_import_paths (the counters hold path words); after sdt_gpu_release_table; on a
  * SDT_FLAG_CONTIG_INDEX context; on a context with a communicator (a shard cannot tell "absent" from "another rank's
- * bucket").  n == 0 / nreads == 0: SDT_OK, nothing touched.  The calls never write the table. */
+ * bucket").  n == 0 / nreads == 0: SDT_OK, nothing touched.  The calls never write the table.
+ *
+ * Substitution errors corrected against the table (k-mer-spectrum correction, the usual step in front of a de Bruijn assembler).
+ * Added without a change of SDT_ABI_VERSION: the five calls and sdt_read_fix are additions, nothing that existed has changed.
+ * The rule is deterministic and decides every read on its own.  A read has n = len - K + 1 k-mers (0 for len < K) with the counts
+ * c[j] that profile_reads sees (absent = 0; the deleted flag is ignored).  k-mer j is WEAK iff c[j] < min_count; a RUN is a maximal
+ * stretch [a, b] of weak k-mers, l = b - a + 1.  Every run is judged on the read as it came (a substitution at p changes only
+ * k-mers of its own run):
+ *     a == 0 && b == n - 1  (nothing solid in the read)   no candidate
+ *     a > 0 && b < n - 1    (interior)                    candidate iff l == K;  p = b
+ *     a == 0 && b < n - 1   (head)                        candidate iff l <= K;  p = b
+ *     a > 0 && b == n - 1   (tail)                        candidate iff l <= K;  p = a + K - 1
+ * For a candidate each base x != read[p] is tried: x is valid iff every k-mer j in [a, b] of the read with base p replaced by x
+ * has a count >= min_count.  Exactly one valid x: base p becomes x.  None or several: the read stays as it is.  min_count == 0:
+ * nothing is weak, nothing changes.
+ *   correct_reads:  fix[i] for read i of a batch (packed as for sdt_gpu_push_reads): kmers as sdt_read_cov, weak k-mers before the
+ *                   correction, runs, substitutions made.  out_words (may be NULL): nwords words, the stream with the substitutions
+ *                   made (pad words as they came).  edits (may be NULL): one word per substitution,
+ *                       read << 18 | pos << 2 | new_base      (pos 0-based, < 65536; read = index in the batch)
+ *                   ascending, i.e. by read, then by position; *n_edits = substitutions made.  SDT_EFULL when there are more than
+ *                   max_edits: *n_edits says how many, the first max_edits are stored, fix[] and out_words are complete.
+ *                   (The host and kept forms do not know the number of edits of a piece beforehand: a piece with more edits than
+ *                   its device list holds runs the kernel a second time with a list of the size the first run asked for.)
+ *   correct_reads_device: buffers already on the device; d_out_words must not overlap the input; d_edits in no particular order.
+ *                   max_read_len as for profile_reads_device: a longer read gets kmers = 0xFFFFFFFF (other fields 0), stays as it
+ *                   is in d_out_words, and the call returns SDT_EINVAL.  The call waits for the kernel to know *n_edits.
+ *   correct_kept_reads: the reads kept in HBM; fix[] by READ ORDINAL like profile_kept_reads (SDT_EFULL, nothing written, when a
+ *                   kept read's ordinal is >= out_capacity), edits ascending with the read ordinal in the place of the index.  The
+ *                   kept reads are NOT changed: fetch them and apply the edits.
+ *   kept_batches / fetch_kept_batch: the kept batches back on the host, in the order they were kept: info = nwords, nreads,
+ *                   ord_base, ord_stride; words / offsets NULL: info only.  Needs kept reads, not a table: SDT_ESTATE without
+ *                   them, SDT_EINVAL for i out of range, SDT_EFULL when a capacity is too small, SDT_ESTATE (info
+ *                   included) while pushed batches are not drained (sdt_gpu_finish_count): their copies may be in flight.
+ * State rules and return codes are those of the profile calls.  Nothing here writes the table or the kept reads. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
+typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -461,6 +495,17 @@ int sdt_gpu_profile_reads_device(sdt_ctx *ctx, const void *d_packed_words, const
                                  uint64_t max_read_len, uint32_t min_count, void *d_out);
 int sdt_gpu_profile_kept_reads(sdt_ctx *ctx, uint32_t min_count, sdt_read_cov *out, uint64_t out_capacity,
                                uint64_t *nreads);
+int sdt_gpu_correct_reads_device(sdt_ctx *ctx, const void *d_packed_words, uint64_t nwords, const void *d_offsets,
+                                 uint64_t nreads, uint64_t max_read_len, uint32_t min_count, void *d_fix,
+                                 void *d_out_words, void *d_edits, uint64_t max_edits, uint64_t *n_edits);
+int sdt_gpu_correct_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                          uint64_t nreads, uint32_t min_count, sdt_read_fix *fix, uint32_t *out_words,
+                          uint64_t *edits, uint64_t max_edits, uint64_t *n_edits);
+int sdt_gpu_correct_kept_reads(sdt_ctx *ctx, uint32_t min_count, sdt_read_fix *fix, uint64_t out_capacity,
+                               uint64_t *nreads, uint64_t *edits, uint64_t max_edits, uint64_t *n_edits);
+int sdt_gpu_kept_batches(const sdt_ctx *ctx, uint64_t *n);
+int sdt_gpu_fetch_kept_batch(sdt_ctx *ctx, uint64_t i, uint64_t info[4], uint32_t *words, uint64_t words_cap,
+                             uint64_t *offsets, uint64_t offsets_cap);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

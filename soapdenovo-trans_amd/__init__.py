@@ -122,12 +122,22 @@ _ABI = [
     ("sdt_gpu_profile_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p]),
     ("sdt_gpu_profile_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_uint32, _c.c_void_p]),
     ("sdt_gpu_profile_kept_reads", _c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_correct_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_uint32,
+                                                _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_correct_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p, _c.c_void_p,
+                                         _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_correct_kept_reads", _c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64), _c.c_void_p,
+                                              _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_kept_batches", _c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_fetch_kept_batch", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
 # sdt_read_cov (include/sdt_gpu.h): one record per read of a k-mer coverage profile
 READ_COV_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "found", "solid", "min", "median", "max")])
 COV_TOO_LONG = 0xFFFFFFFF
+# sdt_read_fix (include/sdt_gpu.h): one record per read of a correction; an edit is read << 18 | pos << 2 | new_base
+READ_FIX_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "weak", "runs", "fixed")])
 
 _lib = None
 
@@ -549,6 +559,72 @@ class PregraphGPU:
         n = ctypes.c_uint64()
         self._check(self.lib.sdt_gpu_profile_kept_reads(self._ctx, min_count, _ptr(out), total_reads, ctypes.byref(n)))
         return out, n.value
+
+    # -- substitution errors corrected against the counted table (the rule: include/sdt_gpu.h)
+    def correct_reads(self, words, offsets, min_count: int = 2):
+        """-> (READ_FIX_DTYPE[nreads]: kmers, weak, runs, fixed; the packed stream with the substitutions made; the edits uint64[],
+        read << 18 | pos << 2 | new_base, ascending)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        fix = np.zeros(n, dtype=READ_FIX_DTYPE)
+        out_words = words.copy()
+        cap = max(n // 4, 1024)
+        while True:
+            edits = np.zeros(cap, dtype=np.uint64)
+            got = ctypes.c_uint64()
+            rc = self.lib.sdt_gpu_correct_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, min_count, _ptr(fix), _ptr(out_words),
+                                                _ptr(edits), cap, ctypes.byref(got))
+            if rc == SDT_EFULL and got.value > cap:
+                cap = got.value
+                continue
+            self._check(rc)
+            return fix, out_words, edits[: got.value]
+
+    def correct_reads_device(self, d_words, nwords: int, d_offsets, nreads: int, max_read_len: int, min_count: int, d_fix,
+                             d_out_words=None, d_edits=None, max_edits: int = 0) -> int:
+        """device buffers; d_fix holds nreads records of 16 bytes, d_out_words (optional) nwords words, d_edits (optional) max_edits
+        words in no particular order -> the number of edits (SdtError SDT_EFULL past max_edits: e.needed says how many)"""
+        got = ctypes.c_uint64()
+        rc = self.lib.sdt_gpu_correct_reads_device(self._ctx, _ptr(d_words), nwords, _ptr(d_offsets), nreads, max_read_len, min_count,
+                                                   _ptr(d_fix), _ptr(d_out_words), _ptr(d_edits), max_edits, ctypes.byref(got))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.needed = got.value
+            raise e
+        return got.value
+
+    def correct_kept_reads(self, total_reads: int, min_count: int = 2, out: np.ndarray = None):
+        """the reads kept in HBM -> (READ_FIX_DTYPE[total_reads] by read ordinal, reads corrected, edits with the ordinal as `read`);
+        the kept reads themselves stay as they are: fetch_kept_batch + the edits give the corrected stream"""
+        if out is None:
+            out = np.zeros(total_reads, dtype=READ_FIX_DTYPE)
+        assert out.dtype == READ_FIX_DTYPE and out.flags.c_contiguous and len(out) >= total_reads
+        cap = max(total_reads // 4, 1024)
+        while True:
+            edits = np.zeros(cap, dtype=np.uint64)
+            n, got = ctypes.c_uint64(), ctypes.c_uint64()
+            rc = self.lib.sdt_gpu_correct_kept_reads(self._ctx, min_count, _ptr(out), total_reads, ctypes.byref(n), _ptr(edits), cap,
+                                                     ctypes.byref(got))
+            if rc == SDT_EFULL and got.value > cap:          # (an ordinal past total_reads is SDT_EFULL too, with no edits counted)
+                cap = got.value
+                continue
+            self._check(rc)
+            return out, n.value, edits[: got.value]
+
+    def kept_batches(self) -> int:
+        n = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_kept_batches(self._ctx, ctypes.byref(n)))
+        return n.value
+
+    def fetch_kept_batch(self, i: int):
+        """-> (words uint32[nwords], offsets uint64[nreads + 1], ord_base, ord_stride) of kept batch i, as it was pushed"""
+        info = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_fetch_kept_batch(self._ctx, i, _ptr(info), None, 0, None, 0))
+        words = np.zeros(int(info[0]), dtype=np.uint32)
+        offsets = np.zeros(int(info[1]) + 1, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_fetch_kept_batch(self._ctx, i, _ptr(info), _ptr(words), words.size, _ptr(offsets), offsets.size))
+        return words, offsets, int(info[2]), int(info[3])
 
     def set_read_ordinal(self, base: int, stride: int = 1):
         self._check(self.lib.sdt_gpu_set_read_ordinal(self._ctx, base, stride))

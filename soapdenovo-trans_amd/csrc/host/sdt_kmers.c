@@ -7,6 +7,12 @@
  *       per input line:  <kmer> <found 0|1> <strand +|-> <count> <l: A C T G> <r: A C T G> <linear> <deleted>   (sdt_gpu_search_kmers,
  *       the batch form of search_kmerset, newhash.c:239-283; links as the STORED node has them, strand - = stored as the reverse
  *       complement of the query)
+ *   sdt-kmers correct -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] -o prefix
+ *       substitution errors corrected against the counted table (sdt_gpu_correct_kept_reads; the rule: include/sdt_gpu.h), in stream
+ *       (ordinal) order, so paired files come out interleaved, read1 then read2:
+ *       prefix.readFix: one line per read:  kmers weak runs fixed
+ *       prefix.edits: one line per substitution, ascending:  read pos from to   (read = ordinal + 1, pos 1-based)
+ *       prefix.corrected.fa: every read of the stream, > ordinal + 1 and the sequence on one line (the letters of the 2-bit codes)
  *
  * The query file is read and checked before the device is touched. */
 #include <stdio.h>
@@ -29,6 +35,9 @@ static void usage(void)
 	        "           -> prefix.readCov, one line per read in stream order: kmers found solid min median max\n"
 	        "       sdt-kmers query   -s lib.cfg -K k [-p threads] [-d d] -q kmers.txt [-o out.tsv]\n"
 	        "           -> per line of kmers.txt: kmer found strand count l_A l_C l_T l_G r_A r_C r_T r_G linear deleted\n"
+	        "       sdt-kmers correct -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] -o prefix\n"
+	        "           -> prefix.readFix (per read: kmers weak runs fixed), prefix.edits (per substitution: read pos from to),\n"
+	        "              prefix.corrected.fa (every read, substitution errors corrected against the counted k-mers)\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -109,6 +118,146 @@ static int write_read_cov(const char *path, const sdt_read_cov *cov, unsigned lo
 	return ok ? 0 : -1;
 }
 
+/* text formatted by hand into a block buffer, as write_read_cov does */
+typedef struct { FILE *f; char *buf, *p; int ok; const char *path; } outbuf;
+enum { OB_BLOCK = 1 << 20 };
+
+static int ob_open(outbuf *o, const char *path)
+{
+	o->path = path;
+	o->f = fopen(path, "w");
+	if (!o->f) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path); return -1; }
+	o->buf = o->p = (char *)malloc(OB_BLOCK);
+	o->ok = 1;
+	if (!o->buf) { fprintf(stderr, "sdt-kmers: out of memory\n"); fclose(o->f); o->f = NULL; return -1; }
+	return 0;
+}
+
+/* room for `need` more bytes (need <= OB_BLOCK); after a failed write the block is dropped, never overrun: the caller stops on !ok */
+static void ob_room(outbuf *o, size_t need)
+{
+	if ((size_t)(o->p - o->buf) + need > OB_BLOCK) {
+		if (o->ok) o->ok = fwrite(o->buf, 1, (size_t)(o->p - o->buf), o->f) == (size_t)(o->p - o->buf);
+		o->p = o->buf;
+	}
+}
+
+static int ob_close(outbuf *o)
+{
+	if (o->ok && o->p != o->buf) o->ok = fwrite(o->buf, 1, (size_t)(o->p - o->buf), o->f) == (size_t)(o->p - o->buf);
+	free(o->buf);
+	if (fclose(o->f) != 0) o->ok = 0;
+	if (!o->ok) fprintf(stderr, "sdt-kmers: write to %s failed\n", o->path);
+	return o->ok ? 0 : -1;
+}
+
+static char *put_u64(char *p, uint64_t v, char sep)
+{
+	char t[20];
+	int n = 0;
+	do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
+	while (n) *p++ = t[--n];
+	*p++ = sep;
+	return p;
+}
+
+/* `correct`: the records and the edits from the device, the kept batches back from HBM, the edits applied here */
+static int correct_and_write(sdt_ctx *gpu, unsigned long long reads, uint32_t min_count, const char *prefix)
+{
+	static const char letters[4] = {'A', 'C', 'T', 'G'};
+	const uint64_t m = reads ? reads : 1;
+	sdt_read_fix *fix = (sdt_read_fix *)calloc(m, sizeof(sdt_read_fix));
+	/* (room for one edit per read at first: too little means the whole correction runs again just to hand over the edits) */
+	uint64_t cap = reads + 1024, n_edits = 0, got = 0, nb = 0;
+	uint64_t *edits = (uint64_t *)malloc(cap * sizeof(uint64_t));
+	if (!fix || !edits) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	int rc = sdt_gpu_correct_kept_reads(gpu, min_count, fix, reads, &got, edits, cap, &n_edits);
+	if (rc == SDT_EFULL && n_edits > cap) {                                  /* more edits than guessed: once more with room for all */
+		cap = n_edits;
+		free(edits);
+		edits = (uint64_t *)malloc(cap * sizeof(uint64_t));
+		if (!edits) { fprintf(stderr, "sdt-kmers: out of memory for %llu edits\n", (unsigned long long)cap); return 1; }
+		rc = sdt_gpu_correct_kept_reads(gpu, min_count, fix, reads, &got, edits, cap, &n_edits);
+	}
+	if (rc != SDT_OK) { fprintf(stderr, "sdt_gpu_correct_kept_reads: %s\n", sdt_gpu_last_error()); return 1; }
+	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu corrected\n", reads, (unsigned long long)got); return 1; }
+	/* the kept batches, and where every ordinal's read is */
+	if (sdt_gpu_kept_batches(gpu, &nb) != SDT_OK) { fprintf(stderr, "sdt_gpu_kept_batches: %s\n", sdt_gpu_last_error()); return 1; }
+	uint32_t **bw = (uint32_t **)calloc(nb ? nb : 1, sizeof(uint32_t *));
+	uint64_t **bo = (uint64_t **)calloc(nb ? nb : 1, sizeof(uint64_t *));
+	uint32_t *at_batch = (uint32_t *)malloc(m * sizeof(uint32_t)), *at_read = (uint32_t *)malloc(m * sizeof(uint32_t));
+	if (!bw || !bo || !at_batch || !at_read) { fprintf(stderr, "sdt-kmers: out of memory\n"); return 1; }
+	memset(at_batch, 0xFF, m * sizeof(uint32_t));
+	uint64_t longest = 0;
+	for (uint64_t b = 0; b < nb; b++) {
+		uint64_t info[4];
+		if (sdt_gpu_fetch_kept_batch(gpu, b, info, NULL, 0, NULL, 0) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
+		bw[b] = (uint32_t *)malloc((info[0] ? info[0] : 1) * sizeof(uint32_t));
+		bo[b] = (uint64_t *)malloc((info[1] + 1) * sizeof(uint64_t));
+		if (!bw[b] || !bo[b]) { fprintf(stderr, "sdt-kmers: out of memory for the reads\n"); return 1; }
+		if (sdt_gpu_fetch_kept_batch(gpu, b, info, bw[b], info[0], bo[b], info[1] + 1) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
+		for (uint64_t i = 0; i < info[1]; i++) {
+			const uint64_t ord = info[2] + i * info[3];
+			if (ord >= reads) { fprintf(stderr, "sdt-kmers: a kept read has ordinal %llu of %llu\n", (unsigned long long)ord, reads); return 1; }
+			at_batch[ord] = (uint32_t)b;
+			at_read[ord] = (uint32_t)i;
+			if (bo[b][i + 1] - bo[b][i] > longest) longest = bo[b][i + 1] - bo[b][i];
+		}
+	}
+	if (longest + 64 > OB_BLOCK) { fprintf(stderr, "sdt-kmers: a read of %llu bases\n", (unsigned long long)longest); return 1; }
+	char path[3][4200];
+	snprintf(path[0], sizeof path[0], "%s.readFix", prefix);
+	snprintf(path[1], sizeof path[1], "%s.edits", prefix);
+	snprintf(path[2], sizeof path[2], "%s.corrected.fa", prefix);
+	outbuf of, oe, oa;
+	if (ob_open(&of, path[0]) != 0) return 1;
+	if (ob_open(&oe, path[1]) != 0) { ob_close(&of); return 1; }
+	if (ob_open(&oa, path[2]) != 0) { ob_close(&of); ob_close(&oe); return 1; }
+	unsigned long long with_weak = 0, runs = 0, fixed = 0;
+	uint64_t e = 0;
+	int bad = 0;
+	for (uint64_t ord = 0; ord < reads && !bad; ord++) {
+		if (!of.ok || !oe.ok || !oa.ok) break;                               /* a write failed: ob_close says which */
+		ob_room(&of, 4 * 11);
+		of.p = put_u32(of.p, fix[ord].kmers, ' ');
+		of.p = put_u32(of.p, fix[ord].weak, ' ');
+		of.p = put_u32(of.p, fix[ord].runs, ' ');
+		of.p = put_u32(of.p, fix[ord].fixed, '\n');
+		with_weak += fix[ord].weak != 0;
+		runs += fix[ord].runs;
+		if (at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
+		const uint32_t *w = bw[at_batch[ord]];
+		const uint64_t start = bo[at_batch[ord]][at_read[ord]], len = bo[at_batch[ord]][at_read[ord] + 1] - start;
+		ob_room(&oa, (size_t)len + 24);
+		*oa.p++ = '>';
+		oa.p = put_u64(oa.p, ord + 1, '\n');
+		char *seq = oa.p;
+		for (uint64_t i = 0; i < len; i++) {
+			const uint64_t g = start + i;
+			*oa.p++ = letters[(w[g >> 4] >> (30 - 2 * (int)(g & 15))) & 3u];
+		}
+		*oa.p++ = '\n';
+		for (; e < n_edits && (edits[e] >> 18) == ord; e++, fixed++) {
+			const uint64_t pos = (edits[e] >> 2) & 0xFFFFu;
+			if (pos >= len) { fprintf(stderr, "sdt-kmers: an edit at base %llu of a read of %llu\n", (unsigned long long)pos, (unsigned long long)len); bad = 1; break; }
+			ob_room(&oe, 2 * 21 + 4);
+			oe.p = put_u64(oe.p, ord + 1, ' ');
+			oe.p = put_u64(oe.p, pos + 1, ' ');
+			*oe.p++ = seq[pos];
+			*oe.p++ = ' ';
+			*oe.p++ = seq[pos] = letters[edits[e] & 3u];
+			*oe.p++ = '\n';
+		}
+	}
+	const int all_written = of.ok && oe.ok && oa.ok;
+	if ((ob_close(&of) != 0) | (ob_close(&oe) != 0) | (ob_close(&oa) != 0) || bad) return 1;
+	if (all_written && e != n_edits) { fprintf(stderr, "sdt-kmers: %llu of %llu edits name no read of the stream\n", (unsigned long long)(n_edits - e), (unsigned long long)n_edits); return 1; }
+	for (uint64_t b = 0; b < nb; b++) { free(bw[b]); free(bo[b]); }
+	free(bw); free(bo); free(at_batch); free(at_read); free(fix); free(edits);
+	printf("%llu reads, %llu with weak k-mers, %llu runs, %llu bases corrected into %s\n", reads, with_weak, runs, fixed, path[2]);
+	return 0;
+}
+
 typedef struct { char **text; uint64_t *keys; uint64_t n, cap; } query_set;
 
 /* one k-mer per line, letters ACGT (either case), exactly K of them; blank lines are skipped.  Base codes A0 C1 T2 G3. */
@@ -162,11 +311,11 @@ static int load_queries(const char *path, int K, int nw, query_set *q)
 
 int main(int argc, char **argv)
 {
-	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0)) { usage(); return 255; }
-	const int do_query = strcmp(argv[1], "query") == 0;
+	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0 && strcmp(argv[1], "correct") != 0)) { usage(); return 255; }
+	const int do_query = strcmp(argv[1], "query") == 0, do_correct = strcmp(argv[1], "correct") == 0;
 	char cfgfile[4096] = "", outname[4096] = "", qfile[4096] = "";
 	int K = 23, threads = 8, d = 0, max_k = 0, device = 0, c;
-	unsigned long min_count = 0;
+	unsigned long min_count = do_correct ? 2 : 0;
 	static struct option longopts[] = {{"max-k", required_argument, 0, 1000}, {"device", required_argument, 0, 1001}, {0, 0, 0, 0}};
 	argv++; argc--;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:", longopts, NULL)) != -1) {
@@ -221,7 +370,9 @@ int main(int argc, char **argv)
 	if (d && sdt_gpu_delow(gpu, d, &removed) != SDT_OK) { fprintf(stderr, "sdt_gpu_delow: %s\n", sdt_gpu_last_error()); return 1; }
 	if (d) printf("%llu kmer removed\n", (unsigned long long)removed);
 
-	if (!do_query) {
+	if (do_correct) {
+		if (correct_and_write(gpu, st.reads, (uint32_t)min_count, outname) != 0) return 1;
+	} else if (!do_query) {
 		char path[4200];
 		snprintf(path, sizeof path, "%s.readCov", outname);
 		sdt_read_cov *cov = (sdt_read_cov *)calloc(st.reads ? st.reads : 1, sizeof(sdt_read_cov));

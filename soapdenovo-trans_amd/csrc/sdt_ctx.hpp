@@ -5,6 +5,7 @@
 //   sdt_pass2.hip     second read pass (prlRead2edge): path words, patch table, k_map_reads, arcs
 //   sdt_mapstage.hip  the map stage (prlContig2nodes / prlRead2Ctg)
 //   sdt_search.hip    read-only questions to the counted table: batch k-mer search, per-read k-mer coverage
+//   sdt_correct.hip   substitution errors of reads corrected against the counted table; the kept reads back to the host
 //   sdt_gpu_graph.hip the graph phases (own view of the context: sdt_internal.hpp GraphView)
 // Not part of the ABI: nothing here is visible to a caller of libsdt_gpu.so.
 #pragma once
@@ -156,7 +157,7 @@ struct sdt_ctx {
 	uint64_t *d_hi = nullptr;
 	uint64_t hi_slots = 0;
 	int hi_mode = -1;
-	unsigned long long *d_cov_flags = nullptr;      // [0] reads longer than promised, [1] slots with a high half
+	unsigned long long *d_cov_flags = nullptr;      // [0] reads longer than promised, [1] slots with a high half, [2] edits (sdt_correct.hip)
 	// timing
 	std::vector<EventPair> ev;
 	size_t ev_used = 0;
@@ -209,3 +210,10 @@ void sk_free(sdt_ctx *c);
 // ---- sdt_sharded.hip ----
 void shard_free(sdt_ctx *c);
 int sk_flush_sharded(sdt_ctx *c);
+// ---- sdt_search.hip ---- (shared with sdt_correct.hip)
+namespace sdt { struct HiView; }
+constexpr uint64_t PROFILE_CHUNK_READS = 1ULL << 22, PROFILE_CHUNK_BASES = 1ULL << 29;     // reads / bases of a host batch that are on the device at a time
+uint64_t chunk_items(uint64_t dflt);
+int search_ready(sdt_ctx *c, const char *what);
+int flags_reserve(sdt_ctx *c);
+int hi_prepare(sdt_ctx *c, sdt::HiView *hv);

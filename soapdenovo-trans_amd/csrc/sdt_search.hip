@@ -8,16 +8,16 @@
 static const uint64_t HI_HASH_MAX = 1ULL << 18;
 // queries / reads of a host batch that are on the device at a time
 static const uint64_t SEARCH_CHUNK = 1ULL << 22;
-static const uint64_t PROFILE_CHUNK_READS = 1ULL << 22, PROFILE_CHUNK_BASES = 1ULL << 29;
+// (PROFILE_CHUNK_READS / PROFILE_CHUNK_BASES: sdt_ctx.hpp -- sdt_correct.hip stages its reads the same way)
 // (SDT_SEARCH_CHUNK: test hook -- pieces of that many queries / reads, so that small batches cross piece boundaries)
-static uint64_t chunk_items(uint64_t dflt)
+uint64_t chunk_items(uint64_t dflt)
 {
 	const char *v = sdt_test_env("SDT_SEARCH_CHUNK");
 	return v && atoll(v) > 0 ? (uint64_t)atoll(v) : dflt;
 }
 
 // the state rules of include/sdt_gpu.h, one message each
-static int search_ready(sdt_ctx *c, const char *what)
+int search_ready(sdt_ctx *c, const char *what)
 {
 	if (c->flags & SDT_FLAG_CONTIG_INDEX)
 		return fail(SDT_ESTATE, "%s: a SDT_FLAG_CONTIG_INDEX context holds contig positions, not counts", what);
@@ -32,14 +32,14 @@ static int search_ready(sdt_ctx *c, const char *what)
 	return SDT_OK;
 }
 
-static int flags_reserve(sdt_ctx *c)
+int flags_reserve(sdt_ctx *c)
 {
-	if (!c->d_cov_flags) HIPCHK(hipMalloc((void **)&c->d_cov_flags, 2 * sizeof(unsigned long long)));
+	if (!c->d_cov_flags) HIPCHK(hipMalloc((void **)&c->d_cov_flags, 3 * sizeof(unsigned long long)));
 	return SDT_OK;
 }
 
 // where k_profile_reads finds the high half of a count: collected on the first profile after the table last changed
-static int hi_prepare(sdt_ctx *c, HiView *hv)
+int hi_prepare(sdt_ctx *c, HiView *hv)
 {
 	if (c->hi_mode < 0) {
 		HIPCHK(hipMemsetAsync(c->d_cov_flags + 1, 0, sizeof(unsigned long long), c->stream));

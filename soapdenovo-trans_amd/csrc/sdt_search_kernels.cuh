@@ -44,7 +44,7 @@ __device__ inline uint32_t hi_lookup(const HiView &hv, const uint32_t *__restric
 	}
 }
 
-__global__ __launch_bounds__(TPB) void k_hi_count(const uint32_t *__restrict__ aux, uint64_t slots, unsigned long long *n_hi)
+static __global__ __launch_bounds__(TPB) void k_hi_count(const uint32_t *__restrict__ aux, uint64_t slots, unsigned long long *n_hi)
 {
 	uint32_t mine = 0;
 	for (uint64_t s = blockIdx.x * (uint64_t)TPB + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * TPB)
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(TPB) void k_hi_count(const uint32_t *__restrict__ a
 		atomicAdd(n_hi, (unsigned long long)mine);
 }
 
-__global__ __launch_bounds__(TPB) void k_hi_fill(const uint32_t *__restrict__ aux, uint64_t slots, uint64_t *tab, uint64_t mask)
+static __global__ __launch_bounds__(TPB) void k_hi_fill(const uint32_t *__restrict__ aux, uint64_t slots, uint64_t *tab, uint64_t mask)
 {
 	for (uint64_t s = blockIdx.x * (uint64_t)TPB + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * TPB) {
 		const uint32_t hi = aux[s] & 0xFFFFu;

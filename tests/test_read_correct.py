@@ -1,0 +1,422 @@
+"""GPU (-m gpu): sdt_gpu_correct_reads and its siblings against the Python restatement of the rule (read_correct_util.py) on the
+oracle's node table.  Expectations never come from the library under test: counts are the oracle's (oracle_binding.Oracle.export), the
+rule is plain Python, and every output is compared for exact equality."""
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import oracle_binding as ob
+import golden_util as gu
+import read_correct_util as rc
+from test_kmer_search import canon_kmers, materialise, node_dict_oracle, small_input, workload
+
+pytestmark = pytest.mark.gpu
+
+MIN_COUNTS = (0, 1, 2, 3, 50)
+
+
+def read_len_for(K):
+    return 150 if K <= 33 else 250
+
+
+def concat(reads):
+    offs = np.zeros(len(reads) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(r) for r in reads])
+    return (np.concatenate(reads) if reads else np.zeros(0, dtype=np.uint8)), offs
+
+
+def plant(read, *positions):
+    out = read.copy()
+    for i, p in enumerate(positions):
+        out[p] = (out[p] + 1 + (p + i) % 3) & 3
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def case(K):
+    """the counted input (workload + two transcripts that differ in one base, three copies each), the oracle's node dictionary for it,
+    and the batch to correct: the workload's reads + the hand-made ones.  Built once per K and left unchanged."""
+    from soapdenovo_trans_amd import synth
+    L = read_len_for(K)
+    tx, codes, offs = workload(synth, K, L)
+    rng = np.random.default_rng(900 + K)
+    twin_a = rng.integers(0, 4, size=L, dtype=np.uint8)
+    twin_b = twin_a.copy()
+    twin_b[L // 2] = (twin_b[L // 2] + 1) & 3
+    counted, coffs = concat([codes[int(offs[i]):int(offs[i + 1])] for i in range(len(offs) - 1)] + [twin_a, twin_b] * 3)
+    o = ob.Oracle(K, nsets=5)
+    o.add_reads(counted, coffs)
+    nodes = node_dict_oracle(o)
+    count = rc.table_counts(nodes)
+
+    def solid_templates(read_len, seed, want):
+        c, f = synth.sample_reads(*tx, n_reads=400, read_len=read_len, seed=seed, err=0.0)
+        out = []
+        for i in range(len(f) - 1):
+            r = c[int(f[i]):int(f[i + 1])]
+            if len(r) == read_len and all(count(k) >= 3 for k in canon_kmers(r, K)):
+                out.append(r)
+        assert len(out) >= want, f"K={K}: only {len(out)} of 400 clean reads of {read_len} bases are entirely solid"
+        return out
+
+    t = solid_templates(L, K + 7, 30)
+    long_t = solid_templates(260 + K, K + 8, 1)[0]
+    hand = [plant(t[i], p) for i, p in enumerate([0, 1, K - 2, K - 1, K, K + 1, L - K - 2, L - K - 1, L - K, L - K + 1, L - 2, L - 1])]
+    hand += [plant(t[12 + i], p) for i, p in enumerate([63, 64, 63 + K - 1, 64 + K - 1])]      # runs across k-mer 63 / 64
+    hand += [plant(t[16], K + 7, 2 * K + 10), plant(t[17], K + 7, 2 * K + 2)]                  # two errors K + 3 and K - 5 apart
+    hand += [t[18][:K - 1], t[18][:K], t[18][:K + 1]]
+    hand += [plant(long_t, 5, 130 + K // 2, len(long_t) - 3)]                                  # more than 256 k-mers, three errors
+    hand += [synth.make_transcriptome(3, seed=K + 1000)[0][:L].copy()]                         # all weak
+    amb = twin_a.copy()
+    amb[L // 2] = (amb[L // 2] + 2) & 3                                                        # a third base where the twins differ
+    i_amb = len(hand)
+    hand += [amb]
+    # two neighbours with errors in the last base of one and the first base of the other, both in one 32-bit word
+    if (sum(len(h) for h in hand) + int(offs[-1]) + L) % 16 == 0:
+        hand += [t[19][:3]]
+    i_pair = len(hand)
+    hand += [plant(t[20], L - 1), plant(t[21], 0)]
+    n0 = len(offs) - 1
+    batch, boffs = concat([codes[int(offs[i]):int(offs[i + 1])] for i in range(n0)] + hand)
+    end = int(boffs[n0 + i_pair + 1])
+    assert (end - 1) >> 4 == end >> 4, "the two neighbours do not share a word"
+    assert int(boffs[-1] - boffs[-2]) - K + 1 > 0 and len(long_t) - K + 1 > 256
+    kc = rc.read_kmer_counts(batch, boffs, K, count)
+    return dict(K=K, L=L, counted=counted, coffs=coffs, nodes=nodes, count=count, batch=batch, boffs=boffs, kc=kc, n0=n0,
+                amb=n0 + i_amb, pair=n0 + i_pair, oracle=(o.kmers_in_reads(), o.node_count()))
+
+
+@functools.lru_cache(maxsize=None)
+def expected(K, mc):
+    c = case(K)
+    return rc.expect_correct(c["batch"], c["boffs"], K, c["count"], mc, kmer_counts=c["kc"])
+
+
+def counted_context(pkg, synth, c, flags=0):
+    g = pkg.PregraphGPU(c["K"], est_distinct=1 << 16, flags=flags)
+    g.push_reads(synth.pack_2bit(c["counted"]), c["coffs"])
+    assert g.finish_count() == c["oracle"]
+    return g
+
+
+def assert_outputs(pkg, synth, got, want, codes, offs, what):
+    fix, out_words, edits = got
+    wfix, wout, wedits = want
+    assert fix.dtype == pkg.READ_FIX_DTYPE
+    rc.assert_fix_equal(fix, wfix, what)
+    wwords = synth.pack_2bit(wout)
+    bad = np.nonzero(out_words != wwords)[0]
+    assert out_words.shape == wwords.shape and bad.size == 0, f"{what}: out_words differ at words {bad[:8].tolist()}"
+    assert edits.dtype == np.uint64 and edits.tolist() == wedits.tolist(), f"{what}: edits differ"
+    assert int(fix["fixed"].sum()) == len(edits)
+    for e in edits.tolist():
+        assert codes[int(offs[e >> 18]) + ((e >> 2) & 0xFFFF)] != (e & 3)
+
+
+# ---- 1. the rule ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K,mode", [(21, 0), (31, 1), (31, 2), (33, 0), (63, 0), (95, 0)])
+def test_correct_equals_the_rule(pkg, synth, K, mode):
+    """6 000 ragged reads with errors and the hand-made reads (errors at the boundary positions, runs across k-mer 63 / 64, two runs,
+    reads of K - 1, K, K + 1 bases, more than 256 k-mers, nothing solid, an ambiguous site, two edits in one word); min_count 0, 1, 2,
+    3, 50; fix, out_words (pad words included) and the sorted edits"""
+    c = case(K)
+    words = synth.pack_2bit(c["batch"])
+    with counted_context(pkg, synth, c, flags=mode) as g:
+        for mc in MIN_COUNTS:
+            want = expected(K, mc)
+            got = g.correct_reads(words, c["boffs"], mc)
+            assert_outputs(pkg, synth, got, want, c["batch"], c["boffs"], f"K={K} min_count={mc}")
+            if mc == 0:
+                assert not got[0]["weak"].any() and len(got[2]) == 0 and (got[1] == words).all()
+        assert len(g.correct_reads(words, c["boffs"][:1], 2)[0]) == 0
+    w2, w3 = expected(K, 2), expected(K, 3)
+    assert int(w2[0]["fixed"].sum()) >= 300, "the case must hold errors that the rule corrects"
+    assert tuple(w3[0][c["amb"]])[2:] == (1, 0)                              # the ambiguous site: one run, nothing fixed
+    assert w3[0][c["pair"]]["fixed"] == 1 and w3[0][c["pair"] + 1]["fixed"] == 1
+    assert (w3[0]["runs"] > 1).any() and (w3[0]["fixed"] > 1).any() and (w3[0]["kmers"] == 0).any()
+
+
+# ---- 2. device-pointer form -------------------------------------------------------------------------------------------------------
+def test_correct_device_form_equals_host_form(pkg, synth):
+    import torch
+    dev = torch.device("cuda:0")
+    K, mc = 31, 3
+    c = case(K)
+    wfix, wout, wedits = expected(K, mc)
+    words = synth.pack_2bit(c["batch"])
+    n = len(c["boffs"]) - 1
+    maxlen = int(np.diff(c["boffs"].astype(np.int64)).max())
+    with counted_context(pkg, synth, c) as g:
+        d_w = torch.from_numpy(words.view(np.int32)).to(dev)
+        d_o = torch.from_numpy(c["boffs"].view(np.int64)).to(dev)
+
+        def run(max_read_len, with_out=True, cap=len(wedits) + 7):
+            d_fix = torch.full((n, 4), -1, dtype=torch.int32, device=dev)
+            d_out = torch.full((len(words),), -1, dtype=torch.int32, device=dev) if with_out else None
+            d_ed = torch.full((max(cap, 1),), -1, dtype=torch.int64, device=dev) if with_out else None
+            torch.cuda.synchronize()
+            err = None
+            try:
+                got = g.correct_reads_device(d_w, len(words), d_o, n, max_read_len, mc, d_fix, d_out, d_ed, cap if with_out else 0)
+            except pkg.SdtError as e:
+                err, got = e, e.needed
+            fix = d_fix.cpu().numpy().view(np.uint32).copy().view(pkg.READ_FIX_DTYPE).reshape(-1)
+            out = d_out.cpu().numpy().view(np.uint32) if with_out else None
+            ed = d_ed.cpu().numpy().view(np.uint64) if with_out else None
+            return err, got, fix, out, ed
+
+        err, got, fix, out, ed = run(maxlen)
+        assert err is None and got == len(wedits)
+        assert_outputs(pkg, synth, (fix, out, np.sort(ed[:got])), (wfix, wout, wedits), c["batch"], c["boffs"], "device form")
+        assert (ed[got:] == np.uint64(0xFFFFFFFFFFFFFFFF)).all()
+        # no out_words, no edits
+        err, got, fix, _, _ = run(maxlen, with_out=False)
+        assert err is None and got == len(wedits)
+        rc.assert_fix_equal(fix, wfix, "device form without out_words / edits")
+        # one slot short: SDT_EFULL, the number needed, fix and out_words complete, nothing stored past the end
+        err, got, fix, out, ed = run(maxlen, cap=len(wedits) - 1)
+        assert err is not None and err.code == pkg.SDT_EFULL and got == len(wedits)
+        rc.assert_fix_equal(fix, wfix, "max_edits one short")
+        assert (out == synth.pack_2bit(wout)).all()
+        assert set(ed.tolist()) <= set(wedits.tolist()) and len(set(ed.tolist())) == len(wedits) - 1
+        # a read longer than promised: marked, unchanged in the output, SDT_EINVAL
+        err, got, fix, out, ed = run(maxlen - 1)
+        assert err is not None and err.code == pkg.SDT_EINVAL and "longer" in str(err)
+        longest = np.diff(c["boffs"].astype(np.int64)) == maxlen
+        assert longest.sum() == 1 and wfix["fixed"][longest].sum() == 3
+        assert (fix["kmers"][longest] == pkg.COV_TOO_LONG).all() and all((fix[f][longest] == 0).all() for f in ("weak", "runs", "fixed"))
+        rc.assert_fix_equal(fix[~longest], wfix[~longest], "the other reads of the batch")
+        # ... and that read is in d_out_words as it came: the expected stream with its three edits undone
+        undone = wout.copy()
+        r_long = int(np.nonzero(longest)[0][0])
+        s_long, e_long = int(c["boffs"][r_long]), int(c["boffs"][r_long + 1])
+        undone[s_long:e_long] = c["batch"][s_long:e_long]
+        assert (undone != wout).sum() == 3 and (out == synth.pack_2bit(undone)).all()
+        assert got == len(wedits) - 3 and sorted(ed[:got].tolist()) == [e for e in wedits.tolist() if e >> 18 != r_long]
+        # every read too long: the output words are the input
+        fl_codes, fl_offs = synth.sample_reads(*synth.make_transcriptome(25, seed=K), n_reads=500, read_len=100, seed=5, err=0.01)
+        assert (np.diff(fl_offs.astype(np.int64)) == 100).all()
+        fl_words = synth.pack_2bit(fl_codes)
+        assert rc.expect_correct(fl_codes, fl_offs, K, c["count"], mc)[0]["fixed"].sum() > 20
+        d_w2 = torch.from_numpy(fl_words.view(np.int32)).to(dev)
+        d_o2 = torch.from_numpy(fl_offs.view(np.int64)).to(dev)
+        d_fix = torch.zeros((500, 4), dtype=torch.int32, device=dev)
+        d_out = torch.full((len(fl_words),), -1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        with pytest.raises(pkg.SdtError) as e:
+            g.correct_reads_device(d_w2, len(fl_words), d_o2, 500, 99, mc, d_fix, d_out, None, 0)
+        assert e.value.code == pkg.SDT_EINVAL and e.value.needed == 0
+        rec = d_fix.cpu().numpy().view(np.uint32)
+        assert (rec[:, 0] == pkg.COV_TOO_LONG).all() and (rec[:, 1:] == 0).all()
+        assert (d_out.cpu().numpy().view(np.uint32) == fl_words).all()
+        assert g.correct_reads_device(d_w2, len(fl_words), d_o2, 0, 99, mc, None) == 0
+
+
+# ---- 3. host batches in pieces ----------------------------------------------------------------------------------------------------
+def test_correct_host_batches_go_through_in_pieces(pkg, synth, monkeypatch):
+    """pieces of 777 reads and of one read (test hook): a piece starts in the middle of a word that holds the previous read's last
+    bases, and out_words carries the edits of both.  Pieces of 777 go over the whole batch; pieces of ONE read are a kernel launch, two
+    copies and a wait per read, so they go over the last 300 reads of the workload and all the hand-made ones (the two neighbours
+    with edits in one word among them) -- compared with the rule on exactly those reads, as the whole batch is"""
+    K, mc = 31, 3
+    c = case(K)
+    words = synth.pack_2bit(c["batch"])
+    n0 = c["n0"]
+    tail, toffs = c["batch"][int(c["boffs"][n0 - 300]):], c["boffs"][n0 - 300:] - c["boffs"][n0 - 300]
+    want_tail = rc.expect_correct(tail, toffs, K, c["count"], mc, kmer_counts=c["kc"][n0 - 300:])
+    assert want_tail[0]["fixed"].sum() > 30
+    with counted_context(pkg, synth, c) as g:
+        monkeypatch.setenv("SDT_SEARCH_CHUNK", "777")
+        assert_outputs(pkg, synth, g.correct_reads(words, c["boffs"], mc), expected(K, mc), c["batch"], c["boffs"], "pieces of 777 reads")
+        monkeypatch.setenv("SDT_SEARCH_CHUNK", "1")
+        assert_outputs(pkg, synth, g.correct_reads(synth.pack_2bit(tail), toffs, mc), want_tail, tail, toffs, "pieces of one read")
+
+
+# ---- 4. kept reads ----------------------------------------------------------------------------------------------------------------
+def test_correct_kept_reads_by_ordinal(pkg, synth):
+    K, L, mc = 31, 100, 3
+    tx = synth.make_transcriptome(20, seed=5)
+    (c1, o1), (c2, o2) = synth.sample_pairs(*tx, n_pairs=700, read_len=L, seed=6, err=0.004)
+    ca, oa = synth.sample_reads(*tx, n_reads=1500, read_len=140, seed=7, err=0.004, ragged=True)
+    cb, ob_ = synth.sample_reads(*tx, n_reads=900, read_len=120, seed=8, err=0.004, ragged=False)
+    np1 = len(o1) - 1
+    pushed = [(synth.pack_2bit(c1), o1, 0, 2), (synth.pack_2bit(c2), o2, 1, 2), (synth.pack_2bit(ca), oa, 2 * np1, 1),
+              (synth.pack_2bit(cb), ob_, 2 * np1 + len(oa) - 1, 1)]
+    with pkg.PregraphGPU(K, est_distinct=1 << 16, flags=pkg.SDT_FLAG_KEEP_READS) as g:
+        for w, o, base, stride in pushed[:3]:
+            g.set_read_ordinal(base, stride)
+            g.push_reads(w, o)
+        g.push_wait(g.push_reads_fixed_async(pushed[3][0], len(ob_) - 1, 120))
+        g.finish_count()
+
+        def assert_kept_as_pushed():
+            assert g.kept_batches() == len(pushed)
+            for i, (w, o, base, stride) in enumerate(pushed):
+                gw, go, gb, gs = g.fetch_kept_batch(i)
+                assert (gb, gs) == (base, stride) and gw.shape == w.shape and (gw == w).all() and go.shape == o.shape and (go == o).all()
+
+        assert_kept_as_pushed()
+        reads = []
+        for i in range(np1):
+            reads.append(c1[int(o1[i]):int(o1[i + 1])])
+            reads.append(c2[int(o2[i]):int(o2[i + 1])])
+        reads += [ca[int(oa[i]):int(oa[i + 1])] for i in range(len(oa) - 1)]
+        reads += [cb[int(ob_[i]):int(ob_[i + 1])] for i in range(len(ob_) - 1)]
+        codes, offs = concat(reads)
+        total = len(reads)
+        wfix, wwords, wedits = g.correct_reads(synth.pack_2bit(codes), offs, mc)
+        assert len(wedits) > 100 and (wedits >> np.uint64(18)).max() > 2 * np1 + len(oa)
+        fix, n, edits = g.correct_kept_reads(total, mc)
+        assert n == total and edits.tolist() == wedits.tolist()
+        rc.assert_fix_equal(fix, wfix, "kept reads")
+        assert_kept_as_pushed()                                             # the kept reads are not changed
+        # a larger array: the records past the last ordinal stay as they were
+        big = np.full(total + 5, 0xABABABAB, dtype=np.uint32).repeat(4).view(pkg.READ_FIX_DTYPE)
+        fix, n, edits = g.correct_kept_reads(total + 5, mc, out=big)
+        assert n == total and (fix[total:].view(np.uint32) == 0xABABABAB).all() and edits.tolist() == wedits.tolist()
+        rc.assert_fix_equal(fix[:total], wfix, "kept reads into a larger array")
+        # one record short: SDT_EFULL and nothing written
+        small = np.full(total - 1, 0xABABABAB, dtype=np.uint32).repeat(4).view(pkg.READ_FIX_DTYPE)
+        with pytest.raises(pkg.SdtError) as e:
+            g.correct_kept_reads(total - 1, mc, out=small)
+        assert e.value.code == pkg.SDT_EFULL and "ordinal" in str(e.value)
+        assert (small.view(np.uint32) == 0xABABABAB).all()
+        # fetch_kept_batch: a batch that does not exist, capacities that are too small, info alone
+        info = np.zeros(4, dtype=np.uint64)
+        buf = np.full(len(pushed[0][0]), 0xABABABAB, dtype=np.uint32)
+        obuf = np.zeros(len(o1), dtype=np.uint64)
+        assert g.lib.sdt_gpu_fetch_kept_batch(g._ctx, len(pushed), info.ctypes.data, None, 0, None, 0) == pkg.SDT_EINVAL
+        assert g.lib.sdt_gpu_fetch_kept_batch(g._ctx, 0, info.ctypes.data, buf.ctypes.data, len(buf) - 1, obuf.ctypes.data, len(obuf)) == pkg.SDT_EFULL
+        assert g.lib.sdt_gpu_fetch_kept_batch(g._ctx, 0, info.ctypes.data, buf.ctypes.data, len(buf), obuf.ctypes.data, len(obuf) - 1) == pkg.SDT_EFULL
+        assert (buf == 0xABABABAB).all() and info.tolist() == [len(buf), np1, 0, 2]
+    # against the rule as well: the table is what the oracle counts for the same stream
+    o = ob.Oracle(K, nsets=5)
+    o.add_reads(codes, offs)
+    want = rc.expect_correct(codes, offs, K, rc.table_counts(node_dict_oracle(o)), mc)
+    rc.assert_fix_equal(wfix, want[0], "the stream in ordinal order")
+    assert wedits.tolist() == want[2].tolist() and (wwords == synth.pack_2bit(want[1])).all()
+
+
+# ---- 5. read-only -----------------------------------------------------------------------------------------------------------------
+def test_correct_leaves_the_table_alone(pkg, synth):
+    K, L = 31, 150
+    _, codes, offs = workload(synth, K, L)
+    words = synth.pack_2bit(codes)
+
+    def snapshot(g):
+        keys, l, rf, cnt, first = g.export_nodes(with_first=True)
+        order = np.lexsort(keys.T[::-1])
+        return [a[order].copy() for a in (keys, l, rf, cnt, first)]
+
+    with pkg.PregraphGPU(K, est_distinct=1 << 16, flags=pkg.SDT_FLAG_TRACK_FIRST) as g:
+        g.push_reads(words, offs)
+        g.finish_count()
+        hist0, lin0 = g.mark_and_hist()
+        before = snapshot(g)
+        fix, out_words, edits = g.correct_reads(words, offs, 2)
+        assert len(edits) > 300 and (out_words != words).any()
+        assert (words == synth.pack_2bit(codes)).all()                     # nor the caller's reads
+        after = snapshot(g)
+        for a, b in zip(before, after):
+            assert a.shape == b.shape and (a == b).all()
+        hist1, lin1 = g.mark_and_hist()
+        assert lin1 == lin0 and (hist1 == hist0).all()
+
+
+# ---- 6. state errors --------------------------------------------------------------------------------------------------------------
+def assert_state_error(pkg, g, words, offs, code=None):
+    import torch
+    code = pkg.SDT_ESTATE if code is None else code
+    n = len(offs) - 1
+    d_fix = torch.zeros((n, 4), dtype=torch.int32, device="cuda")
+    d_w = torch.from_numpy(words.view(np.int32)).cuda()
+    d_o = torch.from_numpy(offs.view(np.int64)).cuda()
+    calls = [lambda: g.correct_reads(words, offs, 2), lambda: g.correct_kept_reads(n, 2),
+             lambda: g.correct_reads_device(d_w, len(words), d_o, n, 100, 2, d_fix)]
+    for call in calls:
+        with pytest.raises(pkg.SdtError) as e:
+            call()
+        assert e.value.code == code, str(e.value)
+        assert len(g.lib.sdt_gpu_last_error()) > 10
+
+
+def test_correct_state_errors(pkg, synth):
+    import torch
+    K = 31
+    codes, offs, words = small_input(synth, K)
+    n = len(offs) - 1
+    # pushed, not drained -- and fine again once drained; empty batches are fine in any state
+    with pkg.PregraphGPU(K, est_distinct=1 << 16, flags=pkg.SDT_FLAG_KEEP_READS) as g:
+        g.push_reads(words, offs)
+        assert_state_error(pkg, g, words, offs)
+        assert len(g.correct_reads(words, offs[:1], 2)[0]) == 0
+        g.finish_count()
+        fix, out_words, edits = g.correct_reads(words, offs, 1)
+        assert (fix["kmers"] == 100 - K + 1).all() and not fix["weak"].any() and len(edits) == 0 and (out_words == words).all()
+        assert g.correct_kept_reads(n, 1)[1] == n
+        # counted from device memory and not drained
+        d_w = torch.from_numpy(words.view(np.int32)).cuda()
+        d_o = torch.from_numpy(offs.view(np.int64)).cuda()
+        g.count_reads_device(d_w, len(words), d_o, n, 100)
+        assert_state_error(pkg, g, words, offs)
+        g.finish_count()
+        assert not g.correct_reads(words, offs, 2)[0]["weak"].any()
+        # path words in place of the counters
+        g.load_paths(None, None, None, None, 0)
+        assert_state_error(pkg, g, words, offs)
+        assert g.kept_batches() == 1 and (g.fetch_kept_batch(0)[0] == words).all()       # the kept reads need no table
+    # the table released
+    with pkg.PregraphGPU(K, est_distinct=1 << 16, flags=pkg.SDT_FLAG_KEEP_READS) as g:
+        g.push_reads(words, offs)
+        g.finish_count()
+        g.release_table()
+        assert_state_error(pkg, g, words, offs)
+    # reads were not kept
+    with pkg.PregraphGPU(K, est_distinct=1 << 16) as g:
+        g.push_reads(words, offs)
+        g.finish_count()
+        for call in (lambda: g.correct_kept_reads(n, 2), lambda: g.fetch_kept_batch(0)):
+            with pytest.raises(pkg.SdtError) as e:
+                call()
+            assert e.value.code == pkg.SDT_ESTATE and "kept" in str(e.value)
+        assert g.kept_batches() == 0
+    # a contig index
+    with pkg.PregraphGPU(K, est_distinct=1 << 16, flags=pkg.SDT_FLAG_CONTIG_INDEX) as g:
+        assert_state_error(pkg, g, words, offs)
+    # one shard of a sharded table
+    with pkg.PregraphGPU(K, est_distinct=1 << 16) as g:
+        g.comm_init_shm(f"rcs{os.getpid()}", 0, 1)
+        assert_state_error(pkg, g, words, offs)
+
+
+# ---- 7. the host program ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("d", [0, 1])
+@pytest.mark.parametrize("name", ["se100_k23_p8", "pe150_k31_p8", "se150_k47_p4_63mer"])
+def test_sdt_kmers_correct_cli(pkg, tmp_path, name, d):
+    info = gu.load_case(name)
+    K = pkg.clamp_K(info["K"], gu.VARIANT_MAXK[info["variant"]])
+    cfg = materialise(info, tmp_path)
+    codes, offs = gu.case_reads(info)
+    o = ob.Oracle(K, nsets=4)
+    o.add_reads(codes, offs)
+    if d:
+        o.delow(d)
+    fix, out, edits = rc.expect_correct(codes, offs, K, rc.table_counts(node_dict_oracle(o)), 3)
+    assert int(fix["fixed"].sum()) >= 500, "the case must hold errors that the rule corrects"
+    want = rc.cli_texts(codes, offs, fix, out, edits)
+    exe = os.path.join(pkg.CSRC_DIR, "sdt-kmers")
+    if not os.path.exists(exe):
+        pkg.build()
+    opts = ["-s", cfg, "-K", str(info["K"]), "-p", "4", "--max-k", str(gu.VARIANT_MAXK[info["variant"]])] + (["-d", str(d)] if d else [])
+    r = subprocess.run([exe, "correct"] + opts + ["-c", "3", "-o", str(tmp_path / "out")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    for ext, text in zip(("readFix", "edits", "corrected.fa"), want):
+        got = (tmp_path / f"out.{ext}").read_text()
+        assert got == text, f"{name} -d {d}: out.{ext} differs from the rule ({len(got)} bytes, {len(text)} expected)"
+    last = [x for x in r.stdout.splitlines() if "bases corrected" in x]
+    assert len(last) == 1
+    assert [int(x) for x in last[0].replace(",", " ").split() if x.isdigit()] == \
+        [len(offs) - 1, int((fix["weak"] > 0).sum()), int(fix["runs"].sum()), len(edits)]
