@@ -482,9 +482,57 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  *                   ord_base, ord_stride; words / offsets NULL: info only.  Needs kept reads, not a table: SDT_ESTATE without
  *                   them, SDT_EINVAL for i out of range, SDT_EFULL when a capacity is too small, SDT_ESTATE (info
  *                   included) while pushed batches are not drained (sdt_gpu_finish_count): their copies may be in flight.
- * State rules and return codes are those of the profile calls.  Nothing here writes the table or the kept reads. */
+ * State rules and return codes are those of the profile calls.  Nothing here writes the table or the kept reads.
+ *
+ * In-silico read normalisation against the table: a read is kept with probability target / median k-mer coverage, measured against
+ * the table of ALL reads, so every read is decided on its own and the result does not depend on the order of the reads or on the
+ * launch geometry.  Added without a change of SDT_ABI_VERSION: the five calls and the two structs are additions.  The rule is in
+ * integers only.  A read has n = len - K + 1 k-mers (0 for len < K) with the counts c[j] that profile_reads sees (absent = 0; the
+ * deleted flag is ignored).
+ *     median   the lower median of c[], element (n - 1) / 2 ascending, of the unsaturated 32-bit counts (sdt_read_cov.median)
+ *     S1, S2   the sum and the sum of squares of c'[j] = min(c[j], 65535); n * S2 < 2^64 as n <= 65 536
+ *     a read is ABERRANT iff max_cv_pct > 0 and 10000 * (n * S2 - S1 * S1) > max_cv_pct * max_cv_pct * S1 * S1, evaluated in 128
+ *              bits: stdev / mean > max_cv_pct / 100.  S1 == 0: both sides are 0, not aberrant.
+ * A UNIT is one read, or the two mates of a pair; its id u is the index of its first read (dense forms) or that read's ordinal (kept
+ * form).  cov of a single read = its median; of a pair = (mL + mR + 1) / 2 in 64 bits, or the other mate's median when one mate has
+ * n == 0.  A unit is aberrant iff a mate with n > 0 is.  The same verdict goes to both mates, the first line that applies:
+ *     4  every read of the unit has n == 0                dropped, short
+ *     3  the unit is aberrant                             dropped, aberrant
+ *     0  cov <= target                                    kept
+ *     1  draw(u) * cov < target * 2^32                    kept by draw
+ *     2  otherwise                                        dropped by draw
+ * draw(u) = mix64(seed ^ (u * 0x9E3779B97F4A7C15)) >> 32, the multiplication mod 2^64, mix64(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd;
+ * x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33 (csrc/sdt_kmer.cuh).  cov and target are 32-bit: both products fit 64 bits.
+ * target == 0 is SDT_EINVAL.
+ *   select_reads:   pick[i] for read i of a batch (packed as for sdt_gpu_push_reads): kmers and median as sdt_read_cov, the unit's
+ *                   cov, verdict = the class above | 1 << 4 iff THIS read is aberrant on its own.  paired != 0: reads 2t and 2t + 1
+ *                   are mates (an odd nreads is SDT_EINVAL).  keep (may be NULL): keep[i] = 1 for verdicts 0 and 1, else 0.
+ *                   *n_kept = reads kept.  The batch is staged in pieces as for profile_reads; a piece never splits a pair.
+ *   select_reads_device: buffers already on the device (d_pick nreads records, d_keep nreads bytes or NULL); max_read_len as for
+ *                   profile_reads_device: a longer read gets kmers = 0xFFFFFFFF, median = cov = 0, verdict 4, keep 0, counts as
+ *                   n == 0 for its mate, and the call returns SDT_EINVAL with every other record complete.  The call waits for the
+ *                   kernels to know *n_kept.
+ *   select_kept_reads: the reads kept in HBM; pick[] by READ ORDINAL like profile_kept_reads (SDT_EFULL, nothing written, when a
+ *                   kept read's ordinal is >= out_capacity; records of ordinals that no kept read has are left untouched).
+ *                   pair_ranges[2i], pair_ranges[2i + 1] = [first, end) of ordinals that hold interleaved pairs, the first mate at
+ *                   first + 2t; ascending, disjoint, of even length, else SDT_EINVAL.  Ordinals outside every range are single
+ *                   reads.  A pair of which only one mate is kept in HBM is judged on that mate alone (its id stays the first
+ *                   mate's ordinal).  *nreads = reads decided, *n_kept = reads kept.  Mates sit in different kept batches, so the
+ *                   call holds the records of ALL ordinals on the device at once: 16 B x (highest kept ordinal + 1) of HBM beside
+ *                   the table and the kept reads, SDT_ENOMEM (nothing written) when that does not fit.
+ *   compact_reads:  the reads with keep[i] != 0 of a 2-bit stream, packed base-contiguous again in their order: out_offsets has
+ *                   *n_out_reads + 1 entries (the caller provides nreads + 1), out_words *n_out_words words and 4 pad words of 0
+ *                   after them; the last word is zero past the last base.  SDT_EFULL with *n_out_words (and *n_out_reads) set when
+ *                   out_words_cap < *n_out_words + 4; nothing else is valid then.  The host form stages the whole stream at once.
+ *                   It needs a context for its stream only: allowed in any state and on any kind of context.
+ *   compact_reads_device: buffers on the device; d_out_words must not overlap the input.  The call waits for the kernels.  Its
+ *                   outputs are what sdt_gpu_count_reads_device of another context takes (nwords = *n_out_words + 4).
+ * The select calls follow the state rules and return codes of the profile calls (nreads == 0: SDT_OK, nothing touched).  Nothing
+ * here writes the table or the kept reads. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
+typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
+typedef struct { uint32_t target, max_cv_pct; uint64_t seed; } sdt_norm_params;
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -506,6 +554,20 @@ int sdt_gpu_correct_kept_reads(sdt_ctx *ctx, uint32_t min_count, sdt_read_fix *f
 int sdt_gpu_kept_batches(const sdt_ctx *ctx, uint64_t *n);
 int sdt_gpu_fetch_kept_batch(sdt_ctx *ctx, uint64_t i, uint64_t info[4], uint32_t *words, uint64_t words_cap,
                              uint64_t *offsets, uint64_t offsets_cap);
+int sdt_gpu_select_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                         uint64_t nreads, int paired, const sdt_norm_params *params, sdt_read_pick *pick, uint8_t *keep,
+                         uint64_t *n_kept);
+int sdt_gpu_select_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                                uint64_t max_read_len, int paired, const sdt_norm_params *params, void *d_pick, void *d_keep,
+                                uint64_t *n_kept);
+int sdt_gpu_select_kept_reads(sdt_ctx *ctx, const sdt_norm_params *params, const uint64_t *pair_ranges, uint64_t n_ranges,
+                              sdt_read_pick *pick, uint64_t out_capacity, uint64_t *nreads, uint64_t *n_kept);
+int sdt_gpu_compact_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                          uint64_t nreads, const uint8_t *keep, uint32_t *out_words, uint64_t out_words_cap,
+                          uint64_t *out_offsets, uint64_t *n_out_reads, uint64_t *n_out_words);
+int sdt_gpu_compact_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                                 const void *d_keep, void *d_out_words, uint64_t out_words_cap, void *d_out_offsets,
+                                 uint64_t *n_out_reads, uint64_t *n_out_words);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

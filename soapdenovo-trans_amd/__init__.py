@@ -130,6 +130,16 @@ _ABI = [
                                               _c.c_uint64, _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_kept_batches", _c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_fetch_kept_batch", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64]),
+    ("sdt_gpu_select_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                        _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_select_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_int, _c.c_void_p,
+                                               _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_select_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64,
+                                             _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_compact_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                         _c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_compact_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                                _c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -138,6 +148,15 @@ READ_COV_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "found", "solid", "
 COV_TOO_LONG = 0xFFFFFFFF
 # sdt_read_fix (include/sdt_gpu.h): one record per read of a correction; an edit is read << 18 | pos << 2 | new_base
 READ_FIX_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "weak", "runs", "fixed")])
+# sdt_read_pick (include/sdt_gpu.h): one record per read of a normalisation; verdict = class 0..4 | 1 << 4 iff the read itself is aberrant
+READ_PICK_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "median", "cov", "verdict")])
+PICK_KEPT, PICK_KEPT_DRAW, PICK_DROPPED_DRAW, PICK_ABERRANT, PICK_SHORT = range(5)
+PICK_OWN_ABERRANT = 1 << 4
+
+
+class NormParams(_c.Structure):
+    """sdt_norm_params"""
+    _fields_ = [("target", _c.c_uint32), ("max_cv_pct", _c.c_uint32), ("seed", _c.c_uint64)]
 
 _lib = None
 
@@ -625,6 +644,76 @@ class PregraphGPU:
         offsets = np.zeros(int(info[1]) + 1, dtype=np.uint64)
         self._check(self.lib.sdt_gpu_fetch_kept_batch(self._ctx, i, _ptr(info), _ptr(words), words.size, _ptr(offsets), offsets.size))
         return words, offsets, int(info[2]), int(info[3])
+
+    # -- in-silico normalisation against the counted table (the rule: include/sdt_gpu.h)
+    def select_reads(self, words, offsets, target: int = 50, max_cv_pct: int = 10000, seed: int = 0, paired: bool = False):
+        """-> (READ_PICK_DTYPE[nreads]: kmers, median, cov, verdict; keep uint8[nreads]; reads kept)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        pick = np.zeros(n, dtype=READ_PICK_DTYPE)
+        keep = np.zeros(n, dtype=np.uint8)
+        prm = NormParams(target, max_cv_pct, seed)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_select_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, int(bool(paired)), ctypes.addressof(prm),
+                                                  _ptr(pick), _ptr(keep), ctypes.byref(kept)))
+        return pick, keep, kept.value
+
+    def select_reads_device(self, d_words, d_offsets, nreads: int, max_read_len: int, d_pick, d_keep=None, target: int = 50,
+                            max_cv_pct: int = 10000, seed: int = 0, paired: bool = False) -> int:
+        """device buffers; d_pick holds nreads records of 16 bytes, d_keep (optional) nreads bytes -> reads kept (waits for the kernels)"""
+        prm = NormParams(target, max_cv_pct, seed)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_select_reads_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, max_read_len, int(bool(paired)),
+                                                         ctypes.addressof(prm), _ptr(d_pick), _ptr(d_keep), ctypes.byref(kept)))
+        return kept.value
+
+    def select_kept_reads(self, total_reads: int, pair_ranges=(), target: int = 50, max_cv_pct: int = 10000, seed: int = 0,
+                          out: np.ndarray = None):
+        """the reads kept in HBM; pair_ranges: [first, end) of ordinals that hold interleaved pairs, flat or as rows
+        -> (READ_PICK_DTYPE[total_reads] by read ordinal, reads decided, reads kept)"""
+        if out is None:
+            out = np.zeros(total_reads, dtype=READ_PICK_DTYPE)
+        assert out.dtype == READ_PICK_DTYPE and out.flags.c_contiguous and len(out) >= total_reads
+        ranges = np.ascontiguousarray(np.asarray(pair_ranges, dtype=np.uint64).reshape(-1))
+        assert ranges.size % 2 == 0
+        prm = NormParams(target, max_cv_pct, seed)
+        n, kept = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_select_kept_reads(self._ctx, ctypes.addressof(prm), _ptr(ranges) if ranges.size else None, ranges.size // 2,
+                                                       _ptr(out), total_reads, ctypes.byref(n), ctypes.byref(kept)))
+        return out, n.value, kept.value
+
+    def compact_reads(self, words, offsets, keep, out_words_cap: int = None):
+        """the reads with keep[i] != 0, packed again -> (words uint32[n_out_words + 4], offsets uint64[n_out_reads + 1]);
+        out_words_cap: the room to offer (SdtError SDT_EFULL when it is too small: e.needed says how many words without the pad)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        n = len(offsets) - 1
+        assert len(keep) == n
+        cap = words.size + 4 if out_words_cap is None else out_words_cap
+        out_words = np.full(max(cap, 1), 0xABABABAB, dtype=np.uint32)
+        out_offsets = np.zeros(n + 1, dtype=np.uint64)
+        nr, nw = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self.lib.sdt_gpu_compact_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, _ptr(keep), _ptr(out_words), cap,
+                                            _ptr(out_offsets), ctypes.byref(nr), ctypes.byref(nw))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.needed = nw.value
+            raise e
+        return out_words[: nw.value + 4], out_offsets[: nr.value + 1]
+
+    def compact_reads_device(self, d_words, d_offsets, nreads: int, d_keep, d_out_words, out_words_cap: int, d_out_offsets):
+        """device buffers; d_out_offsets holds nreads + 1 words -> (reads kept, words without the 4 pad words); what
+        count_reads_device of another context takes.  SdtError SDT_EFULL: e.needed = the words without the pad"""
+        nr, nw = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self.lib.sdt_gpu_compact_reads_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, _ptr(d_keep), _ptr(d_out_words),
+                                                   out_words_cap, _ptr(d_out_offsets), ctypes.byref(nr), ctypes.byref(nw))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.needed = nw.value
+            raise e
+        return nr.value, nw.value
 
     def set_read_ordinal(self, base: int, stride: int = 1):
         self._check(self.lib.sdt_gpu_set_read_ordinal(self._ctx, base, stride))

@@ -13,8 +13,19 @@
  *       prefix.readFix: one line per read:  kmers weak runs fixed
  *       prefix.edits: one line per substitution, ascending:  read pos from to   (read = ordinal + 1, pos 1-based)
  *       prefix.corrected.fa: every read of the stream, > ordinal + 1 and the sequence on one line (the letters of the 2-bit codes)
+ *   sdt-kmers normalize -s lib.cfg -K k [-p threads] [-d d] [--target C, default 50] [--max-cv PCT, default 10000, 0 = off]
+ *                       [--seed S, default 0] -o prefix
+ *       in-silico normalisation against the counted table (sdt_gpu_select_kept_reads; the rule: include/sdt_gpu.h): a read, or the two
+ *       mates of a pair, is kept with probability target / median k-mer coverage; the batches of paired files (ord_stride 2) say which
+ *       ordinals hold pairs (normsplit.c)
+ *       prefix.readPick: one line per read in stream order:  kmers median cov verdict
+ *       prefix.norm.pairs.fa: the kept pairs, read 1 then read 2, > ordinal + 1 and the sequence on one line: a p= file of a library
+ *       prefix.norm.single.fa: the kept single reads: an f= file.  Library boundaries are not preserved: the pairs of all paired
+ *       libraries go into the one pairs file.  Only pairs of files (q1=/q2=, f1=/f2=) come as ord_stride 2: an interleaved p= file
+ *       is streamed with stride 1, so its reads are decided one by one and go into the singles file.
  *
  * The query file is read and checked before the device is touched. */
+#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -24,6 +35,7 @@
 #include "libcfg.h"
 #include "seqio.h"
 #include "readstream.h"
+#include "normsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -38,6 +50,16 @@ static void usage(void)
 	        "       sdt-kmers correct -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] -o prefix\n"
 	        "           -> prefix.readFix (per read: kmers weak runs fixed), prefix.edits (per substitution: read pos from to),\n"
 	        "              prefix.corrected.fa (every read, substitution errors corrected against the counted k-mers)\n"
+	        "       sdt-kmers normalize -s lib.cfg -K k [-p threads] [-d d] [--target C, default 50]\n"
+	        "                           [--max-cv PCT, default 10000, 0 = off] [--seed S, default 0] -o prefix\n"
+	        "           a read, or the two mates of a pair, is kept with probability C / its median k-mer coverage; reads without a\n"
+	        "           k-mer, or whose counts have stdev / mean above PCT percent, are dropped; the same seed keeps the same reads\n"
+	        "           -> prefix.readPick (per read in stream order: kmers median cov verdict), prefix.norm.pairs.fa (the kept pairs,\n"
+	        "              read 1 then read 2), prefix.norm.single.fa (the kept single reads)\n"
+	        "           Pairs are the reads of q1=/q2= and f1=/f2= files.  Library boundaries are not preserved: the kept pairs of all\n"
+	        "           paired libraries go into the one pairs file.  The reads of an interleaved p= file are decided one by one, as\n"
+	        "           single reads, and go into the singles file: so do the reads of prefix.norm.pairs.fa given as p= to a second\n"
+	        "           normalize run.\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -56,13 +78,14 @@ static int inflight_retire(sdt_ctx *gpu, int down_to)
 	return 0;
 }
 
-typedef struct { sdt_ctx *gpu; unsigned long long reads; } push_state;
+typedef struct { sdt_ctx *gpu; unsigned long long reads; sdt_pair_ranges *pairs; } push_state;
 
 static int push_batch(void *user, const sdt_batch *b, uint64_t ord_base, uint64_t ord_stride)
 {
 	push_state *st = (push_state *)user;
 	st->reads += b->nreads;
 	if (!b->nreads) return 0;
+	if (st->pairs && sdt_pair_ranges_note(st->pairs, ord_base, ord_stride, b->stream_parity, b->nreads) != 0) { fprintf(stderr, "sdt-kmers: out of memory\n"); return -1; }
 	sdt_gpu_set_read_ordinal(st->gpu, ord_base, ord_stride);
 	if (b->pool_slot >= 0) {
 		uint64_t ticket = 0;
@@ -258,6 +281,93 @@ static int correct_and_write(sdt_ctx *gpu, unsigned long long reads, uint32_t mi
 	return 0;
 }
 
+/* `normalize`: the verdicts from the device, the kept batches back from HBM, the kept reads into the pairs file or the singles file */
+static int normalize_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_norm_params *prm, const sdt_pair_ranges *pairs, const char *prefix)
+{
+	const uint64_t m = reads ? reads : 1;
+	sdt_read_pick *pick = (sdt_read_pick *)malloc(m * sizeof(sdt_read_pick));
+	if (!pick) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	memset(pick, 0xFF, m * sizeof(sdt_read_pick));                           /* (an ordinal that no read has keeps verdict 0xFFFFFFFF) */
+	uint64_t got = 0, n_kept = 0, nb = 0;
+	if (sdt_gpu_select_kept_reads(gpu, prm, pairs->v, pairs->n, pick, reads, &got, &n_kept) != SDT_OK) {
+		fprintf(stderr, "sdt_gpu_select_kept_reads: %s\n", sdt_gpu_last_error());
+		return 1;
+	}
+	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu decided\n", reads, (unsigned long long)got); return 1; }
+	if (sdt_gpu_kept_batches(gpu, &nb) != SDT_OK) { fprintf(stderr, "sdt_gpu_kept_batches: %s\n", sdt_gpu_last_error()); return 1; }
+	uint32_t **bw = (uint32_t **)calloc(nb ? nb : 1, sizeof(uint32_t *));
+	uint64_t **bo = (uint64_t **)calloc(nb ? nb : 1, sizeof(uint64_t *));
+	uint32_t *at_batch = (uint32_t *)malloc(m * sizeof(uint32_t)), *at_read = (uint32_t *)malloc(m * sizeof(uint32_t));
+	if (!bw || !bo || !at_batch || !at_read) { fprintf(stderr, "sdt-kmers: out of memory\n"); return 1; }
+	memset(at_batch, 0xFF, m * sizeof(uint32_t));
+	uint64_t longest = 0;
+	for (uint64_t b = 0; b < nb; b++) {
+		uint64_t info[4];
+		if (sdt_gpu_fetch_kept_batch(gpu, b, info, NULL, 0, NULL, 0) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
+		bw[b] = (uint32_t *)malloc((info[0] ? info[0] : 1) * sizeof(uint32_t));
+		bo[b] = (uint64_t *)malloc((info[1] + 1) * sizeof(uint64_t));
+		if (!bw[b] || !bo[b]) { fprintf(stderr, "sdt-kmers: out of memory for the reads\n"); return 1; }
+		if (sdt_gpu_fetch_kept_batch(gpu, b, info, bw[b], info[0], bo[b], info[1] + 1) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
+		for (uint64_t i = 0; i < info[1]; i++) {
+			const uint64_t ord = info[2] + i * info[3];
+			if (ord >= reads) { fprintf(stderr, "sdt-kmers: a kept read has ordinal %llu of %llu\n", (unsigned long long)ord, reads); return 1; }
+			at_batch[ord] = (uint32_t)b;
+			at_read[ord] = (uint32_t)i;
+			if (bo[b][i + 1] - bo[b][i] > longest) longest = bo[b][i + 1] - bo[b][i];
+		}
+	}
+	if (longest + 64 > OB_BLOCK) { fprintf(stderr, "sdt-kmers: a read of %llu bases\n", (unsigned long long)longest); return 1; }
+	char path[3][4200];
+	snprintf(path[0], sizeof path[0], "%s.readPick", prefix);
+	snprintf(path[1], sizeof path[1], "%s.norm.pairs.fa", prefix);
+	snprintf(path[2], sizeof path[2], "%s.norm.single.fa", prefix);
+	outbuf opick, opair, osingle;
+	if (ob_open(&opick, path[0]) != 0) return 1;
+	if (ob_open(&opair, path[1]) != 0) { ob_close(&opick); return 1; }
+	if (ob_open(&osingle, path[2]) != 0) { ob_close(&opick); ob_close(&opair); return 1; }
+	unsigned long long kept = 0, n_short = 0, aberrant = 0, drawn = 0;
+	size_t cursor = 0;
+	int bad = 0;
+	for (uint64_t ord = 0; ord < reads; ord++) {
+		if (!opick.ok || !opair.ok || !osingle.ok) break;                               /* a write failed: ob_close says which */
+		if (at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
+		ob_room(&opick, 4 * 11);
+		opick.p = put_u32(opick.p, pick[ord].kmers, ' ');
+		opick.p = put_u32(opick.p, pick[ord].median, ' ');
+		opick.p = put_u32(opick.p, pick[ord].cov, ' ');
+		opick.p = put_u32(opick.p, pick[ord].verdict, '\n');
+		const uint32_t cls = pick[ord].verdict & 7u;
+		n_short += cls == 4;
+		aberrant += cls == 3;
+		drawn += cls == 2;
+		if (cls > 1) continue;
+		kept++;
+		outbuf *o = sdt_pair_ranges_holds(pairs, ord, &cursor) ? &opair : &osingle;
+		const uint64_t start = bo[at_batch[ord]][at_read[ord]], len = bo[at_batch[ord]][at_read[ord] + 1] - start;
+		ob_room(o, (size_t)len + 24);
+		o->p = sdt_put_fasta_record(o->p, ord, bw[at_batch[ord]], start, len);
+	}
+	if ((ob_close(&opick) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
+	if (kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
+	for (uint64_t b = 0; b < nb; b++) { free(bw[b]); free(bo[b]); }
+	free(bw); free(bo); free(at_batch); free(at_read); free(pick);
+	printf("%llu of %llu reads kept (%llu short, %llu aberrant, %llu dropped by draw)\n", kept, reads, n_short, aberrant, drawn);
+	return 0;
+}
+
+/* the whole of text as a decimal number of at most `most`, or the option is refused by name */
+static int parse_number(const char *opt, const char *text, unsigned long long most, unsigned long long *v)
+{
+	char *end = NULL;
+	errno = 0;
+	*v = strtoull(text, &end, 10);
+	if (text[0] < '0' || text[0] > '9' || *end || errno || *v > most) {
+		fprintf(stderr, "sdt-kmers: %s %s: a whole number from 0 to %llu is expected\n", opt, text, most);
+		return -1;
+	}
+	return 0;
+}
+
 typedef struct { char **text; uint64_t *keys; uint64_t n, cap; } query_set;
 
 /* one k-mer per line, letters ACGT (either case), exactly K of them; blank lines are skipped.  Base codes A0 C1 T2 G3. */
@@ -311,12 +421,16 @@ static int load_queries(const char *path, int K, int nw, query_set *q)
 
 int main(int argc, char **argv)
 {
-	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0 && strcmp(argv[1], "correct") != 0)) { usage(); return 255; }
-	const int do_query = strcmp(argv[1], "query") == 0, do_correct = strcmp(argv[1], "correct") == 0;
+	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0 && strcmp(argv[1], "correct") != 0 &&
+	                 strcmp(argv[1], "normalize") != 0)) { usage(); return 255; }
+	const int do_query = strcmp(argv[1], "query") == 0, do_correct = strcmp(argv[1], "correct") == 0, do_norm = strcmp(argv[1], "normalize") == 0;
+	sdt_norm_params prm = {50, 10000, 0};
 	char cfgfile[4096] = "", outname[4096] = "", qfile[4096] = "";
 	int K = 23, threads = 8, d = 0, max_k = 0, device = 0, c;
 	unsigned long min_count = do_correct ? 2 : 0;
-	static struct option longopts[] = {{"max-k", required_argument, 0, 1000}, {"device", required_argument, 0, 1001}, {0, 0, 0, 0}};
+	static struct option longopts[] = {{"max-k", required_argument, 0, 1000}, {"device", required_argument, 0, 1001},
+	                                   {"target", required_argument, 0, 1002}, {"max-cv", required_argument, 0, 1003},
+	                                   {"seed", required_argument, 0, 1004}, {0, 0, 0, 0}};
 	argv++; argc--;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:", longopts, NULL)) != -1) {
 		switch (c) {
@@ -329,10 +443,21 @@ int main(int argc, char **argv)
 		case 'c': min_count = strtoul(optarg, NULL, 10); break;
 		case 1000: max_k = atoi(optarg); break;
 		case 1001: device = atoi(optarg); break;
+		case 1002: case 1003: case 1004: {
+			const char *opt = c == 1002 ? "--target" : (c == 1003 ? "--max-cv" : "--seed");
+			unsigned long long v;
+			if (!do_norm) { fprintf(stderr, "sdt-kmers: %s belongs to normalize\n", opt); usage(); return 255; }
+			if (parse_number(opt, optarg, c == 1004 ? UINT64_MAX : UINT32_MAX, &v) != 0) return 255;
+			if (c == 1002) prm.target = (uint32_t)v;
+			else if (c == 1003) prm.max_cv_pct = (uint32_t)v;
+			else prm.seed = v;
+			break;
+		}
 		default: usage(); return 255;
 		}
 	}
 	if (!cfgfile[0] || (do_query ? !qfile[0] : !outname[0])) { usage(); return 255; }
+	if (do_norm && prm.target == 0) { fprintf(stderr, "sdt-kmers: --target must be at least 1\n"); return 255; }
 	if (max_k == 0) max_k = K <= 31 ? 31 : SDT_MAX_K;
 	if (d > 127) d = (signed char)d;                                         /* deLowKmer is a char */
 	/* pregraph.c:38-59 */
@@ -356,7 +481,9 @@ int main(int argc, char **argv)
 		fprintf(stderr, "sdt_gpu_init: %s\n", sdt_gpu_last_error());
 		return 1;
 	}
-	push_state st = {gpu, 0};
+	sdt_pair_ranges pairs;
+	memset(&pairs, 0, sizeof pairs);
+	push_state st = {gpu, 0, do_norm ? &pairs : NULL};
 	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
 	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : threads;
 	sdt_pool_enable(sdt_gpu_host_alloc, sdt_gpu_host_free, parse_threads + PUSH_DEPTH + 8);
@@ -370,7 +497,10 @@ int main(int argc, char **argv)
 	if (d && sdt_gpu_delow(gpu, d, &removed) != SDT_OK) { fprintf(stderr, "sdt_gpu_delow: %s\n", sdt_gpu_last_error()); return 1; }
 	if (d) printf("%llu kmer removed\n", (unsigned long long)removed);
 
-	if (do_correct) {
+	if (do_norm) {
+		if (normalize_and_write(gpu, st.reads, &prm, &pairs, outname) != 0) return 1;
+		sdt_pair_ranges_free(&pairs);
+	} else if (do_correct) {
 		if (correct_and_write(gpu, st.reads, (uint32_t)min_count, outname) != 0) return 1;
 	} else if (!do_query) {
 		char path[4200];

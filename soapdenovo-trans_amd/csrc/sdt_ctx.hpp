@@ -6,6 +6,7 @@
 //   sdt_mapstage.hip  the map stage (prlContig2nodes / prlRead2Ctg)
 //   sdt_search.hip    read-only questions to the counted table: batch k-mer search, per-read k-mer coverage
 //   sdt_correct.hip   substitution errors of reads corrected against the counted table; the kept reads back to the host
+//   sdt_select.hip    in-silico read normalisation against the counted table; a 2-bit stream compacted to the reads kept
 //   sdt_gpu_graph.hip the graph phases (own view of the context: sdt_internal.hpp GraphView)
 // Not part of the ABI: nothing here is visible to a caller of libsdt_gpu.so.
 #pragma once
@@ -157,7 +158,7 @@ struct sdt_ctx {
 	uint64_t *d_hi = nullptr;
 	uint64_t hi_slots = 0;
 	int hi_mode = -1;
-	unsigned long long *d_cov_flags = nullptr;      // [0] reads longer than promised, [1] slots with a high half, [2] edits (sdt_correct.hip)
+	unsigned long long *d_cov_flags = nullptr;      // [0] reads longer than promised, [1] slots with a high half, [2] edits (sdt_correct.hip) / reads kept (sdt_select.hip)
 	// timing
 	std::vector<EventPair> ev;
 	size_t ev_used = 0;
@@ -210,7 +211,7 @@ void sk_free(sdt_ctx *c);
 // ---- sdt_sharded.hip ----
 void shard_free(sdt_ctx *c);
 int sk_flush_sharded(sdt_ctx *c);
-// ---- sdt_search.hip ---- (shared with sdt_correct.hip)
+// ---- sdt_search.hip ---- (shared with sdt_correct.hip and sdt_select.hip)
 namespace sdt { struct HiView; }
 constexpr uint64_t PROFILE_CHUNK_READS = 1ULL << 22, PROFILE_CHUNK_BASES = 1ULL << 29;     // reads / bases of a host batch that are on the device at a time
 uint64_t chunk_items(uint64_t dflt);

@@ -128,6 +128,33 @@ __global__ __launch_bounds__(TPB) void k_search_kmers(const uint64_t *__restrict
 	}
 }
 
+// lower median = element (n - 1) / 2 in ascending order of the n counts in a wave's LDS strip, by radix select: every count lies in
+// [mn, mx], so all of them share the bits above the highest bit in which mn and mx differ; below it one ballot per bit and 64 k-mers
+// decides the next bit.  Uniform over the wave; the caller has fenced the strip.  (k_profile_reads, k_pick_stats)
+__device__ inline uint32_t strip_lower_median(const uint32_t *cnt, int n, uint32_t mn, uint32_t mx, int lane)
+{
+	uint32_t med = mn;
+	if (mn != mx) {
+		const int top = 31 - __clz(mn ^ mx);
+		uint32_t rank = (uint32_t)(n - 1) >> 1;
+		med = top == 31 ? 0u : mx & ~((2u << top) - 1u);
+		for (int b = top; b >= 0; b--) {
+			uint32_t zeros = 0;                                          // counts that match `med` above bit b and have bit b clear
+			for (int base = 0; base < n; base += 64) {
+				const int s = base + lane;
+				const uint32_t v = s < n ? cnt[s] : 0u;
+				const bool z = s < n && ((uint64_t)(v ^ med) >> (b + 1)) == 0 && !((v >> b) & 1u);
+				zeros += (uint32_t)__popcll(__ballot(z));
+			}
+			if (rank >= zeros) {
+				rank -= zeros;
+				med |= 1u << b;
+			}
+		}
+	}
+	return med;
+}
+
 // out[out_base + r * out_stride] for read r: a dense batch has (0, 1); the kept reads of a paired stream their read ordinals.
 // LDS: max_kmers 32-bit counts per wave.
 template <int NW>
@@ -176,27 +203,7 @@ __global__ __launch_bounds__(TPB) void k_profile_reads(const uint32_t *__restric
 		}
 		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 		__builtin_amdgcn_wave_barrier();
-		// lower median = element (n - 1) / 2 in ascending order, by radix select: every count lies in [mn, mx], so all of them share
-		// the bits above the highest bit in which mn and mx differ; below it one ballot per bit and 64 k-mers decides the next bit
-		uint32_t med = mn;
-		if (mn != mx) {
-			const int top = 31 - __clz(mn ^ mx);
-			uint32_t rank = (uint32_t)(n - 1) >> 1;
-			med = top == 31 ? 0u : mx & ~((2u << top) - 1u);
-			for (int b = top; b >= 0; b--) {
-				uint32_t zeros = 0;                                      // counts that match `med` above bit b and have bit b clear
-				for (int base = 0; base < n; base += 64) {
-					const int s = base + lane;
-					const uint32_t v = s < n ? cnt[s] : 0u;
-					const bool z = s < n && ((uint64_t)(v ^ med) >> (b + 1)) == 0 && !((v >> b) & 1u);
-					zeros += (uint32_t)__popcll(__ballot(z));
-				}
-				if (rank >= zeros) {
-					rank -= zeros;
-					med |= 1u << b;
-				}
-			}
-		}
+		const uint32_t med = strip_lower_median(cnt, n, mn, mx, lane);
 		rec.kmers = (uint32_t)n;
 		rec.found = nfound;
 		rec.solid = nsolid;
