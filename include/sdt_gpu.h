@@ -79,10 +79,24 @@ int sdt_gpu_reset(sdt_ctx *ctx);
 
 /* ---- pass 1: chop + insert/count ------------------------------------------------------------- */
 
+/* The longest read pass 1 counts.  Every batch may end up in the direct kernel, which stages 64 reads of the batch's longest
+ * length in one LDS tile of at most 64 KiB: 584 + 16 L bytes.  (The 12-bit position of a super-k-mer record, 4 095, is never the
+ * binding limit.)  A batch that holds a longer read is refused as a whole with SDT_EINVAL by the call that hands it over -- the
+ * message names the length and this limit -- and nothing of it is counted, kept (SDT_FLAG_KEEP_READS) or numbered (read ordinals):
+ * the context goes on as if the call had not been made.
+ *
+ * Below that limit the length of a batch's longest read decides the KERNEL FAMILY and never the result: reads of up to 256 k-mers
+ * take the one-lane-per-read scatter of the locality pipeline, longer ones its strip kernel, and a batch whose scatter tile no
+ * longer fits 160 KiB of LDS (about 1 130 bases while the window holds at most 49 m-mers, K = 31; about 600 bases with the second
+ * hash array of longer windows, K >= 61) is counted by the direct kernel -- silently, under SDT_FLAG_PARTITION too, and in the
+ * middle of a stream, as is a batch whose read ordinals would pass 2^34.  The tables are identical whichever way a batch went. */
+#define SDT_PASS1_MAX_READ_LEN 4059
+
 /* Replaces one `sendWorkSignal(2); sendWorkSignal(1);` pair (prlHashReads.c:523-526,600-606,615-620):
  * chopKmer4read over every read of the batch (:164-310) and put_kmerset of every record
  * (newhash.c:411-462).  Host buffers; the call stages them to the device asynchronously (double
- * buffered) and returns once the buffers may be reused.  Reads shorter than K+1 are skipped (:592). */
+ * buffered) and returns once the buffers may be reused.  Reads shorter than K+1 are skipped (:592).
+ * Longest read: SDT_PASS1_MAX_READ_LEN bases, SDT_EINVAL beyond (see there); the length picks the kernel family, never the result. */
 int sdt_gpu_push_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords,
                        const uint64_t *offsets, uint64_t nreads);
 
@@ -92,10 +106,13 @@ int sdt_gpu_push_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwor
  * the ticket of the buffer it is about to refill, not for every push (prlHashReads.c:493-620 double-buffers the same way:
  * one buffer is parsed while the threads work on the other).  Pinned host memory keeps the copy asynchronous.
  * hint_total_kmers: the caller expects this many k-mers in all, so the first small batch already takes the locality pipeline
- * (cleared by sdt_gpu_reset). */
+ * (cleared by sdt_gpu_reset).
+ * Longest read: SDT_PASS1_MAX_READ_LEN bases (see there); a batch with a longer read is SDT_EINVAL from THIS call, never from the
+ * later call in which its kernels would have been launched; no new ticket is issued for it. */
 int sdt_gpu_push_reads_async(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets, uint64_t nreads,
                              uint64_t *ticket);
-/* a batch whose reads all have read_len bases (read i starts at base i * read_len): no offsets cross PCIe, the device makes them */
+/* a batch whose reads all have read_len bases (read i starts at base i * read_len): no offsets cross PCIe, the device makes them.
+ * Longest read: read_len <= SDT_PASS1_MAX_READ_LEN (see there), SDT_EINVAL from this call beyond. */
 int sdt_gpu_push_reads_fixed_async(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, uint64_t nreads, uint64_t read_len,
                                    uint64_t *ticket);
 int sdt_gpu_push_wait(sdt_ctx *ctx, uint64_t ticket);
@@ -113,7 +130,9 @@ int sdt_gpu_set_read_ordinal(sdt_ctx *ctx, uint64_t base, uint64_t stride);
 
 /* Same, for a batch that is already resident in device memory (device pointers; the bench and the
  * multi-GPU driver use this).  Asynchronous on the context's stream.  max_read_len bounds the longest
- * read of the batch (the reference's maxReadLen, prlHashReads.c:358-366); it sizes the LDS tile. */
+ * read of the batch (the reference's maxReadLen, prlHashReads.c:358-366); it sizes the LDS tile.
+ * Longest read: max_read_len <= SDT_PASS1_MAX_READ_LEN, SDT_EINVAL beyond, before any launch and with nothing counted or numbered;
+ * max_read_len picks the kernel family, never the result.  (A max_read_len smaller than the batch's longest read is not policed.) */
 int sdt_gpu_count_reads_device(sdt_ctx *ctx, const void *d_packed_words, uint64_t nwords,
                                const void *d_offsets, uint64_t nreads, uint64_t max_read_len);
 
@@ -137,6 +156,11 @@ int sdt_gpu_finish_count(sdt_ctx *ctx, uint64_t *kmers_processed, uint64_t *node
  *                            sdt_gpu_count_reads_device; nreads may be 0).  On return the k-mers of all slices are in
  *                            the tables of their owners (asynchronously: sdt_gpu_finish_count drains).
  *   push_reads_sharded       the same for host buffers
+ *                            Longest read: what the level-1 scatter of the locality pipeline holds in 160 KiB of LDS -- about
+ *                            1 130 bases at K = 31, about 600 from K = 61 on (the single-GPU calls hand such a batch to the direct
+ *                            kernel; a rank cannot, the k-mers may be another rank's).  Beyond: SDT_EINVAL on every rank, "reads of
+ *                            <n> bases do not fit the LDS tile of the sharded path", nothing counted or numbered, the contexts go
+ *                            on.  A communicator of ONE rank counts through sdt_gpu_count_reads_device and has its limit instead.
  *   allreduce_i64            COLLECTIVE sum, for counters and the 257 kmerFreq bins (freqStat sums per-thread bins,
  *                            prlHashReads.c:1004-1014)
  *   comm_stats               bytes this rank sent / received in exchanges and the time they took on the exchange stream
@@ -402,7 +426,12 @@ int sdt_gpu_fetch_edge_bases(sdt_ctx *ctx, char *dst, uint64_t nbytes);
  *                  overruns pos_temp[20] there; such a read is reported unmapped.
  *                  max_hits >= nreads; *nhits = entries of hits[] in use (nreads + all further hits); SDT_EFULL
  *                  when hits[] is too small: *nhits says how many the batch needs.
- *   align_reads_device: the same on buffers already in device memory (outputs too). */
+ *   align_reads_device: the same on buffers already in device memory (outputs too).
+ * Limits.  A contig has fewer than 2^24 bases (positions are 24-bit): index_contigs returns SDT_EINVAL before any device work, nothing
+ * of the call is indexed.  A read of align_reads has at most 8 152 k-mers (8 151 + K bases: 8 bytes per k-mer and 40 hit slots per
+ * wavefront in 64 KiB of LDS); a batch (align_reads_device: a max_read_len) beyond is SDT_EINVAL before any launch, the index is
+ * not frozen by that call.  Below, the length only picks the launch geometry (4, 2, 1 wavefronts per workgroup, changing past 1 496
+ * and 3 032 k-mers), never the result. */
 typedef struct {
 	uint32_t contig;             /* READSET.contigID */
 	int32_t contig_offset;       /* READSET.contigOffset */
@@ -450,6 +479,11 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  * sdt_gpu_load_paths / sdt_gpu_import_paths (the counters hold path words); after sdt_gpu_release_table; on a
  * SDT_FLAG_CONTIG_INDEX context; on a context with a communicator (a shard cannot tell "absent" from "another rank's
  * bucket").  n == 0 / nreads == 0: SDT_OK, nothing touched.  The calls never write the table.
+ * Longest read of the profile, correct and select calls, every form: 16 384 k-mers (16 383 + K bases: the read's counts sit in a
+ * strip of LDS, 4 bytes per k-mer, 64 KiB per wavefront).  A host batch that holds a longer read, or a max_read_len beyond, is
+ * SDT_EINVAL from a host-side check before any launch: "reads of <n> bases do not fit the per-wavefront LDS strip", no output
+ * written.  Below, the length only picks the launch geometry (4, 2, 1 wavefronts per workgroup, changing past 4 096 and 8 192
+ * k-mers), never the result.  (Pass 1 itself takes reads of at most SDT_PASS1_MAX_READ_LEN bases; sdt_gpu_keep_reads has no limit.)
  *
  * Substitution errors corrected against the table (k-mer-spectrum correction, the usual step in front of a de Bruijn assembler).
  * Added without a change of SDT_ABI_VERSION: the five calls and sdt_read_fix are additions, nothing that existed has changed.

@@ -474,11 +474,23 @@ void sdto_sets_free(sdto_sets *S)
  * exactly as the reference's batch scan. */
 void sdto_sets_add_read(sdto_sets *S, const uint8_t *codes, int len)
 {
-	enum { MAXL = 8192 };
-	static sdto_kmer keys[MAXL];
-	static uint8_t pc[MAXL], nc[MAXL];
-	static uint64_t hb[MAXL];
-	if (len > MAXL) len = MAXL;
+	/* a read of any length: the record buffers grow to the longest read seen (never shrink, never cut a read) */
+	static sdto_kmer *keys;
+	static uint8_t *pc, *nc;
+	static uint64_t *hb;
+	static int cap;
+	if (len > cap) {
+		cap = len > 2 * cap ? len : 2 * cap;
+		free(keys); free(pc); free(nc); free(hb);
+		keys = (sdto_kmer *)malloc((size_t)cap * sizeof *keys);
+		pc = (uint8_t *)malloc((size_t)cap);
+		nc = (uint8_t *)malloc((size_t)cap);
+		hb = (uint64_t *)malloc((size_t)cap * sizeof *hb);
+		if (!keys || !pc || !nc || !hb) {
+			fprintf(stderr, "sdto_sets_add_read: no memory for a read of %d bases\n", len);
+			abort();
+		}
+	}
 	int n = sdto_chop_read(codes, len, S->K, S->nw, keys, pc, nc, hb);     /* 0 records for a short read; it still has an ordinal */
 	S->kmers_in_reads += (uint64_t)n;
 	for (int i = 0; i < n; i++) {

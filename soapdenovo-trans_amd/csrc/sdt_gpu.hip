@@ -459,6 +459,19 @@ static const uint64_t CHUNK_KMERS = 1ULL << 27;
 
 
 
+// The longest read pass 1 counts: the direct kernel stages a tile of TILE_READS reads in LDS (every batch may end up there, whatever
+// the flags say), and the tile of the longest read must fit 64 KiB.  SDT_PASS1_MAX_READ_LEN (sdt_gpu.h) is that length.
+static bool count_len_ok(uint64_t max_read_len)
+{
+	return max_read_len <= (uint64_t)SDT_PASS1_MAX_READ_LEN && tile_smem_bytes(tile_words_for(max_read_len)) <= 64 * 1024;
+}
+static int fail_count_len(uint64_t max_read_len)
+{
+	return fail(SDT_EINVAL, "read of %llu bases: pass 1 takes reads of at most %d bases (a tile of %d reads needs %zu B of LDS, limit 64 KiB); nothing of the batch was counted",
+	            (unsigned long long)max_read_len, SDT_PASS1_MAX_READ_LEN, TILE_READS,
+	            max_read_len <= (1u << 20) ? tile_smem_bytes(tile_words_for(max_read_len)) : (size_t)0);
+}
+
 static int launch_count(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_offs, uint64_t nreads,
                         uint64_t max_read_len)
 {
@@ -466,12 +479,11 @@ static int launch_count(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_o
 		return SDT_OK;
 	if (max_read_len < (uint64_t)c->K + 1)
 		return SDT_OK;                               // no read can hold a k-mer (prlHashReads.c:592)
+	if (!count_len_ok(max_read_len))                 // (before anything changes: a refused batch leaves no trace)
+		return fail_count_len(max_read_len);
 	search_cache_drop(c);
 	const int mtw = tile_words_for(max_read_len);
 	const size_t smem = tile_smem_bytes(mtw);
-	if (smem > 64 * 1024)
-		return fail(SDT_EINVAL, "max read length %llu needs %zu B of LDS per tile (limit 64 KiB)",
-		            (unsigned long long)max_read_len, smem);
 	const uint64_t per_read = max_read_len - c->K + 1;
 	// The locality pipeline is opt-in in round 1: on MI355X it measures 11 G k-mers/s against the direct
 	// kernel's 19.5 G (profiles/r1/partition_pipeline_50M.md has the per-stage rates and what has to change).
@@ -562,6 +574,10 @@ static int push_reads_enqueue(sdt_ctx *c, const uint32_t *packed_words, uint64_t
 	}
 	if (bad)
 		return fail(SDT_EINVAL, "offsets not monotonic");
+	// the length launch_count refuses is refused HERE, by the call that hands the batch over and before anything of it is staged,
+	// kept or numbered: the launch may be deferred into a later call, which could only report it with the batch half accounted for
+	if (maxlen >= Kp1 && !count_len_ok(maxlen))
+		return fail_count_len(maxlen);
 	const uint64_t total_bases = fixed_len ? nreads * fixed_len : offsets[nreads];
 	if (((total_bases + 15) >> 4) + TAIL_PAD > nwords)
 		return fail(SDT_EINVAL, "packed_words too short: need %llu words incl. %d pad words, got %llu",

@@ -83,6 +83,13 @@ CASES = [
     # K = 127: the (K+1)-mers of length-1 edges are 128 bases long, where the reference's reverseComplement misfires
     # (its length parameter is a char); *.preArc shows it
     dict(name="alleles250_k127_p5_127mer", variant=127, K=127, p=5, d=0, n=6000, L=250, T=5, kind="alleles"),
+    # long reads (970 k-mers and more per read: far past the 256 of the one-lane-per-read scatter).  With 1-word keys the strip
+    # kernel of the locality pipeline still takes them; at K = 63 its second hash array no longer fits the LDS and the batch is
+    # counted by the direct kernel whatever the flags say.  1 000 bases is as far as the reference goes: its pregraph ran reads of
+    # up to 1 023 bases to completion and aborted in malloc's own checks ("corrupted size vs. prev_size") on 1 200 and 1 500, so
+    # nothing longer can have a reference golden.  Transcripts of at least 1 000 bases (tx_lo), so that no read is cut short.
+    dict(name="se1000_k31_p4", variant=31, K=31, p=4, d=0, n=250, L=1000, T=5, kind="se", tx_lo=1000),
+    dict(name="se1000_k63_p3_127mer", variant=127, K=63, p=3, d=0, n=250, L=1000, T=5, kind="se", tx_lo=1000),
 ]
 
 
@@ -90,7 +97,7 @@ def make_case(c):
     cdir = os.path.join(HERE, "cases", c["name"])
     shutil.rmtree(cdir, ignore_errors=True)
     os.makedirs(cdir)
-    tx = synth.make_transcriptome(c["T"], seed=100 + len(c["name"]))
+    tx = synth.make_transcriptome(c["T"], seed=100 + len(c["name"]), lo=c.get("tx_lo", 500))
     tmp = tempfile.mkdtemp(prefix="sdtgold_")
     files = []
     max_rd_len = c.get("max_rd_len", c["L"])

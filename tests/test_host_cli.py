@@ -54,7 +54,10 @@ def test_reader_matches_reference_ingest(pkg, tmp_path, name, threads, chunk, po
 
 
 @pytest.mark.parametrize("nranks", [2, 3, 8])
-@pytest.mark.parametrize("name", ["pe150_k31_p8", "se100_k23_p8_d1", "dirty_ragged_k25_cut80"])
+@pytest.mark.parametrize("name", ["pe150_k31_p8", "se100_k23_p8_d1", "dirty_ragged_k25_cut80",
+                                  # 1 000-base reads: a chunk of 3 000 bytes holds one record and a half (the reader runs on the CPU: both
+                                  # long-read cases go through, whatever the sharded count stage makes of them)
+                                  "se1000_k31_p4", "se1000_k63_p3_127mer"])
 def test_multi_rank_reader_parses_every_chunk_once_and_agrees_on_ordinals(pkg, tmp_path, name, nranks):
     """`sdt-pregraph --gpus N` without a GPU: the pass as one rank walks it (the ordinals of sdt_stream_reads are the truth) against the
     pass as each of N ranks walks it with foreign chunks SKIPPED (seqio.h: sdt_read_shard_skip_foreign): every chunk parsed by exactly its
@@ -180,8 +183,15 @@ def test_cli_kmerfreq_bit_identical(pkg, tmp_path, name, second_pass):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("gpus,second", [(2, "ranks"), (3, "ranks"), (4, "ranks"), (8, "ranks"), (3, "one-chunk"), (2, "rank0"), (3, "host")])
-@pytest.mark.parametrize("name", ["se100_k23_p8_d1", "pe150_k31_p8", "se250_k63_p8_127mer", "dirty_ragged_k25_cut80"])
+@pytest.mark.parametrize("name,gpus,second",
+                         [(name, gpus, second) for name in ["se100_k23_p8_d1", "pe150_k31_p8", "se250_k63_p8_127mer", "dirty_ragged_k25_cut80"]
+                          for gpus, second in [(2, "ranks"), (3, "ranks"), (4, "ranks"), (8, "ranks"), (3, "one-chunk"), (2, "rank0"), (3, "host")]] +
+                         # 1 000-base reads (970 k-mers: the strip kernel behind the sharded scatter, just under its LDS bound) through
+                         # count_reads_sharded: ranks that map their own reads, rank 0 mapping all, and the whole input as one chunk.
+                         # se1000_k63_p3_127mer is left out on purpose: at K = 63 such reads do not fit the scatter's LDS, the sharded path
+                         # returns SDT_EINVAL and `--gpus N` stops where `--gpus 1` runs
+                         # (tests/test_read_lengths.py::test_sharded_path_refuses_what_the_pipeline_cannot_take pins that refusal)
+                         [("se1000_k31_p4", 2, "ranks"), ("se1000_k31_p4", 3, "ranks"), ("se1000_k31_p4", 3, "one-chunk"), ("se1000_k31_p4", 2, "rank0")])
 def test_cli_multi_process_all_files_identical(pkg, tmp_path, name, gpus, second):
     """`sdt-pregraph --gpus N`: one process per rank (forked before HIP is touched; here all on the one GPU of the box over
     the shared-memory transport), the read stream cut into small chunks that alternate between the ranks, pass 1 bucket
@@ -220,16 +230,22 @@ def test_cli_multi_process_all_files_identical(pkg, tmp_path, name, gpus, second
 @pytest.mark.parametrize("K,p,d,L,variant,seed,gpus", [(25, 3, 0, 90, 31, 1, 1), (31, 5, 1, 120, 31, 2, 1), (45, 2, 0, 150, 63, 3, 1),
                                                        (63, 7, 0, 200, 63, 4, 1), (71, 4, 0, 200, 127, 5, 1), (21, 1, 2, 100, 31, 6, 1),
                                                        (31, 4, 0, 150, 31, 7, 2), (47, 3, 1, 150, 63, 8, 3),
-                                                       (31, 6, 0, 150, 31, 9, 0), (55, 2, 0, 250, 63, 10, 0), (95, 3, 0, 250, 127, 11, 0)])
+                                                       (31, 6, 0, 150, 31, 9, 0), (55, 2, 0, 250, 63, 10, 0), (95, 3, 0, 250, 127, 11, 0),
+                                                       # long reads (fewer of them, off transcripts longer than a read): past what the locality
+                                                       # pipeline takes, and the longest read pass 1 counts at all (include/sdt_gpu.h:
+                                                       # SDT_PASS1_MAX_READ_LEN).  The reference itself does not survive such reads: these
+                                                       # rows have the oracle only
+                                                       (31, 4, 0, 2000, 31, 12, 1), (63, 3, 0, 4059, 63, 13, 1)])
 def test_cli_against_oracle_on_fresh_inputs(pkg, synth, tmp_path, K, p, d, L, variant, seed, gpus):
     """beyond the 12 fixtures: seeded synthetic reads (ragged, with errors, a few hairpins) through `sdt-pregraph` on the GPU
     (two configurations with 2 and 3 ranks, bucket sharded; gpus = 0: one GPU with the locality pipeline forced) and through the C oracle's restatement of the WHOLE of pregraph (pass 1, -d, the three cleaning passes, kmer2edges, the
     second read pass) -- the oracle is pinned file by file against the reference on the fixtures
     (tests/test_oracle_vs_reference.py), so agreement here is agreement with the reference on inputs it never saw"""
     import oracle_binding as ob
-    tx = synth.make_transcriptome(14, seed=seed)
-    codes, offs = synth.sample_reads(*tx, n_reads=3000, read_len=L, seed=seed + 100, err=0.004, ragged=True)
-    extra = []
+    long_reads = L > 1000
+    tx = synth.make_transcriptome(14, seed=seed, **(dict(lo=L + 100, hi=2 * L) if long_reads else {}))
+    codes, offs = synth.sample_reads(*tx, n_reads=300 if long_reads else 3000, read_len=L, seed=seed + 100, err=0.004, ragged=True)
+    extra = [tx[0][7:7 + L].copy()] if long_reads else []        # (one read of exactly max_rd_len bases)
     for j in range(4):                                    # hairpins: X + rc(X) -> self-complementary chains
         x = tx[0][150 * j + 11: 150 * j + 11 + L // 2]
         extra += [np.concatenate([x, (x[::-1] ^ 2)]).astype(np.uint8)] * 4
@@ -338,6 +354,20 @@ def test_cli_usage_and_errors(pkg, tmp_path):
     r = subprocess.run([exe, "-s", str(tmp_path / "missing.cfg"), "-o", str(tmp_path / "o")], capture_output=True,
                        text=True)
     assert r.returncode != 0 and "Cannot open" in r.stdout
+    # a read longer than pass 1 takes (4 059 bases, include/sdt_gpu.h) under a max_rd_len that lets it through: the library's refusal
+    # on stderr, a failing exit code, and no output file begun
+    rng = np.random.default_rng(3)
+    letters = np.frombuffer(b"ACTG", dtype=np.uint8)
+    with open(tmp_path / "long.fq", "w") as fq:
+        for i, n in enumerate([150] * 50 + [4500] + [150] * 50):
+            r = letters[rng.integers(0, 4, size=n)].tobytes().decode()
+            fq.write(f"@r{i}\n{r}\n+\n{'I' * n}\n")
+    (tmp_path / "long.cfg").write_text(f"max_rd_len=5000\n[LIB]\navg_ins=200\nreverse_seq=0\nasm_flags=3\nq={tmp_path}/long.fq\n")
+    r = subprocess.run([exe, "pregraph", "-s", str(tmp_path / "long.cfg"), "-K", "31", "-p", "4", "-o", str(tmp_path / "long")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "4500 bases" in r.stderr and "at most 4059 bases" in r.stderr, r.stderr[-2000:]
+    assert sorted(f.name for f in tmp_path.iterdir() if f.name.startswith("long.") and f.name not in ("long.fq", "long.cfg")) == []
 
 
 def first_ordinals(info, K, codes, offs):

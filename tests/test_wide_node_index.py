@@ -82,7 +82,10 @@ def test_cli_past_the_node_limit_stays_on_the_device(pkg, tmp_path, name, base):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("base", [None, BASE], ids=["base0", "base2^32+12345"])
-@pytest.mark.parametrize("name", ["pe150_k31_p8", "se250_k63_p8_127mer", "dirty_ragged_k25_cut80"])
+@pytest.mark.parametrize("name", ["pe150_k31_p8", "se250_k63_p8_127mer", "dirty_ragged_k25_cut80",
+                                  # 1 000-base reads through the sharded count stage.  (Not se1000_k63_p3_127mer: the sharded path refuses
+                                  # 1 000-base reads at K = 63 with SDT_EINVAL, tests/test_read_lengths.py pins it.)
+                                  "se1000_k31_p4"])
 def test_cli_ranks_past_the_node_limit_use_rank0s_device_table(pkg, tmp_path, name, base):
     """`--gpus 3`: past the node limit the shards go into rank 0's device table and the graph phases run there in the 64-bit form"""
     info = gu.load_case(name)
