@@ -479,7 +479,7 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  * sdt_gpu_load_paths / sdt_gpu_import_paths (the counters hold path words); after sdt_gpu_release_table; on a
  * SDT_FLAG_CONTIG_INDEX context; on a context with a communicator (a shard cannot tell "absent" from "another rank's
  * bucket").  n == 0 / nreads == 0: SDT_OK, nothing touched.  The calls never write the table.
- * Longest read of the profile, correct and select calls, every form: 16 384 k-mers (16 383 + K bases: the read's counts sit in a
+ * Longest read of the profile, correct, select and trim calls, every form: 16 384 k-mers (16 383 + K bases: the read's counts sit in a
  * strip of LDS, 4 bytes per k-mer, 64 KiB per wavefront).  A host batch that holds a longer read, or a max_read_len beyond, is
  * SDT_EINVAL from a host-side check before any launch: "reads of <n> bases do not fit the per-wavefront LDS strip", no output
  * written.  Below, the length only picks the launch geometry (4, 2, 1 wavefronts per workgroup, changing past 4 096 and 8 192
@@ -562,11 +562,51 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  *   compact_reads_device: buffers on the device; d_out_words must not overlap the input.  The call waits for the kernels.  Its
  *                   outputs are what sdt_gpu_count_reads_device of another context takes (nwords = *n_out_words + 4).
  * The select calls follow the state rules and return codes of the profile calls (nreads == 0: SDT_OK, nothing touched).  Nothing
- * here writes the table or the kept reads. */
+ * here writes the table or the kept reads.
+ *
+ * Reads trimmed to their longest solid stretch against the table: what correct_reads cannot fix (two errors closer than K, a
+ * candidate with no or several valid alternatives, indels, chimeric junctions) is cut away, so that those k-mers do not go back into
+ * pass 1.  Added without a change of SDT_ABI_VERSION: the five calls, the two structs and the flag are additions.  The rule is
+ * deterministic, in integers only, decides every read on its own and only reads the table.  A read of L bases has n = L - K + 1
+ * k-mers (0 for L < K) with the counts c[j] that profile_reads sees (32-bit, unsaturated, absent = 0; the deleted flag is ignored).
+ *     k-mer j is WEAK iff c[j] < min_count (min_count == 0: nothing is weak), SOLID otherwise
+ *     median   the lower median of c[], as sdt_read_cov.median;  weak = the weak k-mers of the read as it came
+ *     SDT_TRIM_CORRECTED (bit 0 of flags): every run of weak k-mers that sdt_gpu_correct_reads would fix with the same min_count (a
+ *              candidate run with exactly one valid alternative) counts as solid from then on.  A substitution at p changes exactly
+ *              the k-mers of its own run: the corrected read's weak mask is the original mask with the fixed runs cleared, nothing
+ *              more is looked up.  weak and median still describe the read as it came; start and len are in the read's own
+ *              coordinates, which a substitution does not shift.
+ *     a STRETCH is a maximal run [a, a + s) of solid k-mers; it covers bases [a, a + s + K - 1)
+ * The first line that applies decides the read; (start, len) are the kept bases:
+ *     4  short     n == 0                                                                          0, 0
+ *     0  whole     no weak k-mer is left                                                           0, L
+ *     1  gated     min_cov > 0 and median < min_cov (a thin transcript's weak k-mers are not
+ *                  evidence of error)                                                              0, L
+ *     3  dropped   there is no stretch, or the longest covers fewer than min_len bases             0, 0
+ *     2  trimmed   otherwise: the longest stretch, the first among equals                          a, s + K - 1
+ * A stretch covers at least K bases: a min_len of K or less never binds.  An unknown bit in flags is SDT_EINVAL.
+ *   trim_reads:     trim[i] for read i of a batch (packed as for sdt_gpu_push_reads); keep (may be NULL): keep[i] = len > 0;
+ *                   *n_kept = reads with len > 0.  The batch is staged in pieces as for profile_reads.
+ *   trim_reads_device: buffers already on the device (d_trim nreads records, d_keep nreads bytes or NULL); max_read_len as for
+ *                   profile_reads_device: a longer read gets kmers = 0xFFFFFFFF, the other fields 0, verdict 4, keep 0, and the
+ *                   call returns SDT_EINVAL with every other record complete.  The call waits for the kernel to know *n_kept.
+ *   trim_kept_reads: the reads kept in HBM, batch by batch; trim[] by READ ORDINAL like profile_kept_reads (SDT_EFULL, nothing
+ *                   written, when a kept read's ordinal is >= out_capacity; records of ordinals that no kept read has are left
+ *                   untouched).  No pair logic: mates are trimmed independently.  The kept reads are NOT changed.
+ *   compact_trimmed: compact_reads with a range per read: read r contributes bases [offsets[r] + start, + len) of trim[r], len == 0
+ *                   leaves it out.  Pad, zero tail, SDT_EFULL and the sizes of the outputs as for compact_reads.  start + len
+ *                   beyond the read is SDT_EINVAL before anything is staged.  Any state, any kind of context.
+ *   compact_trimmed_device: buffers on the device; d_out_words must not overlap the input.  It cannot refuse a range: start and len
+ *                   are clamped to the read, nothing outside the stream is read.  Its outputs are what sdt_gpu_count_reads_device
+ *                   of another context takes (nwords = *n_out_words + 4).
+ * The trim calls follow the state rules and return codes of the profile calls (nreads == 0: SDT_OK, nothing touched). */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
 typedef struct { uint32_t target, max_cv_pct; uint64_t seed; } sdt_norm_params;
+typedef struct { uint32_t kmers, weak, median, start, len, verdict; } sdt_read_trim;
+typedef struct { uint32_t min_count, min_cov, min_len, flags; } sdt_trim_params;
+#define SDT_TRIM_CORRECTED 1u   /* sdt_trim_params.flags: runs that sdt_gpu_correct_reads would fix count as solid */
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -602,6 +642,20 @@ int sdt_gpu_compact_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t n
 int sdt_gpu_compact_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
                                  const void *d_keep, void *d_out_words, uint64_t out_words_cap, void *d_out_offsets,
                                  uint64_t *n_out_reads, uint64_t *n_out_words);
+int sdt_gpu_trim_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                       uint64_t nreads, const sdt_trim_params *params, sdt_read_trim *trim, uint8_t *keep,
+                       uint64_t *n_kept);
+int sdt_gpu_trim_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                              uint64_t max_read_len, const sdt_trim_params *params, void *d_trim, void *d_keep,
+                              uint64_t *n_kept);
+int sdt_gpu_trim_kept_reads(sdt_ctx *ctx, const sdt_trim_params *params, sdt_read_trim *trim, uint64_t out_capacity,
+                            uint64_t *nreads, uint64_t *n_kept);
+int sdt_gpu_compact_trimmed(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                            uint64_t nreads, const sdt_read_trim *trim, uint32_t *out_words, uint64_t out_words_cap,
+                            uint64_t *out_offsets, uint64_t *n_out_reads, uint64_t *n_out_words);
+int sdt_gpu_compact_trimmed_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                                   const void *d_trim, void *d_out_words, uint64_t out_words_cap, void *d_out_offsets,
+                                   uint64_t *n_out_reads, uint64_t *n_out_words);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

@@ -140,6 +140,16 @@ _ABI = [
                                          _c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_compact_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint64,
                                                 _c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_trim_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                      _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_trim_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                             _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_trim_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64),
+                                           _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_compact_trimmed", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                           _c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_compact_trimmed_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                                  _c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -152,11 +162,20 @@ READ_FIX_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "weak", "runs", "fi
 READ_PICK_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "median", "cov", "verdict")])
 PICK_KEPT, PICK_KEPT_DRAW, PICK_DROPPED_DRAW, PICK_ABERRANT, PICK_SHORT = range(5)
 PICK_OWN_ABERRANT = 1 << 4
+# sdt_read_trim (include/sdt_gpu.h): one record per read of a trim; the kept bases are [start, start + len) of the read
+READ_TRIM_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "weak", "median", "start", "len", "verdict")])
+TRIM_WHOLE, TRIM_GATED, TRIM_TRIMMED, TRIM_DROPPED, TRIM_SHORT = range(5)
+TRIM_CORRECTED = 1                                       # SDT_TRIM_CORRECTED
 
 
 class NormParams(_c.Structure):
     """sdt_norm_params"""
     _fields_ = [("target", _c.c_uint32), ("max_cv_pct", _c.c_uint32), ("seed", _c.c_uint64)]
+
+
+class TrimParams(_c.Structure):
+    """sdt_trim_params"""
+    _fields_ = [("min_count", _c.c_uint32), ("min_cov", _c.c_uint32), ("min_len", _c.c_uint32), ("flags", _c.c_uint32)]
 
 _lib = None
 
@@ -709,6 +728,72 @@ class PregraphGPU:
         nr, nw = ctypes.c_uint64(), ctypes.c_uint64()
         rc = self.lib.sdt_gpu_compact_reads_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, _ptr(d_keep), _ptr(d_out_words),
                                                    out_words_cap, _ptr(d_out_offsets), ctypes.byref(nr), ctypes.byref(nw))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.needed = nw.value
+            raise e
+        return nr.value, nw.value
+
+    # -- reads trimmed to their longest solid stretch against the counted table (the rule: include/sdt_gpu.h)
+    def trim_reads(self, words, offsets, min_count: int = 2, min_cov: int = 0, min_len: int = 0, flags: int = 0):
+        """-> (READ_TRIM_DTYPE[nreads]: kmers, weak, median, start, len, verdict; keep uint8[nreads]; reads with len > 0)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        trim = np.zeros(n, dtype=READ_TRIM_DTYPE)
+        keep = np.zeros(n, dtype=np.uint8)
+        prm = TrimParams(min_count, min_cov, min_len, flags)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_trim_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, ctypes.addressof(prm), _ptr(trim), _ptr(keep),
+                                                ctypes.byref(kept)))
+        return trim, keep, kept.value
+
+    def trim_reads_device(self, d_words, d_offsets, nreads: int, max_read_len: int, d_trim, d_keep=None, min_count: int = 2, min_cov: int = 0,
+                          min_len: int = 0, flags: int = 0) -> int:
+        """device buffers; d_trim holds nreads records of 24 bytes, d_keep (optional) nreads bytes -> reads with len > 0 (waits for the kernel)"""
+        prm = TrimParams(min_count, min_cov, min_len, flags)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_trim_reads_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, max_read_len, ctypes.addressof(prm),
+                                                       _ptr(d_trim), _ptr(d_keep), ctypes.byref(kept)))
+        return kept.value
+
+    def trim_kept_reads(self, total_reads: int, min_count: int = 2, min_cov: int = 0, min_len: int = 0, flags: int = 0, out: np.ndarray = None):
+        """the reads kept in HBM -> (READ_TRIM_DTYPE[total_reads] by read ordinal, reads trimmed, reads with len > 0)"""
+        if out is None:
+            out = np.zeros(total_reads, dtype=READ_TRIM_DTYPE)
+        assert out.dtype == READ_TRIM_DTYPE and out.flags.c_contiguous and len(out) >= total_reads
+        prm = TrimParams(min_count, min_cov, min_len, flags)
+        n, kept = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_trim_kept_reads(self._ctx, ctypes.addressof(prm), _ptr(out), total_reads, ctypes.byref(n), ctypes.byref(kept)))
+        return out, n.value, kept.value
+
+    def compact_trimmed(self, words, offsets, trim, out_words_cap: int = None):
+        """bases [start, start + len) of every read with len > 0, packed again -> (words uint32[n_out_words + 4], offsets
+        uint64[n_out_reads + 1]); out_words_cap: the room to offer (SdtError SDT_EFULL when it is too small: e.needed says how many
+        words without the pad)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        trim = np.ascontiguousarray(trim, dtype=READ_TRIM_DTYPE)
+        n = len(offsets) - 1
+        assert len(trim) == n
+        cap = words.size + 4 if out_words_cap is None else out_words_cap
+        out_words = np.full(max(cap, 1), 0xABABABAB, dtype=np.uint32)
+        out_offsets = np.zeros(n + 1, dtype=np.uint64)
+        nr, nw = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self.lib.sdt_gpu_compact_trimmed(self._ctx, _ptr(words), words.size, _ptr(offsets), n, _ptr(trim), _ptr(out_words), cap,
+                                              _ptr(out_offsets), ctypes.byref(nr), ctypes.byref(nw))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.needed = nw.value
+            raise e
+        return out_words[: nw.value + 4], out_offsets[: nr.value + 1]
+
+    def compact_trimmed_device(self, d_words, d_offsets, nreads: int, d_trim, d_out_words, out_words_cap: int, d_out_offsets):
+        """device buffers; d_out_offsets holds nreads + 1 words -> (reads with len > 0, words without the 4 pad words); what
+        count_reads_device of another context takes.  SdtError SDT_EFULL: e.needed = the words without the pad"""
+        nr, nw = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self.lib.sdt_gpu_compact_trimmed_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, _ptr(d_trim), _ptr(d_out_words),
+                                                     out_words_cap, _ptr(d_out_offsets), ctypes.byref(nr), ctypes.byref(nw))
         if rc != SDT_OK:
             e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
             e.needed = nw.value

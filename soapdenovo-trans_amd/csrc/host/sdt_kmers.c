@@ -23,6 +23,15 @@
  *       prefix.norm.single.fa: the kept single reads: an f= file.  Library boundaries are not preserved: the pairs of all paired
  *       libraries go into the one pairs file.  Only pairs of files (q1=/q2=, f1=/f2=) come as ord_stride 2: an interleaved p= file
  *       is streamed with stride 1, so its reads are decided one by one and go into the singles file.
+ *   sdt-kmers trim -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--min-cov Z, default 0] [--min-len L, default 0]
+ *                  [--correct] -o prefix
+ *       every read cut back to its longest solid stretch against the counted table (sdt_gpu_trim_kept_reads; the rule:
+ *       include/sdt_gpu.h); with --correct the substitutions of `correct` are made first (sdt_gpu_correct_kept_reads and
+ *       SDT_TRIM_CORRECTED).  Mates are trimmed independently; pairs as for normalize (normsplit.c, trimsplit.c)
+ *       prefix.readTrim: one line per read in stream order:  kmers weak median start len verdict
+ *       prefix.trim.pairs.fa: both mates of the pairs of which both survive, read 1 then read 2, > ordinal + 1 and the kept bases
+ *       prefix.trim.single.fa: every other surviving read, the mate of a dropped read among them
+ *       prefix.edits (--correct): as `correct` writes it
  *
  * The query file is read and checked before the device is touched. */
 #include <errno.h>
@@ -36,6 +45,7 @@
 #include "seqio.h"
 #include "readstream.h"
 #include "normsplit.h"
+#include "trimsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -60,6 +70,17 @@ static void usage(void)
 	        "           paired libraries go into the one pairs file.  The reads of an interleaved p= file are decided one by one, as\n"
 	        "           single reads, and go into the singles file: so do the reads of prefix.norm.pairs.fa given as p= to a second\n"
 	        "           normalize run.\n"
+	        "       sdt-kmers trim -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--min-cov Z, default 0]\n"
+	        "                      [--min-len L, default 0] [--correct] -o prefix\n"
+	        "           every read is cut back to its longest stretch of k-mers counted min_count times or more (the first among equals);\n"
+	        "           a read without such a stretch, or whose longest covers fewer than L bases, is dropped; a read whose median k-mer\n"
+	        "           coverage is below Z stays whole; --correct first corrects substitution errors as `correct` does\n"
+	        "           -> prefix.readTrim (per read in stream order: kmers weak median start len verdict; 0 whole, 1 gated, 2 trimmed,\n"
+	        "              3 dropped, 4 short), prefix.trim.pairs.fa (read 1 then read 2 of the pairs of which both mates survive),\n"
+	        "              prefix.trim.single.fa (every other surviving read, the mate of a dropped read among them), with --correct\n"
+	        "              prefix.edits (per substitution: read pos from to)\n"
+	        "           Pairs are the reads of q1=/q2= and f1=/f2= files, mates are trimmed independently; library boundaries go and\n"
+	        "           the reads of a p= file are single reads, as for normalize.\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -184,16 +205,57 @@ static char *put_u64(char *p, uint64_t v, char sep)
 	return p;
 }
 
-/* `correct`: the records and the edits from the device, the kept batches back from HBM, the edits applied here */
-static int correct_and_write(sdt_ctx *gpu, unsigned long long reads, uint32_t min_count, const char *prefix)
+/* the kept batches back from HBM, and where every ordinal's read is */
+typedef struct {
+	uint64_t nb, longest;
+	uint32_t **bw;                                                           /* words of batch b */
+	uint64_t **bo;                                                           /* offsets of batch b */
+	uint32_t *at_batch, *at_read;                                            /* by ordinal; at_batch 0xFFFFFFFF: no kept read has it */
+} kept_reads;
+
+static int kept_fetch(sdt_ctx *gpu, unsigned long long reads, kept_reads *k)
 {
-	static const char letters[4] = {'A', 'C', 'T', 'G'};
 	const uint64_t m = reads ? reads : 1;
-	sdt_read_fix *fix = (sdt_read_fix *)calloc(m, sizeof(sdt_read_fix));
+	memset(k, 0, sizeof *k);
+	if (sdt_gpu_kept_batches(gpu, &k->nb) != SDT_OK) { fprintf(stderr, "sdt_gpu_kept_batches: %s\n", sdt_gpu_last_error()); return 1; }
+	k->bw = (uint32_t **)calloc(k->nb ? k->nb : 1, sizeof(uint32_t *));
+	k->bo = (uint64_t **)calloc(k->nb ? k->nb : 1, sizeof(uint64_t *));
+	k->at_batch = (uint32_t *)malloc(m * sizeof(uint32_t));
+	k->at_read = (uint32_t *)malloc(m * sizeof(uint32_t));
+	if (!k->bw || !k->bo || !k->at_batch || !k->at_read) { fprintf(stderr, "sdt-kmers: out of memory\n"); return 1; }
+	memset(k->at_batch, 0xFF, m * sizeof(uint32_t));
+	for (uint64_t b = 0; b < k->nb; b++) {
+		uint64_t info[4];
+		if (sdt_gpu_fetch_kept_batch(gpu, b, info, NULL, 0, NULL, 0) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
+		k->bw[b] = (uint32_t *)malloc((info[0] ? info[0] : 1) * sizeof(uint32_t));
+		k->bo[b] = (uint64_t *)malloc((info[1] + 1) * sizeof(uint64_t));
+		if (!k->bw[b] || !k->bo[b]) { fprintf(stderr, "sdt-kmers: out of memory for the reads\n"); return 1; }
+		if (sdt_gpu_fetch_kept_batch(gpu, b, info, k->bw[b], info[0], k->bo[b], info[1] + 1) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
+		for (uint64_t i = 0; i < info[1]; i++) {
+			const uint64_t ord = info[2] + i * info[3];
+			if (ord >= reads) { fprintf(stderr, "sdt-kmers: a kept read has ordinal %llu of %llu\n", (unsigned long long)ord, reads); return 1; }
+			k->at_batch[ord] = (uint32_t)b;
+			k->at_read[ord] = (uint32_t)i;
+			if (k->bo[b][i + 1] - k->bo[b][i] > k->longest) k->longest = k->bo[b][i + 1] - k->bo[b][i];
+		}
+	}
+	if (k->longest + 64 > OB_BLOCK) { fprintf(stderr, "sdt-kmers: a read of %llu bases\n", (unsigned long long)k->longest); return 1; }
+	return 0;
+}
+
+static void kept_free(kept_reads *k)
+{
+	for (uint64_t b = 0; b < k->nb; b++) { free(k->bw[b]); free(k->bo[b]); }
+	free(k->bw); free(k->bo); free(k->at_batch); free(k->at_read);
+}
+
+/* sdt_gpu_correct_kept_reads: fix[] by ordinal and the edits, ascending, in a list of the size they need */
+static int correct_kept(sdt_ctx *gpu, unsigned long long reads, uint32_t min_count, sdt_read_fix *fix, uint64_t **edits_out, uint64_t *n_edits_out)
+{
 	/* (room for one edit per read at first: too little means the whole correction runs again just to hand over the edits) */
-	uint64_t cap = reads + 1024, n_edits = 0, got = 0, nb = 0;
+	uint64_t cap = reads + 1024, n_edits = 0, got = 0;
 	uint64_t *edits = (uint64_t *)malloc(cap * sizeof(uint64_t));
-	if (!fix || !edits) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	if (!edits) { fprintf(stderr, "sdt-kmers: out of memory for %llu edits\n", (unsigned long long)cap); return 1; }
 	int rc = sdt_gpu_correct_kept_reads(gpu, min_count, fix, reads, &got, edits, cap, &n_edits);
 	if (rc == SDT_EFULL && n_edits > cap) {                                  /* more edits than guessed: once more with room for all */
 		cap = n_edits;
@@ -204,30 +266,41 @@ static int correct_and_write(sdt_ctx *gpu, unsigned long long reads, uint32_t mi
 	}
 	if (rc != SDT_OK) { fprintf(stderr, "sdt_gpu_correct_kept_reads: %s\n", sdt_gpu_last_error()); return 1; }
 	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu corrected\n", reads, (unsigned long long)got); return 1; }
-	/* the kept batches, and where every ordinal's read is */
-	if (sdt_gpu_kept_batches(gpu, &nb) != SDT_OK) { fprintf(stderr, "sdt_gpu_kept_batches: %s\n", sdt_gpu_last_error()); return 1; }
-	uint32_t **bw = (uint32_t **)calloc(nb ? nb : 1, sizeof(uint32_t *));
-	uint64_t **bo = (uint64_t **)calloc(nb ? nb : 1, sizeof(uint64_t *));
-	uint32_t *at_batch = (uint32_t *)malloc(m * sizeof(uint32_t)), *at_read = (uint32_t *)malloc(m * sizeof(uint32_t));
-	if (!bw || !bo || !at_batch || !at_read) { fprintf(stderr, "sdt-kmers: out of memory\n"); return 1; }
-	memset(at_batch, 0xFF, m * sizeof(uint32_t));
-	uint64_t longest = 0;
-	for (uint64_t b = 0; b < nb; b++) {
-		uint64_t info[4];
-		if (sdt_gpu_fetch_kept_batch(gpu, b, info, NULL, 0, NULL, 0) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
-		bw[b] = (uint32_t *)malloc((info[0] ? info[0] : 1) * sizeof(uint32_t));
-		bo[b] = (uint64_t *)malloc((info[1] + 1) * sizeof(uint64_t));
-		if (!bw[b] || !bo[b]) { fprintf(stderr, "sdt-kmers: out of memory for the reads\n"); return 1; }
-		if (sdt_gpu_fetch_kept_batch(gpu, b, info, bw[b], info[0], bo[b], info[1] + 1) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
-		for (uint64_t i = 0; i < info[1]; i++) {
-			const uint64_t ord = info[2] + i * info[3];
-			if (ord >= reads) { fprintf(stderr, "sdt-kmers: a kept read has ordinal %llu of %llu\n", (unsigned long long)ord, reads); return 1; }
-			at_batch[ord] = (uint32_t)b;
-			at_read[ord] = (uint32_t)i;
-			if (bo[b][i + 1] - bo[b][i] > longest) longest = bo[b][i + 1] - bo[b][i];
-		}
-	}
-	if (longest + 64 > OB_BLOCK) { fprintf(stderr, "sdt-kmers: a read of %llu bases\n", (unsigned long long)longest); return 1; }
+	*edits_out = edits;
+	*n_edits_out = n_edits;
+	return 0;
+}
+
+/* one edit of read `ord` (its bases from `start` of w, len of them) applied to the words and written as "read pos from to"; -1: the
+ * edit names a base the read does not have */
+static int apply_edit(outbuf *oe, uint64_t edit, uint64_t ord, uint32_t *w, uint64_t start, uint64_t len)
+{
+	static const char letters[4] = {'A', 'C', 'T', 'G'};
+	const uint64_t pos = (edit >> 2) & 0xFFFFu, g = start + pos;
+	if (pos >= len) { fprintf(stderr, "sdt-kmers: an edit at base %llu of a read of %llu\n", (unsigned long long)pos, (unsigned long long)len); return -1; }
+	const int sh = 30 - 2 * (int)(g & 15);
+	const uint32_t old = (w[g >> 4] >> sh) & 3u, neu = (uint32_t)(edit & 3u);
+	w[g >> 4] ^= (old ^ neu) << sh;
+	ob_room(oe, 2 * 21 + 4);
+	oe->p = put_u64(oe->p, ord + 1, ' ');
+	oe->p = put_u64(oe->p, pos + 1, ' ');
+	*oe->p++ = letters[old];
+	*oe->p++ = ' ';
+	*oe->p++ = letters[neu];
+	*oe->p++ = '\n';
+	return 0;
+}
+
+/* `correct`: the records and the edits from the device, the kept batches back from HBM, the edits applied here */
+static int correct_and_write(sdt_ctx *gpu, unsigned long long reads, uint32_t min_count, const char *prefix)
+{
+	const uint64_t m = reads ? reads : 1;
+	sdt_read_fix *fix = (sdt_read_fix *)calloc(m, sizeof(sdt_read_fix));
+	uint64_t *edits = NULL, n_edits = 0;
+	if (!fix) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	if (correct_kept(gpu, reads, min_count, fix, &edits, &n_edits) != 0) return 1;
+	kept_reads k;
+	if (kept_fetch(gpu, reads, &k) != 0) return 1;
 	char path[3][4200];
 	snprintf(path[0], sizeof path[0], "%s.readFix", prefix);
 	snprintf(path[1], sizeof path[1], "%s.edits", prefix);
@@ -248,35 +321,19 @@ static int correct_and_write(sdt_ctx *gpu, unsigned long long reads, uint32_t mi
 		of.p = put_u32(of.p, fix[ord].fixed, '\n');
 		with_weak += fix[ord].weak != 0;
 		runs += fix[ord].runs;
-		if (at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
-		const uint32_t *w = bw[at_batch[ord]];
-		const uint64_t start = bo[at_batch[ord]][at_read[ord]], len = bo[at_batch[ord]][at_read[ord] + 1] - start;
+		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
+		uint32_t *w = k.bw[k.at_batch[ord]];
+		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
+		for (; e < n_edits && (edits[e] >> 18) == ord && !bad; e++, fixed++)
+			bad = apply_edit(&oe, edits[e], ord, w, start, len) != 0;
 		ob_room(&oa, (size_t)len + 24);
-		*oa.p++ = '>';
-		oa.p = put_u64(oa.p, ord + 1, '\n');
-		char *seq = oa.p;
-		for (uint64_t i = 0; i < len; i++) {
-			const uint64_t g = start + i;
-			*oa.p++ = letters[(w[g >> 4] >> (30 - 2 * (int)(g & 15))) & 3u];
-		}
-		*oa.p++ = '\n';
-		for (; e < n_edits && (edits[e] >> 18) == ord; e++, fixed++) {
-			const uint64_t pos = (edits[e] >> 2) & 0xFFFFu;
-			if (pos >= len) { fprintf(stderr, "sdt-kmers: an edit at base %llu of a read of %llu\n", (unsigned long long)pos, (unsigned long long)len); bad = 1; break; }
-			ob_room(&oe, 2 * 21 + 4);
-			oe.p = put_u64(oe.p, ord + 1, ' ');
-			oe.p = put_u64(oe.p, pos + 1, ' ');
-			*oe.p++ = seq[pos];
-			*oe.p++ = ' ';
-			*oe.p++ = seq[pos] = letters[edits[e] & 3u];
-			*oe.p++ = '\n';
-		}
+		oa.p = sdt_put_fasta_record(oa.p, ord, w, start, len);
 	}
 	const int all_written = of.ok && oe.ok && oa.ok;
 	if ((ob_close(&of) != 0) | (ob_close(&oe) != 0) | (ob_close(&oa) != 0) || bad) return 1;
 	if (all_written && e != n_edits) { fprintf(stderr, "sdt-kmers: %llu of %llu edits name no read of the stream\n", (unsigned long long)(n_edits - e), (unsigned long long)n_edits); return 1; }
-	for (uint64_t b = 0; b < nb; b++) { free(bw[b]); free(bo[b]); }
-	free(bw); free(bo); free(at_batch); free(at_read); free(fix); free(edits);
+	kept_free(&k);
+	free(fix); free(edits);
 	printf("%llu reads, %llu with weak k-mers, %llu runs, %llu bases corrected into %s\n", reads, with_weak, runs, fixed, path[2]);
 	return 0;
 }
@@ -288,35 +345,14 @@ static int normalize_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt
 	sdt_read_pick *pick = (sdt_read_pick *)malloc(m * sizeof(sdt_read_pick));
 	if (!pick) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
 	memset(pick, 0xFF, m * sizeof(sdt_read_pick));                           /* (an ordinal that no read has keeps verdict 0xFFFFFFFF) */
-	uint64_t got = 0, n_kept = 0, nb = 0;
+	uint64_t got = 0, n_kept = 0;
 	if (sdt_gpu_select_kept_reads(gpu, prm, pairs->v, pairs->n, pick, reads, &got, &n_kept) != SDT_OK) {
 		fprintf(stderr, "sdt_gpu_select_kept_reads: %s\n", sdt_gpu_last_error());
 		return 1;
 	}
 	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu decided\n", reads, (unsigned long long)got); return 1; }
-	if (sdt_gpu_kept_batches(gpu, &nb) != SDT_OK) { fprintf(stderr, "sdt_gpu_kept_batches: %s\n", sdt_gpu_last_error()); return 1; }
-	uint32_t **bw = (uint32_t **)calloc(nb ? nb : 1, sizeof(uint32_t *));
-	uint64_t **bo = (uint64_t **)calloc(nb ? nb : 1, sizeof(uint64_t *));
-	uint32_t *at_batch = (uint32_t *)malloc(m * sizeof(uint32_t)), *at_read = (uint32_t *)malloc(m * sizeof(uint32_t));
-	if (!bw || !bo || !at_batch || !at_read) { fprintf(stderr, "sdt-kmers: out of memory\n"); return 1; }
-	memset(at_batch, 0xFF, m * sizeof(uint32_t));
-	uint64_t longest = 0;
-	for (uint64_t b = 0; b < nb; b++) {
-		uint64_t info[4];
-		if (sdt_gpu_fetch_kept_batch(gpu, b, info, NULL, 0, NULL, 0) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
-		bw[b] = (uint32_t *)malloc((info[0] ? info[0] : 1) * sizeof(uint32_t));
-		bo[b] = (uint64_t *)malloc((info[1] + 1) * sizeof(uint64_t));
-		if (!bw[b] || !bo[b]) { fprintf(stderr, "sdt-kmers: out of memory for the reads\n"); return 1; }
-		if (sdt_gpu_fetch_kept_batch(gpu, b, info, bw[b], info[0], bo[b], info[1] + 1) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
-		for (uint64_t i = 0; i < info[1]; i++) {
-			const uint64_t ord = info[2] + i * info[3];
-			if (ord >= reads) { fprintf(stderr, "sdt-kmers: a kept read has ordinal %llu of %llu\n", (unsigned long long)ord, reads); return 1; }
-			at_batch[ord] = (uint32_t)b;
-			at_read[ord] = (uint32_t)i;
-			if (bo[b][i + 1] - bo[b][i] > longest) longest = bo[b][i + 1] - bo[b][i];
-		}
-	}
-	if (longest + 64 > OB_BLOCK) { fprintf(stderr, "sdt-kmers: a read of %llu bases\n", (unsigned long long)longest); return 1; }
+	kept_reads k;
+	if (kept_fetch(gpu, reads, &k) != 0) return 1;
 	char path[3][4200];
 	snprintf(path[0], sizeof path[0], "%s.readPick", prefix);
 	snprintf(path[1], sizeof path[1], "%s.norm.pairs.fa", prefix);
@@ -330,7 +366,7 @@ static int normalize_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt
 	int bad = 0;
 	for (uint64_t ord = 0; ord < reads; ord++) {
 		if (!opick.ok || !opair.ok || !osingle.ok) break;                               /* a write failed: ob_close says which */
-		if (at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
+		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
 		ob_room(&opick, 4 * 11);
 		opick.p = put_u32(opick.p, pick[ord].kmers, ' ');
 		opick.p = put_u32(opick.p, pick[ord].median, ' ');
@@ -343,15 +379,84 @@ static int normalize_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt
 		if (cls > 1) continue;
 		kept++;
 		outbuf *o = sdt_pair_ranges_holds(pairs, ord, &cursor) ? &opair : &osingle;
-		const uint64_t start = bo[at_batch[ord]][at_read[ord]], len = bo[at_batch[ord]][at_read[ord] + 1] - start;
+		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
 		ob_room(o, (size_t)len + 24);
-		o->p = sdt_put_fasta_record(o->p, ord, bw[at_batch[ord]], start, len);
+		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start, len);
 	}
 	if ((ob_close(&opick) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
 	if (kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
-	for (uint64_t b = 0; b < nb; b++) { free(bw[b]); free(bo[b]); }
-	free(bw); free(bo); free(at_batch); free(at_read); free(pick);
+	kept_free(&k);
+	free(pick);
 	printf("%llu of %llu reads kept (%llu short, %llu aberrant, %llu dropped by draw)\n", kept, reads, n_short, aberrant, drawn);
+	return 0;
+}
+
+/* `trim`: the records (and with --correct the edits) from the device, the kept batches back from HBM, the edits applied here, the kept
+ * bases of every read into the pairs file (both mates survive) or the singles file (trimsplit.c) */
+static int trim_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_trim_params *prm, const sdt_pair_ranges *pairs, const char *prefix)
+{
+	const uint64_t m = reads ? reads : 1;
+	const int correct = (prm->flags & SDT_TRIM_CORRECTED) != 0;
+	sdt_read_trim *trim = (sdt_read_trim *)calloc(m, sizeof(sdt_read_trim));
+	sdt_read_fix *fix = correct ? (sdt_read_fix *)calloc(m, sizeof(sdt_read_fix)) : NULL;
+	if (!trim || (correct && !fix)) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	uint64_t got = 0, n_kept = 0, *edits = NULL, n_edits = 0;
+	if (sdt_gpu_trim_kept_reads(gpu, prm, trim, reads, &got, &n_kept) != SDT_OK) {
+		fprintf(stderr, "sdt_gpu_trim_kept_reads: %s\n", sdt_gpu_last_error());
+		return 1;
+	}
+	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu trimmed\n", reads, (unsigned long long)got); return 1; }
+	if (correct && correct_kept(gpu, reads, prm->min_count, fix, &edits, &n_edits) != 0) return 1;
+	kept_reads k;
+	if (kept_fetch(gpu, reads, &k) != 0) return 1;
+	char path[4][4200];
+	snprintf(path[0], sizeof path[0], "%s.readTrim", prefix);
+	snprintf(path[1], sizeof path[1], "%s.trim.pairs.fa", prefix);
+	snprintf(path[2], sizeof path[2], "%s.trim.single.fa", prefix);
+	snprintf(path[3], sizeof path[3], "%s.edits", prefix);
+	outbuf otrim, opair, osingle, oe;
+	if (ob_open(&otrim, path[0]) != 0) return 1;
+	if (ob_open(&opair, path[1]) != 0) { ob_close(&otrim); return 1; }
+	if (ob_open(&osingle, path[2]) != 0) { ob_close(&otrim); ob_close(&opair); return 1; }
+	if (correct && ob_open(&oe, path[3]) != 0) { ob_close(&otrim); ob_close(&opair); ob_close(&osingle); return 1; }
+	unsigned long long by_verdict[5] = {0, 0, 0, 0, 0}, kept = 0, bases_in = 0, bases_out = 0;
+	size_t cursor = 0;
+	uint64_t e = 0;
+	int bad = 0;
+	for (uint64_t ord = 0; ord < reads && !bad; ord++) {
+		if (!otrim.ok || !opair.ok || !osingle.ok || (correct && !oe.ok)) break;    /* a write failed: ob_close says which */
+		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
+		const sdt_read_trim *t = trim + ord;
+		ob_room(&otrim, SDT_TRIM_LINE_MAX);
+		otrim.p = sdt_put_trim_line(otrim.p, t);
+		uint32_t *w = k.bw[k.at_batch[ord]];
+		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
+		if (t->verdict > 4 || (uint64_t)t->start + t->len > len) {
+			fprintf(stderr, "sdt-kmers: the record of read %llu keeps [%u, %u + %u) of %llu bases, verdict %u\n", (unsigned long long)ord + 1, t->start,
+			        t->start, t->len, (unsigned long long)len, t->verdict);
+			bad = 1;
+			break;
+		}
+		by_verdict[t->verdict]++;
+		bases_in += len;
+		for (; e < n_edits && (edits[e] >> 18) == ord && !bad; e++)
+			bad = apply_edit(&oe, edits[e], ord, w, start, len) != 0;
+		const int to = sdt_trim_route(pairs, &cursor, trim, reads, ord);
+		if (to == SDT_TRIM_TO_NONE) continue;
+		kept++;
+		bases_out += t->len;
+		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
+		ob_room(o, (size_t)t->len + 24);
+		o->p = sdt_put_fasta_record(o->p, ord, w, start + t->start, t->len);
+	}
+	const int all_written = otrim.ok && opair.ok && osingle.ok && (!correct || oe.ok);
+	if ((ob_close(&otrim) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) | (correct && ob_close(&oe) != 0) || bad) return 1;
+	if (all_written && e != n_edits) { fprintf(stderr, "sdt-kmers: %llu of %llu edits name no read of the stream\n", (unsigned long long)(n_edits - e), (unsigned long long)n_edits); return 1; }
+	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
+	kept_free(&k);
+	free(trim); free(fix); free(edits);
+	printf("%llu reads: %llu whole, %llu gated, %llu trimmed, %llu dropped, %llu short; %llu bases in, %llu bases out\n", reads, by_verdict[0],
+	       by_verdict[1], by_verdict[2], by_verdict[3], by_verdict[4], bases_in, bases_out);
 	return 0;
 }
 
@@ -422,15 +527,18 @@ static int load_queries(const char *path, int K, int nw, query_set *q)
 int main(int argc, char **argv)
 {
 	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0 && strcmp(argv[1], "correct") != 0 &&
-	                 strcmp(argv[1], "normalize") != 0)) { usage(); return 255; }
+	                 strcmp(argv[1], "normalize") != 0 && strcmp(argv[1], "trim") != 0)) { usage(); return 255; }
 	const int do_query = strcmp(argv[1], "query") == 0, do_correct = strcmp(argv[1], "correct") == 0, do_norm = strcmp(argv[1], "normalize") == 0;
+	const int do_trim = strcmp(argv[1], "trim") == 0;
 	sdt_norm_params prm = {50, 10000, 0};
+	sdt_trim_params tprm = {0, 0, 0, 0};
 	char cfgfile[4096] = "", outname[4096] = "", qfile[4096] = "";
 	int K = 23, threads = 8, d = 0, max_k = 0, device = 0, c;
-	unsigned long min_count = do_correct ? 2 : 0;
+	unsigned long min_count = do_correct || do_trim ? 2 : 0;
 	static struct option longopts[] = {{"max-k", required_argument, 0, 1000}, {"device", required_argument, 0, 1001},
 	                                   {"target", required_argument, 0, 1002}, {"max-cv", required_argument, 0, 1003},
-	                                   {"seed", required_argument, 0, 1004}, {0, 0, 0, 0}};
+	                                   {"seed", required_argument, 0, 1004}, {"min-cov", required_argument, 0, 1005},
+	                                   {"min-len", required_argument, 0, 1006}, {"correct", no_argument, 0, 1007}, {0, 0, 0, 0}};
 	argv++; argc--;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:", longopts, NULL)) != -1) {
 		switch (c) {
@@ -451,6 +559,16 @@ int main(int argc, char **argv)
 			if (c == 1002) prm.target = (uint32_t)v;
 			else if (c == 1003) prm.max_cv_pct = (uint32_t)v;
 			else prm.seed = v;
+			break;
+		}
+		case 1005: case 1006: case 1007: {
+			const char *opt = c == 1005 ? "--min-cov" : (c == 1006 ? "--min-len" : "--correct");
+			unsigned long long v;
+			if (!do_trim) { fprintf(stderr, "sdt-kmers: %s belongs to trim\n", opt); usage(); return 255; }
+			if (c == 1007) { tprm.flags |= SDT_TRIM_CORRECTED; break; }
+			if (parse_number(opt, optarg, UINT32_MAX, &v) != 0) return 255;
+			if (c == 1005) tprm.min_cov = (uint32_t)v;
+			else tprm.min_len = (uint32_t)v;
 			break;
 		}
 		default: usage(); return 255;
@@ -483,7 +601,7 @@ int main(int argc, char **argv)
 	}
 	sdt_pair_ranges pairs;
 	memset(&pairs, 0, sizeof pairs);
-	push_state st = {gpu, 0, do_norm ? &pairs : NULL};
+	push_state st = {gpu, 0, do_norm || do_trim ? &pairs : NULL};
 	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
 	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : threads;
 	sdt_pool_enable(sdt_gpu_host_alloc, sdt_gpu_host_free, parse_threads + PUSH_DEPTH + 8);
@@ -499,6 +617,10 @@ int main(int argc, char **argv)
 
 	if (do_norm) {
 		if (normalize_and_write(gpu, st.reads, &prm, &pairs, outname) != 0) return 1;
+		sdt_pair_ranges_free(&pairs);
+	} else if (do_trim) {
+		tprm.min_count = (uint32_t)min_count;
+		if (trim_and_write(gpu, st.reads, &tprm, &pairs, outname) != 0) return 1;
 		sdt_pair_ranges_free(&pairs);
 	} else if (do_correct) {
 		if (correct_and_write(gpu, st.reads, (uint32_t)min_count, outname) != 0) return 1;

@@ -19,6 +19,60 @@ static_assert(sizeof(ReadFix) == 16, "sdt_read_fix is four 32-bit words");
 
 constexpr int FIX_MAX_RUN = 127;                         // a candidate run has at most K <= 127 k-mers: two ballots find its end
 
+// what judge_weak_run found for a run that is to be fixed: the run's k-mers [a, a + l), base p of the read becomes neu
+struct RunFix {
+	int l, p;
+	uint32_t old, neu;
+};
+
+// The judgement of the run of weak k-mers that starts at k-mer a of a read (the rule: include/sdt_gpu.h), for the whole wave: the
+// run's shape, the 3 * l look-ups of its alternatives shared among the lanes, and "exactly one alternative makes every k-mer of
+// the run solid".  cnt: the read's counts in the wave's strip (fenced by the caller), n of them.  Uniform over the wave; reads the
+// strip, the stream and the table only.  (k_correct_reads, k_trim_reads)
+template <int NW>
+__device__ inline RunFix judge_weak_run(const uint32_t *words, uint64_t start, int n, int K, const Table<NW> &tbl, const HiView &hv,
+                                      uint32_t min_count, const uint32_t *cnt, int a, int lane)
+{
+	// the run's length, as far as it matters: the first solid k-mer (or the read's end) among the next 128
+	int l = FIX_MAX_RUN + 1;
+#pragma unroll
+	for (int t = 1; t >= 0; t--) {
+		const int q = a + 64 * t + lane;
+		const unsigned long long ends = __ballot(q >= n || cnt[q] >= min_count);
+		if (ends) l = 64 * t + (int)__builtin_ctzll(ends);
+	}
+	const RunFix none = {0, 0, 0, 0};
+	if (l > K) return none;
+	const int b = a + l - 1;
+	const bool head = a == 0, tail = b == n - 1;
+	if (head && tail) return none;                                   // nothing solid in the read
+	if (!head && !tail && l != K) return none;
+	const int p = tail ? a + K - 1 : b;                              // every k-mer of [a, b] holds base p
+	// look-up t of 3 * l: alternative old ^ (t / l + 1) in k-mer a + t % l
+	uint32_t invalid = 0;
+	for (int t0 = 0; t0 < 3 * l; t0 += 64) {
+		const int t = t0 + lane;
+		const bool active = t < 3 * l;
+		const int alt = active ? t / l : 0, j = a + (active ? t - alt * l : 0);
+		Key<NW> fw = global_kmer<NW>(words, start + (uint64_t)j, K);
+		const int bit = 2 * (K - 1 - (p - j));
+#pragma unroll
+		for (int wd = 0; wd < NW; wd++)
+			if (wd == NW - 1 - (bit >> 6)) fw.w[wd] ^= (uint64_t)(alt + 1) << (bit & 63);
+		const Key<NW> rc = key_revcomp<NW>(fw, K);
+		bool f;
+		const uint32_t c = lookup_count<NW>(tbl, key_less<NW>(fw, rc) ? fw : rc, hv, f);         // (lanes past 3 * l look k-mer a up again)
+		const bool miss = active && c < min_count;
+#pragma unroll
+		for (int x = 0; x < 3; x++)
+			if (__ballot(miss && alt == x)) invalid |= 1u << x;
+	}
+	if (__popc(invalid) != 2) return none;                           // none or several alternatives fit
+	const uint64_t g = start + (uint64_t)p;
+	const uint32_t old = (words[g >> 4] >> (30 - 2 * (int)(g & 15))) & 3u;
+	return RunFix{l, p, old, old ^ (uint32_t)(__ffs((int)(~invalid & 7u)))};
+}
+
 // fix[r] for read r of the batch (dense).  An edit is (edit_base + r * edit_stride) << 18 | pos << 2 | new_base: (0, 1) for a batch,
 // the read ordinals for a kept batch.  out_words: NULL, or a copy of `words` made before the launch.  edits: NULL, or max_edits
 // words; *n_edits counts every edit, stored or not.  LDS: max_kmers 32-bit counts per wave.
@@ -72,49 +126,15 @@ __global__ __launch_bounds__(TPB) void k_correct_reads(const uint32_t *__restric
 			while (starts) {
 				const int a = base + (int)__builtin_ctzll(starts);
 				starts &= starts - 1;
-				// the run's length, as far as it matters: the first solid k-mer (or the read's end) among the next 128
-				int l = FIX_MAX_RUN + 1;
-#pragma unroll
-				for (int t = 1; t >= 0; t--) {
-					const int q = a + 64 * t + lane;
-					const unsigned long long ends = __ballot(q >= n || cnt[q] >= min_count);
-					if (ends) l = 64 * t + (int)__builtin_ctzll(ends);
-				}
-				if (l > K) continue;
-				const int b = a + l - 1;
-				const bool head = a == 0, tail = b == n - 1;
-				if (head && tail) continue;                              // nothing solid in the read
-				if (!head && !tail && l != K) continue;
-				const int p = tail ? a + K - 1 : b;                      // every k-mer of [a, b] holds base p
-				const uint64_t g = start + (uint64_t)p;
-				const uint32_t old = (words[g >> 4] >> (30 - 2 * (int)(g & 15))) & 3u;
-				// look-up t of 3 * l: alternative old ^ (t / l + 1) in k-mer a + t % l
-				uint32_t invalid = 0;
-				for (int t0 = 0; t0 < 3 * l; t0 += 64) {
-					const int t = t0 + lane;
-					const bool active = t < 3 * l;
-					const int alt = active ? t / l : 0, j = a + (active ? t - alt * l : 0);
-					Key<NW> fw = global_kmer<NW>(words, start + (uint64_t)j, K);
-					const int bit = 2 * (K - 1 - (p - j));
-#pragma unroll
-					for (int wd = 0; wd < NW; wd++)
-						if (wd == NW - 1 - (bit >> 6)) fw.w[wd] ^= (uint64_t)(alt + 1) << (bit & 63);
-					const Key<NW> rc = key_revcomp<NW>(fw, K);
-					bool f;
-					const uint32_t c = lookup_count<NW>(tbl, key_less<NW>(fw, rc) ? fw : rc, hv, f);     // (lanes past 3 * l look k-mer a up again)
-					const bool miss = active && c < min_count;
-#pragma unroll
-					for (int x = 0; x < 3; x++)
-						if (__ballot(miss && alt == x)) invalid |= 1u << x;
-				}
-				if (__popc(invalid) != 2) continue;                      // none or several alternatives fit
-				const uint32_t neu = old ^ (uint32_t)(__ffs((int)(~invalid & 7u)));
+				const RunFix rf = judge_weak_run<NW>(words, start, n, K, tbl, hv, min_count, cnt, a, lane);
+				if (!rf.l) continue;
+				const uint64_t g = start + (uint64_t)rf.p;
 				nfixed++;
 				if (lane == 0) {
-					if (out_words) atomicXor(out_words + (g >> 4), (old ^ neu) << (30 - 2 * (int)(g & 15)));
+					if (out_words) atomicXor(out_words + (g >> 4), (rf.old ^ rf.neu) << (30 - 2 * (int)(g & 15)));
 					const unsigned long long at = atomicAdd(n_edits, 1ULL);
 					if (edits && at < max_edits)
-						edits[at] = (unsigned long long)(edit_base + r * edit_stride) << 18 | (unsigned long long)p << 2 | neu;
+						edits[at] = (unsigned long long)(edit_base + r * edit_stride) << 18 | (unsigned long long)rf.p << 2 | rf.neu;
 				}
 			}
 		}

@@ -1,9 +1,7 @@
 // sdt_select.hip -- in-silico read normalisation against the counted node table (the rule: include/sdt_gpu.h) = k_pick_stats +
 // k_pick_decide, and the compaction of a 2-bit stream to the reads that were kept = k_compact_place + k_compact_words.  Nothing here
 // writes the table or the kept reads.  State rules, staging in pieces and the high halves of the counts are sdt_search.hip's.
-#include "sdt_ctx.hpp"
-#include "sdt_select_kernels.cuh"
-#include <rocprim/rocprim.hpp>
+#include "sdt_compact.hpp"
 
 // enqueue k_pick_stats for one device-resident batch; d_cov_flags[0] counts the reads longer than max_read_len
 static int launch_pick_stats(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_offs, uint64_t nreads, uint64_t max_read_len,
@@ -87,55 +85,15 @@ static int params_ok(const sdt_norm_params *p, uint64_t nreads, int paired)
 	return SDT_OK;
 }
 
-struct DevBuf {                                          // freed on every way out
-	void *p = nullptr;
-	~DevBuf() { if (p) (void)hipFree(p); }
-	int get(size_t bytes, const char *what)
-	{
-		if (p) { (void)hipFree(p); p = nullptr; }
-		const hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-		if (e != hipSuccess) { p = nullptr; return fail(SDT_ENOMEM, "%s: %zu bytes: %s", what, bytes, hipGetErrorString(e)); }
-		return SDT_OK;
-	}
-};
-
-// the compaction of one device-resident stream, checked arguments
+// the compaction of one device-resident stream to its kept reads, checked arguments
 static int compact_device(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_offs, uint64_t nreads, const uint8_t *d_keep,
                           uint32_t *d_out_words, uint64_t out_words_cap, uint64_t *d_out_offs, uint64_t *n_out_reads, uint64_t *n_out_words)
 {
-	DevBuf new_off, rank, src, tmp;
-	const size_t m = (size_t)nreads + 1;
-	int rc = new_off.get(m * sizeof(uint64_t), "compaction offsets");
-	if (rc == SDT_OK) rc = rank.get(m * sizeof(uint64_t), "compaction ranks");
-	if (rc == SDT_OK) rc = src.get(m * sizeof(uint64_t), "compaction sources");
-	if (rc != SDT_OK) return rc;
-	const auto lens = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), KeptLen{d_keep, d_offs, nreads});
-	const auto flags = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), KeptFlag{d_keep, nreads});
-	size_t tb1 = 0, tb2 = 0;
-	HIPCHK(rocprim::exclusive_scan(nullptr, tb1, lens, (uint64_t *)new_off.p, uint64_t(0), m, rocprim::plus<uint64_t>(), c->stream));
-	HIPCHK(rocprim::exclusive_scan(nullptr, tb2, flags, (uint64_t *)rank.p, uint64_t(0), m, rocprim::plus<uint64_t>(), c->stream));
-	rc = tmp.get(tb1 > tb2 ? tb1 : tb2, "compaction scan");
-	if (rc != SDT_OK) return rc;
-	HIPCHK(rocprim::exclusive_scan(tmp.p, tb1, lens, (uint64_t *)new_off.p, uint64_t(0), m, rocprim::plus<uint64_t>(), c->stream));
-	HIPCHK(rocprim::exclusive_scan(tmp.p, tb2, flags, (uint64_t *)rank.p, uint64_t(0), m, rocprim::plus<uint64_t>(), c->stream));
-	hipLaunchKernelGGL(k_compact_place, dim3(scan_grid(c, m)), dim3(TPB), 0, c->stream, d_keep, d_offs, nreads, (const uint64_t *)new_off.p,
-	                   (const uint64_t *)rank.p, d_out_offs, (uint64_t *)src.p);
-	HIPCHK(hipGetLastError());
-	uint64_t bases = 0, kept = 0;
-	HIPCHK(hipMemcpyAsync(&bases, (uint64_t *)new_off.p + nreads, sizeof bases, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(&kept, (uint64_t *)rank.p + nreads, sizeof kept, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	const uint64_t nw = (bases + 15) >> 4;
-	if (n_out_reads) *n_out_reads = kept;
-	if (n_out_words) *n_out_words = nw;
-	if (out_words_cap < nw + TAIL_PAD)
-		return fail(SDT_EFULL, "sdt_gpu_compact_reads: the kept reads take %llu words and %d pad words, out_words holds %llu",
-		            (unsigned long long)nw, TAIL_PAD, (unsigned long long)out_words_cap);
-	hipLaunchKernelGGL(k_compact_words, dim3(scan_grid(c, nw + TAIL_PAD)), dim3(TPB), 0, c->stream, d_words, (const uint64_t *)d_out_offs,
-	                   (const uint64_t *)src.p, kept, nw, d_out_words);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipStreamSynchronize(c->stream));             // (the scratch arrays go when this returns)
-	return SDT_OK;
+	const auto place = [&](int grid, const uint64_t *new_off, const uint64_t *rank, uint64_t *src) {
+		hipLaunchKernelGGL(k_compact_place, dim3(grid), dim3(TPB), 0, c->stream, d_keep, d_offs, nreads, new_off, rank, d_out_offs, src);
+	};
+	return compact_stream(c, "sdt_gpu_compact_reads", d_words, nreads, KeptLen{d_keep, d_offs, nreads}, KeptFlag{d_keep, nreads}, place,
+	                      d_out_words, out_words_cap, d_out_offs, n_out_reads, n_out_words);
 }
 
 extern "C" {

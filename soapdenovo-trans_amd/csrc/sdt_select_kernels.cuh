@@ -100,10 +100,10 @@ struct UnitSeg {
 
 // one lane per unit.  segs == NULL: the one stretch `dense`.  npick: records of pick[] (a mate past it is not there).  The unit's id
 // in the draw is id_base + the record index of its first read.  keep (may be NULL) is indexed like pick.  A record whose verdict
-// is PICK_ABSENT belongs to no read: it is left as it is, and its mate is judged alone.
-__global__ __launch_bounds__(TPB) void k_pick_decide(ReadPick *__restrict__ pick, uint64_t npick, const UnitSeg *__restrict__ segs, uint32_t nsegs,
-                                                     UnitSeg dense, uint64_t nunits, uint64_t id_base, uint32_t target, uint64_t seed,
-                                                     uint8_t *__restrict__ keep, unsigned long long *n_kept)
+// is PICK_ABSENT belongs to no read: it is left as it is, and its mate is judged alone.  (static: sdt_trim.hip includes this header too)
+static __global__ __launch_bounds__(TPB) void k_pick_decide(ReadPick *__restrict__ pick, uint64_t npick, const UnitSeg *__restrict__ segs,
+                                                            uint32_t nsegs, UnitSeg dense, uint64_t nunits, uint64_t id_base, uint32_t target,
+                                                            uint64_t seed, uint8_t *__restrict__ keep, unsigned long long *n_kept)
 {
 	uint32_t mine = 0;
 	for (uint64_t u0 = blockIdx.x * (uint64_t)TPB; u0 < nunits; u0 += (uint64_t)gridDim.x * TPB) {
