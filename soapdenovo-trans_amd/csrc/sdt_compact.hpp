@@ -1,21 +1,9 @@
 // sdt_compact.hpp -- the host side of the compaction of a 2-bit stream, shared by sdt_select.hip (whole kept reads) and sdt_trim.hip
-// (a kept range per read): two scans, a placement kernel of the caller's, k_compact_words.
+// (a kept range per read): two scans, a placement kernel of the caller's, k_compact_words; and the host form around it.
 #pragma once
-#include "sdt_ctx.hpp"
+#include "sdt_readstage.hpp"
 #include "sdt_select_kernels.cuh"
 #include <rocprim/rocprim.hpp>
-
-struct DevBuf {                                          // freed on every way out
-	void *p = nullptr;
-	~DevBuf() { if (p) (void)hipFree(p); }
-	int get(size_t bytes, const char *what)
-	{
-		if (p) { (void)hipFree(p); p = nullptr; }
-		const hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-		if (e != hipSuccess) { p = nullptr; return fail(SDT_ENOMEM, "%s: %zu bytes: %s", what, bytes, hipGetErrorString(e)); }
-		return SDT_OK;
-	}
-};
 
 // The compaction of one device-resident stream, checked arguments.  len_of(r) / flag_of(r): the bases read r contributes and whether it
 // contributes any, for r in [0, nreads] (0 at nreads).  place(grid, new_off, rank, src): enqueues the kernel that writes d_out_offs[rank[r]]
@@ -55,5 +43,55 @@ static int compact_stream(sdt_ctx *c, const char *what, const uint32_t *d_words,
 	                   (const uint64_t *)src.p, kept, nw, d_out_words);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(c->stream));             // (the scratch arrays go when this returns)
+	return SDT_OK;
+}
+
+// The compaction of a host stream, checked pointers: the whole stream at once, because the output of pieces would meet in the middle
+// of words.  tally(i, bases, kept): adds what read i keeps by the caller's host array to the two sums, or refuses the record.
+// sel / sel_bytes: that array, uploaded for device(d_words, d_offs, d_sel, d_out_words, out_words_cap, d_out_offs, &reads, &words),
+// the caller's device form.  What the output takes is known before anything is staged: nothing is staged for one that does not fit.
+template <class Tally, class Device>
+static int compact_host(sdt_ctx *c, const char *what, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets, uint64_t nreads,
+                        Tally tally, const void *sel, size_t sel_bytes, Device device, uint32_t *out_words, uint64_t out_words_cap,
+                        uint64_t *out_offsets, uint64_t *n_out_reads, uint64_t *n_out_words)
+{
+	StreamCheck in;
+	int rc = stream_args_ok(offsets, nreads, nwords, &in);
+	uint64_t bases = 0, kept = 0;
+	for (uint64_t i = 0; i < nreads && rc == SDT_OK; i++) rc = tally(i, bases, kept);
+	if (rc != SDT_OK) return rc;
+	const uint64_t need = (bases + 15) >> 4;
+	if (out_words_cap < need + TAIL_PAD) {
+		if (n_out_reads) *n_out_reads = kept;
+		if (n_out_words) *n_out_words = need;
+		return fail(SDT_EFULL, "%s: the kept reads take %llu words and %d pad words, out_words holds %llu", what, (unsigned long long)need, TAIL_PAD,
+		            (unsigned long long)out_words_cap);
+	}
+	HIPCHK(hipSetDevice(c->device));
+	DevBuf d_w, d_o, d_s, d_ow, d_oo;
+	rc = d_w.get(in.need_words * sizeof(uint32_t), "compaction staging");
+	if (rc == SDT_OK) rc = d_o.get((nreads + 1) * sizeof(uint64_t), "compaction staging");
+	if (rc == SDT_OK) rc = d_s.get(sel_bytes, "compaction staging");
+	if (rc == SDT_OK) rc = d_ow.get((need + TAIL_PAD) * sizeof(uint32_t), "compaction staging");
+	if (rc == SDT_OK) rc = d_oo.get((nreads + 1) * sizeof(uint64_t), "compaction staging");
+	if (rc != SDT_OK) return rc;
+	const uint64_t zero = 0;
+	if (nreads) {
+		HIPCHK(hipMemcpyAsync(d_w.p, packed_words, in.need_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemcpyAsync(d_o.p, offsets, (nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemcpyAsync(d_s.p, sel, sel_bytes, hipMemcpyHostToDevice, c->stream));
+	} else {
+		HIPCHK(hipMemcpyAsync(d_o.p, &zero, sizeof zero, hipMemcpyHostToDevice, c->stream));
+	}
+	uint64_t got_reads = 0, got_words = 0;
+	rc = device((const uint32_t *)d_w.p, (const uint64_t *)d_o.p, d_s.p, (uint32_t *)d_ow.p, need + TAIL_PAD, (uint64_t *)d_oo.p, &got_reads, &got_words);
+	if (rc != SDT_OK) return rc;
+	if (got_reads != kept || got_words != need)
+		return fail(SDT_EHIP, "%s: the device kept %llu reads in %llu words, the host counted %llu in %llu", what, (unsigned long long)got_reads,
+		            (unsigned long long)got_words, (unsigned long long)kept, (unsigned long long)need);
+	HIPCHK(hipMemcpy(out_words, d_ow.p, (need + TAIL_PAD) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(out_offsets, d_oo.p, (kept + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	if (n_out_reads) *n_out_reads = kept;
+	if (n_out_words) *n_out_words = need;
 	return SDT_OK;
 }

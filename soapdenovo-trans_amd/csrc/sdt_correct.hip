@@ -1,101 +1,58 @@
 // sdt_correct.hip -- k-mer-spectrum correction of substitution errors in reads against the counted node table = k_correct_reads
 // (the rule: include/sdt_gpu.h), and the way back to the host for the reads kept in HBM.  Nothing here writes the table or the
-// kept reads.  State rules, staging in pieces and the high halves of the counts are sdt_search.hip's.
-#include "sdt_ctx.hpp"
+// kept reads.  State rules and the high halves of the counts are sdt_search.hip's; launch geometry, staging in pieces and the walk over
+// the kept batches are sdt_readstage.hpp's.
+#include "sdt_readstage.hpp"
 #include "sdt_correct_kernels.cuh"
 #include <algorithm>
 
-// enqueue k_correct_reads for one device-resident batch; d_cov_flags[0] counts the reads longer than max_read_len, [2] the edits
-static int launch_correct(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_offs, uint64_t nreads, uint64_t max_read_len,
-                          uint32_t min_count, ReadFix *d_fix, uint32_t *d_out, unsigned long long *d_edits, uint64_t max_edits,
-                          uint64_t edit_base, uint64_t edit_stride)
-{
-	HiView hv;
-	int rc = hi_prepare(c, &hv);
-	if (rc != SDT_OK) return rc;
-	if (max_read_len < (uint64_t)c->K) max_read_len = (uint64_t)c->K;
-	const uint64_t mk = max_read_len - c->K + 1;
-	const size_t per_wave = (size_t)mk * sizeof(uint32_t);
-	if (per_wave > 64 * 1024)
-		return fail(SDT_EINVAL, "reads of %llu bases do not fit the per-wavefront LDS strip (%llu k-mers, 16384 at most)",
-		            (unsigned long long)max_read_len, (unsigned long long)mk);
-	int waves = 4;
-	while (waves > 1 && per_wave * waves > 64 * 1024) waves >>= 1;
-	uint64_t blocks = (nreads + waves - 1) / waves;
-	const uint64_t cap = (uint64_t)c->cu_count * 32;
-	if (blocks > cap) blocks = cap;
-	if (blocks == 0) blocks = 1;
-	EventPair *ev = next_event(c);
-	if (ev) HIPCHK(hipEventRecord(ev->a, c->stream));
-#define CORRECT_LAUNCH(NWV) hipLaunchKernelGGL(k_correct_reads<NWV>, dim3((unsigned)blocks), dim3(TPB), per_wave * waves, c->stream, d_words, d_offs, nreads, \
-	c->K, table_of<NWV>(c), hv, min_count, (int)mk, waves, d_fix, d_out, d_edits, (unsigned long long)max_edits, c->d_cov_flags + 2,          \
-	edit_base, edit_stride, c->d_cov_flags)
-	if (c->nw == 1) CORRECT_LAUNCH(1);
-	else if (c->nw == 2) CORRECT_LAUNCH(2);
-	else CORRECT_LAUNCH(4);
-#undef CORRECT_LAUNCH
-	HIPCHK(hipGetLastError());
-	if (ev) {
-		HIPCHK(hipEventRecord(ev->b, c->stream));
-		ev->kmers = nreads * mk;                         // (an upper bound, as for the count kernels)
-	}
-	return SDT_OK;
-}
-
 // one device-resident batch, checked arguments: the copy of the stream, the kernel, and the wait for its two counters
+// (d_cov_flags[2]: the edits)
 static int correct_device(sdt_ctx *c, const uint32_t *d_words, uint64_t nwords, const uint64_t *d_offs, uint64_t nreads, uint64_t max_read_len,
                           uint32_t min_count, ReadFix *d_fix, uint32_t *d_out, unsigned long long *d_edits, uint64_t max_edits,
                           uint64_t edit_base, uint64_t edit_stride, uint64_t *n_edits)
 {
-	int rc = flags_reserve(c);
+	int rc = flags_begin(c);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipMemsetAsync(c->d_cov_flags, 0, sizeof(unsigned long long), c->stream));
-	HIPCHK(hipMemsetAsync(c->d_cov_flags + 2, 0, sizeof(unsigned long long), c->stream));
 	if (d_out) HIPCHK(hipMemcpyAsync(d_out, d_words, nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-	rc = launch_correct(c, d_words, d_offs, nreads, max_read_len, min_count, d_fix, d_out, d_edits, d_edits ? max_edits : 0, edit_base, edit_stride);
+	const unsigned long long room = d_edits ? max_edits : 0;
+	rc = launch_strip(c, nreads, max_read_len, [&](auto nw, const StripGeometry &geo, const HiView &hv) {
+		constexpr int NW = decltype(nw)::value;
+		hipLaunchKernelGGL(k_correct_reads<NW>, dim3(geo.blocks), dim3(TPB), geo.lds_bytes, c->stream, d_words, d_offs, nreads, c->K, table_of<NW>(c),
+		                   hv, min_count, (int)geo.mk, geo.waves, d_fix, d_out, d_edits, room, c->d_cov_flags + 2, edit_base, edit_stride,
+		                   c->d_cov_flags);
+	});
 	if (rc != SDT_OK) return rc;
 	unsigned long long fl[3] = {0, 0, 0};
-	HIPCHK(hipMemcpyAsync(fl, c->d_cov_flags, sizeof fl, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
+	rc = flags_end(c, "sdt_gpu_correct_reads", max_read_len, fl);
 	if (n_edits) *n_edits = fl[2];
-	if (fl[0])
-		return fail(SDT_EINVAL, "sdt_gpu_correct_reads: %llu reads are longer than max_read_len = %llu; their records have kmers = 0xFFFFFFFF",
-		            fl[0], (unsigned long long)max_read_len);
+	if (rc != SDT_OK) return rc;
 	if (d_edits && fl[2] > max_edits)
 		return fail(SDT_EFULL, "sdt_gpu_correct_reads: %llu edits, edits[] holds %llu", fl[2], (unsigned long long)max_edits);
 	return SDT_OK;
 }
 
 // a batch whose number of edits nobody knows: the list grows to what the kernel asked for and the batch runs once more
-struct EditBuf {
-	unsigned long long *d = nullptr;
-	uint64_t cap = 0;
-	~EditBuf() { if (d) (void)hipFree(d); }
-};
 static int correct_device_grow(sdt_ctx *c, const uint32_t *d_words, uint64_t nwords, const uint64_t *d_offs, uint64_t nreads, uint64_t max_read_len,
-                               uint32_t min_count, ReadFix *d_fix, EditBuf *eb, uint64_t edit_base, uint64_t edit_stride,
+                               uint32_t min_count, ReadFix *d_fix, DevBuf *eb, uint64_t edit_base, uint64_t edit_stride,
                                std::vector<uint64_t> *all)
 {
 	for (int attempt = 0; attempt < 2; attempt++) {
-		if (eb->cap == 0) {
-			eb->cap = nreads / 4 + 1024;
-			HIPCHK(hipMalloc((void **)&eb->d, eb->cap * sizeof(unsigned long long)));
-		}
+		int rc = eb->p ? SDT_OK : eb->get((nreads / 4 + 1024) * sizeof(unsigned long long), "edit list");
+		if (rc != SDT_OK) return rc;
+		const uint64_t room = eb->cap / sizeof(unsigned long long);
 		uint64_t got = 0;
-		const int rc = correct_device(c, d_words, nwords, d_offs, nreads, max_read_len, min_count, d_fix, nullptr, eb->d, eb->cap, edit_base,
-		                              edit_stride, &got);
-		if (rc == SDT_EFULL && got > eb->cap && attempt == 0) {
-			HIPCHK(hipFree(eb->d));
-			eb->d = nullptr;
-			eb->cap = 0;
-			HIPCHK(hipMalloc((void **)&eb->d, got * sizeof(unsigned long long)));
-			eb->cap = got;
+		rc = correct_device(c, d_words, nwords, d_offs, nreads, max_read_len, min_count, d_fix, nullptr, (unsigned long long *)eb->p, room, edit_base,
+		                    edit_stride, &got);
+		if (rc == SDT_EFULL && got > room && attempt == 0) {
+			rc = eb->get(got * sizeof(unsigned long long), "edit list");
+			if (rc != SDT_OK) return rc;
 			continue;
 		}
 		if (rc != SDT_OK) return rc;
 		const size_t at = all->size();
 		all->resize(at + got);
-		if (got) HIPCHK(hipMemcpy(all->data() + at, eb->d, got * sizeof(uint64_t), hipMemcpyDeviceToHost));
+		if (got) HIPCHK(hipMemcpy(all->data() + at, eb->p, got * sizeof(uint64_t), hipMemcpyDeviceToHost));
 		return SDT_OK;
 	}
 	return fail(SDT_EHIP, "sdt_gpu_correct_reads: the number of edits changed between two runs of one batch");
@@ -146,54 +103,22 @@ int sdt_gpu_correct_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwo
 		return fail(SDT_EINVAL, "NULL argument");
 	int rc = search_ready(c, "sdt_gpu_correct_reads");
 	if (rc != SDT_OK) return rc;
-	for (uint64_t i = 0; i < nreads; i++)
-		if (offsets[i + 1] < offsets[i])
-			return fail(SDT_EINVAL, "offsets not monotonic at read %llu", (unsigned long long)i);
-	if (((offsets[nreads] + 15) >> 4) + TAIL_PAD > nwords)
-		return fail(SDT_EINVAL, "packed_words too short: need %llu words incl. %d pad words", (unsigned long long)(((offsets[nreads] + 15) >> 4) + TAIL_PAD), TAIL_PAD);
+	StreamCheck in;
+	StripGeometry geo;
+	rc = stream_args_ok(offsets, nreads, nwords, &in);
+	if (rc == SDT_OK) rc = strip_plan(c, nreads, in.longest, &geo);      // (the whole call is refused before a piece's records are written)
+	if (rc != SDT_OK) return rc;
 	HIPCHK(hipSetDevice(c->device));
-	// in pieces, as sdt_gpu_profile_reads stages them: a run of reads, the words that hold them (offsets rebased to the piece's first
-	// word) and their records; the edits of a piece name its reads from 0
-	const uint64_t piece_reads = chunk_items(PROFILE_CHUNK_READS);
-	std::vector<uint64_t> rel, all;
-	uint32_t *d_w = nullptr;
-	uint64_t *d_o = nullptr;
-	ReadFix *d_r = nullptr;
-	EditBuf eb;
-	uint64_t cap_w = 0, cap_r = 0;
-	for (uint64_t r0 = 0; r0 < nreads && rc == SDT_OK;) {
-		uint64_t r1 = r0 + 1, maxlen = offsets[r1] - offsets[r0];
-		while (r1 < nreads && r1 - r0 < piece_reads && offsets[r1 + 1] - offsets[r0] <= PROFILE_CHUNK_BASES) {
-			if (offsets[r1 + 1] - offsets[r1] > maxlen) maxlen = offsets[r1 + 1] - offsets[r1];
-			r1++;
-		}
-		const uint64_t w0 = offsets[r0] >> 4, w1 = ((offsets[r1] + 15) >> 4) + TAIL_PAD, nw = w1 - w0, nr = r1 - r0;
-		rel.resize(nr + 1);
-		for (uint64_t i = 0; i <= nr; i++) rel[i] = offsets[r0 + i] - (w0 << 4);
-		if (cap_w < nw || cap_r < nr) {
-			HIPCHK(hipStreamSynchronize(c->stream));
-			if (d_w) (void)hipFree(d_w);
-			if (d_o) (void)hipFree(d_o);
-			if (d_r) (void)hipFree(d_r);
-			d_w = nullptr; d_o = nullptr; d_r = nullptr;
-			cap_w = nw; cap_r = nr;
-			hipError_t e = hipMalloc((void **)&d_w, cap_w * sizeof(uint32_t));
-			if (e == hipSuccess) e = hipMalloc((void **)&d_o, (cap_r + 1) * sizeof(uint64_t));
-			if (e == hipSuccess) e = hipMalloc((void **)&d_r, cap_r * sizeof(ReadFix));
-			if (e != hipSuccess) { rc = fail(SDT_ENOMEM, "correction staging: %s", hipGetErrorString(e)); break; }
-		}
-		hipError_t e = hipMemcpyAsync(d_w, packed_words + w0, nw * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-		if (e == hipSuccess) e = hipMemcpyAsync(d_o, rel.data(), (nr + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
-		if (e != hipSuccess) { rc = fail(SDT_EHIP, "correction staging: %s", hipGetErrorString(e)); break; }
-		rc = correct_device_grow(c, d_w, nw, d_o, nr, maxlen, min_count, d_r, &eb, r0, 1, &all);      // (waits for the kernel: rel may be refilled)
-		if (rc != SDT_OK) break;
-		e = hipMemcpy(fix + r0, d_r, nr * sizeof(ReadFix), hipMemcpyDeviceToHost);
-		if (e != hipSuccess) { rc = fail(SDT_EHIP, "correction records: %s", hipGetErrorString(e)); break; }
-		r0 = r1;
-	}
-	if (d_w) (void)hipFree(d_w);
-	if (d_o) (void)hipFree(d_o);
-	if (d_r) (void)hipFree(d_r);
+	// the edits of a piece name its reads from its first read's index in the batch
+	std::vector<uint64_t> all;
+	DevBuf d_r, eb;
+	rc = for_each_piece(c, packed_words, offsets, nreads, 1, "correction staging", [&](const StagedPiece &p) -> int {
+		int rc = d_r.reserve(p.nr * sizeof(ReadFix), "correction staging");
+		if (rc == SDT_OK) rc = correct_device_grow(c, p.d_words, p.nwords, p.d_offs, p.nr, p.maxlen, min_count, (ReadFix *)d_r.p, &eb, p.r0, 1, &all);
+		if (rc != SDT_OK) return rc;
+		HIPCHK(hipMemcpy(fix + p.r0, d_r.p, p.nr * sizeof(ReadFix), hipMemcpyDeviceToHost));
+		return SDT_OK;
+	});
 	if (rc != SDT_OK) return rc;
 	// the corrected stream on the host: a piece may start in a word that also holds the previous read's last bases, so the words
 	// of the pieces are not put together -- the edits are applied to a copy of the input
@@ -217,18 +142,13 @@ int sdt_gpu_correct_kept_reads(sdt_ctx *c, uint32_t min_count, sdt_read_fix *fix
 	if (n_edits) *n_edits = 0;
 	int rc = search_ready(c, "sdt_gpu_correct_kept_reads");
 	if (rc != SDT_OK) return rc;
-	if (!(c->flags & SDT_FLAG_KEEP_READS) && c->kept.empty())
-		return fail(SDT_ESTATE, "the reads were not kept: init with SDT_FLAG_KEEP_READS (or hand them over with sdt_gpu_keep_reads)");
-	uint64_t total = 0, most = 0;
+	uint64_t total, most, npick;
+	rc = kept_span(c, out_capacity, "fix", &total, &most, &npick);
+	if (rc != SDT_OK) return rc;
 	for (const auto &kb : c->kept) {
-		if (!kb.nreads) continue;
 		const uint64_t last = kb.ord_base + (kb.nreads - 1) * kb.ord_stride;
-		if (last >= out_capacity)
-			return fail(SDT_EFULL, "a kept read has ordinal %llu, fix[] holds %llu records", (unsigned long long)last, (unsigned long long)out_capacity);
-		if (last >> 46)
+		if (kb.nreads && last >> 46)
 			return fail(SDT_ELIMIT, "a kept read has ordinal %llu: an edit holds 46 bits of it", (unsigned long long)last);
-		total += kb.nreads;
-		if (kb.nreads > most) most = kb.nreads;
 	}
 	if (total == 0)
 		return SDT_OK;
@@ -236,23 +156,18 @@ int sdt_gpu_correct_kept_reads(sdt_ctx *c, uint32_t min_count, sdt_read_fix *fix
 		return fail(SDT_EINVAL, "NULL argument");
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
-	// batch by batch: dense records on the device, scattered to their ordinals on the host (nothing else of fix[] is touched)
-	ReadFix *d_r = nullptr;
-	HIPCHK(hipMalloc((void **)&d_r, most * sizeof(ReadFix)));
+	// batch by batch: dense records on the device, scattered to their ordinals on the host
+	DevBuf d_r, eb;
+	rc = d_r.get(most * sizeof(ReadFix), "correction records");
+	if (rc != SDT_OK) return rc;
 	std::vector<ReadFix> tmp(most);
 	std::vector<uint64_t> all;
-	EditBuf eb;
 	for (const auto &kb : c->kept) {
 		if (!kb.nreads) continue;
-		rc = correct_device_grow(c, kb.d_words, kb.nwords, kb.d_offs, kb.nreads, kb.maxlen, min_count, d_r, &eb, kb.ord_base, kb.ord_stride, &all);
-		if (rc != SDT_OK) break;
-		const hipError_t e = hipMemcpy(tmp.data(), d_r, kb.nreads * sizeof(ReadFix), hipMemcpyDeviceToHost);
-		if (e != hipSuccess) { rc = fail(SDT_EHIP, "correction records: %s", hipGetErrorString(e)); break; }
-		for (uint64_t i = 0; i < kb.nreads; i++)
-			memcpy(fix + (kb.ord_base + i * kb.ord_stride), &tmp[i], sizeof(ReadFix));
+		rc = correct_device_grow(c, kb.d_words, kb.nwords, kb.d_offs, kb.nreads, kb.maxlen, min_count, (ReadFix *)d_r.p, &eb, kb.ord_base, kb.ord_stride, &all);
+		if (rc == SDT_OK) rc = scatter_by_ordinal(fix, kb, d_r, tmp);
+		if (rc != SDT_OK) return rc;
 	}
-	(void)hipFree(d_r);
-	if (rc != SDT_OK) return rc;
 	if (nreads) *nreads = total;
 	return hand_over_edits(all, edits, max_edits, n_edits, "sdt_gpu_correct_kept_reads");
 }
@@ -270,8 +185,8 @@ int sdt_gpu_fetch_kept_batch(sdt_ctx *c, uint64_t i, uint64_t info[4], uint32_t 
 {
 	if (!c || !info)
 		return fail(SDT_EINVAL, "NULL argument");
-	if (!(c->flags & SDT_FLAG_KEEP_READS) && c->kept.empty())
-		return fail(SDT_ESTATE, "the reads were not kept: init with SDT_FLAG_KEEP_READS (or hand them over with sdt_gpu_keep_reads)");
+	const int rc = kept_ready(c);
+	if (rc != SDT_OK) return rc;
 	if (i >= c->kept.size())
 		return fail(SDT_EINVAL, "kept batch %llu of %zu", (unsigned long long)i, c->kept.size());
 	if (c->staged_head < c->staged.size())

@@ -7,6 +7,8 @@
 //   sdt_search.hip    read-only questions to the counted table: batch k-mer search, per-read k-mer coverage
 //   sdt_correct.hip   substitution errors of reads corrected against the counted table; the kept reads back to the host
 //   sdt_select.hip    in-silico read normalisation against the counted table; a 2-bit stream compacted to the reads kept
+//   sdt_trim.hip      reads cut back to their longest solid stretch against the counted table; a 2-bit stream compacted to kept ranges
+//                     (these four read stages share a host layer of their own: sdt_readstage.hpp over sdt_read_plan.h, sdt_compact.hpp)
 //   sdt_gpu_graph.hip the graph phases (own view of the context: sdt_internal.hpp GraphView)
 // Not part of the ABI: nothing here is visible to a caller of libsdt_gpu.so.
 #pragma once
@@ -211,10 +213,4 @@ void sk_free(sdt_ctx *c);
 // ---- sdt_sharded.hip ----
 void shard_free(sdt_ctx *c);
 int sk_flush_sharded(sdt_ctx *c);
-// ---- sdt_search.hip ---- (shared with sdt_correct.hip and sdt_select.hip)
-namespace sdt { struct HiView; }
-constexpr uint64_t PROFILE_CHUNK_READS = 1ULL << 22, PROFILE_CHUNK_BASES = 1ULL << 29;     // reads / bases of a host batch that are on the device at a time
-uint64_t chunk_items(uint64_t dflt);
-int search_ready(sdt_ctx *c, const char *what);
-int flags_reserve(sdt_ctx *c);
-int hi_prepare(sdt_ctx *c, sdt::HiView *hv);
+// (what the read stages on the counted table share -- sdt_search.hip, sdt_correct.hip, sdt_select.hip, sdt_trim.hip: sdt_readstage.hpp)

@@ -1,0 +1,177 @@
+// sdt_readstage.hpp -- the host layer of the read stages on the counted table, over the context: what sdt_search.hip (profile),
+// sdt_correct.hip, sdt_select.hip (normalise) and sdt_trim.hip do the same way.  A stage is a strip kernel (one wavefront per read,
+// its k-mers' counts in a strip of LDS) with up to three forms: a device-resident batch, a host batch staged in pieces, and the
+// reads kept in HBM with records by read ordinal.  The decisions themselves are pure functions in sdt_read_plan.h; here they meet
+// the context, the stream and the messages.  Each stage keeps its kernel's own arguments and nothing else of this.
+#pragma once
+#include "sdt_ctx.hpp"
+#include "sdt_read_plan.h"
+#include "sdt_search_kernels.cuh"
+#include <type_traits>
+
+// ---- sdt_search.hip ----
+constexpr uint64_t PROFILE_CHUNK_READS = 1ULL << 22, PROFILE_CHUNK_BASES = 1ULL << 29;     // reads / bases of a host batch that are on the device at a time
+uint64_t chunk_items(uint64_t dflt);               // (SDT_SEARCH_CHUNK: test hook -- pieces of that many queries / reads)
+int search_ready(sdt_ctx *c, const char *what);    // the state rules of include/sdt_gpu.h, one message each
+int flags_reserve(sdt_ctx *c);
+int hi_prepare(sdt_ctx *c, HiView *hv);            // where a strip kernel finds the high half of a count past 65 535
+
+struct DevBuf {                                          // freed on every way out
+	void *p = nullptr;
+	size_t cap = 0;
+	~DevBuf() { if (p) (void)hipFree(p); }
+	int get(size_t bytes, const char *what)
+	{
+		if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+		const hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+		if (e != hipSuccess) { p = nullptr; return fail(SDT_ENOMEM, "%s: %zu bytes: %s", what, bytes, hipGetErrorString(e)); }
+		cap = bytes;
+		return SDT_OK;
+	}
+	// at least `bytes`: what it holds is kept only if it was large enough already
+	int reserve(size_t bytes, const char *what) { return p && cap >= bytes ? SDT_OK : get(bytes, what); }
+};
+
+// fn(std::integral_constant<int, NW>{}) for the context's key width
+template <class Fn>
+static void by_key_width(const sdt_ctx *c, Fn fn)
+{
+	if (c->nw == 1) fn(std::integral_constant<int, 1>{});
+	else if (c->nw == 2) fn(std::integral_constant<int, 2>{});
+	else fn(std::integral_constant<int, 4>{});
+}
+
+// the geometry of a strip kernel over reads of up to max_read_len bases, or the refusal of reads that no strip holds
+static int strip_plan(const sdt_ctx *c, uint64_t nreads, uint64_t max_read_len, StripGeometry *geo)
+{
+	*geo = strip_geometry(c->K, nreads, max_read_len, c->cu_count);
+	if (!geo->fits)
+		return fail(SDT_EINVAL, "reads of %llu bases do not fit the per-wavefront LDS strip (%llu k-mers, 16384 at most)",
+		            (unsigned long long)geo->max_read_len, (unsigned long long)geo->mk);
+	return SDT_OK;
+}
+
+// Enqueue a strip kernel for one device-resident batch.  fn(nw, geo, hv) launches it: nw is a std::integral_constant of the key width,
+// geo gives grid, LDS bytes, mk and waves, hv the high halves of the counts.
+template <class Fn>
+static int launch_strip(sdt_ctx *c, uint64_t nreads, uint64_t max_read_len, Fn fn)
+{
+	HiView hv;
+	int rc = hi_prepare(c, &hv);
+	if (rc != SDT_OK) return rc;
+	StripGeometry geo;
+	rc = strip_plan(c, nreads, max_read_len, &geo);
+	if (rc != SDT_OK) return rc;
+	EventPair *ev = next_event(c);
+	if (ev) HIPCHK(hipEventRecord(ev->a, c->stream));
+	by_key_width(c, [&](auto nw) { fn(nw, geo, hv); });
+	HIPCHK(hipGetLastError());
+	if (ev) {
+		HIPCHK(hipEventRecord(ev->b, c->stream));
+		ev->kmers = nreads * geo.mk;                     // (an upper bound, as for the count kernels)
+	}
+	return SDT_OK;
+}
+
+// the offsets and the length of a host stream, with the two messages; s->longest: the bases of its longest read, s->need_words: its words
+static int stream_args_ok(const uint64_t *offsets, uint64_t nreads, uint64_t nwords, StreamCheck *s)
+{
+	*s = check_stream(offsets, nreads, nwords, TAIL_PAD);
+	if (s->fault == STREAM_NOT_MONOTONIC)
+		return fail(SDT_EINVAL, "offsets not monotonic at read %llu", (unsigned long long)s->read);
+	if (s->fault == STREAM_TOO_SHORT)
+		return fail(SDT_EINVAL, "packed_words too short: need %llu words incl. %d pad words", (unsigned long long)s->need_words, TAIL_PAD);
+	return SDT_OK;
+}
+
+// A checked host batch through the device in pieces (sdt_read_plan.h: next_piece): a run of reads, the words that hold them and their
+// offsets, rebased to the piece's first word.  step = 2 keeps the mates of a pair in one piece.  body(piece) runs the stage on it and
+// copies its records back; it has to wait for its kernels, because the next piece is staged in the same buffers.
+struct StagedPiece {
+	const uint32_t *d_words;
+	const uint64_t *d_offs;
+	uint64_t nwords, r0, nr, maxlen;
+};
+template <class Body>
+static int for_each_piece(sdt_ctx *c, const uint32_t *words, const uint64_t *offsets, uint64_t nreads, uint64_t step, const char *what, Body body)
+{
+	uint64_t piece_reads = chunk_items(PROFILE_CHUNK_READS);
+	if (step > 1) piece_reads = piece_reads < step ? step : piece_reads - piece_reads % step;
+	std::vector<uint64_t> rel;
+	DevBuf d_w, d_o;
+	for (uint64_t r0 = 0; r0 < nreads;) {
+		const ReadPiece p = next_piece(offsets, nreads, r0, step, piece_reads, PROFILE_CHUNK_BASES, TAIL_PAD);
+		const uint64_t nr = p.r1 - r0;
+		rel.resize(nr + 1);
+		for (uint64_t i = 0; i <= nr; i++) rel[i] = offsets[r0 + i] - (p.w0 << 4);
+		const size_t wbytes = p.nwords * sizeof(uint32_t), obytes = (nr + 1) * sizeof(uint64_t);
+		if (d_w.cap < wbytes || d_o.cap < obytes) HIPCHK(hipStreamSynchronize(c->stream));
+		int rc = d_w.reserve(wbytes, what);
+		if (rc == SDT_OK) rc = d_o.reserve(obytes, what);
+		if (rc != SDT_OK) return rc;
+		HIPCHK(hipMemcpyAsync(d_w.p, words + p.w0, wbytes, hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemcpyAsync(d_o.p, rel.data(), obytes, hipMemcpyHostToDevice, c->stream));
+		rc = body(StagedPiece{(const uint32_t *)d_w.p, (const uint64_t *)d_o.p, p.nwords, r0, nr, p.maxlen});
+		if (rc != SDT_OK) return rc;
+		r0 = p.r1;
+	}
+	return SDT_OK;
+}
+
+// The two counters of a strip kernel, d_cov_flags[0] (reads longer than max_read_len) and [2] (the stage's own: edits, reads kept):
+// zeroed before the launch; read back after it, which waits for the kernel.  fl[] is filled before [0] is turned into the refusal.
+static int flags_begin(sdt_ctx *c)
+{
+	const int rc = flags_reserve(c);
+	if (rc != SDT_OK) return rc;
+	HIPCHK(hipMemsetAsync(c->d_cov_flags, 0, sizeof(unsigned long long), c->stream));
+	HIPCHK(hipMemsetAsync(c->d_cov_flags + 2, 0, sizeof(unsigned long long), c->stream));
+	return SDT_OK;
+}
+static int flags_end(sdt_ctx *c, const char *what, uint64_t max_read_len, unsigned long long fl[3])
+{
+	HIPCHK(hipMemcpyAsync(fl, c->d_cov_flags, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	if (fl[0])
+		return fail(SDT_EINVAL, "%s: %llu reads are longer than max_read_len = %llu; their records have kmers = 0xFFFFFFFF", what, fl[0],
+		            (unsigned long long)max_read_len);
+	return SDT_OK;
+}
+
+// ---- the reads kept in HBM ----
+static int kept_ready(const sdt_ctx *c)
+{
+	if (!(c->flags & SDT_FLAG_KEEP_READS) && c->kept.empty())
+		return fail(SDT_ESTATE, "the reads were not kept: init with SDT_FLAG_KEEP_READS (or hand them over with sdt_gpu_keep_reads)");
+	return SDT_OK;
+}
+
+// every kept read's ordinal lies in the caller's array_name[out_capacity]; *total: the kept reads, *most: those of the largest batch,
+// *npick: one past the largest ordinal
+static int kept_span(const sdt_ctx *c, uint64_t out_capacity, const char *array_name, uint64_t *total, uint64_t *most, uint64_t *npick)
+{
+	const int rc = kept_ready(c);
+	if (rc != SDT_OK) return rc;
+	*total = *most = *npick = 0;
+	for (const auto &kb : c->kept) {
+		if (!kb.nreads) continue;
+		const uint64_t last = kb.ord_base + (kb.nreads - 1) * kb.ord_stride;
+		if (last >= out_capacity)
+			return fail(SDT_EFULL, "a kept read has ordinal %llu, %s[] holds %llu records", (unsigned long long)last, array_name,
+			            (unsigned long long)out_capacity);
+		*total += kb.nreads;
+		if (kb.nreads > *most) *most = kb.nreads;
+		if (last + 1 > *npick) *npick = last + 1;
+	}
+	return SDT_OK;
+}
+
+// the dense records of one kept batch from the device to their ordinals in out[] (nothing else of out[] is touched)
+template <class Rec>
+static int scatter_by_ordinal(void *out, const sdt_ctx::KeptBatch &kb, const DevBuf &d_rec, std::vector<Rec> &tmp)
+{
+	HIPCHK(hipMemcpy(tmp.data(), d_rec.p, kb.nreads * sizeof(Rec), hipMemcpyDeviceToHost));
+	for (uint64_t i = 0; i < kb.nreads; i++)
+		memcpy((char *)out + (kb.ord_base + i * kb.ord_stride) * sizeof(Rec), &tmp[i], sizeof(Rec));
+	return SDT_OK;
+}

@@ -506,10 +506,11 @@ def as_records(t, dtype):
 
 
 @pytest.mark.parametrize("K", [31, 95])
-def test_read_only_entry_points_at_long_reads(pkg, synth, K):
+def test_read_only_entry_points_at_long_reads(pkg, synth, K, monkeypatch):
     """profile, correct (min_count 2) and select (target 6; max_cv_pct 150 and 0) over reads of 4 096, 4 097, 8 192, 8 193 and 16 384
     k-mers -- 4, 2 and 1 wavefronts per workgroup -- in the host forms, the device forms and the kept-reads forms, against the Python
-    restatements; one k-mer more is SDT_EINVAL with the outputs untouched"""
+    restatements; one k-mer more is SDT_EINVAL with the outputs untouched (profile, correct, select and trim), also when the read that
+    is too long comes in a later piece than a read that fits"""
     import torch
     c = long_case(K)
     eb = long_expected(c, "b")
@@ -581,23 +582,30 @@ def test_read_only_entry_points_at_long_reads(pkg, synth, K):
         over, ooffs = concat([c["tx"][:100].copy(), c["tx"][:STRIP_MAX_KMERS + K].copy()])
         owords = synth.pack_2bit(over)
         lib, ctx = g.lib, g._ctx
-        cov, fix, pick = (np.full(2 * w, 0xABABABAB, dtype=np.uint32) for w in (6, 4, 4))      # records of 6, 4 and 4 words
+        cov, fix, pick, trim = (np.full(2 * w, 0xABABABAB, dtype=np.uint32) for w in (6, 4, 4, 6))      # records of 6, 4, 4 and 6 words
         keep = np.full(2, 0xAB, dtype=np.uint8)
         outw = np.full(len(owords), 0xABABABAB, dtype=np.uint32)
         import ctypes
         ne, nkept = ctypes.c_uint64(77), ctypes.c_uint64(77)
         prm = pkg.NormParams(6, 150, 1)
+        tprm = pkg.TrimParams(2, 0, 0, 0)
         p = lambda a: ctypes.c_void_p(a.ctypes.data)
         calls = [lambda: lib.sdt_gpu_profile_reads(ctx, p(owords), owords.size, p(ooffs), 2, 2, p(cov)),
                  lambda: lib.sdt_gpu_correct_reads(ctx, p(owords), owords.size, p(ooffs), 2, 2, p(fix), p(outw), None, 0, ctypes.byref(ne)),
-                 lambda: lib.sdt_gpu_select_reads(ctx, p(owords), owords.size, p(ooffs), 2, 0, ctypes.addressof(prm), p(pick), p(keep), ctypes.byref(nkept))]
-        for call in calls:
-            assert call() == pkg.SDT_EINVAL
-            msg = lib.sdt_gpu_last_error().decode()
-            assert str(STRIP_MAX_KMERS + K) in msg and str(STRIP_MAX_KMERS) in msg, msg
-        for a in (cov, fix, pick):
-            assert (a == 0xABABABAB).all()
-        assert (keep == 0xAB).all() and (outw == 0xABABABAB).all()
+                 lambda: lib.sdt_gpu_select_reads(ctx, p(owords), owords.size, p(ooffs), 2, 0, ctypes.addressof(prm), p(pick), p(keep), ctypes.byref(nkept)),
+                 lambda: lib.sdt_gpu_trim_reads(ctx, p(owords), owords.size, p(ooffs), 2, ctypes.addressof(tprm), p(trim), p(keep), ctypes.byref(nkept))]
+        # as one piece, and with the 100-base read as a piece of its own ahead of the long one: the whole call is refused
+        for piece in (None, "1"):
+            if piece:
+                monkeypatch.setenv("SDT_SEARCH_CHUNK", piece)
+            for call in calls:
+                assert call() == pkg.SDT_EINVAL
+                msg = lib.sdt_gpu_last_error().decode()
+                assert str(STRIP_MAX_KMERS + K) in msg and str(STRIP_MAX_KMERS) in msg, msg
+            for a in (cov, fix, pick, trim):
+                assert (a == 0xABABABAB).all(), piece
+            assert (keep == 0xAB).all() and (outw == 0xABABABAB).all(), piece
+        monkeypatch.delenv("SDT_SEARCH_CHUNK")
         d_ow = torch.from_numpy(owords.view(np.int32)).cuda()
         d_oo = torch.from_numpy(ooffs.view(np.int64)).cuda()
         d2 = torch.full((2, 6), -1, dtype=torch.int32, device="cuda")
