@@ -599,7 +599,46 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  *   compact_trimmed_device: buffers on the device; d_out_words must not overlap the input.  It cannot refuse a range: start and len
  *                   are clamped to the read, nothing outside the stream is read.  Its outputs are what sdt_gpu_count_reads_device
  *                   of another context takes (nwords = *n_out_words + 4).
- * The trim calls follow the state rules and return codes of the profile calls (nreads == 0: SDT_OK, nothing touched). */
+ * The trim calls follow the state rules and return codes of the profile calls (nreads == 0: SDT_OK, nothing touched).
+ *
+ * Exact copies of a read or of a read pair dropped (PCR and optical duplicates: they add no k-mer and inflate the counts that -d,
+ * min_count and the normalisation's median key on).  Needs NO counted table: it runs before pass 1, and dedup -> compact_reads_device
+ * -> count_reads_device goes without a copy to the host.  Added without a change of SDT_ABI_VERSION: the three calls, the two structs
+ * and the flag are additions.  The rule is exact, deterministic and independent of any hash function and of the launch geometry.
+ *     A UNIT is one read, or the two mates of a pair; its id is the index of its first read (dense forms) or that read's ordinal
+ *     (kept form), as for select_reads.  Two reads are EQUAL iff they have the same length and the same bases (two reads of length 0
+ *     are equal).  Two units are EQUAL iff they hold the same number of reads and those are equal mate by mate; with
+ *     SDT_DEDUP_MATE_SWAP (bit 0 of flags) pairs (a, b) and (c, d) are also equal when a = d and b = c: the same fragment read from
+ *     the other strand of an unstranded library.  A single read never equals a pair.  Reverse complements of single reads are NOT
+ *     considered (out of scope).  An unknown bit in flags is SDT_EINVAL; reserved is ignored.
+ *     Equality partitions the units into CLASSES; the unit with the smallest id of a class is kept, the others are dropped.  Every
+ *     read of a unit gets the same record:
+ *         first    the smallest unit id of the class (the kept unit's own id)
+ *         copies   the units of the class, the same in every record of the class, saturating at 2^32 - 1
+ *         verdict  0 kept, 1 dropped
+ *   dedup_reads:    dup[i] for read i of a batch (packed as for sdt_gpu_push_reads).  paired != 0: reads 2t and 2t + 1 are mates (an
+ *                   odd nreads is SDT_EINVAL).  keep (may be NULL): keep[i] = 1 for verdict 0, else 0; *n_kept = reads kept.  Reads
+ *                   depend on each other: the whole stream is staged at once, like compact_reads.
+ *   dedup_reads_device: buffers already on the device (d_dup nreads records of 16 bytes, d_keep nreads bytes or NULL).  The call waits
+ *                   for the kernels to know *n_kept.  d_keep is what sdt_gpu_compact_reads_device takes.
+ *   dedup_kept_reads: the reads kept in HBM, over ALL kept batches at once (mates and copies sit in different batches); dup[] by READ
+ *                   ORDINAL like select_kept_reads (SDT_EFULL, nothing written, when a kept read's ordinal is >= out_capacity;
+ *                   records of ordinals that no kept read has are left untouched); pair_ranges with the meaning and the checks of
+ *                   select_kept_reads.  A pair of which only one mate is kept in HBM is a single-read unit (its id stays the first
+ *                   mate's ordinal).  *nreads = reads decided, *n_kept = reads kept.  The kept reads are NOT changed.
+ * State: the dense forms need a context for its stream only: any state, any kind of context, like compact_reads.  The kept form
+ * needs kept reads, not a table: the rules of sdt_gpu_kept_batches (SDT_ESTATE without kept reads or while pushed batches are not
+ * drained).  nreads == 0: SDT_OK, nothing touched.  There is NO limit on the read length: no per-wavefront strip is involved.
+ * How: a 64-bit fingerprint per read, of its bases wherever they start in a word; then rounds over the unresolved units: the unit
+ * fingerprints go into a hash set, the smallest unit of a slot is its representative, and every other unit of the slot is compared
+ * with it base by base: equal: dropped; different (a collision of fingerprints): it meets its own class in the next round, under
+ * another salt.  Every round resolves the class of every slot's smallest unit; in practice there is one round.  SDT_ELIMIT, no host
+ * output written, past 64 rounds (the device forms' d_dup and d_keep then hold records of resolved units only).
+ * Device memory held during the call, beside the reads, SDT_ENOMEM (nothing written) when it does not fit:
+ *     the hash set      24 B per slot (fingerprint, representative, copies); slots = the power of two >= 2 x units, < 4 x units
+ *     dense forms       8 B per read (its fingerprint); the host form also the stream, 16 B + 1 B per read of records and keep
+ *     kept form         per ordinal up to the highest kept one: 24 B (fingerprint, length, where the read's bases start) and the
+ *                       16 B record */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -607,6 +646,9 @@ typedef struct { uint32_t target, max_cv_pct; uint64_t seed; } sdt_norm_params;
 typedef struct { uint32_t kmers, weak, median, start, len, verdict; } sdt_read_trim;
 typedef struct { uint32_t min_count, min_cov, min_len, flags; } sdt_trim_params;
 #define SDT_TRIM_CORRECTED 1u   /* sdt_trim_params.flags: runs that sdt_gpu_correct_reads would fix count as solid */
+typedef struct { uint64_t first; uint32_t copies, verdict; } sdt_read_dup;   /* 16 bytes */
+typedef struct { uint32_t flags, reserved; } sdt_dedup_params;
+#define SDT_DEDUP_MATE_SWAP 1u  /* sdt_dedup_params.flags: pairs (a, b) and (b, a) are copies of each other */
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -656,6 +698,13 @@ int sdt_gpu_compact_trimmed(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t
 int sdt_gpu_compact_trimmed_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
                                    const void *d_trim, void *d_out_words, uint64_t out_words_cap, void *d_out_offsets,
                                    uint64_t *n_out_reads, uint64_t *n_out_words);
+int sdt_gpu_dedup_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                        uint64_t nreads, int paired, const sdt_dedup_params *params, sdt_read_dup *dup, uint8_t *keep,
+                        uint64_t *n_kept);
+int sdt_gpu_dedup_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                               int paired, const sdt_dedup_params *params, void *d_dup, void *d_keep, uint64_t *n_kept);
+int sdt_gpu_dedup_kept_reads(sdt_ctx *ctx, const sdt_dedup_params *params, const uint64_t *pair_ranges, uint64_t n_ranges,
+                             sdt_read_dup *dup, uint64_t out_capacity, uint64_t *nreads, uint64_t *n_kept);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

@@ -150,6 +150,12 @@ _ABI = [
                                            _c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_compact_trimmed_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint64,
                                                   _c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_dedup_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                       _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_dedup_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                              _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_dedup_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64,
+                                            _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -166,6 +172,10 @@ PICK_OWN_ABERRANT = 1 << 4
 READ_TRIM_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "weak", "median", "start", "len", "verdict")])
 TRIM_WHOLE, TRIM_GATED, TRIM_TRIMMED, TRIM_DROPPED, TRIM_SHORT = range(5)
 TRIM_CORRECTED = 1                                       # SDT_TRIM_CORRECTED
+# sdt_read_dup (include/sdt_gpu.h): one record per read of a duplicate filter; first = the smallest unit id of the read's class
+READ_DUP_DTYPE = np.dtype([("first", np.uint64), ("copies", np.uint32), ("verdict", np.uint32)])
+DUP_KEPT, DUP_DROPPED = range(2)
+SDT_DEDUP_MATE_SWAP = 1
 
 
 class NormParams(_c.Structure):
@@ -176,6 +186,11 @@ class NormParams(_c.Structure):
 class TrimParams(_c.Structure):
     """sdt_trim_params"""
     _fields_ = [("min_count", _c.c_uint32), ("min_cov", _c.c_uint32), ("min_len", _c.c_uint32), ("flags", _c.c_uint32)]
+
+
+class DedupParams(_c.Structure):
+    """sdt_dedup_params"""
+    _fields_ = [("flags", _c.c_uint32), ("reserved", _c.c_uint32)]
 
 _lib = None
 
@@ -799,6 +814,42 @@ class PregraphGPU:
             e.needed = nw.value
             raise e
         return nr.value, nw.value
+
+    # -- exact copies of a read or of a read pair dropped; needs no counted table (the rule: include/sdt_gpu.h)
+    def dedup_reads(self, words, offsets, paired: bool = False, flags: int = 0):
+        """-> (READ_DUP_DTYPE[nreads]: first, copies, verdict; keep uint8[nreads]; reads kept)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        dup = np.zeros(n, dtype=READ_DUP_DTYPE)
+        keep = np.zeros(n, dtype=np.uint8)
+        prm = DedupParams(flags, 0)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_dedup_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, int(bool(paired)), ctypes.addressof(prm),
+                                                 _ptr(dup), _ptr(keep), ctypes.byref(kept)))
+        return dup, keep, kept.value
+
+    def dedup_reads_device(self, d_words, d_offsets, nreads: int, d_dup, d_keep=None, paired: bool = False, flags: int = 0) -> int:
+        """device buffers; d_dup holds nreads records of 16 bytes, d_keep (optional) nreads bytes -> reads kept (waits for the kernels)"""
+        prm = DedupParams(flags, 0)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_dedup_reads_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, int(bool(paired)),
+                                                        ctypes.addressof(prm), _ptr(d_dup), _ptr(d_keep), ctypes.byref(kept)))
+        return kept.value
+
+    def dedup_kept_reads(self, total_reads: int, pair_ranges=(), flags: int = 0, out: np.ndarray = None):
+        """the reads kept in HBM; pair_ranges: [first, end) of ordinals that hold interleaved pairs, flat or as rows
+        -> (READ_DUP_DTYPE[total_reads] by read ordinal, reads decided, reads kept)"""
+        if out is None:
+            out = np.zeros(total_reads, dtype=READ_DUP_DTYPE)
+        assert out.dtype == READ_DUP_DTYPE and out.flags.c_contiguous and len(out) >= total_reads
+        ranges = np.ascontiguousarray(np.asarray(pair_ranges, dtype=np.uint64).reshape(-1))
+        assert ranges.size % 2 == 0
+        prm = DedupParams(flags, 0)
+        n, kept = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_dedup_kept_reads(self._ctx, ctypes.addressof(prm), _ptr(ranges) if ranges.size else None, ranges.size // 2,
+                                                      _ptr(out), total_reads, ctypes.byref(n), ctypes.byref(kept)))
+        return out, n.value, kept.value
 
     def set_read_ordinal(self, base: int, stride: int = 1):
         self._check(self.lib.sdt_gpu_set_read_ordinal(self._ctx, base, stride))

@@ -32,6 +32,12 @@
  *       prefix.trim.pairs.fa: both mates of the pairs of which both survive, read 1 then read 2, > ordinal + 1 and the kept bases
  *       prefix.trim.single.fa: every other surviving read, the mate of a dropped read among them
  *       prefix.edits (--correct): as `correct` writes it
+ *   sdt-kmers dedup -s lib.cfg -K k [-p threads] [--mate-swap] -o prefix
+ *       exact copies of a read, or of a pair, dropped (sdt_gpu_dedup_kept_reads; the rule: include/sdt_gpu.h): of every class of equal
+ *       units the first in stream order is kept; --mate-swap: pairs (a, b) and (b, a) are copies too.  Pairs as for normalize
+ *       prefix.readDup: one line per read in stream order:  first copies verdict   (first = the ordinal of the kept unit's first read)
+ *       prefix.dedup.pairs.fa / prefix.dedup.single.fa: the kept pairs / single reads, as normalize writes them
+ *       prefix.dupLevels: one line per class size present, ascending:  copies classes reads   (dupsplit.c)
  *
  * The query file is read and checked before the device is touched. */
 #include <errno.h>
@@ -46,6 +52,7 @@
 #include "readstream.h"
 #include "normsplit.h"
 #include "trimsplit.h"
+#include "dupsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -81,6 +88,14 @@ static void usage(void)
 	        "              prefix.edits (per substitution: read pos from to)\n"
 	        "           Pairs are the reads of q1=/q2= and f1=/f2= files, mates are trimmed independently; library boundaries go and\n"
 	        "           the reads of a p= file are single reads, as for normalize.\n"
+	        "       sdt-kmers dedup -s lib.cfg -K k [-p threads] [--mate-swap] -o prefix\n"
+	        "           exact copies of a read, or of the two mates of a pair, are dropped: the first in stream order is kept;\n"
+	        "           --mate-swap: pairs (a, b) and (b, a) are copies of each other (an unstranded library)\n"
+	        "           -> prefix.readDup (per read in stream order: first copies verdict; first = the ordinal of the first read of the\n"
+	        "              kept unit, copies = units in the class, verdict 0 kept, 1 dropped), prefix.dedup.pairs.fa (the kept pairs,\n"
+	        "              read 1 then read 2), prefix.dedup.single.fa (the kept single reads), prefix.dupLevels (per class size present,\n"
+	        "              ascending: copies classes reads)\n"
+	        "           Pairs are the reads of q1=/q2= and f1=/f2= files; the reads of a p= file are single reads, as for normalize.\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -391,6 +406,73 @@ static int normalize_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt
 	return 0;
 }
 
+/* `dedup`: the records from the device, the kept batches back from HBM, the kept reads into the pairs file or the singles file, the
+ * table of duplication levels (dupsplit.c) */
+static int dedup_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_dedup_params *prm, const sdt_pair_ranges *pairs, const char *prefix)
+{
+	const uint64_t m = reads ? reads : 1;
+	sdt_read_dup *dup = (sdt_read_dup *)malloc(m * sizeof(sdt_read_dup));
+	if (!dup) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	memset(dup, 0xFF, m * sizeof(sdt_read_dup));                             /* (an ordinal that no read has keeps verdict 0xFFFFFFFF) */
+	uint64_t got = 0, n_kept = 0;
+	if (sdt_gpu_dedup_kept_reads(gpu, prm, pairs->v, pairs->n, dup, reads, &got, &n_kept) != SDT_OK) {
+		fprintf(stderr, "sdt_gpu_dedup_kept_reads: %s\n", sdt_gpu_last_error());
+		return 1;
+	}
+	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu decided\n", reads, (unsigned long long)got); return 1; }
+	kept_reads k;
+	if (kept_fetch(gpu, reads, &k) != 0) return 1;
+	char path[4][4200];
+	snprintf(path[0], sizeof path[0], "%s.readDup", prefix);
+	snprintf(path[1], sizeof path[1], "%s.dedup.pairs.fa", prefix);
+	snprintf(path[2], sizeof path[2], "%s.dedup.single.fa", prefix);
+	snprintf(path[3], sizeof path[3], "%s.dupLevels", prefix);
+	outbuf odup, opair, osingle, olev;
+	if (ob_open(&odup, path[0]) != 0) return 1;
+	if (ob_open(&opair, path[1]) != 0) { ob_close(&odup); return 1; }
+	if (ob_open(&osingle, path[2]) != 0) { ob_close(&odup); ob_close(&opair); return 1; }
+	if (ob_open(&olev, path[3]) != 0) { ob_close(&odup); ob_close(&opair); ob_close(&osingle); return 1; }
+	sdt_dup_levels lv;
+	memset(&lv, 0, sizeof lv);
+	unsigned long long kept = 0;
+	size_t cursor = 0;
+	int bad = 0;
+	for (uint64_t ord = 0; ord < reads; ord++) {
+		if (!odup.ok || !opair.ok || !osingle.ok) break;                                /* a write failed: ob_close says which */
+		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
+		const sdt_read_dup *r = dup + ord;
+		if (r->verdict > 1 || r->copies == 0 || r->first > ord) {
+			fprintf(stderr, "sdt-kmers: the record of read %llu is %llu %u %u\n", (unsigned long long)ord + 1, (unsigned long long)r->first, r->copies, r->verdict);
+			bad = 1;
+			break;
+		}
+		ob_room(&odup, SDT_DUP_LINE_MAX);
+		odup.p = sdt_put_dup_line(odup.p, r);
+		/* (every ordinal has a read here, so the first read of a kept unit is the one whose ordinal is the unit's id) */
+		if (sdt_dup_levels_note(&lv, r, r->verdict == 0 && r->first == ord) != 0) { fprintf(stderr, "sdt-kmers: out of memory\n"); bad = 1; break; }
+		if (r->verdict != 0) continue;
+		kept++;
+		outbuf *o = sdt_pair_ranges_holds(pairs, ord, &cursor) ? &opair : &osingle;
+		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
+		ob_room(o, (size_t)len + 24);
+		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start, len);
+	}
+	unsigned long long classes = 0;
+	for (size_t i = 0; i < lv.n && !bad; i++) {
+		ob_room(&olev, SDT_DUP_LEVEL_LINE_MAX);
+		olev.p = sdt_put_dup_level_line(olev.p, lv.v + i);
+		classes += lv.v[i].classes;
+	}
+	sdt_dup_levels_free(&lv);
+	const int all_written = odup.ok && opair.ok && osingle.ok && olev.ok;
+	if ((ob_close(&odup) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) | (ob_close(&olev) != 0) || bad) return 1;
+	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
+	kept_free(&k);
+	free(dup);
+	printf("%llu of %llu reads kept in %llu classes\n", kept, reads, classes);
+	return 0;
+}
+
 /* `trim`: the records (and with --correct the edits) from the device, the kept batches back from HBM, the edits applied here, the kept
  * bases of every read into the pairs file (both mates survive) or the singles file (trimsplit.c) */
 static int trim_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_trim_params *prm, const sdt_pair_ranges *pairs, const char *prefix)
@@ -527,9 +609,10 @@ static int load_queries(const char *path, int K, int nw, query_set *q)
 int main(int argc, char **argv)
 {
 	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0 && strcmp(argv[1], "correct") != 0 &&
-	                 strcmp(argv[1], "normalize") != 0 && strcmp(argv[1], "trim") != 0)) { usage(); return 255; }
+	                 strcmp(argv[1], "normalize") != 0 && strcmp(argv[1], "trim") != 0 && strcmp(argv[1], "dedup") != 0)) { usage(); return 255; }
 	const int do_query = strcmp(argv[1], "query") == 0, do_correct = strcmp(argv[1], "correct") == 0, do_norm = strcmp(argv[1], "normalize") == 0;
-	const int do_trim = strcmp(argv[1], "trim") == 0;
+	const int do_trim = strcmp(argv[1], "trim") == 0, do_dedup = strcmp(argv[1], "dedup") == 0;
+	sdt_dedup_params dprm = {0, 0};
 	sdt_norm_params prm = {50, 10000, 0};
 	sdt_trim_params tprm = {0, 0, 0, 0};
 	char cfgfile[4096] = "", outname[4096] = "", qfile[4096] = "";
@@ -538,7 +621,8 @@ int main(int argc, char **argv)
 	static struct option longopts[] = {{"max-k", required_argument, 0, 1000}, {"device", required_argument, 0, 1001},
 	                                   {"target", required_argument, 0, 1002}, {"max-cv", required_argument, 0, 1003},
 	                                   {"seed", required_argument, 0, 1004}, {"min-cov", required_argument, 0, 1005},
-	                                   {"min-len", required_argument, 0, 1006}, {"correct", no_argument, 0, 1007}, {0, 0, 0, 0}};
+	                                   {"min-len", required_argument, 0, 1006}, {"correct", no_argument, 0, 1007},
+	                                   {"mate-swap", no_argument, 0, 1008}, {0, 0, 0, 0}};
 	argv++; argc--;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:", longopts, NULL)) != -1) {
 		switch (c) {
@@ -571,6 +655,10 @@ int main(int argc, char **argv)
 			else tprm.min_len = (uint32_t)v;
 			break;
 		}
+		case 1008:
+			if (!do_dedup) { fprintf(stderr, "sdt-kmers: --mate-swap belongs to dedup\n"); usage(); return 255; }
+			dprm.flags |= SDT_DEDUP_MATE_SWAP;
+			break;
 		default: usage(); return 255;
 		}
 	}
@@ -601,7 +689,7 @@ int main(int argc, char **argv)
 	}
 	sdt_pair_ranges pairs;
 	memset(&pairs, 0, sizeof pairs);
-	push_state st = {gpu, 0, do_norm || do_trim ? &pairs : NULL};
+	push_state st = {gpu, 0, do_norm || do_trim || do_dedup ? &pairs : NULL};
 	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
 	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : threads;
 	sdt_pool_enable(sdt_gpu_host_alloc, sdt_gpu_host_free, parse_threads + PUSH_DEPTH + 8);
@@ -621,6 +709,9 @@ int main(int argc, char **argv)
 	} else if (do_trim) {
 		tprm.min_count = (uint32_t)min_count;
 		if (trim_and_write(gpu, st.reads, &tprm, &pairs, outname) != 0) return 1;
+		sdt_pair_ranges_free(&pairs);
+	} else if (do_dedup) {
+		if (dedup_and_write(gpu, st.reads, &dprm, &pairs, outname) != 0) return 1;
 		sdt_pair_ranges_free(&pairs);
 	} else if (do_correct) {
 		if (correct_and_write(gpu, st.reads, (uint32_t)min_count, outname) != 0) return 1;

@@ -102,4 +102,68 @@ inline ReadPiece next_piece(const uint64_t *offsets, uint64_t nreads, uint64_t r
 	return p;
 }
 
+// ---- units of the reads kept in HBM: single reads and interleaved pairs, by read ordinal (select_kept_reads, dedup_kept_reads) ----
+// (tools/dedup_plan_check.cpp holds the cut to a walk over the ordinals)
+// pair_ranges[2i], pair_ranges[2i + 1] = [first, end) of ordinals that hold pairs, the first mate at first + 2t: ascending, disjoint,
+// of even length.  Returns n_ranges when they are, else the index of the first range that is not, and why.
+enum PairRangeFault { PAIR_RANGES_OK = 0, PAIR_RANGE_NOT_PAIRS, PAIR_RANGE_OVERLAPS };
+
+inline uint64_t check_pair_ranges(const uint64_t *pair_ranges, uint64_t n_ranges, PairRangeFault *fault)
+{
+	*fault = PAIR_RANGES_OK;
+	for (uint64_t i = 0; i < n_ranges; i++) {
+		const uint64_t first = pair_ranges[2 * i], end = pair_ranges[2 * i + 1];
+		if (end < first || ((end - first) & 1)) { *fault = PAIR_RANGE_NOT_PAIRS; return i; }
+		if (i && first < pair_ranges[2 * i - 1]) { *fault = PAIR_RANGE_OVERLAPS; return i; }
+	}
+	return n_ranges;
+}
+
+// a stretch of units: unit unit0 + t is the read at ordinal ord0 + t * stride, and with stride == 2 its mate at the next ordinal
+struct UnitStretch {
+	uint64_t unit0, ord0, stride;
+};
+
+// The units of ordinals [0, n_ord) under checked pair ranges, as stretches in ascending order: single reads up to a range, the pairs
+// of the range, and so on up to the last ordinal.  A range is cut at n_ord (a pair that n_ord cuts is a unit of its first mate); empty
+// stretches are left out.  out holds 2 * n_ranges + 1 stretches at most (NULL: they are only counted).  Returns the stretches;
+// *units: the units in them.
+inline uint64_t cut_unit_stretches(const uint64_t *pair_ranges, uint64_t n_ranges, uint64_t n_ord, UnitStretch *out, uint64_t *units)
+{
+	uint64_t n = 0, at = 0;
+	*units = 0;
+	for (uint64_t i = 0; i < n_ranges && at < n_ord; i++) {
+		const uint64_t first = pair_ranges[2 * i], end = pair_ranges[2 * i + 1] < n_ord ? pair_ranges[2 * i + 1] : n_ord;
+		if (first >= n_ord || end == first) continue;
+		if (first > at) {
+			if (out) out[n] = {*units, at, 1};
+			n++;
+			*units += first - at;
+		}
+		if (out) out[n] = {*units, first, 2};
+		n++;
+		*units += (end - first + 1) >> 1;
+		at = pair_ranges[2 * i + 1];
+	}
+	if (at < n_ord) {
+		if (out) out[n] = {*units, at, 1};
+		n++;
+		*units += n_ord - at;
+	}
+	return n;
+}
+
+// ---- the duplicate filter (sdt_dedup.hip): a hash set of unit fingerprints, open addressing, linear probing ----
+// the table for `units` units: a power of two of at least 2 * units slots (load <= 1/2: a probe ends), less than 4 * units beyond one unit
+constexpr uint64_t DEDUP_SLOT_BYTES = 24;                // fingerprint, representative, copies
+constexpr uint64_t DEDUP_ENT_BYTES = 24;                 // kept form, per ordinal: fingerprint, where the bases start, length
+constexpr int DEDUP_MAX_ROUNDS = 64;                     // every round resolves a class per occupied slot at least; past this: SDT_ELIMIT
+
+inline uint64_t dedup_table_slots(uint64_t units)
+{
+	uint64_t slots = 2;
+	while (slots < 2 * units && slots < (1ULL << 62)) slots <<= 1;
+	return slots;
+}
+
 } // namespace sdt

@@ -135,15 +135,15 @@ int sdt_gpu_select_kept_reads(sdt_ctx *c, const sdt_norm_params *params, const u
 	if (rc != SDT_OK) return rc;
 	if (n_ranges && !pair_ranges)
 		return fail(SDT_EINVAL, "NULL argument");
-	for (uint64_t i = 0; i < n_ranges; i++) {
-		const uint64_t first = pair_ranges[2 * i], end = pair_ranges[2 * i + 1];
-		if (end < first || ((end - first) & 1))
-			return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) does not hold whole pairs", (unsigned long long)i, (unsigned long long)first,
-			            (unsigned long long)end);
-		if (i && first < pair_ranges[2 * i - 1])
-			return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) starts before range %llu ends: ranges are ascending and disjoint",
-			            (unsigned long long)i, (unsigned long long)first, (unsigned long long)end, (unsigned long long)(i - 1));
-	}
+	PairRangeFault fault;
+	const uint64_t bad = check_pair_ranges(pair_ranges, n_ranges, &fault);
+	if (fault == PAIR_RANGE_NOT_PAIRS)
+		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) does not hold whole pairs", (unsigned long long)bad,
+		            (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1]);
+	if (fault == PAIR_RANGE_OVERLAPS)
+		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) starts before range %llu ends: ranges are ascending and disjoint",
+		            (unsigned long long)bad, (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1],
+		            (unsigned long long)(bad - 1));
 	rc = search_ready(c, "sdt_gpu_select_kept_reads");
 	if (rc != SDT_OK) return rc;
 	uint64_t total, most, npick;
@@ -156,23 +156,10 @@ int sdt_gpu_select_kept_reads(sdt_ctx *c, const sdt_norm_params *params, const u
 	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	// the unit list, as stretches: single reads up to a range, the pairs of the range, and so on up to the last ordinal a read has
-	std::vector<UnitSeg> segs;
-	uint64_t units = 0, at = 0;
-	for (uint64_t i = 0; i < n_ranges && at < npick; i++) {
-		const uint64_t first = pair_ranges[2 * i], end = pair_ranges[2 * i + 1] < npick ? pair_ranges[2 * i + 1] : npick;
-		if (first >= npick || end == first) continue;
-		if (first > at) {
-			segs.push_back({units, at, 1});
-			units += first - at;
-		}
-		segs.push_back({units, first, 2});
-		units += (end - first + 1) >> 1;                 // (npick may cut a pair: its first mate is a unit, the kernel finds no second)
-		at = pair_ranges[2 * i + 1];
-	}
-	if (at < npick) {
-		segs.push_back({units, at, 1});
-		units += npick - at;
-	}
+	// (npick may cut a pair: its first mate is a unit, the kernel finds no second)
+	std::vector<UnitSeg> segs(2 * n_ranges + 1);
+	uint64_t units = 0;
+	segs.resize(cut_unit_stretches(pair_ranges, n_ranges, npick, segs.data(), &units));
 	// records by ordinal on the device, preset to "no read": every kept batch fills in its own, then the units are decided
 	DevBuf d_pick, d_segs;
 	rc = d_pick.get(npick * sizeof(ReadPick), "selection records");

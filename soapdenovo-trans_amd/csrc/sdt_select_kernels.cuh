@@ -10,6 +10,7 @@
 //                     atomics, no partial-word stores, the same words whatever the launch geometry.
 #pragma once
 #include "sdt_search_kernels.cuh"
+#include "sdt_read_plan.h"
 
 namespace sdt {
 
@@ -94,9 +95,8 @@ __global__ __launch_bounds__(TPB) void k_pick_stats(const uint32_t *__restrict__
 }
 
 // a stretch of units: unit unit0 + t is the read at record ord0 + t * stride, and with stride == 2 its mate at the next record
-struct UnitSeg {
-	uint64_t unit0, ord0, stride;
-};
+// (sdt_read_plan.h: cut_unit_stretches makes the list of the kept form)
+using UnitSeg = UnitStretch;
 
 // one lane per unit.  segs == NULL: the one stretch `dense`.  npick: records of pick[] (a mate past it is not there).  The unit's id
 // in the draw is id_base + the record index of its first read.  keep (may be NULL) is indexed like pick.  A record whose verdict
