@@ -156,6 +156,12 @@ _ABI = [
                                               _c.c_void_p, _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_dedup_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64,
                                             _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_clip_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                      _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_clip_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                             _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_clip_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64),
+                                           _c.POINTER(_c.c_uint64)]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -176,6 +182,11 @@ TRIM_CORRECTED = 1                                       # SDT_TRIM_CORRECTED
 READ_DUP_DTYPE = np.dtype([("first", np.uint64), ("copies", np.uint32), ("verdict", np.uint32)])
 DUP_KEPT, DUP_DROPPED = range(2)
 SDT_DEDUP_MATE_SWAP = 1
+# sdt_read_clip (include/sdt_gpu.h): one record per read of a clip; adapters = (1 + 3' adapter, or 0) | (1 + 5' adapter, or 0) << 16; the
+# kept bases are [start, start + len) of the read, where READ_TRIM_DTYPE has them
+READ_CLIP_DTYPE = np.dtype([(f, np.uint32) for f in ("adapters", "tail3", "tail5", "start", "len", "verdict")])
+CLIP_WHOLE, CLIP_CLIPPED, CLIP_DROPPED = 0, 2, 3
+CLIP_MAX_ADAPTERS, CLIP_MAX_ADAPTER_LEN = 256, 128
 
 
 class NormParams(_c.Structure):
@@ -191,6 +202,30 @@ class TrimParams(_c.Structure):
 class DedupParams(_c.Structure):
     """sdt_dedup_params"""
     _fields_ = [("flags", _c.c_uint32), ("reserved", _c.c_uint32)]
+
+
+class ClipParams(_c.Structure):
+    """sdt_clip_params; tail3_bases / tail5_bases: masks of base codes (A 1, C 2, T 4, G 8)"""
+    _fields_ = [(f, _c.c_uint32) for f in ("min_overlap", "max_err_pct", "min_len", "min_tail", "tail_err_pct", "tail3_bases", "tail5_bases",
+                                           "flags")]
+
+
+class AdapterSet(_c.Structure):
+    """sdt_adapter_set"""
+    _fields_ = [("words", _c.c_void_p), ("offsets", _c.c_void_p), ("ends", _c.c_void_p), ("n", _c.c_uint32), ("reserved", _c.c_uint32)]
+
+
+def pack_adapters(adapters):
+    """[(codes, end)] -> (AdapterSet, the arrays it points into: keep them alive)"""
+    codes = [np.asarray(a, dtype=np.uint8).reshape(-1) for a, _ in adapters]
+    offsets = np.zeros(len(codes) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(a) for a in codes], dtype=np.uint64)
+    flat = np.concatenate(codes) if codes else np.zeros(0, dtype=np.uint8)
+    flat = np.concatenate([flat, np.zeros(-len(flat) % 16 + 16, dtype=np.uint8)]).astype(np.uint32).reshape(-1, 16)
+    words = np.ascontiguousarray((flat << (30 - 2 * np.arange(16, dtype=np.uint32))).sum(axis=1, dtype=np.uint32))
+    ends = np.ascontiguousarray([e for _, e in adapters], dtype=np.uint8)
+    aset = AdapterSet(words.ctypes.data, offsets.ctypes.data, ends.ctypes.data if len(ends) else None, len(codes), 0)
+    return aset, (words, offsets, ends)
 
 _lib = None
 
@@ -849,6 +884,47 @@ class PregraphGPU:
         n, kept = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self.lib.sdt_gpu_dedup_kept_reads(self._ctx, ctypes.addressof(prm), _ptr(ranges) if ranges.size else None, ranges.size // 2,
                                                       _ptr(out), total_reads, ctypes.byref(n), ctypes.byref(kept)))
+        return out, n.value, kept.value
+
+    # -- adapters and poly-A/T tails clipped from reads; needs no counted table (the rule: include/sdt_gpu.h)
+    @staticmethod
+    def _clip_args(adapters, params):
+        """adapters: [(codes, end)] (end 0: 3', 1: 5') or a ready (AdapterSet, arrays); params: ClipParams or its fields as a dict"""
+        prm = params if isinstance(params, ClipParams) else ClipParams(**(params or {}))
+        aset, alive = adapters if adapters and isinstance(adapters[0], AdapterSet) else pack_adapters(list(adapters or ()))
+        return prm, aset, alive
+
+    def clip_reads(self, words, offsets, adapters=(), params=None):
+        """-> (READ_CLIP_DTYPE[nreads]: adapters, tail3, tail5, start, len, verdict; keep uint8[nreads]; reads with len > 0)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        clip = np.zeros(n, dtype=READ_CLIP_DTYPE)
+        keep = np.zeros(n, dtype=np.uint8)
+        prm, aset, alive = self._clip_args(adapters, params)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_clip_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, ctypes.addressof(prm), ctypes.addressof(aset),
+                                                _ptr(clip), _ptr(keep), ctypes.byref(kept)))
+        return clip, keep, kept.value
+
+    def clip_reads_device(self, d_words, d_offsets, nreads: int, d_clip, d_keep=None, adapters=(), params=None) -> int:
+        """device buffers; d_clip holds nreads records of 24 bytes (what compact_trimmed_device takes), d_keep (optional) nreads bytes
+        -> reads with len > 0 (waits for the kernel)"""
+        prm, aset, alive = self._clip_args(adapters, params)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_clip_reads_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, ctypes.addressof(prm),
+                                                       ctypes.addressof(aset), _ptr(d_clip), _ptr(d_keep), ctypes.byref(kept)))
+        return kept.value
+
+    def clip_kept_reads(self, total_reads: int, adapters=(), params=None, out: np.ndarray = None):
+        """the reads kept in HBM -> (READ_CLIP_DTYPE[total_reads] by read ordinal, reads clipped, reads with len > 0)"""
+        if out is None:
+            out = np.zeros(total_reads, dtype=READ_CLIP_DTYPE)
+        assert out.dtype == READ_CLIP_DTYPE and out.flags.c_contiguous and len(out) >= total_reads
+        prm, aset, alive = self._clip_args(adapters, params)
+        n, kept = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_clip_kept_reads(self._ctx, ctypes.addressof(prm), ctypes.addressof(aset), _ptr(out), total_reads,
+                                                     ctypes.byref(n), ctypes.byref(kept)))
         return out, n.value, kept.value
 
     def set_read_ordinal(self, base: int, stride: int = 1):

@@ -38,6 +38,15 @@
  *       prefix.readDup: one line per read in stream order:  first copies verdict   (first = the ordinal of the kept unit's first read)
  *       prefix.dedup.pairs.fa / prefix.dedup.single.fa: the kept pairs / single reads, as normalize writes them
  *       prefix.dupLevels: one line per class size present, ascending:  copies classes reads   (dupsplit.c)
+ *   sdt-kmers clip -s lib.cfg -K k [-p threads] [-a adapters3.fa] [-g adapters5.fa] [--tail3 LETTERS] [--tail5 LETTERS]
+ *                  [--min-overlap N, default 5] [--error-pct P, default 10] [--min-tail N, default 10] [--tail-error-pct P, default 20]
+ *                  [--min-len L, default 0] -o prefix
+ *       sequencing adapters and poly-A/T tails clipped from every read (sdt_gpu_clip_kept_reads; the rule: include/sdt_gpu.h).  The
+ *       adapter files are FASTA, letters ACGT in either case, read and checked before the device is touched; -a: 3' adapters, -g: 5'
+ *       adapters, the 3' file first in the numbering.  Mates are clipped independently; pairs and routing as for trim (clipsplit.c)
+ *       prefix.readClip: one line per read in stream order:  adapter3 adapter5 tail3 tail5 start len verdict
+ *       prefix.clip.pairs.fa / prefix.clip.single.fa: the kept bases of the surviving reads, as trim writes them
+ *       prefix.clipStats: per adapter  index name end reads bases,  then tail3 / tail5  reads bases,  then whole, clipped, dropped
  *
  * The query file is read and checked before the device is touched. */
 #include <errno.h>
@@ -53,6 +62,7 @@
 #include "normsplit.h"
 #include "trimsplit.h"
 #include "dupsplit.h"
+#include "clipsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -96,6 +106,18 @@ static void usage(void)
 	        "              read 1 then read 2), prefix.dedup.single.fa (the kept single reads), prefix.dupLevels (per class size present,\n"
 	        "              ascending: copies classes reads)\n"
 	        "           Pairs are the reads of q1=/q2= and f1=/f2= files; the reads of a p= file are single reads, as for normalize.\n"
+	        "       sdt-kmers clip -s lib.cfg -K k [-p threads] [-a adapters3.fa] [-g adapters5.fa] [--tail3 LETTERS] [--tail5 LETTERS]\n"
+	        "                      [--min-overlap N, default 5] [--error-pct P, default 10] [--min-tail N, default 10]\n"
+	        "                      [--tail-error-pct P, default 20] [--min-len L, default 0] -o prefix\n"
+	        "           sequencing adapters (FASTA files, letters ACGT: -a at the 3' end, -g at the 5' end; an overlap of N bases or more\n"
+	        "           with at most P percent mismatches, no indels) and tails of the given letters (--tail3 A, --tail5 T: poly-A and\n"
+	        "           poly-T; N bases or more, at most P percent other letters) are clipped from every read; a read of which fewer than\n"
+	        "           max(L, 1) bases are left is dropped.  Needs no counted k-mers: run it before every other subcommand.\n"
+	        "           -> prefix.readClip (per read in stream order: adapter3 adapter5 tail3 tail5 start len verdict; adapters 1-based in\n"
+	        "              the order -a then -g, 0 none; verdict 0 whole, 2 clipped, 3 dropped), prefix.clip.pairs.fa (read 1 then read 2 of\n"
+	        "              the pairs of which both mates survive), prefix.clip.single.fa (every other surviving read), prefix.clipStats\n"
+	        "              (per adapter: index name end reads bases; tail3 and tail5: reads bases; whole, clipped, dropped: reads)\n"
+	        "           Pairs are the reads of q1=/q2= and f1=/f2= files, mates are clipped independently, as for trim.\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -542,6 +564,83 @@ static int trim_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_trim
 	return 0;
 }
 
+/* `clip`: the records from the device, the kept batches back from HBM, the kept bases of every read into the pairs file (both mates
+ * survive) or the singles file, routed as trim routes them; the statistics (clipsplit.c) */
+static int clip_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_clip_params *prm, const sdt_adapter_list *ads, const sdt_pair_ranges *pairs,
+                          const char *prefix)
+{
+	const uint64_t m = reads ? reads : 1;
+	sdt_read_clip *clip = (sdt_read_clip *)calloc(m, sizeof(sdt_read_clip));
+	sdt_clip_stats stats;
+	if (!clip || sdt_clip_stats_init(&stats, ads->n) != 0) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	const sdt_adapter_set set = sdt_adapters_set(ads);
+	uint64_t got = 0, n_kept = 0;
+	if (sdt_gpu_clip_kept_reads(gpu, prm, &set, clip, reads, &got, &n_kept) != SDT_OK) {
+		fprintf(stderr, "sdt_gpu_clip_kept_reads: %s\n", sdt_gpu_last_error());
+		return 1;
+	}
+	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu clipped\n", reads, (unsigned long long)got); return 1; }
+	kept_reads k;
+	if (kept_fetch(gpu, reads, &k) != 0) return 1;
+	char path[4][4200];
+	snprintf(path[0], sizeof path[0], "%s.readClip", prefix);
+	snprintf(path[1], sizeof path[1], "%s.clip.pairs.fa", prefix);
+	snprintf(path[2], sizeof path[2], "%s.clip.single.fa", prefix);
+	snprintf(path[3], sizeof path[3], "%s.clipStats", prefix);
+	outbuf oclip, opair, osingle;
+	if (ob_open(&oclip, path[0]) != 0) return 1;
+	if (ob_open(&opair, path[1]) != 0) { ob_close(&oclip); return 1; }
+	if (ob_open(&osingle, path[2]) != 0) { ob_close(&oclip); ob_close(&opair); return 1; }
+	unsigned long long kept = 0, bases_in = 0, bases_out = 0;
+	size_t cursor = 0;
+	int bad = 0;
+	for (uint64_t ord = 0; ord < reads; ord++) {
+		if (!oclip.ok || !opair.ok || !osingle.ok) break;                              /* a write failed: ob_close says which */
+		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
+		const sdt_read_clip *t = clip + ord;
+		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
+		if (sdt_clip_stats_note(&stats, t, len) != 0) {
+			fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->adapters, t->tail3,
+			        t->tail5, t->start, t->len, t->verdict, (unsigned long long)len);
+			bad = 1;
+			break;
+		}
+		ob_room(&oclip, SDT_CLIP_LINE_MAX);
+		oclip.p = sdt_put_clip_line(oclip.p, t);
+		bases_in += len;
+		/* (start and len sit where sdt_read_trim has them: clipsplit.h) */
+		const int to = sdt_trim_route(pairs, &cursor, (const sdt_read_trim *)clip, reads, ord);
+		if (to == SDT_TRIM_TO_NONE) continue;
+		kept++;
+		bases_out += t->len;
+		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
+		ob_room(o, (size_t)t->len + 24);
+		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start + t->start, t->len);
+	}
+	const int all_written = oclip.ok && opair.ok && osingle.ok;
+	if ((ob_close(&oclip) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
+	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
+	FILE *fs = fopen(path[3], "w");
+	if (!fs || (sdt_clip_stats_write(fs, &stats, ads) != 0) | (fclose(fs) != 0)) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path[3]); return 1; }
+	printf("%llu reads: %llu whole, %llu clipped, %llu dropped; %llu bases in, %llu bases out\n", reads, (unsigned long long)stats.whole,
+	       (unsigned long long)stats.clipped, (unsigned long long)stats.dropped, bases_in, bases_out);
+	kept_free(&k);
+	sdt_clip_stats_free(&stats);
+	free(clip);
+	return 0;
+}
+
+/* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
+static int tail_mask(const char *opt, const char *text)
+{
+	int mask = 0;
+	for (const char *c = text; *c; c++) {
+		if (!strchr("ACGTacgt", *c)) { fprintf(stderr, "sdt-kmers: %s %s: letters of ACGT are expected\n", opt, text); return -1; }
+		mask |= 1 << ((*c & 6) >> 1);
+	}
+	return mask;
+}
+
 /* the whole of text as a decimal number of at most `most`, or the option is refused by name */
 static int parse_number(const char *opt, const char *text, unsigned long long most, unsigned long long *v)
 {
@@ -609,9 +708,11 @@ static int load_queries(const char *path, int K, int nw, query_set *q)
 int main(int argc, char **argv)
 {
 	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0 && strcmp(argv[1], "correct") != 0 &&
-	                 strcmp(argv[1], "normalize") != 0 && strcmp(argv[1], "trim") != 0 && strcmp(argv[1], "dedup") != 0)) { usage(); return 255; }
+	                 strcmp(argv[1], "normalize") != 0 && strcmp(argv[1], "trim") != 0 && strcmp(argv[1], "dedup") != 0 && strcmp(argv[1], "clip") != 0)) { usage(); return 255; }
 	const int do_query = strcmp(argv[1], "query") == 0, do_correct = strcmp(argv[1], "correct") == 0, do_norm = strcmp(argv[1], "normalize") == 0;
-	const int do_trim = strcmp(argv[1], "trim") == 0, do_dedup = strcmp(argv[1], "dedup") == 0;
+	const int do_trim = strcmp(argv[1], "trim") == 0, do_dedup = strcmp(argv[1], "dedup") == 0, do_clip = strcmp(argv[1], "clip") == 0;
+	sdt_clip_params cprm = {5, 10, 0, 10, 20, 0, 0, 0};
+	char afile[2][4096] = {"", ""};                                          /* -a: 3' adapters, -g: 5' adapters */
 	sdt_dedup_params dprm = {0, 0};
 	sdt_norm_params prm = {50, 10000, 0};
 	sdt_trim_params tprm = {0, 0, 0, 0};
@@ -622,9 +723,12 @@ int main(int argc, char **argv)
 	                                   {"target", required_argument, 0, 1002}, {"max-cv", required_argument, 0, 1003},
 	                                   {"seed", required_argument, 0, 1004}, {"min-cov", required_argument, 0, 1005},
 	                                   {"min-len", required_argument, 0, 1006}, {"correct", no_argument, 0, 1007},
-	                                   {"mate-swap", no_argument, 0, 1008}, {0, 0, 0, 0}};
+	                                   {"mate-swap", no_argument, 0, 1008}, {"tail3", required_argument, 0, 1009},
+	                                   {"tail5", required_argument, 0, 1010}, {"min-overlap", required_argument, 0, 1011},
+	                                   {"error-pct", required_argument, 0, 1012}, {"min-tail", required_argument, 0, 1013},
+	                                   {"tail-error-pct", required_argument, 0, 1014}, {0, 0, 0, 0}};
 	argv++; argc--;
-	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:", longopts, NULL)) != -1) {
+	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:", longopts, NULL)) != -1) {
 		switch (c) {
 		case 's': snprintf(cfgfile, sizeof cfgfile, "%s", optarg); break;
 		case 'o': snprintf(outname, sizeof outname, "%s", optarg); break;
@@ -648,11 +752,31 @@ int main(int argc, char **argv)
 		case 1005: case 1006: case 1007: {
 			const char *opt = c == 1005 ? "--min-cov" : (c == 1006 ? "--min-len" : "--correct");
 			unsigned long long v;
-			if (!do_trim) { fprintf(stderr, "sdt-kmers: %s belongs to trim\n", opt); usage(); return 255; }
+			if (!do_trim && !(do_clip && c == 1006)) { fprintf(stderr, "sdt-kmers: %s belongs to trim%s\n", opt, c == 1006 ? " and clip" : ""); usage(); return 255; }
 			if (c == 1007) { tprm.flags |= SDT_TRIM_CORRECTED; break; }
 			if (parse_number(opt, optarg, UINT32_MAX, &v) != 0) return 255;
 			if (c == 1005) tprm.min_cov = (uint32_t)v;
-			else tprm.min_len = (uint32_t)v;
+			else tprm.min_len = cprm.min_len = (uint32_t)v;
+			break;
+		}
+		case 'a': case 'g': case 1009: case 1010: case 1011: case 1012: case 1013: case 1014: {
+			static const char *const names[] = {"--tail3", "--tail5", "--min-overlap", "--error-pct", "--min-tail", "--tail-error-pct"};
+			const char *opt = c == 'a' ? "-a" : (c == 'g' ? "-g" : names[c - 1009]);
+			unsigned long long v;
+			if (!do_clip) { fprintf(stderr, "sdt-kmers: %s belongs to clip\n", opt); usage(); return 255; }
+			if (c == 'a' || c == 'g') { snprintf(afile[c == 'g'], sizeof afile[0], "%s", optarg); break; }
+			if (c == 1009 || c == 1010) {
+				const int mask = tail_mask(opt, optarg);
+				if (mask < 0) return 255;
+				if (c == 1009) cprm.tail3_bases = (uint32_t)mask; else cprm.tail5_bases = (uint32_t)mask;
+				break;
+			}
+			if (parse_number(opt, optarg, c == 1012 || c == 1014 ? 100 : UINT32_MAX, &v) != 0) return 255;
+			if ((c == 1011 || c == 1013) && v == 0) { fprintf(stderr, "sdt-kmers: %s must be at least 1\n", opt); return 255; }
+			if (c == 1011) cprm.min_overlap = (uint32_t)v;
+			else if (c == 1012) cprm.max_err_pct = (uint32_t)v;
+			else if (c == 1013) cprm.min_tail = (uint32_t)v;
+			else cprm.tail_err_pct = (uint32_t)v;
 			break;
 		}
 		case 1008:
@@ -672,6 +796,19 @@ int main(int argc, char **argv)
 	else if (K > max_k) K = max_k;
 	const int nw = K <= 31 ? 1 : (K <= 63 ? 2 : 4);
 
+	/* the adapter files are read and checked before the device is touched, the 3' file first */
+	sdt_adapter_list ads;
+	memset(&ads, 0, sizeof ads);
+	for (int e = 0; e < 2 && do_clip; e++) {
+		char err[4400];
+		if (afile[e][0] && sdt_adapters_load(&ads, afile[e], e, err, sizeof err) != 0) { fprintf(stderr, "sdt-kmers: %s\n", err); return 2; }
+	}
+	for (uint32_t i = 0; i < ads.n; i++)
+		if (ads.offsets[i + 1] - ads.offsets[i] < cprm.min_overlap) {
+			fprintf(stderr, "sdt-kmers: adapter %s has %llu bases, fewer than --min-overlap %u\n", ads.names[i],
+			        (unsigned long long)(ads.offsets[i + 1] - ads.offsets[i]), cprm.min_overlap);
+			return 2;
+		}
 	query_set qs;
 	memset(&qs, 0, sizeof qs);
 	if (do_query) {
@@ -689,7 +826,7 @@ int main(int argc, char **argv)
 	}
 	sdt_pair_ranges pairs;
 	memset(&pairs, 0, sizeof pairs);
-	push_state st = {gpu, 0, do_norm || do_trim || do_dedup ? &pairs : NULL};
+	push_state st = {gpu, 0, do_norm || do_trim || do_dedup || do_clip ? &pairs : NULL};
 	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
 	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : threads;
 	sdt_pool_enable(sdt_gpu_host_alloc, sdt_gpu_host_free, parse_threads + PUSH_DEPTH + 8);
@@ -713,6 +850,10 @@ int main(int argc, char **argv)
 	} else if (do_dedup) {
 		if (dedup_and_write(gpu, st.reads, &dprm, &pairs, outname) != 0) return 1;
 		sdt_pair_ranges_free(&pairs);
+	} else if (do_clip) {
+		if (clip_and_write(gpu, st.reads, &cprm, &ads, &pairs, outname) != 0) return 1;
+		sdt_pair_ranges_free(&pairs);
+		sdt_adapters_free(&ads);
 	} else if (do_correct) {
 		if (correct_and_write(gpu, st.reads, (uint32_t)min_count, outname) != 0) return 1;
 	} else if (!do_query) {

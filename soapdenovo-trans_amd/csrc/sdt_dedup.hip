@@ -6,15 +6,6 @@
 #include "sdt_readstage.hpp"
 #include "sdt_dedup_kernels.cuh"
 
-// one wavefront per item, the kernels stride
-static int wave_grid(const sdt_ctx *c, uint64_t items)
-{
-	const uint64_t per = TPB / 64, cap = (uint64_t)c->cu_count * 32;
-	uint64_t blocks = items / per + (items % per != 0);
-	if (blocks > cap) blocks = cap;
-	return blocks ? (int)blocks : 1;
-}
-
 // (SDT_DEDUP_FP_BITS = 1 .. 64: test hook -- only the low bits of every unit fingerprint are kept, so that small inputs collide and
 // go through later rounds)
 static uint64_t fp_mask(void)

@@ -52,6 +52,19 @@ __device__ inline uint64_t read_chunk(const ReadRef &r, uint64_t c)
 	return nb == 32 ? v : v & ~(~0ULL >> (2 * nb));
 }
 
+// read_chunk from any base: bases [q, q + 32) of the read (q < len) as one 64-bit value, first base in the most significant pair, zero
+// past the read's end.  Only words that hold a base of the window are read.  (sdt_clip_kernels.cuh)
+__device__ inline uint64_t read_window(const ReadRef &r, uint64_t q)
+{
+	const uint64_t left = r.len - q, at = r.sh + q;
+	const uint32_t nb = left < 32 ? (uint32_t)left : 32u, sh = (uint32_t)(at & 15), last = sh + nb - 1;
+	const uint32_t *w = r.w + (at >> 4);
+	const uint64_t hi = (uint64_t)w[0] << 32 | (last >= 16 ? w[1] : 0u);
+	uint64_t v = hi << (2 * sh);
+	if (last >= 32) v |= (uint64_t)w[2] >> (32 - 2 * sh);                              // (then sh > 0)
+	return nb == 32 ? v : v & ~(~0ULL >> (2 * nb));
+}
+
 // the entry of a read ordinal in the kept form: lensh = 1 << 63 | len << 4 | sh; all zero: no kept read has this ordinal
 struct DedupEnt {
 	uint64_t fp;

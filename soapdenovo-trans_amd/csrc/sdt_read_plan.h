@@ -2,7 +2,8 @@
 // sdt_select.hip, sdt_trim.hip) decide on the host before anything reaches the device, as PURE functions: the launch geometry of a
 // strip kernel, the check of a host stream's offsets, and the cut of a host batch into the pieces that are staged one at a time.
 // sdt_readstage.hpp calls them for every stage; tools/read_plan_check.cpp (tests/test_read_plan.py) calls them on the CPU under
-// sanitizers.  No HIP in here.
+// sanitizers.  The two stages that need no table have theirs here too: the duplicate filter (sdt_dedup.hip) and the adapter and tail
+// clipping (sdt_clip.hip).  No HIP in here.
 #pragma once
 #include <stdint.h>
 
@@ -164,6 +165,74 @@ inline uint64_t dedup_table_slots(uint64_t units)
 	uint64_t slots = 2;
 	while (slots < 2 * units && slots < (1ULL << 62)) slots <<= 1;
 	return slots;
+}
+
+// ---- adapter and tail clipping (sdt_clip.hip): what is refused before any launch, and the adapters as the kernel takes them ----
+// (tools/clip_plan_check.cpp runs both checks and the split on the CPU under sanitizers)
+constexpr uint32_t CLIP_MAX_ADAPTERS = 256;              // SDT_CLIP_MAX_ADAPTERS
+constexpr uint32_t CLIP_MAX_ADAPTER_LEN = 128;           // SDT_CLIP_MAX_ADAPTER_LEN
+constexpr uint32_t CLIP_ADAPTER_CHUNKS = CLIP_MAX_ADAPTER_LEN / 32;
+
+struct ClipParams {                                      // == sdt_clip_params of include/sdt_gpu.h
+	uint32_t min_overlap, max_err_pct, min_len, min_tail, tail_err_pct, tail3_bases, tail5_bases, flags;
+};
+
+enum ClipFault {
+	CLIP_OK = 0,
+	CLIP_FLAGS, CLIP_MIN_OVERLAP, CLIP_MAX_ERR_PCT, CLIP_TAIL_ERR_PCT, CLIP_TAIL3_BASES, CLIP_TAIL5_BASES, CLIP_MIN_TAIL,      // the parameters
+	CLIP_TOO_MANY, CLIP_OFFSETS, CLIP_ADAPTER_EMPTY, CLIP_ADAPTER_LONG, CLIP_ADAPTER_SHORT, CLIP_ADAPTER_END                   // the adapter set
+};
+
+// the first field of the parameters that is refused, in the order of the struct's rules in include/sdt_gpu.h
+inline ClipFault check_clip_params(const ClipParams &p)
+{
+	if (p.flags != 0) return CLIP_FLAGS;
+	if (p.min_overlap == 0) return CLIP_MIN_OVERLAP;
+	if (p.max_err_pct > 100) return CLIP_MAX_ERR_PCT;
+	if (p.tail_err_pct > 100) return CLIP_TAIL_ERR_PCT;
+	if (p.tail3_bases > 15) return CLIP_TAIL3_BASES;
+	if (p.tail5_bases > 15) return CLIP_TAIL5_BASES;
+	if (p.min_tail == 0 && (p.tail3_bases | p.tail5_bases)) return CLIP_MIN_TAIL;
+	return CLIP_OK;
+}
+
+// n adapters of offsets[i + 1] - offsets[i] bases, ends[i] = 0 (3') or 1 (5').  *index: the adapter that is refused (n for CLIP_TOO_MANY)
+inline ClipFault check_adapter_set(const uint64_t *offsets, const uint8_t *ends, uint64_t n, uint32_t min_overlap, uint64_t *index)
+{
+	*index = n;
+	if (n > CLIP_MAX_ADAPTERS) return CLIP_TOO_MANY;
+	for (uint64_t i = 0; i < n; i++) {
+		*index = i;
+		if (offsets[i + 1] < offsets[i]) return CLIP_OFFSETS;
+		const uint64_t m = offsets[i + 1] - offsets[i];
+		if (m == 0) return CLIP_ADAPTER_EMPTY;
+		if (m > CLIP_MAX_ADAPTER_LEN) return CLIP_ADAPTER_LONG;
+		if (m < min_overlap) return CLIP_ADAPTER_SHORT;
+		if (ends[i] > 1) return CLIP_ADAPTER_END;
+	}
+	*index = n;
+	return CLIP_OK;
+}
+
+// An adapter as the kernel takes it: 32 bases per 64-bit chunk, so that one XOR with a window of the read compares 32 bases.
+//   3': chunk c holds bases [32 c, 32 c + 32), the first in the most significant pair, zero past the adapter's end
+//   5': chunk c holds bases [m - 32 c - 32, m - 32 c), the LAST in the least significant pair, zero before the adapter's start
+struct ClipAdapter {
+	uint64_t chunk[CLIP_ADAPTER_CHUNKS];
+	uint32_t m, id;                // bases; the adapter's index in the caller's set
+};
+
+// adapter `id` of a checked set (words: 16 bases per word, first base in the most significant pair)
+inline ClipAdapter split_adapter(const uint32_t *words, const uint64_t *offsets, const uint8_t *ends, uint32_t id)
+{
+	ClipAdapter a = {{0, 0, 0, 0}, (uint32_t)(offsets[id + 1] - offsets[id]), id};
+	for (uint32_t k = 0; k < a.m; k++) {
+		const uint64_t pos = offsets[id] + k;
+		const uint64_t b = (words[pos >> 4] >> (30 - 2 * (pos & 15))) & 3u;
+		if (ends[id] == 0) a.chunk[k >> 5] |= b << (62 - 2 * (k & 31));
+		else a.chunk[(a.m - 1 - k) >> 5] |= b << (2 * ((a.m - 1 - k) & 31));
+	}
+	return a;
 }
 
 } // namespace sdt

@@ -138,6 +138,15 @@ static int flags_end(sdt_ctx *c, const char *what, uint64_t max_read_len, unsign
 	return SDT_OK;
 }
 
+// the grid of a kernel that gives every wavefront one item and strides over the rest (sdt_dedup.hip, sdt_clip.hip)
+static int wave_grid(const sdt_ctx *c, uint64_t items)
+{
+	const uint64_t per = TPB / 64, cap = (uint64_t)c->cu_count * 32;
+	uint64_t blocks = items / per + (items % per != 0);
+	if (blocks > cap) blocks = cap;
+	return blocks ? (int)blocks : 1;
+}
+
 // ---- the reads kept in HBM ----
 static int kept_ready(const sdt_ctx *c)
 {
