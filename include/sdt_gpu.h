@@ -692,8 +692,58 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  * adapter of 0 or of more than 128 bases; an adapter shorter than min_overlap (it could never hit); adapter offsets that are not
  * monotonic; ends[i] > 1; NULL params.
  * Out of scope: base qualities and quality trimming (the streams have none); indels in the adapter alignment; IUPAC letters;
- * adapter detection from mate overlap; reverse-complement variants of an adapter (the user lists them as adapters of their own);
- * clipping inside pass 1 itself. */
+ * adapter detection from mate overlap (that is overlap_pairs, below: it runs in front of clip and needs no adapter list);
+ * reverse-complement variants of an adapter (the user lists them as adapters of their own); clipping inside pass 1 itself.
+ *
+ * The overlap of the two mates of a pair, and read-through pairs clipped without an adapter list.  When a fragment is shorter than
+ * the read, both mates run through into adapter; with the wrong adapter file, or a custom kit, clip_reads leaves those bases in.
+ * The two mates carry the proof themselves: mate 2 reverse-complemented lies on mate 1, and everything past the fragment's end is
+ * not transcript.  A pair that overlaps also gives the library's fragment length (avg_ins of the library config).  Needs NO counted
+ * table, no adapter list and no base qualities; overlap -> compact_trimmed_device -> clip -> ... -> count goes without a copy to the
+ * host.  Added without a change of SDT_ABI_VERSION: the three calls and the two structs are additions.
+ *     Integers only.  Every pair is decided on its own.  Nothing is read but the two mates.  The result does not depend on the launch
+ *     geometry or on where a read starts in its word.
+ *     Bases are the stream's codes (A 0, C 1, T 2, G 3), so the complement of code x is x ^ 2.
+ *     A pair is (a, b): a of La bases, b of Lb bases.  b' is the reverse complement of b: b'[q] = b[Lb - 1 - q] ^ 2.
+ *     SHIFT.   Putting b'[0] under a[d] is the shift d, -Lb < d < La.  Its insert (the fragment length it implies) is F = d + Lb >= 1.
+ *              Its columns are i in [max(0, d), min(La, d + Lb)).  o is their number.  h is the number of columns with
+ *              a[i] != b'[i - d].
+ *     ADMISSIBLE.  d is ADMISSIBLE iff o >= min_overlap and 100 h <= max_err_pct o.
+ *     THE PAIR'S OVERLAP is the admissible shift of greatest score o - 3 h (+1 a match, -2 a mismatch, the scoring of clip's tails).
+ *              Among equal scores the greatest F wins (the one that clips least).  If no shift is admissible, there is no overlap.
+ *     KEPT BASES.  With an overlap of insert F, every mate keeps start = 0, len = min(L, F).  Whatever a read holds past the
+ *              fragment's end is adapter, on either mate and for unequal mate lengths alike.  Without an overlap, len = L.
+ *     VERDICT, with the numbers of sdt_read_trim; the first line that applies:
+ *         3  dropped   len < max(min_len, 1)                        record: start = len = 0
+ *         0  whole     len == L
+ *         2  clipped   otherwise
+ *     RECORD.  Both mates get overlap = o, mismatches = h, insert = F of the chosen shift (all 0 without one).  A dropped read's
+ *              record still says what was found.  Mates are judged for min_len independently, as in clip.
+ *     SINGLE READS.  The kept form's ordinals outside every pair range, and a pair of which one mate is not kept in HBM, get the
+ *              record of a pair without overlap.
+ *     Defaults of the command line: min_overlap 30, max_err_pct 10, min_len 0.  Chance hits, by brute force on the CPU: of 3 000
+ *     pairs of random 150-base reads, none had an admissible shift at min_overlap 12, 16, 20 or 30 under 10 %.
+ *   overlap_pairs:  ov[i] for read i of a batch (packed as for sdt_gpu_push_reads) in which reads 2t and 2t + 1 are mates; keep (may
+ *                   be NULL): keep[i] = len > 0; *n_kept = reads with len > 0.  The batch is staged in pieces of whole pairs.
+ *   overlap_pairs_device: buffers already on the device (d_ov nreads records of 24 bytes, d_keep nreads bytes or NULL).  The call
+ *                   waits for the kernel to know *n_kept.  d_ov is what sdt_gpu_compact_trimmed_device takes: start, len and verdict
+ *                   sit where sdt_read_trim has them, so both compaction calls take an array of sdt_read_overlap through a pointer cast.
+ *   overlap_kept_pairs: the reads kept in HBM, over ALL kept batches at once (mates sit in different batches); ov[] by READ ORDINAL
+ *                   like dedup_kept_reads (SDT_EFULL, nothing written, when a kept read's ordinal is >= out_capacity; records of
+ *                   ordinals that no kept read has are left untouched); pair_ranges with the meaning and the checks of
+ *                   select_kept_reads.  *nreads = reads decided, *n_kept = reads with len > 0.  The kept reads are NOT changed.
+ * State: the dense forms need a context for its stream only: any state, any kind of context, like dedup_reads.  The kept form
+ * follows the rules of sdt_gpu_kept_batches.  nreads == 0: SDT_OK, nothing touched.  There is NO limit on the read length: a
+ * wavefront walks the shifts 64 at a time (start, len and insert are 32-bit, as in sdt_read_trim).
+ * SDT_EINVAL, from a check on the host before any launch, with a message that names the field and its value: flags != 0;
+ * min_overlap == 0; max_err_pct > 100; NULL params; an odd nreads in the dense forms; pair ranges that select_kept_reads refuses.
+ * Device memory held during the call, beside the reads, SDT_ENOMEM (nothing written) when it does not fit:
+ *     device form       8 B (the counter of the reads kept)
+ *     host form         the piece of the stream that is staged, and 24 B + 1 B per read of it for records and keep
+ *     kept form         per ordinal up to the highest kept one: 24 B (where the read's bases start and its length: the entry of
+ *                       dedup_kept_reads) and the 24 B record; 24 B per stretch of units (at most 2 x n_ranges + 1)
+ * Out of scope: merging the mates into one read; correcting mismatching bases in the overlap (needs qualities); indels; overlaps in
+ * which mate 2 is not reverse-complemented; any change to clip. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -711,6 +761,8 @@ typedef struct { uint32_t min_overlap, max_err_pct, min_len, min_tail,
                           tail_err_pct, tail3_bases, tail5_bases, flags; } sdt_clip_params;
 typedef struct { const uint32_t *words; const uint64_t *offsets; const uint8_t *ends;
                  uint32_t n, reserved; } sdt_adapter_set;
+typedef struct { uint32_t overlap, mismatches, insert, start, len, verdict; } sdt_read_overlap;   /* 24 bytes */
+typedef struct { uint32_t min_overlap, max_err_pct, min_len, flags; } sdt_overlap_params;
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -775,6 +827,14 @@ int sdt_gpu_clip_reads_device(sdt_ctx *ctx, const void *d_packed_words, const vo
                               uint64_t *n_kept);
 int sdt_gpu_clip_kept_reads(sdt_ctx *ctx, const sdt_clip_params *params, const sdt_adapter_set *adapters,
                             sdt_read_clip *clip, uint64_t out_capacity, uint64_t *nreads, uint64_t *n_kept);
+int sdt_gpu_overlap_pairs(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                          uint64_t nreads, const sdt_overlap_params *params, sdt_read_overlap *ov, uint8_t *keep,
+                          uint64_t *n_kept);
+int sdt_gpu_overlap_pairs_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                                 const sdt_overlap_params *params, void *d_ov, void *d_keep, uint64_t *n_kept);
+int sdt_gpu_overlap_kept_pairs(sdt_ctx *ctx, const sdt_overlap_params *params, const uint64_t *pair_ranges,
+                               uint64_t n_ranges, sdt_read_overlap *ov, uint64_t out_capacity, uint64_t *nreads,
+                               uint64_t *n_kept);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

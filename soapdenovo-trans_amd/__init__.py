@@ -162,6 +162,12 @@ _ABI = [
                                              _c.c_void_p, _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_clip_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64),
                                            _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_overlap_pairs", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                         _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_overlap_pairs_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_overlap_kept_pairs", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64,
+                                              _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -187,6 +193,10 @@ SDT_DEDUP_MATE_SWAP = 1
 READ_CLIP_DTYPE = np.dtype([(f, np.uint32) for f in ("adapters", "tail3", "tail5", "start", "len", "verdict")])
 CLIP_WHOLE, CLIP_CLIPPED, CLIP_DROPPED = 0, 2, 3
 CLIP_MAX_ADAPTERS, CLIP_MAX_ADAPTER_LEN = 256, 128
+# sdt_read_overlap (include/sdt_gpu.h): one record per read of a mate overlap; overlap, mismatches and insert are the pair's (0: none); the
+# kept bases are [start, start + len) of the read, where READ_TRIM_DTYPE has them
+READ_OVERLAP_DTYPE = np.dtype([(f, np.uint32) for f in ("overlap", "mismatches", "insert", "start", "len", "verdict")])
+OVERLAP_WHOLE, OVERLAP_CLIPPED, OVERLAP_DROPPED = 0, 2, 3
 
 
 class NormParams(_c.Structure):
@@ -208,6 +218,14 @@ class ClipParams(_c.Structure):
     """sdt_clip_params; tail3_bases / tail5_bases: masks of base codes (A 1, C 2, T 4, G 8)"""
     _fields_ = [(f, _c.c_uint32) for f in ("min_overlap", "max_err_pct", "min_len", "min_tail", "tail_err_pct", "tail3_bases", "tail5_bases",
                                            "flags")]
+
+
+class OverlapParams(_c.Structure):
+    """sdt_overlap_params; the defaults of `sdt-kmers overlap`"""
+    _fields_ = [(f, _c.c_uint32) for f in ("min_overlap", "max_err_pct", "min_len", "flags")]
+
+    def __init__(self, min_overlap=30, max_err_pct=10, min_len=0, flags=0):
+        super().__init__(min_overlap, max_err_pct, min_len, flags)
 
 
 class AdapterSet(_c.Structure):
@@ -925,6 +943,49 @@ class PregraphGPU:
         n, kept = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self.lib.sdt_gpu_clip_kept_reads(self._ctx, ctypes.addressof(prm), ctypes.addressof(aset), _ptr(out), total_reads,
                                                      ctypes.byref(n), ctypes.byref(kept)))
+        return out, n.value, kept.value
+
+    # -- the overlap of the two mates of a pair; read-through pairs clipped without an adapter list (the rule: include/sdt_gpu.h)
+    @staticmethod
+    def _overlap_params(params):
+        """params: OverlapParams or its fields as a dict"""
+        return params if isinstance(params, OverlapParams) else OverlapParams(**(params or {}))
+
+    def overlap_pairs(self, words, offsets, params=None):
+        """reads 2t and 2t + 1 are mates
+        -> (READ_OVERLAP_DTYPE[nreads]: overlap, mismatches, insert, start, len, verdict; keep uint8[nreads]; reads with len > 0)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        ov = np.zeros(n, dtype=READ_OVERLAP_DTYPE)
+        keep = np.zeros(n, dtype=np.uint8)
+        prm = self._overlap_params(params)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_overlap_pairs(self._ctx, _ptr(words), words.size, _ptr(offsets), n, ctypes.addressof(prm), _ptr(ov), _ptr(keep),
+                                                   ctypes.byref(kept)))
+        return ov, keep, kept.value
+
+    def overlap_pairs_device(self, d_words, d_offsets, nreads: int, d_ov, d_keep=None, params=None) -> int:
+        """device buffers; d_ov holds nreads records of 24 bytes (what compact_trimmed_device takes), d_keep (optional) nreads bytes
+        -> reads with len > 0 (waits for the kernel)"""
+        prm = self._overlap_params(params)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_overlap_pairs_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, ctypes.addressof(prm), _ptr(d_ov),
+                                                          _ptr(d_keep), ctypes.byref(kept)))
+        return kept.value
+
+    def overlap_kept_pairs(self, total_reads: int, pair_ranges=(), params=None, out: np.ndarray = None):
+        """the reads kept in HBM; pair_ranges: [first, end) of ordinals that hold interleaved pairs, flat or as rows
+        -> (READ_OVERLAP_DTYPE[total_reads] by read ordinal, reads decided, reads with len > 0)"""
+        if out is None:
+            out = np.zeros(total_reads, dtype=READ_OVERLAP_DTYPE)
+        assert out.dtype == READ_OVERLAP_DTYPE and out.flags.c_contiguous and len(out) >= total_reads
+        ranges = np.ascontiguousarray(np.asarray(pair_ranges, dtype=np.uint64).reshape(-1))
+        assert ranges.size % 2 == 0
+        prm = self._overlap_params(params)
+        n, kept = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_overlap_kept_pairs(self._ctx, ctypes.addressof(prm), _ptr(ranges) if ranges.size else None, ranges.size // 2,
+                                                        _ptr(out), total_reads, ctypes.byref(n), ctypes.byref(kept)))
         return out, n.value, kept.value
 
     def set_read_ordinal(self, base: int, stride: int = 1):

@@ -47,6 +47,14 @@
  *       prefix.readClip: one line per read in stream order:  adapter3 adapter5 tail3 tail5 start len verdict
  *       prefix.clip.pairs.fa / prefix.clip.single.fa: the kept bases of the surviving reads, as trim writes them
  *       prefix.clipStats: per adapter  index name end reads bases,  then tail3 / tail5  reads bases,  then whole, clipped, dropped
+ *   sdt-kmers overlap -s lib.cfg -K k [-p threads] [--min-overlap N, default 30] [--max-err PCT, default 10] [--min-len L, default 0]
+ *                     -o prefix
+ *       the overlap of the two mates of every pair, and what lies past the fragment's end clipped from both mates without an adapter
+ *       list (sdt_gpu_overlap_kept_pairs; the rule: include/sdt_gpu.h).  Pairs as for normalize, routing as for clip; a library
+ *       without pairs is allowed: every read is whole (overlapsplit.c)
+ *       prefix.readOverlap: one line per read in stream order:  overlap mismatches insert start len verdict
+ *       prefix.overlap.pairs.fa / prefix.overlap.single.fa: the kept bases of the surviving reads, as clip writes them
+ *       prefix.insertHist: per insert that occurs, ascending:  insert pairs,  then  # pairs P overlapping V clipped C median M
  *
  * The query file is read and checked before the device is touched. */
 #include <errno.h>
@@ -63,6 +71,7 @@
 #include "trimsplit.h"
 #include "dupsplit.h"
 #include "clipsplit.h"
+#include "overlapsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -118,6 +127,17 @@ static void usage(void)
 	        "              the pairs of which both mates survive), prefix.clip.single.fa (every other surviving read), prefix.clipStats\n"
 	        "              (per adapter: index name end reads bases; tail3 and tail5: reads bases; whole, clipped, dropped: reads)\n"
 	        "           Pairs are the reads of q1=/q2= and f1=/f2= files, mates are clipped independently, as for trim.\n"
+	        "       sdt-kmers overlap -s lib.cfg -K k [-p threads] [--min-overlap N, default 30] [--max-err PCT, default 10]\n"
+	        "                         [--min-len L, default 0] -o prefix\n"
+	        "           mate 2 of every pair, reverse-complemented, is laid on mate 1 at every shift; the best shift with N columns or more\n"
+	        "           and at most PCT percent mismatches (no indels) is the pair's overlap and gives the fragment length (insert); what a\n"
+	        "           mate holds past the fragment's end is adapter and is clipped, whatever the adapter was; a read of which fewer than\n"
+	        "           max(L, 1) bases are left is dropped.  Needs no adapter list and no counted k-mers: run it in front of clip.\n"
+	        "           -> prefix.readOverlap (per read in stream order: overlap mismatches insert start len verdict; verdict 0 whole,\n"
+	        "              2 clipped, 3 dropped), prefix.overlap.pairs.fa (read 1 then read 2 of the pairs of which both mates survive),\n"
+	        "              prefix.overlap.single.fa (every other surviving read), prefix.insertHist (per insert that occurs, ascending:\n"
+	        "              insert pairs; then: # pairs P overlapping V clipped C median M, the lower median of the inserts)\n"
+	        "           Pairs are the reads of q1=/q2= and f1=/f2= files; the reads of a p= file are single reads, as for normalize.\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -630,6 +650,83 @@ static int clip_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_clip
 	return 0;
 }
 
+/* `overlap`: the records from the device, the kept batches back from HBM, the kept bases of every read into the pairs file (both mates
+ * survive) or the singles file, routed as trim routes them; the histogram of the inserts (overlapsplit.c) */
+static int overlap_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_overlap_params *prm, const sdt_pair_ranges *pairs, const char *prefix)
+{
+	const uint64_t m = reads ? reads : 1;
+	sdt_read_overlap *ov = (sdt_read_overlap *)calloc(m, sizeof(sdt_read_overlap));
+	if (!ov) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	uint64_t got = 0, n_kept = 0;
+	if (sdt_gpu_overlap_kept_pairs(gpu, prm, pairs->v, pairs->n, ov, reads, &got, &n_kept) != SDT_OK) {
+		fprintf(stderr, "sdt_gpu_overlap_kept_pairs: %s\n", sdt_gpu_last_error());
+		return 1;
+	}
+	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu decided\n", reads, (unsigned long long)got); return 1; }
+	kept_reads k;
+	if (kept_fetch(gpu, reads, &k) != 0) return 1;
+	char path[4][4200];
+	snprintf(path[0], sizeof path[0], "%s.readOverlap", prefix);
+	snprintf(path[1], sizeof path[1], "%s.overlap.pairs.fa", prefix);
+	snprintf(path[2], sizeof path[2], "%s.overlap.single.fa", prefix);
+	snprintf(path[3], sizeof path[3], "%s.insertHist", prefix);
+	outbuf oov, opair, osingle;
+	if (ob_open(&oov, path[0]) != 0) return 1;
+	if (ob_open(&opair, path[1]) != 0) { ob_close(&oov); return 1; }
+	if (ob_open(&osingle, path[2]) != 0) { ob_close(&oov); ob_close(&opair); return 1; }
+	sdt_insert_hist hist;
+	memset(&hist, 0, sizeof hist);
+	unsigned long long kept = 0, by_verdict[4] = {0, 0, 0, 0}, bases_in = 0, bases_out = 0;
+	size_t cursor = 0, pcursor = 0;
+	uint64_t len_first = 0;                                                  /* the first mate's bases, while the second is awaited */
+	int bad = 0;
+	for (uint64_t ord = 0; ord < reads; ord++) {
+		if (!oov.ok || !opair.ok || !osingle.ok) break;                              /* a write failed: ob_close says which */
+		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
+		const sdt_read_overlap *t = ov + ord;
+		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
+		int ok = sdt_overlap_record_ok(t, len);
+		if (ok && sdt_pair_ranges_holds(pairs, ord, &pcursor)) {
+			if (((ord - pairs->v[2 * pcursor]) & 1) == 0) len_first = len;
+			else {
+				const int rc = sdt_insert_hist_note(&hist, t - 1, t, len_first, len);
+				if (rc == -1) { fprintf(stderr, "sdt-kmers: out of memory\n"); bad = 1; break; }
+				ok = rc == 0;
+			}
+		}
+		if (!ok) {
+			fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->overlap, t->mismatches,
+			        t->insert, t->start, t->len, t->verdict, (unsigned long long)len);
+			bad = 1;
+			break;
+		}
+		ob_room(&oov, SDT_OVERLAP_LINE_MAX);
+		oov.p = sdt_put_overlap_line(oov.p, t);
+		by_verdict[t->verdict]++;
+		bases_in += len;
+		/* (start and len sit where sdt_read_trim has them: overlapsplit.h) */
+		const int to = sdt_trim_route(pairs, &cursor, (const sdt_read_trim *)ov, reads, ord);
+		if (to == SDT_TRIM_TO_NONE) continue;
+		kept++;
+		bases_out += t->len;
+		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
+		ob_room(o, (size_t)t->len + 24);
+		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start + t->start, t->len);
+	}
+	const int all_written = oov.ok && opair.ok && osingle.ok;
+	if ((ob_close(&oov) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
+	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
+	const unsigned long long overlapping = hist.n, median = sdt_insert_hist_median(&hist);
+	FILE *fh = fopen(path[3], "w");
+	if (!fh || (sdt_insert_hist_write(fh, &hist) != 0) | (fclose(fh) != 0)) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path[3]); return 1; }
+	printf("%llu reads: %llu whole, %llu clipped, %llu dropped; %llu bases in, %llu bases out; %llu pairs, %llu overlapping, median insert %llu\n", reads,
+	       by_verdict[0], by_verdict[2], by_verdict[3], bases_in, bases_out, (unsigned long long)hist.pairs, overlapping, median);
+	kept_free(&k);
+	sdt_insert_hist_free(&hist);
+	free(ov);
+	return 0;
+}
+
 /* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
 static int tail_mask(const char *opt, const char *text)
 {
@@ -708,9 +805,12 @@ static int load_queries(const char *path, int K, int nw, query_set *q)
 int main(int argc, char **argv)
 {
 	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0 && strcmp(argv[1], "correct") != 0 &&
-	                 strcmp(argv[1], "normalize") != 0 && strcmp(argv[1], "trim") != 0 && strcmp(argv[1], "dedup") != 0 && strcmp(argv[1], "clip") != 0)) { usage(); return 255; }
+	                 strcmp(argv[1], "normalize") != 0 && strcmp(argv[1], "trim") != 0 && strcmp(argv[1], "dedup") != 0 && strcmp(argv[1], "clip") != 0 &&
+	                 strcmp(argv[1], "overlap") != 0)) { usage(); return 255; }
 	const int do_query = strcmp(argv[1], "query") == 0, do_correct = strcmp(argv[1], "correct") == 0, do_norm = strcmp(argv[1], "normalize") == 0;
 	const int do_trim = strcmp(argv[1], "trim") == 0, do_dedup = strcmp(argv[1], "dedup") == 0, do_clip = strcmp(argv[1], "clip") == 0;
+	const int do_overlap = strcmp(argv[1], "overlap") == 0;
+	sdt_overlap_params oprm = {30, 10, 0, 0};
 	sdt_clip_params cprm = {5, 10, 0, 10, 20, 0, 0, 0};
 	char afile[2][4096] = {"", ""};                                          /* -a: 3' adapters, -g: 5' adapters */
 	sdt_dedup_params dprm = {0, 0};
@@ -726,7 +826,8 @@ int main(int argc, char **argv)
 	                                   {"mate-swap", no_argument, 0, 1008}, {"tail3", required_argument, 0, 1009},
 	                                   {"tail5", required_argument, 0, 1010}, {"min-overlap", required_argument, 0, 1011},
 	                                   {"error-pct", required_argument, 0, 1012}, {"min-tail", required_argument, 0, 1013},
-	                                   {"tail-error-pct", required_argument, 0, 1014}, {0, 0, 0, 0}};
+	                                   {"tail-error-pct", required_argument, 0, 1014}, {"max-err", required_argument, 0, 1015},
+	                                   {0, 0, 0, 0}};
 	argv++; argc--;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:", longopts, NULL)) != -1) {
 		switch (c) {
@@ -752,18 +853,22 @@ int main(int argc, char **argv)
 		case 1005: case 1006: case 1007: {
 			const char *opt = c == 1005 ? "--min-cov" : (c == 1006 ? "--min-len" : "--correct");
 			unsigned long long v;
-			if (!do_trim && !(do_clip && c == 1006)) { fprintf(stderr, "sdt-kmers: %s belongs to trim%s\n", opt, c == 1006 ? " and clip" : ""); usage(); return 255; }
+			if (!do_trim && !((do_clip || do_overlap) && c == 1006)) {
+				fprintf(stderr, "sdt-kmers: %s belongs to trim%s\n", opt, c == 1006 ? ", clip and overlap" : "");
+				usage();
+				return 255;
+			}
 			if (c == 1007) { tprm.flags |= SDT_TRIM_CORRECTED; break; }
 			if (parse_number(opt, optarg, UINT32_MAX, &v) != 0) return 255;
 			if (c == 1005) tprm.min_cov = (uint32_t)v;
-			else tprm.min_len = cprm.min_len = (uint32_t)v;
+			else tprm.min_len = cprm.min_len = oprm.min_len = (uint32_t)v;
 			break;
 		}
 		case 'a': case 'g': case 1009: case 1010: case 1011: case 1012: case 1013: case 1014: {
 			static const char *const names[] = {"--tail3", "--tail5", "--min-overlap", "--error-pct", "--min-tail", "--tail-error-pct"};
 			const char *opt = c == 'a' ? "-a" : (c == 'g' ? "-g" : names[c - 1009]);
 			unsigned long long v;
-			if (!do_clip) { fprintf(stderr, "sdt-kmers: %s belongs to clip\n", opt); usage(); return 255; }
+			if (!do_clip && !(do_overlap && c == 1011)) { fprintf(stderr, "sdt-kmers: %s belongs to clip\n", opt); usage(); return 255; }
 			if (c == 'a' || c == 'g') { snprintf(afile[c == 'g'], sizeof afile[0], "%s", optarg); break; }
 			if (c == 1009 || c == 1010) {
 				const int mask = tail_mask(opt, optarg);
@@ -773,10 +878,17 @@ int main(int argc, char **argv)
 			}
 			if (parse_number(opt, optarg, c == 1012 || c == 1014 ? 100 : UINT32_MAX, &v) != 0) return 255;
 			if ((c == 1011 || c == 1013) && v == 0) { fprintf(stderr, "sdt-kmers: %s must be at least 1\n", opt); return 255; }
-			if (c == 1011) cprm.min_overlap = (uint32_t)v;
+			if (c == 1011) cprm.min_overlap = oprm.min_overlap = (uint32_t)v;
 			else if (c == 1012) cprm.max_err_pct = (uint32_t)v;
 			else if (c == 1013) cprm.min_tail = (uint32_t)v;
 			else cprm.tail_err_pct = (uint32_t)v;
+			break;
+		}
+		case 1015: {
+			unsigned long long v;
+			if (!do_overlap) { fprintf(stderr, "sdt-kmers: --max-err belongs to overlap\n"); usage(); return 255; }
+			if (parse_number("--max-err", optarg, 100, &v) != 0) return 255;
+			oprm.max_err_pct = (uint32_t)v;
 			break;
 		}
 		case 1008:
@@ -826,7 +938,7 @@ int main(int argc, char **argv)
 	}
 	sdt_pair_ranges pairs;
 	memset(&pairs, 0, sizeof pairs);
-	push_state st = {gpu, 0, do_norm || do_trim || do_dedup || do_clip ? &pairs : NULL};
+	push_state st = {gpu, 0, do_norm || do_trim || do_dedup || do_clip || do_overlap ? &pairs : NULL};
 	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
 	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : threads;
 	sdt_pool_enable(sdt_gpu_host_alloc, sdt_gpu_host_free, parse_threads + PUSH_DEPTH + 8);
@@ -854,6 +966,9 @@ int main(int argc, char **argv)
 		if (clip_and_write(gpu, st.reads, &cprm, &ads, &pairs, outname) != 0) return 1;
 		sdt_pair_ranges_free(&pairs);
 		sdt_adapters_free(&ads);
+	} else if (do_overlap) {
+		if (overlap_and_write(gpu, st.reads, &oprm, &pairs, outname) != 0) return 1;
+		sdt_pair_ranges_free(&pairs);
 	} else if (do_correct) {
 		if (correct_and_write(gpu, st.reads, (uint32_t)min_count, outname) != 0) return 1;
 	} else if (!do_query) {

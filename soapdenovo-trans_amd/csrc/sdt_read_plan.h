@@ -2,8 +2,8 @@
 // sdt_select.hip, sdt_trim.hip) decide on the host before anything reaches the device, as PURE functions: the launch geometry of a
 // strip kernel, the check of a host stream's offsets, and the cut of a host batch into the pieces that are staged one at a time.
 // sdt_readstage.hpp calls them for every stage; tools/read_plan_check.cpp (tests/test_read_plan.py) calls them on the CPU under
-// sanitizers.  The two stages that need no table have theirs here too: the duplicate filter (sdt_dedup.hip) and the adapter and tail
-// clipping (sdt_clip.hip).  No HIP in here.
+// sanitizers.  The three stages that need no table have theirs here too: the duplicate filter (sdt_dedup.hip), the adapter and tail
+// clipping (sdt_clip.hip) and the mate overlap (sdt_overlap.hip).  No HIP in here.
 #pragma once
 #include <stdint.h>
 
@@ -233,6 +233,33 @@ inline ClipAdapter split_adapter(const uint32_t *words, const uint64_t *offsets,
 		else a.chunk[(a.m - 1 - k) >> 5] |= b << (2 * ((a.m - 1 - k) & 31));
 	}
 	return a;
+}
+
+// ---- mate overlap (sdt_overlap.hip): what is refused before any launch, and the shifts a pair is tried at ----
+// (tools/overlap_plan_check.cpp runs the check and holds the span of the shifts to a walk over every shift)
+struct OverlapParams {                                   // == sdt_overlap_params of include/sdt_gpu.h
+	uint32_t min_overlap, max_err_pct, min_len, flags;
+};
+
+enum OverlapFault { OVERLAP_OK = 0, OVERLAP_FLAGS, OVERLAP_MIN_OVERLAP, OVERLAP_MAX_ERR_PCT, OVERLAP_ODD_READS };
+
+// the first thing that is refused, in the order of the rules in include/sdt_gpu.h; dense_reads: the reads of a dense form, in which
+// reads 2t and 2t + 1 are mates (0 for the kept form)
+inline OverlapFault check_overlap_params(const OverlapParams &p, uint64_t dense_reads)
+{
+	if (p.flags != 0) return OVERLAP_FLAGS;
+	if (p.min_overlap == 0) return OVERLAP_MIN_OVERLAP;
+	if (p.max_err_pct > 100) return OVERLAP_MAX_ERR_PCT;
+	if (dense_reads & 1) return OVERLAP_ODD_READS;
+	return OVERLAP_OK;
+}
+
+// Mates of La and Lb bases: the shifts d whose overlap o = min(La, d + Lb) - max(0, d) is at least min_overlap (>= 1) are the
+// overlap_shifts() consecutive ones from d = min_overlap - Lb, up to d = La - min_overlap; none when a mate is shorter than min_overlap.
+// (constexpr: the kernel calls it too)
+constexpr uint64_t overlap_shifts(uint64_t La, uint64_t Lb, uint32_t min_overlap)
+{
+	return La < min_overlap || Lb < min_overlap ? 0 : La + Lb - 2 * (uint64_t)min_overlap + 1;
 }
 
 } // namespace sdt
