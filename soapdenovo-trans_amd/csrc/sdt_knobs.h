@@ -34,6 +34,14 @@ static inline const char *sdt_tuning_env(const char *name)
 #endif
 }
 
+/* the size thresholds of the locality pipeline (csrc/sdt_pipeline.hpp: batch, count launch, work item sizes) are tuning switches AND test
+ * hooks: tests/test_fullsize_paths.py shrinks them so that inputs of test size take the branches that only a full-size batch reaches */
+static inline const char *sdt_size_env(const char *name)
+{
+	const char *v = sdt_tuning_env(name);
+	return v ? v : sdt_test_env(name);
+}
+
 static inline int sdt_knob_int(const char *v, int dflt) { return v && *v ? atoi(v) : dflt; }
 
 #endif
