@@ -743,7 +743,71 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  *     kept form         per ordinal up to the highest kept one: 24 B (where the read's bases start and its length: the entry of
  *                       dedup_kept_reads) and the 24 B record; 24 B per stretch of units (at most 2 x n_ranges + 1)
  * Out of scope: merging the mates into one read; correcting mismatching bases in the overlap (needs qualities); indels; overlaps in
- * which mate 2 is not reverse-complemented; any change to clip. */
+ * which mate 2 is not reverse-complemented; any change to clip.
+ *
+ * Low-complexity reads flagged, dropped or trimmed: reads, or parts of reads, that are homopolymers, di- or tri-nucleotide repeats, or
+ * runs of N (the 2-bit stream cannot show N: the host codes it as G, so a run of N arrives as poly-G, and nothing downstream can tell
+ * a called G-run from an N-run).  clip_reads removes tails at the ends only; internal poly-A, (AC)n and poly-G runs still reach the
+ * table, where their k-mers make the giant minimizer buckets of pass 1, and, being solid (they recur across transcripts),
+ * correct_reads and trim_reads leave them in and they join unrelated transcripts in the graph.  Needs NO counted table, no base
+ * qualities and no pair logic; overlap -> compact_trimmed -> clip -> compact_trimmed -> complexity -> compact_trimmed -> dedup ->
+ * compact -> count goes without a copy to the host.  Added without a change of SDT_ABI_VERSION: the three calls and the two structs
+ * are additions.
+ *     Integers only.  Every read is decided on its own.  Nothing is read but the read.  The result does not depend on the launch
+ *     geometry or on where a read starts in its word.  Bases are the stream's codes (A 0, C 1, T 2, G 3); a read has L bases r[0, L).
+ *     WINDOWS.  W = 0 for L = 0, else W = max(1, ceil(L / 32) - 1).  Window j is [32 j, min(32 j + 64, L)), with m_j bases and
+ *              l_j = max(0, m_j - 2) triplets (r[i], r[i + 1], r[i + 2]).  So L = 150 gives [0,64) [32,96) [64,128) [96,150), L = 64
+ *              one window, L = 65 two, and the last window always has more than 32 bases unless it is the only one.  With c_t the
+ *              number of the window's triplets of kind t (64 kinds), D_j = sum over t of c_t (c_t - 1): the number of ordered pairs
+ *              of equal triplets, 0 <= D_j <= l_j (l_j - 1).
+ *     LOW.     Window j is LOW iff l_j >= 2 and 100 D_j >= max_score_pct l_j (l_j - 1).
+ *     SCORE.   The read's score is the maximum over the windows with l_j >= 2 of floor(100 D_j / (l_j (l_j - 1))); without such a
+ *              window it is 0.  A homopolymer scores 100.
+ *     LOW BASES.  A base is low iff a LOW window covers it; B is the number of low bases.  The clean stretch is the longest run of
+ *              bases that are not low, the first among equals: (s, n), n = 0 if all are low.
+ *     KEPT RANGE.  flags = 0 (filter): start = 0, len = L, unless 100 B > max_low_pct L, in which case len = 0.
+ *              SDT_COMPLEXITY_TRIM: start = s, len = n; max_low_pct must be 0.
+ *     VERDICT, with the numbers of sdt_read_trim; the first line that applies:
+ *         3  dropped   len < max(min_len, 1)                        record: start = len = 0
+ *         0  whole     len == L
+ *         2  clipped   otherwise
+ *     RECORD.  windows = W, low = the number of LOW windows, score; start, len and verdict sit where sdt_read_trim has them.  A
+ *              dropped read's record still says what was found.
+ *     What the score does, on the CPU (numpy, seed 1): repeats of period 1 / 2 / 3 / 4 / 6 fill a 64-base window with scores
+ *     100 / 49 / 32 / 23 / 15.  A random window has mean score 1.56 at every length; of 200 000 random 64-base windows none reached
+ *     7 (the maximum was 5.6); of 200 000 random 33-base windows 46 (0.02 %) reached 7 and 6 (0.003 %) reached 10.  Of 20 000
+ *     random reads, those with a LOW window at max_score_pct 10 / 7 / 5: L = 150: 0 / 0 / 6; L = 100: 0 / 3 / 28; L = 97: 0 / 3 / 35
+ *     (the short last window is where chance hits).  A run planted at base 60 of 200 random 150-base reads, at 10: poly-A of 20
+ *     bases alone scores 8 (18 triplets of 62: 306 of 3 782) and passes; with what chance adds the median score was 9 and 77 reads
+ *     had a low window.  Poly-A of 25 bases: median 15, one window low in 92 reads and two in 108.  Poly-A of 30 bases: median 21,
+ *     both covering windows low in all 200.  (AC)n of 30 bases: median 11, a low window in 182 reads.  A run that falls into a short
+ *     last window weighs more: 20 bases of poly-A in a window of 54 score 11.
+ *     Hence the defaults of the command line: max_score_pct 10, max_low_pct 50, min_len 0.  The 50 is a choice, not a measurement:
+ *     a 150-base read with one 30-base internal run has 96 of its 150 bases low and is dropped under it.  Known coarseness: a low
+ *     window is low as a whole, so under SDT_COMPLEXITY_TRIM it removes all 64 of its bases.
+ *   complexity_reads: cx[i] for read i of a batch (packed as for sdt_gpu_push_reads); keep (may be NULL): keep[i] = len > 0;
+ *                   *n_kept = reads with len > 0.  The batch is staged in pieces as for profile_reads.
+ *   complexity_reads_device: buffers already on the device (d_cx nreads records of 24 bytes, d_keep nreads bytes or NULL).  The call
+ *                   waits for the kernel to know *n_kept.  d_cx is what sdt_gpu_compact_trimmed_device takes: both compaction calls
+ *                   take an array of sdt_read_complexity through a pointer cast.
+ *   complexity_kept_reads: the reads kept in HBM, batch by batch; cx[] by READ ORDINAL like trim_kept_reads (SDT_EFULL, nothing
+ *                   written, when a kept read's ordinal is >= out_capacity; records of ordinals that no kept read has are left
+ *                   untouched).  SDT_ESTATE when batches were pushed and sdt_gpu_finish_count has not drained them, whether
+ *                   their copies are still queued or they are counted and not yet synchronised.  *nreads = reads decided.  Mates are judged
+ *                   independently.  The kept reads are NOT changed.
+ * State: the dense forms need a context for its stream only: any state, any kind of context, like dedup_reads.  The kept form
+ * follows the rules of sdt_gpu_kept_batches.  nreads == 0: SDT_OK, nothing touched.  There is NO limit on the read length: a
+ * wavefront walks a read one window at a time (windows, low, start and len are 32-bit, as in sdt_read_trim).
+ * SDT_EINVAL, from a check on the host before any launch, with a message that names the field and its value: NULL params; flag bits
+ * other than SDT_COMPLEXITY_TRIM; max_score_pct 0 (every window would be low) or > 100; max_low_pct > 100; max_low_pct != 0 under
+ * SDT_COMPLEXITY_TRIM.
+ * Device memory held during the call, beside the reads, SDT_ENOMEM (nothing written) when it does not fit:
+ *     device form       8 B (the counter of the reads kept)
+ *     host form         the piece of the stream that is staged, and 24 B + 1 B per read of it for records and keep
+ *     kept form         the 24 B records of the largest kept batch
+ * Out of scope: entropy or other scores; masking bases inside a kept read (the stream has no N); more than one kept stretch per read;
+ * a window other than 64 bases every 32; pair-aware decisions (mates are judged independently, as in clip; the command line routes
+ * the survivors); any change to clip, overlap or pass 1. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -763,6 +827,9 @@ typedef struct { const uint32_t *words; const uint64_t *offsets; const uint8_t *
                  uint32_t n, reserved; } sdt_adapter_set;
 typedef struct { uint32_t overlap, mismatches, insert, start, len, verdict; } sdt_read_overlap;   /* 24 bytes */
 typedef struct { uint32_t min_overlap, max_err_pct, min_len, flags; } sdt_overlap_params;
+typedef struct { uint32_t windows, low, score, start, len, verdict; } sdt_read_complexity;   /* 24 bytes */
+typedef struct { uint32_t max_score_pct, max_low_pct, min_len, flags; } sdt_complexity_params;
+#define SDT_COMPLEXITY_TRIM 1u  /* sdt_complexity_params.flags: keep the longest clean stretch instead of judging the whole read */
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -835,6 +902,13 @@ int sdt_gpu_overlap_pairs_device(sdt_ctx *ctx, const void *d_packed_words, const
 int sdt_gpu_overlap_kept_pairs(sdt_ctx *ctx, const sdt_overlap_params *params, const uint64_t *pair_ranges,
                                uint64_t n_ranges, sdt_read_overlap *ov, uint64_t out_capacity, uint64_t *nreads,
                                uint64_t *n_kept);
+int sdt_gpu_complexity_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                             uint64_t nreads, const sdt_complexity_params *params, sdt_read_complexity *cx, uint8_t *keep,
+                             uint64_t *n_kept);
+int sdt_gpu_complexity_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                                    const sdt_complexity_params *params, void *d_cx, void *d_keep, uint64_t *n_kept);
+int sdt_gpu_complexity_kept_reads(sdt_ctx *ctx, const sdt_complexity_params *params, sdt_read_complexity *cx,
+                                  uint64_t out_capacity, uint64_t *nreads, uint64_t *n_kept);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

@@ -168,6 +168,12 @@ _ABI = [
                                                 _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_overlap_kept_pairs", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64,
                                               _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_complexity_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                            _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_complexity_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                   _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_complexity_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64),
+                                                 _c.POINTER(_c.c_uint64)]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -197,6 +203,11 @@ CLIP_MAX_ADAPTERS, CLIP_MAX_ADAPTER_LEN = 256, 128
 # kept bases are [start, start + len) of the read, where READ_TRIM_DTYPE has them
 READ_OVERLAP_DTYPE = np.dtype([(f, np.uint32) for f in ("overlap", "mismatches", "insert", "start", "len", "verdict")])
 OVERLAP_WHOLE, OVERLAP_CLIPPED, OVERLAP_DROPPED = 0, 2, 3
+# sdt_read_complexity (include/sdt_gpu.h): one record per read of a low-complexity filter; windows scored, LOW windows, the highest window
+# score in percent; the kept bases are [start, start + len) of the read, where READ_TRIM_DTYPE has them
+READ_COMPLEXITY_DTYPE = np.dtype([(f, np.uint32) for f in ("windows", "low", "score", "start", "len", "verdict")])
+COMPLEXITY_WHOLE, COMPLEXITY_CLIPPED, COMPLEXITY_DROPPED = 0, 2, 3
+SDT_COMPLEXITY_TRIM = 1
 
 
 class NormParams(_c.Structure):
@@ -226,6 +237,14 @@ class OverlapParams(_c.Structure):
 
     def __init__(self, min_overlap=30, max_err_pct=10, min_len=0, flags=0):
         super().__init__(min_overlap, max_err_pct, min_len, flags)
+
+
+class ComplexityParams(_c.Structure):
+    """sdt_complexity_params; the defaults of `sdt-kmers complexity`"""
+    _fields_ = [(f, _c.c_uint32) for f in ("max_score_pct", "max_low_pct", "min_len", "flags")]
+
+    def __init__(self, max_score_pct=10, max_low_pct=50, min_len=0, flags=0):
+        super().__init__(max_score_pct, max_low_pct, min_len, flags)
 
 
 class AdapterSet(_c.Structure):
@@ -986,6 +1005,45 @@ class PregraphGPU:
         n, kept = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self.lib.sdt_gpu_overlap_kept_pairs(self._ctx, ctypes.addressof(prm), _ptr(ranges) if ranges.size else None, ranges.size // 2,
                                                         _ptr(out), total_reads, ctypes.byref(n), ctypes.byref(kept)))
+        return out, n.value, kept.value
+
+    # -- low-complexity reads flagged, dropped or trimmed; needs no counted table (the rule: include/sdt_gpu.h)
+    @staticmethod
+    def _complexity_params(params):
+        """params: ComplexityParams or its fields as a dict"""
+        return params if isinstance(params, ComplexityParams) else ComplexityParams(**(params or {}))
+
+    def complexity_reads(self, words, offsets, params=None):
+        """-> (READ_COMPLEXITY_DTYPE[nreads]: windows, low, score, start, len, verdict; keep uint8[nreads]; reads with len > 0)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        cx = np.zeros(n, dtype=READ_COMPLEXITY_DTYPE)
+        keep = np.zeros(n, dtype=np.uint8)
+        prm = self._complexity_params(params)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_complexity_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, ctypes.addressof(prm), _ptr(cx),
+                                                      _ptr(keep), ctypes.byref(kept)))
+        return cx, keep, kept.value
+
+    def complexity_reads_device(self, d_words, d_offsets, nreads: int, d_cx, d_keep=None, params=None) -> int:
+        """device buffers; d_cx holds nreads records of 24 bytes (what compact_trimmed_device takes), d_keep (optional) nreads bytes
+        -> reads with len > 0 (waits for the kernel)"""
+        prm = self._complexity_params(params)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_complexity_reads_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, ctypes.addressof(prm), _ptr(d_cx),
+                                                             _ptr(d_keep), ctypes.byref(kept)))
+        return kept.value
+
+    def complexity_kept_reads(self, total_reads: int, params=None, out: np.ndarray = None):
+        """the reads kept in HBM -> (READ_COMPLEXITY_DTYPE[total_reads] by read ordinal, reads decided, reads with len > 0)"""
+        if out is None:
+            out = np.zeros(total_reads, dtype=READ_COMPLEXITY_DTYPE)
+        assert out.dtype == READ_COMPLEXITY_DTYPE and out.flags.c_contiguous and len(out) >= total_reads
+        prm = self._complexity_params(params)
+        n, kept = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_complexity_kept_reads(self._ctx, ctypes.addressof(prm), _ptr(out), total_reads, ctypes.byref(n),
+                                                           ctypes.byref(kept)))
         return out, n.value, kept.value
 
     def set_read_ordinal(self, base: int, stride: int = 1):

@@ -55,6 +55,14 @@
  *       prefix.readOverlap: one line per read in stream order:  overlap mismatches insert start len verdict
  *       prefix.overlap.pairs.fa / prefix.overlap.single.fa: the kept bases of the surviving reads, as clip writes them
  *       prefix.insertHist: per insert that occurs, ascending:  insert pairs,  then  # pairs P overlapping V clipped C median M
+ *   sdt-kmers complexity -s lib.cfg -K k [-p threads] [--max-score P, default 10] [--max-low Q, default 50] [--trim-low]
+ *                        [--min-len L, default 0] -o prefix
+ *       low-complexity reads (homopolymers, short tandem repeats, runs of N, which the stream shows as poly-G) dropped, or with
+ *       --trim-low cut back to their longest clean stretch (sdt_gpu_complexity_kept_reads; the rule: include/sdt_gpu.h).  Mates are
+ *       judged independently; pairs and routing as for clip (cxsplit.c)
+ *       prefix.readComplexity: one line per read in stream order:  windows low score start len verdict
+ *       prefix.cx.pairs.fa / prefix.cx.single.fa: the kept bases of the surviving reads, as clip writes them
+ *       prefix.scoreHist: per score that occurs, ascending:  score reads,  then  # reads R low V dropped D clipped C
  *
  * The query file is read and checked before the device is touched. */
 #include <errno.h>
@@ -72,6 +80,7 @@
 #include "dupsplit.h"
 #include "clipsplit.h"
 #include "overlapsplit.h"
+#include "cxsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -138,6 +147,21 @@ static void usage(void)
 	        "              prefix.overlap.single.fa (every other surviving read), prefix.insertHist (per insert that occurs, ascending:\n"
 	        "              insert pairs; then: # pairs P overlapping V clipped C median M, the lower median of the inserts)\n"
 	        "           Pairs are the reads of q1=/q2= and f1=/f2= files; the reads of a p= file are single reads, as for normalize.\n"
+	        "       sdt-kmers complexity -s lib.cfg -K k [-p threads] [--max-score P, default 10] [--max-low Q, default 50] [--trim-low]\n"
+	        "                            [--min-len L, default 0] -o prefix\n"
+	        "           every read is scored in windows of 64 bases that start every 32: the score is the percentage of the pairs of the\n"
+	        "           window's triplets that are equal (a homopolymer 100, (AC)n 49, random sequence 1 to 2); a window of score P or more\n"
+	        "           is low, and so is every base of it.  A read of which more than Q percent of the bases are low is dropped.  Q = 50\n"
+	        "           is a choice, not a measurement: a 150-base read with one internal run of 30 bases has 96 low bases and is dropped.\n"
+	        "           --trim-low (needs --max-low 0 or none): the longest stretch without a low base is kept instead, the first among\n"
+	        "           equals; a low window loses all 64 of its bases.  A read of which fewer than max(L, 1) bases are left is dropped.\n"
+	        "           Runs of N are poly-G in the 2-bit stream and are caught as such.  Needs no counted k-mers: run it after clip.\n"
+	        "           -> prefix.readComplexity (per read in stream order: windows low score start len verdict; low = the windows that are\n"
+	        "              low, score = the highest window score; verdict 0 whole, 2 clipped, 3 dropped), prefix.cx.pairs.fa (read 1 then\n"
+	        "              read 2 of the pairs of which both mates survive), prefix.cx.single.fa (every other surviving read),\n"
+	        "              prefix.scoreHist (per score that occurs, ascending: score reads; then: # reads R low V dropped D clipped C,\n"
+	        "              V = the reads that have a low window)\n"
+	        "           Pairs are the reads of q1=/q2= and f1=/f2= files, mates are judged independently, as for clip.\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -727,6 +751,70 @@ static int overlap_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_o
 	return 0;
 }
 
+/* `complexity`: the records from the device, the kept batches back from HBM, the kept bases of every read into the pairs file (both
+ * mates survive) or the singles file, routed as clip routes them; the histogram of the scores (cxsplit.c) */
+static int complexity_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_complexity_params *prm, const sdt_pair_ranges *pairs, const char *prefix)
+{
+	const uint64_t m = reads ? reads : 1;
+	sdt_read_complexity *cx = (sdt_read_complexity *)calloc(m, sizeof(sdt_read_complexity));
+	if (!cx) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	uint64_t got = 0, n_kept = 0;
+	if (sdt_gpu_complexity_kept_reads(gpu, prm, cx, reads, &got, &n_kept) != SDT_OK) {
+		fprintf(stderr, "sdt_gpu_complexity_kept_reads: %s\n", sdt_gpu_last_error());
+		return 1;
+	}
+	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu decided\n", reads, (unsigned long long)got); return 1; }
+	kept_reads k;
+	if (kept_fetch(gpu, reads, &k) != 0) return 1;
+	char path[4][4200];
+	snprintf(path[0], sizeof path[0], "%s.readComplexity", prefix);
+	snprintf(path[1], sizeof path[1], "%s.cx.pairs.fa", prefix);
+	snprintf(path[2], sizeof path[2], "%s.cx.single.fa", prefix);
+	snprintf(path[3], sizeof path[3], "%s.scoreHist", prefix);
+	outbuf ocx, opair, osingle;
+	if (ob_open(&ocx, path[0]) != 0) return 1;
+	if (ob_open(&opair, path[1]) != 0) { ob_close(&ocx); return 1; }
+	if (ob_open(&osingle, path[2]) != 0) { ob_close(&ocx); ob_close(&opair); return 1; }
+	sdt_score_hist hist;
+	memset(&hist, 0, sizeof hist);
+	unsigned long long kept = 0, bases_in = 0, bases_out = 0;
+	size_t cursor = 0;
+	int bad = 0;
+	for (uint64_t ord = 0; ord < reads; ord++) {
+		if (!ocx.ok || !opair.ok || !osingle.ok) break;                                /* a write failed: ob_close says which */
+		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
+		const sdt_read_complexity *t = cx + ord;
+		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
+		if (sdt_score_hist_note(&hist, t, len) != 0) {
+			fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->windows, t->low,
+			        t->score, t->start, t->len, t->verdict, (unsigned long long)len);
+			bad = 1;
+			break;
+		}
+		ob_room(&ocx, SDT_CX_LINE_MAX);
+		ocx.p = sdt_put_cx_line(ocx.p, t);
+		bases_in += len;
+		/* (start and len sit where sdt_read_trim has them: cxsplit.h) */
+		const int to = sdt_trim_route(pairs, &cursor, (const sdt_read_trim *)cx, reads, ord);
+		if (to == SDT_TRIM_TO_NONE) continue;
+		kept++;
+		bases_out += t->len;
+		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
+		ob_room(o, (size_t)t->len + 24);
+		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start + t->start, t->len);
+	}
+	const int all_written = ocx.ok && opair.ok && osingle.ok;
+	if ((ob_close(&ocx) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
+	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
+	FILE *fh = fopen(path[3], "w");
+	if (!fh || (sdt_score_hist_write(fh, &hist) != 0) | (fclose(fh) != 0)) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path[3]); return 1; }
+	printf("%llu reads: %llu with a low window, %llu clipped, %llu dropped; %llu bases in, %llu bases out\n", reads, (unsigned long long)hist.low,
+	       (unsigned long long)hist.clipped, (unsigned long long)hist.dropped, bases_in, bases_out);
+	kept_free(&k);
+	free(cx);
+	return 0;
+}
+
 /* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
 static int tail_mask(const char *opt, const char *text)
 {
@@ -806,11 +894,13 @@ int main(int argc, char **argv)
 {
 	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0 && strcmp(argv[1], "correct") != 0 &&
 	                 strcmp(argv[1], "normalize") != 0 && strcmp(argv[1], "trim") != 0 && strcmp(argv[1], "dedup") != 0 && strcmp(argv[1], "clip") != 0 &&
-	                 strcmp(argv[1], "overlap") != 0)) { usage(); return 255; }
+	                 strcmp(argv[1], "overlap") != 0 && strcmp(argv[1], "complexity") != 0)) { usage(); return 255; }
 	const int do_query = strcmp(argv[1], "query") == 0, do_correct = strcmp(argv[1], "correct") == 0, do_norm = strcmp(argv[1], "normalize") == 0;
 	const int do_trim = strcmp(argv[1], "trim") == 0, do_dedup = strcmp(argv[1], "dedup") == 0, do_clip = strcmp(argv[1], "clip") == 0;
-	const int do_overlap = strcmp(argv[1], "overlap") == 0;
+	const int do_overlap = strcmp(argv[1], "overlap") == 0, do_cx = strcmp(argv[1], "complexity") == 0;
 	sdt_overlap_params oprm = {30, 10, 0, 0};
+	sdt_complexity_params xprm = {10, 50, 0, 0};
+	int max_low_given = 0;
 	sdt_clip_params cprm = {5, 10, 0, 10, 20, 0, 0, 0};
 	char afile[2][4096] = {"", ""};                                          /* -a: 3' adapters, -g: 5' adapters */
 	sdt_dedup_params dprm = {0, 0};
@@ -827,6 +917,8 @@ int main(int argc, char **argv)
 	                                   {"tail5", required_argument, 0, 1010}, {"min-overlap", required_argument, 0, 1011},
 	                                   {"error-pct", required_argument, 0, 1012}, {"min-tail", required_argument, 0, 1013},
 	                                   {"tail-error-pct", required_argument, 0, 1014}, {"max-err", required_argument, 0, 1015},
+	                                   {"max-score", required_argument, 0, 1016}, {"max-low", required_argument, 0, 1017},
+	                                   {"trim-low", no_argument, 0, 1018},
 	                                   {0, 0, 0, 0}};
 	argv++; argc--;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:", longopts, NULL)) != -1) {
@@ -853,15 +945,15 @@ int main(int argc, char **argv)
 		case 1005: case 1006: case 1007: {
 			const char *opt = c == 1005 ? "--min-cov" : (c == 1006 ? "--min-len" : "--correct");
 			unsigned long long v;
-			if (!do_trim && !((do_clip || do_overlap) && c == 1006)) {
-				fprintf(stderr, "sdt-kmers: %s belongs to trim%s\n", opt, c == 1006 ? ", clip and overlap" : "");
+			if (!do_trim && !((do_clip || do_overlap || do_cx) && c == 1006)) {
+				fprintf(stderr, "sdt-kmers: %s belongs to trim%s\n", opt, c == 1006 ? ", clip, overlap and complexity" : "");
 				usage();
 				return 255;
 			}
 			if (c == 1007) { tprm.flags |= SDT_TRIM_CORRECTED; break; }
 			if (parse_number(opt, optarg, UINT32_MAX, &v) != 0) return 255;
 			if (c == 1005) tprm.min_cov = (uint32_t)v;
-			else tprm.min_len = cprm.min_len = oprm.min_len = (uint32_t)v;
+			else tprm.min_len = cprm.min_len = oprm.min_len = xprm.min_len = (uint32_t)v;
 			break;
 		}
 		case 'a': case 'g': case 1009: case 1010: case 1011: case 1012: case 1013: case 1014: {
@@ -891,6 +983,17 @@ int main(int argc, char **argv)
 			oprm.max_err_pct = (uint32_t)v;
 			break;
 		}
+		case 1016: case 1017: case 1018: {
+			const char *opt = c == 1016 ? "--max-score" : (c == 1017 ? "--max-low" : "--trim-low");
+			unsigned long long v;
+			if (!do_cx) { fprintf(stderr, "sdt-kmers: %s belongs to complexity\n", opt); usage(); return 255; }
+			if (c == 1018) { xprm.flags |= SDT_COMPLEXITY_TRIM; break; }
+			if (parse_number(opt, optarg, 100, &v) != 0) return 255;
+			if (c == 1016 && v == 0) { fprintf(stderr, "sdt-kmers: --max-score must be at least 1: at 0 every window would be low\n"); return 255; }
+			if (c == 1016) xprm.max_score_pct = (uint32_t)v;
+			else { xprm.max_low_pct = (uint32_t)v; max_low_given = 1; }
+			break;
+		}
 		case 1008:
 			if (!do_dedup) { fprintf(stderr, "sdt-kmers: --mate-swap belongs to dedup\n"); usage(); return 255; }
 			dprm.flags |= SDT_DEDUP_MATE_SWAP;
@@ -900,6 +1003,14 @@ int main(int argc, char **argv)
 	}
 	if (!cfgfile[0] || (do_query ? !qfile[0] : !outname[0])) { usage(); return 255; }
 	if (do_norm && prm.target == 0) { fprintf(stderr, "sdt-kmers: --target must be at least 1\n"); return 255; }
+	if (xprm.flags & SDT_COMPLEXITY_TRIM) {
+		if (max_low_given && xprm.max_low_pct != 0) {
+			fprintf(stderr, "sdt-kmers: --max-low %u with --trim-low: the longest clean stretch is kept, whatever fraction is low; give --max-low 0 or none\n",
+			        xprm.max_low_pct);
+			return 255;
+		}
+		xprm.max_low_pct = 0;
+	}
 	if (max_k == 0) max_k = K <= 31 ? 31 : SDT_MAX_K;
 	if (d > 127) d = (signed char)d;                                         /* deLowKmer is a char */
 	/* pregraph.c:38-59 */
@@ -938,7 +1049,7 @@ int main(int argc, char **argv)
 	}
 	sdt_pair_ranges pairs;
 	memset(&pairs, 0, sizeof pairs);
-	push_state st = {gpu, 0, do_norm || do_trim || do_dedup || do_clip || do_overlap ? &pairs : NULL};
+	push_state st = {gpu, 0, do_norm || do_trim || do_dedup || do_clip || do_overlap || do_cx ? &pairs : NULL};
 	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
 	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : threads;
 	sdt_pool_enable(sdt_gpu_host_alloc, sdt_gpu_host_free, parse_threads + PUSH_DEPTH + 8);
@@ -968,6 +1079,9 @@ int main(int argc, char **argv)
 		sdt_adapters_free(&ads);
 	} else if (do_overlap) {
 		if (overlap_and_write(gpu, st.reads, &oprm, &pairs, outname) != 0) return 1;
+		sdt_pair_ranges_free(&pairs);
+	} else if (do_cx) {
+		if (complexity_and_write(gpu, st.reads, &xprm, &pairs, outname) != 0) return 1;
 		sdt_pair_ranges_free(&pairs);
 	} else if (do_correct) {
 		if (correct_and_write(gpu, st.reads, (uint32_t)min_count, outname) != 0) return 1;

@@ -2,8 +2,8 @@
 // sdt_select.hip, sdt_trim.hip) decide on the host before anything reaches the device, as PURE functions: the launch geometry of a
 // strip kernel, the check of a host stream's offsets, and the cut of a host batch into the pieces that are staged one at a time.
 // sdt_readstage.hpp calls them for every stage; tools/read_plan_check.cpp (tests/test_read_plan.py) calls them on the CPU under
-// sanitizers.  The three stages that need no table have theirs here too: the duplicate filter (sdt_dedup.hip), the adapter and tail
-// clipping (sdt_clip.hip) and the mate overlap (sdt_overlap.hip).  No HIP in here.
+// sanitizers.  The four stages that need no table have theirs here too: the duplicate filter (sdt_dedup.hip), the adapter and tail
+// clipping (sdt_clip.hip), the mate overlap (sdt_overlap.hip) and the low-complexity filter (sdt_complexity.hip).  No HIP in here.
 #pragma once
 #include <stdint.h>
 
@@ -260,6 +260,40 @@ inline OverlapFault check_overlap_params(const OverlapParams &p, uint64_t dense_
 constexpr uint64_t overlap_shifts(uint64_t La, uint64_t Lb, uint32_t min_overlap)
 {
 	return La < min_overlap || Lb < min_overlap ? 0 : La + Lb - 2 * (uint64_t)min_overlap + 1;
+}
+
+// ---- low-complexity reads (sdt_complexity.hip): what is refused before any launch, and the windows a read is scored in ----
+// (tools/complexity_plan_check.cpp runs the check and holds the windows to a walk over every base)
+struct ComplexityParams {                                // == sdt_complexity_params of include/sdt_gpu.h
+	uint32_t max_score_pct, max_low_pct, min_len, flags;
+};
+constexpr uint32_t COMPLEXITY_TRIM = 1u;                 // SDT_COMPLEXITY_TRIM
+constexpr uint64_t COMPLEXITY_WINDOW = 64, COMPLEXITY_STEP = 32;
+
+enum ComplexityFault { COMPLEXITY_OK = 0, COMPLEXITY_FLAGS, COMPLEXITY_MAX_SCORE_PCT, COMPLEXITY_MAX_LOW_PCT, COMPLEXITY_TRIM_MAX_LOW_PCT };
+
+// the first field that is refused, in the order of the rules in include/sdt_gpu.h
+inline ComplexityFault check_complexity_params(const ComplexityParams &p)
+{
+	if (p.flags & ~COMPLEXITY_TRIM) return COMPLEXITY_FLAGS;
+	if (p.max_score_pct == 0 || p.max_score_pct > 100) return COMPLEXITY_MAX_SCORE_PCT;
+	if (p.max_low_pct > 100) return COMPLEXITY_MAX_LOW_PCT;
+	if ((p.flags & COMPLEXITY_TRIM) && p.max_low_pct != 0) return COMPLEXITY_TRIM_MAX_LOW_PCT;
+	return COMPLEXITY_OK;
+}
+
+// A read of L bases is scored in complexity_windows(L) windows of 64 bases that start every 32 bases; window j is
+// [complexity_window_begin(j), complexity_window_end(j, L)).  Every base is in a window, the last window ends at L and has more than 32
+// bases unless it is the only one.  Bases [32 k, 32 k + 32) are covered by the windows k - 1 and k that exist, and by no other.
+// (constexpr: the kernel calls them too)
+constexpr uint64_t complexity_windows(uint64_t L)
+{
+	return L == 0 ? 0 : (L <= 2 * COMPLEXITY_STEP ? 1 : (L + COMPLEXITY_STEP - 1) / COMPLEXITY_STEP - 1);
+}
+constexpr uint64_t complexity_window_begin(uint64_t j) { return j * COMPLEXITY_STEP; }
+constexpr uint64_t complexity_window_end(uint64_t j, uint64_t L)
+{
+	return j * COMPLEXITY_STEP + COMPLEXITY_WINDOW < L ? j * COMPLEXITY_STEP + COMPLEXITY_WINDOW : L;
 }
 
 } // namespace sdt
