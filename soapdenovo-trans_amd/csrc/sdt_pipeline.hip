@@ -85,7 +85,8 @@ int sk_alloc(sdt_ctx *c, uint64_t want_kmers, uint64_t per_read)
 		HIPCHK(hipStreamSynchronize(c->stream));
 		sk_free(c);
 	}
-	const int rw = sk_rec_words(c->nw), rw2 = sk_rec2_stride(c->nw);      // words per record; per slot of a level-2 chunk
+	const bool compact = sk_compact(c);
+	const int rw = sk_rec_words(c->nw), rw2 = sk_rec2_stride(c->nw, compact);      // words per record; per slot of a level-2 chunk
 	const int w = c->K - sk_minimizer_len(c->K) + 1;
 	// records: a run ends where the minimizer's bucket changes (every (w + 1) / 2 k-mers for a random order of the m-mers) or
 	// where the record is full (every `max run` k-mers at the latest): 1 / (2 / (w + 1) + 1 / max run) k-mers per record is what
@@ -94,7 +95,14 @@ int sk_alloc(sdt_ctx *c, uint64_t want_kmers, uint64_t per_read)
 	// `pool_direct` in the pipeline statistics: nothing is lost, but a fifth of the k-mers of a K = 95 job went that way and
 	// tripled its scatter time when the pools were sized at (w + 1) / 2 * 3 / 4).  4-word keys and reads of more than 256 k-mers go
 	// through the strip kernel, which also cuts at multiples of the record capacity: a fifth more room.  A read is at least one record.
+	// The compact level-2 record's shorter runs (28 instead of 32 k-mers at K = 31) enter as the RATIO of the two modelled rates (+ 3.6 % of
+	// records at K = 31 by the model; the measured figure is in profiles/l2_compact), applied to the record count below: through the whole
+	// number `div` the same 3.6 % became 8 -> 7, a seventh more chunks, which pushed the 24 G k-mers of the headline workload past the 2^28
+	// chunk ids of a list entry and cut every step into two batches.  (Reads the strip kernel takes: its power-of-two cap.)
+	const bool strips = c->nw == 4 || per_read > (uint64_t)SK_SEQ_MAX_KMERS;
+	const int cap_c = strips ? sk_pow2_floor(sk_max_run(c->K, c->nw, compact)) : sk_max_run(c->K, c->nw, compact);
 	const double rate = 2.0 / (double)(w + 1) + 1.0 / (double)sk_max_run(c->K, c->nw);
+	const double more = compact ? (2.0 / (double)(w + 1) + 1.0 / (double)cap_c) / rate : 1.0;
 	double run = 1.0 / rate * ((c->nw == 4 || per_read > (uint64_t)SK_SEQ_MAX_KMERS) ? 0.8 : 1.0);
 	if (run > (double)per_read) run = (double)per_read;
 	uint64_t div = (uint64_t)run;
@@ -107,7 +115,7 @@ int sk_alloc(sdt_ctx *c, uint64_t want_kmers, uint64_t per_read)
 	k.cap_is_max = cap >= SK_BATCH_MAX_KMERS;
 	const uint32_t wgs = (uint32_t)c->cu_count * 6;
 	for (;; cap /= 2) {
-		const uint64_t recs = cap / div;
+		const uint64_t recs = (uint64_t)((double)(cap / div) * more);
 		// (SDT_SK_POOL_CHUNKS1: test hook -- a level-1 pool of that many chunks, so that small inputs overflow it: tests/test_gpu_parity.py,
 		// tests/test_sharded.py)
 		const uint64_t chunks1 = sdt_knob_int(sdt_test_env("SDT_SK_POOL_CHUNKS1"), 0) > 0 ? (uint64_t)sdt_knob_int(sdt_test_env("SDT_SK_POOL_CHUNKS1"), 0) : recs / SK_CAP1 + (uint64_t)wgs * SK_NB1 + 1024;
@@ -165,7 +173,7 @@ int sk_alloc(sdt_ctx *c, uint64_t want_kmers, uint64_t per_read)
 	return sk_reset_pool1(c);
 }
 
-template <int NW, bool TRACK> static int sk_launch_count_t(sdt_ctx *c, uint32_t i0, uint32_t i1, uint32_t launch)
+template <int NW, bool TRACK, bool COMPACT> static int sk_launch_count_t(sdt_ctx *c, uint32_t i0, uint32_t i1, uint32_t launch)
 {
 	sdt_ctx::SkState &k = c->sk;
 	const size_t smem = sk_count_smem<NW, TRACK>();
@@ -173,8 +181,8 @@ template <int NW, bool TRACK> static int sk_launch_count_t(sdt_ctx *c, uint32_t 
 	const unsigned per_cu = (unsigned)((160 * 1024) / (smem + 256));
 	unsigned grid = (unsigned)c->cu_count * (per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu));
 	if (grid > i1 - i0) grid = i1 - i0;
-	HIPCHK(hipFuncSetAttribute((const void *)k_sk_count<NW, TRACK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-	hipLaunchKernelGGL((k_sk_count<NW, TRACK>), dim3(grid), dim3(SkCntGeo<NW, TRACK>::TPB), smem, c->stream, k.p2, k.list2, (const uint4 *)k.citems, i0, i1,
+	HIPCHK(hipFuncSetAttribute((const void *)k_sk_count<NW, TRACK, COMPACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+	hipLaunchKernelGGL((k_sk_count<NW, TRACK, COMPACT>), dim3(grid), dim3(SkCntGeo<NW, TRACK>::TPB), smem, c->stream, k.p2, k.list2, (const uint4 *)k.citems, i0, i1,
 	                   k.next_item + launch, c->K, flat_of<NW>(c), c->d_stats);
 	HIPCHK(hipGetLastError());
 	return SDT_OK;
@@ -182,7 +190,13 @@ template <int NW, bool TRACK> static int sk_launch_count_t(sdt_ctx *c, uint32_t 
 
 template <int NW> static int sk_launch_count(sdt_ctx *c, uint32_t i0, uint32_t i1, uint32_t launch)
 {
-	return c->d_first ? sk_launch_count_t<NW, true>(c, i0, i1, launch) : sk_launch_count_t<NW, false>(c, i0, i1, launch);
+	if (c->d_first)
+		return sk_launch_count_t<NW, true, false>(c, i0, i1, launch);
+	if constexpr (NW == 1)
+		if (sk_compact(c))
+			return sk_launch_count_t<1, false, true>(c, i0, i1, launch);
+	// (also a context made for ordinals whose ordinals have been dropped: its records stay the 24-byte ones)
+	return sk_launch_count_t<NW, false, false>(c, i0, i1, launch);
 }
 
 
@@ -214,12 +228,18 @@ int sk_split(sdt_ctx *c, const SkPool &src, const uint32_t *list, uint32_t nitem
 	if (nitems) {
 		SK_CHK(hipMemcpyAsync(k.items, k.h_items, (size_t)nitems * sizeof(SkItem), hipMemcpyHostToDevice, c->stream));
 		// staged (round 5): records wait in LDS for a group of 4 (2), groups are stored whole; one workgroup of 1024 lanes per CU by its LDS alone
-		const size_t sm = c->nw == 1 ? SkL2Stage<1>::SMEM : (c->nw == 2 ? SkL2Stage<2>::SMEM : SkL2Stage<4>::SMEM);
-		const void *fn = c->nw == 1 ? (const void *)k_sk_scatter_records_staged<1> : (c->nw == 2 ? (const void *)k_sk_scatter_records_staged<2> : (const void *)k_sk_scatter_records_staged<4>);
-		SK_CHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-		if (c->nw == 1) hipLaunchKernelGGL(k_sk_scatter_records_staged<1>, dim3(nitems), dim3(SK_L2S_TPB), sm, c->stream, src, list, k.items, k.p2, k.cnt2, k.kmers2, c->d_stats);
-		else if (c->nw == 2) hipLaunchKernelGGL(k_sk_scatter_records_staged<2>, dim3(nitems), dim3(SK_L2S_TPB), sm, c->stream, src, list, k.items, k.p2, k.cnt2, k.kmers2, c->d_stats);
-		else hipLaunchKernelGGL(k_sk_scatter_records_staged<4>, dim3(nitems), dim3(SK_L2S_TPB), sm, c->stream, src, list, k.items, k.p2, k.cnt2, k.kmers2, c->d_stats);
+		// (1-word keys without ordinals: 16-byte compact records, a group is one aligned 64-byte block)
+#define SK_L2_LAUNCH(NW, COMPACT)                                                                                                   \
+		do {                                                                                                                        \
+			const size_t sm = SkL2Stage<NW, COMPACT>::SMEM;                                                                         \
+			SK_CHK(hipFuncSetAttribute((const void *)k_sk_scatter_records_staged<NW, COMPACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm)); \
+			hipLaunchKernelGGL((k_sk_scatter_records_staged<NW, COMPACT>), dim3(nitems), dim3(SK_L2S_TPB), sm, c->stream, src, list, k.items, k.p2, k.cnt2, k.kmers2, c->d_stats); \
+		} while (0)
+		if (c->nw == 1 && sk_compact(c)) SK_L2_LAUNCH(1, true);
+		else if (c->nw == 1) SK_L2_LAUNCH(1, false);
+		else if (c->nw == 2) SK_L2_LAUNCH(2, false);
+		else SK_L2_LAUNCH(4, false);
+#undef SK_L2_LAUNCH
 		SK_CHK(hipGetLastError());
 	}
 	if (after_l2)
@@ -390,7 +410,9 @@ int sk_scatter_launch(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_off
 	sdt_ctx::SkState &k = c->sk;
 	const uint64_t per_read = max_read_len - c->K + 1;
 	const SkGeo geo = sk_geo(c->K, max_read_len);
-	const int m = sk_minimizer_len(c->K), ncap = sk_max_run(c->K, c->nw);
+	// (the run cap of a compact level-2 record is no power of two at K = 29..31 -- 30 / 28: the one-lane-per-read kernel takes any cap; the
+	// strip kernel cuts at multiples of the cap, j & (ncap - 1), and gets the largest power of two that fits)
+	const int m = sk_minimizer_len(c->K), ncap = sk_max_run(c->K, c->nw, sk_compact(c));
 	const uint64_t ntiles = (nr + SK_TILE_READS - 1) / SK_TILE_READS;
 	const unsigned grid = (unsigned)(ntiles < k.wgs ? ntiles : k.wgs);
 	EventPair *ev = next_event(c);
@@ -402,7 +424,7 @@ int sk_scatter_launch(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_off
 #define SK_SCATTER(NW)                                                                                                             \
 	do {                                                                                                                       \
 		HIPCHK(hipFuncSetAttribute((const void *)k_sk_scatter_reads<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.smem)); \
-		hipLaunchKernelGGL(k_sk_scatter_reads<NW>, dim3(grid), dim3(TPB), geo.smem, c->stream, d_words, d_offs, nr, c->K, m, ncap, \
+		hipLaunchKernelGGL(k_sk_scatter_reads<NW>, dim3(grid), dim3(TPB), geo.smem, c->stream, d_words, d_offs, nr, c->K, m, sk_pow2_floor(ncap), \
 		                   geo.mtw, geo.tile_words, geo.hv_words, geo.hv2_words, geo.bits_words, k.p1, k.cursors, k.blk, k.cnt1, sk_tbl<NW>(c, allow_direct), c->d_stats, ob, c->ord_stride); \
 	} while (0)
 	// one lane per read where the window length has an instantiation and the run list can hold a read

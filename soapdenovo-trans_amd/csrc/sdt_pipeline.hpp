@@ -23,6 +23,11 @@ static const uint32_t SK_MAX_COUNT_LAUNCHES = 4096;          // k-mers per k_sk_
 			return fail(e4_ == hipErrorOutOfMemory ? SDT_ENOMEM : SDT_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e4_), __FILE__, __LINE__); \
 	} while (0)
 
+// Level-2 records in the 16-byte compact form (sdt_sk_record2.h)?  Decided by the key width and the context's flags alone -- both fixed at
+// init -- so that the run cap of level 1, the pools, the level-2 scatter and the count stage cannot disagree.  (Not by c->d_first: the
+// ordinals are dropped once the graph is laid out and come back with the next reset.)
+static inline bool sk_compact(const sdt_ctx *c) { return sdt::sk_compact2(c->nw, (c->flags & SDT_FLAG_TRACK_FIRST) != 0); }
+
 struct SkGeo { int mtw, tile_words, hv_words, hv2_words, bits_words; size_t smem; };
 SkGeo sk_geo(int K, uint64_t max_read_len);
 bool sk_applicable(const sdt_ctx *c, uint64_t max_read_len);

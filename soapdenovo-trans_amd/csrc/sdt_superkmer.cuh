@@ -20,7 +20,8 @@
 //                        its level-1 bucket (256 of them).  Space comes from a pool of fixed-size chunks; every
 //                        workgroup owns one open chunk per bucket and reserves slots with LDS atomics, so the
 //                        only global atomic is the pool bump once per 128 chunks.
-//   k_sk_scatter_records level 2: every level-1 bucket is split 1024 ways the same way (records only move).
+//   k_sk_scatter_records level 2: every level-1 bucket is split 1024 ways the same way (records only move; 1-word keys without
+//                        ordinals: packed to 16 bytes on the way, sdt_sk_record2.h -- a group of four is one aligned 64-byte block).
 //   k_sk_count           one workgroup per final bucket (2^18): records -> LDS -> k-mers -> an LDS hash table
 //                        whose entries have the layout of the node table's (key, val); LDS atomics do the
 //                        counting (wave64, 4096 slots); at the end every LDS entry is merged into the node table
@@ -33,6 +34,7 @@
 #include "sdt_kmer.cuh"
 #include "sdt_minimizer.cuh"
 #include "sdt_table.cuh"
+#include "sdt_sk_record2.h"      // sk_max_run, the compact level-2 record of 1-word keys (plain C++: also tested on the CPU)
 
 namespace sdt {
 
@@ -44,7 +46,6 @@ constexpr int SK_CAP1 = 32;                      // records per level-1 chunk
 constexpr int SK_CAP2 = SDT_SK_CAP2;             // records per level-2 chunk (16 or 32: the fill of a chunk rides in the top bits of its list entry)
 static_assert(SK_CAP2 == 16 || SK_CAP2 == 32, "a level-2 chunk holds 16 or 32 records");
 constexpr uint32_t SK_NOCHUNK = 0xFFFFFFFFu;
-constexpr int SK_MAX_RUN = 64;                   // k-mers per record (6-bit field holds n - 1)
 
 // record: REC_WORDS 64-bit words
 //   [0] read ordinal (34 bits) << 30 | position of the run's first k-mer in its read (12 bits) << 18 |
@@ -61,26 +62,23 @@ template <int NW> struct SkFmt {
 	// bytes.  SDT_SK_REC2_PAD=1 gives the records 32-byte slots (the fourth word written as zero: a group is one aligned 128-byte line)
 	// -- measured: the level-2 scatter got SLOWER, 64.7 / 66.7 -> 69.4 / 68.6 ms per step (a third more bytes; the kernel is not bound by
 	// the write rate but by its own phases: two barriers and a serial book-keeping section per tile of 512 records at 8 waves per CU).
-	// Kept as a build knob, off.
+	// With the round loop that waits once (profiles/l2_compact): split 43.9 -> 41.9 ms on the 200 M-read workload, and the 20 GB the
+	// padding adds to pool 2 cut the step into two batches (count + 3 ms): nothing gained.  Kept as a build knob, off.
 #ifndef SDT_SK_REC2_PAD
 #define SDT_SK_REC2_PAD 0
 #endif
 	static constexpr int REC2_STRIDE = (NW == 1 && SDT_SK_REC2_PAD) ? 4 : REC_WORDS;
+	// (1-word keys without ordinals do not use these slots at all: their level-2 records are the 16-byte compact form of
+	// sdt_sk_record2.h, a group of four is one aligned 64-byte block; the knob concerns the ordinal path only)
 };
 constexpr uint64_t SK_MAX_READ_ORDINAL = 1ULL << 34;             // reads of one run the header can number
 constexpr int SK_MAX_READ_LEN = (1 << SK_POSBITS) - 1;                            // positions the header can hold
 
 __host__ __device__ inline int sk_rec_words(int nw) { return nw == 1 ? 3 : (nw == 2 ? 5 : 7); }
-__host__ __device__ inline int sk_rec2_stride(int nw) { return nw == 1 ? SkFmt<1>::REC2_STRIDE : (nw == 2 ? SkFmt<2>::REC2_STRIDE : SkFmt<4>::REC2_STRIDE); }
-
-// longest run a record can hold: n + K - 1 bases + 2 context bases must fit the base words; a power of two
-__host__ __device__ inline int sk_max_run(int K, int nw)
+// words per slot of a level-2 chunk
+__host__ __device__ inline int sk_rec2_stride(int nw, bool compact)
 {
-	const int cap = 32 * (nw == 1 ? 2 : (nw == 2 ? 4 : 6)) - K - 1;
-	int n = SK_MAX_RUN;
-	while (n > cap)
-		n >>= 1;
-	return n;
+	return compact ? SK_REC2C_WORDS : (nw == 1 ? SkFmt<1>::REC2_STRIDE : (nw == 2 ? SkFmt<2>::REC2_STRIDE : SkFmt<4>::REC2_STRIDE));
 }
 
 // the m bases starting at base index p of a packed word stream (16 bases per uint32, first base in bits 31..30)

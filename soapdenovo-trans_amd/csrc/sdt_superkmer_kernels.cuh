@@ -462,22 +462,46 @@ __device__ unsigned long long g_l2_log_cap = 0;
                                   // C3: split 50.8 (1) -> 44.8 ms (2); before the runs of chunk ids came out of the workgroup's block (sk_alloc_chunks)
                                   // 2 and 4 were SLOWER (69 / 98 ms against 54.6): more records per round = more sub-buckets that need a run of chunks
 #endif
-template <int NW> struct SkL2Stage {
+// COMPACT (1-word keys without ordinals): the record is packed to 16 bytes (sdt_sk_record2.h) as soon as its ticket is drawn -- the
+// stage holds 16-byte records (64 KB instead of 96), a group of S = 4 is one 16-byte store per lane into ONE aligned 64-byte block
+// (scattered 96-byte pieces write at 1.43 TB/s, whole blocks at 3.2: tools/box_probe.hip `pieces`), a chunk is 256 bytes.  (S = 8
+// would need 128 KB of stage beside 30 KB of books: it does not fit.)
+template <int NW, bool COMPACT = false> struct SkL2Stage {
+	static_assert(!COMPACT || NW == 1, "the compact level-2 record is the 1-word keys'");
 	static constexpr int S = NW == 1 ? SDT_SK_L2S_S1 : 2;            // records per group
 	static constexpr int GPC = SK_CAP2 / S;                          // groups per chunk
 	static constexpr int RPL = NW == 1 ? SDT_SK_L2S_RPL : (NW == 2 ? (SDT_SK_L2S_RPL < 2 ? SDT_SK_L2S_RPL : 2) : 1);      // records per lane and round
-	static constexpr size_t SMEM = (size_t)SK_NB2 * S * SkFmt<NW>::REC_WORDS * 8;
+	static constexpr int RWS = COMPACT ? SK_REC2C_WORDS : SkFmt<NW>::REC_WORDS;             // words of a record in the stage
+	static constexpr int RW2 = COMPACT ? SK_REC2C_WORDS : SkFmt<NW>::REC2_STRIDE;           // words per slot of a level-2 chunk
+	static constexpr size_t SMEM = (size_t)SK_NB2 * S * RWS * 8;
 };
 
-template <int NW>
+// a staged record into its slot of a level-2 chunk
+template <int NW, bool COMPACT> __device__ inline void sk_store_staged(uint64_t *dst, const uint64_t (&rec)[SkL2Stage<NW, COMPACT>::RWS])
+{
+	if constexpr (COMPACT)
+		*reinterpret_cast<ulonglong2 *>(dst) = make_ulonglong2(rec[0], rec[1]);
+	else
+		sk_store_record2<NW>(dst, rec);
+}
+
+// The round loop waits for memory ONCE, at its top.  One workgroup of 16 waves runs per CU and nothing else is resident to hide a
+// wait, so every wait in the round is exposed; rounds 5-6 had four (a drain of the previous round's stores where the prefetched
+// registers were copied, and three dependent round trips: list entry -> chunk meta -> `fill` computed on the spot, twice per lane).
+// Now every value a round needs was asked for a round (records, raw meta word) or two rounds (chunk ids) before; the top of the round
+// waits for all of it -- and for the previous round's stores, which the compiler cannot count past their branches --, takes the values,
+// and issues ALL loads of the coming rounds back to back and unconditionally (a lane with nothing to load reads a harmless address:
+// behind a branch the compiler cannot count the loads in flight).  Tickets, books and stores then run without a wait for a load.
+template <int NW, bool COMPACT>
 __global__ __launch_bounds__(SK_L2S_TPB, SDT_SK_L2S_WGS) void k_sk_scatter_records_staged(SkPool src, const uint32_t *__restrict__ list1,
                                                                          const SkItem *__restrict__ items, SkPool dst,
                                                                          uint32_t *__restrict__ g_cnt, unsigned long long *__restrict__ g_kmers, Stats *stats)
 {
-	constexpr int RW = SkFmt<NW>::REC_WORDS, RW2 = SkFmt<NW>::REC2_STRIDE, S = SkL2Stage<NW>::S, GPC = SkL2Stage<NW>::GPC;
+	using L2 = SkL2Stage<NW, COMPACT>;
+	constexpr int RW = SkFmt<NW>::REC_WORDS, RWS = L2::RWS, RW2 = L2::RW2, S = L2::S, GPC = L2::GPC;
 	constexpr int CPT = SK_L2S_TPB / SK_CAP1;         // chunks per sweep
-	constexpr int D = SkL2Stage<NW>::RPL;            // sweeps (records per lane) per round
-	extern __shared__ unsigned long long s_stage[];  // SK_NB2 x S records
+	constexpr int D = L2::RPL;                       // sweeps (records per lane) per round
+	extern __shared__ __attribute__((aligned(16))) unsigned long long s_stage[];  // SK_NB2 x S records
 	__shared__ uint32_t s_cnt[SK_NB2];               // tickets of the running round (start: the records waiting in the stage)
 	__shared__ uint32_t s_open[SK_NB2];              // open chunk of the sub-bucket (SK_NOCHUNK: none)
 	__shared__ uint32_t s_pub_open[SK_NB2], s_pub_new[SK_NB2], s_pub_g[SK_NB2];     // what phase 2 of the round needs: the open chunk and the groups used in it
@@ -516,53 +540,75 @@ __global__ __launch_bounds__(SK_L2S_TPB, SDT_SK_L2S_WGS) void k_sk_scatter_recor
 	};
 	// records and chunk ids are loaded a round ahead / two rounds ahead (registers: this kernel runs one workgroup per CU)
 	const uint32_t slot = (uint32_t)tid % SK_CAP1, cfirst = it.c0 + (uint32_t)tid / SK_CAP1;
-	uint32_t id_a[D], id_b[D], fill_a[D];
-	uint64_t rec_a[D][RW];
+	// (a position past the item's end reads the item's first entry / chunk 0: a load that is always issued can be counted)
+	uint32_t id_b[D], meta_a[D];                     // chunk ids of the next round but one; RAW meta words of the next round's chunks
+	uint64_t rec_a[D][RW];                           // (`fill` is shifted out where it is used, a round later: nothing waits here)
+	{
+		uint32_t id_a[D];
 #pragma unroll
-	for (int d = 0; d < D; d++) {
-		const uint32_t ca = cfirst + (uint32_t)d * CPT, cb = ca + (uint32_t)D * CPT;
-		id_a[d] = ca < it.c1 ? list1[ca] : SK_NOCHUNK;
-		id_b[d] = cb < it.c1 ? list1[cb] : SK_NOCHUNK;
-	}
+		for (int d = 0; d < D; d++) {
+			const uint32_t ca = cfirst + (uint32_t)d * CPT, cb = ca + (uint32_t)D * CPT;
+			id_a[d] = list1[ca < it.c1 ? ca : it.c0];
+			id_b[d] = list1[cb < it.c1 ? cb : it.c0];
+		}
 #pragma unroll
-	for (int d = 0; d < D; d++) {
-		fill_a[d] = 0;
-#pragma unroll
-		for (int i = 0; i < RW; i++)
-			rec_a[d][i] = 0;
-		if (id_a[d] != SK_NOCHUNK) {
-			fill_a[d] = src.meta[id_a[d]] >> 24;
-			sk_load_record<RW>(src.recs + ((size_t)id_a[d] * SK_CAP1 + slot) * RW, rec_a[d]);
+		for (int d = 0; d < D; d++) {
+			const uint32_t ca = cfirst + (uint32_t)d * CPT;
+			const uint32_t id = ca < it.c1 ? id_a[d] : 0u;
+			meta_a[d] = src.meta[id];
+			sk_load_record<RW>(src.recs + ((size_t)id * SK_CAP1 + slot) * RW, rec_a[d]);
 		}
 	}
 	// (the rounds are uniform: every lane of the workgroup runs the same number of them, barriers included)
 	const uint32_t nsweep = (it.c1 - it.c0 + CPT - 1) / CPT;
 	for (uint32_t sw = 0; sw < nsweep; sw += (uint32_t)D) {
-		uint64_t rec[D][RW];
+		uint64_t rec[D][RWS];
 		uint32_t b2[D], t[D];
 		bool valid[D];
+		// ---- 0: THE wait of the round.  Every prefetched register is used here, so the one wait the compiler must place -- for all
+		// of them, and with them for every store of the round before -- stands in front of the loads below, not behind them.
+#pragma unroll
+		for (int d = 0; d < D; d++) {
+			asm volatile("" : "+v"(id_b[d]), "+v"(meta_a[d]));
+#pragma unroll
+			for (int i = 0; i < RW; i++)
+				asm volatile("" : "+v"(rec_a[d][i]));
+		}
+		uint64_t hdr[D];
+		uint32_t fill[D];
 #pragma unroll
 		for (int d = 0; d < D; d++) {
 			const uint32_t ci = cfirst + (sw + (uint32_t)d) * CPT;
+			hdr[d] = rec_a[d][0];
+			fill[d] = ci < it.c1 ? meta_a[d] >> 24 : 0u;
+			if constexpr (COMPACT) {
+				sk_pack2(rec_a[d][0], rec_a[d][1], rec_a[d][2], rec[d][0], rec[d][1]);
+			} else {
 #pragma unroll
-			for (int i = 0; i < RW; i++)
-				rec[d][i] = rec_a[d][i];
-			const uint32_t fill = ci < it.c1 ? fill_a[d] : 0u;
-			id_a[d] = id_b[d];
-			const uint32_t cn = ci + 2u * (uint32_t)D * CPT;
-			id_b[d] = cn < it.c1 ? list1[cn] : SK_NOCHUNK;
-			if (id_a[d] != SK_NOCHUNK) {
-				fill_a[d] = src.meta[id_a[d]] >> 24;
-				sk_load_record<RW>(src.recs + ((size_t)id_a[d] * SK_CAP1 + slot) * RW, rec_a[d]);
+				for (int i = 0; i < RW; i++)
+					rec[d][i] = rec_a[d][i];
 			}
-			valid[d] = slot < fill;
+		}
+		// every load of the coming rounds, back to back: the ids of the round after next, meta word and record of the next one
+#pragma unroll
+		for (int d = 0; d < D; d++) {
+			const uint32_t ci = cfirst + (sw + (uint32_t)d) * CPT;
+			const uint32_t c1n = ci + (uint32_t)D * CPT, c2n = ci + 2u * (uint32_t)D * CPT;
+			const uint32_t id = c1n < it.c1 ? id_b[d] : 0u;
+			id_b[d] = list1[c2n < it.c1 ? c2n : it.c0];
+			meta_a[d] = src.meta[id];
+			sk_load_record<RW>(src.recs + ((size_t)id * SK_CAP1 + slot) * RW, rec_a[d]);
+		}
+#pragma unroll
+		for (int d = 0; d < D; d++) {
+			valid[d] = slot < fill[d];
 			// ---- 1: tickets
 			b2[d] = 0;
 			t[d] = 0;
 			if (valid[d]) {
-				b2[d] = sk_hdr_l2(rec[d][0]);
+				b2[d] = sk_hdr_l2(hdr[d]);
 				t[d] = atomicAdd(&s_cnt[b2[d]], 1u);
-				atomicAdd(&s_kc[b2[d]], (uint32_t)sk_hdr_n(rec[d][0]));
+				atomicAdd(&s_kc[b2[d]], (uint32_t)sk_hdr_n(hdr[d]));
 			}
 		}
 		__syncthreads();
@@ -589,12 +635,12 @@ __global__ __launch_bounds__(SK_L2S_TPB, SDT_SK_L2S_WGS) void k_sk_scatter_recor
 			s_pub_g[i] = used | (G << 8);
 			if (G && f) {                                // the records that waited leave with the first group
 				for (uint32_t j = 0; j < f; j++) {
-					uint64_t old[RW];
+					uint64_t old[RWS];
 #pragma unroll
-					for (int w = 0; w < RW; w++)
-						old[w] = s_stage[((size_t)i * S + j) * RW + w];
+					for (int w = 0; w < RWS; w++)
+						old[w] = s_stage[((size_t)i * S + j) * RWS + w];
 					uint64_t *p = slot_of(open, used, first_new, j);
-					if (p) sk_store_record2<NW>(p, old);
+					if (p) sk_store_staged<NW, COMPACT>(p, old);
 					else failed++;
 				}
 			}
@@ -623,13 +669,13 @@ __global__ __launch_bounds__(SK_L2S_TPB, SDT_SK_L2S_WGS) void k_sk_scatter_recor
 			const uint32_t g = s_pub_g[b2[d]], G = g >> 8, used = g & 0xFFu;
 			if (t[d] / S < G) {
 				uint64_t *p = slot_of(s_pub_open[b2[d]], used, s_pub_new[b2[d]], t[d]);
-				if (p) sk_store_record2<NW>(p, rec[d]);
+				if (p) sk_store_staged<NW, COMPACT>(p, rec[d]);
 				else failed++;
 			} else {
 				const uint32_t at = t[d] - G * S;
 #pragma unroll
-				for (int i = 0; i < RW; i++)
-					s_stage[((size_t)b2[d] * S + at) * RW + i] = rec[d][i];
+				for (int i = 0; i < RWS; i++)
+					s_stage[((size_t)b2[d] * S + at) * RWS + i] = rec[d][i];
 			}
 		}
 	}
@@ -647,11 +693,11 @@ __global__ __launch_bounds__(SK_L2S_TPB, SDT_SK_L2S_WGS) void k_sk_scatter_recor
 			}
 			if (open != SK_NOCHUNK) {
 				for (uint32_t j = 0; j < f; j++) {
-					uint64_t rec[RW];
+					uint64_t rec[RWS];
 #pragma unroll
-					for (int w = 0; w < RW; w++)
-						rec[w] = s_stage[((size_t)i * S + j) * RW + w];
-					sk_store_record2<NW>(dst.recs + ((size_t)open * SK_CAP2 + used * S + j) * RW2, rec);
+					for (int w = 0; w < RWS; w++)
+						rec[w] = s_stage[((size_t)i * S + j) * RWS + w];
+					sk_store_staged<NW, COMPACT>(dst.recs + ((size_t)open * SK_CAP2 + used * S + j) * RW2, rec);
 				}
 			} else {
 				failed += f;
@@ -833,7 +879,9 @@ constexpr uint32_t SK_CNT_MAX_SINCE = 65535;     // k-mers counted into the LDS 
 // about ninety uniform values: the overflow lives in lanes of vector registers.  Raising the scalar budget by hand
 // (amdgpu_waves_per_eu(4, 8) + amdgpu_num_vgpr(32) + amdgpu_num_sgpr(96)) removed every spill and cost the second workgroup
 // per CU: 172 -> 251 ms per step on the 200 M-read workload.)
-template <int NW, bool TRACK>
+// COMPACT: the pool holds the 16-byte records of sdt_sk_record2.h (1-word keys without ordinals): phase A is one 16-byte load and an
+// unpack into the same header / base words the 24-byte record gives, everything behind phase A is the same code.
+template <int NW, bool TRACK, bool COMPACT>
 __global__ __launch_bounds__((SkCntGeo<NW, TRACK>::TPB), (SkCntGeo<NW, TRACK>::WAVES_PER_SIMD)) void k_sk_count(SkPool pool, const uint32_t *__restrict__ list2, const uint4 *__restrict__ items,
                                                          uint32_t item0, uint32_t item1, uint32_t *__restrict__ next_item, int K,
                                                          Table<NW> tbl, Stats *stats)
@@ -946,7 +994,7 @@ __global__ __launch_bounds__((SkCntGeo<NW, TRACK>::TPB), (SkCntGeo<NW, TRACK>::W
 		// A list entry carries the chunk's fill (k_sk_chunk_place): pool.meta is not read here.  (LDS-DMA -- global_load_lds_dword,
 		// no destination register at all -- was tried for both and ran 10..50x slower than no prefetch: profiles/r3.)
 		auto rec_ptr = [&](uint32_t e, uint32_t t) -> const uint64_t * {
-			return pool.recs + ((size_t)(e & ((1u << SK_LIST2_FILL_SHIFT) - 1u)) * SK_CAP2 + t % SK_CAP2) * SkFmt<NW>::REC2_STRIDE;
+			return pool.recs + ((size_t)(e & ((1u << SK_LIST2_FILL_SHIFT) - 1u)) * SK_CAP2 + t % SK_CAP2) * (COMPACT ? SK_REC2C_WORDS : SkFmt<NW>::REC2_STRIDE);
 		};
 		auto rec_ok = [&](uint32_t e, uint32_t t) -> bool { return e != SK_NOCHUNK && t % SK_CAP2 <= (e >> SK_LIST2_FILL_SHIFT); };
 		auto ent_row = [&](uint32_t t) -> uint32_t * { return s_ent + (t % 3u) * CPT; };
@@ -976,13 +1024,21 @@ __global__ __launch_bounds__((SkCntGeo<NW, TRACK>::TPB), (SkCntGeo<NW, TRACK>::W
 			// (every lane loads, from a harmless address when it has nothing to load: behind a branch the compiler cannot count
 			// the loads in flight and waits for all of them; and the prefetches are issued BEHIND the loads this phase waits
 			// for, because vector memory returns in order)
-			sk_load_record<RW>(ok ? rec_ptr(e, ot) : pool.recs, nx);
+			ulonglong2 cx = make_ulonglong2(0ULL, 0ULL);
+			if constexpr (COMPACT) {
+				static_assert(!COMPACT || (NW == 1 && !TRACK), "compact records carry no ordinals");
+				cx = *reinterpret_cast<const ulonglong2 *>(ok ? rec_ptr(e, ot) : pool.recs);
+			} else {
+				sk_load_record<RW>(ok ? rec_ptr(e, ot) : pool.recs, nx);
+			}
 			const bool ring_ok = ot < CPT && cb + 2 * CPT + (uint32_t)ot < c1;
 			ring_e = (list2 + cb)[ring_ok ? 2 * CPT + ot : 0];
 			if (!ring_ok)
 				ring_e = SK_NOCHUNK;
 			if (SDT_SK_PREFETCH)
 				pf = *(const uint32_t *)(rec_ok(e1, ot) ? rec_ptr(e1, ot) : pool.recs);
+			if constexpr (COMPACT)
+				sk_unpack2(cx.x, cx.y, nx[0], nx[1], nx[RW - 1]);
 			if (ot < TR) {
 				if (ok) {
 					h0 = nx[0];
