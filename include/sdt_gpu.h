@@ -807,7 +807,60 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  *     kept form         the 24 B records of the largest kept batch
  * Out of scope: entropy or other scores; masking bases inside a kept read (the stream has no N); more than one kept stretch per read;
  * a window other than 64 bases every 32; pair-aware decisions (mates are judged independently, as in clip; the command line routes
- * the survivors); any change to clip, overlap or pass 1. */
+ * the survivors); any change to clip, overlap or pass 1.
+ *
+ * Reads trimmed and filtered by their base qualities: the first stage of the chain and the only one that reads qualities.  The bases a
+ * sequencer was unsure of are where the error k-mers come from; correct_reads and trim_reads can deal with those only after a whole
+ * count.  It is also the only stage that can see an N: the 2-bit stream codes N as G, but sequencers give N a quality of 2, so a run
+ * of N is cut at the ends of a read and counted as low bases inside it.  Needs NO counted table and does NOT look at the bases.
+ * Qualities are only valid while the offsets are those of the input, so the stage goes first:
+ * quality -> compact_trimmed_device (on the 2-bit words, same offsets) -> overlap -> ...; NO later stage carries qualities along.
+ * Added without a change of SDT_ABI_VERSION: the two calls and the two structs are additions.
+ *     Integers only.  Every read is decided on its own.  Nothing is read but the read's own quality bytes.  The result does not
+ *     depend on the launch geometry or on where a read starts in memory.
+ *     INPUT.   quals: one byte per base, under the same offsets[nreads + 1] (in bases, here: in bytes) as the read's 2-bit stream.
+ *              Read r has L = offsets[r + 1] - offsets[r] bytes c[0, L).  The quality of base i is q_i = 0 if c_i < phred_offset,
+ *              else min(c_i - phred_offset, 93).
+ *     SEGMENT (Mott's rule, as `seqtk trimfq` and `phred` use it).  s_i = q_i - cut_q; P_0 = 0, P_j = s_0 + ... + s_(j-1).  The kept
+ *              segment is the [a, b), 0 <= a <= b <= L, with the greatest P_b - P_a; among equal sums the smallest a wins, among
+ *              those the greatest b.  So all s_i < 0 gives a = b = 0; cut_q = 0 keeps the whole read (trimming is off); a base
+ *              with q_i = cut_q at the edge of the segment is kept.  Equivalent form, the one a scan computes: for every b,
+ *              M_b = min over a <= b of P_a and a_b the smallest a that attains it; take the b that is greatest under the key
+ *              (P_b - M_b descending, a_b ascending, b descending).
+ *     MEASURES of the segment, n = b - a.  low = the bases of [a, b) with q_i < low_q.  E = the sum over [a, b) of e[q_i], in
+ *              millionths of an expected error: e[q] = 10^6 * 10^(-q / 10) rounded to the nearest integer (94 entries; e[0] =
+ *              1 000 000, e[1] = 794 328, e[3] = 501 187, e[20] = 10 000, e[30] = 1 000, e[60..63] = 1, e[64..93] = 0; no entry is
+ *              a tie), summed in 64 bits.  ee_ppm = floor(E / n), 0 for n = 0: expected errors per million bases, 10^6 at most.
+ *     VERDICT, with the numbers of sdt_read_trim; the first line that applies:
+ *         3  dropped   n < max(min_len, 1)                          record: start = len = 0
+ *         3  dropped   100 low > max_low_pct n                      record: start = len = 0
+ *         3  dropped   max_ee_ppm != 0 and ee_ppm > max_ee_ppm      record: start = len = 0
+ *         0  whole     n == L                                       record: start = 0, len = L
+ *         2  clipped   otherwise                                    record: start = a, len = n
+ *     RECORD.  sdt_read_quality: span = n, low, ee_ppm; start, len and verdict sit where sdt_read_trim has them.  A dropped read's
+ *              record still says what was found: from span, low, ee_ppm and the parameters anyone can tell which line dropped it.
+ *     PARAMETERS.  max_low_pct = 100 or low_q = 0: the low-base filter is off.  max_ee_ppm = 0: the expected-error filter is off.
+ *     The defaults of the command line are phred_offset 33, cut_q 20, low_q 15, max_low_pct 40, max_ee_ppm 0, min_len 0: the usual
+ *     figures of `fastp` and `cutadapt`.  They are a choice, not a measurement.
+ *   quality_reads:  out[i] for read i of a host batch of nbytes quality bytes; keep (may be NULL): keep[i] = len > 0; *n_kept = reads
+ *                   with len > 0.  The batch is staged in pieces as for profile_reads, each from a 4-byte-aligned byte of the stream.
+ *   quality_reads_device: buffers already on the device: d_quals 4-byte aligned and readable up to offsets[nreads] rounded up to 4
+ *                   (bytes outside the reads never change a result), d_out nreads records of 24 bytes, d_keep nreads bytes or NULL.
+ *                   The call waits for the kernel to know *n_kept.  d_out is what sdt_gpu_compact_trimmed_device takes: both
+ *                   compaction calls take an array of sdt_read_quality through a pointer cast.
+ * State: a context is needed for its stream only: any state, any kind of context, like dedup_reads.  nreads == 0: SDT_OK, nothing
+ * touched, whatever the rest says.  There is NO limit on the read length: a wavefront walks a read 256 bases at a time (span, start
+ * and len are 32-bit, as in sdt_read_trim).
+ * SDT_EINVAL, from a check on the host before any launch, with a message that names the field and its value: NULL params;
+ * phred_offset other than 0, 33 or 64; cut_q > 93; low_q > 93; max_low_pct > 100; flags != 0; reserved != 0.  The host form also:
+ * offsets that are not monotonic, nbytes < offsets[nreads].  The device form also: d_quals not 4-byte aligned.
+ * Device memory held during the call, beside the qualities, SDT_ENOMEM (nothing written) when it does not fit:
+ *     device form       8 B (the counter of the reads kept)
+ *     host form         the piece of the stream that is staged with its offsets, and 24 B + 1 B per read of it for records and keep
+ * Out of scope: sliding-window cuts; per-end thresholds; masking bases; qualities carried through later stages or written out (the
+ * outputs stay FASTA like every other stage's); a kept form (the reads kept in HBM carry no qualities, and sdt_gpu_keep_reads is
+ * not changed); pair-aware decisions (mates are judged independently; the command line routes the survivors); any change to another
+ * stage. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -830,6 +883,8 @@ typedef struct { uint32_t min_overlap, max_err_pct, min_len, flags; } sdt_overla
 typedef struct { uint32_t windows, low, score, start, len, verdict; } sdt_read_complexity;   /* 24 bytes */
 typedef struct { uint32_t max_score_pct, max_low_pct, min_len, flags; } sdt_complexity_params;
 #define SDT_COMPLEXITY_TRIM 1u  /* sdt_complexity_params.flags: keep the longest clean stretch instead of judging the whole read */
+typedef struct { uint32_t span, low, ee_ppm, start, len, verdict; } sdt_read_quality;   /* 24 bytes */
+typedef struct { uint32_t phred_offset, cut_q, low_q, max_low_pct, max_ee_ppm, min_len, flags, reserved; } sdt_quality_params;
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -909,6 +964,10 @@ int sdt_gpu_complexity_reads_device(sdt_ctx *ctx, const void *d_packed_words, co
                                     const sdt_complexity_params *params, void *d_cx, void *d_keep, uint64_t *n_kept);
 int sdt_gpu_complexity_kept_reads(sdt_ctx *ctx, const sdt_complexity_params *params, sdt_read_complexity *cx,
                                   uint64_t out_capacity, uint64_t *nreads, uint64_t *n_kept);
+int sdt_gpu_quality_reads(sdt_ctx *ctx, const uint8_t *quals, uint64_t nbytes, const uint64_t *offsets, uint64_t nreads,
+                          const sdt_quality_params *params, sdt_read_quality *out, uint8_t *keep, uint64_t *n_kept);
+int sdt_gpu_quality_reads_device(sdt_ctx *ctx, const void *d_quals, const void *d_offsets, uint64_t nreads,
+                                 const sdt_quality_params *params, void *d_out, void *d_keep, uint64_t *n_kept);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

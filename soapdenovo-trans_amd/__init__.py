@@ -174,6 +174,10 @@ _ABI = [
                                                    _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_complexity_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64),
                                                  _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_quality_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                         _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_quality_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                _c.POINTER(_c.c_uint64)]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -208,6 +212,10 @@ OVERLAP_WHOLE, OVERLAP_CLIPPED, OVERLAP_DROPPED = 0, 2, 3
 READ_COMPLEXITY_DTYPE = np.dtype([(f, np.uint32) for f in ("windows", "low", "score", "start", "len", "verdict")])
 COMPLEXITY_WHOLE, COMPLEXITY_CLIPPED, COMPLEXITY_DROPPED = 0, 2, 3
 SDT_COMPLEXITY_TRIM = 1
+# sdt_read_quality (include/sdt_gpu.h): one record per read of a quality trim; the bases of the best segment, those of them below
+# low_q, its expected errors per million bases; the kept bases are [start, start + len) of the read, where READ_TRIM_DTYPE has them
+READ_QUALITY_DTYPE = np.dtype([(f, np.uint32) for f in ("span", "low", "ee_ppm", "start", "len", "verdict")])
+QUALITY_WHOLE, QUALITY_CLIPPED, QUALITY_DROPPED = 0, 2, 3
 
 
 class NormParams(_c.Structure):
@@ -245,6 +253,14 @@ class ComplexityParams(_c.Structure):
 
     def __init__(self, max_score_pct=10, max_low_pct=50, min_len=0, flags=0):
         super().__init__(max_score_pct, max_low_pct, min_len, flags)
+
+
+class QualityParams(_c.Structure):
+    """sdt_quality_params; the defaults of `sdt-kmers qtrim`"""
+    _fields_ = [(f, _c.c_uint32) for f in ("phred_offset", "cut_q", "low_q", "max_low_pct", "max_ee_ppm", "min_len", "flags", "reserved")]
+
+    def __init__(self, phred_offset=33, cut_q=20, low_q=15, max_low_pct=40, max_ee_ppm=0, min_len=0, flags=0, reserved=0):
+        super().__init__(phred_offset, cut_q, low_q, max_low_pct, max_ee_ppm, min_len, flags, reserved)
 
 
 class AdapterSet(_c.Structure):
@@ -1045,6 +1061,35 @@ class PregraphGPU:
         self._check(self.lib.sdt_gpu_complexity_kept_reads(self._ctx, ctypes.addressof(prm), _ptr(out), total_reads, ctypes.byref(n),
                                                            ctypes.byref(kept)))
         return out, n.value, kept.value
+
+    # -- reads trimmed and filtered by their base qualities; needs no counted table and not the bases (the rule: include/sdt_gpu.h)
+    @staticmethod
+    def _quality_params(params):
+        """params: QualityParams or its fields as a dict"""
+        return params if isinstance(params, QualityParams) else QualityParams(**(params or {}))
+
+    def quality_reads(self, quals, offsets, params=None):
+        """quals: one byte per base under offsets -> (READ_QUALITY_DTYPE[nreads]: span, low, ee_ppm, start, len, verdict;
+        keep uint8[nreads]; reads with len > 0)"""
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        out = np.zeros(n, dtype=READ_QUALITY_DTYPE)
+        keep = np.zeros(n, dtype=np.uint8)
+        prm = self._quality_params(params)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_quality_reads(self._ctx, _ptr(quals), quals.size, _ptr(offsets), n, ctypes.addressof(prm), _ptr(out),
+                                                   _ptr(keep), ctypes.byref(kept)))
+        return out, keep, kept.value
+
+    def quality_reads_device(self, d_quals, d_offsets, nreads: int, d_out, d_keep=None, params=None) -> int:
+        """device buffers; d_quals 4-byte aligned, d_out holds nreads records of 24 bytes (what compact_trimmed_device takes), d_keep
+        (optional) nreads bytes -> reads with len > 0 (waits for the kernel)"""
+        prm = self._quality_params(params)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_quality_reads_device(self._ctx, _ptr(d_quals), _ptr(d_offsets), nreads, ctypes.addressof(prm), _ptr(d_out),
+                                                          _ptr(d_keep), ctypes.byref(kept)))
+        return kept.value
 
     def set_read_ordinal(self, base: int, stride: int = 1):
         self._check(self.lib.sdt_gpu_set_read_ordinal(self._ctx, base, stride))

@@ -63,6 +63,15 @@
  *       prefix.readComplexity: one line per read in stream order:  windows low score start len verdict
  *       prefix.cx.pairs.fa / prefix.cx.single.fa: the kept bases of the surviving reads, as clip writes them
  *       prefix.scoreHist: per score that occurs, ascending:  score reads,  then  # reads R low V dropped D clipped C
+ *   sdt-kmers qtrim -s lib.cfg -K k [-p threads] [--phred 33|64, default 33] [--cut-q Q, default 20] [--low-q Q, default 15]
+ *                   [--max-low-bases PCT, default 40] [--max-ee PPM, default 0 = off] [--min-len L, default 0] -o prefix
+ *       reads cut to their best segment by their base qualities (Mott's rule) and dropped by low bases and expected errors
+ *       (sdt_gpu_quality_reads on every batch as it is parsed; the rule: include/sdt_gpu.h).  FASTQ libraries only.  Mates are
+ *       judged independently; pairs and routing as for clip (qualsplit.c)
+ *       prefix.readQual: one line per read in stream order:  span low ee_ppm start len verdict
+ *       prefix.qtrim.pairs.fa / prefix.qtrim.single.fa: the kept bases of the surviving reads, as clip writes them
+ *       prefix.lenHist: per kept length that occurs, ascending:  len reads,  then
+ *           # reads R whole W clipped C dropped D short S low V errors X bases_in I bases_out O
  *
  * The query file is read and checked before the device is touched. */
 #include <errno.h>
@@ -81,6 +90,7 @@
 #include "clipsplit.h"
 #include "overlapsplit.h"
 #include "cxsplit.h"
+#include "qualsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -162,6 +172,24 @@ static void usage(void)
 	        "              prefix.scoreHist (per score that occurs, ascending: score reads; then: # reads R low V dropped D clipped C,\n"
 	        "              V = the reads that have a low window)\n"
 	        "           Pairs are the reads of q1=/q2= and f1=/f2= files, mates are judged independently, as for clip.\n"
+	        "       sdt-kmers qtrim -s lib.cfg -K k [-p threads] [--phred 33|64, default 33] [--cut-q Q, default 20] [--low-q Q, default 15]\n"
+	        "                       [--max-low-bases PCT, default 40] [--max-ee PPM, default 0] [--min-len L, default 0] -o prefix\n"
+	        "           every read is cut to the segment [a, b) with the greatest sum of (quality - Q) over its bases (Mott's rule, as\n"
+	        "           seqtk trimfq; the first among equal sums, and the longest of those; --cut-q 0 keeps every read whole).  Then a read\n"
+	        "           is dropped if fewer than max(L, 1) bases are left, if more than PCT percent of them have a quality below --low-q\n"
+	        "           (PCT 100 or --low-q 0: off), or if --max-ee is not 0 and the expected errors per million bases of the segment\n"
+	        "           (10^6 * 10^(-q / 10) per base, rounded; floor of their mean) exceed it.  The defaults are the usual figures of\n"
+	        "           fastp and cutadapt: a choice, not a measurement.  The bases are not looked at: a run of N has quality 2 and is cut\n"
+	        "           at the ends of a read and counted as low bases inside it.  Run it first: no other stage has the qualities.\n"
+	        "           FASTQ libraries only (q1= / q2= / q=): a library with an f=, f1=, f2=, p= or b= file is refused, and so is a record\n"
+	        "           whose quality line is not as long as its sequence line, before a data file is written.\n"
+	        "           -> prefix.readQual (per read in stream order: span low ee_ppm start len verdict; span = the bases of the segment,\n"
+	        "              low = those of them below --low-q, ee_ppm = its expected errors per million bases; verdict 0 whole, 2 clipped,\n"
+	        "              3 dropped), prefix.qtrim.pairs.fa (read 1 then read 2 of the pairs of which both mates survive),\n"
+	        "              prefix.qtrim.single.fa (every other surviving read), prefix.lenHist (per kept length that occurs, ascending:\n"
+	        "              len reads; then: # reads R whole W clipped C dropped D short S low V errors X bases_in I bases_out O, where\n"
+	        "              S, V and X are the dropped reads by the line that dropped them)\n"
+	        "           Pairs are the reads of q1=/q2= files, mates are judged independently, as for clip.\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -815,6 +843,110 @@ static int complexity_and_write(sdt_ctx *gpu, unsigned long long reads, const sd
 	return 0;
 }
 
+/* `qtrim`, while the reads stream: every FASTQ batch's qualities through sdt_gpu_quality_reads on a context of its own (nothing of the
+ * asynchronous push path is touched), the records to the batch's ordinals; then the batch is pushed like any other */
+typedef struct {
+	push_state push;
+	sdt_ctx *qgpu;
+	const sdt_quality_params *prm;
+	sdt_read_quality *rec, *dense;                                           /* by ordinal; of one batch */
+	uint64_t cap, dense_cap, n_kept;
+} qtrim_state;
+
+static int qtrim_batch(void *user, const sdt_batch *b, uint64_t ord_base, uint64_t ord_stride)
+{
+	qtrim_state *q = (qtrim_state *)user;
+	if (b->qual_faults) {
+		fprintf(stderr, "sdt-kmers: %llu records of the batch at read %llu have a quality line that is not as long as their sequence line\n",
+		        (unsigned long long)b->qual_faults, (unsigned long long)ord_base + 1);
+		return -1;
+	}
+	if (b->nreads) {
+		if (!b->quals) { fprintf(stderr, "sdt-kmers: the batch at read %llu has no qualities\n", (unsigned long long)ord_base + 1); return -1; }
+		const uint64_t need = ord_base + (b->nreads - 1) * ord_stride + 1;
+		if (need > q->cap) {
+			uint64_t ncap = q->cap ? q->cap : 1 << 16;
+			while (ncap < need) ncap *= 2;
+			sdt_read_quality *nr = (sdt_read_quality *)realloc(q->rec, ncap * sizeof(sdt_read_quality));
+			if (!nr) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", (unsigned long long)ncap); return -1; }
+			memset(nr + q->cap, 0, (ncap - q->cap) * sizeof(sdt_read_quality));
+			q->rec = nr;
+			q->cap = ncap;
+		}
+		if (b->nreads > q->dense_cap) {
+			free(q->dense);
+			q->dense = (sdt_read_quality *)malloc(b->nreads * sizeof(sdt_read_quality));
+			q->dense_cap = q->dense ? b->nreads : 0;
+			if (!q->dense) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", (unsigned long long)b->nreads); return -1; }
+		}
+		uint64_t kept = 0;
+		if (sdt_gpu_quality_reads(q->qgpu, b->quals, b->offsets[b->nreads], b->offsets, b->nreads, q->prm, q->dense, NULL, &kept) != SDT_OK) {
+			fprintf(stderr, "sdt_gpu_quality_reads: %s\n", sdt_gpu_last_error());
+			return -1;
+		}
+		q->n_kept += kept;
+		for (uint64_t i = 0; i < b->nreads; i++) q->rec[ord_base + i * ord_stride] = q->dense[i];
+	}
+	return push_batch(&q->push, b, ord_base, ord_stride);
+}
+
+/* `qtrim`, after the stream: the kept batches back from HBM, the kept bases of every read into the pairs file (both mates survive) or
+ * the singles file, routed as clip routes them; the histogram of the kept lengths (qualsplit.c) */
+static int qtrim_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_quality_params *prm, const sdt_read_quality *rec, uint64_t n_kept,
+                           const sdt_pair_ranges *pairs, const char *prefix)
+{
+	kept_reads k;
+	if (kept_fetch(gpu, reads, &k) != 0) return 1;
+	char path[4][4200];
+	snprintf(path[0], sizeof path[0], "%s.readQual", prefix);
+	snprintf(path[1], sizeof path[1], "%s.qtrim.pairs.fa", prefix);
+	snprintf(path[2], sizeof path[2], "%s.qtrim.single.fa", prefix);
+	snprintf(path[3], sizeof path[3], "%s.lenHist", prefix);
+	outbuf oq, opair, osingle;
+	if (ob_open(&oq, path[0]) != 0) return 1;
+	if (ob_open(&opair, path[1]) != 0) { ob_close(&oq); return 1; }
+	if (ob_open(&osingle, path[2]) != 0) { ob_close(&oq); ob_close(&opair); return 1; }
+	sdt_len_hist hist;
+	memset(&hist, 0, sizeof hist);
+	unsigned long long kept = 0;
+	size_t cursor = 0;
+	int bad = 0;
+	for (uint64_t ord = 0; ord < reads; ord++) {
+		if (!oq.ok || !opair.ok || !osingle.ok) break;                                 /* a write failed: ob_close says which */
+		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
+		const sdt_read_quality *t = rec + ord;
+		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
+		const int noted = sdt_len_hist_note(&hist, t, len, prm);
+		if (noted != 0) {
+			if (noted == -1) fprintf(stderr, "sdt-kmers: out of memory for the histogram\n");
+			else fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->span, t->low,
+			             t->ee_ppm, t->start, t->len, t->verdict, (unsigned long long)len);
+			bad = 1;
+			break;
+		}
+		ob_room(&oq, SDT_QUAL_LINE_MAX);
+		oq.p = sdt_put_qual_line(oq.p, t);
+		/* (start and len sit where sdt_read_trim has them: qualsplit.h) */
+		const int to = sdt_trim_route(pairs, &cursor, (const sdt_read_trim *)rec, reads, ord);
+		if (to == SDT_TRIM_TO_NONE) continue;
+		kept++;
+		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
+		ob_room(o, (size_t)t->len + 24);
+		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start + t->start, t->len);
+	}
+	const int all_written = oq.ok && opair.ok && osingle.ok;
+	if ((ob_close(&oq) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
+	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
+	FILE *fh = fopen(path[3], "w");
+	if (!fh || (sdt_len_hist_write(fh, &hist) != 0) | (fclose(fh) != 0)) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path[3]); return 1; }
+	printf("%llu reads: %llu whole, %llu clipped, %llu dropped (%llu short, %llu low bases, %llu expected errors); %llu bases in, %llu bases out\n", reads,
+	       (unsigned long long)hist.whole, (unsigned long long)hist.clipped, (unsigned long long)hist.dropped, (unsigned long long)hist.n_short,
+	       (unsigned long long)hist.n_low, (unsigned long long)hist.n_errors, (unsigned long long)hist.bases_in, (unsigned long long)hist.bases_out);
+	sdt_len_hist_free(&hist);
+	kept_free(&k);
+	return 0;
+}
+
 /* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
 static int tail_mask(const char *opt, const char *text)
 {
@@ -894,10 +1026,11 @@ int main(int argc, char **argv)
 {
 	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0 && strcmp(argv[1], "correct") != 0 &&
 	                 strcmp(argv[1], "normalize") != 0 && strcmp(argv[1], "trim") != 0 && strcmp(argv[1], "dedup") != 0 && strcmp(argv[1], "clip") != 0 &&
-	                 strcmp(argv[1], "overlap") != 0 && strcmp(argv[1], "complexity") != 0)) { usage(); return 255; }
+	                 strcmp(argv[1], "overlap") != 0 && strcmp(argv[1], "complexity") != 0 && strcmp(argv[1], "qtrim") != 0)) { usage(); return 255; }
 	const int do_query = strcmp(argv[1], "query") == 0, do_correct = strcmp(argv[1], "correct") == 0, do_norm = strcmp(argv[1], "normalize") == 0;
 	const int do_trim = strcmp(argv[1], "trim") == 0, do_dedup = strcmp(argv[1], "dedup") == 0, do_clip = strcmp(argv[1], "clip") == 0;
-	const int do_overlap = strcmp(argv[1], "overlap") == 0, do_cx = strcmp(argv[1], "complexity") == 0;
+	const int do_overlap = strcmp(argv[1], "overlap") == 0, do_cx = strcmp(argv[1], "complexity") == 0, do_qtrim = strcmp(argv[1], "qtrim") == 0;
+	sdt_quality_params qprm = {33, 20, 15, 40, 0, 0, 0, 0};
 	sdt_overlap_params oprm = {30, 10, 0, 0};
 	sdt_complexity_params xprm = {10, 50, 0, 0};
 	int max_low_given = 0;
@@ -918,7 +1051,9 @@ int main(int argc, char **argv)
 	                                   {"error-pct", required_argument, 0, 1012}, {"min-tail", required_argument, 0, 1013},
 	                                   {"tail-error-pct", required_argument, 0, 1014}, {"max-err", required_argument, 0, 1015},
 	                                   {"max-score", required_argument, 0, 1016}, {"max-low", required_argument, 0, 1017},
-	                                   {"trim-low", no_argument, 0, 1018},
+	                                   {"trim-low", no_argument, 0, 1018}, {"phred", required_argument, 0, 1019},
+	                                   {"cut-q", required_argument, 0, 1020}, {"low-q", required_argument, 0, 1021},
+	                                   {"max-low-bases", required_argument, 0, 1022}, {"max-ee", required_argument, 0, 1023},
 	                                   {0, 0, 0, 0}};
 	argv++; argc--;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:", longopts, NULL)) != -1) {
@@ -945,15 +1080,15 @@ int main(int argc, char **argv)
 		case 1005: case 1006: case 1007: {
 			const char *opt = c == 1005 ? "--min-cov" : (c == 1006 ? "--min-len" : "--correct");
 			unsigned long long v;
-			if (!do_trim && !((do_clip || do_overlap || do_cx) && c == 1006)) {
-				fprintf(stderr, "sdt-kmers: %s belongs to trim%s\n", opt, c == 1006 ? ", clip, overlap and complexity" : "");
+			if (!do_trim && !((do_clip || do_overlap || do_cx || do_qtrim) && c == 1006)) {
+				fprintf(stderr, "sdt-kmers: %s belongs to trim%s\n", opt, c == 1006 ? ", clip, overlap, complexity and qtrim" : "");
 				usage();
 				return 255;
 			}
 			if (c == 1007) { tprm.flags |= SDT_TRIM_CORRECTED; break; }
 			if (parse_number(opt, optarg, UINT32_MAX, &v) != 0) return 255;
 			if (c == 1005) tprm.min_cov = (uint32_t)v;
-			else tprm.min_len = cprm.min_len = oprm.min_len = xprm.min_len = (uint32_t)v;
+			else tprm.min_len = cprm.min_len = oprm.min_len = xprm.min_len = qprm.min_len = (uint32_t)v;
 			break;
 		}
 		case 'a': case 'g': case 1009: case 1010: case 1011: case 1012: case 1013: case 1014: {
@@ -992,6 +1127,20 @@ int main(int argc, char **argv)
 			if (c == 1016 && v == 0) { fprintf(stderr, "sdt-kmers: --max-score must be at least 1: at 0 every window would be low\n"); return 255; }
 			if (c == 1016) xprm.max_score_pct = (uint32_t)v;
 			else { xprm.max_low_pct = (uint32_t)v; max_low_given = 1; }
+			break;
+		}
+		case 1019: case 1020: case 1021: case 1022: case 1023: {
+			static const char *const names[] = {"--phred", "--cut-q", "--low-q", "--max-low-bases", "--max-ee"};
+			const char *opt = names[c - 1019];
+			unsigned long long v;
+			if (!do_qtrim) { fprintf(stderr, "sdt-kmers: %s belongs to qtrim\n", opt); usage(); return 255; }
+			if (parse_number(opt, optarg, c == 1019 ? 64 : (c == 1022 ? 100 : (c == 1023 ? UINT32_MAX : 93)), &v) != 0) return 255;
+			if (c == 1019 && v != 33 && v != 64) { fprintf(stderr, "sdt-kmers: --phred %llu: 33 or 64\n", v); return 255; }
+			if (c == 1019) qprm.phred_offset = (uint32_t)v;
+			else if (c == 1020) qprm.cut_q = (uint32_t)v;
+			else if (c == 1021) qprm.low_q = (uint32_t)v;
+			else if (c == 1022) qprm.max_low_pct = (uint32_t)v;
+			else qprm.max_ee_ppm = (uint32_t)v;
 			break;
 		}
 		case 1008:
@@ -1041,6 +1190,12 @@ int main(int argc, char **argv)
 	sdt_cfg cfg;
 	if (sdt_cfg_load(cfgfile, &cfg) != 0) return 255;
 	const int max_read_len = cfg.max_rd_len ? cfg.max_rd_len : 100;         /* prlHashReads.c:361-364 */
+	/* qtrim: every read needs its qualities; refused before the device is touched and before anything is written */
+	for (int i = 0; i < cfg.nlibs && do_qtrim; i++) {
+		const sdt_lib *l = &cfg.libs[i];
+		const char *fasta = l->nf ? l->f[0] : (l->nf1 ? l->f1[0] : (l->nf2 ? l->f2[0] : (l->np ? l->p[0] : (l->nb ? l->b[0] : NULL))));
+		if (fasta) { fprintf(stderr, "sdt-kmers: qtrim needs base qualities: %s is not a FASTQ file (q1= / q2= / q=)\n", fasta); return 2; }
+	}
 
 	sdt_ctx *gpu = NULL;
 	if (sdt_gpu_init(&gpu, device, K, 0, do_query ? 0u : SDT_FLAG_KEEP_READS) != SDT_OK) {
@@ -1049,11 +1204,25 @@ int main(int argc, char **argv)
 	}
 	sdt_pair_ranges pairs;
 	memset(&pairs, 0, sizeof pairs);
-	push_state st = {gpu, 0, do_norm || do_trim || do_dedup || do_clip || do_overlap || do_cx ? &pairs : NULL};
+	push_state st = {gpu, 0, do_norm || do_trim || do_dedup || do_clip || do_overlap || do_cx || do_qtrim ? &pairs : NULL};
+	qtrim_state qst;
+	memset(&qst, 0, sizeof qst);
+	if (do_qtrim) {
+		if (sdt_gpu_init(&qst.qgpu, device, K, 1, 0) != SDT_OK) { fprintf(stderr, "sdt_gpu_init: %s\n", sdt_gpu_last_error()); return 1; }
+		qst.push = st;
+		qst.prm = &qprm;
+		sdt_read_quals(1);
+	}
 	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
 	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : threads;
 	sdt_pool_enable(sdt_gpu_host_alloc, sdt_gpu_host_free, parse_threads + PUSH_DEPTH + 8);
-	int rc = sdt_stream_reads(&cfg, max_read_len, parse_threads > 0 ? parse_threads : 1, chunk, 0, push_batch, &st, NULL);
+	int rc = do_qtrim ? sdt_stream_reads(&cfg, max_read_len, parse_threads > 0 ? parse_threads : 1, chunk, 0, qtrim_batch, &qst, NULL)
+	                  : sdt_stream_reads(&cfg, max_read_len, parse_threads > 0 ? parse_threads : 1, chunk, 0, push_batch, &st, NULL);
+	if (do_qtrim) {
+		st.reads = qst.push.reads;
+		sdt_read_quals(0);
+		sdt_gpu_destroy(qst.qgpu);
+	}
 	if (rc == 0 && inflight_retire(gpu, 0) != 0) rc = -1;
 	sdt_pool_disable();
 	if (rc != 0) { sdt_gpu_destroy(gpu); return 1; }
@@ -1083,6 +1252,11 @@ int main(int argc, char **argv)
 	} else if (do_cx) {
 		if (complexity_and_write(gpu, st.reads, &xprm, &pairs, outname) != 0) return 1;
 		sdt_pair_ranges_free(&pairs);
+	} else if (do_qtrim) {
+		if (st.reads > qst.cap) { fprintf(stderr, "sdt-kmers: %llu reads streamed, records for %llu\n", st.reads, (unsigned long long)qst.cap); return 1; }
+		if (qtrim_and_write(gpu, st.reads, &qprm, qst.rec, qst.n_kept, &pairs, outname) != 0) return 1;
+		sdt_pair_ranges_free(&pairs);
+		free(qst.rec); free(qst.dense);
 	} else if (do_correct) {
 		if (correct_and_write(gpu, st.reads, (uint32_t)min_count, outname) != 0) return 1;
 	} else if (!do_query) {

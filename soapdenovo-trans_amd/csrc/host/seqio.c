@@ -36,6 +36,9 @@ void sdt_read_shard_begin(int rank, int nranks, int keep_all)
 
 void sdt_read_shard_skip_foreign(int on) { g_shard_skip = on; }
 
+static int g_read_quals = 0;
+void sdt_read_quals(int on) { g_read_quals = on; }
+
 typedef struct {
 	chunk_t *chunks;
 	int nchunks, next, turn;    /* next: chunk numbers handed out; turn: chunks whose pool buffer has been handed out */
@@ -154,6 +157,25 @@ static inline void pk_put(packer_t *p, unsigned code)
 	p->nbases++;
 }
 
+/* ---- the quality bytes of a FASTQ chunk, one per base of the stream (sdt_read_quals) ---- */
+typedef struct {
+	uint8_t *q;
+	uint64_t cap, n;
+} qbuf_t;
+
+static void qb_reserve(qbuf_t *b, uint64_t more)
+{
+	if (b->n + more + 8 > b->cap) {
+		uint64_t ncap = b->cap ? b->cap * 2 : 1 << 16;
+		while (ncap < b->n + more + 8) ncap *= 2;
+		b->q = (uint8_t *)realloc(b->q, ncap);
+		b->cap = ncap;
+	}
+}
+
+/* the quality byte of character i of a sequence line whose quality line has qn bytes: byte 0 where that line is too short */
+static inline uint8_t qual_at(const char *qs, int qn, int i) { return i < qn ? (uint8_t)qs[i] : 0; }
+
 /* Fast path for the common line -- nothing but letters: 32 characters per step.  The base code is bits 1..2 of the
  * character in either case ((c & 6) >> 1, inc/def.h:39-42), so after a check that all 32 bytes are letters the codes
  * are one shift and one mask away, and PEXT squeezes the 2-bit codes of 8 bytes into 16 bits (first base on top).
@@ -225,8 +247,9 @@ static int have_avx2_bmi2(void)
 	return c;
 }
 
-/* one sequence line -> stream; returns coded length */
-static int encode_line(packer_t *pk, const char *s, int n, int max_read_len, int reverse)
+/* one sequence line -> stream; returns coded length.  qb != NULL: the quality line qs[0, qn) goes along, a byte per base that is
+ * coded: cut where the sequence is cut, without the bytes of the characters that are dropped, reversed where the read is */
+static int encode_line(packer_t *pk, const char *s, int n, int max_read_len, int reverse, qbuf_t *qb, const char *qs, int qn)
 {
 	unsigned char tmp[8192];
 	unsigned char *codes = tmp;
@@ -238,19 +261,31 @@ static int encode_line(packer_t *pk, const char *s, int n, int max_read_len, int
 		s += fast;
 		n -= fast;
 	}
+	if (qb) {
+		/* (the fast path takes letters only: none of its characters is dropped) */
+		qb_reserve(qb, (uint64_t)fast + (uint64_t)n);
+		for (int i = 0; i < fast; i++) qb->q[qb->n++] = qual_at(qs, qn, i);
+	}
 	if (n > (int)sizeof tmp) codes = (unsigned char *)malloc((size_t)n);
+	uint8_t *quals = qb ? qb->q + qb->n : NULL;            /* of the coded bases, in the order of the line */
 	int m = 0;
 	for (int i = 0; i < n; i++) {
 		unsigned char c = (unsigned char)s[i];
 		if (c >= 'a' && c <= 'z') c = (unsigned char)(c - 'a' + 'A');
 		if (c >= 'A' && c <= 'Z') codes[m++] = (unsigned char)((c & 6) >> 1);
 		else if (c == '.') codes[m++] = 0;
+		else continue;
+		if (quals) quals[m - 1] = qual_at(qs, qn, fast + i);
 	}
 	pk_reserve(pk, (uint64_t)m);
 	if (!reverse)
 		for (int i = 0; i < m; i++) pk_put(pk, codes[i]);
-	else
+	else {
 		for (int i = m - 1; i >= 0; i--) pk_put(pk, codes[i] ^ 2u);
+		if (quals)
+			for (int i = 0; i < m / 2; i++) { const uint8_t t = quals[i]; quals[i] = quals[m - 1 - i]; quals[m - 1 - i] = t; }
+	}
+	if (qb) qb->n += (uint64_t)m;
 	if (codes != tmp) free(codes);
 	return m + fast;
 }
@@ -274,6 +309,10 @@ static void parse_chunk(job_t *J, chunk_t *c)
 		return;
 	}
 	packer_t pk = {0};
+	qbuf_t qb = {0};
+	const int with_quals = g_read_quals && J->fmt == 'q' && c->encode;
+	uint64_t qual_faults = 0;
+	if (with_quals) qb_reserve(&qb, 0);
 	uint64_t cap_off = 1024, n = 0;
 	uint64_t *offs;
 	int offs_pooled = 0;
@@ -301,11 +340,16 @@ static void parse_chunk(job_t *J, chunk_t *c)
 			const char *se = line_end(seq, end);
 			int sl = (int)(se - seq);
 			if (sl > 0 && seq[sl - 1] == '\r') sl--;
-			if (c->encode) len = encode_line(&pk, seq, sl, J->max_read_len, J->reverse);
 			const char *plus = se < end ? se + 1 : end;
 			const char *pe = line_end(plus, end);
 			const char *qual = pe < end ? pe + 1 : end;
 			const char *qe = line_end(qual, end);
+			if (with_quals) {
+				int ql = (int)(qe - qual);
+				if (ql > 0 && qual[ql - 1] == '\r') ql--;
+				qual_faults += ql != sl;                  /* the record gets the bytes it has, byte 0 for the rest */
+				len = encode_line(&pk, seq, sl, J->max_read_len, J->reverse, &qb, qual, ql);
+			} else if (c->encode) len = encode_line(&pk, seq, sl, J->max_read_len, J->reverse, NULL, NULL, 0);
 			p = qe < end ? qe + 1 : end;
 		} else {
 			/* FASTA: sequence lines up to the next '>' at a line start are one read (the reference only
@@ -330,7 +374,7 @@ static void parse_chunk(job_t *J, chunk_t *c)
 				bl += sl;
 				q = se < end ? se + 1 : end;
 			}
-			if (c->encode) len = encode_line(&pk, buf, (int)bl, J->max_read_len, J->reverse);
+			if (c->encode) len = encode_line(&pk, buf, (int)bl, J->max_read_len, J->reverse, NULL, NULL, 0);
 			if (buf != stackbuf) free(buf);
 			p = q;
 		}
@@ -373,6 +417,8 @@ static void parse_chunk(job_t *J, chunk_t *c)
 	c->out.chunk_index = c->index;
 	c->out.count_unknown = 0;
 	c->out.stream_id = c->out.stream_parity = 0;
+	c->out.quals = qb.q;                                   /* NULL unless sdt_read_quals is on and the file is FASTQ */
+	c->out.qual_faults = qual_faults;
 	if (!c->encode) {                                      /* a foreign chunk: only the number of records matters */
 		free(pk.w);
 		free(offs);
@@ -494,6 +540,7 @@ int sdt_read_file(const char *path, int fmt, int max_read_len, int reverse, int 
 		sdt_reader_wait_ms += t_b - t_a;
 		sdt_reader_fn_ms += seq_now() - t_b;
 		total += J.chunks[i].out.nreads;
+		free(J.chunks[i].out.quals);                          /* (never a pool buffer) */
 		if (J.chunks[i].out.pool_slot >= 0) {                 /* the callback may have kept the buffer (sdt_pool_take) */
 			pthread_mutex_lock(&g_pool.mu);
 			const int kept = g_pool.slot[J.chunks[i].out.pool_slot].state == 2;

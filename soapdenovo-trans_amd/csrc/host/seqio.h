@@ -26,7 +26,16 @@ typedef struct {
 	int count_unknown;      /* 1: a foreign chunk that was not even scanned (sdt_read_shard_skip_foreign): nreads is 0, the owner knows */
 	int stream_id;          /* number of the file within the pass */
 	int stream_parity;      /* paired files: 0 = the reads of this file take the even ordinals of the pair, 1 = the odd ones */
+	/* sdt_read_quals(1), FASTQ only (else NULL / 0) */
+	uint8_t *quals;         /* the raw quality bytes, one per base of the stream, under the same offsets; a malloc block, never a pool
+	                         * buffer, freed by the reader after the callback */
+	uint64_t qual_faults;   /* records whose quality line is not as long as their sequence line: they have the bytes they have, then byte 0 */
 } sdt_batch;
+
+/* Opt-in, default off (nothing changes then, not even the allocations): FASTQ batches also carry their quality bytes, parallel to the
+ * bases through everything the sequence line goes through: the cut to max_read_len, the characters that are dropped (their quality
+ * bytes are dropped with them), and reverse_seq (the qualities are reversed).  Set it before sdt_read_file, not while one runs. */
+void sdt_read_quals(int on);
 
 /* Optional pool of output buffers for a host that hands batches to the device ASYNCHRONOUSLY from pinned memory (the
  * reference double-buffers its read buffers the same way, prlHashReads.c:493-620): chunks are packed straight into pool

@@ -2,8 +2,9 @@
 // sdt_select.hip, sdt_trim.hip) decide on the host before anything reaches the device, as PURE functions: the launch geometry of a
 // strip kernel, the check of a host stream's offsets, and the cut of a host batch into the pieces that are staged one at a time.
 // sdt_readstage.hpp calls them for every stage; tools/read_plan_check.cpp (tests/test_read_plan.py) calls them on the CPU under
-// sanitizers.  The four stages that need no table have theirs here too: the duplicate filter (sdt_dedup.hip), the adapter and tail
-// clipping (sdt_clip.hip), the mate overlap (sdt_overlap.hip) and the low-complexity filter (sdt_complexity.hip).  No HIP in here.
+// sanitizers.  The five stages that need no table have theirs here too: the duplicate filter (sdt_dedup.hip), the adapter and tail
+// clipping (sdt_clip.hip), the mate overlap (sdt_overlap.hip), the low-complexity filter (sdt_complexity.hip) and the quality trim
+// (sdt_quality.hip), which also has its cut of a byte stream into pieces here.  No HIP in here.
 #pragma once
 #include <stdint.h>
 
@@ -294,6 +295,90 @@ constexpr uint64_t complexity_window_begin(uint64_t j) { return j * COMPLEXITY_S
 constexpr uint64_t complexity_window_end(uint64_t j, uint64_t L)
 {
 	return j * COMPLEXITY_STEP + COMPLEXITY_WINDOW < L ? j * COMPLEXITY_STEP + COMPLEXITY_WINDOW : L;
+}
+
+// ---- quality trimming (sdt_quality.hip): what is refused before any launch, the expected errors of a quality, and a host stream of
+// quality bytes cut into pieces ----
+// (tools/quality_plan_check.cpp runs the check, holds the table to the exact rounding and the pieces to a cover of every read)
+struct QualityParams {                                   // == sdt_quality_params of include/sdt_gpu.h
+	uint32_t phred_offset, cut_q, low_q, max_low_pct, max_ee_ppm, min_len, flags, reserved;
+};
+constexpr uint32_t QUALITY_MAX_Q = 93;                   // '~' - '!': the highest quality a FASTQ byte can say
+
+enum QualityFault { QUALITY_OK = 0, QUALITY_PHRED_OFFSET, QUALITY_CUT_Q, QUALITY_LOW_Q, QUALITY_MAX_LOW_PCT, QUALITY_FLAGS, QUALITY_RESERVED };
+
+// the first field that is refused, in the order of the rules in include/sdt_gpu.h
+inline QualityFault check_quality_params(const QualityParams &p)
+{
+	if (p.phred_offset != 0 && p.phred_offset != 33 && p.phred_offset != 64) return QUALITY_PHRED_OFFSET;
+	if (p.cut_q > QUALITY_MAX_Q) return QUALITY_CUT_Q;
+	if (p.low_q > QUALITY_MAX_Q) return QUALITY_LOW_Q;
+	if (p.max_low_pct > 100) return QUALITY_MAX_LOW_PCT;
+	if (p.flags != 0) return QUALITY_FLAGS;
+	if (p.reserved != 0) return QUALITY_RESERVED;
+	return QUALITY_OK;
+}
+
+// the quality a byte says: 0 below the offset, 93 at most
+constexpr uint32_t quality_of(uint32_t byte, uint32_t phred_offset)
+{
+	return byte < phred_offset ? 0 : (byte - phred_offset > QUALITY_MAX_Q ? QUALITY_MAX_Q : byte - phred_offset);
+}
+
+// e[q] = 10^6 * 10^(-q / 10) rounded to the nearest integer: the expected errors of a base of quality q, in millionths.  No entry is
+// a tie: (2 t - 1)^10 10^q <= (2 10^6)^10 < (2 t + 1)^10 10^q holds for every entry t (the left half for t >= 1).
+// (constexpr: the kernel calls it too)
+constexpr uint32_t QUALITY_EE_PPM[QUALITY_MAX_Q + 1] = {
+	1000000, 794328, 630957, 501187, 398107, 316228, 251189, 199526, 158489, 125893,
+	100000, 79433, 63096, 50119, 39811, 31623, 25119, 19953, 15849, 12589,
+	10000, 7943, 6310, 5012, 3981, 3162, 2512, 1995, 1585, 1259,
+	1000, 794, 631, 501, 398, 316, 251, 200, 158, 126,
+	100, 79, 63, 50, 40, 32, 25, 20, 16, 13,
+	10, 8, 6, 5, 4, 3, 3, 2, 2, 1,
+	1, 1, 1, 1, 0, 0, 0, 0, 0, 0,
+	0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+	0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+	0, 0, 0, 0,
+};
+
+// a host stream of quality bytes: nreads reads in nbytes bytes, read i = bytes [offsets[i], offsets[i + 1]).  As check_stream, without
+// pad: need_words is here the BYTES the stream takes.
+inline StreamCheck check_byte_stream(const uint64_t *offsets, uint64_t nreads, uint64_t nbytes)
+{
+	StreamCheck s = {STREAM_OK, 0, 0, 0};
+	for (uint64_t i = 0; i < nreads; i++) {
+		if (offsets[i + 1] < offsets[i]) {
+			s.fault = STREAM_NOT_MONOTONIC;
+			s.read = i;
+			return s;
+		}
+		raise_to(s.longest, offsets[i + 1] - offsets[i]);
+	}
+	s.need_words = nreads ? offsets[nreads] : 0;
+	if (s.need_words > nbytes) s.fault = STREAM_TOO_SHORT;
+	return s;
+}
+
+// The piece of a checked byte stream that starts at read r0, as next_piece with units of one read: the first read is always taken
+// (so a read longer than piece_bytes is a piece of its own), further ones while the piece stays below piece_reads reads and within
+// piece_bytes bytes.  The piece is staged as bytes [b0, b0 + nbytes) of the stream; b0 is the start of its first read rounded down to
+// a multiple of 4, so that a read keeps its place within a 32-bit word, and the piece's offsets are rebased to b0.
+struct BytePiece {
+	uint64_t r1;                   // reads [r0, r1)
+	uint64_t b0, nbytes;           // read i of the piece starts at byte offsets[r0 + i] - b0 of them; nbytes ends with the last read
+};
+
+inline BytePiece next_byte_piece(const uint64_t *offsets, uint64_t nreads, uint64_t r0, uint64_t piece_reads, uint64_t piece_bytes)
+{
+	uint64_t lo = 1, hi = piece_reads ? piece_reads : 1;
+	if (hi > nreads - r0) hi = nreads - r0;
+	while (lo < hi) {
+		const uint64_t mid = lo + (hi - lo + 1) / 2;
+		if (offsets[r0 + mid] - offsets[r0] <= piece_bytes) lo = mid; else hi = mid - 1;
+	}
+	BytePiece p = {r0 + lo, offsets[r0] & ~3ULL, 0};
+	p.nbytes = offsets[p.r1] - p.b0;
+	return p;
 }
 
 } // namespace sdt

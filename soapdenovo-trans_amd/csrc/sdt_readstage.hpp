@@ -73,12 +73,15 @@ static int launch_strip(sdt_ctx *c, uint64_t nreads, uint64_t max_read_len, Fn f
 	return SDT_OK;
 }
 
+// (one message for the streams of bases and of bytes)
+static int offsets_descend(const StreamCheck *s) { return fail(SDT_EINVAL, "offsets not monotonic at read %llu", (unsigned long long)s->read); }
+
 // the offsets and the length of a host stream, with the two messages; s->longest: the bases of its longest read, s->need_words: its words
 static int stream_args_ok(const uint64_t *offsets, uint64_t nreads, uint64_t nwords, StreamCheck *s)
 {
 	*s = check_stream(offsets, nreads, nwords, TAIL_PAD);
 	if (s->fault == STREAM_NOT_MONOTONIC)
-		return fail(SDT_EINVAL, "offsets not monotonic at read %llu", (unsigned long long)s->read);
+		return offsets_descend(s);
 	if (s->fault == STREAM_TOO_SHORT)
 		return fail(SDT_EINVAL, "packed_words too short: need %llu words incl. %d pad words", (unsigned long long)s->need_words, TAIL_PAD);
 	return SDT_OK;
@@ -118,7 +121,49 @@ static int for_each_piece(sdt_ctx *c, const uint32_t *words, const uint64_t *off
 	return SDT_OK;
 }
 
-// The two counters of a strip kernel, d_cov_flags[0] (reads longer than max_read_len) and [2] (the stage's own: edits, reads kept):
+// The same for a checked host stream of BYTES, one per base, under the offsets of the 2-bit stream (the base qualities:
+// sdt_quality.hip; sdt_read_plan.h: next_byte_piece).  A piece starts at a multiple of 4 bytes of the stream, so a read keeps its
+// place within a 32-bit word; the device buffer ends at a multiple of 4, and what lies behind the last read in it is not set.
+struct StagedBytePiece {
+	const uint8_t *d_bytes;
+	const uint64_t *d_offs;
+	uint64_t nbytes, r0, nr;
+};
+static int byte_stream_args_ok(const uint64_t *offsets, uint64_t nreads, uint64_t nbytes, StreamCheck *s)
+{
+	*s = check_byte_stream(offsets, nreads, nbytes);
+	if (s->fault == STREAM_NOT_MONOTONIC)
+		return offsets_descend(s);
+	if (s->fault == STREAM_TOO_SHORT)
+		return fail(SDT_EINVAL, "quals too short: need %llu bytes", (unsigned long long)s->need_words);
+	return SDT_OK;
+}
+template <class Body>
+static int for_each_byte_piece(sdt_ctx *c, const uint8_t *bytes, const uint64_t *offsets, uint64_t nreads, const char *what, Body body)
+{
+	const uint64_t piece_reads = chunk_items(PROFILE_CHUNK_READS);
+	std::vector<uint64_t> rel;
+	DevBuf d_b, d_o;
+	for (uint64_t r0 = 0; r0 < nreads;) {
+		const BytePiece p = next_byte_piece(offsets, nreads, r0, piece_reads, PROFILE_CHUNK_BASES);
+		const uint64_t nr = p.r1 - r0;
+		rel.resize(nr + 1);
+		for (uint64_t i = 0; i <= nr; i++) rel[i] = offsets[r0 + i] - p.b0;
+		const size_t bbytes = (p.nbytes + 3) & ~(size_t)3, obytes = (nr + 1) * sizeof(uint64_t);
+		if (d_b.cap < bbytes || d_o.cap < obytes) HIPCHK(hipStreamSynchronize(c->stream));
+		int rc = d_b.reserve(bbytes, what);
+		if (rc == SDT_OK) rc = d_o.reserve(obytes, what);
+		if (rc != SDT_OK) return rc;
+		if (p.nbytes) HIPCHK(hipMemcpyAsync(d_b.p, bytes + p.b0, p.nbytes, hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemcpyAsync(d_o.p, rel.data(), obytes, hipMemcpyHostToDevice, c->stream));
+		rc = body(StagedBytePiece{(const uint8_t *)d_b.p, (const uint64_t *)d_o.p, p.nbytes, r0, nr});
+		if (rc != SDT_OK) return rc;
+		r0 = p.r1;
+	}
+	return SDT_OK;
+}
+
+// The two counters of a strip kernel,d_cov_flags[0] (reads longer than max_read_len) and [2] (the stage's own: edits, reads kept):
 // zeroed before the launch; read back after it, which waits for the kernel.  fl[] is filled before [0] is turned into the refusal.
 static int flags_begin(sdt_ctx *c)
 {
