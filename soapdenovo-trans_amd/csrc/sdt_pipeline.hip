@@ -85,8 +85,8 @@ int sk_alloc(sdt_ctx *c, uint64_t want_kmers, uint64_t per_read)
 		HIPCHK(hipStreamSynchronize(c->stream));
 		sk_free(c);
 	}
-	const bool compact = sk_compact(c);
-	const int rw = sk_rec_words(c->nw), rw2 = sk_rec2_stride(c->nw, compact);      // words per record; per slot of a level-2 chunk
+	const bool compact = sk_compact(c), compact1 = sk_compact_l1(c);
+	const int rw = sk_rec1_words(c), rw2 = sk_rec2_stride(c->nw, compact);      // words per slot of a level-1 chunk; of a level-2 chunk
 	const int w = c->K - sk_minimizer_len(c->K) + 1;
 	// records: a run ends where the minimizer's bucket changes (every (w + 1) / 2 k-mers for a random order of the m-mers) or
 	// where the record is full (every `max run` k-mers at the latest): 1 / (2 / (w + 1) + 1 / max run) k-mers per record is what
@@ -99,8 +99,11 @@ int sk_alloc(sdt_ctx *c, uint64_t want_kmers, uint64_t per_read)
 	// records at K = 31 by the model; the measured figure is in profiles/l2_compact), applied to the record count below: through the whole
 	// number `div` the same 3.6 % became 8 -> 7, a seventh more chunks, which pushed the 24 G k-mers of the headline workload past the 2^28
 	// chunk ids of a list entry and cut every step into two batches.  (Reads the strip kernel takes: its power-of-two cap.)
+	// The compact LEVEL-1 record (sdt_sk_record1.h) caps the runs lower still, 23 k-mers at K = 31, and enters the same way: + 10 % of
+	// records by the model (measured: + 0.0012 %, profiles/l1_compact: a window of 21 m-mers rarely keeps its bucket for 23 k-mers), `div`
+	// stays 8 and the step one batch; both level-1 kernels take that cap as it is.
 	const bool strips = c->nw == 4 || per_read > (uint64_t)SK_SEQ_MAX_KMERS;
-	const int cap_c = strips ? sk_pow2_floor(sk_max_run(c->K, c->nw, compact)) : sk_max_run(c->K, c->nw, compact);
+	const int cap_c = compact1 ? sk_max_run1(c->K, SK_L2BITS) : (strips ? sk_pow2_floor(sk_max_run(c->K, c->nw, compact)) : sk_max_run(c->K, c->nw, compact));
 	const double rate = 2.0 / (double)(w + 1) + 1.0 / (double)sk_max_run(c->K, c->nw);
 	const double more = compact ? (2.0 / (double)(w + 1) + 1.0 / (double)cap_c) / rate : 1.0;
 	double run = 1.0 / rate * ((c->nw == 4 || per_read > (uint64_t)SK_SEQ_MAX_KMERS) ? 0.8 : 1.0);
@@ -411,8 +414,12 @@ int sk_scatter_launch(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_off
 	const uint64_t per_read = max_read_len - c->K + 1;
 	const SkGeo geo = sk_geo(c->K, max_read_len);
 	// (the run cap of a compact level-2 record is no power of two at K = 29..31 -- 30 / 28: the one-lane-per-read kernel takes any cap; the
-	// strip kernel cuts at multiples of the cap, j & (ncap - 1), and gets the largest power of two that fits)
-	const int m = sk_minimizer_len(c->K), ncap = sk_max_run(c->K, c->nw, sk_compact(c));
+	// strip kernel cuts at multiples of the cap in the read and gets the largest power of two that fits -- except with compact level-1
+	// records, sdt_sk_record1.h: their cap of 54 - K goes to both kernels as it is, its power-of-two floor would halve the records of
+	// K = 23..27, 32 -> 16)
+	const bool compact1 = sk_compact_l1(c);
+	const int m = sk_minimizer_len(c->K), ncap = compact1 ? sk_max_run1(c->K, SK_L2BITS) : sk_max_run(c->K, c->nw, sk_compact(c));
+	const int ncap_strips = compact1 ? ncap : sk_pow2_floor(ncap);
 	const uint64_t ntiles = (nr + SK_TILE_READS - 1) / SK_TILE_READS;
 	const unsigned grid = (unsigned)(ntiles < k.wgs ? ntiles : k.wgs);
 	EventPair *ev = next_event(c);
@@ -421,10 +428,10 @@ int sk_scatter_launch(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_off
 	ev->kmers = nr * per_read;
 	ev->stage = SDT_STAGE_SK_SCATTER;
 	HIPCHK(hipEventRecord(ev->a, c->stream));
-#define SK_SCATTER(NW)                                                                                                             \
+#define SK_SCATTER(NW, C1)                                                                                                         \
 	do {                                                                                                                       \
-		HIPCHK(hipFuncSetAttribute((const void *)k_sk_scatter_reads<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.smem)); \
-		hipLaunchKernelGGL(k_sk_scatter_reads<NW>, dim3(grid), dim3(TPB), geo.smem, c->stream, d_words, d_offs, nr, c->K, m, sk_pow2_floor(ncap), \
+		HIPCHK(hipFuncSetAttribute((const void *)k_sk_scatter_reads<NW, C1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo.smem)); \
+		hipLaunchKernelGGL((k_sk_scatter_reads<NW, C1>), dim3(grid), dim3(TPB), geo.smem, c->stream, d_words, d_offs, nr, c->K, m, ncap_strips, \
 		                   geo.mtw, geo.tile_words, geo.hv_words, geo.hv2_words, geo.bits_words, k.p1, k.cursors, k.blk, k.cnt1, sk_tbl<NW>(c, allow_direct), c->d_stats, ob, c->ord_stride); \
 	} while (0)
 	// one lane per read where the window length has an instantiation and the run list can hold a read
@@ -439,11 +446,13 @@ int sk_scatter_launch(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_off
 		a.mtw = (int)(((uint64_t)SK_SEQ_TILE * max_read_len + 16 + 15) / 16) + TAIL_PAD + 1;
 		a.pool = k.p1; a.cursors = k.cursors; a.blk = k.blk; a.cnt = k.cnt1; a.stats = c->d_stats;
 		a.ord_base = ob; a.ord_stride = c->ord_stride; a.max_wgs = k.wgs; a.cu_count = c->cu_count; a.stream = c->stream;
+		a.compact1 = compact1;
 		HIPCHK(seq1 ? sk_seq_launch_nw1(w, a, sk_tbl<1>(c, allow_direct)) : (w <= 33 ? sk_seq_launch_nw2_lo(w, a, sk_tbl<2>(c, allow_direct))
 		            : (w <= 43 ? sk_seq_launch_nw2_mid(w, a, sk_tbl<2>(c, allow_direct)) : sk_seq_launch_nw2_hi(w, a, sk_tbl<2>(c, allow_direct)))));
-	} else if (c->nw == 1) SK_SCATTER(1);
-	else if (c->nw == 2) SK_SCATTER(2);
-	else SK_SCATTER(4);
+	} else if (c->nw == 1 && compact1) SK_SCATTER(1, true);
+	else if (c->nw == 1) SK_SCATTER(1, false);
+	else if (c->nw == 2) SK_SCATTER(2, false);
+	else SK_SCATTER(4, false);
 #undef SK_SCATTER
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(ev->b, c->stream));

@@ -27,7 +27,10 @@ static const uint32_t SK_MAX_COUNT_LAUNCHES = 4096;          // k-mers per k_sk_
 // init -- so that the run cap of level 1, the pools, the level-2 scatter and the count stage cannot disagree.  (Not by c->d_first: the
 // ordinals are dropped once the graph is laid out and come back with the next reset.)
 static inline bool sk_compact(const sdt_ctx *c) { return sdt::sk_compact2(c->nw, (c->flags & SDT_FLAG_TRACK_FIRST) != 0); }
-
+// ... and the level-1 records in theirs (sdt_sk_record1.h)?  The same two facts (and the A/B knob SDT_SK_COMPACT1).
+static inline bool sk_compact_l1(const sdt_ctx *c) { return sdt::sk_compact1(c->nw, (c->flags & SDT_FLAG_TRACK_FIRST) != 0); }
+// 64-bit words of a level-1 record of this context: the slots of pool 1, of the exchange buffers of a sharded context, of what travels
+static inline int sk_rec1_words(const sdt_ctx *c) { return sdt::sk_rec1_stride(c->nw, sk_compact_l1(c)); }
 struct SkGeo { int mtw, tile_words, hv_words, hv2_words, bits_words; size_t smem; };
 SkGeo sk_geo(int K, uint64_t max_read_len);
 bool sk_applicable(const sdt_ctx *c, uint64_t max_read_len);

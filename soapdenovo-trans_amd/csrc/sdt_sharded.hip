@@ -33,7 +33,7 @@ int shard_alloc(sdt_ctx *c)
 		return SDT_OK;
 	HIPCHK(hipStreamSynchronize(c->stream));
 	shard_free(c);
-	const size_t cw = (size_t)SK_CAP1 * sk_rec_words(c->nw) * 8;
+	const size_t cw = (size_t)SK_CAP1 * sk_rec1_words(c) * 8;
 	h.send_chunks = k.p1.chunks;
 	h.recv_chunks = k.p1.chunks + k.p1.chunks / 4;   // a rank receives ~ what it sends; head room for unequal buckets
 	if (sdt_test_env("SDT_SHARD_RECV_CHUNKS"))             // (tests: force sub-rounds)
@@ -104,7 +104,7 @@ int sk_flush_sharded(sdt_ctx *c)
 	// sub-rounds, pieces and buffer layouts: pure functions of the matrix (sdt_shard_plan.h) -- every rank computes every
 	// rank's layout from it, so all agree without another message
 	const uint32_t S = shard_subrounds(mat.data(), n, blo, h.recv_chunks);
-	const size_t cw = (size_t)SK_CAP1 * sk_rec_words(c->nw) * 8;
+	const size_t cw = (size_t)SK_CAP1 * sk_rec1_words(c) * 8;
 	for (uint32_t t = 0; t < S; t++) {
 		const int slot = (int)(h.round & 1);
 		ShardRound sr;
@@ -172,7 +172,9 @@ int sk_flush_sharded(sdt_ctx *c)
 			HIPCHK(hipStreamWaitEvent(c->stream, h.ev_xdone[slot], 0));
 		if (plan.pre[n]) {
 			const unsigned g = (unsigned)c->cu_count * 8;
-			if (c->nw == 1) hipLaunchKernelGGL(k_sk_gather<SkFmt<1>::REC_WORDS>, dim3(g), dim3(256), 0, c->stream, k.p1, k.list1, plan, h.send[slot], h.send_meta[slot], h.recv[slot], h.recv_meta[slot]);
+			// (whole chunks of level-1 records as they lie in pool 1: sk_rec1_words(c) words per record)
+			if (sk_rec1_words(c) == SK_REC1C_WORDS) hipLaunchKernelGGL(k_sk_gather<SK_REC1C_WORDS>, dim3(g), dim3(256), 0, c->stream, k.p1, k.list1, plan, h.send[slot], h.send_meta[slot], h.recv[slot], h.recv_meta[slot]);
+			else if (c->nw == 1) hipLaunchKernelGGL(k_sk_gather<SkFmt<1>::REC_WORDS>, dim3(g), dim3(256), 0, c->stream, k.p1, k.list1, plan, h.send[slot], h.send_meta[slot], h.recv[slot], h.recv_meta[slot]);
 			else if (c->nw == 2) hipLaunchKernelGGL(k_sk_gather<SkFmt<2>::REC_WORDS>, dim3(g), dim3(256), 0, c->stream, k.p1, k.list1, plan, h.send[slot], h.send_meta[slot], h.recv[slot], h.recv_meta[slot]);
 			else hipLaunchKernelGGL(k_sk_gather<SkFmt<4>::REC_WORDS>, dim3(g), dim3(256), 0, c->stream, k.p1, k.list1, plan, h.send[slot], h.send_meta[slot], h.recv[slot], h.recv_meta[slot]);
 			HIPCHK(hipGetLastError());

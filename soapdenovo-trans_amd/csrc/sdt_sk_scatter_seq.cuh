@@ -225,8 +225,22 @@ constexpr int SK_SEQ_RUNCAP = 24;                // runs per read the list holds
 constexpr int SK_SEQ_MAX_KMERS = 256;            // k-mers per read (the list entry has 8 bits for the position, 6 for n - 1)
 
 
+// a level-1 record into its slot: C1 (1-word keys without ordinals) the 16-byte compact form of sdt_sk_record1.h in ONE 16-byte store
+// (the slots of a chunk are 16-byte aligned: the read ordinal and the position of rec[0] are dropped), otherwise the record as it is
+template <int NW, bool C1> __device__ inline void sk_store_record1(uint64_t *recs, uint32_t chunk, uint32_t pos, const uint64_t (&rec)[SkFmt<NW>::REC_WORDS])
+{
+	if constexpr (C1) {
+		static_assert(NW == 1, "the compact level-1 record is the 1-word keys'");
+		uint64_t w0, w1;
+		sk_pack1(rec[0], rec[1], rec[2], SK_L2BITS, w0, w1);
+		*reinterpret_cast<ulonglong2 *>(recs + ((size_t)chunk * SK_CAP1 + pos) * SK_REC1C_WORDS) = make_ulonglong2(w0, w1);
+	} else {
+		sk_store_record<SkFmt<NW>::REC_WORDS>(recs + ((size_t)chunk * SK_CAP1 + pos) * SkFmt<NW>::REC_WORDS, rec);
+	}
+}
+
 // cut run [j0, j0 + n) of a read out of the tile and append the record to its level-1 bucket
-template <int NW>
+template <int NW, bool C1 = false>
 __device__ inline void sk_emit_run(const uint32_t *words, int rb_r, int len_r, int nk_r, int K, uint64_t read_ord, int j0, int n,
                                    uint32_t fb, unsigned long long *s_cur, unsigned long long *s_blk, const SkPool &pool,
                                    uint32_t *s_cnt, const Table<NW> &tbl, uint32_t &claimed, uint32_t &failed, uint32_t &done,
@@ -239,7 +253,7 @@ __device__ inline void sk_emit_run(const uint32_t *words, int rb_r, int len_r, i
 	if (sk_reserve(s_cur, s_blk, l1, l1, SK_CAP1, pool, s_cnt, chunk, pos)) {
 		const int len = hp + n + K - 1 + hn, ps = rb_r + j0 - hp;
 		uint64_t rec[RW];
-		rec[0] = sk_header(read_ord, (uint32_t)j0, l2, n, hp, hn);
+		rec[0] = C1 ? sk_rec1c_hdr(l2, n, hp, hn, SK_L2BITS) : sk_header(read_ord, (uint32_t)j0, l2, n, hp, hn);
 #pragma unroll
 		for (int k = 0; k < BW; k++) {
 			uint64_t wv = 0;
@@ -251,7 +265,7 @@ __device__ inline void sk_emit_run(const uint32_t *words, int rb_r, int len_r, i
 			}
 			rec[1 + k] = wv;
 		}
-		sk_store_record<RW>(pool.recs + ((size_t)chunk * SK_CAP1 + pos) * RW, rec);
+		sk_store_record1<NW, C1>(pool.recs, chunk, pos, rec);
 		emitted += (uint32_t)n;
 	} else if (!tbl.ent) {
 		// no chunk left and no table to fall back on (a sharded context: this rank does not own every key; the caller gets SDT_EFULL)
@@ -269,7 +283,8 @@ __device__ inline void sk_emit_run(const uint32_t *words, int rb_r, int len_r, i
 	}
 }
 
-template <int NW, int W>
+// C1: compact 16-byte level-1 records (1-word keys without ordinals, sdt_sk_record1.h; ncap is then sk_max_run1's)
+template <int NW, int W, bool C1 = false>
 __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_reads_seq(const uint32_t *__restrict__ packed, const uint64_t *__restrict__ offs,
                                                                       uint64_t nreads, int K, int m, int ncap, int max_tile_words, SkPool pool,
                                                                       unsigned long long *__restrict__ g_cursors, unsigned long long *__restrict__ g_blk,
@@ -349,7 +364,7 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 					if (nrun < SK_SEQ_RUNCAP)
 						runs[nrun] = (fb0 << 6) | (uint32_t)(j - j0 - 1);
 					else
-						sk_emit_run<NW>(words, rb_r, len_r, nk_r, K, read_ord, j0, j - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted);
+						sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, j0, j - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted);
 					nrun++;
 					j0 = j;
 					fb0 = fb;
@@ -387,7 +402,7 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 			if (nrun < SK_SEQ_RUNCAP)
 				runs[nrun] = (fb0 << 6) | (uint32_t)(nk_r - j0 - 1);
 			else
-				sk_emit_run<NW>(words, rb_r, len_r, nk_r, K, read_ord, j0, nk_r - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted);
+				sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, j0, nk_r - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted);
 			nrun++;
 		}
 		SK_TICK(1);
@@ -395,7 +410,7 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 		for (int k = 0, jr = 0; k < nlist; k++) {        // (the listed runs are the read's first ones, back to back from k-mer 0)
 			const uint32_t e = runs[k];
 			const int nr = (int)(e & 63u) + 1;
-			sk_emit_run<NW>(words, rb_r, len_r, nk_r, K, read_ord, jr, nr, e >> 6, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted);
+			sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, jr, nr, e >> 6, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted);
 			jr += nr;
 		}
 		__syncthreads();                             // the tile buffers are reused
@@ -442,21 +457,22 @@ struct SkSeqLaunch {
 	unsigned max_wgs;
 	int cu_count;
 	hipStream_t stream;
+	bool compact1;             // 1-word keys: 16-byte level-1 records (sdt_sk_record1.h)
 };
 
-template <int NW, int W> inline hipError_t sk_seq_launch_one(const SkSeqLaunch &a, const Table<NW> &tbl)
+template <int NW, int W, bool C1 = false> inline hipError_t sk_seq_launch_one(const SkSeqLaunch &a, const Table<NW> &tbl)
 {
 	const size_t smem = (size_t)SK_NB1 * 8 + (size_t)(SK_SEQ_TILE + 2) * 4 + (size_t)SK_SEQ_TILE * SK_SEQ_RUNCAP * 4 + (size_t)(LDS_LEAD + a.mtw) * 4;
-	hipError_t e = hipFuncSetAttribute((const void *)k_sk_scatter_reads_seq<NW, W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+	hipError_t e = hipFuncSetAttribute((const void *)k_sk_scatter_reads_seq<NW, W, C1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 	if (e != hipSuccess) return e;
 	int per_cu = 0;
-	e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sk_scatter_reads_seq<NW, W>, SK_SEQ_TILE, smem);
+	e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sk_scatter_reads_seq<NW, W, C1>, SK_SEQ_TILE, smem);
 	if (e != hipSuccess) return e;
 	uint64_t res = (uint64_t)(per_cu > 0 ? per_cu : 1) * (uint64_t)a.cu_count;
 	if (res > a.max_wgs) res = a.max_wgs;
 	const uint64_t nt = (a.nreads + SK_SEQ_TILE - 1) / SK_SEQ_TILE;
 	const unsigned grid = (unsigned)(nt < res ? nt : res);
-	hipLaunchKernelGGL((k_sk_scatter_reads_seq<NW, W>), dim3(grid), dim3(SK_SEQ_TILE), smem, a.stream, a.words, a.offs, a.nreads, a.K, a.m, a.ncap,
+	hipLaunchKernelGGL((k_sk_scatter_reads_seq<NW, W, C1>), dim3(grid), dim3(SK_SEQ_TILE), smem, a.stream, a.words, a.offs, a.nreads, a.K, a.m, a.ncap,
 	                   a.mtw, a.pool, a.cursors, a.blk, a.cnt, tbl, a.stats, a.ord_base, a.ord_stride);
 	return hipGetLastError();
 }

@@ -13,7 +13,8 @@
 // read as ONE record (a "super-k-mer"): 8 B of header + the run's bases with one base of context either side
 // (the prev / next neighbour codes of chopKmer4read, prlHashReads.c:215-230,275-308, are read off them).  That
 // is ~3 B per k-mer occurrence (24-byte records of ~8 k-mers at K = 31) instead of the 16-B (key, meta) record of the
-// per-k-mer exchange.
+// per-k-mer exchange.  (1-word keys without first-occurrence ordinals: 16-byte records at both levels -- nobody reads the ordinal and
+// the position of their header, sdt_sk_record1.h -- ~1.6 B per k-mer occurrence.)
 //
 //   k_sk_scatter_reads(_seq)  chop + minimizers per tile of reads in LDS (_seq: one lane walks one read, rolling m-mers and a
 //                        block sliding minimum; otherwise strips of 64 positions per wave), cut the runs, append each record to
@@ -21,7 +22,8 @@
 //                        workgroup owns one open chunk per bucket and reserves slots with LDS atomics, so the
 //                        only global atomic is the pool bump once per 128 chunks.
 //   k_sk_scatter_records level 2: every level-1 bucket is split 1024 ways the same way (records only move; 1-word keys without
-//                        ordinals: packed to 16 bytes on the way, sdt_sk_record2.h -- a group of four is one aligned 64-byte block).
+//                        ordinals: 16 bytes in, the level-2 bucket cleared, 16 bytes out, sdt_sk_record1.h / sdt_sk_record2.h -- a
+//                        group of four is one aligned 64-byte block).
 //   k_sk_count           one workgroup per final bucket (2^18): records -> LDS -> k-mers -> an LDS hash table
 //                        whose entries have the layout of the node table's (key, val); LDS atomics do the
 //                        counting (wave64, 4096 slots); at the end every LDS entry is merged into the node table
@@ -35,6 +37,7 @@
 #include "sdt_minimizer.cuh"
 #include "sdt_table.cuh"
 #include "sdt_sk_record2.h"      // sk_max_run, the compact level-2 record of 1-word keys (plain C++: also tested on the CPU)
+#include "sdt_sk_record1.h"      // ... and their compact level-1 record: the level-2 record + the level-2 bucket, 16 bytes as well
 
 namespace sdt {
 
@@ -53,6 +56,8 @@ constexpr uint32_t SK_NOCHUNK = 0xFFFFFFFFu;
 //   [1..] the bases [first k-mer - has_prev, last k-mer + K + has_next), 2 bits each, first base in the MOST
 //         significant pair of word 1 (the packed-read convention of include/sdt_gpu.h), zero padded
 // (the level-1 bucket of a record is where it lies; the level-2 bucket rides in the header: 24 / 40 / 56 bytes per record)
+// 1-word keys without ordinals do not use this layout at level 1 either: their level-1 record is the 16-byte compact form of
+// sdt_sk_record1.h (bases, then the low 8 + SK_L2BITS bits of this header), a chunk of 32 is 512 bytes of whole 64-byte blocks.
 template <int NW> struct SkFmt {
 	static constexpr int BW = NW == 1 ? 2 : (NW == 2 ? 4 : 6);     // base words: 64 / 128 / 192 bases
 	static constexpr int REC_WORDS = 1 + BW;                       // 24 / 40 / 56 bytes
@@ -75,6 +80,8 @@ constexpr uint64_t SK_MAX_READ_ORDINAL = 1ULL << 34;             // reads of one
 constexpr int SK_MAX_READ_LEN = (1 << SK_POSBITS) - 1;                            // positions the header can hold
 
 __host__ __device__ inline int sk_rec_words(int nw) { return nw == 1 ? 3 : (nw == 2 ? 5 : 7); }
+// words per slot of a level-1 chunk
+__host__ __device__ inline int sk_rec1_stride(int nw, bool compact1) { return compact1 ? SK_REC1C_WORDS : sk_rec_words(nw); }
 // words per slot of a level-2 chunk
 __host__ __device__ inline int sk_rec2_stride(int nw, bool compact)
 {
@@ -115,7 +122,7 @@ constexpr uint32_t SK_HDR_KIND_MASK = (1u << (8 + SK_L2BITS)) - 1u;     // bucke
 struct SkItem { uint32_t b1, c0, c1, pad; };      // level 2: one work item = a run [c0, c1) of the chunk list of ONE level-1 bucket
 constexpr int SK_TILE_READS = 32;                // reads per tile of k_sk_scatter_reads (half of k_count_reads': LDS for 6 workgroups per CU)
 struct SkPool {
-	uint64_t *recs;            // chunks * cap * REC_WORDS words
+	uint64_t *recs;            // chunks * cap * words per slot (level 1: sk_rec1_stride, level 2: sk_rec2_stride)
 	uint32_t *meta;            // per chunk: bucket (24 bits) | records in use << 24
 	uint32_t *next;            // bump allocator: chunks handed out
 	uint32_t chunks;           // capacity

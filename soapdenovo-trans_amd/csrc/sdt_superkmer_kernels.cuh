@@ -77,7 +77,9 @@ constexpr int SK_LIST2_FILL_SHIFT = SK_CAP2 == 16 ? 28 : 27;           // list2 
                                         // many instantiations are compiled in translation units of their own)
 
 // ---- level 1: reads -> super-k-mer records in 256 buckets ----------------------------------------------------
-template <int NW>
+// Full records are cut at multiples of ncap in the read -- any ncap: the compact level-1 record's cap (C1, sdt_sk_record1.h) is
+// no power of two above K = 22, and its pow2 floor would halve the records of K = 23..27 (32 -> 16).
+template <int NW, bool C1 = false>
 __global__ __launch_bounds__(TPB) void k_sk_scatter_reads(const uint32_t *__restrict__ packed, const uint64_t *__restrict__ offs,
                                                           uint64_t nreads, int K, int m, int ncap, int max_tile_words,
                                                           int tile_smem_words, int hv_words, int hv2_words, int bits_words, SkPool pool,
@@ -104,6 +106,13 @@ __global__ __launch_bounds__(TPB) void k_sk_scatter_reads(const uint32_t *__rest
 	const int w = K - m + 1;                         // m-mers per k-mer
 	const uint64_t ntiles = (nreads + SK_TILE_READS - 1) / SK_TILE_READS;
 	uint32_t claimed = 0, failed = 0, done = 0, emitted = 0;
+	// k-mer j of a read starts a full record's successor: j is a multiple of ncap -- a mask where ncap is a power of two, otherwise
+	// j - (j / ncap) * ncap with the quotient as the high word of j * ceil(2^32 / ncap): exact while j * ncap < 2^32 (j < 2^12: SK_MAX_READ_LEN)
+	const bool cap_pow2 = (ncap & (ncap - 1)) == 0;
+	const uint32_t cap_inv = cap_pow2 ? 0u : 0xFFFFFFFFu / (uint32_t)ncap + 1u;
+	auto at_cap = [&](int j) -> bool {
+		return cap_pow2 ? (j & (ncap - 1)) == 0 : (uint32_t)j - __umulhi((uint32_t)j, cap_inv) * (uint32_t)ncap == 0u;
+	};
 #ifdef SDT_SK_TICKS
 	unsigned long long cyc[4] = {0, 0, 0, 0}, t0 = wall_clock64(), t1;
 #define SK_TICK(i) do { t1 = wall_clock64(); cyc[i] += t1 - t0; t0 = t1; } while (0)
@@ -146,7 +155,7 @@ __global__ __launch_bounds__(TPB) void k_sk_scatter_reads(const uint32_t *__rest
 					const bool kv = lane >= 1 && lane <= valid && j < nk_r;
 					if (kv)
 						s_hv[p] = bh;
-					const bool start = kv && (j == 0 || (j & (ncap - 1)) == 0 || sk_final_bucket(bh) != sk_final_bucket(pbh));
+					const bool start = kv && (j == 0 || at_cap(j) || sk_final_bucket(bh) != sk_final_bucket(pbh));
 					const unsigned long long mask = __ballot(start) >> 1;         // bit i: k-mer j0 + i of the read
 					if (lane == 0 && mask) {
 						const uint32_t q0 = tv.pre[r] + (uint32_t)j0, sh = q0 & 63u;
@@ -190,7 +199,7 @@ __global__ __launch_bounds__(TPB) void k_sk_scatter_reads(const uint32_t *__rest
 					const int r = tile_find_read(tv.pre, q);
 					const int j = (int)(q - tv.pre[r]);
 					const int p = (int)tv.rb[r] + j;
-					if (j == 0 || (j & (ncap - 1)) == 0) {    // ncap is a power of two
+					if (j == 0 || at_cap(j)) {
 						start = true;
 					} else {
 						start = sk_final_bucket(bhs[p]) != sk_final_bucket(bhs[p - 1]);
@@ -260,7 +269,7 @@ __global__ __launch_bounds__(TPB) void k_sk_scatter_reads(const uint32_t *__rest
 			if (sk_reserve(s_cur, &s_blk, sk_l1_bucket(bh), sk_l1_bucket(bh), SK_CAP1, pool, s_cnt, chunk, pos)) {
 				const int len = hp + n + K - 1 + hn, ps = p0 - hp;
 				uint64_t rec[RW];
-				rec[0] = sk_header(read_ord, (uint32_t)j, sk_l2_bucket(bh), n, hp, hn);
+				rec[0] = C1 ? sk_rec1c_hdr(sk_l2_bucket(bh), n, hp, hn, SK_L2BITS) : sk_header(read_ord, (uint32_t)j, sk_l2_bucket(bh), n, hp, hn);
 #pragma unroll
 				for (int k = 0; k < BW; k++) {
 					uint64_t wv = 0;
@@ -272,7 +281,7 @@ __global__ __launch_bounds__(TPB) void k_sk_scatter_reads(const uint32_t *__rest
 					}
 					rec[1 + k] = wv;
 				}
-				sk_store_record<RW>(pool.recs + ((size_t)chunk * SK_CAP1 + pos) * RW, rec);
+				sk_store_record1<NW, C1>(pool.recs, chunk, pos, rec);
 				emitted += (uint32_t)n;
 			} else if (!tbl.ent) {
 				failed += (uint32_t)n;                   // (a sharded context has no table to fall back on: sk_emit_run)
@@ -471,6 +480,10 @@ template <int NW, bool COMPACT = false> struct SkL2Stage {
 	static constexpr int S = NW == 1 ? SDT_SK_L2S_S1 : 2;            // records per group
 	static constexpr int GPC = SK_CAP2 / S;                          // groups per chunk
 	static constexpr int RPL = NW == 1 ? SDT_SK_L2S_RPL : (NW == 2 ? (SDT_SK_L2S_RPL < 2 ? SDT_SK_L2S_RPL : 2) : 1);      // records per lane and round
+	// COMPACT records come in compact too (sdt_sk_record1.h: the level-2 record + the level-2 bucket, 16 bytes) unless the A/B build
+	// SDT_SK_COMPACT1=0 keeps the 24-byte level-1 records, which are then packed here
+	static constexpr bool C1 = COMPACT && SDT_SK_COMPACT1;
+	static constexpr int RW1 = C1 ? SK_REC1C_WORDS : SkFmt<NW>::REC_WORDS;                  // words per slot of a level-1 chunk
 	static constexpr int RWS = COMPACT ? SK_REC2C_WORDS : SkFmt<NW>::REC_WORDS;             // words of a record in the stage
 	static constexpr int RW2 = COMPACT ? SK_REC2C_WORDS : SkFmt<NW>::REC2_STRIDE;           // words per slot of a level-2 chunk
 	static constexpr size_t SMEM = (size_t)SK_NB2 * S * RWS * 8;
@@ -483,6 +496,18 @@ template <int NW, bool COMPACT> __device__ inline void sk_store_staged(uint64_t 
 		*reinterpret_cast<ulonglong2 *>(dst) = make_ulonglong2(rec[0], rec[1]);
 	else
 		sk_store_record2<NW>(dst, rec);
+}
+
+// a record out of its slot of a level-1 chunk: the compact form (16-byte aligned slots) in ONE 16-byte load
+template <int RW1, bool C1> __device__ inline void sk_load_record1(const uint64_t *src, uint64_t (&rec)[RW1])
+{
+	if constexpr (C1) {
+		const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(src);
+		rec[0] = v.x;
+		rec[1] = v.y;
+	} else {
+		sk_load_record<RW1>(src, rec);
+	}
 }
 
 // The round loop waits for memory ONCE, at its top.  One workgroup of 16 waves runs per CU and nothing else is resident to hide a
@@ -498,7 +523,8 @@ __global__ __launch_bounds__(SK_L2S_TPB, SDT_SK_L2S_WGS) void k_sk_scatter_recor
                                                                          uint32_t *__restrict__ g_cnt, unsigned long long *__restrict__ g_kmers, Stats *stats)
 {
 	using L2 = SkL2Stage<NW, COMPACT>;
-	constexpr int RW = SkFmt<NW>::REC_WORDS, RWS = L2::RWS, RW2 = L2::RW2, S = L2::S, GPC = L2::GPC;
+	constexpr int RW = L2::RW1, RWS = L2::RWS, RW2 = L2::RW2, S = L2::S, GPC = L2::GPC;      // (RW: words of a record as it comes in)
+	constexpr bool C1 = L2::C1;
 	constexpr int CPT = SK_L2S_TPB / SK_CAP1;         // chunks per sweep
 	constexpr int D = L2::RPL;                       // sweeps (records per lane) per round
 	extern __shared__ __attribute__((aligned(16))) unsigned long long s_stage[];  // SK_NB2 x S records
@@ -556,7 +582,7 @@ __global__ __launch_bounds__(SK_L2S_TPB, SDT_SK_L2S_WGS) void k_sk_scatter_recor
 			const uint32_t ca = cfirst + (uint32_t)d * CPT;
 			const uint32_t id = ca < it.c1 ? id_a[d] : 0u;
 			meta_a[d] = src.meta[id];
-			sk_load_record<RW>(src.recs + ((size_t)id * SK_CAP1 + slot) * RW, rec_a[d]);
+			sk_load_record1<RW, C1>(src.recs + ((size_t)id * SK_CAP1 + slot) * RW, rec_a[d]);
 		}
 	}
 	// (the rounds are uniform: every lane of the workgroup runs the same number of them, barriers included)
@@ -579,9 +605,11 @@ __global__ __launch_bounds__(SK_L2S_TPB, SDT_SK_L2S_WGS) void k_sk_scatter_recor
 #pragma unroll
 		for (int d = 0; d < D; d++) {
 			const uint32_t ci = cfirst + (sw + (uint32_t)d) * CPT;
-			hdr[d] = rec_a[d][0];
+			hdr[d] = rec_a[d][C1 ? 1 : 0];               // the word that holds the level-2 bucket and n
 			fill[d] = ci < it.c1 ? meta_a[d] >> 24 : 0u;
-			if constexpr (COMPACT) {
+			if constexpr (C1) {
+				sk_rec1c_to_rec2c(rec_a[d][0], rec_a[d][1], SK_L2BITS, rec[d][0], rec[d][1]);
+			} else if constexpr (COMPACT) {
 				sk_pack2(rec_a[d][0], rec_a[d][1], rec_a[d][2], rec[d][0], rec[d][1]);
 			} else {
 #pragma unroll
@@ -597,7 +625,7 @@ __global__ __launch_bounds__(SK_L2S_TPB, SDT_SK_L2S_WGS) void k_sk_scatter_recor
 			const uint32_t id = c1n < it.c1 ? id_b[d] : 0u;
 			id_b[d] = list1[c2n < it.c1 ? c2n : it.c0];
 			meta_a[d] = src.meta[id];
-			sk_load_record<RW>(src.recs + ((size_t)id * SK_CAP1 + slot) * RW, rec_a[d]);
+			sk_load_record1<RW, C1>(src.recs + ((size_t)id * SK_CAP1 + slot) * RW, rec_a[d]);
 		}
 #pragma unroll
 		for (int d = 0; d < D; d++) {
@@ -606,9 +634,9 @@ __global__ __launch_bounds__(SK_L2S_TPB, SDT_SK_L2S_WGS) void k_sk_scatter_recor
 			b2[d] = 0;
 			t[d] = 0;
 			if (valid[d]) {
-				b2[d] = sk_hdr_l2(hdr[d]);
+				b2[d] = C1 ? sk_rec1c_l2(hdr[d], SK_L2BITS) : sk_hdr_l2(hdr[d]);
 				t[d] = atomicAdd(&s_cnt[b2[d]], 1u);
-				atomicAdd(&s_kc[b2[d]], (uint32_t)sk_hdr_n(hdr[d]));
+				atomicAdd(&s_kc[b2[d]], (uint32_t)(C1 ? sk_rec1c_n(hdr[d]) : sk_hdr_n(hdr[d])));
 			}
 		}
 		__syncthreads();
