@@ -860,7 +860,65 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  * Out of scope: sliding-window cuts; per-end thresholds; masking bases; qualities carried through later stages or written out (the
  * outputs stay FASTA like every other stage's); a kept form (the reads kept in HBM carry no qualities, and sdt_gpu_keep_reads is
  * not changed); pair-aware decisions (mates are judged independently; the command line routes the survivors); any change to another
- * stage. */
+ * stage.
+ *
+ * Reads screened against reference sequences one already knows: ribosomal RNA, the PhiX spike-in, a mitochondrial genome, vectors or a
+ * host.  Their k-mers are the most abundant solid k-mers of the table, so correct_reads and trim_reads leave them alone, select_reads
+ * spends its budget on them and they make the deepest buckets of pass 1.  The stage drops the reads that hit a reference, or, as a
+ * bait, keeps only those.  It needs NO counted table and has a k of its own: a small hash set on the device, canonical k-mer ->
+ * reference, loaded once and kept by the context.  ... -> clip -> compact -> screen -> compact -> complexity -> dedup -> count goes
+ * without a copy to the host.  Added without a change of SDT_ABI_VERSION: the seven calls and the two structs are additions.
+ *     Integers only.  Every unit is decided on its own.  The result does not depend on the launch geometry, on any hash function or on
+ *     where a read starts in its word.  Bases are the stream's codes (A 0, C 1, T 2, G 3), the complement is x ^ 2, and the canonical
+ *     form of a k-mer is the smaller of itself and its reverse complement as a right-aligned integer.  11 <= k <= 31, even k included.
+ *     SET.     nseqs sequences packed like reads (16 bases per word, the first in the most significant pair, offsets[nseqs + 1] in
+ *              bases, the pad words of sdt_gpu_push_reads behind them), sequence i with ref_of_seq[i] < n_refs.  Several sequences may
+ *              carry one reference: the caller cuts a reference at every letter that is not A, C, G or T, so that no k-mer spans one.
+ *              A sequence of fewer than k bases contributes nothing; a sequence has NO length limit.  The set is the set of the
+ *              canonical k-mers of all sequences; ref(x) of a k-mer x of the set is the SMALLEST ref_of_seq among the sequences that
+ *              hold x or its reverse complement: references listed first win.  The set is a pure function of the input, not of the
+ *              order of the sequences.
+ *     READ.    L bases: kmers = max(L - k + 1, 0); hits = the positions whose canonical k-mer is in the set; ref = the smallest ref(x)
+ *              over the hits, 0xFFFFFFFF without one.  MATCHED iff hits >= max(min_hits, 1) and 100 hits >= min_hit_pct kmers (in 64
+ *              bits).  A read and its reverse complement get the same kmers, hits, ref and state.
+ *     UNIT.    A read, or under paired != 0 the mates 2t and 2t + 1 (an odd nreads is SDT_EINVAL).  A unit is matched iff one of its
+ *              reads is.  flags = 0: a matched unit is dropped; SDT_SCREEN_KEEP_MATCHED: an unmatched unit is dropped.  Every read of
+ *              a unit gets the unit's verdict, 0 kept or 1 dropped, and keeps its own kmers, hits and ref.
+ *     RECORD.  sdt_read_screen: kmers, hits, ref; start = 0, len = L if kept, else 0; start, len and verdict sit where sdt_read_trim
+ *              has them, so both compaction calls take the records through a pointer cast, and keep[i] = (verdict == 0) is what
+ *              sdt_gpu_compact_reads_device takes.
+ *     An N inside a read is a G in the stream, as everywhere else.  The default of the command line, k = 31, is bbduk's usual figure:
+ *     a choice, not a measurement.
+ *   screen_load:    builds the set on the device and waits for it; *n_kmers (may be NULL) = its distinct k-mers.  The set belongs to
+ *                   the context, of any kind and in any state (it needs the stream only): sdt_gpu_destroy frees it, sdt_gpu_reset and
+ *                   the counting calls do not touch it.  A second load replaces it, but only once the new one is complete.  SDT_EINVAL
+ *                   with the previous set kept: k outside 11 .. 31; n_refs = 0 or a ref_of_seq >= n_refs; offsets that are not
+ *                   monotonic or packed_words too short (as for reads); a set without a single k-mer.  SDT_ENOMEM also leaves the
+ *                   previous set.
+ *   screen_unload:  frees the set (SDT_OK without one).
+ *   screen_info:    info = { k, n_refs, distinct k-mers, slots of the table }, all 0 without a set.
+ *   screen_lookup:  refs[i] = ref(keys[i]) for right-aligned k-mers of either strand, 0xFFFFFFFF: absent (also for a key of more than
+ *                   2 k bits).  n == 0: SDT_OK.
+ *   screen_reads:   out[i] for read i of a host batch; keep (may be NULL); *n_kept = reads kept.  The batch is staged in pieces as for
+ *                   profile_reads, mates in one piece.
+ *   screen_reads_device: buffers already on the device (d_out nreads records of 24 bytes, d_keep nreads bytes or NULL).  The call
+ *                   waits for the kernel to know *n_kept.
+ *   screen_kept_reads: the reads kept in HBM, in every respect like sdt_gpu_dedup_kept_reads: records by READ ORDINAL, pair_ranges
+ *                   with the meaning and the checks of select_kept_reads, mates may sit in different kept batches, a pair with one
+ *                   mate kept is a single-read unit, SDT_EFULL (nothing written) when a kept read's ordinal is >= out_capacity,
+ *                   SDT_ESTATE without kept reads or while pushed batches are not drained.  Records of ordinals that no kept read has
+ *                   are left untouched.  The kept reads are NOT changed.
+ * State: screening or looking up without a set is SDT_ESTATE.  nreads == 0: SDT_OK, nothing touched, whatever the rest says.  There is
+ * NO limit on the read length in any form: a wavefront walks a unit 64 k-mer positions at a time (kmers, hits and len are 32-bit).
+ * SDT_EINVAL, from a check on the host before any launch, with a message that names the field and its value: NULL params;
+ * min_hit_pct > 100; a flag other than SDT_SCREEN_KEEP_MATCHED; reserved != 0; an odd nreads under paired.
+ * Device memory: the set is 16 B per slot, slots = the power of two >= 2 x the k-mer positions of the set (1 024 at least); during a
+ * load also the staged sequences, their offsets and 4 B per sequence, and the previous set until the new one is complete.  A call:
+ *     device form       8 B (the counter of the reads kept)
+ *     host form         the piece of the stream that is staged, and 24 B + 1 B per read of it for records and keep
+ *     kept form         the 24 B records of the largest kept batch (the unit verdicts are taken on the host)
+ * Out of scope: Hamming-distance or IUPAC matching; masking the matching bases instead of dropping the read; attribution by majority
+ * vote; k above 31; sets larger than device memory; any change to another stage. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -885,6 +943,10 @@ typedef struct { uint32_t max_score_pct, max_low_pct, min_len, flags; } sdt_comp
 #define SDT_COMPLEXITY_TRIM 1u  /* sdt_complexity_params.flags: keep the longest clean stretch instead of judging the whole read */
 typedef struct { uint32_t span, low, ee_ppm, start, len, verdict; } sdt_read_quality;   /* 24 bytes */
 typedef struct { uint32_t phred_offset, cut_q, low_q, max_low_pct, max_ee_ppm, min_len, flags, reserved; } sdt_quality_params;
+typedef struct { uint32_t kmers, hits, ref, start, len, verdict; } sdt_read_screen;   /* 24 bytes */
+typedef struct { uint32_t min_hits, min_hit_pct, flags, reserved; } sdt_screen_params;
+#define SDT_SCREEN_KEEP_MATCHED 1u  /* sdt_screen_params.flags: bait mode, the unmatched units are dropped */
+#define SDT_SCREEN_NO_REF 0xFFFFFFFFu /* sdt_read_screen.ref / screen_lookup: no reference */
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -968,6 +1030,18 @@ int sdt_gpu_quality_reads(sdt_ctx *ctx, const uint8_t *quals, uint64_t nbytes, c
                           const sdt_quality_params *params, sdt_read_quality *out, uint8_t *keep, uint64_t *n_kept);
 int sdt_gpu_quality_reads_device(sdt_ctx *ctx, const void *d_quals, const void *d_offsets, uint64_t nreads,
                                  const sdt_quality_params *params, void *d_out, void *d_keep, uint64_t *n_kept);
+int sdt_gpu_screen_load(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets, uint64_t nseqs,
+                        const uint32_t *ref_of_seq, uint32_t n_refs, uint32_t k, uint64_t *n_kmers);
+int sdt_gpu_screen_unload(sdt_ctx *ctx);
+int sdt_gpu_screen_info(const sdt_ctx *ctx, uint64_t info[4]);
+int sdt_gpu_screen_lookup(sdt_ctx *ctx, const uint64_t *keys, uint64_t n, uint32_t *refs);
+int sdt_gpu_screen_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                         uint64_t nreads, int paired, const sdt_screen_params *params, sdt_read_screen *out, uint8_t *keep,
+                         uint64_t *n_kept);
+int sdt_gpu_screen_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads, int paired,
+                                const sdt_screen_params *params, void *d_out, void *d_keep, uint64_t *n_kept);
+int sdt_gpu_screen_kept_reads(sdt_ctx *ctx, const sdt_screen_params *params, const uint64_t *pair_ranges, uint64_t n_ranges,
+                              sdt_read_screen *out, uint64_t out_capacity, uint64_t *nreads, uint64_t *n_kept);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

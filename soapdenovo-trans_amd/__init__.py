@@ -178,6 +178,17 @@ _ABI = [
                                          _c.c_void_p, _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_quality_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                                 _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_screen_load", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint32, _c.c_uint32,
+                                       _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_screen_unload", _c.c_int, [_c.c_void_p]),
+    ("sdt_gpu_screen_info", _c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_screen_lookup", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
+    ("sdt_gpu_screen_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                        _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_screen_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                               _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_screen_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64,
+                                             _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -216,6 +227,12 @@ SDT_COMPLEXITY_TRIM = 1
 # low_q, its expected errors per million bases; the kept bases are [start, start + len) of the read, where READ_TRIM_DTYPE has them
 READ_QUALITY_DTYPE = np.dtype([(f, np.uint32) for f in ("span", "low", "ee_ppm", "start", "len", "verdict")])
 QUALITY_WHOLE, QUALITY_CLIPPED, QUALITY_DROPPED = 0, 2, 3
+# sdt_read_screen (include/sdt_gpu.h): one record per read of a reference screen; its k-mers, those of them in the set, the smallest
+# reference among them (SCREEN_NO_REF: none); len = the read's bases if kept, else 0, where READ_TRIM_DTYPE has it; verdict 0 kept, 1 dropped
+READ_SCREEN_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "hits", "ref", "start", "len", "verdict")])
+SCREEN_KEPT, SCREEN_DROPPED = range(2)
+SCREEN_KEEP_MATCHED = 1                                  # SDT_SCREEN_KEEP_MATCHED
+SCREEN_NO_REF = 0xFFFFFFFF
 
 
 class NormParams(_c.Structure):
@@ -261,6 +278,14 @@ class QualityParams(_c.Structure):
 
     def __init__(self, phred_offset=33, cut_q=20, low_q=15, max_low_pct=40, max_ee_ppm=0, min_len=0, flags=0, reserved=0):
         super().__init__(phred_offset, cut_q, low_q, max_low_pct, max_ee_ppm, min_len, flags, reserved)
+
+
+class ScreenParams(_c.Structure):
+    """sdt_screen_params; the defaults of `sdt-kmers screen`"""
+    _fields_ = [(f, _c.c_uint32) for f in ("min_hits", "min_hit_pct", "flags", "reserved")]
+
+    def __init__(self, min_hits=1, min_hit_pct=0, flags=0, reserved=0):
+        super().__init__(min_hits, min_hit_pct, flags, reserved)
 
 
 class AdapterSet(_c.Structure):
@@ -1090,6 +1115,75 @@ class PregraphGPU:
         self._check(self.lib.sdt_gpu_quality_reads_device(self._ctx, _ptr(d_quals), _ptr(d_offsets), nreads, ctypes.addressof(prm), _ptr(d_out),
                                                           _ptr(d_keep), ctypes.byref(kept)))
         return kept.value
+
+    # -- reads screened against reference sequences (rRNA, PhiX, ...); a k-mer set of its own, no counted table (the rule: include/sdt_gpu.h)
+    @staticmethod
+    def _screen_params(params):
+        """params: ScreenParams or its fields as a dict"""
+        return params if isinstance(params, ScreenParams) else ScreenParams(**(params or {}))
+
+    def screen_load(self, words, offsets, ref_of_seq, n_refs: int, k: int = 31) -> int:
+        """sequences packed like reads (with the pad words), ref_of_seq[i] < n_refs -> the distinct k-mers of the set"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ref_of_seq = np.ascontiguousarray(ref_of_seq, dtype=np.uint32)
+        assert len(ref_of_seq) == len(offsets) - 1
+        n = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_screen_load(self._ctx, _ptr(words), words.size, _ptr(offsets), len(offsets) - 1, _ptr(ref_of_seq), n_refs, k,
+                                                 ctypes.byref(n)))
+        return n.value
+
+    def screen_unload(self):
+        self._check(self.lib.sdt_gpu_screen_unload(self._ctx))
+
+    def screen_info(self):
+        """-> (k, n_refs, distinct k-mers, slots); all 0 without a set"""
+        info = (ctypes.c_uint64 * 4)()
+        self._check(self.lib.sdt_gpu_screen_info(self._ctx, info))
+        return tuple(int(v) for v in info)
+
+    def screen_lookup(self, keys) -> np.ndarray:
+        """right-aligned k-mers of either strand -> uint32[n]: the smallest reference that holds each, SCREEN_NO_REF: absent"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        refs = np.zeros(keys.size, dtype=np.uint32)
+        self._check(self.lib.sdt_gpu_screen_lookup(self._ctx, _ptr(keys), keys.size, _ptr(refs)))
+        return refs
+
+    def screen_reads(self, words, offsets, paired: bool = False, params=None):
+        """-> (READ_SCREEN_DTYPE[nreads]: kmers, hits, ref, start, len, verdict; keep uint8[nreads]; reads kept)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        out = np.zeros(n, dtype=READ_SCREEN_DTYPE)
+        keep = np.zeros(n, dtype=np.uint8)
+        prm = self._screen_params(params)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_screen_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, int(bool(paired)), ctypes.addressof(prm),
+                                                  _ptr(out), _ptr(keep), ctypes.byref(kept)))
+        return out, keep, kept.value
+
+    def screen_reads_device(self, d_words, d_offsets, nreads: int, d_out, d_keep=None, paired: bool = False, params=None) -> int:
+        """device buffers; d_out holds nreads records of 24 bytes (what compact_trimmed_device takes), d_keep (optional) nreads bytes
+        (what compact_reads_device takes) -> reads kept (waits for the kernel)"""
+        prm = self._screen_params(params)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_screen_reads_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, int(bool(paired)), ctypes.addressof(prm),
+                                                         _ptr(d_out), _ptr(d_keep), ctypes.byref(kept)))
+        return kept.value
+
+    def screen_kept_reads(self, total_reads: int, pair_ranges=(), params=None, out: np.ndarray = None):
+        """the reads kept in HBM; pair_ranges: [first, end) of ordinals that hold interleaved pairs, flat or as rows
+        -> (READ_SCREEN_DTYPE[total_reads] by read ordinal, reads decided, reads kept)"""
+        if out is None:
+            out = np.zeros(total_reads, dtype=READ_SCREEN_DTYPE)
+        assert out.dtype == READ_SCREEN_DTYPE and out.flags.c_contiguous and len(out) >= total_reads
+        ranges = np.ascontiguousarray(np.asarray(pair_ranges, dtype=np.uint64).reshape(-1))
+        assert ranges.size % 2 == 0
+        prm = self._screen_params(params)
+        n, kept = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_screen_kept_reads(self._ctx, ctypes.addressof(prm), _ptr(ranges) if ranges.size else None, ranges.size // 2,
+                                                       _ptr(out), total_reads, ctypes.byref(n), ctypes.byref(kept)))
+        return out, n.value, kept.value
 
     def set_read_ordinal(self, base: int, stride: int = 1):
         self._check(self.lib.sdt_gpu_set_read_ordinal(self._ctx, base, stride))

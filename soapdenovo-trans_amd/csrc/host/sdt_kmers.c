@@ -72,6 +72,15 @@
  *       prefix.qtrim.pairs.fa / prefix.qtrim.single.fa: the kept bases of the surviving reads, as clip writes them
  *       prefix.lenHist: per kept length that occurs, ascending:  len reads,  then
  *           # reads R whole W clipped C dropped D short S low V errors X bases_in I bases_out O
+ *   sdt-kmers screen -s lib.cfg -K k [-p threads] -r refs.fa [-r more.fa ...] [--screen-k S, default 31] [--min-hits N, default 1]
+ *                    [--min-hit-pct P, default 0] [--keep-matched] -o prefix
+ *       reads that share k-mers of S bases with reference sequences (rRNA, PhiX, a mitochondrial genome, vectors) dropped, or with
+ *       --keep-matched kept alone (sdt_gpu_screen_load, sdt_gpu_screen_kept_reads; the rule: include/sdt_gpu.h).  The reference files
+ *       are FASTA, read and checked before the device is touched; a letter other than ACGT cuts a reference, references listed first
+ *       win a shared k-mer.  The two mates of a pair are decided together; pairs as for normalize, routing as for clip (screensplit.c)
+ *       prefix.readScreen: one line per read in stream order:  kmers hits ref verdict   (ref 1-based in the order of the files, 0 none)
+ *       prefix.screen.pairs.fa / prefix.screen.single.fa: the surviving reads, as clip writes them
+ *       prefix.screenStats: per reference  index name bases reads hits,  then  # reads R matched M kept K dropped D
  *
  * The query file is read and checked before the device is touched. */
 #include <errno.h>
@@ -91,6 +100,7 @@
 #include "overlapsplit.h"
 #include "cxsplit.h"
 #include "qualsplit.h"
+#include "screensplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -190,6 +200,20 @@ static void usage(void)
 	        "              len reads; then: # reads R whole W clipped C dropped D short S low V errors X bases_in I bases_out O, where\n"
 	        "              S, V and X are the dropped reads by the line that dropped them)\n"
 	        "           Pairs are the reads of q1=/q2= files, mates are judged independently, as for clip.\n"
+	        "       sdt-kmers screen -s lib.cfg -K k [-p threads] -r refs.fa [-r more.fa ...] [--screen-k S, default 31]\n"
+	        "                        [--min-hits N, default 1] [--min-hit-pct P, default 0] [--keep-matched] -o prefix\n"
+	        "           reads that come from sequences one already knows (ribosomal RNA, the PhiX spike-in, a mitochondrial genome, vectors)\n"
+	        "           are taken out: the references (FASTA files, any length; a letter other than ACGT cuts a reference) become a set of\n"
+	        "           canonical k-mers of S bases (11 to 31; -K is only the k of the counting context), and a read is matched if N or more\n"
+	        "           of its k-mers, and P percent or more of them, are in the set.  A read, or the two mates of a pair, is dropped if it is\n"
+	        "           matched; --keep-matched keeps the matched ones instead (bait).  A k-mer that several references hold counts for the\n"
+	        "           one listed first.  S = 31 is the usual figure of bbduk: a choice, not a measurement.  An N in a read is a G.\n"
+	        "           Needs no counted k-mers: run it after clip and in front of complexity and dedup.\n"
+	        "           -> prefix.readScreen (per read in stream order: kmers hits ref verdict; ref = the reference of the read's hits that is\n"
+	        "              listed first, 1-based, 0 none; verdict 0 kept, 1 dropped), prefix.screen.pairs.fa (read 1 then read 2 of the pairs\n"
+	        "              that survive), prefix.screen.single.fa (every other surviving read), prefix.screenStats (per reference: index name\n"
+	        "              bases reads hits, reads = the reads whose ref it is, hits = their hits; then: # reads R matched M kept K dropped D)\n"
+	        "           Pairs are the reads of q1=/q2= and f1=/f2= files; the reads of a p= file are single reads, as for normalize.\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -843,6 +867,77 @@ static int complexity_and_write(sdt_ctx *gpu, unsigned long long reads, const sd
 	return 0;
 }
 
+/* `screen`: the references into the device's set, the records from the device, the kept batches back from HBM, every surviving read
+ * into the pairs file (both mates of a pair) or the singles file, routed as clip routes them; the statistics (screensplit.c) */
+static int screen_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_screen_params *prm, uint32_t k, const sdt_ref_set *refs,
+                            const sdt_pair_ranges *pairs, const char *prefix)
+{
+	uint64_t distinct = 0;
+	if (sdt_gpu_screen_load(gpu, refs->words, refs->nwords, refs->offsets, refs->nseqs, refs->ref_of_seq, refs->n_refs, k, &distinct) != SDT_OK) {
+		fprintf(stderr, "sdt_gpu_screen_load: %s\n", sdt_gpu_last_error());
+		return 1;
+	}
+	const uint64_t m = reads ? reads : 1;
+	sdt_read_screen *rec = (sdt_read_screen *)calloc(m, sizeof(sdt_read_screen));
+	sdt_screen_stats stats;
+	if (!rec || sdt_screen_stats_init(&stats, refs->n_refs) != 0) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	uint64_t got = 0, n_kept = 0;
+	if (sdt_gpu_screen_kept_reads(gpu, prm, pairs->v, pairs->n, rec, reads, &got, &n_kept) != SDT_OK) {
+		fprintf(stderr, "sdt_gpu_screen_kept_reads: %s\n", sdt_gpu_last_error());
+		return 1;
+	}
+	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu decided\n", reads, (unsigned long long)got); return 1; }
+	kept_reads kr;
+	if (kept_fetch(gpu, reads, &kr) != 0) return 1;
+	char path[4][4200];
+	snprintf(path[0], sizeof path[0], "%s.readScreen", prefix);
+	snprintf(path[1], sizeof path[1], "%s.screen.pairs.fa", prefix);
+	snprintf(path[2], sizeof path[2], "%s.screen.single.fa", prefix);
+	snprintf(path[3], sizeof path[3], "%s.screenStats", prefix);
+	outbuf orec, opair, osingle;
+	if (ob_open(&orec, path[0]) != 0) return 1;
+	if (ob_open(&opair, path[1]) != 0) { ob_close(&orec); return 1; }
+	if (ob_open(&osingle, path[2]) != 0) { ob_close(&orec); ob_close(&opair); return 1; }
+	unsigned long long kept = 0, bases_in = 0, bases_out = 0;
+	size_t cursor = 0;
+	int bad = 0;
+	for (uint64_t ord = 0; ord < reads; ord++) {
+		if (!orec.ok || !opair.ok || !osingle.ok) break;                               /* a write failed: ob_close says which */
+		if (kr.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
+		const sdt_read_screen *t = rec + ord;
+		const uint64_t start = kr.bo[kr.at_batch[ord]][kr.at_read[ord]], len = kr.bo[kr.at_batch[ord]][kr.at_read[ord] + 1] - start;
+		if (sdt_screen_stats_note(&stats, t, len, k, prm) != 0) {
+			fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->kmers, t->hits, t->ref,
+			        t->start, t->len, t->verdict, (unsigned long long)len);
+			bad = 1;
+			break;
+		}
+		ob_room(&orec, SDT_SCREEN_LINE_MAX);
+		orec.p = sdt_put_screen_line(orec.p, t);
+		bases_in += len;
+		/* (start and len sit where sdt_read_trim has them: screensplit.h) */
+		const int to = sdt_trim_route(pairs, &cursor, (const sdt_read_trim *)rec, reads, ord);
+		if (to == SDT_TRIM_TO_NONE) continue;
+		kept++;
+		bases_out += t->len;
+		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
+		ob_room(o, (size_t)t->len + 24);
+		o->p = sdt_put_fasta_record(o->p, ord, kr.bw[kr.at_batch[ord]], start, t->len);
+	}
+	const int all_written = orec.ok && opair.ok && osingle.ok;
+	if ((ob_close(&orec) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
+	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
+	FILE *fs = fopen(path[3], "w");
+	if (!fs || (sdt_screen_stats_write(fs, &stats, refs) != 0) | (fclose(fs) != 0)) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path[3]); return 1; }
+	printf("%llu reads against %llu k-mers of %u references: %llu matched, %llu kept, %llu dropped; %llu bases in, %llu bases out\n", reads,
+	       (unsigned long long)distinct, refs->n_refs, (unsigned long long)stats.matched, (unsigned long long)stats.kept, (unsigned long long)stats.dropped,
+	       bases_in, bases_out);
+	kept_free(&kr);
+	sdt_screen_stats_free(&stats);
+	free(rec);
+	return 0;
+}
+
 /* `qtrim`, while the reads stream: every FASTQ batch's qualities through sdt_gpu_quality_reads on a context of its own (nothing of the
  * asynchronous push path is touched), the records to the batch's ordinals; then the batch is pushed like any other */
 typedef struct {
@@ -1026,10 +1121,17 @@ int main(int argc, char **argv)
 {
 	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0 && strcmp(argv[1], "correct") != 0 &&
 	                 strcmp(argv[1], "normalize") != 0 && strcmp(argv[1], "trim") != 0 && strcmp(argv[1], "dedup") != 0 && strcmp(argv[1], "clip") != 0 &&
-	                 strcmp(argv[1], "overlap") != 0 && strcmp(argv[1], "complexity") != 0 && strcmp(argv[1], "qtrim") != 0)) { usage(); return 255; }
+	                 strcmp(argv[1], "overlap") != 0 && strcmp(argv[1], "complexity") != 0 && strcmp(argv[1], "qtrim") != 0 &&
+	                 strcmp(argv[1], "screen") != 0)) { usage(); return 255; }
 	const int do_query = strcmp(argv[1], "query") == 0, do_correct = strcmp(argv[1], "correct") == 0, do_norm = strcmp(argv[1], "normalize") == 0;
 	const int do_trim = strcmp(argv[1], "trim") == 0, do_dedup = strcmp(argv[1], "dedup") == 0, do_clip = strcmp(argv[1], "clip") == 0;
 	const int do_overlap = strcmp(argv[1], "overlap") == 0, do_cx = strcmp(argv[1], "complexity") == 0, do_qtrim = strcmp(argv[1], "qtrim") == 0;
+	const int do_screen = strcmp(argv[1], "screen") == 0;
+	sdt_screen_params sprm = {1, 0, 0, 0};
+	uint32_t screen_k = 31;                                                  /* bbduk's usual figure: a choice, not a measurement */
+	enum { MAX_REF_FILES = 256 };
+	static char *rfile[MAX_REF_FILES];
+	int n_rfiles = 0;
 	sdt_quality_params qprm = {33, 20, 15, 40, 0, 0, 0, 0};
 	sdt_overlap_params oprm = {30, 10, 0, 0};
 	sdt_complexity_params xprm = {10, 50, 0, 0};
@@ -1054,9 +1156,11 @@ int main(int argc, char **argv)
 	                                   {"trim-low", no_argument, 0, 1018}, {"phred", required_argument, 0, 1019},
 	                                   {"cut-q", required_argument, 0, 1020}, {"low-q", required_argument, 0, 1021},
 	                                   {"max-low-bases", required_argument, 0, 1022}, {"max-ee", required_argument, 0, 1023},
+	                                   {"screen-k", required_argument, 0, 1024}, {"min-hits", required_argument, 0, 1025},
+	                                   {"min-hit-pct", required_argument, 0, 1026}, {"keep-matched", no_argument, 0, 1027},
 	                                   {0, 0, 0, 0}};
 	argv++; argc--;
-	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:", longopts, NULL)) != -1) {
+	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:r:", longopts, NULL)) != -1) {
 		switch (c) {
 		case 's': snprintf(cfgfile, sizeof cfgfile, "%s", optarg); break;
 		case 'o': snprintf(outname, sizeof outname, "%s", optarg); break;
@@ -1143,6 +1247,24 @@ int main(int argc, char **argv)
 			else qprm.max_ee_ppm = (uint32_t)v;
 			break;
 		}
+		case 'r': case 1024: case 1025: case 1026: case 1027: {
+			static const char *const names[] = {"--screen-k", "--min-hits", "--min-hit-pct", "--keep-matched"};
+			const char *opt = c == 'r' ? "-r" : names[c - 1024];
+			unsigned long long v;
+			if (!do_screen) { fprintf(stderr, "sdt-kmers: %s belongs to screen\n", opt); usage(); return 255; }
+			if (c == 'r') {
+				if (n_rfiles == MAX_REF_FILES) { fprintf(stderr, "sdt-kmers: more than %d -r files\n", MAX_REF_FILES); return 255; }
+				rfile[n_rfiles++] = optarg;
+				break;
+			}
+			if (c == 1027) { sprm.flags |= SDT_SCREEN_KEEP_MATCHED; break; }
+			if (parse_number(opt, optarg, c == 1024 ? 31 : (c == 1026 ? 100 : UINT32_MAX), &v) != 0) return 255;
+			if (c == 1024 && v < 11) { fprintf(stderr, "sdt-kmers: --screen-k %llu: 11 to 31\n", v); return 255; }
+			if (c == 1024) screen_k = (uint32_t)v;
+			else if (c == 1025) sprm.min_hits = (uint32_t)v;
+			else sprm.min_hit_pct = (uint32_t)v;
+			break;
+		}
 		case 1008:
 			if (!do_dedup) { fprintf(stderr, "sdt-kmers: --mate-swap belongs to dedup\n"); usage(); return 255; }
 			dprm.flags |= SDT_DEDUP_MATE_SWAP;
@@ -1151,6 +1273,7 @@ int main(int argc, char **argv)
 		}
 	}
 	if (!cfgfile[0] || (do_query ? !qfile[0] : !outname[0])) { usage(); return 255; }
+	if (do_screen && n_rfiles == 0) { fprintf(stderr, "sdt-kmers: screen needs a reference file: -r refs.fa\n"); usage(); return 255; }
 	if (do_norm && prm.target == 0) { fprintf(stderr, "sdt-kmers: --target must be at least 1\n"); return 255; }
 	if (xprm.flags & SDT_COMPLEXITY_TRIM) {
 		if (max_low_given && xprm.max_low_pct != 0) {
@@ -1181,6 +1304,20 @@ int main(int argc, char **argv)
 			        (unsigned long long)(ads.offsets[i + 1] - ads.offsets[i]), cprm.min_overlap);
 			return 2;
 		}
+	/* the reference files are read and checked before the device is touched, in the order given */
+	sdt_ref_set refs;
+	memset(&refs, 0, sizeof refs);
+	for (int i = 0; i < n_rfiles; i++) {
+		char err[4400];
+		if (sdt_refs_load(&refs, rfile[i], err, sizeof err) != 0) { fprintf(stderr, "sdt-kmers: %s\n", err); return 2; }
+	}
+	if (do_screen) {
+		if (sdt_refs_pack(&refs) != 0) { fprintf(stderr, "sdt-kmers: out of memory for the references\n"); return 2; }
+		uint64_t positions = 0;
+		for (uint64_t i = 0; i < refs.nseqs; i++)
+			if (refs.offsets[i + 1] - refs.offsets[i] >= screen_k) positions += refs.offsets[i + 1] - refs.offsets[i] - screen_k + 1;
+		if (positions == 0) { fprintf(stderr, "sdt-kmers: the references hold no stretch of %u letters ACGT: no k-mer to screen against\n", screen_k); return 2; }
+	}
 	query_set qs;
 	memset(&qs, 0, sizeof qs);
 	if (do_query) {
@@ -1204,7 +1341,7 @@ int main(int argc, char **argv)
 	}
 	sdt_pair_ranges pairs;
 	memset(&pairs, 0, sizeof pairs);
-	push_state st = {gpu, 0, do_norm || do_trim || do_dedup || do_clip || do_overlap || do_cx || do_qtrim ? &pairs : NULL};
+	push_state st = {gpu, 0, do_norm || do_trim || do_dedup || do_clip || do_overlap || do_cx || do_qtrim || do_screen ? &pairs : NULL};
 	qtrim_state qst;
 	memset(&qst, 0, sizeof qst);
 	if (do_qtrim) {
@@ -1252,6 +1389,10 @@ int main(int argc, char **argv)
 	} else if (do_cx) {
 		if (complexity_and_write(gpu, st.reads, &xprm, &pairs, outname) != 0) return 1;
 		sdt_pair_ranges_free(&pairs);
+	} else if (do_screen) {
+		if (screen_and_write(gpu, st.reads, &sprm, screen_k, &refs, &pairs, outname) != 0) return 1;
+		sdt_pair_ranges_free(&pairs);
+		sdt_refs_free(&refs);
 	} else if (do_qtrim) {
 		if (st.reads > qst.cap) { fprintf(stderr, "sdt-kmers: %llu reads streamed, records for %llu\n", st.reads, (unsigned long long)qst.cap); return 1; }
 		if (qtrim_and_write(gpu, st.reads, &qprm, qst.rec, qst.n_kept, &pairs, outname) != 0) return 1;

@@ -9,6 +9,8 @@
 //   sdt_select.hip    in-silico read normalisation against the counted table; a 2-bit stream compacted to the reads kept
 //   sdt_trim.hip      reads cut back to their longest solid stretch against the counted table; a 2-bit stream compacted to kept ranges
 //                     (these four read stages share a host layer of their own: sdt_readstage.hpp over sdt_read_plan.h, sdt_compact.hpp)
+//   sdt_screen.hip    reads screened against reference sequences: a k-mer set of its own that the context keeps (one of the stages in
+//                     front of pass 1 that need no table, like sdt_dedup.hip, sdt_clip.hip, sdt_overlap.hip, sdt_complexity.hip, sdt_quality.hip)
 //   sdt_gpu_graph.hip the graph phases (own view of the context: sdt_internal.hpp GraphView)
 // Not part of the ABI: nothing here is visible to a caller of libsdt_gpu.so.
 #pragma once
@@ -161,6 +163,13 @@ struct sdt_ctx {
 	uint64_t hi_slots = 0;
 	int hi_mode = -1;
 	unsigned long long *d_cov_flags = nullptr;      // [0] reads longer than promised, [1] slots with a high half, [2] edits (sdt_correct.hip) / reads kept (sdt_select.hip)
+	// the reference screen (sdt_screen.hip): a hash set canonical k-mer -> reference of its own k; lives from screen_load to
+	// screen_unload / destroy, nothing else touches it
+	struct ScreenSet {
+		void *tab = nullptr;               // slots of 16 bytes
+		uint64_t slots = 0, n_kmers = 0;
+		uint32_t k = 0, n_refs = 0;
+	} screen;
 	// timing
 	std::vector<EventPair> ev;
 	size_t ev_used = 0;

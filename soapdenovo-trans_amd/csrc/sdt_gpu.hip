@@ -346,6 +346,7 @@ int sdt_gpu_destroy(sdt_ctx *c)
 	if (c->d_hit_cursor) (void)hipFree(c->d_hit_cursor);
 	if (c->d_hi) (void)hipFree(c->d_hi);
 	if (c->d_cov_flags) (void)hipFree(c->d_cov_flags);
+	if (c->screen.tab) (void)hipFree(c->screen.tab);
 	for (int i = 0; i < 5; i++) if (c->ab[i]) (void)hipFree(c->ab[i]);
 	sk_free(c);
 	shard_free(c);

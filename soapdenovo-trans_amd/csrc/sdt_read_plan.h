@@ -2,9 +2,9 @@
 // sdt_select.hip, sdt_trim.hip) decide on the host before anything reaches the device, as PURE functions: the launch geometry of a
 // strip kernel, the check of a host stream's offsets, and the cut of a host batch into the pieces that are staged one at a time.
 // sdt_readstage.hpp calls them for every stage; tools/read_plan_check.cpp (tests/test_read_plan.py) calls them on the CPU under
-// sanitizers.  The five stages that need no table have theirs here too: the duplicate filter (sdt_dedup.hip), the adapter and tail
-// clipping (sdt_clip.hip), the mate overlap (sdt_overlap.hip), the low-complexity filter (sdt_complexity.hip) and the quality trim
-// (sdt_quality.hip), which also has its cut of a byte stream into pieces here.  No HIP in here.
+// sanitizers.  The six stages that need no table have theirs here too: the duplicate filter (sdt_dedup.hip), the adapter and tail
+// clipping (sdt_clip.hip), the mate overlap (sdt_overlap.hip), the low-complexity filter (sdt_complexity.hip), the reference screen
+// (sdt_screen.hip) and the quality trim (sdt_quality.hip), which also has its cut of a byte stream into pieces here.  No HIP in here.
 #pragma once
 #include <stdint.h>
 
@@ -295,6 +295,93 @@ constexpr uint64_t complexity_window_begin(uint64_t j) { return j * COMPLEXITY_S
 constexpr uint64_t complexity_window_end(uint64_t j, uint64_t L)
 {
 	return j * COMPLEXITY_STEP + COMPLEXITY_WINDOW < L ? j * COMPLEXITY_STEP + COMPLEXITY_WINDOW : L;
+}
+
+// ---- the reference screen (sdt_screen.hip): what is refused before any launch, the size of the set's table, the rule of a read and
+// of a unit, and the unit verdicts of the kept form ----
+// (tools/screen_plan_check.cpp runs the check and holds the unit verdicts to a walk over every ordinal)
+struct ScreenParams {                                    // == sdt_screen_params of include/sdt_gpu.h
+	uint32_t min_hits, min_hit_pct, flags, reserved;
+};
+struct ScreenRec {                                       // == sdt_read_screen of include/sdt_gpu.h
+	uint32_t kmers, hits, ref, start, len, verdict;
+};
+constexpr uint32_t SCREEN_KEEP_MATCHED = 1u;             // SDT_SCREEN_KEEP_MATCHED
+constexpr uint32_t SCREEN_PER_READ = 1u << 31;           // (internal, never a caller's: no verdicts, every record keeps len = L; the kept form)
+constexpr uint32_t SCREEN_NO_REF = 0xFFFFFFFFu;          // SDT_SCREEN_NO_REF
+constexpr uint32_t SCREEN_MIN_K = 11, SCREEN_MAX_K = 31;
+constexpr uint64_t SCREEN_MIN_SLOTS = 1024;
+
+enum ScreenFault { SCREEN_OK = 0, SCREEN_MIN_HIT_PCT, SCREEN_FLAGS, SCREEN_RESERVED };
+
+// the first field that is refused, in the order of the rules in include/sdt_gpu.h
+inline ScreenFault check_screen_params(const ScreenParams &p)
+{
+	if (p.min_hit_pct > 100) return SCREEN_MIN_HIT_PCT;
+	if (p.flags & ~SCREEN_KEEP_MATCHED) return SCREEN_FLAGS;
+	if (p.reserved != 0) return SCREEN_RESERVED;
+	return SCREEN_OK;
+}
+
+// the k-mer start positions of a checked stream of sequences: what the table is sized for (a k-mer that occurs twice counts twice)
+inline uint64_t screen_positions(const uint64_t *offsets, uint64_t nseqs, uint32_t k)
+{
+	uint64_t n = 0;
+	for (uint64_t i = 0; i < nseqs; i++) {
+		const uint64_t len = offsets[i + 1] - offsets[i];
+		if (len >= k) n += len - k + 1;
+	}
+	return n;
+}
+
+// the table for that many positions: the power of two >= 2 * positions, SCREEN_MIN_SLOTS at least (load <= 1/2: a probe ends)
+inline uint64_t screen_table_slots(uint64_t positions)
+{
+	uint64_t slots = SCREEN_MIN_SLOTS;
+	while (slots < 2 * positions && slots < (1ULL << 62)) slots <<= 1;
+	return slots;
+}
+
+// (SDT_SCREEN_SLOTS) a forced slot count holds the set iff it is a power of two with an empty slot left whatever the k-mers are
+constexpr bool screen_forced_slots_ok(uint64_t forced, uint64_t positions) { return forced && !(forced & (forced - 1)) && forced > positions; }
+
+// (constexpr: the kernel calls them too)
+constexpr bool screen_read_matched(uint64_t kmers, uint64_t hits, const ScreenParams &p)
+{
+	return hits >= (p.min_hits > 1 ? p.min_hits : 1u) && 100 * hits >= (uint64_t)p.min_hit_pct * kmers;
+}
+constexpr bool screen_unit_dropped(bool matched, uint32_t flags) { return (flags & SCREEN_KEEP_MATCHED) ? !matched : matched; }
+
+// The kept form: rec[o] for the ordinals o < n_ord with present[o] != 0 hold what SCREEN_PER_READ leaves (kmers, hits, ref, len = L).
+// The units are those of cut_unit_stretches under checked pair ranges, and a pair of which one mate is present is a unit of that
+// read.  Every present record gets its unit's start, len and verdict; the others are not looked at.  Returns the reads kept.
+inline uint64_t screen_unit_verdicts(ScreenRec *rec, const uint8_t *present, uint64_t n_ord, const uint64_t *pair_ranges, uint64_t n_ranges,
+                                     const ScreenParams &p)
+{
+	uint64_t kept = 0, at = 0;
+	auto matched = [&](uint64_t o) { return present[o] && screen_read_matched(rec[o].kmers, rec[o].hits, p); };
+	auto decide = [&](uint64_t o, bool dropped) {
+		if (!present[o]) return;
+		rec[o].start = 0;
+		rec[o].verdict = dropped ? 1u : 0u;
+		if (dropped) rec[o].len = 0; else kept++;
+	};
+	auto singles = [&](uint64_t a, uint64_t e) {
+		for (uint64_t o = a; o < e; o++) decide(o, screen_unit_dropped(matched(o), p.flags));
+	};
+	for (uint64_t i = 0; i < n_ranges && at < n_ord; i++) {
+		const uint64_t first = pair_ranges[2 * i], end = pair_ranges[2 * i + 1] < n_ord ? pair_ranges[2 * i + 1] : n_ord;
+		if (first >= n_ord || end == first) continue;
+		singles(at, first);
+		for (uint64_t o = first; o < end; o += 2) {
+			const bool m = matched(o) || (o + 1 < end && matched(o + 1)), d = screen_unit_dropped(m, p.flags);
+			decide(o, d);
+			if (o + 1 < end) decide(o + 1, d);
+		}
+		at = pair_ranges[2 * i + 1];
+	}
+	if (at < n_ord) singles(at, n_ord);
+	return kept;
 }
 
 // ---- quality trimming (sdt_quality.hip): what is refused before any launch, the expected errors of a quality, and a host stream of
