@@ -196,6 +196,15 @@ inline size_t entry_bytes(int nw) { return nw == 1 ? sizeof(Entry<1>) : nw == 2 
 
 inline int scan_grid(const sdt_ctx *c, uint64_t items) { return sdti::scan_grid(c->cu_count, items); }
 
+// (SDT_WAVE_BLOCKS: test hook -- the kernels that give every wavefront a read run in that many workgroups, so that a wavefront takes
+// read after read of a small batch and what it carries from one to the next (an LDS strip, counters) is seen; 0: no hook.  The
+// decision itself is wave_blocks of sdt_read_plan.h)
+inline uint64_t wave_blocks_forced()
+{
+	static const int forced = sdt_knob_int(sdt_test_env("SDT_WAVE_BLOCKS"), 0);
+	return forced > 0 ? (uint64_t)forced : 0;
+}
+
 
 // the table is about to change (nodes counted, moved or replaced): what sdt_search.hip derived from it is stale
 inline void search_cache_drop(sdt_ctx *c) { c->hi_mode = -1; }

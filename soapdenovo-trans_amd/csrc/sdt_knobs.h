@@ -7,6 +7,8 @@
  *   test hooks    honoured only when            shrink a limit or force a path so that SMALL inputs go through it: chunk sizes, pool sizes,
  *                 SDT_TEST_HOOKS=1 is set       receive buffers, workgroup counts, thresholds, the host forms of device phases.  tests/conftest.py
  *                 sdt_test_env()                sets SDT_TEST_HOOKS for the whole suite; a production run ignores every one of them.
+ *                                               The two workgroup counts: SDT_SCAN_BLOCKS (lane-per-item kernels: scan_grid) and
+ *                                               SDT_WAVE_BLOCKS (wavefront-per-read kernels: wave_blocks of sdt_read_plan.h).
  *   tuning        compiled out unless the       A/B measurement switches (batch sizes, launch sizes, table load, alternative kernels' geometry):
  *                 unit is built -DSDT_TUNING    tools/ab_build.sh builds such variants into gpurun_ab/; the shipped library does not look at them.
  *                 sdt_tuning_env()

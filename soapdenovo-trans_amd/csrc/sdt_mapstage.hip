@@ -1,6 +1,7 @@
 // sdt_mapstage.hip -- the map stage's hashing path: prlContig2nodes (prlHashCtg.c:287-425) = k_index_contigs,
 // prlRead2Ctg (prlRead2Ctg.c:656-894) = k_align_reads.
 #include "sdt_ctx.hpp"
+#include "sdt_read_plan.h"
 #include "sdt_ctg_kernels.cuh"
 
 extern "C" {
@@ -119,13 +120,10 @@ static int launch_align(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_o
 		HIPCHK(hipMemcpyAsync(c->d_hit_cursor, &first_extra, sizeof first_extra, hipMemcpyHostToDevice, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream));
 	}
-	uint64_t blocks = (nreads + waves - 1) / waves;
-	const uint64_t cap = (uint64_t)c->cu_count * 32;
-	if (blocks > cap) blocks = cap;
-	if (blocks == 0) blocks = 1;
+	const uint32_t blocks = wave_blocks(nreads, (uint64_t)waves, c->cu_count, wave_blocks_forced());      // (the kernel strides over the reads)
 	EventPair *ev = next_event(c);
 	if (ev) HIPCHK(hipEventRecord(ev->a, c->stream));
-#define ALIGN_LAUNCH(NWV) hipLaunchKernelGGL(k_align_reads<NWV>, dim3((unsigned)blocks), dim3(TPB), per_wave * waves, c->stream, d_words, d_offs, nreads, \
+#define ALIGN_LAUNCH(NWV) hipLaunchKernelGGL(k_align_reads<NWV>, dim3(blocks), dim3(TPB), per_wave * waves, c->stream, d_words, d_offs, nreads, \
 	d_align_len, align_len_all, c->K, table_of<NWV>(c), (const uint32_t *)c->d_ctg_len, \
 	(const uint32_t *)c->d_ctg_twin, c->num_ctg, max_kmers, waves, d_info, d_hits, (unsigned long long)max_hits, c->d_hit_cursor, c->d_stats)
 	if (c->nw == 1) ALIGN_LAUNCH(1);

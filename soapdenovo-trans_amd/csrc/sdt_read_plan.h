@@ -10,6 +10,17 @@
 
 namespace sdt {
 
+// ---- the grid of a kernel that gives every wavefront one item (a read, a pair) and strides over the rest ----
+// `waves` wavefronts of a workgroup take an item each.  The workgroups that `items` items fill, cu_count * 32 at most and one at least;
+// forced != 0 (SDT_WAVE_BLOCKS: test hook) puts that many in the place of cu_count * 32, so that a batch of test size goes round the
+// kernels' loop over the items many times.  Every read stage and align_reads take their grid from here.
+constexpr uint32_t wave_blocks(uint64_t items, uint64_t waves, int cu_count, uint64_t forced)
+{
+	const uint64_t blocks = items / waves + (items % waves != 0);
+	const uint64_t cap = forced ? forced : (uint64_t)cu_count * 32;      // (the kernels stride over the items)
+	return (uint32_t)(blocks > cap ? cap : (blocks ? blocks : 1));
+}
+
 // ---- the launch geometry of a strip kernel ----
 // A strip kernel gives every wavefront one read and a strip of LDS with one 32-bit count per k-mer of the longest read; a workgroup
 // has 64 KiB of strips.  Reads of up to 4 096 k-mers run 4 wavefronts per workgroup, up to 8 192 two, up to 16 384 one; longer reads
@@ -26,7 +37,7 @@ struct StripGeometry {
 	uint32_t blocks;
 };
 
-inline StripGeometry strip_geometry(int K, uint64_t nreads, uint64_t max_read_len, int cu_count)
+inline StripGeometry strip_geometry(int K, uint64_t nreads, uint64_t max_read_len, int cu_count, uint64_t forced_blocks = 0)
 {
 	StripGeometry g = {max_read_len < (uint64_t)K ? (uint64_t)K : max_read_len, 0, false, 0, 0, 0};
 	g.mk = g.max_read_len - (uint64_t)K + 1;
@@ -36,11 +47,7 @@ inline StripGeometry strip_geometry(int K, uint64_t nreads, uint64_t max_read_le
 	g.waves = 4;
 	while (g.waves > 1 && per_wave * g.waves > STRIP_LDS_BYTES) g.waves >>= 1;
 	g.lds_bytes = (uint32_t)(per_wave * g.waves);
-	uint64_t blocks = nreads / g.waves + (nreads % g.waves != 0);
-	const uint64_t cap = (uint64_t)cu_count * 32;      // (the kernels stride over the reads)
-	if (blocks > cap) blocks = cap;
-	if (blocks == 0) blocks = 1;
-	g.blocks = (uint32_t)blocks;
+	g.blocks = wave_blocks(nreads, (uint64_t)g.waves, cu_count, forced_blocks);
 	return g;
 }
 

@@ -44,7 +44,7 @@ static void by_key_width(const sdt_ctx *c, Fn fn)
 // the geometry of a strip kernel over reads of up to max_read_len bases, or the refusal of reads that no strip holds
 static int strip_plan(const sdt_ctx *c, uint64_t nreads, uint64_t max_read_len, StripGeometry *geo)
 {
-	*geo = strip_geometry(c->K, nreads, max_read_len, c->cu_count);
+	*geo = strip_geometry(c->K, nreads, max_read_len, c->cu_count, wave_blocks_forced());
 	if (!geo->fits)
 		return fail(SDT_EINVAL, "reads of %llu bases do not fit the per-wavefront LDS strip (%llu k-mers, 16384 at most)",
 		            (unsigned long long)geo->max_read_len, (unsigned long long)geo->mk);
@@ -186,10 +186,7 @@ static int flags_end(sdt_ctx *c, const char *what, uint64_t max_read_len, unsign
 // the grid of a kernel that gives every wavefront one item and strides over the rest (sdt_dedup.hip, sdt_clip.hip)
 static int wave_grid(const sdt_ctx *c, uint64_t items)
 {
-	const uint64_t per = TPB / 64, cap = (uint64_t)c->cu_count * 32;
-	uint64_t blocks = items / per + (items % per != 0);
-	if (blocks > cap) blocks = cap;
-	return blocks ? (int)blocks : 1;
+	return (int)wave_blocks(items, TPB / 64, c->cu_count, wave_blocks_forced());
 }
 
 // ---- the reads kept in HBM ----

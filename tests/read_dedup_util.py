@@ -130,11 +130,12 @@ COPIES = (1, 2, 3, 7)
 
 
 @functools.lru_cache(maxsize=None)
-def case():
+def case(seed=20240917):
     """34 base sequences of the lengths above, each present 1, 2, 3 or 7 times; near misses of three of them (the last base, the first
     base, one base more, one base fewer, and base 32 of a 65-base read); a second read of length 0; filler reads of 1 .. 15 bases, so
-    that copies start at every base of a word; shuffled by a fixed seed.  Built once and left unchanged."""
-    rng = np.random.default_rng(20240917)
+    that copies start at every base of a word; shuffled by a fixed seed.  Built once per seed and left unchanged (another seed: another
+    draw of the same generator, for the tests that need more reads)."""
+    rng = np.random.default_rng(seed)
     seqs = []
     for L in LENGTHS:
         per = 1 if L in (0, 5000) else 3 if 31 <= L <= 65 else 2
@@ -176,12 +177,12 @@ def case():
 
 
 @functools.lru_cache(maxsize=None)
-def paired_case():
+def paired_case(seed=20240918):
     """pairs: (a, b) three times, (b, a), (a, c), (a, a); (p, q) seven times and (q, p) twice; a pair of two empty reads twice; the
     5 000-base read with a 2 049-base mate twice, and once with the mate one base shorter; and the first reads of case() two by
     two.  The pairs are shuffled by a fixed seed."""
-    c = case()
-    rng = np.random.default_rng(20240918)
+    c = case() if seed == 20240918 else case(seed - 1)
+    rng = np.random.default_rng(seed)
     by_len = {}
     for r in c["reads"]:
         by_len.setdefault(len(r), r)

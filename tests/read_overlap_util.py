@@ -180,10 +180,11 @@ def _mutate(a, where):
 
 
 @functools.lru_cache(maxsize=None)
-def case():
-    """Pairs with planted fragments, each under a name that says what it is there for; built once from a fixed seed and left
-    unchanged.  `pairs` holds (a, b) per name in the order of `names`; reads, codes and offs are the interleaved stream."""
-    rng = np.random.default_rng(20241020)
+def case(seed=20241020):
+    """Pairs with planted fragments, each under a name that says what it is there for; built once per seed and left unchanged
+    (another seed: another draw of the same generator).  `pairs` holds (a, b) per name in the order of `names`; reads, codes and offs
+    are the interleaved stream."""
+    rng = np.random.default_rng(seed)
     rnd = lambda n: rng.integers(0, 4, size=n, dtype=np.uint8)
     cat = lambda *parts: np.concatenate([np.asarray(x, dtype=np.uint8) for x in parts]).astype(np.uint8)
 

@@ -196,11 +196,11 @@ def absent_kmers(k, d, n, seed):
 
 # ---- the named reads: every length at which the kernel takes another path, of three kinds, and their reverse complements ------------
 @functools.lru_cache(maxsize=None)
-def read_case(k):
+def read_case(k, seed=None):
     """-> dict(reads, codes, offs, facts, exact): reads of 0, k - 1, k, k + 1, k + 63, k + 64, 200 and 5 000 bases, cut from the references,
     random, and half of each; then the reverse complement of every one; then a read of k + 99 bases (100 k-mers) whose first k + 36
-    bases are a reference's.  exact: its index"""
-    rng = np.random.default_rng(2000 + k)
+    bases are a reference's.  exact: its index.  seed: another draw of the same generator"""
+    rng = np.random.default_rng(2000 + k if seed is None else seed)
     c = set_case(k)
     big = c["seqs"][0]
     reads = []

@@ -503,6 +503,89 @@ def test_clip_and_overlap_at_offsets_past_2_32(pkg, synth, big_buffer):
 
 
 @gpu
+def test_complexity_and_screen_at_offsets_past_2_32(pkg, synth, big_buffer):
+    """complexity_reads_device (filter and SDT_COMPLEXITY_TRIM) on its own case, and screen_reads_device (single reads; pairs) on the
+    reads of the screen's case at k = 21 against the set of that case: records, keep bytes and the kept count against the restatement
+    at every placement, and against the placement near base 0"""
+    import torch
+    import read_complexity_util as cu
+    import read_screen_util as su
+    from test_read_complexity import TRIM, assert_cx
+    from test_read_screen import assert_screen, load_case
+    with pkg.PregraphGPU(31, est_distinct=1 << 12) as g:
+        c = cu.case()
+        n = len(c["offs"]) - 1
+        for mode, prm, want in (("filter", c["params"], cu.case_expect()), ("trim", dict(c["params"], **TRIM), cu.case_expect(trim=True))):
+            def complexity(p):
+                d_cx = torch.full((n, 6), -3, dtype=torch.int32, device="cuda:0")
+                d_keep = torch.full((n,), 7, dtype=torch.uint8, device="cuda:0")
+                torch.cuda.synchronize()
+                kept = g.complexity_reads_device(big_buffer, p.d_offs, n, d_cx, d_keep, prm)
+                return records(d_cx, pkg.READ_COMPLEXITY_DTYPE), d_keep.cpu().numpy(), kept
+            for s, got in at_placements(big_buffer, c["codes"], c["offs"], complexity).items():
+                assert_cx(pkg, got, want, f"complexity ({mode}) at {s}")
+        k = 21
+        rc, d = su.read_case(k), su.set_dict(k)
+        load_case(g, synth, k)
+        for paired in (False, True):
+            m = (len(rc["offs"]) - 1) & ~1 if paired else len(rc["offs"]) - 1         # (the case has an odd number of reads)
+            want = su.expect_screen(rc["codes"], rc["offs"][:m + 1], k, d, su.params(), paired=paired, facts=rc["facts"][:m])
+
+            def screen(p):
+                d_rec = torch.full((m, 6), -3, dtype=torch.int32, device="cuda:0")
+                d_keep = torch.full((m,), 7, dtype=torch.uint8, device="cuda:0")
+                torch.cuda.synchronize()
+                kept = g.screen_reads_device(big_buffer, p.d_offs, m, d_rec, d_keep, paired=paired, params=su.params())
+                return records(d_rec, pkg.READ_SCREEN_DTYPE), d_keep.cpu().numpy(), kept
+            assert 0 < want[2] < m
+            for s, got in at_placements(big_buffer, rc["codes"], rc["offs"], screen).items():
+                assert_screen(pkg, got, want, f"screen at {s} paired={paired}")
+
+
+@gpu
+def test_quality_at_offsets_past_2_32(pkg):
+    """quality_reads_device addresses BYTES, one per base, with its own arithmetic for the bytes in front of a read within its 32-bit
+    word: the case of test_read_quality.py in a byte buffer of 2^32 + 2^20 bytes of its own, at byte offsets S (one read straddles
+    2^32; all reads above it) and S & 3 (the same place within a word, near byte 0)"""
+    import torch
+    import read_quality_util as qu
+    from test_read_quality import assert_q
+    c = qu.case()
+    n = len(c["offs"]) - 1
+    quals = torch.from_numpy(c["quals"])
+    assert S_STRADDLE & 3 and S_ABOVE & 3                   # (a read's first byte is not the first of its word)
+    buf = torch.zeros(fu.TWO32 + (1 << 20), dtype=torch.uint8, device="cuda:0")
+    try:
+        out = {}
+        with pkg.PregraphGPU(31, est_distinct=1 << 12) as g:
+            for S in (S_STRADDLE, S_ABOVE):
+                for s in (S & 3, S):
+                    aoffs = c["offs"] + np.uint64(s)
+                    if s > 3:
+                        assert_high(s, aoffs)
+                    assert int(aoffs[-1]) + 4 <= buf.numel()
+                    buf[s: s + len(quals)] = quals.cuda()
+                    d_o = torch.from_numpy(aoffs.view(np.int64)).cuda()
+                    d_out = torch.full((n, 6), -3, dtype=torch.int32, device="cuda:0")
+                    d_keep = torch.full((n,), 7, dtype=torch.uint8, device="cuda:0")
+                    torch.cuda.synchronize()
+                    kept = g.quality_reads_device(buf, d_o, n, d_out, d_keep, c["params"])
+                    out[S, s] = (records(d_out, pkg.READ_QUALITY_DTYPE), d_keep.cpu().numpy(), kept)
+                    buf[s: s + len(quals)].zero_()
+                    torch.cuda.synchronize()
+        assert len(out) == 4
+        for (S, s), got in out.items():
+            assert_q(pkg, got, qu.case_expect(), f"quality at byte {s}")
+        runs = list(out.items())
+        for i, (a, x) in enumerate(runs):
+            for b, y in runs[i + 1:]:
+                assert_same(x, y, f"bytes {a[1]} and {b[1]}")
+    finally:
+        del buf
+        torch.cuda.empty_cache()
+
+
+@gpu
 def test_compactions_at_offsets_past_2_32(pkg, synth, big_buffer):
     """compact_reads_device and compact_trimmed_device: the input at the high offsets, the output from base 0 -- words, pad words and
     offsets; length_mix() forty times over (every length next to every other, reads that start at every base of a word), every third

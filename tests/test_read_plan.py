@@ -43,3 +43,19 @@ def test_the_library_uses_this_plan():
         assert everything.count(once) == 1, once
     assert len(re.findall(r"<= (?:piece_bases|PROFILE_CHUNK_BASES)", everything)) == 1, "the bases cap is applied in one place"
     assert not re.search(r"#define \w+_LAUNCH", everything)
+    # the grid of the kernels that give every wavefront a read is decided once, in wave_blocks of sdt_read_plan.h, and its three
+    # users go through it with the value of SDT_WAVE_BLOCKS: wave_grid, the strip geometry (through strip_plan), the launch of
+    # k_align_reads
+    body = lambda text, head: text[text.index(head):].split("\n}\n", 1)[0]
+    assert len(re.findall(r"^constexpr uint32_t wave_blocks\(", plan, re.M)) == 1
+    assert "wave_blocks(" in body(plan, "inline StripGeometry strip_geometry(")
+    assert "wave_blocks(" in body(layer, "static int wave_grid(") and "wave_blocks_forced()" in body(layer, "static int wave_grid(")
+    assert re.search(r"strip_geometry\([^;]*wave_blocks_forced\(\)\);", body(layer, "static int strip_plan("))
+    mapstage = open(os.path.join(CSRC, "sdt_mapstage.hip")).read()
+    launch = body(mapstage, "static int launch_align(")
+    assert '#include "sdt_read_plan.h"' in mapstage
+    assert re.search(r"blocks = wave_blocks\([^;]*wave_blocks_forced\(\)\);", launch) and "k_align_reads<NWV>, dim3(blocks)" in launch
+    stage_units = [n for n in sorted(os.listdir(CSRC)) if re.match(r"sdt_(search|correct|select|trim|dedup|clip|overlap|complexity|quality|screen|mapstage)\w*\.(hip|cuh|hpp|h)$", n)]
+    cap = "".join(open(os.path.join(CSRC, n)).read() for n in stage_units + ["sdt_readstage.hpp", "sdt_read_plan.h", "sdt_compact.hpp"])
+    assert len(re.findall(r"cu_count \* 32", re.sub(r"//.*", "", cap))) == 1, "the cap of the grid is applied in one place"
+    assert cap.count('sdt_test_env("SDT_WAVE_BLOCKS")') == 0 and open(os.path.join(CSRC, "sdt_ctx.hpp")).read().count('sdt_test_env("SDT_WAVE_BLOCKS")') == 1

@@ -242,3 +242,56 @@ def test_quality_of_long_reads(pkg):
         # the same without trimming: every step of every read is measured
         assert_q(pkg, g.quality_reads(quals, offs, dict(p, cut_q=0, max_low_pct=100, max_ee_ppm=0)), qu.expect_quality(quals, offs, dict(p, cut_q=0, max_low_pct=100, max_ee_ppm=0)),
                  "long reads, whole")
+
+
+def test_quality_gain_past_2_30(pkg):
+    """One read whose running gain P - M passes 2^30: from there on the kernel holds the carried minimum, relative to P, at -2^30 (Mr)
+    and takes the gain from the 64-bit values.  cut_q = 40: a base of quality 93 adds 53, a base of quality 0 takes away 40, so the
+    gain needs 2^30 / 53 = 20.3 M bases.  The read: 1 000 bases of quality 0 (the minimum lies at base 1 000, not at 0), quality 93
+    with 3 000 single bases of quality 2 until the gain is 500 bases past 2^30, a dip of 1 000 bases of quality 0 (40 000 down: the
+    gain falls below 2^30 again and passes it a second time behind the dip), 100 000 bases of quality 93, 500 bases of quality 0.
+    Its best segment starts at base 1 000 and ends 500 bases before the end.  The reads before and after it are ordinary ones: nothing
+    carries over."""
+    import torch
+    dev = torch.device("cuda:0")
+    p = qu.params(cut_q=40, phred_offset=33, low_q=15, max_low_pct=100, max_ee_ppm=0, min_len=1)
+    up, down, low_down = qu.MAX_Q - p["cut_q"], p["cut_q"], p["cut_q"] - 2
+    assert (up, down) == (53, 40)
+    head, n_low, dip, tail, end = 1000, 3000, 1000, 100000, 500
+    rise = -(-((1 << 30) + n_low * (up + low_down)) // up) + 500              # bases from the minimum until the gain is 500 bases past 2^30
+    L = head + rise + dip + tail + end
+    q = np.full(L, qu.MAX_Q, dtype=np.int64)
+    q[:head] = 0
+    rng = np.random.default_rng(230)
+    stride = rise // n_low
+    lows = head + np.arange(n_low) * stride + rng.integers(0, stride, n_low)
+    q[lows] = 2
+    q[head + rise:head + rise + dip] = 0
+    q[L - end:] = 0
+    before = (qu.realistic(rng, 150, 0) + 33).astype(np.uint8)
+    after = (qu.realistic(rng, 150, 1) + 33).astype(np.uint8)
+    quals, offs = qu.concat_bytes([before, (q + 33).astype(np.uint8), after])
+    # on the input itself: the gain before the dip, behind it, and at the best end
+    P = np.concatenate([[0], np.cumsum(q - p["cut_q"])])
+    gain = P - np.minimum.accumulate(P)
+    at_dip = head + rise
+    assert 20_000_000 < L < 21_000_000 and len(np.unique(lows)) == n_low and lows.max() < at_dip
+    assert gain[:at_dip + 1].max() == gain[at_dip] > 1 << 30 and int(np.argmax(gain > 1 << 30)) <= L - 100000
+    assert gain[at_dip + dip] < 1 << 30 < gain[at_dip + dip + tail] == gain.max() and int(np.argmin(P)) == head
+    span = L - head - end
+    want = qu.expect_quality(quals, offs, p)
+    middle = (span, n_low + dip, (n_low * int(qu.EE_PPM[2]) + dip * int(qu.EE_PPM[0])) // span, head, span, qu.CLIPPED)
+    assert tuple(int(x) for x in want[0][1].tolist()) == middle
+    lone = [qu.expect_quality(r, np.array([0, len(r)], dtype=np.uint64), p)[0][0] for r in (before, after)]
+    assert want[0][0].tolist() == lone[0].tolist() and want[0][2].tolist() == lone[1].tolist()
+    with pkg.PregraphGPU(K, est_distinct=1 << 12) as g:
+        host = g.quality_reads(quals, offs, p)
+        assert_q(pkg, host, want, "the host form")
+        d_q = torch.from_numpy(np.concatenate([quals, np.zeros(-len(quals) % 4, dtype=np.uint8)])).to(dev)
+        d_o = torch.from_numpy(offs.view(np.int64)).to(dev)
+        d_out = torch.full((3, 6), -3, dtype=torch.int32, device=dev)
+        d_keep = torch.full((3,), 7, dtype=torch.uint8, device=dev)
+        kept = g.quality_reads_device(d_q, d_o, 3, d_out, d_keep, p)
+        out = d_out.cpu().numpy().view(np.uint8).copy().view(pkg.READ_QUALITY_DTYPE).reshape(-1)
+        assert_q(pkg, (out, d_keep.cpu().numpy(), kept), want, "the device form")
+        assert_q(pkg, (out, d_keep.cpu().numpy(), kept), host, "the device form against the host form")

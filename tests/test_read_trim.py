@@ -37,11 +37,12 @@ def revcomp(r):
 
 
 @functools.lru_cache(maxsize=None)
-def case(K):
+def case(K, seed=None):
     """the counted input -- four transcripts of K + 140 bases counted 1, 3, 8 and 64 times and one of K + 8 400 bases counted 4 times
     (in pieces of 3 000 k-mers: every k-mer of it in exactly one piece) -- the oracle's table for it, and the batch to trim; what each
-    group of reads is there for is said where it is made.  Built once per K and left unchanged."""
-    rng = np.random.default_rng(5000 + K)
+    group of reads is there for is said where it is made.  Built once per K and left unchanged.  seed: another draw of the same
+    generator (other transcripts, other reads), for the tests that need more reads."""
+    rng = np.random.default_rng(5000 + K if seed is None else seed)
     Lt = K + 140
     tx = [rng.integers(0, 4, size=Lt, dtype=np.uint8) for _ in COPIES]
     long_tx = rng.integers(0, 4, size=K + 8400, dtype=np.uint8)

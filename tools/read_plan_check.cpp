@@ -1,5 +1,6 @@
 // read_plan_check.cpp -- CPU: what the read stages decide on the host before anything reaches the device (csrc/sdt_read_plan.h):
 //   * strip_geometry: 4 / 2 / 1 wavefronts at 4 096 / 8 192 / 16 384 k-mers, the LDS bytes, the refusal one k-mer further, the grid;
+//   * wave_blocks: the grid of every kernel that gives a wavefront a read, unchanged without SDT_WAVE_BLOCKS, and what the hook forces;
 //   * next_piece: on ragged offsets the pieces tile the batch, keep pairs whole, respect both caps (reads AND bases), are maximal --
 //     which with the tiling fixes the cut -- and name the right words; every offsets array is malloc'ed to exactly nreads + 1
 //     entries, so that under AddressSanitizer a look past it is a finding;
@@ -52,6 +53,47 @@ static void geometry(void)
 			      (unsigned long long)len);
 		}
 	}
+}
+
+// wave_blocks: without a forced value the grid is what it was before the function existed (restated here as it stood); forced 1 and
+// 3 with fewer and with more items than wavefronts; never 0 workgroups, never more than the items fill; and strip_geometry passes the
+// forced value on
+static void grids(void)
+{
+	static const int cus[] = {1, 8, 256};
+	static const uint64_t waves[] = {1, 2, 4};
+	for (const int cu : cus)
+		for (const uint64_t w : waves) {
+			const uint64_t full = w * cu * 32;
+			for (const uint64_t items : {(uint64_t)0, (uint64_t)1, w - 1, w, w + 1, 3 * w - 1, 3 * w, 3 * w + 1, full - 1, full, full + 1, 100 * full + 7, ~(uint64_t)0}) {
+				uint64_t was = items / w + (items % w != 0);
+				const uint64_t cap = (uint64_t)cu * 32;
+				if (was > cap) was = cap;
+				if (was == 0) was = 1;
+				CHECK(wave_blocks(items, w, cu, 0) == was, "%llu items, %llu waves, %d CUs: %u workgroups, %llu before", (unsigned long long)items,
+				      (unsigned long long)w, cu, wave_blocks(items, w, cu, 0), (unsigned long long)was);
+				for (const uint64_t forced : {(uint64_t)1, (uint64_t)3, (uint64_t)100000}) {
+					const uint32_t b = wave_blocks(items, w, cu, forced);
+					const uint64_t fill = items / w + (items % w != 0);
+					CHECK(b >= 1 && b <= forced && (b == forced || b == (fill ? fill : 1)), "%llu items, %llu waves, forced %llu: %u workgroups",
+					      (unsigned long long)items, (unsigned long long)w, (unsigned long long)forced, b);
+				}
+			}
+			// fewer items than the forced workgroups have wavefronts: as many workgroups as the items fill; more: the forced number
+			CHECK(wave_blocks(w, w, cu, 1) == 1 && wave_blocks(w - 1, w, cu, 1) == 1 && wave_blocks(1000 * w, w, cu, 1) == 1, "forced 1");
+			CHECK(wave_blocks(2 * w, w, cu, 3) == 2 && wave_blocks(2 * w + 1, w, cu, 3) == 3 && wave_blocks(3 * w + 1, w, cu, 3) == 3 &&
+			      wave_blocks(1000 * w, w, cu, 3) == 3, "forced 3");
+			CHECK(wave_blocks(0, w, cu, 0) == 1 && wave_blocks(0, w, cu, 1) == 1 && wave_blocks(0, w, cu, 3) == 1, "no items");
+		}
+	// a strip kernel: one wavefront per workgroup at 16 384 k-mers, so forced 1 is a single wavefront for the whole batch
+	for (const uint64_t forced : {(uint64_t)1, (uint64_t)3}) {
+		const StripGeometry one = strip_geometry(31, 1000, 16000, 256, forced), four = strip_geometry(31, 1000, 150, 256, forced);
+		CHECK(one.fits && one.waves == 1 && one.blocks == forced && four.fits && four.waves == 4 && four.blocks == forced, "forced %llu",
+		      (unsigned long long)forced);
+		CHECK(strip_geometry(31, 2, 150, 256, forced).blocks == 1 && strip_geometry(31, 0, 150, 256, forced).blocks == 1, "forced %llu, two reads",
+		      (unsigned long long)forced);
+	}
+	CHECK(strip_geometry(31, 1000, 150, 256, 0).blocks == 250 && strip_geometry(31, 1000, 150, 256).blocks == 250, "forced 0 is no hook");
 }
 
 // nreads + 1 offsets in exactly that much memory: empty reads, reads shorter than K = 31, ordinary ones, and one longer than `longer_than`
@@ -149,6 +191,7 @@ static void streams(void)
 int main(void)
 {
 	geometry();
+	grids();
 	const uint64_t cut = pieces();
 	streams();
 	printf("read_plan_check: ok (%llu pieces)\n", (unsigned long long)cut);
