@@ -2,6 +2,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "clipsplit.h"
+#include "putdec.h"
 
 /* one finished record behind the others; 0, or -1: out of memory */
 static int append(sdt_adapter_list *l, const uint8_t *codes, uint32_t m, const char *name, size_t name_len, int end)
@@ -145,25 +146,15 @@ sdt_adapter_set sdt_adapters_set(const sdt_adapter_list *l)
 	return s;
 }
 
-static char *put_field(char *p, uint32_t v, char sep)
-{
-	char t[10];
-	int n = 0;
-	do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-	while (n) *p++ = t[--n];
-	*p++ = sep;
-	return p;
-}
-
 char *sdt_put_clip_line(char *p, const sdt_read_clip *c)
 {
-	p = put_field(p, c->adapters & 0xFFFFu, ' ');
-	p = put_field(p, c->adapters >> 16, ' ');
-	p = put_field(p, c->tail3, ' ');
-	p = put_field(p, c->tail5, ' ');
-	p = put_field(p, c->start, ' ');
-	p = put_field(p, c->len, ' ');
-	return put_field(p, c->verdict, '\n');
+	p = sdt_put_dec(p, c->adapters & 0xFFFFu, ' ');
+	p = sdt_put_dec(p, c->adapters >> 16, ' ');
+	p = sdt_put_dec(p, c->tail3, ' ');
+	p = sdt_put_dec(p, c->tail5, ' ');
+	p = sdt_put_dec(p, c->start, ' ');
+	p = sdt_put_dec(p, c->len, ' ');
+	return sdt_put_dec(p, c->verdict, '\n');
 }
 
 int sdt_clip_stats_init(sdt_clip_stats *s, uint32_t n_adapters)

@@ -1,15 +1,11 @@
 /* clipsplit.h -- the host side of `sdt-kmers clip` that needs no device: adapter FASTA files into the packed adapter set of
  * include/sdt_gpu.h, what a read's record line looks like, and the statistics of a stream's records.  Where a read goes is
- * trimsplit.h's sdt_trim_route: sdt_read_clip has start and len where sdt_read_trim has them.  Plain C, no GPU library
- * (include/sdt_gpu.h only for the types): tools/clip_host_check.c links it on its own. */
+ * trimsplit.h's sdt_trim_route.  Plain C, no GPU library (include/sdt_gpu.h only for the types): tools/clip_host_check.c links it on its own. */
 #ifndef SDT_CLIPSPLIT_H
 #define SDT_CLIPSPLIT_H
 #include <stddef.h>
 #include <stdio.h>
 #include "../../../include/sdt_gpu.h"
-
-_Static_assert(offsetof(sdt_read_clip, start) == offsetof(sdt_read_trim, start) && offsetof(sdt_read_clip, len) == offsetof(sdt_read_trim, len) &&
-                   sizeof(sdt_read_clip) == sizeof(sdt_read_trim), "sdt_trim_route takes sdt_read_clip records through a pointer cast");
 
 /* the adapters of one or more FASTA files, in the order they were read: what sdt_adapter_set points into, and their names */
 typedef struct {

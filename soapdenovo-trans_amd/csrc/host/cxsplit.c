@@ -1,24 +1,15 @@
 /* cxsplit.c -- see cxsplit.h */
 #include "cxsplit.h"
-
-static char *put_field(char *p, uint32_t v, char sep)
-{
-	char t[10];
-	int n = 0;
-	do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-	while (n) *p++ = t[--n];
-	*p++ = sep;
-	return p;
-}
+#include "putdec.h"
 
 char *sdt_put_cx_line(char *p, const sdt_read_complexity *r)
 {
-	p = put_field(p, r->windows, ' ');
-	p = put_field(p, r->low, ' ');
-	p = put_field(p, r->score, ' ');
-	p = put_field(p, r->start, ' ');
-	p = put_field(p, r->len, ' ');
-	return put_field(p, r->verdict, '\n');
+	p = sdt_put_dec(p, r->windows, ' ');
+	p = sdt_put_dec(p, r->low, ' ');
+	p = sdt_put_dec(p, r->score, ' ');
+	p = sdt_put_dec(p, r->start, ' ');
+	p = sdt_put_dec(p, r->len, ' ');
+	return sdt_put_dec(p, r->verdict, '\n');
 }
 
 int sdt_cx_record_ok(const sdt_read_complexity *r, uint64_t read_len)

@@ -1,15 +1,12 @@
 /* cxsplit.h -- the host side of `sdt-kmers complexity` that needs no device: what a read's record line looks like, whether a record
  * can be that of a read of a given length, and the histogram of the reads' scores with its summary line.  Where a read goes is
- * trimsplit.h's sdt_trim_route: sdt_read_complexity has start and len where sdt_read_trim has them.
+ * trimsplit.h's sdt_trim_route.
  * Plain C, no GPU library (include/sdt_gpu.h only for the types): tools/complexity_host_check.c links it on its own. */
 #ifndef SDT_CXSPLIT_H
 #define SDT_CXSPLIT_H
 #include <stddef.h>
 #include <stdio.h>
 #include "../../../include/sdt_gpu.h"
-
-_Static_assert(offsetof(sdt_read_complexity, start) == offsetof(sdt_read_trim, start) && offsetof(sdt_read_complexity, len) == offsetof(sdt_read_trim, len) &&
-                   sizeof(sdt_read_complexity) == sizeof(sdt_read_trim), "sdt_trim_route takes sdt_read_complexity records through a pointer cast");
 
 /* "windows low score start len verdict\n"; returns the end of what it wrote (at most SDT_CX_LINE_MAX bytes) */
 enum { SDT_CX_LINE_MAX = 6 * 11 };

@@ -2,29 +2,20 @@
 #include <stdlib.h>
 #include <string.h>
 #include "dupsplit.h"
-
-static char *put_dec(char *p, uint64_t v, char sep)
-{
-	char t[20];
-	int n = 0;
-	do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-	while (n) *p++ = t[--n];
-	*p++ = sep;
-	return p;
-}
+#include "putdec.h"
 
 char *sdt_put_dup_line(char *p, const sdt_read_dup *d)
 {
-	p = put_dec(p, d->first, ' ');
-	p = put_dec(p, d->copies, ' ');
-	return put_dec(p, d->verdict, '\n');
+	p = sdt_put_dec(p, d->first, ' ');
+	p = sdt_put_dec(p, d->copies, ' ');
+	return sdt_put_dec(p, d->verdict, '\n');
 }
 
 char *sdt_put_dup_level_line(char *p, const sdt_dup_level *l)
 {
-	p = put_dec(p, l->copies, ' ');
-	p = put_dec(p, l->classes, ' ');
-	return put_dec(p, l->reads, '\n');
+	p = sdt_put_dec(p, l->copies, ' ');
+	p = sdt_put_dec(p, l->classes, ' ');
+	return sdt_put_dec(p, l->reads, '\n');
 }
 
 int sdt_dup_levels_note(sdt_dup_levels *lv, const sdt_read_dup *d, int leads)

@@ -2,6 +2,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "normsplit.h"
+#include "putdec.h"
 
 /* [first, end) into the sorted list; ranges that overlap or touch become one (all of them have even length and the ranges of one
  * pair of files start an even number of ordinals apart, so a merged range pairs the same ordinals) */
@@ -59,17 +60,23 @@ int sdt_pair_ranges_holds(const sdt_pair_ranges *pr, uint64_t ord, size_t *curso
 char *sdt_put_fasta_record(char *p, uint64_t ord, const uint32_t *words, uint64_t start, uint64_t len)
 {
 	static const char letters[4] = {'A', 'C', 'T', 'G'};
-	char t[20];
-	int n = 0;
-	uint64_t v = ord + 1;
 	*p++ = '>';
-	do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-	while (n) *p++ = t[--n];
-	*p++ = '\n';
-	for (uint64_t i = 0; i < len; i++) {
-		const uint64_t g = start + i;
-		*p++ = letters[(words[g >> 4] >> (30 - 2 * (int)(g & 15))) & 3u];
+	p = sdt_put_dec(p, ord + 1, '\n');
+	/* base by base up to a word boundary, then whole words without a branch per base, then the rest.  (The bases are most of what the
+	 * read stages' host side does; how fast a loop of one base per round ran depended on where the linker had put it.) */
+	uint64_t g = start;
+	const uint64_t end = start + len;
+	for (; g < end && (g & 15); g++) *p++ = letters[(words[g >> 4] >> (30 - 2 * (int)(g & 15))) & 3u];
+	for (; g + 16 <= end; g += 16, p += 16) {
+		const uint32_t w = words[g >> 4];
+		for (int j = 0; j < 16; j += 4) {
+			p[j] = letters[(w >> (30 - 2 * j)) & 3u];
+			p[j + 1] = letters[(w >> (28 - 2 * j)) & 3u];
+			p[j + 2] = letters[(w >> (26 - 2 * j)) & 3u];
+			p[j + 3] = letters[(w >> (24 - 2 * j)) & 3u];
+		}
 	}
+	for (; g < end; g++) *p++ = letters[(words[g >> 4] >> (30 - 2 * (int)(g & 15))) & 3u];
 	*p++ = '\n';
 	return p;
 }

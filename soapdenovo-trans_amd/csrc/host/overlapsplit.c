@@ -2,25 +2,16 @@
 #include <stdlib.h>
 #include <string.h>
 #include "overlapsplit.h"
-
-static char *put_field(char *p, uint32_t v, char sep)
-{
-	char t[10];
-	int n = 0;
-	do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-	while (n) *p++ = t[--n];
-	*p++ = sep;
-	return p;
-}
+#include "putdec.h"
 
 char *sdt_put_overlap_line(char *p, const sdt_read_overlap *r)
 {
-	p = put_field(p, r->overlap, ' ');
-	p = put_field(p, r->mismatches, ' ');
-	p = put_field(p, r->insert, ' ');
-	p = put_field(p, r->start, ' ');
-	p = put_field(p, r->len, ' ');
-	return put_field(p, r->verdict, '\n');
+	p = sdt_put_dec(p, r->overlap, ' ');
+	p = sdt_put_dec(p, r->mismatches, ' ');
+	p = sdt_put_dec(p, r->insert, ' ');
+	p = sdt_put_dec(p, r->start, ' ');
+	p = sdt_put_dec(p, r->len, ' ');
+	return sdt_put_dec(p, r->verdict, '\n');
 }
 
 int sdt_overlap_record_ok(const sdt_read_overlap *r, uint64_t read_len)

@@ -1,15 +1,12 @@
 /* overlapsplit.h -- the host side of `sdt-kmers overlap` that needs no device: what a read's record line looks like, whether a record
  * can be that of a read of a given length, and the histogram of the fragment lengths (inserts) of the overlapping pairs with its
- * summary line.  Where a read goes is trimsplit.h's sdt_trim_route: sdt_read_overlap has start and len where sdt_read_trim has them.
+ * summary line.  Where a read goes is trimsplit.h's sdt_trim_route.
  * Plain C, no GPU library (include/sdt_gpu.h only for the types): tools/overlap_host_check.c links it on its own. */
 #ifndef SDT_OVERLAPSPLIT_H
 #define SDT_OVERLAPSPLIT_H
 #include <stddef.h>
 #include <stdio.h>
 #include "../../../include/sdt_gpu.h"
-
-_Static_assert(offsetof(sdt_read_overlap, start) == offsetof(sdt_read_trim, start) && offsetof(sdt_read_overlap, len) == offsetof(sdt_read_trim, len) &&
-                   sizeof(sdt_read_overlap) == sizeof(sdt_read_trim), "sdt_trim_route takes sdt_read_overlap records through a pointer cast");
 
 /* "overlap mismatches insert start len verdict\n"; returns the end of what it wrote (at most SDT_OVERLAP_LINE_MAX bytes) */
 enum { SDT_OVERLAP_LINE_MAX = 6 * 11 };

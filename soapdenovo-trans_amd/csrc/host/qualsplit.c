@@ -2,25 +2,16 @@
 #include <stdlib.h>
 #include <string.h>
 #include "qualsplit.h"
-
-static char *put_field(char *p, uint32_t v, char sep)
-{
-	char t[10];
-	int n = 0;
-	do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-	while (n) *p++ = t[--n];
-	*p++ = sep;
-	return p;
-}
+#include "putdec.h"
 
 char *sdt_put_qual_line(char *p, const sdt_read_quality *r)
 {
-	p = put_field(p, r->span, ' ');
-	p = put_field(p, r->low, ' ');
-	p = put_field(p, r->ee_ppm, ' ');
-	p = put_field(p, r->start, ' ');
-	p = put_field(p, r->len, ' ');
-	return put_field(p, r->verdict, '\n');
+	p = sdt_put_dec(p, r->span, ' ');
+	p = sdt_put_dec(p, r->low, ' ');
+	p = sdt_put_dec(p, r->ee_ppm, ' ');
+	p = sdt_put_dec(p, r->start, ' ');
+	p = sdt_put_dec(p, r->len, ' ');
+	return sdt_put_dec(p, r->verdict, '\n');
 }
 
 int sdt_qual_drop_cause(const sdt_read_quality *r, const sdt_quality_params *p)

@@ -1,16 +1,12 @@
 /* qualsplit.h -- the host side of `sdt-kmers qtrim` that needs no device: what a read's record line looks like, whether a record can
  * be that of a read of a given length under given parameters, which line of the verdict dropped a read, and the histogram of the kept
- * lengths with its summary line.  Where a read goes is trimsplit.h's sdt_trim_route: sdt_read_quality has start and len where
- * sdt_read_trim has them.
+ * lengths with its summary line.  Where a read goes is trimsplit.h's sdt_trim_route.
  * Plain C, no GPU library (include/sdt_gpu.h only for the types): tools/quality_host_check.c links it on its own. */
 #ifndef SDT_QUALSPLIT_H
 #define SDT_QUALSPLIT_H
 #include <stddef.h>
 #include <stdio.h>
 #include "../../../include/sdt_gpu.h"
-
-_Static_assert(offsetof(sdt_read_quality, start) == offsetof(sdt_read_trim, start) && offsetof(sdt_read_quality, len) == offsetof(sdt_read_trim, len) &&
-                   sizeof(sdt_read_quality) == sizeof(sdt_read_trim), "sdt_trim_route takes sdt_read_quality records through a pointer cast");
 
 /* "span low ee_ppm start len verdict\n"; returns the end of what it wrote (at most SDT_QUAL_LINE_MAX bytes) */
 enum { SDT_QUAL_LINE_MAX = 6 * 11 };

@@ -2,6 +2,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "screensplit.h"
+#include "putdec.h"
 
 static int grow(void **p, uint64_t *cap, uint64_t need, size_t elem)
 {
@@ -136,22 +137,12 @@ void sdt_refs_free(sdt_ref_set *s)
 	memset(s, 0, sizeof *s);
 }
 
-static char *put_field(char *p, uint32_t v, char sep)
-{
-	char t[10];
-	int n = 0;
-	do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-	while (n) *p++ = t[--n];
-	*p++ = sep;
-	return p;
-}
-
 char *sdt_put_screen_line(char *p, const sdt_read_screen *r)
 {
-	p = put_field(p, r->kmers, ' ');
-	p = put_field(p, r->hits, ' ');
-	p = put_field(p, r->ref == SDT_SCREEN_NO_REF ? 0u : r->ref + 1, ' ');
-	return put_field(p, r->verdict, '\n');
+	p = sdt_put_dec(p, r->kmers, ' ');
+	p = sdt_put_dec(p, r->hits, ' ');
+	p = sdt_put_dec(p, r->ref == SDT_SCREEN_NO_REF ? 0u : r->ref + 1, ' ');
+	return sdt_put_dec(p, r->verdict, '\n');
 }
 
 int sdt_screen_matched(const sdt_read_screen *r, const sdt_screen_params *prm)

@@ -1,16 +1,12 @@
 /* screensplit.h -- the host side of `sdt-kmers screen` that needs no device: the reference files (FASTA) as the packed segments that
  * sdt_gpu_screen_load takes, what a read's record line looks like, whether a record can be that of a read of a given length, and the
- * statistics per reference with their summary line.  Where a read goes is trimsplit.h's sdt_trim_route: sdt_read_screen has start and
- * len where sdt_read_trim has them.
+ * statistics per reference with their summary line.  Where a read goes is trimsplit.h's sdt_trim_route.
  * Plain C, no GPU library (include/sdt_gpu.h only for the types): tools/screen_host_check.c links it on its own. */
 #ifndef SDT_SCREENSPLIT_H
 #define SDT_SCREENSPLIT_H
 #include <stddef.h>
 #include <stdio.h>
 #include "../../../include/sdt_gpu.h"
-
-_Static_assert(offsetof(sdt_read_screen, start) == offsetof(sdt_read_trim, start) && offsetof(sdt_read_screen, len) == offsetof(sdt_read_trim, len) &&
-                   sizeof(sdt_read_screen) == sizeof(sdt_read_trim), "sdt_trim_route takes sdt_read_screen records through a pointer cast");
 
 /* The references of one or more FASTA files, in the order they were read: reference i has names[i] (the header up to the first blank)
  * and bases[i] letters A, C, G, T.  Every other letter cuts the reference: the stretches between are the segments, packed like reads

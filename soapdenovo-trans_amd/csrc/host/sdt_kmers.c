@@ -82,7 +82,10 @@
  *       prefix.screen.pairs.fa / prefix.screen.single.fa: the surviving reads, as clip writes them
  *       prefix.screenStats: per reference  index name bases reads hits,  then  # reads R matched M kept K dropped D
  *
- * The query file is read and checked before the device is touched. */
+ * The query file is read and checked before the device is touched.
+ *
+ * What a read stage does after the device has decided -- the record lines and the two FASTA files, by ordinal -- is one walk for all of
+ * them (readwalk.c); a stage here is its device calls, a few callbacks for the walk, its statistics file and its summary line. */
 #include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -93,6 +96,8 @@
 #include "libcfg.h"
 #include "seqio.h"
 #include "readstream.h"
+#include "putdec.h"
+#include "readwalk.h"
 #include "normsplit.h"
 #include "trimsplit.h"
 #include "dupsplit.h"
@@ -217,6 +222,15 @@ static void usage(void)
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
+/* "call the ABI, on failure print and leave": 0 when the entry point returned SDT_OK; otherwise 1, after `<entry point>: <error>` has
+ * gone to stderr (the twin of sdt-pregraph's, which knows about ranks: pg_ranks.h) */
+static int gpu_fail(const char *entry)
+{
+	fprintf(stderr, "%s: %s\n", entry, sdt_gpu_last_error());
+	return 1;
+}
+#define SDT_CALL(fn, ...) (fn(__VA_ARGS__) == SDT_OK ? 0 : gpu_fail(#fn))
+
 /* pooled batches (pinned buffers, seqio.h) are pushed asynchronously, as sdt-pregraph does */
 #define PUSH_DEPTH 12
 static struct { int slot[PUSH_DEPTH]; uint64_t ticket[PUSH_DEPTH]; int head, n; } g_inflight;
@@ -224,7 +238,7 @@ static struct { int slot[PUSH_DEPTH]; uint64_t ticket[PUSH_DEPTH]; int head, n; 
 static int inflight_retire(sdt_ctx *gpu, int down_to)
 {
 	while (g_inflight.n > down_to) {
-		if (sdt_gpu_push_wait(gpu, g_inflight.ticket[g_inflight.head]) != SDT_OK) { fprintf(stderr, "sdt_gpu_push_wait: %s\n", sdt_gpu_last_error()); return -1; }
+		if (SDT_CALL(sdt_gpu_push_wait, gpu, g_inflight.ticket[g_inflight.head])) return -1;
 		sdt_pool_release(g_inflight.slot[g_inflight.head]);
 		g_inflight.head = (g_inflight.head + 1) % PUSH_DEPTH;
 		g_inflight.n--;
@@ -245,7 +259,7 @@ static int push_batch(void *user, const sdt_batch *b, uint64_t ord_base, uint64_
 		uint64_t ticket = 0;
 		const int rc = b->fixed_len ? sdt_gpu_push_reads_fixed_async(st->gpu, b->words, b->nwords, b->nreads, b->fixed_len, &ticket)
 		                            : sdt_gpu_push_reads_async(st->gpu, b->words, b->nwords, b->offsets, b->nreads, &ticket);
-		if (rc != SDT_OK) { fprintf(stderr, "sdt_gpu_push_reads_async: %s\n", sdt_gpu_last_error()); return -1; }
+		if (rc != SDT_OK) { gpu_fail("sdt_gpu_push_reads_async"); return -1; }
 		if (inflight_retire(st->gpu, PUSH_DEPTH - 1) != 0) return -1;
 		const int at = (g_inflight.head + g_inflight.n) % PUSH_DEPTH;
 		g_inflight.slot[at] = b->pool_slot;
@@ -254,133 +268,95 @@ static int push_batch(void *user, const sdt_batch *b, uint64_t ord_base, uint64_
 		sdt_pool_take(b->pool_slot);
 		return 0;
 	}
-	if (sdt_gpu_push_reads(st->gpu, b->words, b->nwords, b->offsets, b->nreads) != SDT_OK) {
-		fprintf(stderr, "sdt_gpu_push_reads: %s\n", sdt_gpu_last_error());
-		return -1;
-	}
-	return 0;
+	return SDT_CALL(sdt_gpu_push_reads, st->gpu, b->words, b->nwords, b->offsets, b->nreads) ? -1 : 0;
 }
 
-static char *put_u32(char *p, uint32_t v, char sep)
+/* everything the command line says, and what the files it names held */
+enum { MAX_REF_FILES = 256 };
+typedef struct { char **text; uint64_t *keys; uint64_t n, cap; } query_set;
+typedef struct qtrim_state qtrim_state;
+typedef struct {
+	char cfgfile[4096], outname[4096], qfile[4096];
+	int K, threads, d, max_k, device;
+	unsigned long min_count;
+	sdt_norm_params norm;
+	sdt_trim_params trim;
+	sdt_dedup_params dedup;
+	sdt_clip_params clip;
+	char afile[2][4096];                                                     /* -a: 3' adapters, -g: 5' adapters */
+	sdt_overlap_params overlap;
+	sdt_complexity_params cx;
+	int max_low_given;
+	sdt_quality_params qual;
+	sdt_screen_params screen;
+	uint32_t screen_k;
+	char *rfile[MAX_REF_FILES];
+	int n_rfiles;
+	sdt_adapter_list ads;                                                    /* of afile[] */
+	sdt_ref_set refs;                                                        /* of rfile[] */
+	query_set qs;                                                            /* of qfile */
+	qtrim_state *qtrim;                                                      /* qtrim's records, taken while the reads streamed */
+} options;
+
+/* ---- the device half that every read stage shares ------------------------------------------------------------------------------------ */
+
+/* by ordinal, every byte `fill` (0xFF: an ordinal that no read has keeps verdict 0xFFFFFFFF); NULL after saying that memory ran out */
+static void *records_alloc(unsigned long long reads, size_t size, int fill)
 {
-	char t[10];
-	int n = 0;
-	do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-	while (n) *p++ = t[--n];
-	*p++ = sep;
-	return p;
+	const uint64_t m = reads ? reads : 1;
+	void *rec = fill ? malloc(m * size) : calloc(m, size);
+	if (!rec) fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads);
+	else if (fill) memset(rec, fill, m * size);
+	return rec;
 }
 
-/* prefix.readCov: "kmers found solid min median max" per read (8 M reads are 180 MB of digits: formatted by hand into a block buffer) */
-static int write_read_cov(const char *path, const sdt_read_cov *cov, unsigned long long n)
+static int all_reads_came_back(unsigned long long reads, uint64_t got, const char *done)
 {
-	FILE *fo = fopen(path, "w");
-	if (!fo) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path); return -1; }
-	enum { BLOCK = 1 << 20, LINE_MAX_BYTES = 6 * 11 };
-	char *buf = (char *)malloc(BLOCK), *p = buf;
-	int ok = buf != NULL;
-	for (unsigned long long i = 0; ok && i < n; i++) {
-		p = put_u32(p, cov[i].kmers, ' ');
-		p = put_u32(p, cov[i].found, ' ');
-		p = put_u32(p, cov[i].solid, ' ');
-		p = put_u32(p, cov[i].min, ' ');
-		p = put_u32(p, cov[i].median, ' ');
-		p = put_u32(p, cov[i].max, '\n');
-		if (p - buf > BLOCK - LINE_MAX_BYTES) { ok = fwrite(buf, 1, (size_t)(p - buf), fo) == (size_t)(p - buf); p = buf; }
-	}
-	if (ok && p != buf) ok = fwrite(buf, 1, (size_t)(p - buf), fo) == (size_t)(p - buf);
-	free(buf);
-	if (fclose(fo) != 0) ok = 0;
-	if (!ok) fprintf(stderr, "sdt-kmers: write to %s failed\n", path);
-	return ok ? 0 : -1;
-}
-
-/* text formatted by hand into a block buffer, as write_read_cov does */
-typedef struct { FILE *f; char *buf, *p; int ok; const char *path; } outbuf;
-enum { OB_BLOCK = 1 << 20 };
-
-static int ob_open(outbuf *o, const char *path)
-{
-	o->path = path;
-	o->f = fopen(path, "w");
-	if (!o->f) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path); return -1; }
-	o->buf = o->p = (char *)malloc(OB_BLOCK);
-	o->ok = 1;
-	if (!o->buf) { fprintf(stderr, "sdt-kmers: out of memory\n"); fclose(o->f); o->f = NULL; return -1; }
-	return 0;
-}
-
-/* room for `need` more bytes (need <= OB_BLOCK); after a failed write the block is dropped, never overrun: the caller stops on !ok */
-static void ob_room(outbuf *o, size_t need)
-{
-	if ((size_t)(o->p - o->buf) + need > OB_BLOCK) {
-		if (o->ok) o->ok = fwrite(o->buf, 1, (size_t)(o->p - o->buf), o->f) == (size_t)(o->p - o->buf);
-		o->p = o->buf;
-	}
-}
-
-static int ob_close(outbuf *o)
-{
-	if (o->ok && o->p != o->buf) o->ok = fwrite(o->buf, 1, (size_t)(o->p - o->buf), o->f) == (size_t)(o->p - o->buf);
-	free(o->buf);
-	if (fclose(o->f) != 0) o->ok = 0;
-	if (!o->ok) fprintf(stderr, "sdt-kmers: write to %s failed\n", o->path);
-	return o->ok ? 0 : -1;
-}
-
-static char *put_u64(char *p, uint64_t v, char sep)
-{
-	char t[20];
-	int n = 0;
-	do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-	while (n) *p++ = t[--n];
-	*p++ = sep;
-	return p;
+	if (got != reads) fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu %s\n", reads, (unsigned long long)got, done);
+	return got == reads;
 }
 
 /* the kept batches back from HBM, and where every ordinal's read is */
-typedef struct {
-	uint64_t nb, longest;
-	uint32_t **bw;                                                           /* words of batch b */
-	uint64_t **bo;                                                           /* offsets of batch b */
-	uint32_t *at_batch, *at_read;                                            /* by ordinal; at_batch 0xFFFFFFFF: no kept read has it */
-} kept_reads;
-
 static int kept_fetch(sdt_ctx *gpu, unsigned long long reads, kept_reads *k)
 {
-	const uint64_t m = reads ? reads : 1;
-	memset(k, 0, sizeof *k);
-	if (sdt_gpu_kept_batches(gpu, &k->nb) != SDT_OK) { fprintf(stderr, "sdt_gpu_kept_batches: %s\n", sdt_gpu_last_error()); return 1; }
-	k->bw = (uint32_t **)calloc(k->nb ? k->nb : 1, sizeof(uint32_t *));
-	k->bo = (uint64_t **)calloc(k->nb ? k->nb : 1, sizeof(uint64_t *));
-	k->at_batch = (uint32_t *)malloc(m * sizeof(uint32_t));
-	k->at_read = (uint32_t *)malloc(m * sizeof(uint32_t));
-	if (!k->bw || !k->bo || !k->at_batch || !k->at_read) { fprintf(stderr, "sdt-kmers: out of memory\n"); return 1; }
-	memset(k->at_batch, 0xFF, m * sizeof(uint32_t));
-	for (uint64_t b = 0; b < k->nb; b++) {
+	uint64_t nb = 0;
+	if (SDT_CALL(sdt_gpu_kept_batches, gpu, &nb) || kept_init(k, nb, reads)) return 1;
+	for (uint64_t b = 0; b < nb; b++) {
 		uint64_t info[4];
-		if (sdt_gpu_fetch_kept_batch(gpu, b, info, NULL, 0, NULL, 0) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
-		k->bw[b] = (uint32_t *)malloc((info[0] ? info[0] : 1) * sizeof(uint32_t));
-		k->bo[b] = (uint64_t *)malloc((info[1] + 1) * sizeof(uint64_t));
-		if (!k->bw[b] || !k->bo[b]) { fprintf(stderr, "sdt-kmers: out of memory for the reads\n"); return 1; }
-		if (sdt_gpu_fetch_kept_batch(gpu, b, info, k->bw[b], info[0], k->bo[b], info[1] + 1) != SDT_OK) { fprintf(stderr, "sdt_gpu_fetch_kept_batch: %s\n", sdt_gpu_last_error()); return 1; }
-		for (uint64_t i = 0; i < info[1]; i++) {
-			const uint64_t ord = info[2] + i * info[3];
-			if (ord >= reads) { fprintf(stderr, "sdt-kmers: a kept read has ordinal %llu of %llu\n", (unsigned long long)ord, reads); return 1; }
-			k->at_batch[ord] = (uint32_t)b;
-			k->at_read[ord] = (uint32_t)i;
-			if (k->bo[b][i + 1] - k->bo[b][i] > k->longest) k->longest = k->bo[b][i + 1] - k->bo[b][i];
-		}
+		if (SDT_CALL(sdt_gpu_fetch_kept_batch, gpu, b, info, NULL, 0, NULL, 0)) return 1;
+		uint32_t *w = (uint32_t *)malloc((info[0] ? info[0] : 1) * sizeof(uint32_t));
+		uint64_t *o = (uint64_t *)malloc((info[1] + 1) * sizeof(uint64_t));
+		if (!w || !o) { fprintf(stderr, "sdt-kmers: out of memory for the reads\n"); return 1; }
+		if (SDT_CALL(sdt_gpu_fetch_kept_batch, gpu, b, info, w, info[0], o, info[1] + 1)) return 1;
+		if (kept_add(k, b, w, o, info[1], info[2], info[3])) return 1;
 	}
-	if (k->longest + 64 > OB_BLOCK) { fprintf(stderr, "sdt-kmers: a read of %llu bases\n", (unsigned long long)k->longest); return 1; }
 	return 0;
 }
 
-static void kept_free(kept_reads *k)
+/* the kept batches back from HBM, walked by ordinal into the stage's three files under the prefix (readwalk.h), and released */
+static int fetch_and_walk(sdt_ctx *gpu, unsigned long long reads, const sdt_pair_ranges *pairs, const char *prefix, const sdt_walk_stage *stage, void *state,
+                          uint64_t n_kept, sdt_walk_tally *tally)
 {
-	for (uint64_t b = 0; b < k->nb; b++) { free(k->bw[b]); free(k->bo[b]); }
-	free(k->bw); free(k->bo); free(k->at_batch); free(k->at_read);
+	kept_reads k;
+	if (kept_fetch(gpu, reads, &k) != 0 || sdt_walk_reads(&k, pairs, prefix, stage, state, n_kept, tally) != 0) return 1;
+	kept_free(&k);
+	return 0;
 }
+
+/* a stage's statistics file, prefix + suffix; NULL: it cannot be written */
+static FILE *stats_open(char path[4200], const char *prefix, const char *suffix)
+{
+	snprintf(path, 4200, "%s%s", prefix, suffix);
+	return fopen(path, "w");
+}
+
+static int cannot_write(const char *path)
+{
+	fprintf(stderr, "sdt-kmers: cannot write %s\n", path);
+	return 1;
+}
+
+/* ---- correct, and the edits of `trim --correct` -------------------------------------------------------------------------------------- */
 
 /* sdt_gpu_correct_kept_reads: fix[] by ordinal and the edits, ascending, in a list of the size they need */
 static int correct_kept(sdt_ctx *gpu, unsigned long long reads, uint32_t min_count, sdt_read_fix *fix, uint64_t **edits_out, uint64_t *n_edits_out)
@@ -397,11 +373,20 @@ static int correct_kept(sdt_ctx *gpu, unsigned long long reads, uint32_t min_cou
 		if (!edits) { fprintf(stderr, "sdt-kmers: out of memory for %llu edits\n", (unsigned long long)cap); return 1; }
 		rc = sdt_gpu_correct_kept_reads(gpu, min_count, fix, reads, &got, edits, cap, &n_edits);
 	}
-	if (rc != SDT_OK) { fprintf(stderr, "sdt_gpu_correct_kept_reads: %s\n", sdt_gpu_last_error()); return 1; }
-	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu corrected\n", reads, (unsigned long long)got); return 1; }
+	if (rc != SDT_OK) return gpu_fail("sdt_gpu_correct_kept_reads");
+	if (!all_reads_came_back(reads, got, "corrected")) return 1;
 	*edits_out = edits;
 	*n_edits_out = n_edits;
 	return 0;
+}
+
+/* the edits on their way into the reads and into prefix.edits: the first member of the state of the two stages that have them */
+typedef struct { outbuf oe; char path[4200]; uint64_t *edits, n, e; } edit_walk;
+
+static int edits_open(edit_walk *ed, const char *prefix)
+{
+	snprintf(ed->path, sizeof ed->path, "%s.edits", prefix);
+	return ob_open(&ed->oe, ed->path);
 }
 
 /* one edit of read `ord` (its bases from `start` of w, len of them) applied to the words and written as "read pos from to"; -1: the
@@ -415,8 +400,8 @@ static int apply_edit(outbuf *oe, uint64_t edit, uint64_t ord, uint32_t *w, uint
 	const uint32_t old = (w[g >> 4] >> sh) & 3u, neu = (uint32_t)(edit & 3u);
 	w[g >> 4] ^= (old ^ neu) << sh;
 	ob_room(oe, 2 * 21 + 4);
-	oe->p = put_u64(oe->p, ord + 1, ' ');
-	oe->p = put_u64(oe->p, pos + 1, ' ');
+	oe->p = sdt_put_dec(oe->p, ord + 1, ' ');
+	oe->p = sdt_put_dec(oe->p, pos + 1, ' ');
 	*oe->p++ = letters[old];
 	*oe->p++ = ' ';
 	*oe->p++ = letters[neu];
@@ -424,529 +409,427 @@ static int apply_edit(outbuf *oe, uint64_t edit, uint64_t ord, uint32_t *w, uint
 	return 0;
 }
 
-/* `correct`: the records and the edits from the device, the kept batches back from HBM, the edits applied here */
-static int correct_and_write(sdt_ctx *gpu, unsigned long long reads, uint32_t min_count, const char *prefix)
+/* sdt_walk_stage.edit: the edits of read `ord` */
+static int edits_apply(void *state, uint64_t ord, uint32_t *w, uint64_t start, uint64_t len)
 {
-	const uint64_t m = reads ? reads : 1;
-	sdt_read_fix *fix = (sdt_read_fix *)calloc(m, sizeof(sdt_read_fix));
-	uint64_t *edits = NULL, n_edits = 0;
-	if (!fix) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
-	if (correct_kept(gpu, reads, min_count, fix, &edits, &n_edits) != 0) return 1;
-	kept_reads k;
-	if (kept_fetch(gpu, reads, &k) != 0) return 1;
-	char path[3][4200];
-	snprintf(path[0], sizeof path[0], "%s.readFix", prefix);
-	snprintf(path[1], sizeof path[1], "%s.edits", prefix);
-	snprintf(path[2], sizeof path[2], "%s.corrected.fa", prefix);
-	outbuf of, oe, oa;
-	if (ob_open(&of, path[0]) != 0) return 1;
-	if (ob_open(&oe, path[1]) != 0) { ob_close(&of); return 1; }
-	if (ob_open(&oa, path[2]) != 0) { ob_close(&of); ob_close(&oe); return 1; }
-	unsigned long long with_weak = 0, runs = 0, fixed = 0;
-	uint64_t e = 0;
-	int bad = 0;
-	for (uint64_t ord = 0; ord < reads && !bad; ord++) {
-		if (!of.ok || !oe.ok || !oa.ok) break;                               /* a write failed: ob_close says which */
-		ob_room(&of, 4 * 11);
-		of.p = put_u32(of.p, fix[ord].kmers, ' ');
-		of.p = put_u32(of.p, fix[ord].weak, ' ');
-		of.p = put_u32(of.p, fix[ord].runs, ' ');
-		of.p = put_u32(of.p, fix[ord].fixed, '\n');
-		with_weak += fix[ord].weak != 0;
-		runs += fix[ord].runs;
-		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
-		uint32_t *w = k.bw[k.at_batch[ord]];
-		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
-		for (; e < n_edits && (edits[e] >> 18) == ord && !bad; e++, fixed++)
-			bad = apply_edit(&oe, edits[e], ord, w, start, len) != 0;
-		ob_room(&oa, (size_t)len + 24);
-		oa.p = sdt_put_fasta_record(oa.p, ord, w, start, len);
-	}
-	const int all_written = of.ok && oe.ok && oa.ok;
-	if ((ob_close(&of) != 0) | (ob_close(&oe) != 0) | (ob_close(&oa) != 0) || bad) return 1;
-	if (all_written && e != n_edits) { fprintf(stderr, "sdt-kmers: %llu of %llu edits name no read of the stream\n", (unsigned long long)(n_edits - e), (unsigned long long)n_edits); return 1; }
-	kept_free(&k);
-	free(fix); free(edits);
-	printf("%llu reads, %llu with weak k-mers, %llu runs, %llu bases corrected into %s\n", reads, with_weak, runs, fixed, path[2]);
+	edit_walk *ed = (edit_walk *)state;
+	if (!ed->oe.ok) return -1;                                               /* a write failed: ob_close says which */
+	for (; ed->e < ed->n && (ed->edits[ed->e] >> 18) == ord; ed->e++)
+		if (apply_edit(&ed->oe, ed->edits[ed->e], ord, w, start, len) != 0) return -1;
 	return 0;
 }
 
-/* `normalize`: the verdicts from the device, the kept batches back from HBM, the kept reads into the pairs file or the singles file */
-static int normalize_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_norm_params *prm, const sdt_pair_ranges *pairs, const char *prefix)
+/* after the walk (walked: it went through): the file closed; 0 iff all of it is written and every edit named a read */
+static int edits_close(edit_walk *ed, int walked)
 {
-	const uint64_t m = reads ? reads : 1;
-	sdt_read_pick *pick = (sdt_read_pick *)malloc(m * sizeof(sdt_read_pick));
-	if (!pick) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
-	memset(pick, 0xFF, m * sizeof(sdt_read_pick));                           /* (an ordinal that no read has keeps verdict 0xFFFFFFFF) */
-	uint64_t got = 0, n_kept = 0;
-	if (sdt_gpu_select_kept_reads(gpu, prm, pairs->v, pairs->n, pick, reads, &got, &n_kept) != SDT_OK) {
-		fprintf(stderr, "sdt_gpu_select_kept_reads: %s\n", sdt_gpu_last_error());
+	if (ob_close(&ed->oe) != 0 || !walked) return 1;
+	if (ed->e != ed->n) {
+		fprintf(stderr, "sdt-kmers: %llu of %llu edits name no read of the stream\n", (unsigned long long)(ed->n - ed->e), (unsigned long long)ed->n);
 		return 1;
 	}
-	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu decided\n", reads, (unsigned long long)got); return 1; }
-	kept_reads k;
-	if (kept_fetch(gpu, reads, &k) != 0) return 1;
-	char path[3][4200];
-	snprintf(path[0], sizeof path[0], "%s.readPick", prefix);
-	snprintf(path[1], sizeof path[1], "%s.norm.pairs.fa", prefix);
-	snprintf(path[2], sizeof path[2], "%s.norm.single.fa", prefix);
-	outbuf opick, opair, osingle;
-	if (ob_open(&opick, path[0]) != 0) return 1;
-	if (ob_open(&opair, path[1]) != 0) { ob_close(&opick); return 1; }
-	if (ob_open(&osingle, path[2]) != 0) { ob_close(&opick); ob_close(&opair); return 1; }
-	unsigned long long kept = 0, n_short = 0, aberrant = 0, drawn = 0;
-	size_t cursor = 0;
-	int bad = 0;
-	for (uint64_t ord = 0; ord < reads; ord++) {
-		if (!opick.ok || !opair.ok || !osingle.ok) break;                               /* a write failed: ob_close says which */
-		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
-		ob_room(&opick, 4 * 11);
-		opick.p = put_u32(opick.p, pick[ord].kmers, ' ');
-		opick.p = put_u32(opick.p, pick[ord].median, ' ');
-		opick.p = put_u32(opick.p, pick[ord].cov, ' ');
-		opick.p = put_u32(opick.p, pick[ord].verdict, '\n');
-		const uint32_t cls = pick[ord].verdict & 7u;
-		n_short += cls == 4;
-		aberrant += cls == 3;
-		drawn += cls == 2;
-		if (cls > 1) continue;
-		kept++;
-		outbuf *o = sdt_pair_ranges_holds(pairs, ord, &cursor) ? &opair : &osingle;
-		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
-		ob_room(o, (size_t)len + 24);
-		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start, len);
-	}
-	if ((ob_close(&opick) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
-	if (kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
-	kept_free(&k);
-	free(pick);
-	printf("%llu of %llu reads kept (%llu short, %llu aberrant, %llu dropped by draw)\n", kept, reads, n_short, aberrant, drawn);
+	free(ed->edits);
 	return 0;
 }
+
+typedef struct { edit_walk ed; const sdt_read_fix *rec; unsigned long long with_weak, runs; } correct_state;
+
+static int correct_note(void *state, uint64_t ord, uint64_t read_len, uint64_t *start, uint64_t *len)
+{
+	correct_state *s = (correct_state *)state;
+	(void)read_len; (void)start; (void)len;                                  /* every read is kept whole */
+	s->with_weak += s->rec[ord].weak != 0;
+	s->runs += s->rec[ord].runs;
+	return 0;
+}
+
+static char *correct_line(const void *state, char *p, uint64_t ord)
+{
+	const sdt_read_fix *r = ((const correct_state *)state)->rec + ord;
+	p = sdt_put_dec(p, r->kmers, ' ');
+	p = sdt_put_dec(p, r->weak, ' ');
+	p = sdt_put_dec(p, r->runs, ' ');
+	return sdt_put_dec(p, r->fixed, '\n');
+}
+
+static int correct_alive(const void *state, uint64_t ord)
+{
+	(void)state; (void)ord;
+	return 1;
+}
+
+/* `correct`: the records and the edits from the device, the kept batches back from HBM, the edits applied on the way into the one file */
+static int run_correct(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	static const sdt_walk_stage stage = {{".readFix", NULL, ".corrected.fa"}, 4 * 11, 1, correct_note, correct_line, correct_alive, edits_apply};
+	sdt_read_fix *fix = (sdt_read_fix *)records_alloc(reads, sizeof *fix, 0);
+	correct_state st;
+	memset(&st, 0, sizeof st);
+	if (!fix || correct_kept(gpu, reads, (uint32_t)opt->min_count, fix, &st.ed.edits, &st.ed.n) != 0) return 1;
+	st.rec = fix;
+	sdt_walk_tally t;
+	if (edits_open(&st.ed, opt->outname) != 0) return 1;
+	const int walked = fetch_and_walk(gpu, reads, pairs, opt->outname, &stage, &st, reads, &t) == 0;
+	const unsigned long long fixed = st.ed.e;
+	if (edits_close(&st.ed, walked) != 0) return 1;
+	printf("%llu reads, %llu with weak k-mers, %llu runs, %llu bases corrected into %s.corrected.fa\n", reads, st.with_weak, st.runs, fixed, opt->outname);
+	free(fix);
+	return 0;
+}
+
+/* ---- normalize ------------------------------------------------------------------------------------------------------------------------- */
+typedef struct { const sdt_read_pick *rec; unsigned long long n_short, aberrant, drawn; } norm_state;
+
+static int norm_note(void *state, uint64_t ord, uint64_t read_len, uint64_t *start, uint64_t *len)
+{
+	norm_state *s = (norm_state *)state;
+	const uint32_t cls = s->rec[ord].verdict & 7u;
+	(void)read_len; (void)start; (void)len;                                  /* a kept read is kept whole */
+	s->n_short += cls == 4;
+	s->aberrant += cls == 3;
+	s->drawn += cls == 2;
+	return 0;
+}
+
+static char *norm_line(const void *state, char *p, uint64_t ord)
+{
+	const sdt_read_pick *r = ((const norm_state *)state)->rec + ord;
+	p = sdt_put_dec(p, r->kmers, ' ');
+	p = sdt_put_dec(p, r->median, ' ');
+	p = sdt_put_dec(p, r->cov, ' ');
+	return sdt_put_dec(p, r->verdict, '\n');
+}
+
+static int norm_alive(const void *state, uint64_t ord) { return (((const norm_state *)state)->rec[ord].verdict & 7u) <= 1; }
+
+/* `normalize`: the verdicts from the device, the kept batches back from HBM, the kept reads into the pairs file or the singles file */
+static int run_normalize(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	static const sdt_walk_stage stage = {{".readPick", ".norm.pairs.fa", ".norm.single.fa"}, 4 * 11, 1, norm_note, norm_line, norm_alive, NULL};
+	sdt_read_pick *pick = (sdt_read_pick *)records_alloc(reads, sizeof *pick, 0xFF);
+	uint64_t got = 0, n_kept = 0;
+	if (!pick || SDT_CALL(sdt_gpu_select_kept_reads, gpu, &opt->norm, pairs->v, pairs->n, pick, reads, &got, &n_kept)) return 1;
+	if (!all_reads_came_back(reads, got, "decided")) return 1;
+	norm_state st = {pick, 0, 0, 0};
+	sdt_walk_tally t;
+	if (fetch_and_walk(gpu, reads, pairs, opt->outname, &stage, &st, n_kept, &t) != 0) return 1;
+	printf("%llu of %llu reads kept (%llu short, %llu aberrant, %llu dropped by draw)\n", t.kept, reads, st.n_short, st.aberrant, st.drawn);
+	free(pick);
+	return 0;
+}
+
+/* ---- dedup ----------------------------------------------------------------------------------------------------------------------------- */
+typedef struct { const sdt_read_dup *rec; sdt_dup_levels lv; } dedup_state;
+
+static int dedup_note(void *state, uint64_t ord, uint64_t read_len, uint64_t *start, uint64_t *len)
+{
+	dedup_state *s = (dedup_state *)state;
+	const sdt_read_dup *r = s->rec + ord;
+	(void)read_len; (void)start; (void)len;                                  /* a kept read is kept whole */
+	if (r->verdict > 1 || r->copies == 0 || r->first > ord) {
+		fprintf(stderr, "sdt-kmers: the record of read %llu is %llu %u %u\n", (unsigned long long)ord + 1, (unsigned long long)r->first, r->copies, r->verdict);
+		return -1;
+	}
+	/* (every ordinal has a read here, so the first read of a kept unit is the one whose ordinal is the unit's id) */
+	if (sdt_dup_levels_note(&s->lv, r, r->verdict == 0 && r->first == ord) != 0) { fprintf(stderr, "sdt-kmers: out of memory\n"); return -1; }
+	return 0;
+}
+
+static char *dedup_line(const void *state, char *p, uint64_t ord) { return sdt_put_dup_line(p, ((const dedup_state *)state)->rec + ord); }
+static int dedup_alive(const void *state, uint64_t ord) { return ((const dedup_state *)state)->rec[ord].verdict == 0; }
 
 /* `dedup`: the records from the device, the kept batches back from HBM, the kept reads into the pairs file or the singles file, the
  * table of duplication levels (dupsplit.c) */
-static int dedup_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_dedup_params *prm, const sdt_pair_ranges *pairs, const char *prefix)
+static int run_dedup(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	const uint64_t m = reads ? reads : 1;
-	sdt_read_dup *dup = (sdt_read_dup *)malloc(m * sizeof(sdt_read_dup));
-	if (!dup) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
-	memset(dup, 0xFF, m * sizeof(sdt_read_dup));                             /* (an ordinal that no read has keeps verdict 0xFFFFFFFF) */
+	static const sdt_walk_stage stage = {{".readDup", ".dedup.pairs.fa", ".dedup.single.fa"}, SDT_DUP_LINE_MAX, 1, dedup_note, dedup_line, dedup_alive, NULL};
+	sdt_read_dup *dup = (sdt_read_dup *)records_alloc(reads, sizeof *dup, 0xFF);
 	uint64_t got = 0, n_kept = 0;
-	if (sdt_gpu_dedup_kept_reads(gpu, prm, pairs->v, pairs->n, dup, reads, &got, &n_kept) != SDT_OK) {
-		fprintf(stderr, "sdt_gpu_dedup_kept_reads: %s\n", sdt_gpu_last_error());
-		return 1;
-	}
-	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu decided\n", reads, (unsigned long long)got); return 1; }
-	kept_reads k;
-	if (kept_fetch(gpu, reads, &k) != 0) return 1;
-	char path[4][4200];
-	snprintf(path[0], sizeof path[0], "%s.readDup", prefix);
-	snprintf(path[1], sizeof path[1], "%s.dedup.pairs.fa", prefix);
-	snprintf(path[2], sizeof path[2], "%s.dedup.single.fa", prefix);
-	snprintf(path[3], sizeof path[3], "%s.dupLevels", prefix);
-	outbuf odup, opair, osingle, olev;
-	if (ob_open(&odup, path[0]) != 0) return 1;
-	if (ob_open(&opair, path[1]) != 0) { ob_close(&odup); return 1; }
-	if (ob_open(&osingle, path[2]) != 0) { ob_close(&odup); ob_close(&opair); return 1; }
-	if (ob_open(&olev, path[3]) != 0) { ob_close(&odup); ob_close(&opair); ob_close(&osingle); return 1; }
-	sdt_dup_levels lv;
-	memset(&lv, 0, sizeof lv);
-	unsigned long long kept = 0;
-	size_t cursor = 0;
-	int bad = 0;
-	for (uint64_t ord = 0; ord < reads; ord++) {
-		if (!odup.ok || !opair.ok || !osingle.ok) break;                                /* a write failed: ob_close says which */
-		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
-		const sdt_read_dup *r = dup + ord;
-		if (r->verdict > 1 || r->copies == 0 || r->first > ord) {
-			fprintf(stderr, "sdt-kmers: the record of read %llu is %llu %u %u\n", (unsigned long long)ord + 1, (unsigned long long)r->first, r->copies, r->verdict);
-			bad = 1;
-			break;
-		}
-		ob_room(&odup, SDT_DUP_LINE_MAX);
-		odup.p = sdt_put_dup_line(odup.p, r);
-		/* (every ordinal has a read here, so the first read of a kept unit is the one whose ordinal is the unit's id) */
-		if (sdt_dup_levels_note(&lv, r, r->verdict == 0 && r->first == ord) != 0) { fprintf(stderr, "sdt-kmers: out of memory\n"); bad = 1; break; }
-		if (r->verdict != 0) continue;
-		kept++;
-		outbuf *o = sdt_pair_ranges_holds(pairs, ord, &cursor) ? &opair : &osingle;
-		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
-		ob_room(o, (size_t)len + 24);
-		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start, len);
-	}
+	if (!dup || SDT_CALL(sdt_gpu_dedup_kept_reads, gpu, &opt->dedup, pairs->v, pairs->n, dup, reads, &got, &n_kept)) return 1;
+	if (!all_reads_came_back(reads, got, "decided")) return 1;
+	dedup_state st;
+	memset(&st, 0, sizeof st);
+	st.rec = dup;
+	sdt_walk_tally t;
+	if (fetch_and_walk(gpu, reads, pairs, opt->outname, &stage, &st, n_kept, &t) != 0) return 1;
+	char path[4200];
+	outbuf olev;
+	snprintf(path, sizeof path, "%s.dupLevels", opt->outname);
+	if (ob_open(&olev, path) != 0) return 1;
 	unsigned long long classes = 0;
-	for (size_t i = 0; i < lv.n && !bad; i++) {
+	for (size_t i = 0; i < st.lv.n; i++) {
 		ob_room(&olev, SDT_DUP_LEVEL_LINE_MAX);
-		olev.p = sdt_put_dup_level_line(olev.p, lv.v + i);
-		classes += lv.v[i].classes;
+		olev.p = sdt_put_dup_level_line(olev.p, st.lv.v + i);
+		classes += st.lv.v[i].classes;
 	}
-	sdt_dup_levels_free(&lv);
-	const int all_written = odup.ok && opair.ok && osingle.ok && olev.ok;
-	if ((ob_close(&odup) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) | (ob_close(&olev) != 0) || bad) return 1;
-	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
-	kept_free(&k);
+	if (ob_close(&olev) != 0) return 1;
+	printf("%llu of %llu reads kept in %llu classes\n", t.kept, reads, classes);
+	sdt_dup_levels_free(&st.lv);
 	free(dup);
-	printf("%llu of %llu reads kept in %llu classes\n", kept, reads, classes);
 	return 0;
 }
+
+/* ---- trim ------------------------------------------------------------------------------------------------------------------------------ */
+typedef struct { edit_walk ed; const sdt_read_trim *rec; unsigned long long by_verdict[5]; } trim_state;
+
+static int trim_note(void *state, uint64_t ord, uint64_t read_len, uint64_t *start, uint64_t *len)
+{
+	trim_state *s = (trim_state *)state;
+	const sdt_read_trim *t = s->rec + ord;
+	if (t->verdict > 4 || (uint64_t)t->start + t->len > read_len) {
+		fprintf(stderr, "sdt-kmers: the record of read %llu keeps [%u, %u + %u) of %llu bases, verdict %u\n", (unsigned long long)ord + 1, t->start,
+		        t->start, t->len, (unsigned long long)read_len, t->verdict);
+		return -1;
+	}
+	s->by_verdict[t->verdict]++;
+	*start = t->start;
+	*len = t->len;
+	return 0;
+}
+
+static char *trim_line(const void *state, char *p, uint64_t ord) { return sdt_put_trim_line(p, ((const trim_state *)state)->rec + ord); }
+static int trim_alive(const void *state, uint64_t ord) { return ((const trim_state *)state)->rec[ord].len != 0; }
 
 /* `trim`: the records (and with --correct the edits) from the device, the kept batches back from HBM, the edits applied here, the kept
  * bases of every read into the pairs file (both mates survive) or the singles file (trimsplit.c) */
-static int trim_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_trim_params *prm, const sdt_pair_ranges *pairs, const char *prefix)
+static int run_trim(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	const uint64_t m = reads ? reads : 1;
-	const int correct = (prm->flags & SDT_TRIM_CORRECTED) != 0;
-	sdt_read_trim *trim = (sdt_read_trim *)calloc(m, sizeof(sdt_read_trim));
-	sdt_read_fix *fix = correct ? (sdt_read_fix *)calloc(m, sizeof(sdt_read_fix)) : NULL;
-	if (!trim || (correct && !fix)) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
-	uint64_t got = 0, n_kept = 0, *edits = NULL, n_edits = 0;
-	if (sdt_gpu_trim_kept_reads(gpu, prm, trim, reads, &got, &n_kept) != SDT_OK) {
-		fprintf(stderr, "sdt_gpu_trim_kept_reads: %s\n", sdt_gpu_last_error());
-		return 1;
+	sdt_walk_stage stage = {{".readTrim", ".trim.pairs.fa", ".trim.single.fa"}, SDT_TRIM_LINE_MAX, 0, trim_note, trim_line, trim_alive, NULL};
+	const int correct = (opt->trim.flags & SDT_TRIM_CORRECTED) != 0;
+	opt->trim.min_count = (uint32_t)opt->min_count;
+	sdt_read_trim *trim = (sdt_read_trim *)records_alloc(reads, sizeof *trim, 0);
+	sdt_read_fix *fix = correct ? (sdt_read_fix *)records_alloc(reads, sizeof *fix, 0) : NULL;
+	uint64_t got = 0, n_kept = 0;
+	if (!trim || (correct && !fix) || SDT_CALL(sdt_gpu_trim_kept_reads, gpu, &opt->trim, trim, reads, &got, &n_kept)) return 1;
+	if (!all_reads_came_back(reads, got, "trimmed")) return 1;
+	trim_state st;
+	memset(&st, 0, sizeof st);
+	st.rec = trim;
+	if (correct && correct_kept(gpu, reads, opt->trim.min_count, fix, &st.ed.edits, &st.ed.n) != 0) return 1;
+	sdt_walk_tally t;
+	if (correct) {
+		if (edits_open(&st.ed, opt->outname) != 0) return 1;
+		stage.edit = edits_apply;
 	}
-	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu trimmed\n", reads, (unsigned long long)got); return 1; }
-	if (correct && correct_kept(gpu, reads, prm->min_count, fix, &edits, &n_edits) != 0) return 1;
-	kept_reads k;
-	if (kept_fetch(gpu, reads, &k) != 0) return 1;
-	char path[4][4200];
-	snprintf(path[0], sizeof path[0], "%s.readTrim", prefix);
-	snprintf(path[1], sizeof path[1], "%s.trim.pairs.fa", prefix);
-	snprintf(path[2], sizeof path[2], "%s.trim.single.fa", prefix);
-	snprintf(path[3], sizeof path[3], "%s.edits", prefix);
-	outbuf otrim, opair, osingle, oe;
-	if (ob_open(&otrim, path[0]) != 0) return 1;
-	if (ob_open(&opair, path[1]) != 0) { ob_close(&otrim); return 1; }
-	if (ob_open(&osingle, path[2]) != 0) { ob_close(&otrim); ob_close(&opair); return 1; }
-	if (correct && ob_open(&oe, path[3]) != 0) { ob_close(&otrim); ob_close(&opair); ob_close(&osingle); return 1; }
-	unsigned long long by_verdict[5] = {0, 0, 0, 0, 0}, kept = 0, bases_in = 0, bases_out = 0;
-	size_t cursor = 0;
-	uint64_t e = 0;
-	int bad = 0;
-	for (uint64_t ord = 0; ord < reads && !bad; ord++) {
-		if (!otrim.ok || !opair.ok || !osingle.ok || (correct && !oe.ok)) break;    /* a write failed: ob_close says which */
-		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
-		const sdt_read_trim *t = trim + ord;
-		ob_room(&otrim, SDT_TRIM_LINE_MAX);
-		otrim.p = sdt_put_trim_line(otrim.p, t);
-		uint32_t *w = k.bw[k.at_batch[ord]];
-		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
-		if (t->verdict > 4 || (uint64_t)t->start + t->len > len) {
-			fprintf(stderr, "sdt-kmers: the record of read %llu keeps [%u, %u + %u) of %llu bases, verdict %u\n", (unsigned long long)ord + 1, t->start,
-			        t->start, t->len, (unsigned long long)len, t->verdict);
-			bad = 1;
-			break;
-		}
-		by_verdict[t->verdict]++;
-		bases_in += len;
-		for (; e < n_edits && (edits[e] >> 18) == ord && !bad; e++)
-			bad = apply_edit(&oe, edits[e], ord, w, start, len) != 0;
-		const int to = sdt_trim_route(pairs, &cursor, trim, reads, ord);
-		if (to == SDT_TRIM_TO_NONE) continue;
-		kept++;
-		bases_out += t->len;
-		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
-		ob_room(o, (size_t)t->len + 24);
-		o->p = sdt_put_fasta_record(o->p, ord, w, start + t->start, t->len);
-	}
-	const int all_written = otrim.ok && opair.ok && osingle.ok && (!correct || oe.ok);
-	if ((ob_close(&otrim) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) | (correct && ob_close(&oe) != 0) || bad) return 1;
-	if (all_written && e != n_edits) { fprintf(stderr, "sdt-kmers: %llu of %llu edits name no read of the stream\n", (unsigned long long)(n_edits - e), (unsigned long long)n_edits); return 1; }
-	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
-	kept_free(&k);
-	free(trim); free(fix); free(edits);
-	printf("%llu reads: %llu whole, %llu gated, %llu trimmed, %llu dropped, %llu short; %llu bases in, %llu bases out\n", reads, by_verdict[0],
-	       by_verdict[1], by_verdict[2], by_verdict[3], by_verdict[4], bases_in, bases_out);
+	const int walked = fetch_and_walk(gpu, reads, pairs, opt->outname, &stage, &st, n_kept, &t) == 0;
+	if (correct ? edits_close(&st.ed, walked) != 0 : !walked) return 1;
+	printf("%llu reads: %llu whole, %llu gated, %llu trimmed, %llu dropped, %llu short; %llu bases in, %llu bases out\n", reads, st.by_verdict[0],
+	       st.by_verdict[1], st.by_verdict[2], st.by_verdict[3], st.by_verdict[4], t.bases_in, t.bases_out);
+	free(trim); free(fix);
 	return 0;
 }
 
+/* ---- clip ------------------------------------------------------------------------------------------------------------------------------ */
+typedef struct { const sdt_read_clip *rec; sdt_clip_stats stats; } clip_state;
+
+static int clip_note(void *state, uint64_t ord, uint64_t read_len, uint64_t *start, uint64_t *len)
+{
+	clip_state *s = (clip_state *)state;
+	const sdt_read_clip *t = s->rec + ord;
+	if (sdt_clip_stats_note(&s->stats, t, read_len) != 0) {
+		fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->adapters, t->tail3,
+		        t->tail5, t->start, t->len, t->verdict, (unsigned long long)read_len);
+		return -1;
+	}
+	*start = t->start;
+	*len = t->len;
+	return 0;
+}
+
+static char *clip_line(const void *state, char *p, uint64_t ord) { return sdt_put_clip_line(p, ((const clip_state *)state)->rec + ord); }
+static int clip_alive(const void *state, uint64_t ord) { return ((const clip_state *)state)->rec[ord].len != 0; }
+
 /* `clip`: the records from the device, the kept batches back from HBM, the kept bases of every read into the pairs file (both mates
  * survive) or the singles file, routed as trim routes them; the statistics (clipsplit.c) */
-static int clip_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_clip_params *prm, const sdt_adapter_list *ads, const sdt_pair_ranges *pairs,
-                          const char *prefix)
+static int run_clip(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	const uint64_t m = reads ? reads : 1;
-	sdt_read_clip *clip = (sdt_read_clip *)calloc(m, sizeof(sdt_read_clip));
-	sdt_clip_stats stats;
-	if (!clip || sdt_clip_stats_init(&stats, ads->n) != 0) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
-	const sdt_adapter_set set = sdt_adapters_set(ads);
+	static const sdt_walk_stage stage = {{".readClip", ".clip.pairs.fa", ".clip.single.fa"}, SDT_CLIP_LINE_MAX, 0, clip_note, clip_line, clip_alive, NULL};
+	sdt_read_clip *clip = (sdt_read_clip *)records_alloc(reads, sizeof *clip, 0);
+	clip_state st = {clip, {0}};
+	if (!clip) return 1;
+	if (sdt_clip_stats_init(&st.stats, opt->ads.n) != 0) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	const sdt_adapter_set set = sdt_adapters_set(&opt->ads);
 	uint64_t got = 0, n_kept = 0;
-	if (sdt_gpu_clip_kept_reads(gpu, prm, &set, clip, reads, &got, &n_kept) != SDT_OK) {
-		fprintf(stderr, "sdt_gpu_clip_kept_reads: %s\n", sdt_gpu_last_error());
-		return 1;
-	}
-	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu clipped\n", reads, (unsigned long long)got); return 1; }
-	kept_reads k;
-	if (kept_fetch(gpu, reads, &k) != 0) return 1;
-	char path[4][4200];
-	snprintf(path[0], sizeof path[0], "%s.readClip", prefix);
-	snprintf(path[1], sizeof path[1], "%s.clip.pairs.fa", prefix);
-	snprintf(path[2], sizeof path[2], "%s.clip.single.fa", prefix);
-	snprintf(path[3], sizeof path[3], "%s.clipStats", prefix);
-	outbuf oclip, opair, osingle;
-	if (ob_open(&oclip, path[0]) != 0) return 1;
-	if (ob_open(&opair, path[1]) != 0) { ob_close(&oclip); return 1; }
-	if (ob_open(&osingle, path[2]) != 0) { ob_close(&oclip); ob_close(&opair); return 1; }
-	unsigned long long kept = 0, bases_in = 0, bases_out = 0;
-	size_t cursor = 0;
-	int bad = 0;
-	for (uint64_t ord = 0; ord < reads; ord++) {
-		if (!oclip.ok || !opair.ok || !osingle.ok) break;                              /* a write failed: ob_close says which */
-		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
-		const sdt_read_clip *t = clip + ord;
-		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
-		if (sdt_clip_stats_note(&stats, t, len) != 0) {
-			fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->adapters, t->tail3,
-			        t->tail5, t->start, t->len, t->verdict, (unsigned long long)len);
-			bad = 1;
-			break;
-		}
-		ob_room(&oclip, SDT_CLIP_LINE_MAX);
-		oclip.p = sdt_put_clip_line(oclip.p, t);
-		bases_in += len;
-		/* (start and len sit where sdt_read_trim has them: clipsplit.h) */
-		const int to = sdt_trim_route(pairs, &cursor, (const sdt_read_trim *)clip, reads, ord);
-		if (to == SDT_TRIM_TO_NONE) continue;
-		kept++;
-		bases_out += t->len;
-		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
-		ob_room(o, (size_t)t->len + 24);
-		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start + t->start, t->len);
-	}
-	const int all_written = oclip.ok && opair.ok && osingle.ok;
-	if ((ob_close(&oclip) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
-	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
-	FILE *fs = fopen(path[3], "w");
-	if (!fs || (sdt_clip_stats_write(fs, &stats, ads) != 0) | (fclose(fs) != 0)) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path[3]); return 1; }
-	printf("%llu reads: %llu whole, %llu clipped, %llu dropped; %llu bases in, %llu bases out\n", reads, (unsigned long long)stats.whole,
-	       (unsigned long long)stats.clipped, (unsigned long long)stats.dropped, bases_in, bases_out);
-	kept_free(&k);
-	sdt_clip_stats_free(&stats);
+	if (SDT_CALL(sdt_gpu_clip_kept_reads, gpu, &opt->clip, &set, clip, reads, &got, &n_kept) || !all_reads_came_back(reads, got, "clipped")) return 1;
+	sdt_walk_tally t;
+	if (fetch_and_walk(gpu, reads, pairs, opt->outname, &stage, &st, n_kept, &t) != 0) return 1;
+	char path[4200];
+	FILE *fs = stats_open(path, opt->outname, ".clipStats");
+	if (!fs || (sdt_clip_stats_write(fs, &st.stats, &opt->ads) != 0) | (fclose(fs) != 0)) return cannot_write(path);
+	printf("%llu reads: %llu whole, %llu clipped, %llu dropped; %llu bases in, %llu bases out\n", reads, (unsigned long long)st.stats.whole,
+	       (unsigned long long)st.stats.clipped, (unsigned long long)st.stats.dropped, t.bases_in, t.bases_out);
+	sdt_clip_stats_free(&st.stats);
 	free(clip);
 	return 0;
 }
 
+/* ---- overlap --------------------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+	const sdt_read_overlap *rec;
+	const sdt_pair_ranges *pairs;
+	size_t cursor;                                                           /* into pairs, the note's own */
+	uint64_t len_first;                                                      /* the first mate's bases, while the second is awaited */
+	sdt_insert_hist hist;
+	unsigned long long by_verdict[4];
+} overlap_state;
+
+static int overlap_note(void *state, uint64_t ord, uint64_t read_len, uint64_t *start, uint64_t *len)
+{
+	overlap_state *s = (overlap_state *)state;
+	const sdt_read_overlap *t = s->rec + ord;
+	int ok = sdt_overlap_record_ok(t, read_len);
+	if (ok && sdt_pair_ranges_holds(s->pairs, ord, &s->cursor)) {
+		if (((ord - s->pairs->v[2 * s->cursor]) & 1) == 0) s->len_first = read_len;
+		else {
+			const int rc = sdt_insert_hist_note(&s->hist, t - 1, t, s->len_first, read_len);
+			if (rc == -1) { fprintf(stderr, "sdt-kmers: out of memory\n"); return -1; }
+			ok = rc == 0;
+		}
+	}
+	if (!ok) {
+		fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->overlap, t->mismatches,
+		        t->insert, t->start, t->len, t->verdict, (unsigned long long)read_len);
+		return -1;
+	}
+	s->by_verdict[t->verdict]++;
+	*start = t->start;
+	*len = t->len;
+	return 0;
+}
+
+static char *overlap_line(const void *state, char *p, uint64_t ord) { return sdt_put_overlap_line(p, ((const overlap_state *)state)->rec + ord); }
+static int overlap_alive(const void *state, uint64_t ord) { return ((const overlap_state *)state)->rec[ord].len != 0; }
+
 /* `overlap`: the records from the device, the kept batches back from HBM, the kept bases of every read into the pairs file (both mates
  * survive) or the singles file, routed as trim routes them; the histogram of the inserts (overlapsplit.c) */
-static int overlap_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_overlap_params *prm, const sdt_pair_ranges *pairs, const char *prefix)
+static int run_overlap(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	const uint64_t m = reads ? reads : 1;
-	sdt_read_overlap *ov = (sdt_read_overlap *)calloc(m, sizeof(sdt_read_overlap));
-	if (!ov) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	static const sdt_walk_stage stage = {{".readOverlap", ".overlap.pairs.fa", ".overlap.single.fa"}, SDT_OVERLAP_LINE_MAX, 0,
+	                                     overlap_note, overlap_line, overlap_alive, NULL};
+	sdt_read_overlap *ov = (sdt_read_overlap *)records_alloc(reads, sizeof *ov, 0);
 	uint64_t got = 0, n_kept = 0;
-	if (sdt_gpu_overlap_kept_pairs(gpu, prm, pairs->v, pairs->n, ov, reads, &got, &n_kept) != SDT_OK) {
-		fprintf(stderr, "sdt_gpu_overlap_kept_pairs: %s\n", sdt_gpu_last_error());
-		return 1;
-	}
-	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu decided\n", reads, (unsigned long long)got); return 1; }
-	kept_reads k;
-	if (kept_fetch(gpu, reads, &k) != 0) return 1;
-	char path[4][4200];
-	snprintf(path[0], sizeof path[0], "%s.readOverlap", prefix);
-	snprintf(path[1], sizeof path[1], "%s.overlap.pairs.fa", prefix);
-	snprintf(path[2], sizeof path[2], "%s.overlap.single.fa", prefix);
-	snprintf(path[3], sizeof path[3], "%s.insertHist", prefix);
-	outbuf oov, opair, osingle;
-	if (ob_open(&oov, path[0]) != 0) return 1;
-	if (ob_open(&opair, path[1]) != 0) { ob_close(&oov); return 1; }
-	if (ob_open(&osingle, path[2]) != 0) { ob_close(&oov); ob_close(&opair); return 1; }
-	sdt_insert_hist hist;
-	memset(&hist, 0, sizeof hist);
-	unsigned long long kept = 0, by_verdict[4] = {0, 0, 0, 0}, bases_in = 0, bases_out = 0;
-	size_t cursor = 0, pcursor = 0;
-	uint64_t len_first = 0;                                                  /* the first mate's bases, while the second is awaited */
-	int bad = 0;
-	for (uint64_t ord = 0; ord < reads; ord++) {
-		if (!oov.ok || !opair.ok || !osingle.ok) break;                              /* a write failed: ob_close says which */
-		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
-		const sdt_read_overlap *t = ov + ord;
-		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
-		int ok = sdt_overlap_record_ok(t, len);
-		if (ok && sdt_pair_ranges_holds(pairs, ord, &pcursor)) {
-			if (((ord - pairs->v[2 * pcursor]) & 1) == 0) len_first = len;
-			else {
-				const int rc = sdt_insert_hist_note(&hist, t - 1, t, len_first, len);
-				if (rc == -1) { fprintf(stderr, "sdt-kmers: out of memory\n"); bad = 1; break; }
-				ok = rc == 0;
-			}
-		}
-		if (!ok) {
-			fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->overlap, t->mismatches,
-			        t->insert, t->start, t->len, t->verdict, (unsigned long long)len);
-			bad = 1;
-			break;
-		}
-		ob_room(&oov, SDT_OVERLAP_LINE_MAX);
-		oov.p = sdt_put_overlap_line(oov.p, t);
-		by_verdict[t->verdict]++;
-		bases_in += len;
-		/* (start and len sit where sdt_read_trim has them: overlapsplit.h) */
-		const int to = sdt_trim_route(pairs, &cursor, (const sdt_read_trim *)ov, reads, ord);
-		if (to == SDT_TRIM_TO_NONE) continue;
-		kept++;
-		bases_out += t->len;
-		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
-		ob_room(o, (size_t)t->len + 24);
-		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start + t->start, t->len);
-	}
-	const int all_written = oov.ok && opair.ok && osingle.ok;
-	if ((ob_close(&oov) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
-	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
-	const unsigned long long overlapping = hist.n, median = sdt_insert_hist_median(&hist);
-	FILE *fh = fopen(path[3], "w");
-	if (!fh || (sdt_insert_hist_write(fh, &hist) != 0) | (fclose(fh) != 0)) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path[3]); return 1; }
+	if (!ov || SDT_CALL(sdt_gpu_overlap_kept_pairs, gpu, &opt->overlap, pairs->v, pairs->n, ov, reads, &got, &n_kept)) return 1;
+	if (!all_reads_came_back(reads, got, "decided")) return 1;
+	overlap_state st;
+	memset(&st, 0, sizeof st);
+	st.rec = ov;
+	st.pairs = pairs;
+	sdt_walk_tally t;
+	if (fetch_and_walk(gpu, reads, pairs, opt->outname, &stage, &st, n_kept, &t) != 0) return 1;
+	const unsigned long long overlapping = st.hist.n, median = sdt_insert_hist_median(&st.hist);
+	char path[4200];
+	FILE *fh = stats_open(path, opt->outname, ".insertHist");
+	if (!fh || (sdt_insert_hist_write(fh, &st.hist) != 0) | (fclose(fh) != 0)) return cannot_write(path);
 	printf("%llu reads: %llu whole, %llu clipped, %llu dropped; %llu bases in, %llu bases out; %llu pairs, %llu overlapping, median insert %llu\n", reads,
-	       by_verdict[0], by_verdict[2], by_verdict[3], bases_in, bases_out, (unsigned long long)hist.pairs, overlapping, median);
-	kept_free(&k);
-	sdt_insert_hist_free(&hist);
+	       st.by_verdict[0], st.by_verdict[2], st.by_verdict[3], t.bases_in, t.bases_out, (unsigned long long)st.hist.pairs, overlapping, median);
+	sdt_insert_hist_free(&st.hist);
 	free(ov);
 	return 0;
 }
 
+/* ---- complexity ------------------------------------------------------------------------------------------------------------------------ */
+typedef struct { const sdt_read_complexity *rec; sdt_score_hist hist; } cx_state;
+
+static int cx_note(void *state, uint64_t ord, uint64_t read_len, uint64_t *start, uint64_t *len)
+{
+	cx_state *s = (cx_state *)state;
+	const sdt_read_complexity *t = s->rec + ord;
+	if (sdt_score_hist_note(&s->hist, t, read_len) != 0) {
+		fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->windows, t->low,
+		        t->score, t->start, t->len, t->verdict, (unsigned long long)read_len);
+		return -1;
+	}
+	*start = t->start;
+	*len = t->len;
+	return 0;
+}
+
+static char *cx_line(const void *state, char *p, uint64_t ord) { return sdt_put_cx_line(p, ((const cx_state *)state)->rec + ord); }
+static int cx_alive(const void *state, uint64_t ord) { return ((const cx_state *)state)->rec[ord].len != 0; }
+
 /* `complexity`: the records from the device, the kept batches back from HBM, the kept bases of every read into the pairs file (both
  * mates survive) or the singles file, routed as clip routes them; the histogram of the scores (cxsplit.c) */
-static int complexity_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_complexity_params *prm, const sdt_pair_ranges *pairs, const char *prefix)
+static int run_complexity(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	const uint64_t m = reads ? reads : 1;
-	sdt_read_complexity *cx = (sdt_read_complexity *)calloc(m, sizeof(sdt_read_complexity));
-	if (!cx) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	static const sdt_walk_stage stage = {{".readComplexity", ".cx.pairs.fa", ".cx.single.fa"}, SDT_CX_LINE_MAX, 0, cx_note, cx_line, cx_alive, NULL};
+	sdt_read_complexity *cx = (sdt_read_complexity *)records_alloc(reads, sizeof *cx, 0);
 	uint64_t got = 0, n_kept = 0;
-	if (sdt_gpu_complexity_kept_reads(gpu, prm, cx, reads, &got, &n_kept) != SDT_OK) {
-		fprintf(stderr, "sdt_gpu_complexity_kept_reads: %s\n", sdt_gpu_last_error());
-		return 1;
-	}
-	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu decided\n", reads, (unsigned long long)got); return 1; }
-	kept_reads k;
-	if (kept_fetch(gpu, reads, &k) != 0) return 1;
-	char path[4][4200];
-	snprintf(path[0], sizeof path[0], "%s.readComplexity", prefix);
-	snprintf(path[1], sizeof path[1], "%s.cx.pairs.fa", prefix);
-	snprintf(path[2], sizeof path[2], "%s.cx.single.fa", prefix);
-	snprintf(path[3], sizeof path[3], "%s.scoreHist", prefix);
-	outbuf ocx, opair, osingle;
-	if (ob_open(&ocx, path[0]) != 0) return 1;
-	if (ob_open(&opair, path[1]) != 0) { ob_close(&ocx); return 1; }
-	if (ob_open(&osingle, path[2]) != 0) { ob_close(&ocx); ob_close(&opair); return 1; }
-	sdt_score_hist hist;
-	memset(&hist, 0, sizeof hist);
-	unsigned long long kept = 0, bases_in = 0, bases_out = 0;
-	size_t cursor = 0;
-	int bad = 0;
-	for (uint64_t ord = 0; ord < reads; ord++) {
-		if (!ocx.ok || !opair.ok || !osingle.ok) break;                                /* a write failed: ob_close says which */
-		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
-		const sdt_read_complexity *t = cx + ord;
-		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
-		if (sdt_score_hist_note(&hist, t, len) != 0) {
-			fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->windows, t->low,
-			        t->score, t->start, t->len, t->verdict, (unsigned long long)len);
-			bad = 1;
-			break;
-		}
-		ob_room(&ocx, SDT_CX_LINE_MAX);
-		ocx.p = sdt_put_cx_line(ocx.p, t);
-		bases_in += len;
-		/* (start and len sit where sdt_read_trim has them: cxsplit.h) */
-		const int to = sdt_trim_route(pairs, &cursor, (const sdt_read_trim *)cx, reads, ord);
-		if (to == SDT_TRIM_TO_NONE) continue;
-		kept++;
-		bases_out += t->len;
-		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
-		ob_room(o, (size_t)t->len + 24);
-		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start + t->start, t->len);
-	}
-	const int all_written = ocx.ok && opair.ok && osingle.ok;
-	if ((ob_close(&ocx) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
-	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
-	FILE *fh = fopen(path[3], "w");
-	if (!fh || (sdt_score_hist_write(fh, &hist) != 0) | (fclose(fh) != 0)) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path[3]); return 1; }
-	printf("%llu reads: %llu with a low window, %llu clipped, %llu dropped; %llu bases in, %llu bases out\n", reads, (unsigned long long)hist.low,
-	       (unsigned long long)hist.clipped, (unsigned long long)hist.dropped, bases_in, bases_out);
-	kept_free(&k);
+	if (!cx || SDT_CALL(sdt_gpu_complexity_kept_reads, gpu, &opt->cx, cx, reads, &got, &n_kept) || !all_reads_came_back(reads, got, "decided")) return 1;
+	cx_state st;
+	memset(&st, 0, sizeof st);
+	st.rec = cx;
+	sdt_walk_tally t;
+	if (fetch_and_walk(gpu, reads, pairs, opt->outname, &stage, &st, n_kept, &t) != 0) return 1;
+	char path[4200];
+	FILE *fh = stats_open(path, opt->outname, ".scoreHist");
+	if (!fh || (sdt_score_hist_write(fh, &st.hist) != 0) | (fclose(fh) != 0)) return cannot_write(path);
+	printf("%llu reads: %llu with a low window, %llu clipped, %llu dropped; %llu bases in, %llu bases out\n", reads, (unsigned long long)st.hist.low,
+	       (unsigned long long)st.hist.clipped, (unsigned long long)st.hist.dropped, t.bases_in, t.bases_out);
 	free(cx);
 	return 0;
 }
 
+/* ---- screen ---------------------------------------------------------------------------------------------------------------------------- */
+typedef struct { const sdt_read_screen *rec; const sdt_screen_params *prm; uint32_t k; sdt_screen_stats stats; } screen_state;
+
+static int screen_note(void *state, uint64_t ord, uint64_t read_len, uint64_t *start, uint64_t *len)
+{
+	screen_state *s = (screen_state *)state;
+	const sdt_read_screen *t = s->rec + ord;
+	if (sdt_screen_stats_note(&s->stats, t, read_len, s->k, s->prm) != 0) {
+		fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->kmers, t->hits, t->ref,
+		        t->start, t->len, t->verdict, (unsigned long long)read_len);
+		return -1;
+	}
+	(void)start;                                                             /* (0 in every possible record) */
+	*len = t->len;
+	return 0;
+}
+
+static char *screen_line(const void *state, char *p, uint64_t ord) { return sdt_put_screen_line(p, ((const screen_state *)state)->rec + ord); }
+/* (the device decides the mates of a pair together and says so in len, all or nothing: routed by it, as clip routes) */
+static int screen_alive(const void *state, uint64_t ord) { return ((const screen_state *)state)->rec[ord].len != 0; }
+
 /* `screen`: the references into the device's set, the records from the device, the kept batches back from HBM, every surviving read
  * into the pairs file (both mates of a pair) or the singles file, routed as clip routes them; the statistics (screensplit.c) */
-static int screen_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_screen_params *prm, uint32_t k, const sdt_ref_set *refs,
-                            const sdt_pair_ranges *pairs, const char *prefix)
+static int run_screen(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
+	static const sdt_walk_stage stage = {{".readScreen", ".screen.pairs.fa", ".screen.single.fa"}, SDT_SCREEN_LINE_MAX, 0,
+	                                     screen_note, screen_line, screen_alive, NULL};
+	const sdt_ref_set *refs = &opt->refs;
 	uint64_t distinct = 0;
-	if (sdt_gpu_screen_load(gpu, refs->words, refs->nwords, refs->offsets, refs->nseqs, refs->ref_of_seq, refs->n_refs, k, &distinct) != SDT_OK) {
-		fprintf(stderr, "sdt_gpu_screen_load: %s\n", sdt_gpu_last_error());
-		return 1;
-	}
-	const uint64_t m = reads ? reads : 1;
-	sdt_read_screen *rec = (sdt_read_screen *)calloc(m, sizeof(sdt_read_screen));
-	sdt_screen_stats stats;
-	if (!rec || sdt_screen_stats_init(&stats, refs->n_refs) != 0) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
+	if (SDT_CALL(sdt_gpu_screen_load, gpu, refs->words, refs->nwords, refs->offsets, refs->nseqs, refs->ref_of_seq, refs->n_refs, opt->screen_k, &distinct)) return 1;
+	sdt_read_screen *rec = (sdt_read_screen *)records_alloc(reads, sizeof *rec, 0);
+	screen_state st = {rec, &opt->screen, opt->screen_k, {0}};
+	if (!rec) return 1;
+	if (sdt_screen_stats_init(&st.stats, refs->n_refs) != 0) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", reads); return 1; }
 	uint64_t got = 0, n_kept = 0;
-	if (sdt_gpu_screen_kept_reads(gpu, prm, pairs->v, pairs->n, rec, reads, &got, &n_kept) != SDT_OK) {
-		fprintf(stderr, "sdt_gpu_screen_kept_reads: %s\n", sdt_gpu_last_error());
-		return 1;
-	}
-	if (got != reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu decided\n", reads, (unsigned long long)got); return 1; }
-	kept_reads kr;
-	if (kept_fetch(gpu, reads, &kr) != 0) return 1;
-	char path[4][4200];
-	snprintf(path[0], sizeof path[0], "%s.readScreen", prefix);
-	snprintf(path[1], sizeof path[1], "%s.screen.pairs.fa", prefix);
-	snprintf(path[2], sizeof path[2], "%s.screen.single.fa", prefix);
-	snprintf(path[3], sizeof path[3], "%s.screenStats", prefix);
-	outbuf orec, opair, osingle;
-	if (ob_open(&orec, path[0]) != 0) return 1;
-	if (ob_open(&opair, path[1]) != 0) { ob_close(&orec); return 1; }
-	if (ob_open(&osingle, path[2]) != 0) { ob_close(&orec); ob_close(&opair); return 1; }
-	unsigned long long kept = 0, bases_in = 0, bases_out = 0;
-	size_t cursor = 0;
-	int bad = 0;
-	for (uint64_t ord = 0; ord < reads; ord++) {
-		if (!orec.ok || !opair.ok || !osingle.ok) break;                               /* a write failed: ob_close says which */
-		if (kr.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
-		const sdt_read_screen *t = rec + ord;
-		const uint64_t start = kr.bo[kr.at_batch[ord]][kr.at_read[ord]], len = kr.bo[kr.at_batch[ord]][kr.at_read[ord] + 1] - start;
-		if (sdt_screen_stats_note(&stats, t, len, k, prm) != 0) {
-			fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->kmers, t->hits, t->ref,
-			        t->start, t->len, t->verdict, (unsigned long long)len);
-			bad = 1;
-			break;
-		}
-		ob_room(&orec, SDT_SCREEN_LINE_MAX);
-		orec.p = sdt_put_screen_line(orec.p, t);
-		bases_in += len;
-		/* (start and len sit where sdt_read_trim has them: screensplit.h) */
-		const int to = sdt_trim_route(pairs, &cursor, (const sdt_read_trim *)rec, reads, ord);
-		if (to == SDT_TRIM_TO_NONE) continue;
-		kept++;
-		bases_out += t->len;
-		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
-		ob_room(o, (size_t)t->len + 24);
-		o->p = sdt_put_fasta_record(o->p, ord, kr.bw[kr.at_batch[ord]], start, t->len);
-	}
-	const int all_written = orec.ok && opair.ok && osingle.ok;
-	if ((ob_close(&orec) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
-	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
-	FILE *fs = fopen(path[3], "w");
-	if (!fs || (sdt_screen_stats_write(fs, &stats, refs) != 0) | (fclose(fs) != 0)) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path[3]); return 1; }
+	if (SDT_CALL(sdt_gpu_screen_kept_reads, gpu, &opt->screen, pairs->v, pairs->n, rec, reads, &got, &n_kept)) return 1;
+	if (!all_reads_came_back(reads, got, "decided")) return 1;
+	sdt_walk_tally t;
+	if (fetch_and_walk(gpu, reads, pairs, opt->outname, &stage, &st, n_kept, &t) != 0) return 1;
+	char path[4200];
+	FILE *fs = stats_open(path, opt->outname, ".screenStats");
+	if (!fs || (sdt_screen_stats_write(fs, &st.stats, refs) != 0) | (fclose(fs) != 0)) return cannot_write(path);
 	printf("%llu reads against %llu k-mers of %u references: %llu matched, %llu kept, %llu dropped; %llu bases in, %llu bases out\n", reads,
-	       (unsigned long long)distinct, refs->n_refs, (unsigned long long)stats.matched, (unsigned long long)stats.kept, (unsigned long long)stats.dropped,
-	       bases_in, bases_out);
-	kept_free(&kr);
-	sdt_screen_stats_free(&stats);
+	       (unsigned long long)distinct, refs->n_refs, (unsigned long long)st.stats.matched, (unsigned long long)st.stats.kept,
+	       (unsigned long long)st.stats.dropped, t.bases_in, t.bases_out);
+	sdt_screen_stats_free(&st.stats);
 	free(rec);
 	return 0;
 }
 
-/* `qtrim`, while the reads stream: every FASTQ batch's qualities through sdt_gpu_quality_reads on a context of its own (nothing of the
+/* ---- qtrim ----------------------------------------------------------------------------------------------------------------------------- */
+
+/* while the reads stream: every FASTQ batch's qualities through sdt_gpu_quality_reads on a context of its own (nothing of the
  * asynchronous push path is touched), the records to the batch's ordinals; then the batch is pushed like any other */
-typedef struct {
+struct qtrim_state {
 	push_state push;
 	sdt_ctx *qgpu;
 	const sdt_quality_params *prm;
 	sdt_read_quality *rec, *dense;                                           /* by ordinal; of one batch */
 	uint64_t cap, dense_cap, n_kept;
-} qtrim_state;
+	sdt_len_hist hist;                                                       /* after the stream */
+};
 
 static int qtrim_batch(void *user, const sdt_batch *b, uint64_t ord_base, uint64_t ord_stride)
 {
@@ -975,98 +858,79 @@ static int qtrim_batch(void *user, const sdt_batch *b, uint64_t ord_base, uint64
 			if (!q->dense) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", (unsigned long long)b->nreads); return -1; }
 		}
 		uint64_t kept = 0;
-		if (sdt_gpu_quality_reads(q->qgpu, b->quals, b->offsets[b->nreads], b->offsets, b->nreads, q->prm, q->dense, NULL, &kept) != SDT_OK) {
-			fprintf(stderr, "sdt_gpu_quality_reads: %s\n", sdt_gpu_last_error());
-			return -1;
-		}
+		if (SDT_CALL(sdt_gpu_quality_reads, q->qgpu, b->quals, b->offsets[b->nreads], b->offsets, b->nreads, q->prm, q->dense, NULL, &kept)) return -1;
 		q->n_kept += kept;
 		for (uint64_t i = 0; i < b->nreads; i++) q->rec[ord_base + i * ord_stride] = q->dense[i];
 	}
 	return push_batch(&q->push, b, ord_base, ord_stride);
 }
 
-/* `qtrim`, after the stream: the kept batches back from HBM, the kept bases of every read into the pairs file (both mates survive) or
- * the singles file, routed as clip routes them; the histogram of the kept lengths (qualsplit.c) */
-static int qtrim_and_write(sdt_ctx *gpu, unsigned long long reads, const sdt_quality_params *prm, const sdt_read_quality *rec, uint64_t n_kept,
-                           const sdt_pair_ranges *pairs, const char *prefix)
+static int qtrim_note(void *state, uint64_t ord, uint64_t read_len, uint64_t *start, uint64_t *len)
 {
-	kept_reads k;
-	if (kept_fetch(gpu, reads, &k) != 0) return 1;
-	char path[4][4200];
-	snprintf(path[0], sizeof path[0], "%s.readQual", prefix);
-	snprintf(path[1], sizeof path[1], "%s.qtrim.pairs.fa", prefix);
-	snprintf(path[2], sizeof path[2], "%s.qtrim.single.fa", prefix);
-	snprintf(path[3], sizeof path[3], "%s.lenHist", prefix);
-	outbuf oq, opair, osingle;
-	if (ob_open(&oq, path[0]) != 0) return 1;
-	if (ob_open(&opair, path[1]) != 0) { ob_close(&oq); return 1; }
-	if (ob_open(&osingle, path[2]) != 0) { ob_close(&oq); ob_close(&opair); return 1; }
-	sdt_len_hist hist;
-	memset(&hist, 0, sizeof hist);
-	unsigned long long kept = 0;
-	size_t cursor = 0;
-	int bad = 0;
-	for (uint64_t ord = 0; ord < reads; ord++) {
-		if (!oq.ok || !opair.ok || !osingle.ok) break;                                 /* a write failed: ob_close says which */
-		if (k.at_batch[ord] == 0xFFFFFFFFu) { fprintf(stderr, "sdt-kmers: no kept read has ordinal %llu\n", (unsigned long long)ord); bad = 1; break; }
-		const sdt_read_quality *t = rec + ord;
-		const uint64_t start = k.bo[k.at_batch[ord]][k.at_read[ord]], len = k.bo[k.at_batch[ord]][k.at_read[ord] + 1] - start;
-		const int noted = sdt_len_hist_note(&hist, t, len, prm);
-		if (noted != 0) {
-			if (noted == -1) fprintf(stderr, "sdt-kmers: out of memory for the histogram\n");
-			else fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->span, t->low,
-			             t->ee_ppm, t->start, t->len, t->verdict, (unsigned long long)len);
-			bad = 1;
-			break;
-		}
-		ob_room(&oq, SDT_QUAL_LINE_MAX);
-		oq.p = sdt_put_qual_line(oq.p, t);
-		/* (start and len sit where sdt_read_trim has them: qualsplit.h) */
-		const int to = sdt_trim_route(pairs, &cursor, (const sdt_read_trim *)rec, reads, ord);
-		if (to == SDT_TRIM_TO_NONE) continue;
-		kept++;
-		outbuf *o = to == SDT_TRIM_TO_PAIRS ? &opair : &osingle;
-		ob_room(o, (size_t)t->len + 24);
-		o->p = sdt_put_fasta_record(o->p, ord, k.bw[k.at_batch[ord]], start + t->start, t->len);
-	}
-	const int all_written = oq.ok && opair.ok && osingle.ok;
-	if ((ob_close(&oq) != 0) | (ob_close(&opair) != 0) | (ob_close(&osingle) != 0) || bad) return 1;
-	if (all_written && kept != n_kept) { fprintf(stderr, "sdt-kmers: the device kept %llu reads, the records say %llu\n", (unsigned long long)n_kept, kept); return 1; }
-	FILE *fh = fopen(path[3], "w");
-	if (!fh || (sdt_len_hist_write(fh, &hist) != 0) | (fclose(fh) != 0)) { fprintf(stderr, "sdt-kmers: cannot write %s\n", path[3]); return 1; }
-	printf("%llu reads: %llu whole, %llu clipped, %llu dropped (%llu short, %llu low bases, %llu expected errors); %llu bases in, %llu bases out\n", reads,
-	       (unsigned long long)hist.whole, (unsigned long long)hist.clipped, (unsigned long long)hist.dropped, (unsigned long long)hist.n_short,
-	       (unsigned long long)hist.n_low, (unsigned long long)hist.n_errors, (unsigned long long)hist.bases_in, (unsigned long long)hist.bases_out);
-	sdt_len_hist_free(&hist);
-	kept_free(&k);
-	return 0;
-}
-
-/* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
-static int tail_mask(const char *opt, const char *text)
-{
-	int mask = 0;
-	for (const char *c = text; *c; c++) {
-		if (!strchr("ACGTacgt", *c)) { fprintf(stderr, "sdt-kmers: %s %s: letters of ACGT are expected\n", opt, text); return -1; }
-		mask |= 1 << ((*c & 6) >> 1);
-	}
-	return mask;
-}
-
-/* the whole of text as a decimal number of at most `most`, or the option is refused by name */
-static int parse_number(const char *opt, const char *text, unsigned long long most, unsigned long long *v)
-{
-	char *end = NULL;
-	errno = 0;
-	*v = strtoull(text, &end, 10);
-	if (text[0] < '0' || text[0] > '9' || *end || errno || *v > most) {
-		fprintf(stderr, "sdt-kmers: %s %s: a whole number from 0 to %llu is expected\n", opt, text, most);
+	qtrim_state *q = (qtrim_state *)state;
+	const sdt_read_quality *t = q->rec + ord;
+	const int noted = sdt_len_hist_note(&q->hist, t, read_len, q->prm);
+	if (noted != 0) {
+		if (noted == -1) fprintf(stderr, "sdt-kmers: out of memory for the histogram\n");
+		else fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->span, t->low,
+		             t->ee_ppm, t->start, t->len, t->verdict, (unsigned long long)read_len);
 		return -1;
 	}
+	*start = t->start;
+	*len = t->len;
 	return 0;
 }
 
-typedef struct { char **text; uint64_t *keys; uint64_t n, cap; } query_set;
+static char *qtrim_line(const void *state, char *p, uint64_t ord) { return sdt_put_qual_line(p, ((const qtrim_state *)state)->rec + ord); }
+static int qtrim_alive(const void *state, uint64_t ord) { return ((const qtrim_state *)state)->rec[ord].len != 0; }
+
+/* `qtrim`, after the stream: the kept batches back from HBM, the kept bases of every read into the pairs file (both mates survive) or
+ * the singles file, routed as clip routes them; the histogram of the kept lengths (qualsplit.c) */
+static int run_qtrim(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	static const sdt_walk_stage stage = {{".readQual", ".qtrim.pairs.fa", ".qtrim.single.fa"}, SDT_QUAL_LINE_MAX, 0, qtrim_note, qtrim_line, qtrim_alive, NULL};
+	qtrim_state *q = opt->qtrim;
+	if (reads > q->cap) { fprintf(stderr, "sdt-kmers: %llu reads streamed, records for %llu\n", reads, (unsigned long long)q->cap); return 1; }
+	sdt_walk_tally t;
+	if (fetch_and_walk(gpu, reads, pairs, opt->outname, &stage, q, q->n_kept, &t) != 0) return 1;
+	const sdt_len_hist *h = &q->hist;
+	char path[4200];
+	FILE *fh = stats_open(path, opt->outname, ".lenHist");
+	if (!fh || (sdt_len_hist_write(fh, h) != 0) | (fclose(fh) != 0)) return cannot_write(path);
+	printf("%llu reads: %llu whole, %llu clipped, %llu dropped (%llu short, %llu low bases, %llu expected errors); %llu bases in, %llu bases out\n", reads,
+	       (unsigned long long)h->whole, (unsigned long long)h->clipped, (unsigned long long)h->dropped, (unsigned long long)h->n_short,
+	       (unsigned long long)h->n_low, (unsigned long long)h->n_errors, (unsigned long long)h->bases_in, (unsigned long long)h->bases_out);
+	sdt_len_hist_free(&q->hist);
+	return 0;
+}
+
+/* ---- profile and query ----------------------------------------------------------------------------------------------------------------- */
+
+/* prefix.readCov: "kmers found solid min median max" per read */
+static int run_profile(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	(void)pairs;
+	char path[4200];
+	snprintf(path, sizeof path, "%s.readCov", opt->outname);
+	sdt_read_cov *cov = (sdt_read_cov *)records_alloc(reads, sizeof *cov, 0);
+	uint64_t got = 0;
+	if (!cov || SDT_CALL(sdt_gpu_profile_kept_reads, gpu, (uint32_t)opt->min_count, cov, reads, &got) || !all_reads_came_back(reads, got, "profiled")) return 1;
+	outbuf o;
+	if (ob_open(&o, path) != 0) return 1;
+	for (unsigned long long i = 0; i < reads && o.ok; i++) {
+		ob_room(&o, 6 * 11);
+		o.p = sdt_put_dec(o.p, cov[i].kmers, ' ');
+		o.p = sdt_put_dec(o.p, cov[i].found, ' ');
+		o.p = sdt_put_dec(o.p, cov[i].solid, ' ');
+		o.p = sdt_put_dec(o.p, cov[i].min, ' ');
+		o.p = sdt_put_dec(o.p, cov[i].median, ' ');
+		o.p = sdt_put_dec(o.p, cov[i].max, '\n');
+	}
+	if (ob_close(&o) != 0) return 1;
+	printf("%llu reads profiled into %s\n", reads, path);
+	free(cov);
+	return 0;
+}
 
 /* one k-mer per line, letters ACGT (either case), exactly K of them; blank lines are skipped.  Base codes A0 C1 T2 G3. */
 static int load_queries(const char *path, int K, int nw, query_set *q)
@@ -1117,322 +981,303 @@ static int load_queries(const char *path, int K, int nw, query_set *q)
 	return 0;
 }
 
-int main(int argc, char **argv)
+/* per line of the query file: kmer found strand count l_A l_C l_T l_G r_A r_C r_T r_G linear deleted */
+static int run_query(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	if (argc < 2 || (strcmp(argv[1], "profile") != 0 && strcmp(argv[1], "query") != 0 && strcmp(argv[1], "correct") != 0 &&
-	                 strcmp(argv[1], "normalize") != 0 && strcmp(argv[1], "trim") != 0 && strcmp(argv[1], "dedup") != 0 && strcmp(argv[1], "clip") != 0 &&
-	                 strcmp(argv[1], "overlap") != 0 && strcmp(argv[1], "complexity") != 0 && strcmp(argv[1], "qtrim") != 0 &&
-	                 strcmp(argv[1], "screen") != 0)) { usage(); return 255; }
-	const int do_query = strcmp(argv[1], "query") == 0, do_correct = strcmp(argv[1], "correct") == 0, do_norm = strcmp(argv[1], "normalize") == 0;
-	const int do_trim = strcmp(argv[1], "trim") == 0, do_dedup = strcmp(argv[1], "dedup") == 0, do_clip = strcmp(argv[1], "clip") == 0;
-	const int do_overlap = strcmp(argv[1], "overlap") == 0, do_cx = strcmp(argv[1], "complexity") == 0, do_qtrim = strcmp(argv[1], "qtrim") == 0;
-	const int do_screen = strcmp(argv[1], "screen") == 0;
-	sdt_screen_params sprm = {1, 0, 0, 0};
-	uint32_t screen_k = 31;                                                  /* bbduk's usual figure: a choice, not a measurement */
-	enum { MAX_REF_FILES = 256 };
-	static char *rfile[MAX_REF_FILES];
-	int n_rfiles = 0;
-	sdt_quality_params qprm = {33, 20, 15, 40, 0, 0, 0, 0};
-	sdt_overlap_params oprm = {30, 10, 0, 0};
-	sdt_complexity_params xprm = {10, 50, 0, 0};
-	int max_low_given = 0;
-	sdt_clip_params cprm = {5, 10, 0, 10, 20, 0, 0, 0};
-	char afile[2][4096] = {"", ""};                                          /* -a: 3' adapters, -g: 5' adapters */
-	sdt_dedup_params dprm = {0, 0};
-	sdt_norm_params prm = {50, 10000, 0};
-	sdt_trim_params tprm = {0, 0, 0, 0};
-	char cfgfile[4096] = "", outname[4096] = "", qfile[4096] = "";
-	int K = 23, threads = 8, d = 0, max_k = 0, device = 0, c;
-	unsigned long min_count = do_correct || do_trim ? 2 : 0;
-	static struct option longopts[] = {{"max-k", required_argument, 0, 1000}, {"device", required_argument, 0, 1001},
-	                                   {"target", required_argument, 0, 1002}, {"max-cv", required_argument, 0, 1003},
-	                                   {"seed", required_argument, 0, 1004}, {"min-cov", required_argument, 0, 1005},
-	                                   {"min-len", required_argument, 0, 1006}, {"correct", no_argument, 0, 1007},
-	                                   {"mate-swap", no_argument, 0, 1008}, {"tail3", required_argument, 0, 1009},
-	                                   {"tail5", required_argument, 0, 1010}, {"min-overlap", required_argument, 0, 1011},
-	                                   {"error-pct", required_argument, 0, 1012}, {"min-tail", required_argument, 0, 1013},
-	                                   {"tail-error-pct", required_argument, 0, 1014}, {"max-err", required_argument, 0, 1015},
-	                                   {"max-score", required_argument, 0, 1016}, {"max-low", required_argument, 0, 1017},
-	                                   {"trim-low", no_argument, 0, 1018}, {"phred", required_argument, 0, 1019},
-	                                   {"cut-q", required_argument, 0, 1020}, {"low-q", required_argument, 0, 1021},
-	                                   {"max-low-bases", required_argument, 0, 1022}, {"max-ee", required_argument, 0, 1023},
-	                                   {"screen-k", required_argument, 0, 1024}, {"min-hits", required_argument, 0, 1025},
-	                                   {"min-hit-pct", required_argument, 0, 1026}, {"keep-matched", no_argument, 0, 1027},
+	(void)reads; (void)pairs;
+	const query_set *qs = &opt->qs;
+	/* `linear` is thread_mark's flag (prlHashReads.c:911-967): marked on the table as it is now */
+	int64_t hist[257];
+	uint64_t linear = 0;
+	if (SDT_CALL(sdt_gpu_mark_and_hist, gpu, hist, &linear)) return 1;
+	const uint64_t n = qs->n, m = n ? n : 1;
+	uint32_t *cnt = (uint32_t *)calloc(m, 4), *ll = (uint32_t *)calloc(m, 4), *rf = (uint32_t *)calloc(m, 4);
+	uint8_t *stt = (uint8_t *)calloc(m, 1);
+	if (!cnt || !ll || !rf || !stt) { fprintf(stderr, "sdt-kmers: out of memory\n"); return 1; }
+	if (SDT_CALL(sdt_gpu_search_kmers, gpu, qs->keys, n, cnt, ll, rf, stt)) return 1;
+	FILE *fo = opt->outname[0] ? fopen(opt->outname, "w") : stdout;
+	if (!fo) return cannot_write(opt->outname);
+	for (uint64_t i = 0; i < n; i++)
+		fprintf(fo, "%s\t%d\t%c\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", qs->text[i], stt[i] & 1, (stt[i] & 2) ? '-' : '+', cnt[i],
+		        ll[i] & 63u, (ll[i] >> 6) & 63u, (ll[i] >> 12) & 63u, (ll[i] >> 18) & 63u,
+		        rf[i] & 63u, (rf[i] >> 6) & 63u, (rf[i] >> 12) & 63u, (rf[i] >> 18) & 63u, (rf[i] >> 24) & 1u, (rf[i] >> 25) & 1u);
+	if (fo != stdout && fclose(fo) != 0) { fprintf(stderr, "sdt-kmers: write to %s failed\n", opt->outname); return 1; }
+	free(cnt); free(ll); free(rf); free(stt);
+	return 0;
+}
+
+/* ---- the command line ------------------------------------------------------------------------------------------------------------------ */
+enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, N_SUBCOMMANDS };
+
+static const struct {
+	const char *name;
+	int keep_reads, pairs;                  /* SDT_FLAG_KEEP_READS; the pair ranges are noted while the reads stream */
+	unsigned long min_count;                /* where -c is not given */
+	int (*run)(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs);      /* after the count is finished */
+} subcommands[N_SUBCOMMANDS] = {
+	[PROFILE] = {"profile", 1, 0, 0, run_profile},       [QUERY] = {"query", 0, 0, 0, run_query},
+	[CORRECT] = {"correct", 1, 0, 2, run_correct},       [NORMALIZE] = {"normalize", 1, 1, 0, run_normalize},
+	[TRIM] = {"trim", 1, 1, 2, run_trim},                [DEDUP] = {"dedup", 1, 1, 0, run_dedup},
+	[CLIP] = {"clip", 1, 1, 0, run_clip},                [OVERLAP] = {"overlap", 1, 1, 0, run_overlap},
+	[COMPLEXITY] = {"complexity", 1, 1, 0, run_complexity}, [QTRIM] = {"qtrim", 1, 1, 0, run_qtrim},
+	[SCREEN] = {"screen", 1, 1, 0, run_screen},
+};
+
+enum { O_MAX_K = 1000, O_DEVICE, O_TARGET, O_MAX_CV, O_SEED, O_MIN_COV, O_MIN_LEN, O_CORRECT, O_MATE_SWAP, O_TAIL3, O_TAIL5, O_MIN_OVERLAP, O_ERROR_PCT,
+       O_MIN_TAIL, O_TAIL_ERROR_PCT, O_MAX_ERR, O_MAX_SCORE, O_MAX_LOW, O_TRIM_LOW, O_PHRED, O_CUT_Q, O_LOW_Q, O_MAX_LOW_BASES, O_MAX_EE, O_SCREEN_K,
+       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED };
+
+/* the options that belong to some subcommands only: the name as it is printed, who may be given it, what the refusal says after
+ * "belongs to" (kept, not derived: --min-overlap names clip alone), and the most its value may be where it takes a whole number */
+#define BIT(sub) (1u << (sub))
+static const struct { int code; const char *name; unsigned owners; const char *belongs; unsigned long long most; } owned_options[] = {
+	{O_TARGET, "--target", BIT(NORMALIZE), "normalize", UINT32_MAX}, {O_MAX_CV, "--max-cv", BIT(NORMALIZE), "normalize", UINT32_MAX},
+	{O_SEED, "--seed", BIT(NORMALIZE), "normalize", UINT64_MAX},
+	{O_MIN_COV, "--min-cov", BIT(TRIM), "trim", UINT32_MAX}, {O_CORRECT, "--correct", BIT(TRIM), "trim", 0},
+	{O_MIN_LEN, "--min-len", BIT(TRIM) | BIT(CLIP) | BIT(OVERLAP) | BIT(COMPLEXITY) | BIT(QTRIM), "trim, clip, overlap, complexity and qtrim", UINT32_MAX},
+	{'a', "-a", BIT(CLIP), "clip", 0}, {'g', "-g", BIT(CLIP), "clip", 0}, {O_TAIL3, "--tail3", BIT(CLIP), "clip", 0}, {O_TAIL5, "--tail5", BIT(CLIP), "clip", 0},
+	{O_ERROR_PCT, "--error-pct", BIT(CLIP), "clip", 100}, {O_MIN_TAIL, "--min-tail", BIT(CLIP), "clip", UINT32_MAX},
+	{O_TAIL_ERROR_PCT, "--tail-error-pct", BIT(CLIP), "clip", 100}, {O_MIN_OVERLAP, "--min-overlap", BIT(CLIP) | BIT(OVERLAP), "clip", UINT32_MAX},
+	{O_MAX_ERR, "--max-err", BIT(OVERLAP), "overlap", 100},
+	{O_MAX_SCORE, "--max-score", BIT(COMPLEXITY), "complexity", 100}, {O_MAX_LOW, "--max-low", BIT(COMPLEXITY), "complexity", 100},
+	{O_TRIM_LOW, "--trim-low", BIT(COMPLEXITY), "complexity", 0},
+	{O_PHRED, "--phred", BIT(QTRIM), "qtrim", 64}, {O_CUT_Q, "--cut-q", BIT(QTRIM), "qtrim", 93}, {O_LOW_Q, "--low-q", BIT(QTRIM), "qtrim", 93},
+	{O_MAX_LOW_BASES, "--max-low-bases", BIT(QTRIM), "qtrim", 100}, {O_MAX_EE, "--max-ee", BIT(QTRIM), "qtrim", UINT32_MAX},
+	{'r', "-r", BIT(SCREEN), "screen", 0}, {O_SCREEN_K, "--screen-k", BIT(SCREEN), "screen", 31}, {O_MIN_HITS, "--min-hits", BIT(SCREEN), "screen", UINT32_MAX},
+	{O_MIN_HIT_PCT, "--min-hit-pct", BIT(SCREEN), "screen", 100}, {O_KEEP_MATCHED, "--keep-matched", BIT(SCREEN), "screen", 0},
+	{O_MATE_SWAP, "--mate-swap", BIT(DEDUP), "dedup", 0},
+};
+
+/* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
+static int tail_mask(const char *opt, const char *text)
+{
+	int mask = 0;
+	for (const char *c = text; *c; c++) {
+		if (!strchr("ACGTacgt", *c)) { fprintf(stderr, "sdt-kmers: %s %s: letters of ACGT are expected\n", opt, text); return -1; }
+		mask |= 1 << ((*c & 6) >> 1);
+	}
+	return mask;
+}
+
+/* the whole of text as a decimal number of at most `most`, or the option is refused by name */
+static int parse_number(const char *opt, const char *text, unsigned long long most, unsigned long long *v)
+{
+	char *end = NULL;
+	errno = 0;
+	*v = strtoull(text, &end, 10);
+	if (text[0] < '0' || text[0] > '9' || *end || errno || *v > most) {
+		fprintf(stderr, "sdt-kmers: %s %s: a whole number from 0 to %llu is expected\n", opt, text, most);
+		return -1;
+	}
+	return 0;
+}
+
+/* the options of subcommand `sub` into opt (the defaults are in it); 0, or the exit code after saying why */
+static int parse_options(int argc, char **argv, int sub, options *opt)
+{
+	static struct option longopts[] = {{"max-k", required_argument, 0, O_MAX_K}, {"device", required_argument, 0, O_DEVICE},
+	                                   {"target", required_argument, 0, O_TARGET}, {"max-cv", required_argument, 0, O_MAX_CV},
+	                                   {"seed", required_argument, 0, O_SEED}, {"min-cov", required_argument, 0, O_MIN_COV},
+	                                   {"min-len", required_argument, 0, O_MIN_LEN}, {"correct", no_argument, 0, O_CORRECT},
+	                                   {"mate-swap", no_argument, 0, O_MATE_SWAP}, {"tail3", required_argument, 0, O_TAIL3},
+	                                   {"tail5", required_argument, 0, O_TAIL5}, {"min-overlap", required_argument, 0, O_MIN_OVERLAP},
+	                                   {"error-pct", required_argument, 0, O_ERROR_PCT}, {"min-tail", required_argument, 0, O_MIN_TAIL},
+	                                   {"tail-error-pct", required_argument, 0, O_TAIL_ERROR_PCT}, {"max-err", required_argument, 0, O_MAX_ERR},
+	                                   {"max-score", required_argument, 0, O_MAX_SCORE}, {"max-low", required_argument, 0, O_MAX_LOW},
+	                                   {"trim-low", no_argument, 0, O_TRIM_LOW}, {"phred", required_argument, 0, O_PHRED},
+	                                   {"cut-q", required_argument, 0, O_CUT_Q}, {"low-q", required_argument, 0, O_LOW_Q},
+	                                   {"max-low-bases", required_argument, 0, O_MAX_LOW_BASES}, {"max-ee", required_argument, 0, O_MAX_EE},
+	                                   {"screen-k", required_argument, 0, O_SCREEN_K}, {"min-hits", required_argument, 0, O_MIN_HITS},
+	                                   {"min-hit-pct", required_argument, 0, O_MIN_HIT_PCT}, {"keep-matched", no_argument, 0, O_KEEP_MATCHED},
 	                                   {0, 0, 0, 0}};
-	argv++; argc--;
+	int c;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:r:", longopts, NULL)) != -1) {
+		const char *name = NULL;
+		unsigned long long most = 0, v = 0;
+		for (size_t i = 0; i < sizeof owned_options / sizeof owned_options[0] && !name; i++) {
+			if (owned_options[i].code != c) continue;
+			name = owned_options[i].name;
+			most = owned_options[i].most;
+			if (!(owned_options[i].owners & BIT(sub))) { fprintf(stderr, "sdt-kmers: %s belongs to %s\n", name, owned_options[i].belongs); usage(); return 255; }
+		}
+		if (most && parse_number(name, optarg, most, &v) != 0) return 255;
 		switch (c) {
-		case 's': snprintf(cfgfile, sizeof cfgfile, "%s", optarg); break;
-		case 'o': snprintf(outname, sizeof outname, "%s", optarg); break;
-		case 'q': snprintf(qfile, sizeof qfile, "%s", optarg); break;
-		case 'K': K = atoi(optarg); break;
-		case 'p': threads = atoi(optarg) > 0 ? atoi(optarg) : 1; break;
-		case 'd': d = atoi(optarg) >= 0 ? atoi(optarg) : 0; break;           /* pregraph.c:159 */
-		case 'c': min_count = strtoul(optarg, NULL, 10); break;
-		case 1000: max_k = atoi(optarg); break;
-		case 1001: device = atoi(optarg); break;
-		case 1002: case 1003: case 1004: {
-			const char *opt = c == 1002 ? "--target" : (c == 1003 ? "--max-cv" : "--seed");
-			unsigned long long v;
-			if (!do_norm) { fprintf(stderr, "sdt-kmers: %s belongs to normalize\n", opt); usage(); return 255; }
-			if (parse_number(opt, optarg, c == 1004 ? UINT64_MAX : UINT32_MAX, &v) != 0) return 255;
-			if (c == 1002) prm.target = (uint32_t)v;
-			else if (c == 1003) prm.max_cv_pct = (uint32_t)v;
-			else prm.seed = v;
+		case 's': snprintf(opt->cfgfile, sizeof opt->cfgfile, "%s", optarg); break;
+		case 'o': snprintf(opt->outname, sizeof opt->outname, "%s", optarg); break;
+		case 'q': snprintf(opt->qfile, sizeof opt->qfile, "%s", optarg); break;
+		case 'K': opt->K = atoi(optarg); break;
+		case 'p': opt->threads = atoi(optarg) > 0 ? atoi(optarg) : 1; break;
+		case 'd': opt->d = atoi(optarg) >= 0 ? atoi(optarg) : 0; break;      /* pregraph.c:159 */
+		case 'c': opt->min_count = strtoul(optarg, NULL, 10); break;
+		case O_MAX_K: opt->max_k = atoi(optarg); break;
+		case O_DEVICE: opt->device = atoi(optarg); break;
+		case O_TARGET: opt->norm.target = (uint32_t)v; break;
+		case O_MAX_CV: opt->norm.max_cv_pct = (uint32_t)v; break;
+		case O_SEED: opt->norm.seed = v; break;
+		case O_MIN_COV: opt->trim.min_cov = (uint32_t)v; break;
+		case O_MIN_LEN: opt->trim.min_len = opt->clip.min_len = opt->overlap.min_len = opt->cx.min_len = opt->qual.min_len = (uint32_t)v; break;
+		case O_CORRECT: opt->trim.flags |= SDT_TRIM_CORRECTED; break;
+		case O_MATE_SWAP: opt->dedup.flags |= SDT_DEDUP_MATE_SWAP; break;
+		case 'a': case 'g': snprintf(opt->afile[c == 'g'], sizeof opt->afile[0], "%s", optarg); break;
+		case O_TAIL3: case O_TAIL5: {
+			const int mask = tail_mask(name, optarg);
+			if (mask < 0) return 255;
+			if (c == O_TAIL3) opt->clip.tail3_bases = (uint32_t)mask; else opt->clip.tail5_bases = (uint32_t)mask;
 			break;
 		}
-		case 1005: case 1006: case 1007: {
-			const char *opt = c == 1005 ? "--min-cov" : (c == 1006 ? "--min-len" : "--correct");
-			unsigned long long v;
-			if (!do_trim && !((do_clip || do_overlap || do_cx || do_qtrim) && c == 1006)) {
-				fprintf(stderr, "sdt-kmers: %s belongs to trim%s\n", opt, c == 1006 ? ", clip, overlap, complexity and qtrim" : "");
-				usage();
-				return 255;
-			}
-			if (c == 1007) { tprm.flags |= SDT_TRIM_CORRECTED; break; }
-			if (parse_number(opt, optarg, UINT32_MAX, &v) != 0) return 255;
-			if (c == 1005) tprm.min_cov = (uint32_t)v;
-			else tprm.min_len = cprm.min_len = oprm.min_len = xprm.min_len = qprm.min_len = (uint32_t)v;
+		case O_MIN_OVERLAP: case O_MIN_TAIL:
+			if (v == 0) { fprintf(stderr, "sdt-kmers: %s must be at least 1\n", name); return 255; }
+			if (c == O_MIN_OVERLAP) opt->clip.min_overlap = opt->overlap.min_overlap = (uint32_t)v; else opt->clip.min_tail = (uint32_t)v;
 			break;
-		}
-		case 'a': case 'g': case 1009: case 1010: case 1011: case 1012: case 1013: case 1014: {
-			static const char *const names[] = {"--tail3", "--tail5", "--min-overlap", "--error-pct", "--min-tail", "--tail-error-pct"};
-			const char *opt = c == 'a' ? "-a" : (c == 'g' ? "-g" : names[c - 1009]);
-			unsigned long long v;
-			if (!do_clip && !(do_overlap && c == 1011)) { fprintf(stderr, "sdt-kmers: %s belongs to clip\n", opt); usage(); return 255; }
-			if (c == 'a' || c == 'g') { snprintf(afile[c == 'g'], sizeof afile[0], "%s", optarg); break; }
-			if (c == 1009 || c == 1010) {
-				const int mask = tail_mask(opt, optarg);
-				if (mask < 0) return 255;
-				if (c == 1009) cprm.tail3_bases = (uint32_t)mask; else cprm.tail5_bases = (uint32_t)mask;
-				break;
-			}
-			if (parse_number(opt, optarg, c == 1012 || c == 1014 ? 100 : UINT32_MAX, &v) != 0) return 255;
-			if ((c == 1011 || c == 1013) && v == 0) { fprintf(stderr, "sdt-kmers: %s must be at least 1\n", opt); return 255; }
-			if (c == 1011) cprm.min_overlap = oprm.min_overlap = (uint32_t)v;
-			else if (c == 1012) cprm.max_err_pct = (uint32_t)v;
-			else if (c == 1013) cprm.min_tail = (uint32_t)v;
-			else cprm.tail_err_pct = (uint32_t)v;
+		case O_ERROR_PCT: opt->clip.max_err_pct = (uint32_t)v; break;
+		case O_TAIL_ERROR_PCT: opt->clip.tail_err_pct = (uint32_t)v; break;
+		case O_MAX_ERR: opt->overlap.max_err_pct = (uint32_t)v; break;
+		case O_MAX_SCORE:
+			if (v == 0) { fprintf(stderr, "sdt-kmers: --max-score must be at least 1: at 0 every window would be low\n"); return 255; }
+			opt->cx.max_score_pct = (uint32_t)v;
 			break;
-		}
-		case 1015: {
-			unsigned long long v;
-			if (!do_overlap) { fprintf(stderr, "sdt-kmers: --max-err belongs to overlap\n"); usage(); return 255; }
-			if (parse_number("--max-err", optarg, 100, &v) != 0) return 255;
-			oprm.max_err_pct = (uint32_t)v;
+		case O_MAX_LOW: opt->cx.max_low_pct = (uint32_t)v; opt->max_low_given = 1; break;
+		case O_TRIM_LOW: opt->cx.flags |= SDT_COMPLEXITY_TRIM; break;
+		case O_PHRED:
+			if (v != 33 && v != 64) { fprintf(stderr, "sdt-kmers: --phred %llu: 33 or 64\n", v); return 255; }
+			opt->qual.phred_offset = (uint32_t)v;
 			break;
-		}
-		case 1016: case 1017: case 1018: {
-			const char *opt = c == 1016 ? "--max-score" : (c == 1017 ? "--max-low" : "--trim-low");
-			unsigned long long v;
-			if (!do_cx) { fprintf(stderr, "sdt-kmers: %s belongs to complexity\n", opt); usage(); return 255; }
-			if (c == 1018) { xprm.flags |= SDT_COMPLEXITY_TRIM; break; }
-			if (parse_number(opt, optarg, 100, &v) != 0) return 255;
-			if (c == 1016 && v == 0) { fprintf(stderr, "sdt-kmers: --max-score must be at least 1: at 0 every window would be low\n"); return 255; }
-			if (c == 1016) xprm.max_score_pct = (uint32_t)v;
-			else { xprm.max_low_pct = (uint32_t)v; max_low_given = 1; }
+		case O_CUT_Q: opt->qual.cut_q = (uint32_t)v; break;
+		case O_LOW_Q: opt->qual.low_q = (uint32_t)v; break;
+		case O_MAX_LOW_BASES: opt->qual.max_low_pct = (uint32_t)v; break;
+		case O_MAX_EE: opt->qual.max_ee_ppm = (uint32_t)v; break;
+		case 'r':
+			if (opt->n_rfiles == MAX_REF_FILES) { fprintf(stderr, "sdt-kmers: more than %d -r files\n", MAX_REF_FILES); return 255; }
+			opt->rfile[opt->n_rfiles++] = optarg;
 			break;
-		}
-		case 1019: case 1020: case 1021: case 1022: case 1023: {
-			static const char *const names[] = {"--phred", "--cut-q", "--low-q", "--max-low-bases", "--max-ee"};
-			const char *opt = names[c - 1019];
-			unsigned long long v;
-			if (!do_qtrim) { fprintf(stderr, "sdt-kmers: %s belongs to qtrim\n", opt); usage(); return 255; }
-			if (parse_number(opt, optarg, c == 1019 ? 64 : (c == 1022 ? 100 : (c == 1023 ? UINT32_MAX : 93)), &v) != 0) return 255;
-			if (c == 1019 && v != 33 && v != 64) { fprintf(stderr, "sdt-kmers: --phred %llu: 33 or 64\n", v); return 255; }
-			if (c == 1019) qprm.phred_offset = (uint32_t)v;
-			else if (c == 1020) qprm.cut_q = (uint32_t)v;
-			else if (c == 1021) qprm.low_q = (uint32_t)v;
-			else if (c == 1022) qprm.max_low_pct = (uint32_t)v;
-			else qprm.max_ee_ppm = (uint32_t)v;
+		case O_SCREEN_K:
+			if (v < 11) { fprintf(stderr, "sdt-kmers: --screen-k %llu: 11 to 31\n", v); return 255; }
+			opt->screen_k = (uint32_t)v;
 			break;
-		}
-		case 'r': case 1024: case 1025: case 1026: case 1027: {
-			static const char *const names[] = {"--screen-k", "--min-hits", "--min-hit-pct", "--keep-matched"};
-			const char *opt = c == 'r' ? "-r" : names[c - 1024];
-			unsigned long long v;
-			if (!do_screen) { fprintf(stderr, "sdt-kmers: %s belongs to screen\n", opt); usage(); return 255; }
-			if (c == 'r') {
-				if (n_rfiles == MAX_REF_FILES) { fprintf(stderr, "sdt-kmers: more than %d -r files\n", MAX_REF_FILES); return 255; }
-				rfile[n_rfiles++] = optarg;
-				break;
-			}
-			if (c == 1027) { sprm.flags |= SDT_SCREEN_KEEP_MATCHED; break; }
-			if (parse_number(opt, optarg, c == 1024 ? 31 : (c == 1026 ? 100 : UINT32_MAX), &v) != 0) return 255;
-			if (c == 1024 && v < 11) { fprintf(stderr, "sdt-kmers: --screen-k %llu: 11 to 31\n", v); return 255; }
-			if (c == 1024) screen_k = (uint32_t)v;
-			else if (c == 1025) sprm.min_hits = (uint32_t)v;
-			else sprm.min_hit_pct = (uint32_t)v;
-			break;
-		}
-		case 1008:
-			if (!do_dedup) { fprintf(stderr, "sdt-kmers: --mate-swap belongs to dedup\n"); usage(); return 255; }
-			dprm.flags |= SDT_DEDUP_MATE_SWAP;
-			break;
+		case O_MIN_HITS: opt->screen.min_hits = (uint32_t)v; break;
+		case O_MIN_HIT_PCT: opt->screen.min_hit_pct = (uint32_t)v; break;
+		case O_KEEP_MATCHED: opt->screen.flags |= SDT_SCREEN_KEEP_MATCHED; break;
 		default: usage(); return 255;
 		}
 	}
-	if (!cfgfile[0] || (do_query ? !qfile[0] : !outname[0])) { usage(); return 255; }
-	if (do_screen && n_rfiles == 0) { fprintf(stderr, "sdt-kmers: screen needs a reference file: -r refs.fa\n"); usage(); return 255; }
-	if (do_norm && prm.target == 0) { fprintf(stderr, "sdt-kmers: --target must be at least 1\n"); return 255; }
-	if (xprm.flags & SDT_COMPLEXITY_TRIM) {
-		if (max_low_given && xprm.max_low_pct != 0) {
+	if (!opt->cfgfile[0] || (sub == QUERY ? !opt->qfile[0] : !opt->outname[0])) { usage(); return 255; }
+	if (sub == SCREEN && opt->n_rfiles == 0) { fprintf(stderr, "sdt-kmers: screen needs a reference file: -r refs.fa\n"); usage(); return 255; }
+	if (sub == NORMALIZE && opt->norm.target == 0) { fprintf(stderr, "sdt-kmers: --target must be at least 1\n"); return 255; }
+	if (opt->cx.flags & SDT_COMPLEXITY_TRIM) {
+		if (opt->max_low_given && opt->cx.max_low_pct != 0) {
 			fprintf(stderr, "sdt-kmers: --max-low %u with --trim-low: the longest clean stretch is kept, whatever fraction is low; give --max-low 0 or none\n",
-			        xprm.max_low_pct);
+			        opt->cx.max_low_pct);
 			return 255;
 		}
-		xprm.max_low_pct = 0;
+		opt->cx.max_low_pct = 0;
 	}
-	if (max_k == 0) max_k = K <= 31 ? 31 : SDT_MAX_K;
-	if (d > 127) d = (signed char)d;                                         /* deLowKmer is a char */
+	if (opt->max_k == 0) opt->max_k = opt->K <= 31 ? 31 : SDT_MAX_K;
+	if (opt->d > 127) opt->d = (signed char)opt->d;                          /* deLowKmer is a char */
 	/* pregraph.c:38-59 */
-	if (K % 2 == 0) { K++; printf("K should be an odd number\n"); }
-	if (K < 13) { K = 13; printf("K should not be less than 13\n"); }
-	else if (K > max_k) K = max_k;
-	const int nw = K <= 31 ? 1 : (K <= 63 ? 2 : 4);
+	if (opt->K % 2 == 0) { opt->K++; printf("K should be an odd number\n"); }
+	if (opt->K < 13) { opt->K = 13; printf("K should not be less than 13\n"); }
+	else if (opt->K > opt->max_k) opt->K = opt->max_k;
+	return 0;
+}
 
-	/* the adapter files are read and checked before the device is touched, the 3' file first */
-	sdt_adapter_list ads;
-	memset(&ads, 0, sizeof ads);
-	for (int e = 0; e < 2 && do_clip; e++) {
-		char err[4400];
-		if (afile[e][0] && sdt_adapters_load(&ads, afile[e], e, err, sizeof err) != 0) { fprintf(stderr, "sdt-kmers: %s\n", err); return 2; }
-	}
-	for (uint32_t i = 0; i < ads.n; i++)
-		if (ads.offsets[i + 1] - ads.offsets[i] < cprm.min_overlap) {
-			fprintf(stderr, "sdt-kmers: adapter %s has %llu bases, fewer than --min-overlap %u\n", ads.names[i],
-			        (unsigned long long)(ads.offsets[i + 1] - ads.offsets[i]), cprm.min_overlap);
+/* what the options name is read and checked before the device is touched: the adapter files (the 3' file first), the reference files
+ * in the order given, the query file, the library config, and for qtrim that every library is FASTQ.  0, or the exit code */
+static int load_inputs(int sub, options *opt, sdt_cfg *cfg)
+{
+	char err[4400];
+	for (int e = 0; e < 2; e++)
+		if (opt->afile[e][0] && sdt_adapters_load(&opt->ads, opt->afile[e], e, err, sizeof err) != 0) { fprintf(stderr, "sdt-kmers: %s\n", err); return 2; }
+	for (uint32_t i = 0; i < opt->ads.n; i++)
+		if (opt->ads.offsets[i + 1] - opt->ads.offsets[i] < opt->clip.min_overlap) {
+			fprintf(stderr, "sdt-kmers: adapter %s has %llu bases, fewer than --min-overlap %u\n", opt->ads.names[i],
+			        (unsigned long long)(opt->ads.offsets[i + 1] - opt->ads.offsets[i]), opt->clip.min_overlap);
 			return 2;
 		}
-	/* the reference files are read and checked before the device is touched, in the order given */
-	sdt_ref_set refs;
-	memset(&refs, 0, sizeof refs);
-	for (int i = 0; i < n_rfiles; i++) {
-		char err[4400];
-		if (sdt_refs_load(&refs, rfile[i], err, sizeof err) != 0) { fprintf(stderr, "sdt-kmers: %s\n", err); return 2; }
-	}
-	if (do_screen) {
-		if (sdt_refs_pack(&refs) != 0) { fprintf(stderr, "sdt-kmers: out of memory for the references\n"); return 2; }
+	for (int i = 0; i < opt->n_rfiles; i++)
+		if (sdt_refs_load(&opt->refs, opt->rfile[i], err, sizeof err) != 0) { fprintf(stderr, "sdt-kmers: %s\n", err); return 2; }
+	if (sub == SCREEN) {
+		const sdt_ref_set *refs = &opt->refs;
+		if (sdt_refs_pack(&opt->refs) != 0) { fprintf(stderr, "sdt-kmers: out of memory for the references\n"); return 2; }
 		uint64_t positions = 0;
-		for (uint64_t i = 0; i < refs.nseqs; i++)
-			if (refs.offsets[i + 1] - refs.offsets[i] >= screen_k) positions += refs.offsets[i + 1] - refs.offsets[i] - screen_k + 1;
-		if (positions == 0) { fprintf(stderr, "sdt-kmers: the references hold no stretch of %u letters ACGT: no k-mer to screen against\n", screen_k); return 2; }
+		for (uint64_t i = 0; i < refs->nseqs; i++)
+			if (refs->offsets[i + 1] - refs->offsets[i] >= opt->screen_k) positions += refs->offsets[i + 1] - refs->offsets[i] - opt->screen_k + 1;
+		if (positions == 0) { fprintf(stderr, "sdt-kmers: the references hold no stretch of %u letters ACGT: no k-mer to screen against\n", opt->screen_k); return 2; }
 	}
-	query_set qs;
-	memset(&qs, 0, sizeof qs);
-	if (do_query) {
-		const int rq = load_queries(qfile, K, nw, &qs);
+	if (sub == QUERY) {
+		const int rq = load_queries(opt->qfile, opt->K, opt->K <= 31 ? 1 : (opt->K <= 63 ? 2 : 4), &opt->qs);
 		if (rq != 0) return rq;
 	}
-	sdt_cfg cfg;
-	if (sdt_cfg_load(cfgfile, &cfg) != 0) return 255;
-	const int max_read_len = cfg.max_rd_len ? cfg.max_rd_len : 100;         /* prlHashReads.c:361-364 */
+	if (sdt_cfg_load(opt->cfgfile, cfg) != 0) return 255;
 	/* qtrim: every read needs its qualities; refused before the device is touched and before anything is written */
-	for (int i = 0; i < cfg.nlibs && do_qtrim; i++) {
-		const sdt_lib *l = &cfg.libs[i];
+	for (int i = 0; i < cfg->nlibs && sub == QTRIM; i++) {
+		const sdt_lib *l = &cfg->libs[i];
 		const char *fasta = l->nf ? l->f[0] : (l->nf1 ? l->f1[0] : (l->nf2 ? l->f2[0] : (l->np ? l->p[0] : (l->nb ? l->b[0] : NULL))));
 		if (fasta) { fprintf(stderr, "sdt-kmers: qtrim needs base qualities: %s is not a FASTQ file (q1= / q2= / q=)\n", fasta); return 2; }
 	}
+	return 0;
+}
 
-	sdt_ctx *gpu = NULL;
-	if (sdt_gpu_init(&gpu, device, K, 0, do_query ? 0u : SDT_FLAG_KEEP_READS) != SDT_OK) {
-		fprintf(stderr, "sdt_gpu_init: %s\n", sdt_gpu_last_error());
-		return 1;
-	}
-	sdt_pair_ranges pairs;
-	memset(&pairs, 0, sizeof pairs);
-	push_state st = {gpu, 0, do_norm || do_trim || do_dedup || do_clip || do_overlap || do_cx || do_qtrim || do_screen ? &pairs : NULL};
-	qtrim_state qst;
-	memset(&qst, 0, sizeof qst);
-	if (do_qtrim) {
-		if (sdt_gpu_init(&qst.qgpu, device, K, 1, 0) != SDT_OK) { fprintf(stderr, "sdt_gpu_init: %s\n", sdt_gpu_last_error()); return 1; }
-		qst.push = st;
-		qst.prm = &qprm;
+/* the libraries through pass 1 (qtrim: every batch's qualities judged on the way); 0 with *reads, or 1 */
+static int stream_and_count(sdt_ctx *gpu, int sub, options *opt, const sdt_cfg *cfg, sdt_pair_ranges *pairs, qtrim_state *qst, unsigned long long *reads)
+{
+	const int max_read_len = cfg->max_rd_len ? cfg->max_rd_len : 100;       /* prlHashReads.c:361-364 */
+	push_state st = {gpu, 0, subcommands[sub].pairs ? pairs : NULL};
+	if (sub == QTRIM) {
+		if (SDT_CALL(sdt_gpu_init, &qst->qgpu, opt->device, opt->K, 1, 0)) return 1;
+		qst->push = st;
+		qst->prm = &opt->qual;
 		sdt_read_quals(1);
 	}
 	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
-	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : threads;
+	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : opt->threads;
 	sdt_pool_enable(sdt_gpu_host_alloc, sdt_gpu_host_free, parse_threads + PUSH_DEPTH + 8);
-	int rc = do_qtrim ? sdt_stream_reads(&cfg, max_read_len, parse_threads > 0 ? parse_threads : 1, chunk, 0, qtrim_batch, &qst, NULL)
-	                  : sdt_stream_reads(&cfg, max_read_len, parse_threads > 0 ? parse_threads : 1, chunk, 0, push_batch, &st, NULL);
-	if (do_qtrim) {
-		st.reads = qst.push.reads;
+	int rc = sub == QTRIM ? sdt_stream_reads(cfg, max_read_len, parse_threads > 0 ? parse_threads : 1, chunk, 0, qtrim_batch, qst, NULL)
+	                      : sdt_stream_reads(cfg, max_read_len, parse_threads > 0 ? parse_threads : 1, chunk, 0, push_batch, &st, NULL);
+	if (sub == QTRIM) {
+		st.reads = qst->push.reads;
 		sdt_read_quals(0);
-		sdt_gpu_destroy(qst.qgpu);
+		sdt_gpu_destroy(qst->qgpu);
 	}
 	if (rc == 0 && inflight_retire(gpu, 0) != 0) rc = -1;
 	sdt_pool_disable();
 	if (rc != 0) { sdt_gpu_destroy(gpu); return 1; }
 	uint64_t kmers = 0, nodes = 0, removed = 0;
-	if (sdt_gpu_finish_count(gpu, &kmers, &nodes) != SDT_OK) { fprintf(stderr, "sdt_gpu_finish_count: %s\n", sdt_gpu_last_error()); return 1; }
+	if (SDT_CALL(sdt_gpu_finish_count, gpu, &kmers, &nodes)) return 1;
 	printf("%llu reads, %llu nodes allocated, %llu kmer in reads\n", st.reads, (unsigned long long)nodes, (unsigned long long)kmers);
-	if (d && sdt_gpu_delow(gpu, d, &removed) != SDT_OK) { fprintf(stderr, "sdt_gpu_delow: %s\n", sdt_gpu_last_error()); return 1; }
-	if (d) printf("%llu kmer removed\n", (unsigned long long)removed);
+	if (opt->d && SDT_CALL(sdt_gpu_delow, gpu, opt->d, &removed)) return 1;
+	if (opt->d) printf("%llu kmer removed\n", (unsigned long long)removed);
+	*reads = st.reads;
+	return 0;
+}
 
-	if (do_norm) {
-		if (normalize_and_write(gpu, st.reads, &prm, &pairs, outname) != 0) return 1;
-		sdt_pair_ranges_free(&pairs);
-	} else if (do_trim) {
-		tprm.min_count = (uint32_t)min_count;
-		if (trim_and_write(gpu, st.reads, &tprm, &pairs, outname) != 0) return 1;
-		sdt_pair_ranges_free(&pairs);
-	} else if (do_dedup) {
-		if (dedup_and_write(gpu, st.reads, &dprm, &pairs, outname) != 0) return 1;
-		sdt_pair_ranges_free(&pairs);
-	} else if (do_clip) {
-		if (clip_and_write(gpu, st.reads, &cprm, &ads, &pairs, outname) != 0) return 1;
-		sdt_pair_ranges_free(&pairs);
-		sdt_adapters_free(&ads);
-	} else if (do_overlap) {
-		if (overlap_and_write(gpu, st.reads, &oprm, &pairs, outname) != 0) return 1;
-		sdt_pair_ranges_free(&pairs);
-	} else if (do_cx) {
-		if (complexity_and_write(gpu, st.reads, &xprm, &pairs, outname) != 0) return 1;
-		sdt_pair_ranges_free(&pairs);
-	} else if (do_screen) {
-		if (screen_and_write(gpu, st.reads, &sprm, screen_k, &refs, &pairs, outname) != 0) return 1;
-		sdt_pair_ranges_free(&pairs);
-		sdt_refs_free(&refs);
-	} else if (do_qtrim) {
-		if (st.reads > qst.cap) { fprintf(stderr, "sdt-kmers: %llu reads streamed, records for %llu\n", st.reads, (unsigned long long)qst.cap); return 1; }
-		if (qtrim_and_write(gpu, st.reads, &qprm, qst.rec, qst.n_kept, &pairs, outname) != 0) return 1;
-		sdt_pair_ranges_free(&pairs);
-		free(qst.rec); free(qst.dense);
-	} else if (do_correct) {
-		if (correct_and_write(gpu, st.reads, (uint32_t)min_count, outname) != 0) return 1;
-	} else if (!do_query) {
-		char path[4200];
-		snprintf(path, sizeof path, "%s.readCov", outname);
-		sdt_read_cov *cov = (sdt_read_cov *)calloc(st.reads ? st.reads : 1, sizeof(sdt_read_cov));
-		if (!cov) { fprintf(stderr, "sdt-kmers: out of memory for %llu records\n", st.reads); return 1; }
-		uint64_t got = 0;
-		if (sdt_gpu_profile_kept_reads(gpu, (uint32_t)min_count, cov, st.reads, &got) != SDT_OK) {
-			fprintf(stderr, "sdt_gpu_profile_kept_reads: %s\n", sdt_gpu_last_error());
-			return 1;
-		}
-		if (got != st.reads) { fprintf(stderr, "sdt-kmers: %llu reads streamed, %llu profiled\n", st.reads, (unsigned long long)got); return 1; }
-		if (write_read_cov(path, cov, st.reads) != 0) return 1;
-		printf("%llu reads profiled into %s\n", st.reads, path);
-		free(cov);
-	} else {
-		/* `linear` is thread_mark's flag (prlHashReads.c:911-967): marked on the table as it is now */
-		int64_t hist[257];
-		uint64_t linear = 0;
-		if (sdt_gpu_mark_and_hist(gpu, hist, &linear) != SDT_OK) { fprintf(stderr, "sdt_gpu_mark_and_hist: %s\n", sdt_gpu_last_error()); return 1; }
-		const uint64_t n = qs.n, m = n ? n : 1;
-		uint32_t *cnt = (uint32_t *)calloc(m, 4), *ll = (uint32_t *)calloc(m, 4), *rf = (uint32_t *)calloc(m, 4);
-		uint8_t *stt = (uint8_t *)calloc(m, 1);
-		if (!cnt || !ll || !rf || !stt) { fprintf(stderr, "sdt-kmers: out of memory\n"); return 1; }
-		if (sdt_gpu_search_kmers(gpu, qs.keys, n, cnt, ll, rf, stt) != SDT_OK) { fprintf(stderr, "sdt_gpu_search_kmers: %s\n", sdt_gpu_last_error()); return 1; }
-		FILE *fo = outname[0] ? fopen(outname, "w") : stdout;
-		if (!fo) { fprintf(stderr, "sdt-kmers: cannot write %s\n", outname); return 1; }
-		for (uint64_t i = 0; i < n; i++)
-			fprintf(fo, "%s\t%d\t%c\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", qs.text[i], stt[i] & 1, (stt[i] & 2) ? '-' : '+', cnt[i],
-			        ll[i] & 63u, (ll[i] >> 6) & 63u, (ll[i] >> 12) & 63u, (ll[i] >> 18) & 63u,
-			        rf[i] & 63u, (rf[i] >> 6) & 63u, (rf[i] >> 12) & 63u, (rf[i] >> 18) & 63u, (rf[i] >> 24) & 1u, (rf[i] >> 25) & 1u);
-		if (fo != stdout && fclose(fo) != 0) { fprintf(stderr, "sdt-kmers: write to %s failed\n", outname); return 1; }
-		free(cnt); free(ll); free(rf); free(stt);
-	}
+int main(int argc, char **argv)
+{
+	int sub = 0;
+	while (sub < N_SUBCOMMANDS && (argc < 2 || strcmp(argv[1], subcommands[sub].name) != 0)) sub++;
+	if (sub == N_SUBCOMMANDS) { usage(); return 255; }
+	static options opt = {.K = 23, .threads = 8,
+	                      .norm = {50, 10000, 0}, .clip = {5, 10, 0, 10, 20, 0, 0, 0}, .overlap = {30, 10, 0, 0}, .cx = {10, 50, 0, 0},
+	                      .qual = {33, 20, 15, 40, 0, 0, 0, 0}, .screen = {1, 0, 0, 0},
+	                      .screen_k = 31};                                   /* bbduk's usual figure: a choice, not a measurement */
+	opt.min_count = subcommands[sub].min_count;
+	sdt_cfg cfg;
+	int rc = parse_options(argc - 1, argv + 1, sub, &opt);
+	if (rc == 0) rc = load_inputs(sub, &opt, &cfg);
+	if (rc != 0) return rc;
+
+	sdt_ctx *gpu = NULL;
+	if (SDT_CALL(sdt_gpu_init, &gpu, opt.device, opt.K, 0, subcommands[sub].keep_reads ? SDT_FLAG_KEEP_READS : 0u)) return 1;
+	sdt_pair_ranges pairs;
+	memset(&pairs, 0, sizeof pairs);
+	static qtrim_state qst;
+	opt.qtrim = &qst;
+	unsigned long long reads = 0;
+	if (stream_and_count(gpu, sub, &opt, &cfg, &pairs, &qst, &reads) != 0) return 1;
+	if (subcommands[sub].run(gpu, reads, &opt, &pairs) != 0) return 1;
+	sdt_pair_ranges_free(&pairs);
+	sdt_adapters_free(&opt.ads);
+	sdt_refs_free(&opt.refs);
+	free(qst.rec); free(qst.dense);
 	sdt_gpu_destroy(gpu);
 	sdt_cfg_free(&cfg);
 	return 0;

@@ -11,6 +11,9 @@
 static int failures;
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); failures++; } } while (0)
 
+/* what the route asks of the records' owner: is anything of read `ord` kept */
+static int alive(const void *recs, uint64_t ord) { return ((const sdt_read_trim *)recs)[ord].len != 0; }
+
 int main(void)
 {
 	/* ordinals: 0..2 single reads, [3, 11) four pairs of a pair of files (the range starts at an odd ordinal), 11 a single read,
@@ -45,18 +48,18 @@ int main(void)
 	size_t cur = 0;
 	int pairs_out = 0;
 	for (uint64_t ord = 0; ord < nrec; ord++) {
-		const int got = sdt_trim_route(&pr, &cur, t, nrec, ord);
+		const int got = sdt_trim_route(&pr, &cur, alive, t, nrec, ord);
 		CHECK(got == want[ord]);
 		pairs_out += got == SDT_TRIM_TO_PAIRS;
 	}
 	CHECK(pairs_out % 2 == 0);
-	CHECK(sdt_trim_route(&pr, &cur, t, nrec, nrec) == SDT_TRIM_TO_NONE); /* past the records */
+	CHECK(sdt_trim_route(&pr, &cur, alive, t, nrec, nrec) == SDT_TRIM_TO_NONE); /* past the records */
 	/* no ranges at all */
 	sdt_pair_ranges none;
 	memset(&none, 0, sizeof none);
 	cur = 0;
-	CHECK(sdt_trim_route(&none, &cur, t, nrec, 3) == SDT_TRIM_TO_SINGLE);
-	CHECK(sdt_trim_route(&none, &cur, t, nrec, 5) == SDT_TRIM_TO_NONE);
+	CHECK(sdt_trim_route(&none, &cur, alive, t, nrec, 3) == SDT_TRIM_TO_SINGLE);
+	CHECK(sdt_trim_route(&none, &cur, alive, t, nrec, 5) == SDT_TRIM_TO_NONE);
 
 	/* the record line: the widest fields fill the promised size exactly, the smallest take 12 bytes */
 	char *line = (char *)malloc(SDT_TRIM_LINE_MAX);
