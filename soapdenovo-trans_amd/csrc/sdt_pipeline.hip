@@ -224,7 +224,6 @@ int sk_list1(sdt_ctx *c)
 int sk_split(sdt_ctx *c, const SkPool &src, const uint32_t *list, uint32_t nitems, hipEvent_t after_l2)
 {
 	sdt_ctx::SkState &k = c->sk;
-	const int g = c->cu_count * 8;
 	SK_CHK(hipMemsetAsync(k.p2.next, 0, 4, c->stream));
 	SK_CHK(hipMemsetAsync(k.kmers2, 0, SK_NBF * 8, c->stream));
 	SK_CHK(hipMemsetAsync(k.cnt2, 0, SK_NBF * 4, c->stream));
@@ -247,8 +246,9 @@ int sk_split(sdt_ctx *c, const SkPool &src, const uint32_t *list, uint32_t nitem
 	}
 	if (after_l2)
 		SK_CHK(hipEventRecord(after_l2, c->stream));
-	hipLaunchKernelGGL(k_sk_scan, dim3(1), dim3(1024), 0, c->stream, k.cnt2, k.off2, k.fill2, (int)SK_NBF, (const unsigned long long *)k.kmers2, k.kpre2);
-	hipLaunchKernelGGL(k_sk_chunk_place, dim3(g), dim3(256), 0, c->stream, k.p2, k.off2, k.fill2, k.list2);
+	hipLaunchKernelGGL(k_sk_scan_wide, dim3((SK_NBF + 1023) / 1024), dim3(1024), 0, c->stream, k.cnt2, k.off2, k.fill2, (int)SK_NBF, (const unsigned long long *)k.kmers2, k.kpre2);
+	// (two workgroups of 1024 per CU: all the waves a CU holds)
+	hipLaunchKernelGGL(k_sk_chunk_place, dim3(c->cu_count * 2), dim3(SK_PLACE_TPB), 0, c->stream, k.p2, k.off2, k.fill2, k.list2);
 	SK_CHK(hipGetLastError());
 	SK_CHK(hipMemcpyAsync(k.h_kpre2, k.kpre2, (SK_NBF + 1) * 8, hipMemcpyDeviceToHost, c->stream));
 	SK_CHK(hipMemcpyAsync(k.h_off2, k.off2, (SK_NBF + 1) * 4, hipMemcpyDeviceToHost, c->stream));

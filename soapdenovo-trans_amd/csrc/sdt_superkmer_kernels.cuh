@@ -389,18 +389,146 @@ static __global__ __launch_bounds__(1024) void k_sk_scan(const uint32_t *__restr
 	}
 }
 
-static __global__ __launch_bounds__(256) void k_sk_chunk_place(SkPool pool, const uint32_t *__restrict__ off, uint32_t *__restrict__ fillcur,
-                                                        uint32_t *__restrict__ list)
+// the same scans for many buckets (level 2: 2^18) on the whole chip: workgroup w owns the buckets [1024 w, 1024 w + 1024).  It sums
+// everything in front of them itself -- w loads per lane out of L2, 3 MB for the last workgroup -- instead of waiting for a second
+// kernel or for its neighbours: one launch, no scratch buffer, and the longest workgroup is a few tens of microseconds where the one
+// workgroup of k_sk_scan took 1.18 ms.  off[0..nb], kpre[0..nb] and fillcur = 0 come out as k_sk_scan writes them.
+static __global__ __launch_bounds__(1024) void k_sk_scan_wide(const uint32_t *__restrict__ cnt, uint32_t *__restrict__ off, uint32_t *__restrict__ fillcur,
+                                                       int nb, const unsigned long long *__restrict__ kmers, unsigned long long *__restrict__ kpre)
 {
+	__shared__ unsigned long long s_a[1024], s_b[1024], s_front[2];
+	const int t = threadIdx.x, base = (int)blockIdx.x * 1024, i = base + t;
+	if (t < 2)
+		s_front[t] = 0;
+	unsigned long long a = 0, b = 0;
+	for (int j = t; j < base; j += 1024) {
+		a += cnt[j];
+		b += kmers[j];
+	}
+#pragma unroll
+	for (int d = 32; d > 0; d >>= 1) {
+		a += __shfl_down(a, d);
+		b += __shfl_down(b, d);
+	}
+	const uint32_t ci = i < nb ? cnt[i] : 0u;
+	const unsigned long long ki = i < nb ? kmers[i] : 0ULL;
+	s_a[t] = ci;
+	s_b[t] = ki;
+	__syncthreads();
+	if ((t & 63) == 0 && base) {
+		atomicAdd(&s_front[0], a);
+		atomicAdd(&s_front[1], b);
+	}
+	for (int d = 1; d < 1024; d <<= 1) {
+		const unsigned long long va = t >= d ? s_a[t - d] : 0, vb = t >= d ? s_b[t - d] : 0;
+		__syncthreads();
+		s_a[t] += va;
+		s_b[t] += vb;
+		__syncthreads();
+	}
+	a = s_front[0] + (t ? s_a[t - 1] : 0);
+	b = s_front[1] + (t ? s_b[t - 1] : 0);
+	if (i < nb) {
+		off[i] = (uint32_t)a;
+		fillcur[i] = 0;
+		kpre[i] = b;
+	}
+	if (i == nb - 1) {
+		off[nb] = (uint32_t)(a + ci);
+		kpre[nb] = b + ki;
+	}
+}
+
+// Level 2 (2^18 buckets).  A list entry carries the chunk's fill (1..16) above the 28-bit chunk id, so that k_sk_count needs no look at
+// pool.meta between the chunk id and the record (one memory round trip and one live register less).
+// One returning global atomic and one scattered 4-byte store per chunk (154 M per step of the 200 M-read workload) left L2 as one
+// partly written 64-byte block per entry: WRITE_SIZE 8.5 GB for 0.6 GB of list, 4.28 ms.  So, like k_sk_chunk_place_few, a workgroup
+// takes a STRETCH of chunk ids, counts it per bucket in LDS, reserves one run per bucket with one global atomic and stores the
+// stretch's entries into the runs: the entries of a run are stored within one pass of one workgroup and meet in L2.
+// The level-2 scatter takes its ids in blocks of SK_BLK2 per work item, and a work item is one level-1 bucket; the ~256 items
+// running at a time come from a handful of level-1 buckets (70 items per bucket in that workload), so a stretch of 32 blocks names
+// few level-1 buckets but each of their 1024 sub-buckets several times.  The LDS counters are SK_PLACE_SLOTS x 1024: a level-1
+// bucket takes the first free slot when its first chunk is seen; a chunk whose level-1 bucket finds no slot left takes the
+// per-chunk path.  Nothing is kept per chunk between the passes (the second pass reads pool.meta again, out of L2), so
+// the order of a bucket's chunks in the list is that of arrival, as it always was: the count stage does not depend on it.
+constexpr uint32_t SK_PLACE_TPB = 1024, SK_PLACE_STRETCH = 32u * SK_BLK2, SK_PLACE_SLOTS = 8;
+
+// slot of level-1 bucket b1 (claim = true: the first free one is taken); -1: none
+template <bool CLAIM> __device__ inline int sk_place_slot(uint32_t *s_b1, uint32_t b1)
+{
+	for (int s = 0; s < (int)SK_PLACE_SLOTS; s++) {
+		uint32_t v = __hip_atomic_load(&s_b1[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+		if (CLAIM && v == SK_NOCHUNK) {
+			v = atomicCAS(&s_b1[s], SK_NOCHUNK, b1);
+			if (v == SK_NOCHUNK)
+				v = b1;
+		}
+		if (v == b1)
+			return s;
+		// (a slot never changes once it is taken, so a bucket sits in at most one: the first that others do not hold)
+	}
+	return -1;
+}
+
+static __global__ __launch_bounds__(SK_PLACE_TPB) void k_sk_chunk_place(SkPool pool, const uint32_t *__restrict__ off, uint32_t *__restrict__ fillcur,
+                                                                 uint32_t *__restrict__ list)
+{
+	__shared__ uint32_t s_pos[SK_PLACE_SLOTS * SK_NB2];      // pass 1: chunks per bucket; then: the next list position of the bucket's run
+	__shared__ uint32_t s_b1[SK_PLACE_SLOTS];                // level-1 bucket of a slot (SK_NOCHUNK: free)
 	const uint32_t used = *pool.next, n = used < pool.chunks ? used : pool.chunks;
-	for (uint32_t c = blockIdx.x * 256u + threadIdx.x; c < n; c += gridDim.x * 256u) {
-		const uint32_t mt = pool.meta[c];
-		if (mt == SK_DEAD)
-			continue;
-		const uint32_t b = mt & 0xFFFFFFu;
-		// level 2 only: the entry carries the chunk's fill (1..16) above the 27-bit chunk id, so that k_sk_count needs no
-		// look at pool.meta between the chunk id and the record (one memory round trip and one live register less)
-		list[off[b] + atomicAdd(&fillcur[b], 1u)] = c | (((mt >> 24) - 1u) << SK_LIST2_FILL_SHIFT);
+	const uint32_t tid = threadIdx.x;
+	for (uint32_t c0 = blockIdx.x * SK_PLACE_STRETCH; c0 < n; c0 += gridDim.x * SK_PLACE_STRETCH) {
+		const uint32_t c1 = n - c0 < SK_PLACE_STRETCH ? n : c0 + SK_PLACE_STRETCH;
+		for (uint32_t i = tid; i < SK_PLACE_SLOTS * SK_NB2; i += SK_PLACE_TPB)
+			s_pos[i] = 0;
+		if (tid < SK_PLACE_SLOTS)
+			s_b1[tid] = SK_NOCHUNK;
+		__syncthreads();
+		{
+			uint32_t last_b1 = SK_NOCHUNK;
+			int last_s = -1;
+#pragma unroll 4
+			for (uint32_t c = c0 + tid; c < c1; c += SK_PLACE_TPB) {
+				const uint32_t mt = pool.meta[c];
+				if (mt == SK_DEAD)
+					continue;
+				const uint32_t b = mt & 0xFFFFFFu, b1 = b >> SK_L2BITS;
+				if (b1 != last_b1) {
+					last_b1 = b1;
+					last_s = sk_place_slot<true>(s_b1, b1);
+				}
+				if (last_s >= 0)
+					atomicAdd(&s_pos[(uint32_t)last_s * SK_NB2 + (b & (SK_NB2 - 1))], 1u);
+			}
+		}
+		__syncthreads();
+		for (uint32_t i = tid; i < SK_PLACE_SLOTS * SK_NB2; i += SK_PLACE_TPB) {
+			const uint32_t cnt = s_pos[i];
+			if (cnt) {
+				const uint32_t b = s_b1[i >> SK_L2BITS] * SK_NB2 + (i & (SK_NB2 - 1));
+				s_pos[i] = off[b] + atomicAdd(&fillcur[b], cnt);
+			}
+		}
+		__syncthreads();
+		{
+			uint32_t last_b1 = SK_NOCHUNK;
+			int last_s = -1;
+#pragma unroll 4
+			for (uint32_t c = c0 + tid; c < c1; c += SK_PLACE_TPB) {
+				const uint32_t mt = pool.meta[c];
+				if (mt == SK_DEAD)
+					continue;
+				const uint32_t b = mt & 0xFFFFFFu, b1 = b >> SK_L2BITS;
+				if (b1 != last_b1) {
+					last_b1 = b1;
+					last_s = sk_place_slot<false>(s_b1, b1);
+				}
+				const uint32_t at = last_s >= 0 ? atomicAdd(&s_pos[(uint32_t)last_s * SK_NB2 + (b & (SK_NB2 - 1))], 1u)
+				                                : off[b] + atomicAdd(&fillcur[b], 1u);
+				list[at] = c | (((mt >> 24) - 1u) << SK_LIST2_FILL_SHIFT);
+			}
+		}
+		__syncthreads();
 	}
 }
 
