@@ -74,7 +74,9 @@ int sdt_gpu_destroy(sdt_ctx *ctx);                 /* free_Sets (pregraph.c:107)
 const char *sdt_gpu_last_error(void);
 int sdt_gpu_abi_version(void);
 
-/* forget all nodes, keep allocations (a fresh prlRead2HashTable run on the same context) */
+/* forget all nodes, keep allocations (a fresh prlRead2HashTable run on the same context).  The clear of the node table is deferred: the
+ * first read pushes carry it inside their level-1 scatter, any other call that needs the table clears what is left first
+ * (INTEGRATION.md section 1); no call sees anything but an empty table. */
 int sdt_gpu_reset(sdt_ctx *ctx);
 
 /* ---- pass 1: chop + insert/count ------------------------------------------------------------- */
@@ -1066,7 +1068,10 @@ int sdt_gpu_kernel_time(sdt_ctx *ctx, int reset, double *ms, uint64_t *launches,
 #define SDT_STAGE_SK_COUNT    3   /* k_sk_count: LDS counting + merges */
 #define SDT_STAGE_SK_FOLD     4   /* (ABI 7: the fold of the node log; always 0 now) */
 #define SDT_NSTAGES           5
-#define SDT_NCOUNTERS         20   /* [16] distinct records of the count stage's tiles, [17] records (level-2), [18] k-mers of the distinct records, [19] reserved */
+#define SDT_NCOUNTERS         20   /* [16] distinct records of the count stage's tiles, [17] records (level-2), [18] k-mers of the distinct records,
+                                    * [19] table slots handed to k_clear since the last sdt_gpu_reset: what the level-1 scatter's fused launches left of the deferred
+                                    * clear.  Counted on the host when the k_clear is enqueued; where a replay launch has already cleared the whole table on the
+                                    * device (a pool that ran out of chunks), that k_clear finds it so and stores nothing, and is counted all the same */
 int sdt_gpu_stage_times(sdt_ctx *ctx, double ms[SDT_NSTAGES], uint64_t counters[SDT_NCOUNTERS]);
 /* the device table's slot hash of a canonical key (host-callable, identical to the device function) */
 uint64_t sdt_owner_hash(const uint64_t *key_words_msw_first, int nwords);

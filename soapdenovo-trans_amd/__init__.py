@@ -1287,7 +1287,7 @@ class PregraphGPU:
         self._check(self.lib.sdt_gpu_stage_times(self._ctx, ms, cnt))
         names = ("merges", "lds_spills", "pool_direct", "early_flushes", "chunks_l1", "chunks_l2", "batches", "batch_kmers", "cnt_ticks_setup",
                  "cnt_ticks_fill", "cnt_ticks_count", "cnt_ticks_merge", "sc_ticks_stage", "sc_ticks_minima", "sc_ticks_starts",
-                 "sc_ticks_emit", "distinct_records", "records", "distinct_record_kmers", "reserved1")
+                 "sc_ticks_emit", "distinct_records", "records", "distinct_record_kmers", "host_cleared_slots")
         return [float(x) for x in ms], dict(zip(names, (int(x) for x in cnt)))
 
 

@@ -105,7 +105,7 @@ int sdt_gpu_clip_reads_device(sdt_ctx *c, const void *d_packed_words, const void
 		return fail(SDT_EINVAL, "NULL argument");
 	int rc = args_ok(params, adapters);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	ClipState st;
 	rc = st.prepare(params, adapters);
 	if (rc != SDT_OK) return rc;
@@ -127,7 +127,7 @@ int sdt_gpu_clip_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwords
 	StreamCheck in;
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	ClipState st;
 	rc = st.prepare(params, adapters);
 	if (rc != SDT_OK) return rc;
@@ -151,6 +151,7 @@ int sdt_gpu_clip_kept_reads(sdt_ctx *c, const sdt_clip_params *params, const sdt
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER(c);
 	if (nreads) *nreads = 0;
 	if (n_kept) *n_kept = 0;
 	int rc = args_ok(params, adapters);
@@ -166,7 +167,6 @@ int sdt_gpu_clip_kept_reads(sdt_ctx *c, const sdt_clip_params *params, const sdt
 		return SDT_OK;
 	if (!clip)
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	ClipState st;
 	rc = st.prepare(params, adapters);

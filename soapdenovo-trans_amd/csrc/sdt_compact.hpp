@@ -67,7 +67,7 @@ static int compact_host(sdt_ctx *c, const char *what, const uint32_t *packed_wor
 		return fail(SDT_EFULL, "%s: the kept reads take %llu words and %d pad words, out_words holds %llu", what, (unsigned long long)need, TAIL_PAD,
 		            (unsigned long long)out_words_cap);
 	}
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	DevBuf d_w, d_o, d_s, d_ow, d_oo;
 	rc = d_w.get(in.need_words * sizeof(uint32_t), "compaction staging");
 	if (rc == SDT_OK) rc = d_o.get((nreads + 1) * sizeof(uint64_t), "compaction staging");

@@ -67,7 +67,7 @@ int sdt_gpu_complexity_reads_device(sdt_ctx *c, const void *d_packed_words, cons
 		return fail(SDT_EINVAL, "NULL argument");
 	int rc = args_ok(params);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	DevBuf ctr;
 	rc = ctr.get(sizeof(unsigned long long), "complexity counter");
 	if (rc != SDT_OK) return rc;
@@ -90,7 +90,7 @@ int sdt_gpu_complexity_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t 
 	StreamCheck in;
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	DevBuf ctr, d_r, d_k;
 	rc = ctr.get(sizeof(unsigned long long), "complexity counter");
 	if (rc != SDT_OK) return rc;
@@ -113,6 +113,7 @@ int sdt_gpu_complexity_kept_reads(sdt_ctx *c, const sdt_complexity_params *param
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER(c);
 	if (nreads) *nreads = 0;
 	if (n_kept) *n_kept = 0;
 	int rc = args_ok(params);
@@ -129,7 +130,6 @@ int sdt_gpu_complexity_kept_reads(sdt_ctx *c, const sdt_complexity_params *param
 		return SDT_OK;
 	if (!cx)
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	// batch by batch: dense records on the device, scattered to their ordinals on the host
 	DevBuf ctr, d_r;

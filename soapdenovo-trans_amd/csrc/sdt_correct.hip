@@ -86,7 +86,7 @@ int sdt_gpu_correct_reads_device(sdt_ctx *c, const void *d_packed_words, uint64_
 		return fail(SDT_EINVAL, "NULL argument");
 	int rc = search_ready(c, "sdt_gpu_correct_reads");
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	return correct_device(c, (const uint32_t *)d_packed_words, nwords, (const uint64_t *)d_offsets, nreads, max_read_len, min_count,
 	                      (ReadFix *)d_fix, (uint32_t *)d_out_words, (unsigned long long *)d_edits, max_edits, 0, 1, n_edits);
 }
@@ -108,7 +108,7 @@ int sdt_gpu_correct_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwo
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc == SDT_OK) rc = strip_plan(c, nreads, in.longest, &geo);      // (the whole call is refused before a piece's records are written)
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	// the edits of a piece name its reads from its first read's index in the batch
 	std::vector<uint64_t> all;
 	DevBuf d_r, eb;
@@ -138,6 +138,7 @@ int sdt_gpu_correct_kept_reads(sdt_ctx *c, uint32_t min_count, sdt_read_fix *fix
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER(c);
 	if (nreads) *nreads = 0;
 	if (n_edits) *n_edits = 0;
 	int rc = search_ready(c, "sdt_gpu_correct_kept_reads");
@@ -154,7 +155,6 @@ int sdt_gpu_correct_kept_reads(sdt_ctx *c, uint32_t min_count, sdt_read_fix *fix
 		return SDT_OK;
 	if (!fix)
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	// batch by batch: dense records on the device, scattered to their ordinals on the host
 	DevBuf d_r, eb;
@@ -185,6 +185,7 @@ int sdt_gpu_fetch_kept_batch(sdt_ctx *c, uint64_t i, uint64_t info[4], uint32_t 
 {
 	if (!c || !info)
 		return fail(SDT_EINVAL, "NULL argument");
+	SDT_ENTER(c);
 	const int rc = kept_ready(c);
 	if (rc != SDT_OK) return rc;
 	if (i >= c->kept.size())
@@ -201,7 +202,6 @@ int sdt_gpu_fetch_kept_batch(sdt_ctx *c, uint64_t i, uint64_t info[4], uint32_t 
 	if ((words && words_cap < kb.nwords) || (offsets && offsets_cap < kb.nreads + 1))
 		return fail(SDT_EFULL, "kept batch %llu has %llu words and %llu offsets", (unsigned long long)i, (unsigned long long)kb.nwords,
 		            (unsigned long long)(kb.nreads + 1));
-	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (the uploads) and the offsets of a fixed-length batch, made on the device
 	HIPCHK(hipStreamSynchronize(c->stream));
 	if (words) HIPCHK(hipMemcpy(words, kb.d_words, kb.nwords * sizeof(uint32_t), hipMemcpyDeviceToHost));

@@ -51,6 +51,13 @@ struct sdt_ctx {
 	void *d_ent = nullptr;
 	uint32_t *d_aux = nullptr;
 	uint64_t *d_first = nullptr;       // SDT_FLAG_TRACK_FIRST
+	// The clear DEBT: sdt_gpu_reset does not clear the table, it notes here that the slots [clear_lo, clear_hi) of entries, aux and first
+	// still have to be cleared.  The first fused launches of the level-1 scatter pay it off (sdt_clear_plan.h), settle_clear pays what is
+	// left with k_clear.  Only reset creates debt, and no code but those launches may see a table with debt: every entry point of the
+	// library begins with SDT_ENTER (which settles) -- except the read pushes that end in launch_count (SDT_ENTER_LAZY:
+	// they settle inside, where they stop fusing), reset (SDT_ENTER_LAZY: it replaces the debt) and destroy (it drops it).
+	uint64_t clear_lo = 0, clear_hi = 0;
+	uint64_t host_cleared = 0;         // slots settle_clear has handed to k_clear since the last reset (sdt_gpu_stage_times)
 	uint64_t ord_base = 0, ord_stride = 1;
 	Stats *d_stats = nullptr;
 	Stats *h_stats = nullptr;          // pinned
@@ -102,6 +109,9 @@ struct sdt_ctx {
 		uint4 *citems = nullptr, *h_citems = nullptr;       // work items of k_sk_count: [c0, c1) in list2 + their final buckets (device / pinned; sdt_count_plan.h)
 		uint32_t citems_cap = 0;
 		uint32_t *next_item = nullptr;                      // one counter per k_sk_count launch
+		uint16_t *cut = nullptr;                            // [cut_cap] per read of a fused scatter launch: emissions made before it was cut short
+		uint32_t *cut_flag = nullptr;                       // (sdt_sk_scatter_seq.cuh: SkFuse)
+		uint64_t cut_cap = 0;
 		uint32_t *h_off1 = nullptr, *h_off2 = nullptr;      // pinned
 		unsigned long long *h_kpre2 = nullptr;              // pinned
 		SkItem *h_items = nullptr;                          // pinned
@@ -213,10 +223,21 @@ inline int env_int(const char *name, int dflt) { const char *v = getenv(name); r
 inline int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // ---- sdt_gpu.hip ----
+int settle_clear(sdt_ctx *c);                  // what is left of the clear debt is cleared on c->stream; the debt is dropped
+// the two ways into the library (tests/test_entry_forms.py: every function of include/sdt_gpu.h that takes a context begins with one)
+#define SDT_ENTER_LAZY(c) HIPCHK(hipSetDevice((c)->device))
+#define SDT_ENTER(c)                                  \
+	do {                                              \
+		SDT_ENTER_LAZY(c);                            \
+		const int rc_enter_ = settle_clear(c);        \
+		if (rc_enter_ != SDT_OK) return rc_enter_;    \
+	} while (0)
 uint64_t flat_slots_for(uint64_t nodes);
 void *keep_alloc(sdt_ctx *c, size_t bytes);
 void keep_release(sdt_ctx *c);
-int launch_clear(sdt_ctx *c, void *ent, uint32_t *aux, uint64_t *first, uint64_t slots);
+// slots [lo, slots); the gates: k_clear (sdt_table_kernels.cuh)
+int launch_clear(sdt_ctx *c, void *ent, uint32_t *aux, uint64_t *first, uint64_t slots, uint64_t lo = 0, const uint32_t *only_if = nullptr,
+                 const unsigned long long *unless = nullptr);
 int alloc_table(sdt_ctx *c, uint64_t slots, void **ent, uint32_t **aux, uint64_t **first);
 int sync_stats(sdt_ctx *c);
 int grow_table(sdt_ctx *c, uint64_t need_nodes);

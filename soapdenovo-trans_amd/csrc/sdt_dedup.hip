@@ -116,7 +116,7 @@ int sdt_gpu_dedup_reads_device(sdt_ctx *c, const void *d_packed_words, const voi
 		return fail(SDT_EINVAL, "NULL argument");
 	const int rc = params_ok(params, nreads, paired);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	return dedup_device(c, (const uint32_t *)d_packed_words, (const uint64_t *)d_offsets, nreads, paired, params->flags, (ReadDup *)d_dup,
 	                    (uint8_t *)d_keep, n_kept);
 }
@@ -136,7 +136,7 @@ int sdt_gpu_dedup_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nword
 	StreamCheck in;
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	// copies of a read sit anywhere in the batch: the whole stream is staged at once
 	DevBuf d_w, d_o, d_r, d_k;
 	rc = d_w.get(in.need_words * sizeof(uint32_t), "duplicate staging");
@@ -160,6 +160,7 @@ int sdt_gpu_dedup_kept_reads(sdt_ctx *c, const sdt_dedup_params *params, const u
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER(c);
 	if (nreads) *nreads = 0;
 	if (n_kept) *n_kept = 0;
 	int rc = params_ok(params, 0, 0);
@@ -186,7 +187,6 @@ int sdt_gpu_dedup_kept_reads(sdt_ctx *c, const sdt_dedup_params *params, const u
 		return SDT_OK;
 	if (!dup)
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	std::vector<UnitStretch> segs(2 * n_ranges + 1);
 	uint64_t units = 0;

@@ -36,8 +36,11 @@ int sdti::fail(int code, const char *fmt, ...)
 uint64_t flat_slots_for(uint64_t nodes)
 {
 	static const int pct = sdt_tuning_env("SDT_TABLE_LOAD") && atoi(sdt_tuning_env("SDT_TABLE_LOAD")) >= 10 && atoi(sdt_tuning_env("SDT_TABLE_LOAD")) <= 69 ? atoi(sdt_tuning_env("SDT_TABLE_LOAD")) : 45;
-	uint64_t slots = (uint64_t)((double)nodes * 100.0 / pct) + 4095;
-	slots &= ~4095ULL;
+	// (SDT_TABLE_SLOT_ROUND: test hook -- a multiple of that instead, so that a slot count is no multiple of the unit of the fused clear,
+	// sdt_clear_plan.h: tests/test_fused_clear.py)
+	static const uint64_t step = (uint64_t)clamp_int(sdt_knob_int(sdt_test_env("SDT_TABLE_SLOT_ROUND"), 4096), 1, 4096);
+	uint64_t slots = (uint64_t)((double)nodes * 100.0 / pct) + step - 1;
+	slots -= slots % step;
 	return slots < (1ULL << 16) ? (1ULL << 16) : slots;
 }
 
@@ -70,13 +73,36 @@ void keep_release(sdt_ctx *c)
 }
 
 
-int launch_clear(sdt_ctx *c, void *ent, uint32_t *aux, uint64_t *first, uint64_t slots)
+int launch_clear(sdt_ctx *c, void *ent, uint32_t *aux, uint64_t *first, uint64_t slots, uint64_t lo, const uint32_t *only_if, const unsigned long long *unless)
 {
-	const int g = scan_grid(c, slots);
-	if (c->nw == 1) { Table<1> t{(Entry<1> *)ent, aux, slots, first}; hipLaunchKernelGGL(k_clear<1>, dim3(g), dim3(TPB), 0, c->stream, t); }
-	else if (c->nw == 2) { Table<2> t{(Entry<2> *)ent, aux, slots, first}; hipLaunchKernelGGL(k_clear<2>, dim3(g), dim3(TPB), 0, c->stream, t); }
-	else { Table<4> t{(Entry<4> *)ent, aux, slots, first}; hipLaunchKernelGGL(k_clear<4>, dim3(g), dim3(TPB), 0, c->stream, t); }
+	if (lo >= slots)
+		return SDT_OK;
+	const int g = scan_grid(c, slots - lo);
+	if (c->nw == 1) { Table<1> t{(Entry<1> *)ent, aux, slots, first}; hipLaunchKernelGGL(k_clear<1>, dim3(g), dim3(TPB), 0, c->stream, t, lo, only_if, unless); }
+	else if (c->nw == 2) { Table<2> t{(Entry<2> *)ent, aux, slots, first}; hipLaunchKernelGGL(k_clear<2>, dim3(g), dim3(TPB), 0, c->stream, t, lo, only_if, unless); }
+	else { Table<4> t{(Entry<4> *)ent, aux, slots, first}; hipLaunchKernelGGL(k_clear<4>, dim3(g), dim3(TPB), 0, c->stream, t, lo, only_if, unless); }
 	HIPCHK(hipGetLastError());
+	return SDT_OK;
+}
+
+// SDT_LAZY_CLEAR=0 (tuning switch and test hook): sdt_gpu_reset clears the table itself, as it did before the clear could ride on the
+// level-1 scatter
+static bool lazy_clear()
+{
+	static const bool on = sdt_knob_int(sdt_size_env("SDT_LAZY_CLEAR"), 1) != 0;
+	return on;
+}
+
+int settle_clear(sdt_ctx *c)
+{
+	if (c->clear_lo >= c->clear_hi)
+		return SDT_OK;
+	const uint64_t lo = c->clear_lo, hi = c->clear_hi;
+	const int rc = launch_clear(c, c->d_ent, c->d_aux, c->d_first, hi, lo, nullptr, &c->d_stats->clear_void);
+	if (rc != SDT_OK)
+		return rc;                                   // (the debt stays: the next entry tries again)
+	c->clear_lo = c->clear_hi = 0;
+	c->host_cleared += hi - lo;
 	return SDT_OK;
 }
 
@@ -144,6 +170,7 @@ int grow_table(sdt_ctx *c, uint64_t need_nodes)
 	// (any number of slots: what the nodes need at the load a fresh table is sized for, at least half as many again as before)
 	uint64_t slots = flat_slots_for(need_nodes);
 	if (slots < c->slots + c->slots / 2) slots = c->slots + c->slots / 2;
+	{ const int rcs = settle_clear(c); if (rcs != SDT_OK) return rcs; }       // (k_rehash reads the old table; the new one is cleared at once)
 	search_cache_drop(c);
 	void *ent = nullptr;
 	uint32_t *aux = nullptr;
@@ -183,6 +210,7 @@ int grow_table(sdt_ctx *c, uint64_t need_nodes)
 // be a new node); syncs only when the cheap upper bound says it could
 int ensure_room(sdt_ctx *c, uint64_t incoming)
 {
+	{ const int rcs = settle_clear(c); if (rcs != SDT_OK) return rcs; }       // whoever asks for room is about to put nodes into the table
 	const double room = (double)c->slots * MAX_LOAD;
 	if ((double)(c->distinct_known + c->kmers_since_sync + incoming) <= room)
 		return SDT_OK;
@@ -319,7 +347,7 @@ int sdt_gpu_destroy(sdt_ctx *c)
 {
 	if (!c)
 		return SDT_OK;
-	(void)hipSetDevice(c->device);
+	(void)hipSetDevice(c->device);                   // (no entry form: destroy frees whatever happens, and a debt dies with its table)
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
 	for (auto &p : c->ev) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -362,13 +390,19 @@ int sdt_gpu_reset(sdt_ctx *c)
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER_LAZY(c);                               // (a debt that is still open is replaced, not paid)
 	if ((c->flags & SDT_FLAG_TRACK_FIRST) && !c->d_first)           // (dropped once the device had laid the graph out: sdti::drop_first)
 		HIPCHK(hipMalloc((void **)&c->d_first, c->slots * sizeof(uint64_t)));
-	int rc = launch_clear(c, c->d_ent, c->d_aux, c->d_first, c->slots);
-	if (rc != SDT_OK)
-		return rc;
-	HIPCHK(hipMemsetAsync(c->d_stats, 0, sizeof(Stats), c->stream));
+	// the clear is a debt: the first launches of the level-1 scatter take it along (sdt_clear_plan.h), whoever else comes first settles it
+	HIPCHK(hipMemsetAsync(c->d_stats, 0, sizeof(Stats), c->stream));          // (Stats.clear_void with it: the new debt is all owed)
+	c->clear_lo = 0;
+	c->clear_hi = c->slots;
+	c->host_cleared = 0;
+	if (!lazy_clear()) {
+		const int rc = settle_clear(c);
+		if (rc != SDT_OK)
+			return rc;
+	}
 	search_cache_drop(c);
 	c->sk.l2_in_total = 0;
 	c->sk.stream_flushes = 0;
@@ -440,7 +474,7 @@ int sdt_gpu_set_stream(sdt_ctx *c, void *hip_stream)
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	HIPCHK(hipStreamSynchronize(c->stream));
 	if (c->own_stream) {
 		HIPCHK(hipStreamDestroy(c->stream));
@@ -501,6 +535,7 @@ static int launch_count(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_o
 			c->ord_base += nreads * c->ord_stride;     // the next batch continues the read stream
 		return rcs;
 	}
+	{ const int rcs = settle_clear(c); if (rcs != SDT_OK) return rcs; }       // the direct family counts into the table at once
 	uint64_t chunk_reads = CHUNK_KMERS / per_read;
 	chunk_reads = chunk_reads / TILE_READS * TILE_READS;
 	if (chunk_reads < TILE_READS)
@@ -549,10 +584,10 @@ static int push_reads_enqueue(sdt_ctx *c, const uint32_t *packed_words, uint64_t
 {
 	if (!c || (!packed_words && nwords) || (!offsets && !fixed_len))
 		return fail(SDT_EINVAL, "NULL argument");
+	SDT_ENTER_LAZY(c);                               // (the launch decides: the fused scatter takes the clear debt along, launch_count's direct family settles it)
 	if (ticket) *ticket = c->push_ticket;
 	if (nreads == 0)
 		return SDT_OK;
-	HIPCHK(hipSetDevice(c->device));
 	// nothing queued: the launch cursor is the truth (calls that count device-resident reads advance it on their own, and
 	// sdt_gpu_set_read_ordinal sets both when the queue is empty)
 	if (c->staged_head == c->staged.size()) {
@@ -714,9 +749,9 @@ int sdt_gpu_push_wait(sdt_ctx *c, uint64_t ticket)
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER_LAZY(c);                               // (a wait for a copy: part of the push, which may leave debt for the next one)
 	if (ticket == 0 || ticket > c->push_ticket)
 		return ticket == 0 ? SDT_OK : fail(SDT_EINVAL, "ticket %llu was never issued", (unsigned long long)ticket);
-	HIPCHK(hipSetDevice(c->device));
 	// (copies run in order on one stream: should the ring slot have been reused since, its event stands for a LATER copy)
 	HIPCHK(hipEventSynchronize(c->copied[(ticket - 1) % sdt_ctx::NSTAGE]));
 	return SDT_OK;
@@ -726,13 +761,13 @@ int sdt_gpu_hint_total_kmers(sdt_ctx *c, uint64_t kmers)
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER_LAZY(c);                               // (a hint before the first push must not cost the push its fused clear; grow_table settles)
 	c->expect_kmers = kmers;
 	// The node table for the job NOW -- while nothing is in it (growing it moves nothing) and BEFORE the pools of the locality pipeline
 	// take their share of what is free: pools sized for the announced job on a device whose table then doubles several times left the
 	// table's rebuilds fighting the pools for memory (200 M reads: count stage 0.3 -> 1-3 s, and every later table scan crawled).
 	// One distinct node per 28 k-mers is what deep transcriptome data gives (C3: 35); data that repeats less grows the table as before.
 	if (kmers && c->distinct_known == 0 && c->kmers_since_sync == 0 && c->kmers_total_host == 0 && !c->sk.ready && c->staged_head == c->staged.size()) {
-		HIPCHK(hipSetDevice(c->device));
 		size_t free_b = 0, total_b = 0;
 		HIPCHK(sdti::mem_info(&free_b, &total_b));
 		uint64_t est = kmers / 28;
@@ -765,7 +800,7 @@ int sdt_gpu_count_reads_device(sdt_ctx *c, const void *d_packed_words, uint64_t 
 		return fail(SDT_EINVAL, "NULL argument");
 	if (max_read_len == 0)
 		return fail(SDT_EINVAL, "max_read_len must be > 0");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER_LAZY(c);                               // (as the pushes)
 	const int rcd = drain_staged(c, true);               // (batches pushed earlier come first)
 	if (rcd != SDT_OK) return rcd;
 	return launch_count(c, (const uint32_t *)d_packed_words, (const uint64_t *)d_offsets, nreads, max_read_len);
@@ -775,7 +810,7 @@ int sdt_gpu_finish_count(sdt_ctx *c, uint64_t *kmers_processed, uint64_t *nodes)
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	int rc = sync_stats(c);
 	if (rc != SDT_OK)
 		return rc;
@@ -790,7 +825,7 @@ int sdt_gpu_delow(sdt_ctx *c, int d, uint64_t *removed)
 		return fail(SDT_EINVAL, "ctx is NULL");
 	if (d < 0)
 		d = 0;       // pregraph.c:159: negative -d becomes 0
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	{ const int rcd = drain_staged(c, true); if (rcd != SDT_OK) return rcd; }
 	HIPCHK(hipMemsetAsync(&c->d_stats->scratch, 0, sizeof(unsigned long long), c->stream));
 	const int g = scan_grid(c, view_slots(c));
@@ -809,7 +844,7 @@ int sdt_gpu_mark_and_hist(sdt_ctx *c, int64_t hist[257], uint64_t *linear)
 {
 	if (!c || !hist)
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	{ const int rcd = drain_staged(c, true); if (rcd != SDT_OK) return rcd; }
 	HIPCHK(hipMemsetAsync(&c->d_stats->scratch, 0, sizeof(unsigned long long), c->stream));
 	HIPCHK(hipMemsetAsync(c->d_hist, 0, 257 * sizeof(unsigned long long), c->stream));
@@ -831,7 +866,7 @@ int sdt_gpu_export_nodes(sdt_ctx *c, uint64_t *keys, uint32_t *l_links, uint32_t
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	int rc = sync_stats(c);
 	if (rc != SDT_OK)
 		return rc;
@@ -888,7 +923,7 @@ int sdt_gpu_release_table(sdt_ctx *c)
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	int rc = sdti::release_pass1(c);                 // drains pass 1; the pools go back
 	if (rc != SDT_OK) return rc;
 	search_cache_drop(c);
@@ -908,7 +943,7 @@ int sdt_gpu_kernel_time(sdt_ctx *c, int reset, double *ms, uint64_t *launches, u
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	HIPCHK(hipStreamSynchronize(c->stream));
 	double total = 0;
 	uint64_t km = 0;
@@ -941,7 +976,7 @@ int sdt_gpu_import_nodes(sdt_ctx *c, const uint64_t *keys, const uint32_t *l_lin
 		return fail(SDT_EINVAL, "NULL argument");
 	if (n == 0)
 		return SDT_OK;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	int rc = sync_stats(c);
 	if (rc != SDT_OK) return rc;
 	search_cache_drop(c);
@@ -980,7 +1015,7 @@ int sdt_gpu_stage_times(sdt_ctx *c, double ms[SDT_NSTAGES], uint64_t counters[SD
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	HIPCHK(hipStreamSynchronize(c->stream));
 	if (ms) {
 		for (int i = 0; i < SDT_NSTAGES; i++) ms[i] = 0;
@@ -1007,7 +1042,7 @@ int sdt_gpu_stage_times(sdt_ctx *c, double ms[SDT_NSTAGES], uint64_t counters[SD
 		counters[16] = c->h_stats->sk_distinct_recs;
 		counters[17] = c->h_stats->sk_records;
 		counters[18] = c->h_stats->sk_distinct_kmers;
-		counters[19] = 0;
+		counters[19] = c->host_cleared;
 	}
 	return SDT_OK;
 }
@@ -1016,10 +1051,20 @@ int sdt_gpu_stage_times(sdt_ctx *c, double ms[SDT_NSTAGES], uint64_t counters[SD
 int drain_pushes(sdt_ctx *c, bool force) { return drain_staged(c, force); }
 
 // ---- what the graph unit (sdt_gpu_graph.hip) sees of a context ----------------------------------------------------
+static int graph_enter(sdt_ctx *c)
+{
+	SDT_ENTER(c);
+	return SDT_OK;
+}
+
 sdti::GraphView sdti::graph_view(sdt_ctx *c)
 {
 	GraphView v;
-	v.device = c->device; v.K = c->K; v.nw = c->nw; v.cu_count = c->cu_count;
+	v.device = c->device;
+	// (the graph unit's way into the library: it sees the table through this view only, so the device is set and a clear debt settled
+	//  here; what fails stays in v.rc, which every entry point of that unit returns first: GRAPH_ENTER)
+	v.rc = graph_enter(c);
+	v.K = c->K; v.nw = c->nw; v.cu_count = c->cu_count;
 	v.slots = view_slots(c);
 	v.d_ent = c->d_ent; v.d_aux = c->d_aux; v.d_first = c->d_first;
 	v.d_stats = c->d_stats; v.h_stats = c->h_stats;
@@ -1034,7 +1079,7 @@ int sdti::sync_stats(sdt_ctx *c) { return ::sync_stats(c); }
 // the first-occurrence ordinals have done their work (the device has the visiting order): 8 bytes per table slot go back to the arena
 int sdti::drop_first(sdt_ctx *c)
 {
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	if (c->d_first) { HIPCHK(hipFree(c->d_first)); c->d_first = nullptr; }
 	return SDT_OK;
 }

@@ -130,7 +130,7 @@ extern "C" int sdt_gpu_layout_on_device(sdt_ctx *c, int p, int nw_variant, int s
 {
 	if (!c || !n_out || !set_start) return fail(SDT_EINVAL, "NULL argument");
 	const GraphView v0 = sdti::graph_view(c);
-	HIPCHK(hipSetDevice(v0.device));
+	GRAPH_ENTER(v0);
 	struct timespec ts0_; clock_gettime(CLOCK_MONOTONIC, &ts0_);
 	const double t_call = ts0_.tv_sec * 1e3 + ts0_.tv_nsec * 1e-6;
 	const bool timing = sdt_env("SDT_TIMING") != nullptr;
@@ -397,7 +397,7 @@ int sdt_gpu_layout_sorted_keys(sdt_ctx *c, int p, int nw_variant, uint64_t *keys
 {
 	if (!c || !n_out) return fail(SDT_EINVAL, "NULL argument");
 	const GraphView v0 = sdti::graph_view(c);
-	HIPCHK(hipSetDevice(v0.device));
+	GRAPH_ENTER(v0);
 	int rc = sdti::release_pass1(c);                          // drains pass 1; its pools are not needed any more
 	if (rc != SDT_OK) return rc;
 	const GraphView v = sdti::graph_view(c);                  // (the drain may have grown the table)
@@ -448,7 +448,7 @@ int sdt_gpu_layout_apply(sdt_ctx *c, const uint64_t *order, uint64_t n)
 	const GraphView v = sdti::graph_view(c);
 	sdti::GraphExt *gx = ext_of(v);
 	if (!gx->d_sval || gx->n_sorted != n) return fail(SDT_ESTATE, "call sdt_gpu_layout_sorted_keys first (it sorted %llu nodes, the order has %llu)", (unsigned long long)gx->n_sorted, (unsigned long long)n);
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	int rc = graph_choose_form(gx, n);
 	if (rc != SDT_OK) return rc;
 	if (*v.d_idx) { (void)hipFree(*v.d_idx); *v.d_idx = nullptr; }
@@ -482,7 +482,7 @@ int sdt_gpu_export_ordered(sdt_ctx *c, uint64_t *keys, uint32_t *l_links, uint32
 	const GraphView v = sdti::graph_view(c);
 	sdti::GraphExt *gx = ext_of(v);
 	if (!gx->d_slot_of || gx->n_nodes != n) return fail(SDT_ESTATE, "call sdt_gpu_layout_apply first (it numbered %llu nodes, the arrays hold %llu)", (unsigned long long)gx->n_nodes, (unsigned long long)n);
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	// in pieces of 32 M nodes, double buffered: the kernel of piece k + 1 runs while piece k is on the link
 	const uint64_t PIECE = (uint64_t)32 << 20;
 	Scratch S;
@@ -528,7 +528,7 @@ int sdt_gpu_update_nodes_by_index(sdt_ctx *c, const uint64_t *node, const uint32
 	const GraphView v = sdti::graph_view(c);
 	sdti::GraphExt *gx = ext_of(v);
 	if (!gx->d_slot_of) return fail(SDT_ESTATE, "call sdt_gpu_layout_apply first");
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	Scratch S;
 	uint64_t *d_n;
 	uint32_t *d_l, *d_r;
@@ -552,7 +552,7 @@ int sdt_gpu_tip_walks_labelled(sdt_ctx *c, int thin, int cut_len, uint64_t *n_re
 	if (!*v.d_idx || *v.idx_slots != v.slots) return fail(SDT_ESTATE, "call sdt_gpu_layout_apply (or sdt_gpu_set_node_index) first");
 	sdti::GraphExt *gx = ext_of(v);
 	if (!gx->wide && *v.idx_n >= 0xFFFFFFF0ULL) return fail(SDT_ESTATE, "%llu nodes numbered in the 32-bit form", (unsigned long long)*v.idx_n);
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	return gx->wide ? sdti::tip_walks_labelled(c, ix64_of(gx), thin, cut_len, n_records) : sdti::tip_walks_labelled(c, Ix32(), thin, cut_len, n_records);
 }
 
@@ -563,7 +563,7 @@ int sdt_gpu_minor_out_labelled(sdt_ctx *c, double threshold, uint64_t *n_junctio
 	if (!*v.d_idx || *v.idx_slots != v.slots) return fail(SDT_ESTATE, "call sdt_gpu_layout_apply (or sdt_gpu_set_node_index) first");
 	sdti::GraphExt *gx = ext_of(v);
 	if (!gx->wide && *v.idx_n >= 0xFFFFFFF0ULL) return fail(SDT_ESTATE, "%llu nodes numbered in the 32-bit form", (unsigned long long)*v.idx_n);
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	return gx->wide ? sdti::minor_out_labelled(c, ix64_of(gx), threshold, n_junctions, n_records) : sdti::minor_out_labelled(c, Ix32(), threshold, n_junctions, n_records);
 }
 
@@ -578,7 +578,7 @@ int sdt_gpu_minor_out_commit_begin(sdt_ctx *c, double threshold, uint64_t max_co
 	const uint64_t nn = gx->n_nodes, nr = gx->result_words / 14;
 	if (nr >= 0xFFFFFFF0ULL) return fail(SDT_EINVAL, "commit on the device: 32-bit record indices, %llu records", (unsigned long long)nr);
 	if (!gx->wide && nn >= 0xFFFFFFF0ULL) return fail(SDT_ESTATE, "%llu nodes numbered in the 32-bit form", (unsigned long long)nn);
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	return gx->wide ? sdti::minor_out_commit_begin(c, ix64_of(gx), threshold, max_component, largest, n_skipped, n_skipped_records)
 	                : sdti::minor_out_commit_begin(c, Ix32(), threshold, max_component, largest, n_skipped, n_skipped_records);
 }
@@ -590,7 +590,7 @@ int sdt_gpu_minor_out_commit_finish(sdt_ctx *c, uint64_t *off, uint64_t *linear,
 	const GraphView v = sdti::graph_view(c);
 	sdti::GraphExt *gx = ext_of(v);
 	if (!gx->mo_pending) return fail(SDT_ESTATE, "call sdt_gpu_minor_out_commit_begin first");
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	*off = *linear = *n_written = 0;
 	const uint64_t nn = gx->n_nodes;
 	unsigned long long h_cnt[5] = {0, 0, 0, 0, 0};
@@ -632,7 +632,7 @@ int sdt_gpu_fetch_skipped(sdt_ctx *c, uint64_t *dst, uint64_t n_records)
 	const GraphView v = sdti::graph_view(c);
 	sdti::GraphExt *gx = ext_of(v);
 	if (n_records != gx->n_skipped) return fail(SDT_EINVAL, "the last commit left %llu records to the host, asked for %llu", (unsigned long long)gx->n_skipped, (unsigned long long)n_records);
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	int rc = SDT_OK;
 	if (n_records) rc = sdti::d2h_big(v.copy_stream, dst, gx->d_skipped, n_records * 14 * 8);
 	if (rc == SDT_OK && gx->base) rebase_records(dst, n_records, 14, gx->base);
@@ -646,7 +646,7 @@ int sdt_gpu_fetch_written(sdt_ctx *c, uint64_t *node, uint32_t *l_links, uint32_
 	const GraphView v = sdti::graph_view(c);
 	sdti::GraphExt *gx = ext_of(v);
 	if (n != gx->n_written) return fail(SDT_EINVAL, "the last commit wrote %llu nodes, asked for %llu", (unsigned long long)gx->n_written, (unsigned long long)n);
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	int rc = SDT_OK;
 	if (n) rc = sdti::d2h_big(v.copy_stream, node, gx->d_wnode, n * 8);
 	if (n && rc == SDT_OK) rc = sdti::d2h_big(v.copy_stream, l_links, gx->d_wl, n * 4);
@@ -668,7 +668,7 @@ int sdt_gpu_build_edges(sdt_ctx *c, uint64_t *n_edges, uint64_t *num_ed, uint64_
 	sdti::GraphExt *gx = ext_of(v);
 	if (!gx->d_slot_of || !*v.d_idx || *v.idx_slots != v.slots || *v.idx_n != gx->n_nodes) return fail(SDT_ESTATE, "call sdt_gpu_layout_apply first");
 	if (!gx->wide && gx->n_nodes >= 0xFFFFFFF0ULL) return fail(SDT_ESTATE, "%llu nodes numbered in the 32-bit form", (unsigned long long)gx->n_nodes);
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	return gx->wide ? sdti::build_edges(c, ix64_of(gx), n_edges, num_ed, n_bases) : sdti::build_edges(c, Ix32(), n_edges, num_ed, n_bases);
 }
 
@@ -678,7 +678,7 @@ int sdt_gpu_fetch_edge_bases(sdt_ctx *c, char *dst, uint64_t nbytes)
 	const GraphView v = sdti::graph_view(c);
 	sdti::GraphExt *gx = ext_of(v);
 	if (nbytes != gx->seq_bytes) return fail(SDT_EINVAL, "the edges have %llu bases, asked for %llu", (unsigned long long)gx->seq_bytes, (unsigned long long)nbytes);
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	int rc = SDT_OK;
 	if (nbytes) rc = sdti::d2h_big(v.copy_stream, dst, gx->d_seq, nbytes);
 	if (gx->d_seq) (void)hipFree(gx->d_seq);
@@ -693,7 +693,7 @@ int sdt_gpu_fetch_records(sdt_ctx *c, uint64_t *dst, uint64_t nwords)
 	const GraphView v = sdti::graph_view(c);
 	sdti::GraphExt *gx = ext_of(v);
 	if (nwords != gx->result_words) return fail(SDT_EINVAL, "the last dry run left %llu words, asked for %llu", (unsigned long long)gx->result_words, (unsigned long long)nwords);
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	int rc = SDT_OK;
 	if (nwords) rc = sdti::d2h_big(v.copy_stream, dst, gx->d_result, nwords * 8);
 	if (rc == SDT_OK && gx->result_nodes && gx->base) rebase_records(dst, nwords / gx->result_stride, gx->result_stride, gx->base);
@@ -719,7 +719,7 @@ int sdt_gpu_set_node_index(sdt_ctx *c, const uint64_t *keys, uint64_t n)
 	const GraphView v = sdti::graph_view(c);
 	if (!c || (n && !keys))
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	HIPCHK(hipStreamSynchronize(v.stream));
 	if ((*v.d_idx)) HIPCHK(hipFree((*v.d_idx)));
 	(*v.d_idx) = nullptr;
@@ -750,7 +750,7 @@ int sdt_gpu_update_nodes(sdt_ctx *c, const uint64_t *keys, const uint32_t *l_lin
 		return fail(SDT_EINVAL, "NULL argument");
 	if (!n)
 		return SDT_OK;
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	uint64_t *d_k = nullptr;
 	uint32_t *d_l = nullptr, *d_r = nullptr;
 	int rc = upload_keys(c, keys, n, &d_k);
@@ -786,7 +786,7 @@ int sdt_gpu_tip_walks(sdt_ctx *c, int thin, int cut_len, uint64_t *end_idx, uint
 		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
 	if (n != (*v.idx_n))
 		return fail(SDT_EINVAL, "the node index holds %llu nodes, the output arrays %llu", (unsigned long long)(*v.idx_n), (unsigned long long)n);
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	uint64_t *d_e = nullptr;
 	uint8_t *d_i = nullptr;
 	HIPCHK(hipMalloc((void **)&d_e, (n ? n : 1) * sizeof(uint64_t)));
@@ -819,7 +819,7 @@ int sdt_gpu_minor_out_dry(sdt_ctx *c, double threshold, uint64_t *records, uint6
 		return fail(SDT_EINVAL, "NULL argument");
 	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
 		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	uint8_t *d_need = nullptr, *d_flag = nullptr;
 	uint64_t *d_rec = nullptr;
 	unsigned long long *d_cur = nullptr;
@@ -903,7 +903,7 @@ int sdt_gpu_build_host_index(sdt_ctx *c, uint32_t *index, uint64_t index_slots)
 		return fail(SDT_EINVAL, "index_slots must be a power of two >= 2 x nodes");
 	if ((*v.idx_n) >= 0xFFFFFFFEULL)
 		return fail(SDT_EINVAL, "%llu nodes do not fit 32-bit index entries", (unsigned long long)(*v.idx_n));
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	return host_index_entries<unsigned int>(c, v, index, index_slots);
 }
 
@@ -915,7 +915,7 @@ int sdt_gpu_build_host_index64(sdt_ctx *c, uint64_t *index, uint64_t index_slots
 		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
 	if (index_slots < 2 * (*v.idx_n) || (index_slots & (index_slots - 1)))
 		return fail(SDT_EINVAL, "index_slots must be a power of two >= 2 x nodes");
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	return host_index_entries<unsigned long long>(c, v, (unsigned long long *)index, index_slots);
 }
 
@@ -945,7 +945,7 @@ int sdt_gpu_edge_ports(sdt_ctx *c, uint64_t *records, uint64_t max_records, uint
 		return fail(SDT_EINVAL, "NULL argument");
 	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
 		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	uint64_t *d_rec = nullptr;
 	unsigned long long *d_cur = nullptr, h = 0;
 	const uint64_t m = max_records ? max_records : 1;
@@ -984,7 +984,7 @@ int sdt_gpu_tip_walks_compact(sdt_ctx *c, int thin, int cut_len, uint64_t *recor
 		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
 	if ((*v.idx_n) >= (1ULL << 56))
 		return fail(SDT_EINVAL, "node indices do not fit 56 bits");
-	HIPCHK(hipSetDevice(v.device));
+	GRAPH_ENTER(v);
 	uint64_t *d_rec = nullptr;
 	unsigned long long *d_cur = nullptr, h = 0;
 	const uint64_t m = max_records ? max_records : 1;

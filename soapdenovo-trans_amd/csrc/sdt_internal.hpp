@@ -55,8 +55,11 @@ struct GraphView {
 	uint64_t **d_idx;              // slot -> node index in the visiting order (fields of the context: load_paths reads them too)
 	uint64_t *idx_slots, *idx_n;
 	GraphExt **gx;
+	int rc;                        // SDT_OK, or why the context could not be entered (its device, its clear debt): GRAPH_ENTER returns it
 };
 GraphView graph_view(sdt_ctx *c);
+// every entry point of the graph unit, right behind its graph_view(c)
+#define GRAPH_ENTER(v) do { if ((v).rc != SDT_OK) return (v).rc; } while (0)
 
 template <int NW> inline sdt::Table<NW> table_of(const GraphView &v)
 {

@@ -37,7 +37,9 @@ static inline const char *sdt_tuning_env(const char *name)
 }
 
 /* the size thresholds of the locality pipeline (csrc/sdt_pipeline.hpp: batch, count launch, work item sizes) are tuning switches AND test
- * hooks: tests/test_fullsize_paths.py shrinks them so that inputs of test size take the branches that only a full-size batch reaches */
+ * hooks: tests/test_fullsize_paths.py shrinks them so that inputs of test size take the branches that only a full-size batch reaches.
+ * SDT_LAZY_CLEAR=0 is read the same way: sdt_gpu_reset then clears the node table itself instead of leaving the clear to the first
+ * launches of the level-1 scatter (sdt_clear_plan.h) -- for A/B runs and tests/test_fused_clear.py */
 static inline const char *sdt_size_env(const char *name)
 {
 	const char *v = sdt_tuning_env(name);

@@ -24,6 +24,7 @@ int sdt_gpu_index_contigs(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwo
 {
 	if (!c || !packed_words || !offsets || !ids)
 		return fail(SDT_EINVAL, "NULL argument");
+	SDT_ENTER(c);
 	if (!(c->flags & SDT_FLAG_CONTIG_INDEX))
 		return fail(SDT_ESTATE, "init with SDT_FLAG_CONTIG_INDEX to index contigs");
 	if (c->index_final)
@@ -41,7 +42,6 @@ int sdt_gpu_index_contigs(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwo
 	}
 	if (((offsets[ncontigs] + 15) >> 4) + TAIL_PAD > nwords)
 		return fail(SDT_EINVAL, "packed_words too short: need %llu words incl. %d pad words", (unsigned long long)(((offsets[ncontigs] + 15) >> 4) + TAIL_PAD), TAIL_PAD);
-	HIPCHK(hipSetDevice(c->device));
 	// contig ordinal -> id table grows by this batch
 	if (c->ctg_ord + ncontigs > c->ctg_ids_cap) {
 		const uint64_t cap = (c->ctg_ord + ncontigs) * 2 + 1024;
@@ -79,7 +79,7 @@ int sdt_gpu_set_contig_table(sdt_ctx *c, const uint32_t *length, const uint32_t 
 {
 	if (!c || !length || !twin)
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	HIPCHK(hipStreamSynchronize(c->stream));
 	if (c->d_ctg_len) HIPCHK(hipFree(c->d_ctg_len));
 	if (c->d_ctg_twin) HIPCHK(hipFree(c->d_ctg_twin));
@@ -144,11 +144,11 @@ int sdt_gpu_align_reads_device(sdt_ctx *c, const void *d_packed_words, const voi
 {
 	if (!c || !d_packed_words || !d_offsets || !d_read_info || !d_hits)
 		return fail(SDT_EINVAL, "NULL argument");
+	SDT_ENTER(c);
 	if (max_hits < nreads)
 		return fail(SDT_EINVAL, "hits[] must hold at least one entry per read (%llu < %llu)", (unsigned long long)max_hits, (unsigned long long)nreads);
 	if (!(c->flags & SDT_FLAG_CONTIG_INDEX))
 		return fail(SDT_ESTATE, "init with SDT_FLAG_CONTIG_INDEX");
-	HIPCHK(hipSetDevice(c->device));
 	int rc = launch_align(c, (const uint32_t *)d_packed_words, (const uint64_t *)d_offsets, nreads, max_read_len,
 	                      (const int32_t *)d_align_len, align_len_all, (uint64_t *)d_read_info, (Hit *)d_hits, max_hits);
 	if (rc != SDT_OK) return rc;
@@ -170,6 +170,7 @@ int sdt_gpu_align_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nword
 {
 	if (!c || !packed_words || !offsets || !read_info || (!hits && max_hits))
 		return fail(SDT_EINVAL, "NULL argument");
+	SDT_ENTER(c);
 	if (!(c->flags & SDT_FLAG_CONTIG_INDEX))
 		return fail(SDT_ESTATE, "init with SDT_FLAG_CONTIG_INDEX");
 	if (nreads == 0) { if (nhits) *nhits = 0; return SDT_OK; }
@@ -181,7 +182,6 @@ int sdt_gpu_align_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nword
 	}
 	if (((offsets[nreads] + 15) >> 4) + TAIL_PAD > nwords)
 		return fail(SDT_EINVAL, "packed_words too short: need %llu words incl. %d pad words", (unsigned long long)(((offsets[nreads] + 15) >> 4) + TAIL_PAD), TAIL_PAD);
-	HIPCHK(hipSetDevice(c->device));
 	int rc = ab_reserve(c, 0, nwords * sizeof(uint32_t));
 	if (rc == SDT_OK) rc = ab_reserve(c, 1, (nreads + 1) * sizeof(uint64_t));
 	if (rc == SDT_OK && align_len) rc = ab_reserve(c, 2, nreads * sizeof(int32_t));

@@ -73,7 +73,7 @@ int sdt_gpu_overlap_pairs_device(sdt_ctx *c, const void *d_packed_words, const v
 		return fail(SDT_EINVAL, "NULL argument");
 	int rc = args_ok(params, nreads);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	DevBuf ctr;
 	rc = ctr.get(sizeof(unsigned long long), "overlap counter");
 	if (rc != SDT_OK) return rc;
@@ -96,7 +96,7 @@ int sdt_gpu_overlap_pairs(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwo
 	StreamCheck in;
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	DevBuf ctr, d_r, d_k;
 	rc = ctr.get(sizeof(unsigned long long), "overlap counter");
 	if (rc != SDT_OK) return rc;
@@ -120,6 +120,7 @@ int sdt_gpu_overlap_kept_pairs(sdt_ctx *c, const sdt_overlap_params *params, con
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER(c);
 	if (nreads) *nreads = 0;
 	if (n_kept) *n_kept = 0;
 	int rc = args_ok(params, 0);
@@ -146,7 +147,6 @@ int sdt_gpu_overlap_kept_pairs(sdt_ctx *c, const sdt_overlap_params *params, con
 		return SDT_OK;
 	if (!ov)
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	std::vector<UnitStretch> segs(2 * n_ranges + 1);
 	uint64_t units = 0;

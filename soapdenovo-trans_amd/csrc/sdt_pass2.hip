@@ -40,6 +40,7 @@ int sdt_gpu_load_paths(sdt_ctx *c, const uint64_t *keys, const uint64_t *path_wo
 {
 	if (!c || (npatch && (!patch_keys || !patch_info)))
 		return fail(SDT_EINVAL, "NULL argument");
+	SDT_ENTER(c);
 	const bool by_index = keys == nullptr;
 	// keys == NULL and path_words == NULL: the path words sdt_gpu_build_edges left on the device
 	uint64_t *d_own = (!keys && !path_words && n) ? sdti::graph_take_path_words(c->gx, n) : nullptr;
@@ -49,7 +50,6 @@ int sdt_gpu_load_paths(sdt_ctx *c, const uint64_t *keys, const uint64_t *path_wo
 		if (d_own) (void)hipFree(d_own);
 		return fail(SDT_ESTATE, "keys == NULL needs the node index of sdt_gpu_set_node_index for the same %llu nodes", (unsigned long long)n);
 	}
-	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	search_cache_drop(c);                            // the counters make way for the path words
 	uint64_t *d_k = nullptr, *d_i = nullptr;
@@ -114,9 +114,9 @@ int sdt_gpu_export_paths(sdt_ctx *c, uint64_t *keys, uint64_t *path_words, uint6
 {
 	if (!c || !n)
 		return fail(SDT_EINVAL, "NULL argument");
+	SDT_ENTER(c);
 	if (!c->paths_loaded)
 		return fail(SDT_ESTATE, "call sdt_gpu_load_paths first");
-	HIPCHK(hipSetDevice(c->device));
 	int rc = sync_stats(c);
 	if (rc != SDT_OK) return rc;
 	const uint64_t nodes = c->h_stats->distinct;
@@ -159,7 +159,7 @@ int sdt_gpu_import_paths(sdt_ctx *c, const uint64_t *keys, const uint64_t *path_
 {
 	if (!c || (n && (!keys || !path_words)) || (npatch && (!patch_keys || !patch_info)))
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	int rc = sync_stats(c);
 	if (rc != SDT_OK) return rc;
 	search_cache_drop(c);
@@ -214,11 +214,11 @@ int sdt_gpu_map_reads(sdt_ctx *c, uint64_t *reads_processed, uint64_t *arcs)
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER(c);
 	if (!c->paths_loaded)
 		return fail(SDT_ESTATE, "call sdt_gpu_load_paths first");
 	if (!(c->flags & SDT_FLAG_KEEP_READS) && c->kept.empty())
 		return fail(SDT_ESTATE, "the reads were not kept: init with SDT_FLAG_KEEP_READS (or hand them over with sdt_gpu_keep_reads)");
-	HIPCHK(hipSetDevice(c->device));
 	for (int attempt = 0; attempt < 8; attempt++) {
 		// ArcEnt.first starts at ~0 (atomicMin), key/mult at 0
 		HIPCHK(hipMemsetAsync(c->d_arcs, 0, c->arc_slots * sizeof(ArcEnt), c->stream));
@@ -294,9 +294,9 @@ int sdt_gpu_export_arcs(sdt_ctx *c, uint32_t *from, uint32_t *to, uint32_t *mult
 {
 	if (!c || !from || !to || !mult || !first)
 		return fail(SDT_EINVAL, "NULL argument");
+	SDT_ENTER(c);
 	if (!c->d_arcs)
 		return fail(SDT_ESTATE, "no arcs: call sdt_gpu_map_reads first");
-	HIPCHK(hipSetDevice(c->device));
 	uint32_t *d_f = nullptr, *d_t = nullptr, *d_m = nullptr;
 	uint64_t *d_o = nullptr;
 	unsigned long long *d_cur = nullptr;
@@ -337,7 +337,7 @@ int sdt_gpu_keep_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwords
 		return fail(SDT_EINVAL, "NULL argument");
 	if (nreads == 0)
 		return SDT_OK;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	uint64_t maxlen = 0;
 	for (uint64_t i = 0; i < nreads; i++)
 		if (offsets[i + 1] - offsets[i] > maxlen) maxlen = offsets[i + 1] - offsets[i];

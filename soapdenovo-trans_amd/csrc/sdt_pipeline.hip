@@ -14,7 +14,7 @@ void sk_free(sdt_ctx *c)
 {
 	sdt_ctx::SkState &k = c->sk;
 	void *dev[] = {k.p1.recs, k.p1.meta, k.p1.next, k.p2.recs, k.p2.meta, k.p2.next, k.cursors, k.blk, k.cnt1, k.off1, k.fill1, k.list1,
-	               k.cnt2, k.off2, k.fill2, k.list2, k.kmers2, k.kpre2, k.items, k.citems, k.next_item};
+	               k.cnt2, k.off2, k.fill2, k.list2, k.kmers2, k.kpre2, k.items, k.citems, k.next_item, k.cut, k.cut_flag};
 	for (void *p : dev)
 		if (p) (void)hipFree(p);
 	void *host[] = {k.h_off1, k.h_off2, k.h_kpre2, k.h_items, k.h_citems};
@@ -168,6 +168,11 @@ int sk_alloc(sdt_ctx *c, uint64_t want_kmers, uint64_t per_read)
 	HIPCHK(hipMalloc((void **)&k.citems, (size_t)k.citems_cap * sizeof(uint4)));
 	HIPCHK(hipHostMalloc((void **)&k.h_citems, (size_t)k.citems_cap * sizeof(uint4), hipHostMallocDefault));
 	HIPCHK(hipMalloc((void **)&k.next_item, SK_MAX_COUNT_LAUNCHES * sizeof(uint32_t)));
+	// the fused scatter's note of the reads it cut short: 2 bytes per read of the largest launch these pools take at this read length
+	// (a launch of more reads -- shorter ones, later -- does not fuse: sk_scatter_launch)
+	k.cut_cap = cap / (per_read ? per_read : 1) + SK_SEQ_TILE;
+	HIPCHK(hipMalloc((void **)&k.cut, (size_t)k.cut_cap * sizeof(uint16_t)));
+	HIPCHK(hipMalloc((void **)&k.cut_flag, 64));
 	k.cap_kmers = cap;
 	k.ready = true;
 	if (sdt_env("SDT_TIMING"))
@@ -259,6 +264,7 @@ int sk_split(sdt_ctx *c, const SkPool &src, const uint32_t *list, uint32_t nitem
 int sk_count_all(sdt_ctx *c)
 {
 	sdt_ctx::SkState &k = c->sk;
+	{ const int rcs = settle_clear(c); if (rcs != SDT_OK) return rcs; }       // what the scatter launches left of the clear debt: the merges need the table
 	SK_CHK(hipStreamSynchronize(c->stream));
 	k.st_chunks2 = k.h_off2[SK_NBF];
 	k.st_flushes++;
@@ -422,6 +428,35 @@ int sk_scatter_launch(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_off
 	const int ncap_strips = compact1 ? ncap : sk_pow2_floor(ncap);
 	const uint64_t ntiles = (nr + SK_TILE_READS - 1) / SK_TILE_READS;
 	const unsigned grid = (unsigned)(ntiles < k.wgs ? ntiles : k.wgs);
+	// one lane per read where the window length has an instantiation and the run list can hold a read
+	const int w = c->K - m + 1;
+	static const bool no_seq = sdt_tuning_env("SDT_SK_STRIPS") != NULL;          // A/B switch (tools/, DESIGN.md section 4)
+	// (instantiated: every odd window of 1-word keys with K >= 17 and of 2-word keys, i.e. every odd K from 17 to 63)
+	const bool seq1 = c->nw == 1 && (w & 1) && w >= 9 && w <= 21 && per_read <= (uint64_t)SK_SEQ_MAX_KMERS;
+	const bool seq2 = c->nw == 2 && (w & 1) && w >= 23 && w <= 53 && per_read <= (uint64_t)SK_SEQ_MAX_KMERS;
+	// The table's clear debt rides on this launch where it can (sdt_clear_plan.h): the one-lane-per-read kernel of a context that owns
+	// its whole table.  Everybody else -- the strip kernel, the sharded callers -- settles it first.  The range a fused launch covers
+	// leaves the debt when the launch is enqueued: whatever comes later on the stream is ordered behind it.
+	SkFuse fuse = {SK_FUSE_PLAIN, {0, 0, 0}, {nullptr, nullptr, nullptr}};
+	if ((seq1 || seq2) && !no_seq && allow_direct && c->clear_lo < c->clear_hi && nr <= k.cut_cap) {
+		const uint64_t per_slot = entry_bytes(c->nw) + 4 + (c->d_first ? 8 : 0);
+		const ClearPlan cp = plan_clear(c->clear_lo, c->clear_hi, (nr + SK_SEQ_TILE - 1) / SK_SEQ_TILE, CLEAR_UNIT_SLOTS, clear_cap_units(per_slot));
+		if (cp.hi > cp.lo) {
+			fuse.mode = SK_FUSE_FUSED;
+			fuse.clear.unit0 = cp.lo / CLEAR_UNIT_SLOTS;
+			fuse.clear.unit_end = cp.hi / CLEAR_UNIT_SLOTS;
+			fuse.clear.per_tile = cp.units_per_tile;
+			fuse.redo.cut = k.cut;
+			fuse.redo.flag = k.cut_flag;
+			fuse.redo.done = &c->d_stats->clear_void;
+			HIPCHK(hipMemsetAsync(k.cut_flag, 0, 4, c->stream));
+		}
+	}
+	if (fuse.mode == SK_FUSE_PLAIN) {
+		const int rcs = settle_clear(c);
+		if (rcs != SDT_OK)
+			return rcs;
+	}
 	EventPair *ev = next_event(c);
 	if (!ev)
 		return fail(SDT_EHIP, "hipEventCreate failed");
@@ -434,12 +469,6 @@ int sk_scatter_launch(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_off
 		hipLaunchKernelGGL((k_sk_scatter_reads<NW, C1>), dim3(grid), dim3(TPB), geo.smem, c->stream, d_words, d_offs, nr, c->K, m, ncap_strips, \
 		                   geo.mtw, geo.tile_words, geo.hv_words, geo.hv2_words, geo.bits_words, k.p1, k.cursors, k.blk, k.cnt1, sk_tbl<NW>(c, allow_direct), c->d_stats, ob, c->ord_stride); \
 	} while (0)
-	// one lane per read where the window length has an instantiation and the run list can hold a read
-	const int w = c->K - m + 1;
-	static const bool no_seq = sdt_tuning_env("SDT_SK_STRIPS") != NULL;          // A/B switch (tools/, DESIGN.md section 4)
-	// (instantiated: every odd window of 1-word keys with K >= 17 and of 2-word keys, i.e. every odd K from 17 to 63)
-	const bool seq1 = c->nw == 1 && (w & 1) && w >= 9 && w <= 21 && per_read <= (uint64_t)SK_SEQ_MAX_KMERS;
-	const bool seq2 = c->nw == 2 && (w & 1) && w >= 23 && w <= 53 && per_read <= (uint64_t)SK_SEQ_MAX_KMERS;
 	if ((seq1 || seq2) && !no_seq) {
 		SkSeqLaunch a;
 		a.words = d_words; a.offs = d_offs; a.nreads = nr; a.K = c->K; a.m = m; a.ncap = ncap;
@@ -447,8 +476,27 @@ int sk_scatter_launch(sdt_ctx *c, const uint32_t *d_words, const uint64_t *d_off
 		a.pool = k.p1; a.cursors = k.cursors; a.blk = k.blk; a.cnt = k.cnt1; a.stats = c->d_stats;
 		a.ord_base = ob; a.ord_stride = c->ord_stride; a.max_wgs = k.wgs; a.cu_count = c->cu_count; a.stream = c->stream;
 		a.compact1 = compact1;
-		HIPCHK(seq1 ? sk_seq_launch_nw1(w, a, sk_tbl<1>(c, allow_direct)) : (w <= 33 ? sk_seq_launch_nw2_lo(w, a, sk_tbl<2>(c, allow_direct))
-		            : (w <= 43 ? sk_seq_launch_nw2_mid(w, a, sk_tbl<2>(c, allow_direct)) : sk_seq_launch_nw2_hi(w, a, sk_tbl<2>(c, allow_direct)))));
+		a.fuse = fuse;
+		auto launch = [&]() -> hipError_t {
+			return seq1 ? sk_seq_launch_nw1(w, a, sk_tbl<1>(c, allow_direct)) : (w <= 33 ? sk_seq_launch_nw2_lo(w, a, sk_tbl<2>(c, allow_direct))
+			            : (w <= 43 ? sk_seq_launch_nw2_mid(w, a, sk_tbl<2>(c, allow_direct)) : sk_seq_launch_nw2_hi(w, a, sk_tbl<2>(c, allow_direct))));
+		};
+		HIPCHK(launch());
+		if (fuse.mode == SK_FUSE_FUSED) {
+			c->clear_lo = fuse.clear.unit_end * CLEAR_UNIT_SLOTS;
+			if (c->clear_lo >= c->clear_hi)
+				c->clear_lo = c->clear_hi = 0;
+			// The reads it cut short for want of a chunk (none, as a rule: the workgroups look at the flag and return) take the direct
+			// path behind it, and that path may probe any slot: where the launch leaves debt (the cap, a ragged end) a k_clear that runs
+			// only if the flag is up clears the rest first.  The host does not learn which way it went and goes on carrying the debt; the
+			// replay says so on the device (Stats.clear_void), and every later payment looks there before it stores.
+			if (c->clear_lo < c->clear_hi) {
+				const int rcc = launch_clear(c, c->d_ent, c->d_aux, c->d_first, c->clear_hi, c->clear_lo, k.cut_flag, &c->d_stats->clear_void);
+				if (rcc != SDT_OK) return rcc;
+			}
+			a.fuse.mode = SK_FUSE_REPLAY;
+			HIPCHK(launch());
+		}
 	} else if (c->nw == 1 && compact1) SK_SCATTER(1, true);
 	else if (c->nw == 1) SK_SCATTER(1, false);
 	else if (c->nw == 2) SK_SCATTER(2, false);
@@ -574,7 +622,7 @@ int sdt_kmer_final_bucket(const uint64_t *key_words_msw_first, int K)
 extern "C" int sdt_gpu_debug_l2_log(sdt_ctx *c, void *d_buf, uint64_t cap)
 {
 	unsigned long long *p = (unsigned long long *)d_buf, cp = cap;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_l2_log), &p, sizeof p));
 	HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_l2_log_cap), &cp, sizeof cp));
 	return SDT_OK;

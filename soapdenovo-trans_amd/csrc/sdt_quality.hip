@@ -71,7 +71,7 @@ int sdt_gpu_quality_reads_device(sdt_ctx *c, const void *d_quals, const void *d_
 		return fail(SDT_EINVAL, "d_quals = %p: it must be 4-byte aligned", d_quals);
 	int rc = args_ok(params);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	DevBuf ctr;
 	rc = ctr.get(sizeof(unsigned long long), "quality counter");
 	if (rc != SDT_OK) return rc;
@@ -93,7 +93,7 @@ int sdt_gpu_quality_reads(sdt_ctx *c, const uint8_t *quals, uint64_t nbytes, con
 	StreamCheck in;
 	rc = byte_stream_args_ok(offsets, nreads, nbytes, &in);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	DevBuf ctr, d_r, d_k;
 	rc = ctr.get(sizeof(unsigned long long), "quality counter");
 	if (rc != SDT_OK) return rc;

@@ -95,7 +95,7 @@ int sdt_gpu_screen_load(sdt_ctx *c, const uint32_t *packed_words, uint64_t nword
 			return fail(SDT_EINVAL, "SDT_SCREEN_SLOTS = %s: a power of two above the %llu k-mer positions of the set", v, (unsigned long long)positions);
 		slots = forced;
 	}
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	// the staged sequences go when this returns; the table stays, and replaces the previous one only once it is complete
 	DevBuf d_w, d_o, d_r, d_n, tab;
 	rc = d_w.get(in.need_words * sizeof(uint32_t), "screen staging");
@@ -131,9 +131,9 @@ int sdt_gpu_screen_unload(sdt_ctx *c)
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER(c);
 	if (!c->screen.tab)
 		return SDT_OK;
-	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	(void)hipFree(c->screen.tab);
 	c->screen = sdt_ctx::ScreenSet();
@@ -161,7 +161,7 @@ int sdt_gpu_screen_lookup(sdt_ctx *c, const uint64_t *keys, uint64_t n, uint32_t
 		return fail(SDT_EINVAL, "NULL argument");
 	int rc = set_ready(c, "sdt_gpu_screen_lookup");
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	const uint64_t piece = chunk_items(PROFILE_CHUNK_READS);
 	DevBuf d_k, d_r;
 	rc = d_k.get((n < piece ? n : piece) * sizeof(uint64_t), "screen keys");
@@ -191,7 +191,7 @@ int sdt_gpu_screen_reads_device(sdt_ctx *c, const void *d_packed_words, const vo
 	int rc = args_ok(params, nreads, paired);
 	if (rc == SDT_OK) rc = set_ready(c, "sdt_gpu_screen_reads_device");
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	DevBuf ctr;
 	rc = ctr.get(sizeof(unsigned long long), "screen counter");
 	if (rc != SDT_OK) return rc;
@@ -215,7 +215,7 @@ int sdt_gpu_screen_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwor
 	StreamCheck in;
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	DevBuf ctr, d_r, d_k;
 	rc = ctr.get(sizeof(unsigned long long), "screen counter");
 	if (rc != SDT_OK) return rc;
@@ -239,6 +239,7 @@ int sdt_gpu_screen_kept_reads(sdt_ctx *c, const sdt_screen_params *params, const
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER(c);
 	if (nreads) *nreads = 0;
 	if (n_kept) *n_kept = 0;
 	int rc = args_ok(params, 0, 0);
@@ -266,7 +267,6 @@ int sdt_gpu_screen_kept_reads(sdt_ctx *c, const sdt_screen_params *params, const
 		return SDT_OK;
 	if (!out)
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	// batch by batch: what every read has on its own, dense on the device, scattered to the ordinals of a copy on the host; mates sit
 	// in different batches, so the unit verdicts are taken there (sdt_read_plan.h) before anything of out[] is written

@@ -122,7 +122,7 @@ int sdt_gpu_search_kmers_device(sdt_ctx *c, const void *d_keys, uint64_t n, void
 		return fail(SDT_EINVAL, "NULL argument");
 	int rc = search_ready(c, "sdt_gpu_search_kmers");
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	return launch_search(c, (const uint64_t *)d_keys, n, (uint32_t *)d_count, (uint32_t *)d_l_links, (uint32_t *)d_r_flags, (uint8_t *)d_status);
 }
 
@@ -136,7 +136,7 @@ int sdt_gpu_search_kmers(sdt_ctx *c, const uint64_t *keys, uint64_t n, uint32_t 
 		return fail(SDT_EINVAL, "NULL argument");
 	int rc = search_ready(c, "sdt_gpu_search_kmers");
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	// in pieces through the arena: keys + 13 bytes of answers per query
 	const uint64_t piece = chunk_items(SEARCH_CHUNK), m = n < piece ? n : piece;
 	DevBuf d_k, d_c, d_l, d_r, d_s;
@@ -171,7 +171,7 @@ int sdt_gpu_profile_reads_device(sdt_ctx *c, const void *d_packed_words, const v
 		return fail(SDT_EINVAL, "NULL argument");
 	int rc = search_ready(c, "sdt_gpu_profile_reads");
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	return profile_device(c, (const uint32_t *)d_packed_words, (const uint64_t *)d_offsets, nreads, max_read_len, min_count, (ReadCov *)d_out);
 }
 
@@ -191,7 +191,7 @@ int sdt_gpu_profile_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwo
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc == SDT_OK) rc = strip_plan(c, nreads, in.longest, &geo);      // (the whole call is refused before a piece's records are written)
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	DevBuf d_r;
 	return for_each_piece(c, packed_words, offsets, nreads, 1, "profile staging", [&](const StagedPiece &p) -> int {
 		int rc = d_r.reserve(p.nr * sizeof(ReadCov), "profile staging");
@@ -216,7 +216,7 @@ int sdt_gpu_profile_kept_reads(sdt_ctx *c, uint32_t min_count, sdt_read_cov *out
 		return SDT_OK;
 	if (!out)
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	// batch by batch: dense records on the device, scattered to their ordinals on the host
 	DevBuf d_r;

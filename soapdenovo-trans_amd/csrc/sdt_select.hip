@@ -83,7 +83,7 @@ int sdt_gpu_select_reads_device(sdt_ctx *c, const void *d_packed_words, const vo
 	if (rc != SDT_OK) return rc;
 	rc = search_ready(c, "sdt_gpu_select_reads");
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	return select_device(c, (const uint32_t *)d_packed_words, (const uint64_t *)d_offsets, nreads, max_read_len, paired, params,
 	                     (ReadPick *)d_pick, (uint8_t *)d_keep, 0, n_kept);
 }
@@ -107,7 +107,7 @@ int sdt_gpu_select_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwor
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc == SDT_OK) rc = strip_plan(c, nreads, in.longest, &geo);      // (the whole call is refused before a piece's records are written)
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	// a piece of a paired batch holds whole pairs, and a unit's id in the draw is the index of its first read in the whole batch
 	DevBuf d_r, d_k;
 	uint64_t kept = 0;
@@ -153,7 +153,7 @@ int sdt_gpu_select_kept_reads(sdt_ctx *c, const sdt_norm_params *params, const u
 		return SDT_OK;
 	if (!pick)
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	// the unit list, as stretches: single reads up to a range, the pairs of the range, and so on up to the last ordinal a read has
 	// (npick may cut a pair: its first mate is a unit, the kernel finds no second)
@@ -204,7 +204,7 @@ int sdt_gpu_compact_reads_device(sdt_ctx *c, const void *d_packed_words, const v
 	if (n_out_words) *n_out_words = 0;
 	if (!d_out_words || !d_out_offsets || (nreads && (!d_packed_words || !d_offsets || !d_keep)))
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	return compact_device(c, (const uint32_t *)d_packed_words, (const uint64_t *)d_offsets, nreads, (const uint8_t *)d_keep,
 	                      (uint32_t *)d_out_words, out_words_cap, (uint64_t *)d_out_offsets, n_out_reads, n_out_words);
 }
@@ -215,6 +215,7 @@ int sdt_gpu_compact_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwo
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER(c);
 	if (n_out_reads) *n_out_reads = 0;
 	if (n_out_words) *n_out_words = 0;
 	if (!out_words || !out_offsets || (nreads && (!packed_words || !offsets || !keep)))

@@ -226,9 +226,9 @@ int sdt_gpu_comm_init(sdt_ctx *c, const sdt_comm_id *id, int rank, int nranks)
 {
 	if (!c || !id || nranks < 1 || nranks > 64 || rank < 0 || rank >= nranks)
 		return fail(SDT_EINVAL, "bad argument (1..64 ranks)");
+	SDT_ENTER(c);
 	if (c->comm.kind)
 		return fail(SDT_ESTATE, "the context already has a communicator");
-	HIPCHK(hipSetDevice(c->device));
 	return c->comm.open_rccl((const NcclId *)id, rank, nranks);
 }
 
@@ -236,9 +236,9 @@ int sdt_gpu_comm_init_shm(sdt_ctx *c, const char *name, int rank, int nranks)
 {
 	if (!c || !name || nranks < 1 || nranks > 64 || rank < 0 || rank >= nranks)
 		return fail(SDT_EINVAL, "bad argument (1..64 ranks)");
+	SDT_ENTER(c);
 	if (c->comm.kind)
 		return fail(SDT_ESTATE, "the context already has a communicator");
-	HIPCHK(hipSetDevice(c->device));
 	return c->comm.open_shm(name, rank, nranks, true);
 }
 
@@ -271,7 +271,7 @@ int sdt_gpu_allreduce_i64(sdt_ctx *c, int64_t *vals, int n)
 {
 	if (!c || !vals || n < 0 || (size_t)n * sizeof(int64_t) > SHM_CTRL_BYTES)
 		return fail(SDT_EINVAL, "bad argument");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	return c->comm.allreduce_sum_host(vals, n);
 }
 
@@ -279,7 +279,7 @@ int sdt_gpu_comm_stats(sdt_ctx *c, uint64_t *bytes_sent, uint64_t *bytes_recv, d
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	if (c->comm.xstream)
 		HIPCHK(hipStreamSynchronize(c->comm.xstream));
 	c->comm.harvest_time();
@@ -343,12 +343,12 @@ int sdt_gpu_count_reads_sharded(sdt_ctx *c, const void *d_packed_words, uint64_t
 	(void)nwords;
 	if (!c || (nreads && (!d_packed_words || !d_offsets)))
 		return fail(SDT_EINVAL, "NULL argument");
+	SDT_ENTER(c);
 	if (c->comm.kind == 0 || c->comm.nranks == 1) {
 		if (nreads == 0)
 			return SDT_OK;
 		return sdt_gpu_count_reads_device(c, d_packed_words, nwords, d_offsets, nreads, max_read_len);
 	}
-	HIPCHK(hipSetDevice(c->device));
 	{ const int rcd = drain_pushes(c, true); if (rcd != SDT_OK) return rcd; }
 	Comm &cm = c->comm;
 	sdt_ctx::SkState &k = c->sk;
@@ -437,7 +437,7 @@ int sdt_gpu_push_reads_sharded(sdt_ctx *c, const uint32_t *packed_words, uint64_
 {
 	if (!c || (nreads && (!packed_words || !offsets)))
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	uint64_t maxlen = 0;
 	for (uint64_t i = 0; i < nreads; i++) {
 		if (offsets[i + 1] < offsets[i])

@@ -7,6 +7,7 @@
 #include "sdt_kmer.cuh"
 #include "sdt_table.cuh"
 #include "sdt_superkmer.cuh"
+#include "sdt_clear_plan.h"
 
 using namespace sdt;
 
@@ -225,6 +226,59 @@ constexpr int SK_SEQ_RUNCAP = 24;                // runs per read the list holds
 constexpr int SK_SEQ_MAX_KMERS = 256;            // k-mers per read (the list entry has 8 bits for the position, 6 for n - 1)
 
 
+// ---- the node table's clear, carried by the scatter (sdt_clear_plan.h) ----
+// sdt_gpu_reset leaves the table's clear as a debt; the first scatter launches behind it pay it off: k_clear only stores and this
+// kernel only computes (94 % VALU issue, a fifth of HBM), and the two cannot share the chip as two kernels.
+//   plain   the kernel as it was
+//   fused   every tile first stores the clear pattern over its share of the debt -- 16-byte stores with no wait behind them (vmcnt counts
+//           stores on gfx9: the wait of the NEXT tile's load covers them, a whole walk later; profiles/fused_clear has the ISA).  The table is not clear
+//           yet, so a run that finds no chunk cannot take the direct path: the lane stops emitting for that read, raises the flag and
+//           leaves in cut[read] how many emissions it had made (SK_CUT_NONE: all of them)
+//   replay  enqueued behind every fused launch over the same reads, when the clear is complete by stream order: returns at once unless
+//           the flag is up (one near-empty launch per reset); otherwise walks the reads that were cut short again and sends every
+//           emission from cut[read] on through table_put.  Reserves nothing, clears nothing.  table_put may probe any slot, so where the
+//           fused launch left debt the host puts a k_clear in between that runs only if the flag is up; the host does not learn of
+//           it, so the replay notes in Stats.clear_void that the whole table has been cleared and is in use, and every later payment
+//           of the debt -- a fused launch's stores, settle_clear's k_clear -- looks there first and stores nothing.
+// A lane's emissions are numbered in the order it makes them: the on-the-spot runs past SK_SEQ_RUNCAP first, then the listed runs.
+enum : uint32_t { SK_FUSE_PLAIN = 0, SK_FUSE_FUSED = 1, SK_FUSE_REPLAY = 2 };
+constexpr uint32_t SK_CUT_NONE = 0xFFFFu;
+struct SkFuse {
+	uint32_t mode;
+	struct { uint64_t unit0, unit_end; uint32_t per_tile; } clear;       // tile t: units [unit0 + t * per_tile, + per_tile), clipped at unit_end
+	struct { uint16_t *cut; uint32_t *flag; unsigned long long *done; } redo;      // cut[read of the launch]; one flag word; Stats.clear_void
+};
+
+// 16-byte stores of the clear: plain ones.  They keep the line in the XCD's L2, where the workgroups' open level-1 chunks live; stores
+// that write through and drop it (sc1) were measured against them on the 200 M-read workload and were slower (profiles/fused_clear).
+typedef uint32_t sk_u4 __attribute__((ext_vector_type(4)));
+
+// the pattern k_clear writes -- key words KEY_EMPTY, val 0, aux 0, first ORD_NONE -- over this tile's units, coalesced across the workgroup
+template <int NW> __device__ inline void sk_clear_tile(const Table<NW> &tbl, const SkFuse &fz, uint64_t tile, uint32_t tid, uint32_t lanes)
+{
+	static_assert(NW == 1 || NW == 2, "16-byte pieces of Entry<1> and Entry<2>");
+	const uint64_t u0 = fz.clear.unit0 + tile * fz.clear.per_tile;
+	if (u0 >= fz.clear.unit_end)
+		return;
+	const uint64_t left = fz.clear.unit_end - u0;
+	const uint32_t ns = (uint32_t)(left < fz.clear.per_tile ? left : fz.clear.per_tile) * CLEAR_UNIT_SLOTS;
+	const uint64_t s0 = u0 * CLEAR_UNIT_SLOTS;
+	constexpr uint32_t EP = sizeof(Entry<NW>) / 16;      // 16-byte pieces of an entry: {key, val} / {key, key} {val, pad}
+	const sk_u4 empty = {0xFFFFFFFFu, 0xFFFFFFFFu, NW == 1 ? 0u : 0xFFFFFFFFu, NW == 1 ? 0u : 0xFFFFFFFFu}, zero = {0u, 0u, 0u, 0u};
+	const sk_u4 none = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+	sk_u4 *e = reinterpret_cast<sk_u4 *>(tbl.ent + s0);
+	for (uint32_t i = tid; i < ns * EP; i += lanes)
+		e[i] = (NW == 2 && (i & 1u)) ? zero : empty;
+	sk_u4 *a = reinterpret_cast<sk_u4 *>(tbl.aux + s0);
+	for (uint32_t i = tid; i < ns / 4; i += lanes)
+		a[i] = zero;
+	if (tbl.first) {
+		sk_u4 *f = reinterpret_cast<sk_u4 *>(tbl.first + s0);
+		for (uint32_t i = tid; i < ns / 2; i += lanes)
+			f[i] = none;
+	}
+}
+
 // a level-1 record into its slot: C1 (1-word keys without ordinals) the 16-byte compact form of sdt_sk_record1.h in ONE 16-byte store
 // (the slots of a chunk are 16-byte aligned: the read ordinal and the position of rec[0] are dropped), otherwise the record as it is
 template <int NW, bool C1> __device__ inline void sk_store_record1(uint64_t *recs, uint32_t chunk, uint32_t pos, const uint64_t (&rec)[SkFmt<NW>::REC_WORDS])
@@ -244,13 +298,27 @@ template <int NW, bool C1 = false>
 __device__ inline void sk_emit_run(const uint32_t *words, int rb_r, int len_r, int nk_r, int K, uint64_t read_ord, int j0, int n,
                                    uint32_t fb, unsigned long long *s_cur, unsigned long long *s_blk, const SkPool &pool,
                                    uint32_t *s_cnt, const Table<NW> &tbl, uint32_t &claimed, uint32_t &failed, uint32_t &done,
-                                   uint32_t &emitted)
+                                   uint32_t &emitted, const SkFuse &fz, uint32_t &emis, uint32_t &cutv)
 {
 	constexpr int BW = SkFmt<NW>::BW, RW = SkFmt<NW>::REC_WORDS;
 	const int hp = j0 > 0, hn = j0 + n < nk_r;
 	const uint32_t l1 = fb >> SK_L2BITS, l2 = fb & (SK_NB2 - 1);
 	uint32_t chunk, pos;
-	if (sk_reserve(s_cur, s_blk, l1, l1, SK_CAP1, pool, s_cnt, chunk, pos)) {
+	if (fz.mode == SK_FUSE_REPLAY) {
+		// the emissions the fused launch made are in the pool; the others take the direct path now that the table is clear
+		if (emis++ >= cutv) {
+			for (int jj = j0; jj < j0 + n; jj++) {
+				uint32_t prev, next;
+				const Key<NW> key = chop_record<NW>(words, rb_r, len_r, jj, K, prev, next);
+				const uint64_t ord = tbl.first ? (read_ord << 16) | (uint64_t)jj : ORD_NONE;
+				if (!table_put<NW>(tbl, key, prev, next, claimed, ord))
+					failed++;
+				done++;
+			}
+		}
+	} else if (fz.mode == SK_FUSE_FUSED && cutv != SK_CUT_NONE) {
+		// (this read was cut short: the replay launch takes the rest)
+	} else if (sk_reserve(s_cur, s_blk, l1, l1, SK_CAP1, pool, s_cnt, chunk, pos)) {
 		const int len = hp + n + K - 1 + hn, ps = rb_r + j0 - hp;
 		uint64_t rec[RW];
 		rec[0] = C1 ? sk_rec1c_hdr(l2, n, hp, hn, SK_L2BITS) : sk_header(read_ord, (uint32_t)j0, l2, n, hp, hn);
@@ -267,6 +335,11 @@ __device__ inline void sk_emit_run(const uint32_t *words, int rb_r, int len_r, i
 		}
 		sk_store_record1<NW, C1>(pool.recs, chunk, pos, rec);
 		emitted += (uint32_t)n;
+		emis++;
+	} else if (fz.mode == SK_FUSE_FUSED) {
+		// no chunk left and the table not clear yet: the read is cut here (see SkFuse)
+		cutv = emis;
+		*fz.redo.flag = 1u;
 	} else if (!tbl.ent) {
 		// no chunk left and no table to fall back on (a sharded context: this rank does not own every key; the caller gets SDT_EFULL)
 		failed += (uint32_t)n;
@@ -289,9 +362,17 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
                                                                       uint64_t nreads, int K, int m, int ncap, int max_tile_words, SkPool pool,
                                                                       unsigned long long *__restrict__ g_cursors, unsigned long long *__restrict__ g_blk,
                                                                       uint32_t *__restrict__ g_cnt, Table<NW> tbl, Stats *stats,
-                                                                      uint64_t ord_base, uint64_t ord_stride)
+                                                                      uint64_t ord_base, uint64_t ord_stride, SkFuse fz)
 {
 	constexpr int TR = SK_SEQ_TILE;
+	const bool replay = fz.mode == SK_FUSE_REPLAY;
+	if (replay) {
+		if (*fz.redo.flag == 0)
+			return;                                  // no read of the fused launch was cut short
+		if (blockIdx.x == 0 && threadIdx.x == 0)
+			*fz.redo.done = 1ULL;
+	}
+	const bool clearing = fz.mode == SK_FUSE_FUSED && *fz.redo.done == 0;
 	extern __shared__ uint32_t smem[];
 	unsigned long long *s_cur = (unsigned long long *)smem;                               // SK_NB1
 	uint32_t *s_rb = (uint32_t *)(s_cur + SK_NB1);                                        // TR + 2
@@ -300,11 +381,11 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 	__shared__ unsigned long long s_blk;
 	__shared__ uint32_t s_cnt[SK_NB1];               // chunks opened per bucket (see k_sk_scatter_reads)
 	const int tid = threadIdx.x;
-	for (int i = tid; i < SK_NB1; i += TR) {
+	for (int i = tid; i < SK_NB1 && !replay; i += TR) {
 		s_cur[i] = g_cursors[(size_t)blockIdx.x * SK_NB1 + i];
 		s_cnt[i] = 0;
 	}
-	if (tid == 0)
+	if (tid == 0 && !replay)
 		s_blk = g_blk[blockIdx.x];
 	const uint64_t ntiles = (nreads + TR - 1) / TR;
 	const uint32_t mmask = (1u << (2 * m)) - 1u;
@@ -323,6 +404,8 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 		int nwords = (int)(((offs[r0 + nr] + 15) >> 4) - word0) + TAIL_PAD;
 		if (nwords > max_tile_words)
 			nwords = max_tile_words;                     // cannot happen when max_read_len was honoured
+		// (replay only; loaded in front of the tile's loads so that THEIR wait covers it: behind the clear it would put a wait on the stores)
+		uint32_t emis = 0, cutv = replay && tid < nr ? (uint32_t)fz.redo.cut[r0 + tid] : SK_CUT_NONE;
 		s_rb[tid] = (uint32_t)(offs[r0 + (tid < nr ? tid : nr)] - (word0 << 4));
 		if (tid == 0)
 			s_rb[TR] = (uint32_t)(offs[r0 + nr] - (word0 << 4));
@@ -331,11 +414,13 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 		for (int i = tid; i < nwords; i += TR)
 			s_words[LDS_LEAD + i] = packed[word0 + i];
 		__syncthreads();
+		if (clearing)
+			sk_clear_tile<NW>(tbl, fz, tile, (uint32_t)tid, (uint32_t)TR);
 		SK_TICK(0);
 		const uint32_t *words = s_words + LDS_LEAD;
 		const int rb_r = (int)s_rb[tid];
 		const int len_r = tid < nr ? (int)s_rb[tid + 1] - rb_r : 0;
-		const int nk_r = len_r >= K + 1 ? len_r - K + 1 : 0;                // prlHashReads.c:592
+		const int nk_r = len_r >= K + 1 && !(replay && cutv == SK_CUT_NONE) ? len_r - K + 1 : 0;                // prlHashReads.c:592
 		const uint64_t read_ord = ord_base + (r0 + (uint64_t)tid) * ord_stride;
 		uint32_t *runs = s_runs + tid * SK_SEQ_RUNCAP;
 		int nrun = 0;
@@ -364,7 +449,7 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 					if (nrun < SK_SEQ_RUNCAP)
 						runs[nrun] = (fb0 << 6) | (uint32_t)(j - j0 - 1);
 					else
-						sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, j0, j - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted);
+						sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, j0, j - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted, fz, emis, cutv);
 					nrun++;
 					j0 = j;
 					fb0 = fb;
@@ -402,7 +487,7 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 			if (nrun < SK_SEQ_RUNCAP)
 				runs[nrun] = (fb0 << 6) | (uint32_t)(nk_r - j0 - 1);
 			else
-				sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, j0, nk_r - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted);
+				sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, j0, nk_r - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted, fz, emis, cutv);
 			nrun++;
 		}
 		SK_TICK(1);
@@ -410,20 +495,23 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 		for (int k = 0, jr = 0; k < nlist; k++) {        // (the listed runs are the read's first ones, back to back from k-mer 0)
 			const uint32_t e = runs[k];
 			const int nr = (int)(e & 63u) + 1;
-			sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, jr, nr, e >> 6, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted);
+			sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, jr, nr, e >> 6, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted, fz, emis, cutv);
 			jr += nr;
 		}
+		if (fz.mode == SK_FUSE_FUSED && tid < nr)
+			fz.redo.cut[r0 + tid] = (uint16_t)cutv;
 		__syncthreads();                             // the tile buffers are reused
 		SK_TICK(3);
 	}
 #undef SK_TICK
-	for (int i = tid; i < SK_NB1; i += TR) {
+	for (int i = tid; i < SK_NB1 && !replay; i += TR) {
 		g_cursors[(size_t)blockIdx.x * SK_NB1 + i] = s_cur[i];
 		if (s_cnt[i])
 			atomicAdd(&g_cnt[i], s_cnt[i]);
 	}
 	if (tid == 0) {
-		g_blk[blockIdx.x] = s_blk;
+		if (!replay)
+			g_blk[blockIdx.x] = s_blk;
 #ifdef SDT_SK_TICKS
 		for (int i = 0; i < 4; i++)
 			atomicAdd(&stats->sk_cyc1[i], cyc[i]);
@@ -458,6 +546,7 @@ struct SkSeqLaunch {
 	int cu_count;
 	hipStream_t stream;
 	bool compact1;             // 1-word keys: 16-byte level-1 records (sdt_sk_record1.h)
+	SkFuse fuse;               // plain, or the table's clear fused in / the replay launch behind such a launch
 };
 
 template <int NW, int W, bool C1 = false> inline hipError_t sk_seq_launch_one(const SkSeqLaunch &a, const Table<NW> &tbl)
@@ -473,7 +562,7 @@ template <int NW, int W, bool C1 = false> inline hipError_t sk_seq_launch_one(co
 	const uint64_t nt = (a.nreads + SK_SEQ_TILE - 1) / SK_SEQ_TILE;
 	const unsigned grid = (unsigned)(nt < res ? nt : res);
 	hipLaunchKernelGGL((k_sk_scatter_reads_seq<NW, W, C1>), dim3(grid), dim3(SK_SEQ_TILE), smem, a.stream, a.words, a.offs, a.nreads, a.K, a.m, a.ncap,
-	                   a.mtw, a.pool, a.cursors, a.blk, a.cnt, tbl, a.stats, a.ord_base, a.ord_stride);
+	                   a.mtw, a.pool, a.cursors, a.blk, a.cnt, tbl, a.stats, a.ord_base, a.ord_stride, a.fuse);
 	return hipGetLastError();
 }
 

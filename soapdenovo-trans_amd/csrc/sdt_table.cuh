@@ -125,6 +125,8 @@ struct Stats {             // device counters, one cache line each would be nice
 	unsigned long long sk_distinct_kmers; // k-mers of the distinct records
 	unsigned long long sk_cyc1[4]; // k_sk_scatter_reads, thread 0 of every workgroup: clock ticks in tile staging / window minima / run starts / emission
 	unsigned long long sk_cyc[4];  // k_sk_count, wave 0 of every workgroup: clock ticks in set-up / tile fill + scan / counting / merging
+	unsigned long long clear_void; // != 0: the device has settled the whole clear debt of the last reset itself (a replay launch of the level-1
+	                               // scatter needed the table) -- whatever the host still pays of it is skipped on the device (k_clear, SkFuse)
 };
 
 __device__ inline uint64_t ld_relaxed(const uint64_t *p)

@@ -42,10 +42,15 @@ __global__ __launch_bounds__(TPB) void k_count_reads(const uint32_t *__restrict_
 	}
 }
 
-template <int NW> __global__ __launch_bounds__(TPB) void k_clear(Table<NW> tbl)
+// slots [lo, slots) (lo > 0: what the fused scatter launches left of a reset's clear debt, sdt_clear_plan.h).  The two gates are that
+// debt's: `unless` (Stats.clear_void) says that the device has cleared the whole table already and nodes may be in it; `only_if` is the
+// flag of a fused scatter launch whose replay needs the rest of the debt cleared NOW (sk_scatter_launch).  Both NULL: clear.
+template <int NW> __global__ __launch_bounds__(TPB) void k_clear(Table<NW> tbl, uint64_t lo, const uint32_t *only_if, const unsigned long long *unless)
 {
+	if ((only_if && *only_if == 0) || (unless && *unless != 0))
+		return;
 	const uint64_t slots = tbl.slots();
-	for (uint64_t s = blockIdx.x * (uint64_t)TPB + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * TPB) {
+	for (uint64_t s = lo + blockIdx.x * (uint64_t)TPB + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * TPB) {
 		Entry<NW> e;
 #pragma unroll
 		for (int i = 0; i < NW; i++)

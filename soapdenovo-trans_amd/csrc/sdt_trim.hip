@@ -63,7 +63,7 @@ int sdt_gpu_trim_reads_device(sdt_ctx *c, const void *d_packed_words, const void
 	if (rc != SDT_OK) return rc;
 	rc = search_ready(c, "sdt_gpu_trim_reads");
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	return trim_device(c, (const uint32_t *)d_packed_words, (const uint64_t *)d_offsets, nreads, max_read_len, params, (ReadTrim *)d_trim,
 	                   (uint8_t *)d_keep, n_kept);
 }
@@ -87,7 +87,7 @@ int sdt_gpu_trim_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwords
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc == SDT_OK) rc = strip_plan(c, nreads, in.longest, &geo);      // (the whole call is refused before a piece's records are written)
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	DevBuf d_r, d_k;
 	uint64_t kept = 0;
 	rc = for_each_piece(c, packed_words, offsets, nreads, 1, "trim staging", [&](const StagedPiece &p) -> int {
@@ -121,7 +121,7 @@ int sdt_gpu_trim_kept_reads(sdt_ctx *c, const sdt_trim_params *params, sdt_read_
 		return SDT_OK;
 	if (!trim)
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	// batch by batch: dense records on the device, scattered to their ordinals on the host
 	DevBuf d_r;
@@ -150,7 +150,7 @@ int sdt_gpu_compact_trimmed_device(sdt_ctx *c, const void *d_packed_words, const
 	if (n_out_words) *n_out_words = 0;
 	if (!d_out_words || !d_out_offsets || (nreads && (!d_packed_words || !d_offsets || !d_trim)))
 		return fail(SDT_EINVAL, "NULL argument");
-	HIPCHK(hipSetDevice(c->device));
+	SDT_ENTER(c);
 	return compact_trimmed_device(c, (const uint32_t *)d_packed_words, (const uint64_t *)d_offsets, nreads, (const ReadTrim *)d_trim,
 	                              (uint32_t *)d_out_words, out_words_cap, (uint64_t *)d_out_offsets, n_out_reads, n_out_words);
 }
@@ -161,6 +161,7 @@ int sdt_gpu_compact_trimmed(sdt_ctx *c, const uint32_t *packed_words, uint64_t n
 {
 	if (!c)
 		return fail(SDT_EINVAL, "ctx is NULL");
+	SDT_ENTER(c);
 	if (n_out_reads) *n_out_reads = 0;
 	if (n_out_words) *n_out_words = 0;
 	if (!out_words || !out_offsets || (nreads && (!packed_words || !offsets || !trim)))
