@@ -920,7 +920,102 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  *     host form         the piece of the stream that is staged, and 24 B + 1 B per read of it for records and keep
  *     kept form         the 24 B records of the largest kept batch (the unit verdicts are taken on the host)
  * Out of scope: Hamming-distance or IUPAC matching; masking the matching bases instead of dropping the read; attribution by majority
- * vote; k above 31; sets larger than device memory; any change to another stage. */
+ * vote; k above 31; sets larger than device memory; any change to another stage.
+ *
+ * The two mates of an overlapping pair merged into one fragment read, and base qualities carried through one compaction.  These are
+ * the two things that the overlap stage and the quality stage list as out of scope ("merging the mates into one read; correcting
+ * mismatching bases in the overlap (needs qualities)", "NO later stage carries qualities along"): they went here.  An overlapping
+ * pair puts every base of its overlap into pass 1 twice, once per strand, with independent errors, which inflates the counts of short
+ * fragments only; and the second read pass links edges within one read, so a merged fragment crosses junctions that neither mate
+ * crosses.  Needs NO counted table.  quality -> compact_trimmed_device + compact_quals_trimmed_device -> overlap -> merge (with the
+ * qualities) -> compact_trimmed_device of the merge records for the rest goes without a copy to the host.  Added without a change of
+ * SDT_ABI_VERSION: the five calls, the two structs and SDT_MERGE_MERGED are additions.
+ *     Integers only.  Every pair is decided on its own.  Nothing is read but the two mates, their two overlap records and, if given,
+ *     their quality bytes.  The result does not depend on the launch geometry, on where a read starts in its word, or on where the
+ *     merged read starts in the output's word.  Bases are the stream's codes (A 0, C 1, T 2, G 3).  b' is the reverse complement of
+ *     b: b'[q] = b[Lb - 1 - q] ^ 2.
+ *     INPUT.   The 2-bit stream and its offsets as for overlap_pairs; ov, the sdt_read_overlap records of the same reads as
+ *              overlap_pairs wrote them; optionally quals, one byte per base under the same offsets, exactly the input of
+ *              sdt_gpu_quality_reads, or NULL.  The stage does not search for an overlap: it acts on the record, as compact_trimmed
+ *              acts on a trim record.
+ *     MERGEABLE.  Pair t has mates a = read 2t of La bases and b = read 2t + 1 of Lb bases, Fa = ov[2t].insert, Fb = ov[2t + 1].insert.
+ *              With F = Fa the pair is MERGED iff all of these hold:
+ *                  Fa == Fb
+ *                  1 <= F < La + Lb       (every shift d = F - Lb with -Lb < d < La: at least one column exists unless a mate has
+ *                                          no bases, and every position of [0, F) is covered by a or by b'; checked on the CPU for
+ *                                          more than 825 combinations of La, Lb, F)
+ *                  max(min_len, 1) <= F
+ *                  max_len == 0 or F <= max_len
+ *              A pair without overlap (Fa == Fb == 0) is not merged.  Any other record pair that violates one of the first two lines
+ *              is INCONSISTENT: the host form and the kept form refuse the whole call with SDT_EINVAL before anything is staged,
+ *              with a message that names the pair and the two inserts; the device form cannot read the records on the host, treats
+ *              such a pair as not merged and never reads outside the two mates.  A mate that its overlap record dropped for min_len
+ *              still takes part: the record's insert decides, not its len.
+ *     MERGED READ.  m[0, F), with d = F - Lb.  For position p:
+ *                  p < La only (p < d)                       m[p] = a[p]
+ *                  p - d in [0, Lb) only (p >= La)           m[p] = b'[p - d]
+ *                  both, a[p] == b'[p - d]                   that base
+ *                  both, they differ: a MISMATCH COLUMN      without quals: a[p].  With quals: qa is the quality of a's base p, qb
+ *                                                            that of b's base Lb - 1 - (p - d), both read as the quality stage reads
+ *                                                            them (c < phred_offset gives 0, else min(c - phred_offset, 93)).  If
+ *                                                            qb > qa the base is b'[p - d] and the column counts in from_b; otherwise
+ *                                                            it is a[p].  A tie goes to mate 1.
+ *     RECORD.  One sdt_read_merge per READ; both mates get the same first three fields.  merged = F if merged, else 0.  mismatches =
+ *              the mismatch columns, recounted by this stage, 0 if not merged.  from_b as above.  start, len and verdict sit where
+ *              sdt_read_trim has them and say what is left of this read in the stream of UNMERGED reads: for a merged pair
+ *              start = len = 0 and verdict = 5 (SDT_MERGE_MERGED); for every other read the start, len and verdict of its overlap
+ *              record, copied.  So the records go to sdt_gpu_compact_trimmed / _device as they are, and what comes out is the stream
+ *              of the pairs that did not merge.
+ *     MERGED STREAM.  Output read j is the j-th merged pair in ascending pair index (kept form: ascending ordinal of the first mate),
+ *              packed like any stream: 16 bases per word, the first base in the most significant pair, out_offsets[n_merged + 1] from
+ *              0, the tail bits zero and the pad words of sdt_gpu_push_reads (zero) behind.  It is what sdt_gpu_count_reads_device of
+ *              another context, dedup_reads_device(paired = 0) and the other dense forms take.  (offsets[nreads] - offsets[0] + 15) /
+ *              16 + 4 words always suffice for out_words, nreads / 2 + 1 entries for out_offsets.
+ *     SINGLE READS.  The kept form's ordinals outside every pair range, and a pair of which one mate is not kept in HBM, get their
+ *              overlap record's start, len and verdict copied and are never merged.
+ *     Defaults of the command line: min_len 0, max_len 0 (no limit), phred_offset 33.
+ *   merge_pairs:    mg[i] for read i of a host batch in which reads 2t and 2t + 1 are mates; quals (may be NULL) holds offsets[nreads]
+ *                   bytes.  The whole stream is staged at once, like compact_reads, because the output of pieces would meet in the
+ *                   middle of words.  SDT_EFULL with *n_merged and *n_out_words set, and nothing written or staged, when
+ *                   out_words_cap < *n_out_words + 4.
+ *   merge_pairs_device: buffers already on the device: d_ov and d_mg nreads records of 24 bytes, d_quals NULL or 4-byte aligned,
+ *                   d_out_offsets nreads / 2 + 1 words; d_out_words must not overlap the input.  SDT_EFULL as above, nothing written.
+ *                   The call waits for the kernels.  d_mg is what sdt_gpu_compact_trimmed_device takes.
+ *   merge_kept_pairs: the reads kept in HBM, over ALL kept batches at once like overlap_kept_pairs: ov[] and mg[] by READ ORDINAL
+ *                   (SDT_EFULL, nothing written, when a kept read's ordinal is >= out_capacity; records of ordinals that no kept read
+ *                   has are neither read nor written); pair_ranges with the meaning and the checks of select_kept_reads.  No
+ *                   qualities (the kept reads carry none): a mismatch column takes mate 1's base, phred_offset is ignored.  out_words
+ *                   and out_offsets are host arrays of out_words_cap words and out_reads_cap + 1 entries; SDT_EFULL with *n_merged and
+ *                   *n_out_words set, and nothing written, when either is short.  *nreads = reads decided.  The kept reads are NOT
+ *                   changed.
+ *   compact_quals_trimmed: the bytes [offsets[r] + start, + len) of every read r, by the records that compact_trimmed takes (any of
+ *                   the 24-byte records of the stages), go to where compact_trimmed, on the same records, puts the read's bases: one
+ *                   after the other in read order.  The output offsets are those that compact_trimmed writes and are not written
+ *                   again.  *n_out_bytes = the bytes kept; the output is zero-padded to a multiple of 4 bytes, and SDT_EFULL (with
+ *                   *n_out_bytes set, nothing written) when out_cap is less than that.  start + len beyond the read is SDT_EINVAL
+ *                   before anything is staged, as are offsets that are not monotonic and nbytes < offsets[nreads].
+ *   compact_quals_trimmed_device: buffers on the device; d_out_quals 4-byte aligned (SDT_EINVAL otherwise) and not overlapping the
+ *                   input: what quality_reads_device and merge_pairs_device require of d_quals.  It cannot refuse a range: start
+ *                   and len are clamped to the read, as in compact_trimmed_device.
+ * State: the dense forms need a context for its stream only: any state, any kind of context, like dedup_reads.  The kept form
+ * follows the rules of sdt_gpu_kept_batches.  nreads == 0: SDT_OK, *n_merged = 0 and out_offsets[0] = 0 if given, nothing else
+ * touched.  There is NO limit on the read length: a wavefront walks a fragment 2 048 bases at a time (merged, start and len are
+ * 32-bit, as in sdt_read_trim).
+ * SDT_EINVAL, from a check on the host before any launch, with a message that names the field and its value: NULL params; flags != 0;
+ * max_len != 0 and max_len < max(min_len, 1); phred_offset other than 0, 33 or 64 when quals are given (ignored when quals is NULL);
+ * an odd nreads in the dense forms; the device form: d_quals not 4-byte aligned; pair ranges that select_kept_reads refuses.
+ * Device memory held during the call, beside the reads, the records and the output, SDT_ENOMEM (nothing written) when it does not fit:
+ *     merge, device form   per pair 4 B (its merged length) and 3 x 8 B (the scans: output offset, rank, place in the scratch), the
+ *                          scans' temporary storage, and the scratch stream: 8 B per 32 bases of every merged read, each rounded up,
+ *                          with 8 B per merged pair for its place in it
+ *     merge, host form     that, the whole staged stream with its offsets, 24 B + 24 B per read for the two kinds of records, the
+ *                          qualities if given, and the output
+ *     merge, kept form     per ordinal up to the highest kept one: the 24 B entry of dedup_kept_reads and 24 B + 24 B for the two
+ *                          kinds of records; 24 B per stretch of units; the device form's scratch per unit; the output
+ *     compact_quals_trimmed  8 B per read (the scan) and its temporary storage; the host form also the staged bytes, offsets,
+ *                          records and the output
+ * Out of scope: qualities of the merged read (the outputs stay FASTA); indels; merging without an overlap record; a kept form with
+ * qualities (the kept reads carry none); any change to overlap, quality or the compaction calls. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -949,6 +1044,9 @@ typedef struct { uint32_t kmers, hits, ref, start, len, verdict; } sdt_read_scre
 typedef struct { uint32_t min_hits, min_hit_pct, flags, reserved; } sdt_screen_params;
 #define SDT_SCREEN_KEEP_MATCHED 1u  /* sdt_screen_params.flags: bait mode, the unmatched units are dropped */
 #define SDT_SCREEN_NO_REF 0xFFFFFFFFu /* sdt_read_screen.ref / screen_lookup: no reference */
+typedef struct { uint32_t merged, mismatches, from_b, start, len, verdict; } sdt_read_merge;   /* 24 bytes */
+typedef struct { uint32_t min_len, max_len, phred_offset, flags; } sdt_merge_params;
+#define SDT_MERGE_MERGED 5u     /* sdt_read_merge.verdict: the pair was merged, nothing of this read is left in the unmerged stream */
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -1044,6 +1142,23 @@ int sdt_gpu_screen_reads_device(sdt_ctx *ctx, const void *d_packed_words, const 
                                 const sdt_screen_params *params, void *d_out, void *d_keep, uint64_t *n_kept);
 int sdt_gpu_screen_kept_reads(sdt_ctx *ctx, const sdt_screen_params *params, const uint64_t *pair_ranges, uint64_t n_ranges,
                               sdt_read_screen *out, uint64_t out_capacity, uint64_t *nreads, uint64_t *n_kept);
+int sdt_gpu_merge_pairs(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets, uint64_t nreads,
+                        const sdt_read_overlap *ov, const uint8_t *quals, const sdt_merge_params *params, sdt_read_merge *mg,
+                        uint32_t *out_words, uint64_t out_words_cap, uint64_t *out_offsets, uint64_t *n_merged,
+                        uint64_t *n_out_words);
+int sdt_gpu_merge_pairs_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                               const void *d_ov, const void *d_quals, const sdt_merge_params *params, void *d_mg,
+                               void *d_out_words, uint64_t out_words_cap, void *d_out_offsets, uint64_t *n_merged,
+                               uint64_t *n_out_words);
+int sdt_gpu_merge_kept_pairs(sdt_ctx *ctx, const sdt_merge_params *params, const uint64_t *pair_ranges, uint64_t n_ranges,
+                             const sdt_read_overlap *ov, sdt_read_merge *mg, uint64_t out_capacity, uint32_t *out_words,
+                             uint64_t out_words_cap, uint64_t *out_offsets, uint64_t out_reads_cap, uint64_t *nreads,
+                             uint64_t *n_merged, uint64_t *n_out_words);
+int sdt_gpu_compact_quals_trimmed(sdt_ctx *ctx, const uint8_t *quals, uint64_t nbytes, const uint64_t *offsets,
+                                  uint64_t nreads, const sdt_read_trim *recs, uint8_t *out_quals, uint64_t out_cap,
+                                  uint64_t *n_out_bytes);
+int sdt_gpu_compact_quals_trimmed_device(sdt_ctx *ctx, const void *d_quals, const void *d_offsets, uint64_t nreads,
+                                         const void *d_recs, void *d_out_quals, uint64_t out_cap, uint64_t *n_out_bytes);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

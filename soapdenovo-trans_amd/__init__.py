@@ -189,6 +189,18 @@ _ABI = [
                                                _c.c_void_p, _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_screen_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64,
                                              _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_merge_pairs", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                       _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_merge_pairs_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                              _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.POINTER(_c.c_uint64),
+                                              _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_merge_kept_pairs", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                            _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64),
+                                            _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_compact_quals_trimmed", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                                 _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_compact_quals_trimmed_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                                        _c.c_uint64, _c.POINTER(_c.c_uint64)]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -233,6 +245,11 @@ READ_SCREEN_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "hits", "ref", "
 SCREEN_KEPT, SCREEN_DROPPED = range(2)
 SCREEN_KEEP_MATCHED = 1                                  # SDT_SCREEN_KEEP_MATCHED
 SCREEN_NO_REF = 0xFFFFFFFF
+# sdt_read_merge (include/sdt_gpu.h): one record per read of a merge; merged = the fragment's bases (0: the pair was not merged),
+# mismatches = the mismatch columns of the overlap, from_b = those of them decided for mate 2 by the qualities; start, len and verdict
+# say what is left of the read in the stream of unmerged reads, where READ_TRIM_DTYPE has them (a merged pair: 0, 0, MERGE_MERGED)
+READ_MERGE_DTYPE = np.dtype([(f, np.uint32) for f in ("merged", "mismatches", "from_b", "start", "len", "verdict")])
+MERGE_MERGED = 5                                         # SDT_MERGE_MERGED
 
 
 class NormParams(_c.Structure):
@@ -286,6 +303,14 @@ class ScreenParams(_c.Structure):
 
     def __init__(self, min_hits=1, min_hit_pct=0, flags=0, reserved=0):
         super().__init__(min_hits, min_hit_pct, flags, reserved)
+
+
+class MergeParams(_c.Structure):
+    """sdt_merge_params; the defaults of `sdt-kmers merge`"""
+    _fields_ = [(f, _c.c_uint32) for f in ("min_len", "max_len", "phred_offset", "flags")]
+
+    def __init__(self, min_len=0, max_len=0, phred_offset=33, flags=0):
+        super().__init__(min_len, max_len, phred_offset, flags)
 
 
 class AdapterSet(_c.Structure):
@@ -1115,6 +1140,112 @@ class PregraphGPU:
         self._check(self.lib.sdt_gpu_quality_reads_device(self._ctx, _ptr(d_quals), _ptr(d_offsets), nreads, ctypes.addressof(prm), _ptr(d_out),
                                                           _ptr(d_keep), ctypes.byref(kept)))
         return kept.value
+
+    # -- the mates of an overlapping pair merged into one fragment read by their overlap records; qualities through a compaction (the
+    # rule: include/sdt_gpu.h)
+    @staticmethod
+    def _merge_params(params):
+        """params: MergeParams or its fields as a dict"""
+        return params if isinstance(params, MergeParams) else MergeParams(**(params or {}))
+
+    def _merge_error(self, rc, n_merged, n_words):
+        e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+        e.needed, e.n_merged = n_words.value, n_merged.value
+        return e
+
+    def merge_pairs(self, words, offsets, ov, quals=None, params=None, out_words_cap: int = None):
+        """reads 2t and 2t + 1 are mates, ov their READ_OVERLAP_DTYPE records, quals (optional) one byte per base under offsets
+        -> (READ_MERGE_DTYPE[nreads], words uint32[n_out_words + 4] of the merged reads, offsets uint64[n_merged + 1]);
+        SdtError SDT_EFULL when out_words_cap is too small: e.needed = the words without the pad, e.n_merged = the pairs that merge"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ov = np.ascontiguousarray(ov, dtype=READ_OVERLAP_DTYPE)
+        n = len(offsets) - 1
+        assert len(ov) == n
+        if quals is not None:
+            quals = np.ascontiguousarray(quals, dtype=np.uint8)
+            assert quals.size >= (int(offsets[-1]) if n else 0)
+        cap = (((int(offsets[-1]) - int(offsets[0]) + 15) >> 4) if n else 0) + 4 if out_words_cap is None else out_words_cap
+        mg = np.zeros(n, dtype=READ_MERGE_DTYPE)
+        out_words = np.full(max(cap, 1), 0xABABABAB, dtype=np.uint32)
+        out_offsets = np.zeros(n // 2 + 1, dtype=np.uint64)
+        prm = self._merge_params(params)
+        nm, nw = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self.lib.sdt_gpu_merge_pairs(self._ctx, _ptr(words), words.size, _ptr(offsets), n, _ptr(ov), _ptr(quals), ctypes.addressof(prm),
+                                          _ptr(mg), _ptr(out_words), cap, _ptr(out_offsets), ctypes.byref(nm), ctypes.byref(nw))
+        if rc != SDT_OK:
+            raise self._merge_error(rc, nm, nw)
+        return mg, out_words[: nw.value + 4], out_offsets[: nm.value + 1]
+
+    def merge_pairs_device(self, d_words, d_offsets, nreads: int, d_ov, d_mg, d_out_words, out_words_cap: int, d_out_offsets, d_quals=None,
+                           params=None):
+        """device buffers; d_ov and d_mg hold nreads records of 24 bytes (d_mg is what compact_trimmed_device takes), d_quals (optional)
+        4-byte aligned, d_out_offsets nreads // 2 + 1 words -> (pairs merged, words without the 4 pad words); SdtError SDT_EFULL: e.needed,
+        e.n_merged"""
+        prm = self._merge_params(params)
+        nm, nw = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self.lib.sdt_gpu_merge_pairs_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, _ptr(d_ov), _ptr(d_quals),
+                                                 ctypes.addressof(prm), _ptr(d_mg), _ptr(d_out_words), out_words_cap, _ptr(d_out_offsets),
+                                                 ctypes.byref(nm), ctypes.byref(nw))
+        if rc != SDT_OK:
+            raise self._merge_error(rc, nm, nw)
+        return nm.value, nw.value
+
+    def merge_kept_pairs(self, total_reads: int, ov, pair_ranges=(), params=None, out: np.ndarray = None, out_words_cap: int = 0,
+                         out_reads_cap: int = None):
+        """the reads kept in HBM; ov: READ_OVERLAP_DTYPE by read ordinal (what overlap_kept_pairs wrote); pair_ranges as there
+        -> (READ_MERGE_DTYPE[total_reads] by read ordinal, words of the merged reads with their 4 pad words, offsets uint64[n_merged + 1],
+        reads decided); SdtError SDT_EFULL when a capacity is too small: e.needed, e.n_merged"""
+        if out is None:
+            out = np.zeros(total_reads, dtype=READ_MERGE_DTYPE)
+        assert out.dtype == READ_MERGE_DTYPE and out.flags.c_contiguous and len(out) >= total_reads
+        ov = np.ascontiguousarray(ov, dtype=READ_OVERLAP_DTYPE)
+        assert len(ov) >= total_reads
+        ranges = np.ascontiguousarray(np.asarray(pair_ranges, dtype=np.uint64).reshape(-1))
+        assert ranges.size % 2 == 0
+        rcap = total_reads // 2 if out_reads_cap is None else out_reads_cap
+        out_words = np.full(max(out_words_cap, 1), 0xABABABAB, dtype=np.uint32)
+        out_offsets = np.zeros(rcap + 1, dtype=np.uint64)
+        prm = self._merge_params(params)
+        n, nm, nw = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self.lib.sdt_gpu_merge_kept_pairs(self._ctx, ctypes.addressof(prm), _ptr(ranges) if ranges.size else None, ranges.size // 2, _ptr(ov),
+                                               _ptr(out), total_reads, _ptr(out_words), out_words_cap, _ptr(out_offsets), rcap, ctypes.byref(n),
+                                               ctypes.byref(nm), ctypes.byref(nw))
+        if rc != SDT_OK:
+            raise self._merge_error(rc, nm, nw)
+        return out, out_words[: nw.value + 4], out_offsets[: nm.value + 1], n.value
+
+    def compact_quals_trimmed(self, quals, offsets, recs, out_cap: int = None):
+        """the bytes [start, start + len) of every read, by 24-byte records with start and len where READ_TRIM_DTYPE has them, one read
+        after the other -> (uint8[bytes kept, zero-padded to a multiple of 4], bytes kept); what compact_trimmed does to the bases under the same records.  SdtError SDT_EFULL when
+        out_cap is less than the bytes kept rounded up to 4: e.needed = the bytes kept"""
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        recs = np.ascontiguousarray(recs)
+        assert recs.dtype.itemsize == 24 and len(recs) == len(offsets) - 1
+        n = len(offsets) - 1
+        cap = (quals.size + 3) & ~3 if out_cap is None else out_cap
+        out = np.full(max(cap, 1), 0xAB, dtype=np.uint8)
+        nb = ctypes.c_uint64()
+        rc = self.lib.sdt_gpu_compact_quals_trimmed(self._ctx, _ptr(quals), quals.size, _ptr(offsets), n, _ptr(recs), _ptr(out), cap,
+                                                    ctypes.byref(nb))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.needed = nb.value
+            raise e
+        return out[: (nb.value + 3) & ~3], nb.value
+
+    def compact_quals_trimmed_device(self, d_quals, d_offsets, nreads: int, d_recs, d_out_quals, out_cap: int) -> int:
+        """device buffers; d_out_quals 4-byte aligned, out_cap bytes -> bytes kept (the output is zero-padded to a multiple of 4);
+        SdtError SDT_EFULL: e.needed = the bytes kept"""
+        nb = ctypes.c_uint64()
+        rc = self.lib.sdt_gpu_compact_quals_trimmed_device(self._ctx, _ptr(d_quals), _ptr(d_offsets), nreads, _ptr(d_recs), _ptr(d_out_quals),
+                                                           out_cap, ctypes.byref(nb))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.needed = nb.value
+            raise e
+        return nb.value
 
     # -- reads screened against reference sequences (rRNA, PhiX, ...); a k-mer set of its own, no counted table (the rule: include/sdt_gpu.h)
     @staticmethod

@@ -81,6 +81,15 @@
  *       prefix.readScreen: one line per read in stream order:  kmers hits ref verdict   (ref 1-based in the order of the files, 0 none)
  *       prefix.screen.pairs.fa / prefix.screen.single.fa: the surviving reads, as clip writes them
  *       prefix.screenStats: per reference  index name bases reads hits,  then  # reads R matched M kept K dropped D
+ *   sdt-kmers merge -s lib.cfg -K k [-p threads] [--min-overlap N, default 30] [--max-err PCT, default 10] [--min-len L, default 0]
+ *                   [--min-merged L, default 0] [--max-merged L, default 0 = no limit] -o prefix
+ *       the two mates of every pair that overlaps merged into one fragment read (sdt_gpu_overlap_kept_pairs, then
+ *       sdt_gpu_merge_kept_pairs; the rule: include/sdt_gpu.h); FASTA and FASTQ libraries alike, no qualities are used: a mismatch
+ *       column takes mate 1's base.  Pairs as for normalize; a library without pairs is allowed: nothing merges (mergesplit.c)
+ *       prefix.readMerge: one line per read in stream order:  merged mismatches from_b start len verdict
+ *       prefix.merge.fa: the merged fragments, one record per merged pair, > the first mate's ordinal + 1
+ *       prefix.merge.pairs.fa / prefix.merge.single.fa: the kept bases of the reads that did not merge, as overlap writes them
+ *       prefix.insertHist: as overlap writes it
  *
  * The query file is read and checked before the device is touched.
  *
@@ -106,6 +115,7 @@
 #include "cxsplit.h"
 #include "qualsplit.h"
 #include "screensplit.h"
+#include "mergesplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -219,6 +229,22 @@ static void usage(void)
 	        "              that survive), prefix.screen.single.fa (every other surviving read), prefix.screenStats (per reference: index name\n"
 	        "              bases reads hits, reads = the reads whose ref it is, hits = their hits; then: # reads R matched M kept K dropped D)\n"
 	        "           Pairs are the reads of q1=/q2= and f1=/f2= files; the reads of a p= file are single reads, as for normalize.\n"
+	        "       sdt-kmers merge -s lib.cfg -K k [-p threads] [--min-overlap N, default 30] [--max-err PCT, default 10]\n"
+	        "                       [--min-len L, default 0] [--min-merged L, default 0] [--max-merged L, default 0] -o prefix\n"
+	        "           the overlap of the two mates of every pair is found as `overlap` finds it (--min-overlap, --max-err, --min-len are\n"
+	        "           its options); a pair that overlaps with a fragment of at least max(--min-merged, 1) and, unless --max-merged is 0, at\n"
+	        "           most --max-merged bases is merged into one read of the fragment's length: mate 1, then what mate 2,\n"
+	        "           reverse-complemented, adds behind it.  Where the two mates differ in the overlap, the base of mate 1 stays (the\n"
+	        "           command line has no qualities: FASTA and FASTQ libraries alike).  The reads of every other pair are kept as\n"
+	        "           `overlap` keeps them.  Needs no counted k-mers: run it in the place of overlap.\n"
+	        "           -> prefix.readMerge (per read in stream order: merged mismatches from_b start len verdict; merged = the fragment's\n"
+	        "              bases, 0 if the pair did not merge; mismatches = the columns of the overlap in which the mates differ; start,\n"
+	        "              len and verdict say what is left of the read outside the merged file: verdict 5 merged, else 0 whole,\n"
+	        "              2 clipped, 3 dropped), prefix.merge.fa (one record per merged pair, named by the first mate's read number),\n"
+	        "              prefix.merge.pairs.fa (read 1 then read 2 of the pairs that did not merge and of which both mates survive),\n"
+	        "              prefix.merge.single.fa (every other surviving read), prefix.insertHist (as overlap writes it)\n"
+	        "           and one line: merge: reads R pairs P overlapping V merged M mismatch columns C bases in I bases out O\n"
+	        "           Pairs are the reads of q1=/q2= and f1=/f2= files; a library without pairs is allowed: nothing merges.\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -285,6 +311,7 @@ typedef struct {
 	sdt_clip_params clip;
 	char afile[2][4096];                                                     /* -a: 3' adapters, -g: 5' adapters */
 	sdt_overlap_params overlap;
+	sdt_merge_params merge;
 	sdt_complexity_params cx;
 	int max_low_given;
 	sdt_quality_params qual;
@@ -726,6 +753,121 @@ static int run_overlap(sdt_ctx *gpu, unsigned long long reads, options *opt, con
 	return 0;
 }
 
+/* ---- merge ----------------------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+	overlap_state ov;                                                        /* the overlap records, checked and counted as `overlap` does */
+	const sdt_read_merge *rec;
+	uint64_t first_ord;                                                      /* the first mate's ordinal, while the second is awaited */
+	sdt_merge_stats stats;
+} merge_state;
+
+static int merge_note(void *state, uint64_t ord, uint64_t read_len, uint64_t *start, uint64_t *len)
+{
+	merge_state *s = (merge_state *)state;
+	const sdt_read_merge *t = s->rec + ord;
+	uint64_t ov_start = 0, ov_len = read_len;
+	if (overlap_note(&s->ov, ord, read_len, &ov_start, &ov_len) != 0) return -1;
+	int ok = sdt_merge_record_ok(t, s->ov.rec + ord, read_len);
+	/* (overlap_note has moved the cursor: the range that holds ord, if one does) */
+	if (ok && sdt_pair_ranges_holds(s->ov.pairs, ord, &s->ov.cursor)) {
+		if (((ord - s->ov.pairs->v[2 * s->ov.cursor]) & 1) == 0) s->first_ord = ord;
+		else ok = sdt_merge_stats_note(&s->stats, s->rec + s->first_ord, t, s->ov.rec + s->first_ord, s->ov.rec + ord) == 0;
+	} else if (ok) ok = t->merged == 0;                                      /* a single read is never merged */
+	if (!ok) {
+		fprintf(stderr, "sdt-kmers: the merge record of read %llu is %u %u %u %u %u %u of %llu bases\n", (unsigned long long)ord + 1, t->merged, t->mismatches,
+		        t->from_b, t->start, t->len, t->verdict, (unsigned long long)read_len);
+		return -1;
+	}
+	*start = t->start;
+	*len = t->len;
+	return 0;
+}
+
+static char *merge_line(const void *state, char *p, uint64_t ord) { return sdt_put_merge_line(p, ((const merge_state *)state)->rec + ord); }
+static int merge_alive(const void *state, uint64_t ord) { return ((const merge_state *)state)->rec[ord].len != 0; }
+
+/* prefix.merge.fa: output read j of the merged stream under the name of the j-th merged pair's first mate; 0, or 1 after saying why */
+static int merged_write(const char *prefix, const sdt_pair_ranges *pairs, const sdt_read_merge *mg, uint64_t reads, const uint32_t *words,
+                        const uint64_t *offsets, uint64_t n_merged)
+{
+	static const char letters[4] = {'A', 'C', 'T', 'G'};
+	char path[4200];
+	outbuf o;
+	snprintf(path, sizeof path, "%s.merge.fa", prefix);
+	if (ob_open(&o, path) != 0) return 1;
+	uint64_t j = 0;
+	for (size_t r = 0; r < pairs->n && o.ok; r++)
+		for (uint64_t ord = pairs->v[2 * r]; ord + 1 < pairs->v[2 * r + 1] && ord + 1 < reads && o.ok; ord += 2) {
+			if (!mg[ord].merged) continue;
+			if (j == n_merged || offsets[j + 1] - offsets[j] != mg[ord].merged) {
+				fprintf(stderr, "sdt-kmers: the merged stream does not hold the %u bases of the pair at read %llu\n", mg[ord].merged, (unsigned long long)ord + 1);
+				ob_close(&o);
+				return 1;
+			}
+			ob_room(&o, 24);
+			*o.p++ = '>';
+			o.p = sdt_put_dec(o.p, ord + 1, '\n');
+			for (uint64_t b = offsets[j]; b < offsets[j + 1] && o.ok;) {       /* (a fragment may be longer than a block) */
+				const uint64_t n = offsets[j + 1] - b < 65536 ? offsets[j + 1] - b : 65536;
+				ob_room(&o, (size_t)n + 1);
+				for (uint64_t e = b + n; b < e; b++) *o.p++ = letters[(words[b >> 4] >> (30 - 2 * (int)(b & 15))) & 3u];
+			}
+			*o.p++ = '\n';
+			j++;
+		}
+	if (ob_close(&o) != 0) return 1;
+	if (j != n_merged) { fprintf(stderr, "sdt-kmers: %llu pairs merged, the records name %llu\n", (unsigned long long)n_merged, (unsigned long long)j); return 1; }
+	return 0;
+}
+
+/* `merge`: the overlap records and then the merge records and the merged stream from the device, the kept batches back from HBM, the
+ * kept bases of the reads that did not merge into the pairs file or the singles file as overlap routes them, the merged fragments
+ * into a file of their own; the histogram of the inserts (overlapsplit.c), the statistics (mergesplit.c) */
+static int run_merge(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	static const sdt_walk_stage stage = {{".readMerge", ".merge.pairs.fa", ".merge.single.fa"}, SDT_MERGE_LINE_MAX, 0, merge_note, merge_line, merge_alive, NULL};
+	sdt_read_overlap *ov = (sdt_read_overlap *)records_alloc(reads, sizeof *ov, 0);
+	sdt_read_merge *mg = (sdt_read_merge *)records_alloc(reads, sizeof *mg, 0);
+	uint64_t got = 0, n_kept = 0, n_merged = 0, n_words = 0;
+	if (!ov || !mg || SDT_CALL(sdt_gpu_overlap_kept_pairs, gpu, &opt->overlap, pairs->v, pairs->n, ov, reads, &got, &n_kept)) return 1;
+	if (!all_reads_came_back(reads, got, "decided")) return 1;
+	/* only a pair with an overlap merges, into as many bases as its insert says: that bounds the merged stream */
+	uint64_t cap_bases = 0, cap_reads = 0;
+	for (size_t r = 0; r < pairs->n; r++)
+		for (uint64_t ord = pairs->v[2 * r]; ord + 1 < pairs->v[2 * r + 1] && ord + 1 < reads; ord += 2)
+			if (ov[ord].insert) { cap_bases += ov[ord].insert; cap_reads++; }
+	const uint64_t cap_words = ((cap_bases + 15) >> 4) + 4;
+	uint32_t *words = (uint32_t *)malloc(cap_words * sizeof(uint32_t));
+	uint64_t *offsets = (uint64_t *)malloc((cap_reads + 1) * sizeof(uint64_t));
+	if (!words || !offsets) { fprintf(stderr, "sdt-kmers: out of memory for %llu merged bases\n", (unsigned long long)cap_bases); return 1; }
+	offsets[0] = 0;
+	if (SDT_CALL(sdt_gpu_merge_kept_pairs, gpu, &opt->merge, pairs->v, pairs->n, ov, mg, reads, words, cap_words, offsets, cap_reads, &got, &n_merged, &n_words)) return 1;
+	if (!all_reads_came_back(reads, got, "decided")) return 1;
+	n_kept = 0;
+	for (unsigned long long i = 0; i < reads; i++) n_kept += mg[i].len != 0;
+	merge_state st;
+	memset(&st, 0, sizeof st);
+	st.ov.rec = ov;
+	st.ov.pairs = pairs;
+	st.rec = mg;
+	sdt_walk_tally t;
+	if (fetch_and_walk(gpu, reads, pairs, opt->outname, &stage, &st, n_kept, &t) != 0) return 1;
+	if (st.stats.merged != n_merged || st.stats.merged_bases != offsets[n_merged]) {
+		fprintf(stderr, "sdt-kmers: the records say %llu pairs merged into %llu bases, the device %llu into %llu\n", (unsigned long long)st.stats.merged,
+		        (unsigned long long)st.stats.merged_bases, (unsigned long long)n_merged, (unsigned long long)offsets[n_merged]);
+		return 1;
+	}
+	if (merged_write(opt->outname, pairs, mg, reads, words, offsets, n_merged) != 0) return 1;
+	char path[4200], summary[512];
+	FILE *fh = stats_open(path, opt->outname, ".insertHist");
+	if (!fh || (sdt_insert_hist_write(fh, &st.ov.hist) != 0) | (fclose(fh) != 0)) return cannot_write(path);
+	sdt_merge_summary(summary, sizeof summary, &st.stats, reads, t.bases_in, t.bases_out);
+	printf("%s\n", summary);
+	sdt_insert_hist_free(&st.ov.hist);
+	free(words); free(offsets); free(ov); free(mg);
+	return 0;
+}
+
 /* ---- complexity ------------------------------------------------------------------------------------------------------------------------ */
 typedef struct { const sdt_read_complexity *rec; sdt_score_hist hist; } cx_state;
 
@@ -1007,7 +1149,7 @@ static int run_query(sdt_ctx *gpu, unsigned long long reads, options *opt, const
 }
 
 /* ---- the command line ------------------------------------------------------------------------------------------------------------------ */
-enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, N_SUBCOMMANDS };
+enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, N_SUBCOMMANDS };
 
 static const struct {
 	const char *name;
@@ -1020,12 +1162,12 @@ static const struct {
 	[TRIM] = {"trim", 1, 1, 2, run_trim},                [DEDUP] = {"dedup", 1, 1, 0, run_dedup},
 	[CLIP] = {"clip", 1, 1, 0, run_clip},                [OVERLAP] = {"overlap", 1, 1, 0, run_overlap},
 	[COMPLEXITY] = {"complexity", 1, 1, 0, run_complexity}, [QTRIM] = {"qtrim", 1, 1, 0, run_qtrim},
-	[SCREEN] = {"screen", 1, 1, 0, run_screen},
+	[SCREEN] = {"screen", 1, 1, 0, run_screen},             [MERGE] = {"merge", 1, 1, 0, run_merge},
 };
 
 enum { O_MAX_K = 1000, O_DEVICE, O_TARGET, O_MAX_CV, O_SEED, O_MIN_COV, O_MIN_LEN, O_CORRECT, O_MATE_SWAP, O_TAIL3, O_TAIL5, O_MIN_OVERLAP, O_ERROR_PCT,
        O_MIN_TAIL, O_TAIL_ERROR_PCT, O_MAX_ERR, O_MAX_SCORE, O_MAX_LOW, O_TRIM_LOW, O_PHRED, O_CUT_Q, O_LOW_Q, O_MAX_LOW_BASES, O_MAX_EE, O_SCREEN_K,
-       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED };
+       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED };
 
 /* the options that belong to some subcommands only: the name as it is printed, who may be given it, what the refusal says after
  * "belongs to" (kept, not derived: --min-overlap names clip alone), and the most its value may be where it takes a whole number */
@@ -1034,11 +1176,11 @@ static const struct { int code; const char *name; unsigned owners; const char *b
 	{O_TARGET, "--target", BIT(NORMALIZE), "normalize", UINT32_MAX}, {O_MAX_CV, "--max-cv", BIT(NORMALIZE), "normalize", UINT32_MAX},
 	{O_SEED, "--seed", BIT(NORMALIZE), "normalize", UINT64_MAX},
 	{O_MIN_COV, "--min-cov", BIT(TRIM), "trim", UINT32_MAX}, {O_CORRECT, "--correct", BIT(TRIM), "trim", 0},
-	{O_MIN_LEN, "--min-len", BIT(TRIM) | BIT(CLIP) | BIT(OVERLAP) | BIT(COMPLEXITY) | BIT(QTRIM), "trim, clip, overlap, complexity and qtrim", UINT32_MAX},
+	{O_MIN_LEN, "--min-len", BIT(TRIM) | BIT(CLIP) | BIT(OVERLAP) | BIT(COMPLEXITY) | BIT(QTRIM) | BIT(MERGE), "trim, clip, overlap, complexity and qtrim", UINT32_MAX},
 	{'a', "-a", BIT(CLIP), "clip", 0}, {'g', "-g", BIT(CLIP), "clip", 0}, {O_TAIL3, "--tail3", BIT(CLIP), "clip", 0}, {O_TAIL5, "--tail5", BIT(CLIP), "clip", 0},
 	{O_ERROR_PCT, "--error-pct", BIT(CLIP), "clip", 100}, {O_MIN_TAIL, "--min-tail", BIT(CLIP), "clip", UINT32_MAX},
-	{O_TAIL_ERROR_PCT, "--tail-error-pct", BIT(CLIP), "clip", 100}, {O_MIN_OVERLAP, "--min-overlap", BIT(CLIP) | BIT(OVERLAP), "clip", UINT32_MAX},
-	{O_MAX_ERR, "--max-err", BIT(OVERLAP), "overlap", 100},
+	{O_TAIL_ERROR_PCT, "--tail-error-pct", BIT(CLIP), "clip", 100}, {O_MIN_OVERLAP, "--min-overlap", BIT(CLIP) | BIT(OVERLAP) | BIT(MERGE), "clip", UINT32_MAX},
+	{O_MAX_ERR, "--max-err", BIT(OVERLAP) | BIT(MERGE), "overlap", 100},
 	{O_MAX_SCORE, "--max-score", BIT(COMPLEXITY), "complexity", 100}, {O_MAX_LOW, "--max-low", BIT(COMPLEXITY), "complexity", 100},
 	{O_TRIM_LOW, "--trim-low", BIT(COMPLEXITY), "complexity", 0},
 	{O_PHRED, "--phred", BIT(QTRIM), "qtrim", 64}, {O_CUT_Q, "--cut-q", BIT(QTRIM), "qtrim", 93}, {O_LOW_Q, "--low-q", BIT(QTRIM), "qtrim", 93},
@@ -1046,6 +1188,7 @@ static const struct { int code; const char *name; unsigned owners; const char *b
 	{'r', "-r", BIT(SCREEN), "screen", 0}, {O_SCREEN_K, "--screen-k", BIT(SCREEN), "screen", 31}, {O_MIN_HITS, "--min-hits", BIT(SCREEN), "screen", UINT32_MAX},
 	{O_MIN_HIT_PCT, "--min-hit-pct", BIT(SCREEN), "screen", 100}, {O_KEEP_MATCHED, "--keep-matched", BIT(SCREEN), "screen", 0},
 	{O_MATE_SWAP, "--mate-swap", BIT(DEDUP), "dedup", 0},
+	{O_MIN_MERGED, "--min-merged", BIT(MERGE), "merge", UINT32_MAX}, {O_MAX_MERGED, "--max-merged", BIT(MERGE), "merge", UINT32_MAX},
 };
 
 /* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
@@ -1089,6 +1232,7 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 	                                   {"max-low-bases", required_argument, 0, O_MAX_LOW_BASES}, {"max-ee", required_argument, 0, O_MAX_EE},
 	                                   {"screen-k", required_argument, 0, O_SCREEN_K}, {"min-hits", required_argument, 0, O_MIN_HITS},
 	                                   {"min-hit-pct", required_argument, 0, O_MIN_HIT_PCT}, {"keep-matched", no_argument, 0, O_KEEP_MATCHED},
+	                                   {"min-merged", required_argument, 0, O_MIN_MERGED}, {"max-merged", required_argument, 0, O_MAX_MERGED},
 	                                   {0, 0, 0, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:r:", longopts, NULL)) != -1) {
@@ -1157,11 +1301,17 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 		case O_MIN_HITS: opt->screen.min_hits = (uint32_t)v; break;
 		case O_MIN_HIT_PCT: opt->screen.min_hit_pct = (uint32_t)v; break;
 		case O_KEEP_MATCHED: opt->screen.flags |= SDT_SCREEN_KEEP_MATCHED; break;
+		case O_MIN_MERGED: opt->merge.min_len = (uint32_t)v; break;
+		case O_MAX_MERGED: opt->merge.max_len = (uint32_t)v; break;
 		default: usage(); return 255;
 		}
 	}
 	if (!opt->cfgfile[0] || (sub == QUERY ? !opt->qfile[0] : !opt->outname[0])) { usage(); return 255; }
 	if (sub == SCREEN && opt->n_rfiles == 0) { fprintf(stderr, "sdt-kmers: screen needs a reference file: -r refs.fa\n"); usage(); return 255; }
+	if (sub == MERGE && opt->merge.max_len != 0 && opt->merge.max_len < (opt->merge.min_len > 1 ? opt->merge.min_len : 1u)) {
+		fprintf(stderr, "sdt-kmers: --max-merged %u is below --min-merged %u: no pair could merge (0: no limit)\n", opt->merge.max_len, opt->merge.min_len);
+		return 255;
+	}
 	if (sub == NORMALIZE && opt->norm.target == 0) { fprintf(stderr, "sdt-kmers: --target must be at least 1\n"); return 255; }
 	if (opt->cx.flags & SDT_COMPLEXITY_TRIM) {
 		if (opt->max_low_given && opt->cx.max_low_pct != 0) {
@@ -1257,7 +1407,7 @@ int main(int argc, char **argv)
 	if (sub == N_SUBCOMMANDS) { usage(); return 255; }
 	static options opt = {.K = 23, .threads = 8,
 	                      .norm = {50, 10000, 0}, .clip = {5, 10, 0, 10, 20, 0, 0, 0}, .overlap = {30, 10, 0, 0}, .cx = {10, 50, 0, 0},
-	                      .qual = {33, 20, 15, 40, 0, 0, 0, 0}, .screen = {1, 0, 0, 0},
+	                      .qual = {33, 20, 15, 40, 0, 0, 0, 0}, .screen = {1, 0, 0, 0}, .merge = {0, 0, 33, 0},
 	                      .screen_k = 31};                                   /* bbduk's usual figure: a choice, not a measurement */
 	opt.min_count = subcommands[sub].min_count;
 	sdt_cfg cfg;

@@ -4,7 +4,8 @@
 // sdt_readstage.hpp calls them for every stage; tools/read_plan_check.cpp (tests/test_read_plan.py) calls them on the CPU under
 // sanitizers.  The six stages that need no table have theirs here too: the duplicate filter (sdt_dedup.hip), the adapter and tail
 // clipping (sdt_clip.hip), the mate overlap (sdt_overlap.hip), the low-complexity filter (sdt_complexity.hip), the reference screen
-// (sdt_screen.hip) and the quality trim (sdt_quality.hip), which also has its cut of a byte stream into pieces here.  No HIP in here.
+// (sdt_screen.hip) and the quality trim (sdt_quality.hip), which also has its cut of a byte stream into pieces here.  The merge of
+// overlapping mates (sdt_merge.hip) has its refusals and the decision of a pair here.  No HIP in here.
 #pragma once
 #include <stdint.h>
 
@@ -269,6 +270,42 @@ constexpr uint64_t overlap_shifts(uint64_t La, uint64_t Lb, uint32_t min_overlap
 {
 	return La < min_overlap || Lb < min_overlap ? 0 : La + Lb - 2 * (uint64_t)min_overlap + 1;
 }
+
+// ---- merging the mates of a pair (sdt_merge.hip): what is refused before any launch, and whether a pair of overlap records merges ----
+// (tools/merge_plan_check.cpp runs the check and holds the decision to the rule's four lines and to a cover of every position)
+struct MergeParams {                                     // == sdt_merge_params of include/sdt_gpu.h
+	uint32_t min_len, max_len, phred_offset, flags;
+};
+
+enum MergeFault { MERGE_OK = 0, MERGE_FLAGS, MERGE_MAX_LEN, MERGE_PHRED_OFFSET, MERGE_ODD_READS };
+
+// the first thing that is refused, in the order of the rules in include/sdt_gpu.h; with_quals: qualities are given (phred_offset is
+// looked at only then); dense_reads: the reads of a dense form, in which reads 2t and 2t + 1 are mates (0 for the kept form)
+inline MergeFault check_merge_params(const MergeParams &p, bool with_quals, uint64_t dense_reads)
+{
+	if (p.flags != 0) return MERGE_FLAGS;
+	if (p.max_len != 0 && p.max_len < (p.min_len > 1 ? p.min_len : 1u)) return MERGE_MAX_LEN;
+	if (with_quals && p.phred_offset != 0 && p.phred_offset != 33 && p.phred_offset != 64) return MERGE_PHRED_OFFSET;
+	if (dense_reads & 1) return MERGE_ODD_READS;
+	return MERGE_OK;
+}
+
+// Mates of La and Lb bases whose overlap records say the inserts Fa and Fb: the length of the merged read (Fa), 0 when the pair is not
+// merged (no overlap: Fa == Fb == 0, or a length that min_len or max_len refuses), MERGE_INCONSISTENT when the two records cannot
+// come from one overlap of these mates: Fa != Fb, or an insert that no shift -Lb < d < La gives (F >= La + Lb).  For a merged pair
+// every position of [0, F) is covered by a or by b' and at least one by both.  (constexpr: the kernel and the scans call it too)
+constexpr int64_t MERGE_INCONSISTENT = -1;
+constexpr int64_t merge_decide(uint64_t La, uint64_t Lb, uint32_t Fa, uint32_t Fb, uint32_t min_len, uint32_t max_len)
+{
+	if (Fa != Fb) return MERGE_INCONSISTENT;
+	if (Fa == 0) return 0;
+	if ((uint64_t)Fa >= La + Lb) return MERGE_INCONSISTENT;
+	if (Fa < (min_len > 1 ? min_len : 1u)) return 0;
+	if (max_len != 0 && Fa > max_len) return 0;
+	return (int64_t)Fa;
+}
+// the 64-bit values of 32 bases that a merged read of F bases takes in the scratch stream
+constexpr uint64_t merge_chunks(uint64_t F) { return (F + 31) >> 5; }
 
 // ---- low-complexity reads (sdt_complexity.hip): what is refused before any launch, and the windows a read is scored in ----
 // (tools/complexity_plan_check.cpp runs the check and holds the windows to a walk over every base)
