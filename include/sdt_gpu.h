@@ -1015,7 +1015,60 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  *     compact_quals_trimmed  8 B per read (the scan) and its temporary storage; the host form also the staged bytes, offsets,
  *                          records and the output
  * Out of scope: qualities of the merged read (the outputs stay FASTA); indels; merging without an overlap record; a kept form with
- * qualities (the kept reads carry none); any change to overlap, quality or the compaction calls. */
+ * qualities (the kept reads carry none); any change to overlap, quality or the compaction calls.
+ *
+ * A per-cycle QC report of a read batch: base composition, qualities, lengths, GC and mean quality.  Every stage above is driven by
+ * parameters (cut_q, low_q, the tails, the adapters, min_len, the Phred offset); this is the view of the data they act on, before and
+ * after a stage: it takes the 24-byte records of any stage as ranges, so the "after" view needs no compaction.  It is the one read
+ * stage that is a reduction over the whole batch and not a record per read.  Needs NO counted table.  Added without a change of
+ * SDT_ABI_VERSION: the three calls, the struct and the two constants are additions.
+ *     Integers only.  Every count is exact.  The result does not depend on the launch geometry, on where a read starts in its word or
+ *     byte, or on how a host batch is cut into pieces.
+ *     INPUT.   The 2-bit stream and offsets[nreads + 1] in bases as for every read batch (16 bases per word, the first in the most
+ *              significant pair, A 0, C 1, T 2, G 3); optionally quals, one byte per base under the same offsets; optionally ranges,
+ *              nreads records of 24 bytes of which only start and len, where sdt_read_trim has them, are read; optionally classes,
+ *              one byte per read.
+ *     COUNTED. Read r is COUNTED iff classes is NULL or classes[r] == class_sel, else PASSED OVER.  It has L = offsets[r + 1] -
+ *              offsets[r] bases; its counted bases are [s, s + n): s = 0 and n = L without ranges, s = start and n = len with them.
+ *              The device form clamps s and n to the read as sdt_gpu_compact_trimmed_device does, and a read whose range had to be
+ *              clamped adds 1 to totals[4]; the host form refuses such a range.  Base i, 0 <= i < n, is the stream's base s + i.
+ *     QUALITY of base i, as in sdt_gpu_quality_reads: q = 0 if its byte < phred_offset, else min(byte - phred_offset, 93).
+ *     ROW of base i.  C = cycles, R = C + 1 rows.  row = min(i, C); under SDT_QC_FROM_END row = min(n - 1 - i, C).  Row C takes
+ *              everything past the C-th cycle.
+ *     REPORT.  A flat array of uint64_t of sdt_gpu_qc_report_words(C) = 203 + 99 R words, the sections in this order:
+ *                  totals      8       [0] reads counted  [1] of those the empty ones (n = 0; they enter no histogram but len[0])
+ *                                      [2] bases counted  [3] reads passed over  [4] ranges clamped (device form only)  [5..7] 0
+ *                  base[R][4]  4 R     counted bases by row and code
+ *                  qual[R][94] 94 R    counted bases by row and q; untouched when quals is NULL
+ *                  len[R]      R       counted reads by min(n, C)
+ *                  gc[101]     101     counted reads with n >= 1 by floor(100 (#C + #G) / n)
+ *                  meanq[94]   94      counted reads with n >= 1 by floor(sum of q / n); untouched when quals is NULL
+ *              For any input: sum base = totals[2]; sum qual = totals[2] with qualities; sum len = totals[0]; sum gc = totals[0] -
+ *              totals[1]; for a forward row c < C the sum of base[c][.] is the number of counted reads with n > c.
+ *     THE CALL ADDS TO THE REPORT.  The caller zeroes it once; batches, pieces and classes then accumulate, and report(A ++ B) =
+ *     report(A) + report(B).
+ *   qc_report_words: 203 + 99 (cycles + 1); 0 for cycles = 0 or > SDT_QC_MAX_CYCLES.
+ *   qc_reads:       a host batch, staged in pieces as for profile_reads; the qualities of a piece from a 4-byte-aligned byte of the
+ *                   stream, with the piece's ranges and classes.  The pieces add into a report on the device, which is added to
+ *                   report[] once, after the last piece: on any error report[] is untouched.
+ *   qc_reads_device: buffers already on the device: d_quals NULL or 4-byte aligned and readable up to offsets[nreads] rounded up to
+ *                   4, d_ranges NULL or nreads records of 24 bytes, d_classes NULL or nreads bytes, d_report 8-byte aligned.  No
+ *                   word of the stream and no quality word without a counted base is read.
+ *   Both forms wait for their kernels.
+ * State: a context is needed for its stream only: any state, any kind of context, like dedup_reads.  nreads == 0: SDT_OK, nothing
+ * touched, whatever the rest says.  There is NO limit on the read length: a workgroup walks a read 256 bases at a time per wavefront,
+ * and what lies past cycle C is counted in 64 bits.
+ * SDT_EINVAL, from a check on the host before any launch, with a message that names the field and its value: NULL params; cycles = 0
+ * or > SDT_QC_MAX_CYCLES; phred_offset other than 0, 33 or 64 (also without quals: the check is a pure function of the params); a
+ * flag other than SDT_QC_FROM_END; class_sel > 255; reserved != 0.  The host form also: offsets that are not monotonic; nwords or
+ * nbytes too short (as for reads and qualities); a range with start + len > L (the message names the read); report_words <
+ * sdt_gpu_qc_report_words(cycles).  The device form also: d_quals not 4-byte aligned; d_report not 8-byte aligned.
+ * Device memory held during the call, beside the reads, SDT_ENOMEM (nothing written) when it does not fit:
+ *     device form       none
+ *     host form         the piece of the stream that is staged with its offsets, its quality bytes, 24 B + 1 B per read of it for
+ *                       ranges and classes where given, and a report-sized buffer (8 B x (203 + 99 R), 3.2 MB at most)
+ * Out of scope: a kept form (the reads kept in HBM carry no qualities); duplication levels (dedup has them); adapter content (clip has
+ * it); over-represented sequences; per-tile statistics; HTML or plots; any change to another stage or to the parser. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -1047,6 +1100,9 @@ typedef struct { uint32_t min_hits, min_hit_pct, flags, reserved; } sdt_screen_p
 typedef struct { uint32_t merged, mismatches, from_b, start, len, verdict; } sdt_read_merge;   /* 24 bytes */
 typedef struct { uint32_t min_len, max_len, phred_offset, flags; } sdt_merge_params;
 #define SDT_MERGE_MERGED 5u     /* sdt_read_merge.verdict: the pair was merged, nothing of this read is left in the unmerged stream */
+#define SDT_QC_MAX_CYCLES 4096
+#define SDT_QC_FROM_END   1u    /* sdt_qc_params.flags: rows count from the last counted base of a read */
+typedef struct { uint32_t cycles, phred_offset, flags, class_sel, reserved; } sdt_qc_params;
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -1159,6 +1215,13 @@ int sdt_gpu_compact_quals_trimmed(sdt_ctx *ctx, const uint8_t *quals, uint64_t n
                                   uint64_t *n_out_bytes);
 int sdt_gpu_compact_quals_trimmed_device(sdt_ctx *ctx, const void *d_quals, const void *d_offsets, uint64_t nreads,
                                          const void *d_recs, void *d_out_quals, uint64_t out_cap, uint64_t *n_out_bytes);
+uint64_t sdt_gpu_qc_report_words(uint32_t cycles);
+int sdt_gpu_qc_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint8_t *quals, uint64_t nbytes,
+                     const uint64_t *offsets, uint64_t nreads, const sdt_read_trim *ranges, const uint8_t *classes,
+                     const sdt_qc_params *params, uint64_t *report, uint64_t report_words);
+int sdt_gpu_qc_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_quals, const void *d_offsets,
+                            uint64_t nreads, const void *d_ranges, const void *d_classes, const sdt_qc_params *params,
+                            void *d_report);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

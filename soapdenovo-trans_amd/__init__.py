@@ -201,6 +201,11 @@ _ABI = [
                                                  _c.c_uint64, _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_compact_quals_trimmed_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
                                                         _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_qc_report_words", _c.c_uint64, [_c.c_uint32]),
+    ("sdt_gpu_qc_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p,
+                                    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64]),
+    ("sdt_gpu_qc_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                           _c.c_void_p, _c.c_void_p]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -250,6 +255,11 @@ SCREEN_NO_REF = 0xFFFFFFFF
 # say what is left of the read in the stream of unmerged reads, where READ_TRIM_DTYPE has them (a merged pair: 0, 0, MERGE_MERGED)
 READ_MERGE_DTYPE = np.dtype([(f, np.uint32) for f in ("merged", "mismatches", "from_b", "start", "len", "verdict")])
 MERGE_MERGED = 5                                         # SDT_MERGE_MERGED
+# the QC report (include/sdt_gpu.h): a flat uint64 array of 203 + 99 (cycles + 1) words that qc_reads ADDS to; qc_sections cuts it up
+QC_MAX_CYCLES = 4096                                     # SDT_QC_MAX_CYCLES
+QC_FROM_END = 1                                          # SDT_QC_FROM_END
+QC_TILE = 152                                            # rows of the kernel's LDS tile (csrc/sdt_read_plan.h: QC_TILE; tools/qc_plan_check.cpp prints it)
+QC_QUALS, QC_GC_BINS, QC_TOTALS = 94, 101, 8
 
 
 class NormParams(_c.Structure):
@@ -311,6 +321,32 @@ class MergeParams(_c.Structure):
 
     def __init__(self, min_len=0, max_len=0, phred_offset=33, flags=0):
         super().__init__(min_len, max_len, phred_offset, flags)
+
+
+class QcParams(_c.Structure):
+    """sdt_qc_params; the defaults of `sdt-kmers qc`"""
+    _fields_ = [(f, _c.c_uint32) for f in ("cycles", "phred_offset", "flags", "class_sel", "reserved")]
+
+    def __init__(self, cycles=1024, phred_offset=33, flags=0, class_sel=0, reserved=0):
+        super().__init__(cycles, phred_offset, flags, class_sel, reserved)
+
+
+def qc_report_words(cycles: int) -> int:
+    """words of the report for `cycles` cycles: 203 + 99 (cycles + 1); 0 for cycles out of range (sdt_gpu_qc_report_words)"""
+    return int(load_library().sdt_gpu_qc_report_words(cycles))
+
+
+def qc_sections(report: np.ndarray, cycles: int) -> dict:
+    """the sections of a report as numpy VIEWS: totals[8], base[R][4], qual[R][94], len[R], gc[101], meanq[94]; R = cycles + 1"""
+    R = cycles + 1
+    assert report.dtype == np.uint64 and report.ndim == 1 and report.size >= QC_TOTALS + 99 * R + QC_GC_BINS + QC_QUALS
+    out, at = {}, 0
+    for name, shape in (("totals", (QC_TOTALS,)), ("base", (R, 4)), ("qual", (R, QC_QUALS)), ("len", (R,)), ("gc", (QC_GC_BINS,)),
+                        ("meanq", (QC_QUALS,))):
+        n = int(np.prod(shape))
+        out[name] = report[at: at + n].reshape(shape)
+        at += n
+    return out
 
 
 class AdapterSet(_c.Structure):
@@ -1140,6 +1176,42 @@ class PregraphGPU:
         self._check(self.lib.sdt_gpu_quality_reads_device(self._ctx, _ptr(d_quals), _ptr(d_offsets), nreads, ctypes.addressof(prm), _ptr(d_out),
                                                           _ptr(d_keep), ctypes.byref(kept)))
         return kept.value
+
+    # -- the per-cycle QC report of a batch: histograms that the call ADDS to; needs no counted table (the rule: include/sdt_gpu.h)
+    @staticmethod
+    def _qc_params(params):
+        """params: QcParams or its fields as a dict"""
+        return params if isinstance(params, QcParams) else QcParams(**(params or {}))
+
+    def qc_reads(self, words, offsets, quals=None, ranges=None, classes=None, params=None, report: np.ndarray = None, nbytes: int = None):
+        """a host batch; quals (optional) one byte per base under offsets, ranges (optional) 24-byte records with start and len where
+        READ_TRIM_DTYPE has them, classes (optional) uint8[nreads] -> the report (uint64), which the call ADDS to (a new one is zero)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        prm = self._qc_params(params)
+        if quals is not None:
+            quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        if ranges is not None:
+            ranges = np.ascontiguousarray(ranges)
+            assert ranges.dtype.itemsize == 24 and len(ranges) == n
+        if classes is not None:
+            classes = np.ascontiguousarray(classes, dtype=np.uint8)
+            assert len(classes) == n
+        if report is None:
+            report = np.zeros(max(qc_report_words(prm.cycles), 1), dtype=np.uint64)
+        assert report.dtype == np.uint64 and report.flags.c_contiguous
+        nb = (quals.size if quals is not None else 0) if nbytes is None else nbytes
+        self._check(self.lib.sdt_gpu_qc_reads(self._ctx, _ptr(words), words.size, _ptr(quals), nb, _ptr(offsets), n, _ptr(ranges), _ptr(classes),
+                                              ctypes.addressof(prm), _ptr(report), report.size))
+        return report
+
+    def qc_reads_device(self, d_words, d_offsets, nreads: int, d_report, d_quals=None, d_ranges=None, d_classes=None, params=None):
+        """device buffers; d_quals (optional) 4-byte aligned, d_ranges (optional) nreads records of 24 bytes, d_classes (optional) nreads
+        bytes, d_report 8-byte aligned uint64 words that the call ADDS to (waits for the kernel)"""
+        prm = self._qc_params(params)
+        self._check(self.lib.sdt_gpu_qc_reads_device(self._ctx, _ptr(d_words), _ptr(d_quals), _ptr(d_offsets), nreads, _ptr(d_ranges),
+                                                     _ptr(d_classes), ctypes.addressof(prm), _ptr(d_report)))
 
     # -- the mates of an overlapping pair merged into one fragment read by their overlap records; qualities through a compaction (the
     # rule: include/sdt_gpu.h)

@@ -90,6 +90,12 @@
  *       prefix.merge.fa: the merged fragments, one record per merged pair, > the first mate's ordinal + 1
  *       prefix.merge.pairs.fa / prefix.merge.single.fa: the kept bases of the reads that did not merge, as overlap writes them
  *       prefix.insertHist: as overlap writes it
+ *   sdt-kmers qc -s lib.cfg -K k [-p threads] [--cycles C, default 1024] [--phred 33|64, default 33] [--from-end] -o prefix
+ *       the per-cycle QC report of the libraries as they stream: base composition and qualities by cycle, read lengths, GC and mean
+ *       quality, by class of reads (0 single reads, 1 first mates, 2 second mates).  One sdt_gpu_qc_reads per batch into the report of
+ *       the batch's class (the rule: include/sdt_gpu.h); nothing is counted or kept.  FASTQ and FASTA libraries alike: the quality
+ *       outputs say which class came without qualities (qcsplit.c, which documents the three files)
+ *       prefix.qcBases / prefix.qcQuals / prefix.qcReads, and one line per class on stdout
  *
  * The query file is read and checked before the device is touched.
  *
@@ -116,6 +122,7 @@
 #include "qualsplit.h"
 #include "screensplit.h"
 #include "mergesplit.h"
+#include "qcsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -245,6 +252,21 @@ static void usage(void)
 	        "              prefix.merge.single.fa (every other surviving read), prefix.insertHist (as overlap writes it)\n"
 	        "           and one line: merge: reads R pairs P overlapping V merged M mismatch columns C bases in I bases out O\n"
 	        "           Pairs are the reads of q1=/q2= and f1=/f2= files; a library without pairs is allowed: nothing merges.\n"
+	        "       sdt-kmers qc -s lib.cfg -K k [-p threads] [--cycles C, default 1024] [--phred 33|64, default 33] [--from-end] -o prefix\n"
+	        "           what the parameters of the other stages act on, before or after any of them: per cycle (the position of a base in\n"
+	        "           its read, from 0; --from-end: counted from the read's last base) the base composition and the qualities, per read\n"
+	        "           its length, its GC content and its mean quality; by class of reads: 0 single reads, 1 first mates, 2 second mates\n"
+	        "           (the reads of q1=/q2= and f1=/f2= files).  Row C, written as C+, takes everything past the C-th cycle (C from 1 to\n"
+	        "           4096).  FASTQ and FASTA libraries alike; -K is only the k of the context.  Nothing is counted, kept or changed.\n"
+	        "           A record whose quality line is not as long as its sequence line stops the run before a file is written.\n"
+	        "           -> prefix.qcBases (# class row reads A C T G: per class and row that has a base; reads = the reads that reach the\n"
+	        "              row, in row C+ the bases past it), prefix.qcQuals (# class row bases mean_x100 min q10 q25 median q75 q90 max: per\n"
+	        "              class and row; mean_x100 = floor(100 * mean quality); the percentile at p = the smallest quality whose cumulative\n"
+	        "              count reaches ceil(p * bases / 100); a class without qualities has the one line: # class K: no qualities),\n"
+	        "              prefix.qcReads (# hist class bin reads: the histograms len, gc and meanq, only the bins that hold a read; len =\n"
+	        "              min(bases, C), bin C written as C+; gc = floor of the percentage of C and G; meanq = floor of the mean quality)\n"
+	        "           and one line per class: qc: class K reads R empty E bases B gc G q20 X q30 Y (G, X, Y in hundredths of a percent:\n"
+	        "           the share of C and G, of the bases of quality 20 and more, of 30 and more; - without qualities)\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -315,6 +337,7 @@ typedef struct {
 	sdt_complexity_params cx;
 	int max_low_given;
 	sdt_quality_params qual;
+	sdt_qc_params qc;
 	sdt_screen_params screen;
 	uint32_t screen_k;
 	char *rfile[MAX_REF_FILES];
@@ -1046,6 +1069,83 @@ static int run_qtrim(sdt_ctx *gpu, unsigned long long reads, options *opt, const
 	return 0;
 }
 
+/* ---- qc ------------------------------------------------------------------------------------------------------------------------------ */
+
+/* while the reads stream: every batch through sdt_gpu_qc_reads into the host report of its class.  A batch of a pair of files takes
+ * every second ordinal (ord_stride 2), the first ordinal of a pair in the read-1 file: the rule by which sdt_pair_ranges_note makes
+ * the pair ranges; every other batch holds single reads.  So the class bytes of a batch are all the same, and one call covers it */
+typedef struct {
+	sdt_ctx *gpu;
+	sdt_qc_params prm;
+	uint64_t words, reads;
+	uint64_t *report[SDT_QC_CLASSES], with_quals[SDT_QC_CLASSES];
+	uint8_t *classes;
+	uint64_t classes_cap;
+} qc_state;
+
+static int qc_batch(void *user, const sdt_batch *b, uint64_t ord_base, uint64_t ord_stride)
+{
+	qc_state *q = (qc_state *)user;
+	if (b->qual_faults) {
+		fprintf(stderr, "sdt-kmers: %llu records of the batch at read %llu have a quality line that is not as long as their sequence line\n",
+		        (unsigned long long)b->qual_faults, (unsigned long long)ord_base + 1);
+		return -1;
+	}
+	q->reads += b->nreads;
+	if (!b->nreads) return 0;
+	const int k = ord_stride == 2 ? 1 + (b->stream_parity & 1) : 0;
+	if (b->nreads > q->classes_cap) {
+		free(q->classes);
+		q->classes = (uint8_t *)malloc(b->nreads);
+		q->classes_cap = q->classes ? b->nreads : 0;
+	}
+	if (!q->report[k]) q->report[k] = (uint64_t *)calloc(q->words, sizeof(uint64_t));
+	if (!q->classes || !q->report[k]) { fprintf(stderr, "sdt-kmers: out of memory for the report\n"); return -1; }
+	memset(q->classes, k, b->nreads);
+	q->prm.class_sel = (uint32_t)k;
+	if (SDT_CALL(sdt_gpu_qc_reads, q->gpu, b->words, b->nwords, b->quals, b->quals ? b->offsets[b->nreads] : 0, b->offsets, b->nreads, NULL, q->classes,
+	             &q->prm, q->report[k], q->words)) return -1;
+	if (b->quals) q->with_quals[k] += b->nreads;
+	return 0;
+}
+
+/* `qc`: the libraries streamed once with their qualities, then the three files (qcsplit.c) and a line per class */
+static int run_qc(options *opt, const sdt_cfg *cfg)
+{
+	static qc_state q;
+	q.prm = opt->qc;
+	q.words = sdt_gpu_qc_report_words(opt->qc.cycles);
+	if (q.words != sdt_qc_words(opt->qc.cycles)) { fprintf(stderr, "sdt-kmers: the library's report has %llu words\n", (unsigned long long)q.words); return 1; }
+	if (SDT_CALL(sdt_gpu_init, &q.gpu, opt->device, opt->K, 1, 0)) return 1;
+	const int max_read_len = cfg->max_rd_len ? cfg->max_rd_len : 100;
+	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
+	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : opt->threads;
+	sdt_read_quals(1);
+	const int rc = sdt_stream_reads(cfg, max_read_len, parse_threads > 0 ? parse_threads : 1, chunk, 0, qc_batch, &q, NULL);
+	sdt_read_quals(0);
+	sdt_gpu_destroy(q.gpu);
+	if (rc != 0) return 1;
+	sdt_qc_class cls[SDT_QC_CLASSES];
+	for (int k = 0; k < SDT_QC_CLASSES; k++) { cls[k].report = q.report[k]; cls[k].with_quals = q.with_quals[k]; }
+	static int (*const writers[3])(FILE *, const sdt_qc_class *, uint32_t) = {sdt_qc_bases_write, sdt_qc_quals_write, sdt_qc_reads_write};
+	static const char *const suffix[3] = {".qcBases", ".qcQuals", ".qcReads"};
+	for (int i = 0; i < 3; i++) {
+		char path[4200];
+		FILE *f = stats_open(path, opt->outname, suffix[i]);
+		if (!f || (writers[i](f, cls, opt->qc.cycles) != 0) | (fclose(f) != 0)) return cannot_write(path);
+	}
+	printf("%llu reads\n", (unsigned long long)q.reads);
+	for (int k = 0; k < SDT_QC_CLASSES; k++) {
+		char line[SDT_QC_LINE_MAX];
+		if (!cls[k].report) continue;
+		sdt_qc_summary(line, k, &cls[k], opt->qc.cycles);
+		fputs(line, stdout);
+		free(q.report[k]);
+	}
+	free(q.classes);
+	return 0;
+}
+
 /* ---- profile and query ----------------------------------------------------------------------------------------------------------------- */
 
 /* prefix.readCov: "kmers found solid min median max" per read */
@@ -1149,7 +1249,7 @@ static int run_query(sdt_ctx *gpu, unsigned long long reads, options *opt, const
 }
 
 /* ---- the command line ------------------------------------------------------------------------------------------------------------------ */
-enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, N_SUBCOMMANDS };
+enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, N_SUBCOMMANDS };
 
 static const struct {
 	const char *name;
@@ -1163,11 +1263,12 @@ static const struct {
 	[CLIP] = {"clip", 1, 1, 0, run_clip},                [OVERLAP] = {"overlap", 1, 1, 0, run_overlap},
 	[COMPLEXITY] = {"complexity", 1, 1, 0, run_complexity}, [QTRIM] = {"qtrim", 1, 1, 0, run_qtrim},
 	[SCREEN] = {"screen", 1, 1, 0, run_screen},             [MERGE] = {"merge", 1, 1, 0, run_merge},
+	[QC] = {"qc", 0, 0, 0, NULL},                           /* (streams on its own and counts nothing: run_qc, from main) */
 };
 
 enum { O_MAX_K = 1000, O_DEVICE, O_TARGET, O_MAX_CV, O_SEED, O_MIN_COV, O_MIN_LEN, O_CORRECT, O_MATE_SWAP, O_TAIL3, O_TAIL5, O_MIN_OVERLAP, O_ERROR_PCT,
        O_MIN_TAIL, O_TAIL_ERROR_PCT, O_MAX_ERR, O_MAX_SCORE, O_MAX_LOW, O_TRIM_LOW, O_PHRED, O_CUT_Q, O_LOW_Q, O_MAX_LOW_BASES, O_MAX_EE, O_SCREEN_K,
-       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED };
+       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED, O_CYCLES, O_FROM_END };
 
 /* the options that belong to some subcommands only: the name as it is printed, who may be given it, what the refusal says after
  * "belongs to" (kept, not derived: --min-overlap names clip alone), and the most its value may be where it takes a whole number */
@@ -1183,12 +1284,13 @@ static const struct { int code; const char *name; unsigned owners; const char *b
 	{O_MAX_ERR, "--max-err", BIT(OVERLAP) | BIT(MERGE), "overlap", 100},
 	{O_MAX_SCORE, "--max-score", BIT(COMPLEXITY), "complexity", 100}, {O_MAX_LOW, "--max-low", BIT(COMPLEXITY), "complexity", 100},
 	{O_TRIM_LOW, "--trim-low", BIT(COMPLEXITY), "complexity", 0},
-	{O_PHRED, "--phred", BIT(QTRIM), "qtrim", 64}, {O_CUT_Q, "--cut-q", BIT(QTRIM), "qtrim", 93}, {O_LOW_Q, "--low-q", BIT(QTRIM), "qtrim", 93},
+	{O_PHRED, "--phred", BIT(QTRIM) | BIT(QC), "qtrim", 64}, {O_CUT_Q, "--cut-q", BIT(QTRIM), "qtrim", 93}, {O_LOW_Q, "--low-q", BIT(QTRIM), "qtrim", 93},
 	{O_MAX_LOW_BASES, "--max-low-bases", BIT(QTRIM), "qtrim", 100}, {O_MAX_EE, "--max-ee", BIT(QTRIM), "qtrim", UINT32_MAX},
 	{'r', "-r", BIT(SCREEN), "screen", 0}, {O_SCREEN_K, "--screen-k", BIT(SCREEN), "screen", 31}, {O_MIN_HITS, "--min-hits", BIT(SCREEN), "screen", UINT32_MAX},
 	{O_MIN_HIT_PCT, "--min-hit-pct", BIT(SCREEN), "screen", 100}, {O_KEEP_MATCHED, "--keep-matched", BIT(SCREEN), "screen", 0},
 	{O_MATE_SWAP, "--mate-swap", BIT(DEDUP), "dedup", 0},
 	{O_MIN_MERGED, "--min-merged", BIT(MERGE), "merge", UINT32_MAX}, {O_MAX_MERGED, "--max-merged", BIT(MERGE), "merge", UINT32_MAX},
+	{O_CYCLES, "--cycles", BIT(QC), "qc", SDT_QC_MAX_CYCLES}, {O_FROM_END, "--from-end", BIT(QC), "qc", 0},
 };
 
 /* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
@@ -1233,6 +1335,7 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 	                                   {"screen-k", required_argument, 0, O_SCREEN_K}, {"min-hits", required_argument, 0, O_MIN_HITS},
 	                                   {"min-hit-pct", required_argument, 0, O_MIN_HIT_PCT}, {"keep-matched", no_argument, 0, O_KEEP_MATCHED},
 	                                   {"min-merged", required_argument, 0, O_MIN_MERGED}, {"max-merged", required_argument, 0, O_MAX_MERGED},
+	                                   {"cycles", required_argument, 0, O_CYCLES}, {"from-end", no_argument, 0, O_FROM_END},
 	                                   {0, 0, 0, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:r:", longopts, NULL)) != -1) {
@@ -1284,7 +1387,7 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 		case O_TRIM_LOW: opt->cx.flags |= SDT_COMPLEXITY_TRIM; break;
 		case O_PHRED:
 			if (v != 33 && v != 64) { fprintf(stderr, "sdt-kmers: --phred %llu: 33 or 64\n", v); return 255; }
-			opt->qual.phred_offset = (uint32_t)v;
+			opt->qual.phred_offset = opt->qc.phred_offset = (uint32_t)v;
 			break;
 		case O_CUT_Q: opt->qual.cut_q = (uint32_t)v; break;
 		case O_LOW_Q: opt->qual.low_q = (uint32_t)v; break;
@@ -1303,6 +1406,11 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 		case O_KEEP_MATCHED: opt->screen.flags |= SDT_SCREEN_KEEP_MATCHED; break;
 		case O_MIN_MERGED: opt->merge.min_len = (uint32_t)v; break;
 		case O_MAX_MERGED: opt->merge.max_len = (uint32_t)v; break;
+		case O_CYCLES:
+			if (v == 0) { fprintf(stderr, "sdt-kmers: --cycles must be at least 1\n"); return 255; }
+			opt->qc.cycles = (uint32_t)v;
+			break;
+		case O_FROM_END: opt->qc.flags |= SDT_QC_FROM_END; break;
 		default: usage(); return 255;
 		}
 	}
@@ -1408,12 +1516,17 @@ int main(int argc, char **argv)
 	static options opt = {.K = 23, .threads = 8,
 	                      .norm = {50, 10000, 0}, .clip = {5, 10, 0, 10, 20, 0, 0, 0}, .overlap = {30, 10, 0, 0}, .cx = {10, 50, 0, 0},
 	                      .qual = {33, 20, 15, 40, 0, 0, 0, 0}, .screen = {1, 0, 0, 0}, .merge = {0, 0, 33, 0},
-	                      .screen_k = 31};                                   /* bbduk's usual figure: a choice, not a measurement */
+	                      .qc = {1024, 33, 0, 0, 0}, .screen_k = 31};                                   /* bbduk's usual figure: a choice, not a measurement */
 	opt.min_count = subcommands[sub].min_count;
 	sdt_cfg cfg;
 	int rc = parse_options(argc - 1, argv + 1, sub, &opt);
 	if (rc == 0) rc = load_inputs(sub, &opt, &cfg);
 	if (rc != 0) return rc;
+	if (sub == QC) {
+		rc = run_qc(&opt, &cfg);
+		sdt_cfg_free(&cfg);
+		return rc;
+	}
 
 	sdt_ctx *gpu = NULL;
 	if (SDT_CALL(sdt_gpu_init, &gpu, opt.device, opt.K, 0, subcommands[sub].keep_reads ? SDT_FLAG_KEEP_READS : 0u)) return 1;

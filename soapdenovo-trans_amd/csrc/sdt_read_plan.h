@@ -5,7 +5,8 @@
 // sanitizers.  The six stages that need no table have theirs here too: the duplicate filter (sdt_dedup.hip), the adapter and tail
 // clipping (sdt_clip.hip), the mate overlap (sdt_overlap.hip), the low-complexity filter (sdt_complexity.hip), the reference screen
 // (sdt_screen.hip) and the quality trim (sdt_quality.hip), which also has its cut of a byte stream into pieces here.  The merge of
-// overlapping mates (sdt_merge.hip) has its refusals and the decision of a pair here.  No HIP in here.
+// overlapping mates (sdt_merge.hip) has its refusals and the decision of a pair here, the QC report (sdt_qc.hip) its refusals, the
+// layout of the report and its grid.  No HIP in here.
 #pragma once
 #include <stdint.h>
 
@@ -510,6 +511,55 @@ inline BytePiece next_byte_piece(const uint64_t *offsets, uint64_t nreads, uint6
 	BytePiece p = {r0 + lo, offsets[r0] & ~3ULL, 0};
 	p.nbytes = offsets[p.r1] - p.b0;
 	return p;
+}
+
+// ---- the per-cycle QC report (sdt_qc.hip): what is refused before any launch, the layout of the report, and the grid ----
+// (tools/qc_plan_check.cpp runs the check on every field and holds the layout to the table of include/sdt_gpu.h)
+struct QcParams {                                        // == sdt_qc_params of include/sdt_gpu.h
+	uint32_t cycles, phred_offset, flags, class_sel, reserved;
+};
+constexpr uint32_t QC_MAX_CYCLES = 4096;                 // SDT_QC_MAX_CYCLES
+constexpr uint32_t QC_FROM_END = 1u;                     // SDT_QC_FROM_END
+constexpr uint32_t QC_QUALS = QUALITY_MAX_Q + 1;         // the qualities a base can have: 0 .. 93
+constexpr uint32_t QC_GC_BINS = 101;                     // 0 .. 100 percent
+constexpr uint32_t QC_TOTALS = 8;
+
+enum QcFault { QC_OK = 0, QC_CYCLES, QC_PHRED_OFFSET, QC_FLAGS, QC_CLASS_SEL, QC_RESERVED };
+
+// the first field that is refused, in the order of the rules in include/sdt_gpu.h
+inline QcFault check_qc_params(const QcParams &p)
+{
+	if (p.cycles == 0 || p.cycles > QC_MAX_CYCLES) return QC_CYCLES;
+	if (p.phred_offset != 0 && p.phred_offset != 33 && p.phred_offset != 64) return QC_PHRED_OFFSET;
+	if (p.flags & ~QC_FROM_END) return QC_FLAGS;
+	if (p.class_sel > 255) return QC_CLASS_SEL;
+	if (p.reserved != 0) return QC_RESERVED;
+	return QC_OK;
+}
+
+// where the sections of the report start, in 64-bit words, for C cycles (R = C + 1 rows); words = 203 + 99 R
+struct QcLayout {
+	uint64_t rows, totals, base, qual, len, gc, meanq, words;
+};
+constexpr QcLayout qc_layout(uint32_t cycles)
+{
+	const uint64_t R = (uint64_t)cycles + 1;
+	return QcLayout{R, 0, QC_TOTALS, QC_TOTALS + 4 * R, QC_TOTALS + 4 * R + QC_QUALS * R, QC_TOTALS + 4 * R + QC_QUALS * R + R,
+	                QC_TOTALS + 4 * R + QC_QUALS * R + R + QC_GC_BINS, QC_TOTALS + 4 * R + QC_QUALS * R + R + QC_GC_BINS + QC_QUALS};
+}
+constexpr uint64_t qc_report_words(uint32_t cycles) { return cycles == 0 || cycles > QC_MAX_CYCLES ? 0 : qc_layout(cycles).words; }
+static_assert(qc_layout(1).words == 203 + 99 * 2 && qc_layout(4096).words == 203 + 99 * 4097, "203 + 99 R");
+
+// The QC kernel's workgroups: QC_WAVES wavefronts take a read each and stride over the rest, all of them counting into the one set
+// of LDS histograms of their workgroup.  Every workgroup flushes its whole tile once per pass, so there are at most two per CU: the
+// flush volume goes with the workgroups, not with the reads.  forced != 0 (SDT_WAVE_BLOCKS) puts that many in the place of the cap.
+constexpr int QC_WAVES = 16;
+// Rows of the LDS tile.  152 puts reads of 150 and 151 bases, the usual ones, through in ONE pass over the batch; the tile, len[4097], gc,
+// meanq and row C are then 78 152 bytes of LDS, above the 64 KiB of the other kernels, and still two workgroups per CU (160 KiB).
+constexpr int QC_TILE = 152;
+constexpr uint32_t qc_blocks(uint64_t nreads, int cu_count, uint64_t forced)
+{
+	return wave_blocks(nreads, QC_WAVES, cu_count, forced ? forced : (uint64_t)(cu_count > 0 ? cu_count : 1) * 2);
 }
 
 } // namespace sdt
