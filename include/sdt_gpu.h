@@ -1068,7 +1068,52 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  *     host form         the piece of the stream that is staged with its offsets, its quality bytes, 24 B + 1 B per read of it for
  *                       ranges and classes where given, and a report-sized buffer (8 B x (203 + 99 R), 3.2 MB at most)
  * Out of scope: a kept form (the reads kept in HBM carry no qualities); duplication levels (dedup has them); adapter content (clip has
- * it); over-represented sequences; per-tile statistics; HTML or plots; any change to another stage or to the parser. */
+ * it); over-represented sequences; per-tile statistics; HTML or plots; any change to another stage or to the parser.
+ *
+ * An assembly scored against the counted table.  search_kmers answers k-mer -> count and profile_reads reads -> coverage; this is the
+ * other direction: which nodes of the table does a set of sequences (contigs, transcripts, scaffolds cut at their N runs) cover, and
+ * how often -- what KAT comp / spectra-cn and Merqury compute: how much of the reads' solid k-mer content the assembly holds
+ * (completeness), how much of the assembly has no read support (errors, chimeric junctions, a consensus QV), and how many times the
+ * assembly holds each read k-mer (collapsed or duplicated isoforms).  Needs the counted table, and writes nothing to it.  Added
+ * without a change of SDT_ABI_VERSION: the five calls, the two structs and the two constants are additions.
+ *     Integers only.  Everything is exact and does not depend on the order of the sequences, on how they are split over adds or
+ *     pieces, on where a sequence starts in its word, or on the launch geometry.
+ *     An ASSEMBLY is a set of sequences packed as for sdt_gpu_push_reads (words, offsets[nseqs + 1] in bases), of any length.
+ *     A sequence of L bases has n = L - K + 1 k-mers (0 for L < K).  k-mer j has the count c[j] that profile_reads sees: the
+ *     canonical k-mer looked up, the 32-bit count with its high half, absent = 0, the deleted flag ignored.  k-mer j is WEAK iff
+ *     c[j] < max(min_count, 1).  A GAP is a maximal run of weak k-mers.
+ *     RECORD, per sequence (sdt_seq_support, 32 bytes):
+ *         kmers  n                            found   the j with a node               solid  the j that are not weak
+ *         sum    the sum of c[j], 64 bits     gaps    the number of gaps
+ *         longest_gap  the length of the longest gap, 0 if none
+ *         longest_at   its first k-mer, the first among equals; kmers if there is none
+ *     L < K: kmers = 0, longest_at = 0, every other field 0.
+ *     COPY NUMBER.  Per node of the table cn is kept: the k-mer occurrences in all sequences added since asm_begin whose canonical
+ *     form is that node, saturating at 255.  Both strands feed the same node; a palindrome of even K counts once per occurrence.
+ *     SPECTRUM.  A matrix of rows x SDT_ASM_CN_COLS uint64_t: m[r][c] = the occupied slots with min(count, rows - 1) = r and
+ *     min(cn, 7) = c.  Row 0 holds whatever nodes have a count of 0; none is special-cased, and deleted nodes are counted like others.
+ *     TOTALS, uint64_t[4], kept on the device over all adds: sequences, k-mers, found, solid.
+ *   asm_begin:      allocates one byte per table slot (rounded up to 4), owned by the context, and zeroes it and the totals; params
+ *                   are kept for the adds and the spectrum.  A second begin starts over.
+ *   asm_add:        a host batch, staged in pieces as for profile_reads; out NULL: tally only, else nseqs records.  Waits.
+ *   asm_add_device: buffers already on the device; d_out NULL or nseqs records of 32 bytes, 8-byte aligned.  Asynchronous on the
+ *                   context's stream.  A sequence has fewer than 2^32 bases (the host form checks it).
+ *   asm_spectrum:   any number of times between adds; matrix (rows x 8, as given to asm_begin) and totals, either may be NULL, not
+ *                   both.  Waits.
+ *   asm_end:        frees the tally (sdt_gpu_destroy does too).  Without a begin: SDT_OK.
+ * There is NO limit on the length of a sequence in either form: a wavefront walks a sequence 64 k-mer positions at a time and keeps
+ * no count of it but the record's sums, where profile_reads holds a sequence's counts in LDS (16 384 k-mers at most).
+ * nseqs == 0: SDT_OK, nothing touched, whatever the rest says.
+ * SDT_ESTATE: asm_begin under the state rules of search_kmers, with its messages (a SDT_FLAG_CONTIG_INDEX context, a shard, after
+ * load_paths / import_paths, a released table, batches pushed and not drained); asm_add and asm_spectrum without a begin, after
+ * asm_end, and once the table has changed since asm_begin (counted into, grown, reset, imported, released, path words loaded):
+ * "the table changed since sdt_gpu_asm_begin" -- a tally is by slot and is never read against another table.
+ * SDT_EINVAL, before any launch: NULL params; rows < 2 or > SDT_ASM_MAX_ROWS; flags or reserved not 0; offsets not monotonic or
+ * nwords too short (as for reads); a sequence of 2^32 bases or more (host form); d_out not 8-byte aligned (device form).
+ * Device memory: from asm_begin to asm_end one byte per table slot and 64 KiB for totals and matrix, SDT_ENOMEM when it does not fit;
+ * the host form of asm_add also the staged piece with its offsets and 32 B per sequence of it.
+ * Out of scope: distinct counting of assembly-only k-mers (they show as kmers - found, by occurrence); a k other than the table's K;
+ * sharded contexts (refused); a kept-read form; plots; any change to profile_reads or its limit. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -1103,6 +1148,10 @@ typedef struct { uint32_t min_len, max_len, phred_offset, flags; } sdt_merge_par
 #define SDT_QC_MAX_CYCLES 4096
 #define SDT_QC_FROM_END   1u    /* sdt_qc_params.flags: rows count from the last counted base of a read */
 typedef struct { uint32_t cycles, phred_offset, flags, class_sel, reserved; } sdt_qc_params;
+#define SDT_ASM_CN_COLS  8      /* columns of the spectrum: assembly copy number 0 .. 6, and 7 and more */
+#define SDT_ASM_MAX_ROWS 1024
+typedef struct { uint64_t sum; uint32_t kmers, found, solid, gaps, longest_gap, longest_at; } sdt_seq_support;   /* 32 bytes */
+typedef struct { uint32_t min_count, rows, flags, reserved; } sdt_asm_params;   /* flags, reserved: 0 */
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -1222,6 +1271,12 @@ int sdt_gpu_qc_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords
 int sdt_gpu_qc_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_quals, const void *d_offsets,
                             uint64_t nreads, const void *d_ranges, const void *d_classes, const sdt_qc_params *params,
                             void *d_report);
+int sdt_gpu_asm_begin(sdt_ctx *ctx, const sdt_asm_params *params);
+int sdt_gpu_asm_add(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets, uint64_t nseqs,
+                    sdt_seq_support *out);
+int sdt_gpu_asm_add_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nseqs, void *d_out);
+int sdt_gpu_asm_spectrum(sdt_ctx *ctx, uint64_t *matrix, uint64_t totals[4]);
+int sdt_gpu_asm_end(sdt_ctx *ctx);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

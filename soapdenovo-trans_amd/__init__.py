@@ -206,6 +206,11 @@ _ABI = [
                                     _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64]),
     ("sdt_gpu_qc_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
                                            _c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_asm_begin", _c.c_int, [_c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_asm_add", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
+    ("sdt_gpu_asm_add_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
+    ("sdt_gpu_asm_spectrum", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_asm_end", _c.c_int, [_c.c_void_p]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -260,6 +265,10 @@ QC_MAX_CYCLES = 4096                                     # SDT_QC_MAX_CYCLES
 QC_FROM_END = 1                                          # SDT_QC_FROM_END
 QC_TILE = 152                                            # rows of the kernel's LDS tile (csrc/sdt_read_plan.h: QC_TILE; tools/qc_plan_check.cpp prints it)
 QC_QUALS, QC_GC_BINS, QC_TOTALS = 94, 101, 8
+# sdt_seq_support (include/sdt_gpu.h): one record of 32 bytes per sequence of an assembly scored against the counted table; sum = the
+# sum of its k-mers' counts, a gap = a maximal run of weak k-mers, longest_at = the first k-mer of the longest (kmers: none)
+SEQ_SUPPORT_DTYPE = np.dtype([("sum", np.uint64)] + [(f, np.uint32) for f in ("kmers", "found", "solid", "gaps", "longest_gap", "longest_at")])
+ASM_CN_COLS, ASM_MAX_ROWS = 8, 1024                      # SDT_ASM_CN_COLS, SDT_ASM_MAX_ROWS
 
 
 class NormParams(_c.Structure):
@@ -329,6 +338,14 @@ class QcParams(_c.Structure):
 
     def __init__(self, cycles=1024, phred_offset=33, flags=0, class_sel=0, reserved=0):
         super().__init__(cycles, phred_offset, flags, class_sel, reserved)
+
+
+class AsmParams(_c.Structure):
+    """sdt_asm_params; the defaults of `sdt-kmers evaluate`"""
+    _fields_ = [(f, _c.c_uint32) for f in ("min_count", "rows", "flags", "reserved")]
+
+    def __init__(self, min_count=2, rows=256, flags=0, reserved=0):
+        super().__init__(min_count, rows, flags, reserved)
 
 
 def qc_report_words(cycles: int) -> int:
@@ -1212,6 +1229,38 @@ class PregraphGPU:
         prm = self._qc_params(params)
         self._check(self.lib.sdt_gpu_qc_reads_device(self._ctx, _ptr(d_words), _ptr(d_quals), _ptr(d_offsets), nreads, _ptr(d_ranges),
                                                      _ptr(d_classes), ctypes.addressof(prm), _ptr(d_report)))
+
+    # -- an assembly scored against the counted table: a record per sequence, a copy number per node, the spectrum (the rule:
+    # include/sdt_gpu.h).  Nothing is written to the table; the tally lives from asm_begin to asm_end
+    def asm_begin(self, params=None):
+        """params: AsmParams or its fields as a dict; zeroes the tally (one byte per table slot) and the totals"""
+        prm = params if isinstance(params, AsmParams) else AsmParams(**(params or {}))
+        self._check(self.lib.sdt_gpu_asm_begin(self._ctx, ctypes.addressof(prm)))
+        self._asm_rows = prm.rows
+
+    def asm_add(self, words, offsets, records: bool = True):
+        """a host batch of sequences of any length -> SEQ_SUPPORT_DTYPE[nseqs], or None with records=False (tally only)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        out = np.zeros(n, dtype=SEQ_SUPPORT_DTYPE) if records else None
+        self._check(self.lib.sdt_gpu_asm_add(self._ctx, _ptr(words), words.size, _ptr(offsets), n, _ptr(out)))
+        return out
+
+    def asm_add_device(self, d_words, d_offsets, nseqs: int, d_out=None):
+        """device buffers; d_out None or nseqs records of 32 bytes; asynchronous on the context's stream"""
+        self._check(self.lib.sdt_gpu_asm_add_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nseqs, _ptr(d_out)))
+
+    def asm_spectrum(self):
+        """-> (matrix uint64[rows, ASM_CN_COLS]: occupied slots by min(count, rows - 1) and min(copy number, 7); totals uint64[4]:
+        sequences, k-mers, found, solid over all adds since asm_begin)"""
+        matrix = np.zeros((getattr(self, "_asm_rows", ASM_MAX_ROWS), ASM_CN_COLS), dtype=np.uint64)
+        totals = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_asm_spectrum(self._ctx, _ptr(matrix), _ptr(totals)))
+        return matrix, totals
+
+    def asm_end(self):
+        self._check(self.lib.sdt_gpu_asm_end(self._ctx))
 
     # -- the mates of an overlapping pair merged into one fragment read by their overlap records; qualities through a compaction (the
     # rule: include/sdt_gpu.h)

@@ -16,20 +16,22 @@ static int grow(void **p, uint64_t *cap, uint64_t need, size_t elem)
 	return 0;
 }
 
-/* the open segment [from, s->ncodes) of reference ref becomes a sequence, unless it is empty */
-static int close_segment(sdt_ref_set *s, uint64_t from, uint32_t ref)
+/* the open segment [from, s->ncodes) of reference ref, which starts at letter `at` of its record, becomes a sequence, unless it is empty */
+static int close_segment(sdt_ref_set *s, uint64_t from, uint32_t ref, uint64_t at)
 {
 	if (from == s->ncodes) return 0;
 	uint64_t cap = s->seqs_cap;
 	/* offsets holds one more than ref_of_seq: both grow to the same capacity + 1 */
 	if (s->nseqs + 1 > s->seqs_cap) {
-		uint64_t ocap = s->seqs_cap ? s->seqs_cap + 1 : 0;
+		uint64_t ocap = s->seqs_cap ? s->seqs_cap + 1 : 0, scap = s->seqs_cap;
 		if (grow((void **)&s->ref_of_seq, &cap, s->nseqs + 1, sizeof(uint32_t)) != 0) return -1;
+		if (grow((void **)&s->seg_start, &scap, cap, sizeof(uint64_t)) != 0) return -1;
 		if (grow((void **)&s->offsets, &ocap, cap + 1, sizeof(uint64_t)) != 0) return -1;
 		s->seqs_cap = cap;
 	}
 	s->offsets[s->nseqs] = from;
 	s->offsets[s->nseqs + 1] = s->ncodes;
+	s->seg_start[s->nseqs] = at;
 	s->ref_of_seq[s->nseqs++] = ref;
 	return 0;
 }
@@ -38,12 +40,12 @@ int sdt_refs_parse(sdt_ref_set *s, const char *label, const char *text, size_t n
 {
 	unsigned long long line = 1, header_line = 0;
 	int in_record = 0, seen = 0;                             /* a header was read; its record has a sequence character */
-	uint64_t from = s->ncodes;
+	uint64_t from = s->ncodes, letters = 0, from_at = 0;     /* letters of the record so far; the open segment starts at from_at */
 	size_t i = 0;
 	while (i < n) {
 		if (text[i] == '>') {
 			if (in_record && !seen) { snprintf(err, errcap, "%s line %llu: the record has no sequence", label, header_line); return -1; }
-			if (in_record && close_segment(s, from, s->n_refs - 1) != 0) goto nomem;
+			if (in_record && close_segment(s, from, s->n_refs - 1, from_at) != 0) goto nomem;
 			size_t e = i + 1, b = i + 1;
 			while (e < n && text[e] != '\n') e++;
 			size_t ne = b;
@@ -62,6 +64,7 @@ int sdt_refs_parse(sdt_ref_set *s, const char *label, const char *text, size_t n
 			seen = 0;
 			header_line = line;
 			from = s->ncodes;
+			letters = from_at = 0;
 			i = e;                                               /* (at the newline, or at the end) */
 			continue;
 		}
@@ -78,9 +81,11 @@ int sdt_refs_parse(sdt_ref_set *s, const char *label, const char *text, size_t n
 		case 'G': case 'g': code = 3; break;
 		default: code = -1; break;
 		}
+		letters++;
 		if (code < 0) {                                          /* any other letter cuts the reference */
-			if (close_segment(s, from, s->n_refs - 1) != 0) goto nomem;
+			if (close_segment(s, from, s->n_refs - 1, from_at) != 0) goto nomem;
 			from = s->ncodes;
+			from_at = letters;
 			continue;
 		}
 		if (grow((void **)&s->codes, &s->codes_cap, s->ncodes + 1, 1) != 0) goto nomem;
@@ -88,7 +93,7 @@ int sdt_refs_parse(sdt_ref_set *s, const char *label, const char *text, size_t n
 		s->bases[s->n_refs - 1]++;
 	}
 	if (in_record && !seen) { snprintf(err, errcap, "%s line %llu: the record has no sequence", label, header_line); return -1; }
-	if (in_record && close_segment(s, from, s->n_refs - 1) != 0) goto nomem;
+	if (in_record && close_segment(s, from, s->n_refs - 1, from_at) != 0) goto nomem;
 	return 0;
 nomem:
 	snprintf(err, errcap, "%s: out of memory", label);
@@ -133,7 +138,7 @@ int sdt_refs_pack(sdt_ref_set *s)
 void sdt_refs_free(sdt_ref_set *s)
 {
 	for (uint32_t i = 0; i < s->n_refs; i++) free(s->names[i]);
-	free(s->names); free(s->bases); free(s->codes); free(s->offsets); free(s->ref_of_seq); free(s->words);
+	free(s->names); free(s->bases); free(s->codes); free(s->offsets); free(s->ref_of_seq); free(s->words); free(s->seg_start);
 	memset(s, 0, sizeof *s);
 }
 

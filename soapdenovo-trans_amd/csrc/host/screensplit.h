@@ -23,6 +23,7 @@ typedef struct {
 	uint32_t n_refs, refs_cap;
 	uint32_t *words;                /* sdt_refs_pack */
 	uint64_t nwords;
+	uint64_t *seg_start;            /* per segment: where it starts inside its reference, counting every letter of the record (0-based) */
 } sdt_ref_set;
 
 /* One FASTA text of n bytes appended to the set.  Letters in either case; wrapped lines are joined; blank lines, blanks and '\r' are

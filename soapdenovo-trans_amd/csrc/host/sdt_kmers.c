@@ -96,6 +96,15 @@
  *       the batch's class (the rule: include/sdt_gpu.h); nothing is counted or kept.  FASTQ and FASTA libraries alike: the quality
  *       outputs say which class came without qualities (qcsplit.c, which documents the three files)
  *       prefix.qcBases / prefix.qcQuals / prefix.qcReads, and one line per class on stdout
+ *   sdt-kmers evaluate -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] --assembly contigs.fa [--assembly more.fa ...]
+ *                      [--rows R, default 256] -o prefix
+ *       an assembly scored against the counted k-mers of the reads (sdt_gpu_asm_begin / _add / _spectrum; the rule: include/sdt_gpu.h):
+ *       how much of the reads' solid k-mer content it holds, how much of it has no read support, and how many times it holds each
+ *       read k-mer.  The assembly files are FASTA, read and checked before the device is touched; every letter outside ACGT cuts a
+ *       contig into segments, so the N runs of a scaffold never become k-mers (asmsplit.c folds the segments back)
+ *       prefix.asmSupport: per contig  index name bases kmers found solid sum gaps longest_gap longest_at
+ *       prefix.asmSpectrum: row c0 .. c7 for the rows of the copy-number spectrum that hold a node
+ *       and one line: evaluate: sequences S kmers N found F solid V nodes D solid_nodes E covered C completeness_x100 P qv_x100 Q
  *
  * The query file is read and checked before the device is touched.
  *
@@ -123,6 +132,7 @@
 #include "screensplit.h"
 #include "mergesplit.h"
 #include "qcsplit.h"
+#include "asmsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -267,6 +277,22 @@ static void usage(void)
 	        "              min(bases, C), bin C written as C+; gc = floor of the percentage of C and G; meanq = floor of the mean quality)\n"
 	        "           and one line per class: qc: class K reads R empty E bases B gc G q20 X q30 Y (G, X, Y in hundredths of a percent:\n"
 	        "           the share of C and G, of the bases of quality 20 and more, of 30 and more; - without qualities)\n"
+	        "       sdt-kmers evaluate -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] --assembly contigs.fa\n"
+	        "                          [--assembly more.fa ...] [--rows R, default 256] -o prefix\n"
+	        "           an assembly (FASTA files, any line wrapping; a letter other than ACGT cuts a contig, so a scaffold's N runs give no\n"
+	        "           k-mers) is scored against the counted k-mers of the reads.  A k-mer of the assembly is weak if the reads hold it\n"
+	        "           fewer than max(min_count, 1) times; a gap is a maximal run of weak k-mers: one wrong base makes a gap of K, a\n"
+	        "           chimeric junction one of K - 1.  Every node of the table gets the number of times the assembly holds it, either\n"
+	        "           strand, up to 255.  R from 2 to 1024, above min_count: row R - 1 takes every larger count.\n"
+	        "           -> prefix.asmSupport (per contig: index name bases kmers found solid sum gaps longest_gap longest_at; found = the\n"
+	        "              k-mers the reads hold at all, solid = those not weak, sum = the sum of the counts, longest_at = the first base of\n"
+	        "              the longest gap's first k-mer, 0-based in the contig, kmers if there is no gap), prefix.asmSpectrum (row c0 .. c7\n"
+	        "              for every row that holds a node: the nodes counted min(row, R - 1) times that the assembly holds 0, 1, .. 6, 7 or\n"
+	        "              more times)\n"
+	        "           and one line: evaluate: sequences S kmers N found F solid V nodes D solid_nodes E covered C completeness_x100 P\n"
+	        "           qv_x100 Q (S = the stretches of ACGT scored; E = the nodes counted min_count times or more, C = those of them in\n"
+	        "           the assembly, P = floor(10000 C / E); Q = round(100 * -10 log10(1 - (V / N)^(1 / K))), inf when V = N; - when the\n"
+	        "           divisor is 0)\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -342,6 +368,9 @@ typedef struct {
 	uint32_t screen_k;
 	char *rfile[MAX_REF_FILES];
 	int n_rfiles;
+	char *asmfile[MAX_REF_FILES];                                            /* --assembly: into refs, as the references of screen */
+	int n_asmfiles;
+	uint32_t rows;
 	sdt_adapter_list ads;                                                    /* of afile[] */
 	sdt_ref_set refs;                                                        /* of rfile[] */
 	query_set qs;                                                            /* of qfile */
@@ -1248,8 +1277,38 @@ static int run_query(sdt_ctx *gpu, unsigned long long reads, options *opt, const
 	return 0;
 }
 
+/* ---- evaluate -------------------------------------------------------------------------------------------------------------------------- */
+
+/* `evaluate`: the segments of the assembly against the counted table in one add, the spectrum, and the three outputs (asmsplit.c) */
+static int run_evaluate(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	(void)reads; (void)pairs;
+	const sdt_ref_set *refs = &opt->refs;
+	const sdt_asm_params prm = {(uint32_t)opt->min_count, opt->rows, 0, 0};
+	sdt_seq_support *seg = (sdt_seq_support *)records_alloc(refs->nseqs, sizeof *seg, 0);
+	sdt_asm_contig *ctg = (sdt_asm_contig *)records_alloc(refs->n_refs, sizeof *ctg, 0);
+	uint64_t *matrix = (uint64_t *)records_alloc((unsigned long long)opt->rows * SDT_ASM_CN_COLS, sizeof *matrix, 0);
+	uint64_t totals[4];
+	if (!seg || !ctg || !matrix) return 1;
+	if (SDT_CALL(sdt_gpu_asm_begin, gpu, &prm) || SDT_CALL(sdt_gpu_asm_add, gpu, refs->words, refs->nwords, refs->offsets, refs->nseqs, seg) ||
+	    SDT_CALL(sdt_gpu_asm_spectrum, gpu, matrix, totals) || SDT_CALL(sdt_gpu_asm_end, gpu))
+		return 1;
+	sdt_asm_fold(refs, seg, ctg);
+	sdt_asm_nodes nodes;
+	if (sdt_asm_nodes_of(matrix, opt->rows, (uint32_t)opt->min_count, &nodes) != 0) { fprintf(stderr, "sdt-kmers: --rows %u does not exceed -c %lu\n", opt->rows, opt->min_count); return 1; }
+	char path[4200], line[SDT_ASM_SUMMARY_MAX];
+	FILE *fs = stats_open(path, opt->outname, ".asmSupport");
+	if (!fs || (sdt_asm_support_write(fs, refs, ctg) != 0) | (fclose(fs) != 0)) return cannot_write(path);
+	fs = stats_open(path, opt->outname, ".asmSpectrum");
+	if (!fs || (sdt_asm_spectrum_write(fs, matrix, opt->rows) != 0) | (fclose(fs) != 0)) return cannot_write(path);
+	sdt_asm_summary(line, totals, &nodes, opt->K);
+	fputs(line, stdout);
+	free(seg); free(ctg); free(matrix);
+	return 0;
+}
+
 /* ---- the command line ------------------------------------------------------------------------------------------------------------------ */
-enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, N_SUBCOMMANDS };
+enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, N_SUBCOMMANDS };
 
 static const struct {
 	const char *name;
@@ -1264,11 +1323,12 @@ static const struct {
 	[COMPLEXITY] = {"complexity", 1, 1, 0, run_complexity}, [QTRIM] = {"qtrim", 1, 1, 0, run_qtrim},
 	[SCREEN] = {"screen", 1, 1, 0, run_screen},             [MERGE] = {"merge", 1, 1, 0, run_merge},
 	[QC] = {"qc", 0, 0, 0, NULL},                           /* (streams on its own and counts nothing: run_qc, from main) */
+	[EVALUATE] = {"evaluate", 0, 0, 2, run_evaluate},
 };
 
 enum { O_MAX_K = 1000, O_DEVICE, O_TARGET, O_MAX_CV, O_SEED, O_MIN_COV, O_MIN_LEN, O_CORRECT, O_MATE_SWAP, O_TAIL3, O_TAIL5, O_MIN_OVERLAP, O_ERROR_PCT,
        O_MIN_TAIL, O_TAIL_ERROR_PCT, O_MAX_ERR, O_MAX_SCORE, O_MAX_LOW, O_TRIM_LOW, O_PHRED, O_CUT_Q, O_LOW_Q, O_MAX_LOW_BASES, O_MAX_EE, O_SCREEN_K,
-       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED, O_CYCLES, O_FROM_END };
+       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED, O_CYCLES, O_FROM_END, O_ASSEMBLY, O_ROWS };
 
 /* the options that belong to some subcommands only: the name as it is printed, who may be given it, what the refusal says after
  * "belongs to" (kept, not derived: --min-overlap names clip alone), and the most its value may be where it takes a whole number */
@@ -1291,6 +1351,7 @@ static const struct { int code; const char *name; unsigned owners; const char *b
 	{O_MATE_SWAP, "--mate-swap", BIT(DEDUP), "dedup", 0},
 	{O_MIN_MERGED, "--min-merged", BIT(MERGE), "merge", UINT32_MAX}, {O_MAX_MERGED, "--max-merged", BIT(MERGE), "merge", UINT32_MAX},
 	{O_CYCLES, "--cycles", BIT(QC), "qc", SDT_QC_MAX_CYCLES}, {O_FROM_END, "--from-end", BIT(QC), "qc", 0},
+	{O_ASSEMBLY, "--assembly", BIT(EVALUATE), "evaluate", 0}, {O_ROWS, "--rows", BIT(EVALUATE), "evaluate", SDT_ASM_MAX_ROWS},
 };
 
 /* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
@@ -1336,6 +1397,7 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 	                                   {"min-hit-pct", required_argument, 0, O_MIN_HIT_PCT}, {"keep-matched", no_argument, 0, O_KEEP_MATCHED},
 	                                   {"min-merged", required_argument, 0, O_MIN_MERGED}, {"max-merged", required_argument, 0, O_MAX_MERGED},
 	                                   {"cycles", required_argument, 0, O_CYCLES}, {"from-end", no_argument, 0, O_FROM_END},
+	                                   {"assembly", required_argument, 0, O_ASSEMBLY}, {"rows", required_argument, 0, O_ROWS},
 	                                   {0, 0, 0, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:r:", longopts, NULL)) != -1) {
@@ -1411,11 +1473,25 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 			opt->qc.cycles = (uint32_t)v;
 			break;
 		case O_FROM_END: opt->qc.flags |= SDT_QC_FROM_END; break;
+		case O_ASSEMBLY:
+			if (opt->n_asmfiles == MAX_REF_FILES) { fprintf(stderr, "sdt-kmers: more than %d --assembly files\n", MAX_REF_FILES); return 255; }
+			opt->asmfile[opt->n_asmfiles++] = optarg;
+			break;
+		case O_ROWS:
+			if (v < 2) { fprintf(stderr, "sdt-kmers: --rows %llu: 2 to %d\n", v, SDT_ASM_MAX_ROWS); return 255; }
+			opt->rows = (uint32_t)v;
+			break;
 		default: usage(); return 255;
 		}
 	}
 	if (!opt->cfgfile[0] || (sub == QUERY ? !opt->qfile[0] : !opt->outname[0])) { usage(); return 255; }
 	if (sub == SCREEN && opt->n_rfiles == 0) { fprintf(stderr, "sdt-kmers: screen needs a reference file: -r refs.fa\n"); usage(); return 255; }
+	if (sub == EVALUATE && opt->n_asmfiles == 0) { fprintf(stderr, "sdt-kmers: evaluate needs an assembly: --assembly contigs.fa\n"); usage(); return 255; }
+	if (sub == EVALUATE && opt->rows <= opt->min_count) {
+		fprintf(stderr, "sdt-kmers: --rows %u must exceed -c %lu: the last row takes every larger count, and the solid nodes are summed from the rows\n", opt->rows,
+		        opt->min_count);
+		return 255;
+	}
 	if (sub == MERGE && opt->merge.max_len != 0 && opt->merge.max_len < (opt->merge.min_len > 1 ? opt->merge.min_len : 1u)) {
 		fprintf(stderr, "sdt-kmers: --max-merged %u is below --min-merged %u: no pair could merge (0: no limit)\n", opt->merge.max_len, opt->merge.min_len);
 		return 255;
@@ -1460,6 +1536,16 @@ static int load_inputs(int sub, options *opt, sdt_cfg *cfg)
 		for (uint64_t i = 0; i < refs->nseqs; i++)
 			if (refs->offsets[i + 1] - refs->offsets[i] >= opt->screen_k) positions += refs->offsets[i + 1] - refs->offsets[i] - opt->screen_k + 1;
 		if (positions == 0) { fprintf(stderr, "sdt-kmers: the references hold no stretch of %u letters ACGT: no k-mer to screen against\n", opt->screen_k); return 2; }
+	}
+	for (int i = 0; i < opt->n_asmfiles; i++)
+		if (sdt_refs_load(&opt->refs, opt->asmfile[i], err, sizeof err) != 0) { fprintf(stderr, "sdt-kmers: %s\n", err); return 2; }
+	if (sub == EVALUATE) {
+		const sdt_ref_set *refs = &opt->refs;
+		if (sdt_refs_pack(&opt->refs) != 0) { fprintf(stderr, "sdt-kmers: out of memory for the assembly\n"); return 2; }
+		uint64_t longest = 0;
+		for (uint64_t i = 0; i < refs->nseqs; i++)
+			if (refs->offsets[i + 1] - refs->offsets[i] > longest) longest = refs->offsets[i + 1] - refs->offsets[i];
+		if (longest < (uint64_t)opt->K) { fprintf(stderr, "sdt-kmers: the assembly holds no stretch of %d letters ACGT: no k-mer to score\n", opt->K); return 255; }
 	}
 	if (sub == QUERY) {
 		const int rq = load_queries(opt->qfile, opt->K, opt->K <= 31 ? 1 : (opt->K <= 63 ? 2 : 4), &opt->qs);
@@ -1516,7 +1602,7 @@ int main(int argc, char **argv)
 	static options opt = {.K = 23, .threads = 8,
 	                      .norm = {50, 10000, 0}, .clip = {5, 10, 0, 10, 20, 0, 0, 0}, .overlap = {30, 10, 0, 0}, .cx = {10, 50, 0, 0},
 	                      .qual = {33, 20, 15, 40, 0, 0, 0, 0}, .screen = {1, 0, 0, 0}, .merge = {0, 0, 33, 0},
-	                      .qc = {1024, 33, 0, 0, 0}, .screen_k = 31};                                   /* bbduk's usual figure: a choice, not a measurement */
+	                      .qc = {1024, 33, 0, 0, 0}, .screen_k = 31, .rows = 256};                                   /* bbduk's usual figure: a choice, not a measurement */
 	opt.min_count = subcommands[sub].min_count;
 	sdt_cfg cfg;
 	int rc = parse_options(argc - 1, argv + 1, sub, &opt);

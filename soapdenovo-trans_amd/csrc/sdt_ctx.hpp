@@ -11,6 +11,7 @@
 //                     (these four read stages share a host layer of their own: sdt_readstage.hpp over sdt_read_plan.h, sdt_compact.hpp)
 //   sdt_screen.hip    reads screened against reference sequences: a k-mer set of its own that the context keeps (one of the stages in
 //                     front of pass 1 that need no table, like sdt_dedup.hip, sdt_clip.hip, sdt_overlap.hip, sdt_complexity.hip, sdt_quality.hip)
+//   sdt_asm.hip       an assembly scored against the counted table: per-sequence support records, a copy number per node, the spectrum
 //   sdt_gpu_graph.hip the graph phases (own view of the context: sdt_internal.hpp GraphView)
 // Not part of the ABI: nothing here is visible to a caller of libsdt_gpu.so.
 #pragma once
@@ -180,6 +181,15 @@ struct sdt_ctx {
 		uint64_t slots = 0, n_kmers = 0;
 		uint32_t k = 0, n_refs = 0;
 	} screen;
+	// the assembly tally (sdt_asm.hip): one byte per table slot, four to a 32-bit word, and the four totals; lives from asm_begin to
+	// asm_end / destroy.  It belongs to one state of the table: search_cache_drop marks it stale, and a stale tally is refused, not read
+	struct AsmTally {
+		uint32_t *cn = nullptr;            // (slots + 3) / 4 words
+		unsigned long long *totals = nullptr;      // [4] sequences, k-mers, found, solid; [4 ..] the matrix of the last asm_spectrum
+		uint64_t slots = 0;                // the table's slots at asm_begin
+		uint32_t min_count = 0, rows = 0;
+		bool open = false, stale = false;
+	} asmt;
 	// timing
 	std::vector<EventPair> ev;
 	size_t ev_used = 0;
@@ -216,8 +226,13 @@ inline uint64_t wave_blocks_forced()
 }
 
 
-// the table is about to change (nodes counted, moved or replaced): what sdt_search.hip derived from it is stale
-inline void search_cache_drop(sdt_ctx *c) { c->hi_mode = -1; }
+// the table is about to change (nodes counted, moved or replaced): what sdt_search.hip derived from it is stale, and so is the
+// assembly tally of sdt_asm.hip, which is kept by slot
+inline void search_cache_drop(sdt_ctx *c)
+{
+	c->hi_mode = -1;
+	c->asmt.stale = true;
+}
 
 inline int env_int(const char *name, int dflt) { const char *v = getenv(name); return v && *v ? atoi(v) : dflt; }
 inline int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }

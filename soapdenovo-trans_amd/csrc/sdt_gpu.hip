@@ -375,6 +375,8 @@ int sdt_gpu_destroy(sdt_ctx *c)
 	if (c->d_hi) (void)hipFree(c->d_hi);
 	if (c->d_cov_flags) (void)hipFree(c->d_cov_flags);
 	if (c->screen.tab) (void)hipFree(c->screen.tab);
+	if (c->asmt.cn) (void)hipFree(c->asmt.cn);
+	if (c->asmt.totals) (void)hipFree(c->asmt.totals);
 	for (int i = 0; i < 5; i++) if (c->ab[i]) (void)hipFree(c->ab[i]);
 	sk_free(c);
 	shard_free(c);

@@ -96,6 +96,37 @@ __device__ inline uint32_t lookup_count(const Table<NW> &tbl, const Key<NW> &k, 
 	return 0;
 }
 
+// lookup_count's sibling for the one caller that needs the node as well as its count (k_asm_support tallies by slot): the same probe,
+// the same loads, and slot_out is set iff found
+template <int NW>
+__device__ inline uint32_t lookup_count_slot(const Table<NW> &tbl, const Key<NW> &k, const HiView &hv, bool &found, uint64_t &slot_out)
+{
+	uint64_t slot, lo, n;
+	probe_begin<NW>(tbl, k, slot, lo, n);
+	found = false;
+	for (uint64_t probe = 0; probe < n; probe++, slot = probe_next(slot, lo, n)) {
+		uint64_t val;
+		if constexpr (NW == 1) {
+			const ulonglong2 kv = *reinterpret_cast<const ulonglong2 *>(tbl.ent + slot);
+			if (kv.x == KEY_EMPTY) return 0;
+			if (kv.x != k.w[0]) continue;
+			val = kv.y;
+		} else {
+			const Entry<NW> *e = tbl.ent + slot;
+			if (e->key[0] == KEY_EMPTY) return 0;
+			bool same = true;
+#pragma unroll
+			for (int w = 0; w < NW; w++) same = same && e->key[w] == k.w[w];
+			if (!same) continue;
+			val = e->val;
+		}
+		found = true;
+		slot_out = slot;
+		return (uint32_t)(val >> 48) | (hi_lookup(hv, tbl.aux, slot) << 16);
+	}
+	return 0;
+}
+
 // status[i]: bit 0 found, bit 1 the query is the larger strand (the node is stored as its reverse complement; set whether or not
 // the node exists).  count / l_links / r_flags: the words k_export writes for the node, as the STORED node has them; 0 when absent.
 template <int NW>
