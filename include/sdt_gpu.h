@@ -1113,7 +1113,48 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  * Device memory: from asm_begin to asm_end one byte per table slot and 64 KiB for totals and matrix, SDT_ENOMEM when it does not fit;
  * the host form of asm_add also the staged piece with its offsets and 32 B per sequence of it.
  * Out of scope: distinct counting of assembly-only k-mers (they show as kmers - found, by occurrence); a k other than the table's K;
- * sharded contexts (refused); a kept-read form; plots; any change to profile_reads or its limit. */
+ * sharded contexts (refused); a kept-read form; plots; any change to profile_reads or its limit.
+ *
+ * Two counted tables compared.  The table can be asked by k-mer, by read and by assembly; these two calls ask it against ANOTHER
+ * table: how many solid k-mers of the raw library does the trimmed, normalised or deduplicated one still hold, how many did it
+ * lose, how many did correction invent; are two samples the same tissue (Jaccard, Bray-Curtis over k-mers: what Mash and KAT comp
+ * give); which k-mers are solid here and absent there.  Two contexts with counted tables of the same K on one device; nothing is
+ * written to either.  Added without a change of SDT_ABI_VERSION: the two calls, the two structs and the constant are additions.
+ *     Integers only.  Everything is exact and does not depend on the slot layout of either table (their sizes, how often they were
+ *     grown), on the launch geometry, or on how the high halves of the counts are read.
+ *     COUNTS.  For a canonical k-mer x, cA(x) is the count profile_reads sees in A: 32 bits with the high half, absent = 0, the
+ *     deleted flag ignored; cB(x) the same in B.  x is IN A iff it has a node in A (whatever its count).
+ *     MATRIX.  rows x cols uint64_t: m[r][c] = the distinct canonical k-mers of A u B with min(cA, rows - 1) = r and
+ *     min(cB, cols - 1) = c.  Nothing is special-cased: a node whose count is 0 lands in row or column 0 like an absent k-mer.
+ *     TOTALS, uint64_t[8]:  [0] nodes in A   [1] nodes in B   [2] nodes in both   [3] the sum of cA over A   [4] the sum of cB over B
+ *         [5] the sum of min(cA, cB) over the shared nodes (the minimum is taken per node, before summing)
+ *         [6] the sum of cA over the shared nodes   [7] the sum of cB over the shared nodes
+ *     Jaccard, the two containments and Bray-Curtis are functions of the totals; the caller computes them.
+ *     SELECTION.  The k-mers IN A with min_a <= cA <= max_a and min_b <= cB <= max_b (cB = 0 for a k-mer that is not in B): keys in
+ *     the layout of sdt_gpu_export_nodes (sdt_gpu_key_words words per k-mer, most significant first) with both counts, in no
+ *     particular order.  The k-mers only in B: the same call with the contexts swapped.
+ *     SYMMETRIES.  compare(B, A) is the transpose of compare(A, B) with totals [0]/[1], [3]/[4], [6]/[7] swapped; compare(A, A) is
+ *     diagonal with [0] = [1] = [2].  a == b is allowed.
+ *   compare_tables: matrix (rows x cols) and totals, either may be NULL, not both.  Waits.
+ *   compare_select: any of keys, count_a, count_b may be NULL.  *n = the number of matching k-mers, whatever capacity is; at most
+ *                   capacity of them are written, and which ones when there are more is not specified.  capacity = 0 with NULL
+ *                   arrays asks for the size.  Waits.
+ * The work runs on A's stream, after B's stream has been drained; the time of a pass is booked on the context whose table it walks
+ * (sdt_gpu_kernel_time: the first pass and the selection on A, the second pass on B).  Neither context's assembly tally is touched
+ * or made stale; the high halves of each context come through its own cache, which is filled if it was not.
+ * SDT_ESTATE: each context under the state rules of search_kmers, with its messages (a SDT_FLAG_CONTIG_INDEX context, a shard, after
+ * load_paths / import_paths, a released table, batches pushed and not drained); the message begins with the call's name and says
+ * which context failed: "sdt_gpu_compare_tables: context B: ...".
+ * SDT_EINVAL, before any launch, with the field and its value: a NULL context, NULL params or range; different K (both named);
+ * different devices; rows or cols < 2; rows x cols > SDT_CMP_MAX_CELLS; flags or reserved not 0; matrix and totals both NULL;
+ * min_a > max_a or min_b > max_b; capacity > 0 with every array NULL; capacity > 2^31 (the list of one call: narrow the ranges).
+ * Device memory held during the call, SDT_ENOMEM (nothing written) when it does not fit:
+ *     compare_tables    totals and matrix: 64 B + 8 B x rows x cols, 128 KiB + 64 B at most
+ *     compare_select    16 B; with capacity > 0 also the list in chunks of 256 records of 8 B x (key words + 1) --
+ *                       capacity / 192 + 1 chunks and one per wavefront of the grid -- 8 B per chunk, and the dense copy of what
+ *                       was written
+ * Out of scope: more than two tables; tables of different K; sharded contexts (refused); sketches; statistics on the counts;
+ * scaling by library size (the matrix is raw); a read filter by the selection; a device-pointer form of the selection. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -1152,6 +1193,9 @@ typedef struct { uint32_t cycles, phred_offset, flags, class_sel, reserved; } sd
 #define SDT_ASM_MAX_ROWS 1024
 typedef struct { uint64_t sum; uint32_t kmers, found, solid, gaps, longest_gap, longest_at; } sdt_seq_support;   /* 32 bytes */
 typedef struct { uint32_t min_count, rows, flags, reserved; } sdt_asm_params;   /* flags, reserved: 0 */
+#define SDT_CMP_MAX_CELLS 16384 /* rows * cols: the matrix of a workgroup is 32-bit counters in 64 KiB of LDS */
+typedef struct { uint32_t rows, cols, flags, reserved; } sdt_cmp_params;   /* rows, cols >= 2; flags, reserved: 0 */
+typedef struct { uint32_t min_a, max_a, min_b, max_b; } sdt_cmp_range;
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -1277,6 +1321,9 @@ int sdt_gpu_asm_add(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords,
 int sdt_gpu_asm_add_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nseqs, void *d_out);
 int sdt_gpu_asm_spectrum(sdt_ctx *ctx, uint64_t *matrix, uint64_t totals[4]);
 int sdt_gpu_asm_end(sdt_ctx *ctx);
+int sdt_gpu_compare_tables(sdt_ctx *a, sdt_ctx *b, const sdt_cmp_params *params, uint64_t *matrix, uint64_t totals[8]);
+int sdt_gpu_compare_select(sdt_ctx *a, sdt_ctx *b, const sdt_cmp_range *range, uint64_t *keys, uint32_t *count_a,
+                           uint32_t *count_b, uint64_t capacity, uint64_t *n);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

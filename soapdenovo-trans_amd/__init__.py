@@ -211,6 +211,8 @@ _ABI = [
     ("sdt_gpu_asm_add_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
     ("sdt_gpu_asm_spectrum", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
     ("sdt_gpu_asm_end", _c.c_int, [_c.c_void_p]),
+    ("sdt_gpu_compare_tables", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_compare_select", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -269,6 +271,7 @@ QC_QUALS, QC_GC_BINS, QC_TOTALS = 94, 101, 8
 # sum of its k-mers' counts, a gap = a maximal run of weak k-mers, longest_at = the first k-mer of the longest (kmers: none)
 SEQ_SUPPORT_DTYPE = np.dtype([("sum", np.uint64)] + [(f, np.uint32) for f in ("kmers", "found", "solid", "gaps", "longest_gap", "longest_at")])
 ASM_CN_COLS, ASM_MAX_ROWS = 8, 1024                      # SDT_ASM_CN_COLS, SDT_ASM_MAX_ROWS
+CMP_MAX_CELLS = 16384                                    # SDT_CMP_MAX_CELLS
 
 
 class NormParams(_c.Structure):
@@ -346,6 +349,22 @@ class AsmParams(_c.Structure):
 
     def __init__(self, min_count=2, rows=256, flags=0, reserved=0):
         super().__init__(min_count, rows, flags, reserved)
+
+
+class CmpParams(_c.Structure):
+    """sdt_cmp_params; the defaults of `sdt-kmers compare`"""
+    _fields_ = [(f, _c.c_uint32) for f in ("rows", "cols", "flags", "reserved")]
+
+    def __init__(self, rows=64, cols=64, flags=0, reserved=0):
+        super().__init__(rows, cols, flags, reserved)
+
+
+class CmpRange(_c.Structure):
+    """sdt_cmp_range; the default: the k-mers of A that B does not hold"""
+    _fields_ = [(f, _c.c_uint32) for f in ("min_a", "max_a", "min_b", "max_b")]
+
+    def __init__(self, min_a=1, max_a=2**32 - 1, min_b=0, max_b=0):
+        super().__init__(min_a, max_a, min_b, max_b)
 
 
 def qc_report_words(cycles: int) -> int:
@@ -1262,6 +1281,13 @@ class PregraphGPU:
     def asm_end(self):
         self._check(self.lib.sdt_gpu_asm_end(self._ctx))
 
+    # -- this context's counted table against another's (the rule: include/sdt_gpu.h); nothing is written to either
+    def compare(self, other, rows: int = 64, cols: int = 64):
+        return compare_tables(self, other, rows, cols)
+
+    def compare_select(self, other, min_a: int = 1, max_a: int = 2**32 - 1, min_b: int = 0, max_b: int = 0, capacity=None):
+        return compare_select(self, other, min_a, max_a, min_b, max_b, capacity)
+
     # -- the mates of an overlapping pair merged into one fragment read by their overlap records; qualities through a compaction (the
     # rule: include/sdt_gpu.h)
     @staticmethod
@@ -1541,6 +1567,46 @@ class PregraphGPU:
                  "cnt_ticks_fill", "cnt_ticks_count", "cnt_ticks_merge", "sc_ticks_stage", "sc_ticks_minima", "sc_ticks_starts",
                  "sc_ticks_emit", "distinct_records", "records", "distinct_record_kmers", "host_cleared_slots")
         return [float(x) for x in ms], dict(zip(names, (int(x) for x in cnt)))
+
+
+def compare_tables(a: PregraphGPU, b: PregraphGPU, rows: int = 64, cols: int = 64, params=None):
+    """two counted tables of the same K on one device -> (matrix uint64[rows, cols]: the distinct canonical k-mers of A u B by
+    min(cA, rows - 1) and min(cB, cols - 1); totals uint64[8]: nodes in A, in B, in both, sum cA, sum cB, sum min(cA, cB) over the
+    shared nodes, sum cA and sum cB over the shared nodes).  params: a CmpParams instead of rows and cols"""
+    prm = params if isinstance(params, CmpParams) else CmpParams(rows, cols)
+    # (the arrays are sized before the library has checked the params: what it would refuse gets arrays of one cell)
+    ok = 0 < prm.rows * prm.cols <= CMP_MAX_CELLS
+    matrix = np.zeros((prm.rows, prm.cols) if ok else (1, 1), dtype=np.uint64)
+    totals = np.zeros(8, dtype=np.uint64)
+    a._check(a.lib.sdt_gpu_compare_tables(a._ctx, b._ctx, ctypes.addressof(prm), _ptr(matrix), _ptr(totals)))
+    return matrix, totals
+
+
+def compare_select(a: PregraphGPU, b: PregraphGPU, min_a: int = 1, max_a: int = 2**32 - 1, min_b: int = 0, max_b: int = 0, capacity=None):
+    """the k-mers of A with min_a <= cA <= max_a and min_b <= cB <= max_b (cB = 0: not in B) -> (keys uint64[m, key words] in the
+    layout of export_nodes, count_a uint32[m], count_b uint32[m]) in no particular order.  capacity None: the size is asked for
+    first and m is the number of matches; else m = min(matches, capacity).  The number of matches itself: compare_select_count"""
+    rg = CmpRange(min_a, max_a, min_b, max_b)
+    n = ctypes.c_uint64()
+    if capacity is None:
+        a._check(a.lib.sdt_gpu_compare_select(a._ctx, b._ctx, ctypes.addressof(rg), None, None, None, 0, ctypes.byref(n)))
+        capacity = n.value
+    m = int(capacity)
+    keys = np.zeros((m, a.nw), dtype=np.uint64)
+    ca = np.zeros(m, dtype=np.uint32)
+    cb = np.zeros(m, dtype=np.uint32)
+    if m:
+        a._check(a.lib.sdt_gpu_compare_select(a._ctx, b._ctx, ctypes.addressof(rg), _ptr(keys), _ptr(ca), _ptr(cb), m, ctypes.byref(n)))
+    m = min(m, n.value)
+    return keys[:m], ca[:m], cb[:m]
+
+
+def compare_select_count(a: PregraphGPU, b: PregraphGPU, min_a: int = 1, max_a: int = 2**32 - 1, min_b: int = 0, max_b: int = 0) -> int:
+    """how many k-mers compare_select would give: capacity = 0 with no arrays"""
+    rg = CmpRange(min_a, max_a, min_b, max_b)
+    n = ctypes.c_uint64()
+    a._check(a.lib.sdt_gpu_compare_select(a._ctx, b._ctx, ctypes.addressof(rg), None, None, None, 0, ctypes.byref(n)))
+    return n.value
 
 
 def new_comm_id() -> bytes:

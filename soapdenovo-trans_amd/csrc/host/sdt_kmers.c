@@ -105,6 +105,13 @@
  *       prefix.asmSupport: per contig  index name bases kmers found solid sum gaps longest_gap longest_at
  *       prefix.asmSpectrum: row c0 .. c7 for the rows of the copy-number spectrum that hold a node
  *       and one line: evaluate: sequences S kmers N found F solid V nodes D solid_nodes E covered C completeness_x100 P qv_x100 Q
+ *   sdt-kmers compare -s a.cfg --against b.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--rows R, default 64]
+ *                     [--cols C, default 64] [--select MINA:MAXA:MINB:MAXB] [--max-list N, default 1000000] -o prefix
+ *       the counted k-mers of two sets of libraries against each other (sdt_gpu_compare_tables, sdt_gpu_compare_select; the rule:
+ *       include/sdt_gpu.h): a.cfg is counted into one context, b.cfg into a second on the same device, -d applied to both
+ *       prefix.cmpMatrix: the joint spectrum; prefix.cmpKmers (--select): the k-mers of A in the ranges, with both counts
+ *       and one line: compare: nodes_a X nodes_b Y shared S solid_a P solid_b Q solid_shared T jaccard_x10000 J contain_a_x10000 U
+ *       contain_b_x10000 V braycurtis_x10000 W   (cmpsplit.c, which documents the files and the ratios)
  *
  * The query file is read and checked before the device is touched.
  *
@@ -133,6 +140,7 @@
 #include "mergesplit.h"
 #include "qcsplit.h"
 #include "asmsplit.h"
+#include "cmpsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -293,6 +301,21 @@ static void usage(void)
 	        "           qv_x100 Q (S = the stretches of ACGT scored; E = the nodes counted min_count times or more, C = those of them in\n"
 	        "           the assembly, P = floor(10000 C / E); Q = round(100 * -10 log10(1 - (V / N)^(1 / K))), inf when V = N; - when the\n"
 	        "           divisor is 0)\n"
+	        "       sdt-kmers compare -s a.cfg --against b.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--rows R, default 64]\n"
+	        "                         [--cols C, default 64] [--select MINA:MAXA:MINB:MAXB] [--max-list N, default 1000000] -o prefix\n"
+	        "           the k-mers of the libraries of a.cfg (A) and of b.cfg (B) are counted into two tables on one device, -d applied to\n"
+	        "           both, and the tables are compared: cA and cB are the counts of a canonical k-mer in A and in B, 0 where it is absent.\n"
+	        "           R and C from 2, R x C up to 16384, both above min_count: row R - 1 and column C - 1 take every larger count.\n"
+	        "           -> prefix.cmpMatrix (a header line a\\b 0 1 .. C-1+ that names the columns, then per row r: r m[r][0] .. m[r][C-1], the\n"
+	        "              distinct k-mers of A and B together with min(cA, R - 1) = r and min(cB, C - 1) = c; the last row is written R-1+),\n"
+	        "              prefix.cmpKmers (with --select: kmer cA cB for the k-mers of A with MINA <= cA <= MAXA and MINB <= cB <= MAXB, in\n"
+	        "              letters, ascending; at most N lines, and when more matched a last line # M matched; the k-mers of B alone: swap\n"
+	        "              the two configs)\n"
+	        "           and per library its count line, prefixed A: / B:, and one line: compare: nodes_a X nodes_b Y shared S solid_a P\n"
+	        "           solid_b Q solid_shared T jaccard_x10000 J contain_a_x10000 U contain_b_x10000 V braycurtis_x10000 W (P, Q, T = the\n"
+	        "           k-mers counted min_count times or more in A, in B, in both; J = floor(10000 S / (X + Y - S)), U = floor(10000 S / X),\n"
+	        "           V = floor(10000 S / Y), W = floor(10000 (sum cA + sum cB - 2 sum min(cA, cB)) / (sum cA + sum cB)); 0 when the\n"
+	        "           divisor is 0)\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -371,6 +394,11 @@ typedef struct {
 	char *asmfile[MAX_REF_FILES];                                            /* --assembly: into refs, as the references of screen */
 	int n_asmfiles;
 	uint32_t rows;
+	char againstfile[4096];                                                  /* compare: --against, the library config of B */
+	sdt_cfg against;                                                         /* of againstfile */
+	uint32_t cols, select[4];                                                /* compare: --cols; --select min_a max_a min_b max_b */
+	int select_given;
+	unsigned long long max_list;
 	sdt_adapter_list ads;                                                    /* of afile[] */
 	sdt_ref_set refs;                                                        /* of rfile[] */
 	query_set qs;                                                            /* of qfile */
@@ -1307,8 +1335,47 @@ static int run_evaluate(sdt_ctx *gpu, unsigned long long reads, options *opt, co
 	return 0;
 }
 
+/* ---- compare --------------------------------------------------------------------------------------------------------------------------- */
+
+/* `compare`: two counted tables, A and B; the matrix with its totals, the selection where asked for, and the outputs (cmpsplit.c) */
+static int run_compare(sdt_ctx *a, sdt_ctx *b, const options *opt)
+{
+	const sdt_cmp_params prm = {opt->rows, opt->cols, 0, 0};
+	uint64_t *matrix = (uint64_t *)records_alloc((unsigned long long)opt->rows * opt->cols, sizeof *matrix, 0);
+	uint64_t totals[8];
+	if (!matrix) return 1;
+	if (SDT_CALL(sdt_gpu_compare_tables, a, b, &prm, matrix, totals)) return 1;
+	sdt_cmp_solid solid;
+	if (sdt_cmp_solid_of(matrix, opt->rows, opt->cols, (uint32_t)opt->min_count, &solid) != 0) {
+		fprintf(stderr, "sdt-kmers: --rows %u and --cols %u must exceed -c %lu\n", opt->rows, opt->cols, opt->min_count);
+		return 1;
+	}
+	char path[4200], line[SDT_CMP_SUMMARY_MAX];
+	FILE *fs = stats_open(path, opt->outname, ".cmpMatrix");
+	if (!fs || (sdt_cmp_matrix_write(fs, matrix, opt->rows, opt->cols) != 0) | (fclose(fs) != 0)) return cannot_write(path);
+	if (opt->select_given) {
+		const sdt_cmp_range rg = {opt->select[0], opt->select[1], opt->select[2], opt->select[3]};
+		uint64_t matched = 0, got = 0;
+		if (SDT_CALL(sdt_gpu_compare_select, a, b, &rg, NULL, NULL, NULL, 0, &matched)) return 1;
+		const uint64_t cap = matched < opt->max_list ? matched : opt->max_list;
+		const int nw = sdt_gpu_key_words(a);
+		uint64_t *keys = (uint64_t *)records_alloc(cap * (unsigned long long)nw, sizeof *keys, 0);
+		uint32_t *ca = (uint32_t *)records_alloc(cap, sizeof *ca, 0), *cb = (uint32_t *)records_alloc(cap, sizeof *cb, 0);
+		if (!keys || !ca || !cb) return 1;
+		if (cap && SDT_CALL(sdt_gpu_compare_select, a, b, &rg, keys, ca, cb, cap, &got)) return 1;
+		if (cap && got != matched) { fprintf(stderr, "sdt-kmers: %llu k-mers matched, then %llu\n", (unsigned long long)matched, (unsigned long long)got); return 1; }
+		fs = stats_open(path, opt->outname, ".cmpKmers");
+		if (!fs || (sdt_cmp_kmers_write(fs, keys, ca, cb, cap, nw, opt->K, matched) != 0) | (fclose(fs) != 0)) return cannot_write(path);
+		free(keys); free(ca); free(cb);
+	}
+	sdt_cmp_summary(line, totals, &solid);
+	fputs(line, stdout);
+	free(matrix);
+	return 0;
+}
+
 /* ---- the command line ------------------------------------------------------------------------------------------------------------------ */
-enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, N_SUBCOMMANDS };
+enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, COMPARE, N_SUBCOMMANDS };
 
 static const struct {
 	const char *name;
@@ -1324,11 +1391,12 @@ static const struct {
 	[SCREEN] = {"screen", 1, 1, 0, run_screen},             [MERGE] = {"merge", 1, 1, 0, run_merge},
 	[QC] = {"qc", 0, 0, 0, NULL},                           /* (streams on its own and counts nothing: run_qc, from main) */
 	[EVALUATE] = {"evaluate", 0, 0, 2, run_evaluate},
+	[COMPARE] = {"compare", 0, 0, 2, NULL},                 /* (counts two sets of libraries into two contexts: run_compare, from main) */
 };
 
 enum { O_MAX_K = 1000, O_DEVICE, O_TARGET, O_MAX_CV, O_SEED, O_MIN_COV, O_MIN_LEN, O_CORRECT, O_MATE_SWAP, O_TAIL3, O_TAIL5, O_MIN_OVERLAP, O_ERROR_PCT,
        O_MIN_TAIL, O_TAIL_ERROR_PCT, O_MAX_ERR, O_MAX_SCORE, O_MAX_LOW, O_TRIM_LOW, O_PHRED, O_CUT_Q, O_LOW_Q, O_MAX_LOW_BASES, O_MAX_EE, O_SCREEN_K,
-       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED, O_CYCLES, O_FROM_END, O_ASSEMBLY, O_ROWS };
+       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED, O_CYCLES, O_FROM_END, O_ASSEMBLY, O_ROWS, O_AGAINST, O_COLS, O_SELECT, O_MAX_LIST };
 
 /* the options that belong to some subcommands only: the name as it is printed, who may be given it, what the refusal says after
  * "belongs to" (kept, not derived: --min-overlap names clip alone), and the most its value may be where it takes a whole number */
@@ -1351,7 +1419,9 @@ static const struct { int code; const char *name; unsigned owners; const char *b
 	{O_MATE_SWAP, "--mate-swap", BIT(DEDUP), "dedup", 0},
 	{O_MIN_MERGED, "--min-merged", BIT(MERGE), "merge", UINT32_MAX}, {O_MAX_MERGED, "--max-merged", BIT(MERGE), "merge", UINT32_MAX},
 	{O_CYCLES, "--cycles", BIT(QC), "qc", SDT_QC_MAX_CYCLES}, {O_FROM_END, "--from-end", BIT(QC), "qc", 0},
-	{O_ASSEMBLY, "--assembly", BIT(EVALUATE), "evaluate", 0}, {O_ROWS, "--rows", BIT(EVALUATE), "evaluate", SDT_ASM_MAX_ROWS},
+	{O_ASSEMBLY, "--assembly", BIT(EVALUATE), "evaluate", 0}, {O_ROWS, "--rows", BIT(EVALUATE) | BIT(COMPARE), "evaluate", SDT_CMP_MAX_CELLS / 2},
+	{O_AGAINST, "--against", BIT(COMPARE), "compare", 0}, {O_COLS, "--cols", BIT(COMPARE), "compare", SDT_CMP_MAX_CELLS / 2},
+	{O_SELECT, "--select", BIT(COMPARE), "compare", 0}, {O_MAX_LIST, "--max-list", BIT(COMPARE), "compare", 1ULL << 31},
 };
 
 /* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
@@ -1398,6 +1468,8 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 	                                   {"min-merged", required_argument, 0, O_MIN_MERGED}, {"max-merged", required_argument, 0, O_MAX_MERGED},
 	                                   {"cycles", required_argument, 0, O_CYCLES}, {"from-end", no_argument, 0, O_FROM_END},
 	                                   {"assembly", required_argument, 0, O_ASSEMBLY}, {"rows", required_argument, 0, O_ROWS},
+	                                   {"against", required_argument, 0, O_AGAINST}, {"cols", required_argument, 0, O_COLS},
+	                                   {"select", required_argument, 0, O_SELECT}, {"max-list", required_argument, 0, O_MAX_LIST},
 	                                   {0, 0, 0, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:r:", longopts, NULL)) != -1) {
@@ -1478,9 +1550,25 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 			opt->asmfile[opt->n_asmfiles++] = optarg;
 			break;
 		case O_ROWS:
-			if (v < 2) { fprintf(stderr, "sdt-kmers: --rows %llu: 2 to %d\n", v, SDT_ASM_MAX_ROWS); return 255; }
+			if (v < 2 || (sub == EVALUATE && v > SDT_ASM_MAX_ROWS)) {
+				fprintf(stderr, "sdt-kmers: --rows %llu: 2 to %d\n", v, sub == EVALUATE ? SDT_ASM_MAX_ROWS : SDT_CMP_MAX_CELLS / 2);
+				return 255;
+			}
 			opt->rows = (uint32_t)v;
 			break;
+		case O_AGAINST: snprintf(opt->againstfile, sizeof opt->againstfile, "%s", optarg); break;
+		case O_COLS:
+			if (v < 2) { fprintf(stderr, "sdt-kmers: --cols %llu: 2 to %d\n", v, SDT_CMP_MAX_CELLS / 2); return 255; }
+			opt->cols = (uint32_t)v;
+			break;
+		case O_SELECT:
+			if (sdt_cmp_parse_select(optarg, opt->select) != 0) {
+				fprintf(stderr, "sdt-kmers: --select %s: MINA:MAXA:MINB:MAXB is expected, four whole numbers below 2^32 with MINA <= MAXA and MINB <= MAXB\n", optarg);
+				return 255;
+			}
+			opt->select_given = 1;
+			break;
+		case O_MAX_LIST: opt->max_list = v; break;
 		default: usage(); return 255;
 		}
 	}
@@ -1490,6 +1578,16 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 	if (sub == EVALUATE && opt->rows <= opt->min_count) {
 		fprintf(stderr, "sdt-kmers: --rows %u must exceed -c %lu: the last row takes every larger count, and the solid nodes are summed from the rows\n", opt->rows,
 		        opt->min_count);
+		return 255;
+	}
+	if (sub == COMPARE && !opt->againstfile[0]) { fprintf(stderr, "sdt-kmers: compare needs a second library config: --against b.cfg\n"); usage(); return 255; }
+	if (sub == COMPARE && (unsigned long long)opt->rows * opt->cols > SDT_CMP_MAX_CELLS) {
+		fprintf(stderr, "sdt-kmers: --rows %u x --cols %u = %llu cells: %d at most\n", opt->rows, opt->cols, (unsigned long long)opt->rows * opt->cols, SDT_CMP_MAX_CELLS);
+		return 255;
+	}
+	if (sub == COMPARE && (opt->rows <= opt->min_count || opt->cols <= opt->min_count)) {
+		fprintf(stderr, "sdt-kmers: --rows %u and --cols %u must exceed -c %lu: the last row and column take every larger count, and the solid k-mers are summed from them\n",
+		        opt->rows, opt->cols, opt->min_count);
 		return 255;
 	}
 	if (sub == MERGE && opt->merge.max_len != 0 && opt->merge.max_len < (opt->merge.min_len > 1 ? opt->merge.min_len : 1u)) {
@@ -1552,6 +1650,7 @@ static int load_inputs(int sub, options *opt, sdt_cfg *cfg)
 		if (rq != 0) return rq;
 	}
 	if (sdt_cfg_load(opt->cfgfile, cfg) != 0) return 255;
+	if (sub == COMPARE && sdt_cfg_load(opt->againstfile, &opt->against) != 0) return 255;
 	/* qtrim: every read needs its qualities; refused before the device is touched and before anything is written */
 	for (int i = 0; i < cfg->nlibs && sub == QTRIM; i++) {
 		const sdt_lib *l = &cfg->libs[i];
@@ -1561,9 +1660,14 @@ static int load_inputs(int sub, options *opt, sdt_cfg *cfg)
 	return 0;
 }
 
-/* the libraries through pass 1 (qtrim: every batch's qualities judged on the way); 0 with *reads, or 1 */
-static int stream_and_count(sdt_ctx *gpu, int sub, options *opt, const sdt_cfg *cfg, sdt_pair_ranges *pairs, qtrim_state *qst, unsigned long long *reads)
+/* the libraries through pass 1 (qtrim: every batch's qualities judged on the way); 0 with *reads, or 1 after the context was
+ * destroyed or what failed was said.  says: in front of the lines it prints.  May be called again for another context (compare): the
+ * parser pool is enabled and disabled per call, and the ring of pushes in flight, which a call that failed leaves as it was, starts
+ * empty */
+static int stream_and_count(sdt_ctx *gpu, int sub, options *opt, const sdt_cfg *cfg, sdt_pair_ranges *pairs, qtrim_state *qst, unsigned long long *reads,
+                            const char *says)
 {
+	g_inflight.head = g_inflight.n = 0;
 	const int max_read_len = cfg->max_rd_len ? cfg->max_rd_len : 100;       /* prlHashReads.c:361-364 */
 	push_state st = {gpu, 0, subcommands[sub].pairs ? pairs : NULL};
 	if (sub == QTRIM) {
@@ -1587,9 +1691,9 @@ static int stream_and_count(sdt_ctx *gpu, int sub, options *opt, const sdt_cfg *
 	if (rc != 0) { sdt_gpu_destroy(gpu); return 1; }
 	uint64_t kmers = 0, nodes = 0, removed = 0;
 	if (SDT_CALL(sdt_gpu_finish_count, gpu, &kmers, &nodes)) return 1;
-	printf("%llu reads, %llu nodes allocated, %llu kmer in reads\n", st.reads, (unsigned long long)nodes, (unsigned long long)kmers);
+	printf("%s%llu reads, %llu nodes allocated, %llu kmer in reads\n", says, st.reads, (unsigned long long)nodes, (unsigned long long)kmers);
 	if (opt->d && SDT_CALL(sdt_gpu_delow, gpu, opt->d, &removed)) return 1;
-	if (opt->d) printf("%llu kmer removed\n", (unsigned long long)removed);
+	if (opt->d) printf("%s%llu kmer removed\n", says, (unsigned long long)removed);
 	*reads = st.reads;
 	return 0;
 }
@@ -1602,8 +1706,9 @@ int main(int argc, char **argv)
 	static options opt = {.K = 23, .threads = 8,
 	                      .norm = {50, 10000, 0}, .clip = {5, 10, 0, 10, 20, 0, 0, 0}, .overlap = {30, 10, 0, 0}, .cx = {10, 50, 0, 0},
 	                      .qual = {33, 20, 15, 40, 0, 0, 0, 0}, .screen = {1, 0, 0, 0}, .merge = {0, 0, 33, 0},
-	                      .qc = {1024, 33, 0, 0, 0}, .screen_k = 31, .rows = 256};                                   /* bbduk's usual figure: a choice, not a measurement */
+	                      .qc = {1024, 33, 0, 0, 0}, .screen_k = 31, .rows = 256, .cols = 64, .max_list = 1000000};                                   /* bbduk's usual figure: a choice, not a measurement */
 	opt.min_count = subcommands[sub].min_count;
+	if (sub == COMPARE) opt.rows = 64;
 	sdt_cfg cfg;
 	int rc = parse_options(argc - 1, argv + 1, sub, &opt);
 	if (rc == 0) rc = load_inputs(sub, &opt, &cfg);
@@ -1621,7 +1726,20 @@ int main(int argc, char **argv)
 	static qtrim_state qst;
 	opt.qtrim = &qst;
 	unsigned long long reads = 0;
-	if (stream_and_count(gpu, sub, &opt, &cfg, &pairs, &qst, &reads) != 0) return 1;
+	if (sub == COMPARE) {
+		/* A is counted and drained before B's libraries stream; both contexts then live side by side on the device */
+		sdt_ctx *gpu_b = NULL;
+		if (stream_and_count(gpu, sub, &opt, &cfg, &pairs, &qst, &reads, "A: ") != 0) return 1;
+		if (SDT_CALL(sdt_gpu_init, &gpu_b, opt.device, opt.K, 0, 0u)) { sdt_gpu_destroy(gpu); return 1; }
+		if (stream_and_count(gpu_b, sub, &opt, &opt.against, &pairs, &qst, &reads, "B: ") != 0) { sdt_gpu_destroy(gpu); return 1; }
+		rc = run_compare(gpu, gpu_b, &opt);
+		sdt_gpu_destroy(gpu_b);
+		sdt_gpu_destroy(gpu);
+		sdt_cfg_free(&opt.against);
+		sdt_cfg_free(&cfg);
+		return rc;
+	}
+	if (stream_and_count(gpu, sub, &opt, &cfg, &pairs, &qst, &reads, "") != 0) return 1;
 	if (subcommands[sub].run(gpu, reads, &opt, &pairs) != 0) return 1;
 	sdt_pair_ranges_free(&pairs);
 	sdt_adapters_free(&opt.ads);

@@ -12,6 +12,8 @@
 //   sdt_screen.hip    reads screened against reference sequences: a k-mer set of its own that the context keeps (one of the stages in
 //                     front of pass 1 that need no table, like sdt_dedup.hip, sdt_clip.hip, sdt_overlap.hip, sdt_complexity.hip, sdt_quality.hip)
 //   sdt_asm.hip       an assembly scored against the counted table: per-sequence support records, a copy number per node, the spectrum
+//   sdt_compare.hip   two counted tables compared: the joint count spectrum and the k-mers within given ranges of both counts (the one
+//                     unit whose entry points take two contexts)
 //   sdt_gpu_graph.hip the graph phases (own view of the context: sdt_internal.hpp GraphView)
 // Not part of the ABI: nothing here is visible to a caller of libsdt_gpu.so.
 #pragma once

@@ -1,0 +1,263 @@
+"""GPU (-m gpu): two counted tables compared on the device (sdt_gpu_compare_tables, sdt_gpu_compare_select) against the Python
+restatement of the rule (table_compare_util.py): matrix, totals and selections, all exact.  Counts come from the oracle, never from
+the library.  The two contexts of a pair are created with different table sizes, so the same k-mer sits at unrelated slots: a probe
+that read the walked table's slot, or its high half, in the other table would miss the named cells below."""
+import ctypes
+import functools
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+import table_compare_util as tu
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EST_A, EST_B = 1 << 16, 1 << 20
+
+
+def counted(pkg, synth, reads, K, est, want=None, flags=0):
+    g = pkg.PregraphGPU(K, est_distinct=est, flags=flags)
+    g.push_reads(synth.pack_2bit(reads[0]), reads[1])
+    got = g.finish_count()
+    assert want is None or got == want, (got, want)
+    return g
+
+
+def pair(pkg, synth, case, flags=0, est_b=EST_B):
+    return (counted(pkg, synth, case["a"], case["K"], EST_A, (case["kmers_a"], case["nodes_a"]), flags),
+            counted(pkg, synth, case["b"], case["K"], est_b, (case["kmers_b"], case["nodes_b"]), flags))
+
+
+def same(got, want, what):
+    (m, t), (wm, wt) = got, want
+    assert m.shape == wm.shape and m.dtype == np.uint64 and t.shape == (8,), what
+    bad = np.argwhere(m != wm)
+    assert bad.size == 0, f"{what}: cells {bad[:6].tolist()} got {[int(m[tuple(b)]) for b in bad[:6]]} want {[int(wm[tuple(b)]) for b in bad[:6]]}"
+    assert (t == wt).all(), f"{what}: totals {t.tolist()} want {wt.tolist()}"
+
+
+# ---- 1. the model, per key width ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K,flags", [(23, 0), (31, 1), (31, 2), (47, 0), (63, 0), (95, 0), (127, 0)])
+def test_matrix_and_totals_equal_the_model(pkg, synth, K, flags):
+    """1, 2 and 4 key words, both pass-1 kernel families at K = 31 (SDT_FLAG_DIRECT = 1, SDT_FLAG_PARTITION = 2).  64 x 64, and 2 x 8192:
+    the cell cap exactly, where the workgroup's matrix fills 64 KiB of LDS.  Named cells: the B-only k-mers (row 0: a kernel without its
+    second pass leaves them out), the shared node past 65 535 (the cap cell, and totals [5] .. [7]: a high half from the wrong table
+    changes them), the cap column."""
+    assert (pkg.SDT_FLAG_DIRECT, pkg.SDT_FLAG_PARTITION) == (1, 2)
+    case = tu.pair_case(synth, K)
+    A, B, p = case["A"], case["B"], case["polya"]
+    a, b = pair(pkg, synth, case, flags)
+    with a, b:
+        assert a.nw == b.nw == (1 if K <= 31 else 2 if K <= 63 else 4)
+        assert a.lib.sdt_gpu_table_slots(a._ctx) != b.lib.sdt_gpu_table_slots(b._ctx)
+        m, t = pkg.compare_tables(a, b, 64, 64)
+        same((m, t), tu.compare(A, B, 64, 64), f"K={K} flags={flags} 64 x 64")
+        assert m[0, 1:].sum() == t[1] - t[2] > 0 and m[1:, 0].sum() >= t[0] - t[2] > 0 and m[63, 63] >= 1 and m[:63, 63].sum() >= 1
+        assert t[5] >= min(A[p], B[p]) > 65535 and t[6] >= A[p] and t[7] >= B[p] and A[p] != B[p]
+        same(a.compare(b, 2, 8192), tu.compare(A, B, 2, 8192), f"K={K} flags={flags} 2 x 8192")
+        m2, _ = pkg.compare_tables(a, b, 2, 8192)
+        assert m2[1, 8191] >= 1 and m2[0].sum() == t[1] - t[2]
+
+
+# ---- 2. the high halves in both forms; 4. selection: in a child process under the test hooks ---------------------------------------------------
+RANGES = {"a_only_solid": (2, tu.U32, 0, 0), "shared": (1, tu.U32, 1, tu.U32), "everything": (0, tu.U32, 0, tu.U32), "empty": (3, 3, 70000, 70001)}
+
+CHILD = """
+import sys
+sys.path[:0] = [{root!r}, {tests!r}]
+import ctypes
+import numpy as np
+import __graft_entry__ as ge
+pkg = ge.load_package()
+from soapdenovo_trans_amd import synth
+import table_compare_util as tu
+from test_table_compare import pair, RANGES
+case = tu.pair_case(synth, 31)
+out = {{}}
+a, b = pair(pkg, synth, case)
+with a, b:
+    out["m"], out["t"] = pkg.compare_tables(a, b, 64, 64)
+    out["m2"], out["t2"] = pkg.compare_tables(a, b, 2, 8192)
+    for name, rg in RANGES.items():
+        out["n_" + name] = np.array([pkg.compare_select_count(a, b, *rg)])
+        out["k_" + name], out["a_" + name], out["b_" + name] = pkg.compare_select(a, b, *rg)
+    n = int(out["n_everything"][0])
+    cap = n - 3
+    keys, ca, cb = np.zeros((cap + 8, a.nw), dtype=np.uint64), np.zeros(cap + 8, dtype=np.uint32), np.zeros(cap + 8, dtype=np.uint32)
+    keys[cap:], ca[cap:], cb[cap:] = 0xDEAD, 0xDEAD, 0xDEAD
+    got = ctypes.c_uint64()
+    rg = pkg.CmpRange(*RANGES["everything"])
+    a._check(a.lib.sdt_gpu_compare_select(a._ctx, b._ctx, ctypes.addressof(rg), pkg._ptr(keys), pkg._ptr(ca), pkg._ptr(cb), cap, ctypes.byref(got)))
+    out["cap_n"], out["cap_k"], out["cap_a"], out["cap_b"] = np.array([got.value]), keys, ca, cb
+    # keys alone, and counts alone
+    k_only = np.zeros((n, a.nw), dtype=np.uint64)
+    a._check(a.lib.sdt_gpu_compare_select(a._ctx, b._ctx, ctypes.addressof(rg), pkg._ptr(k_only), None, None, n, ctypes.byref(got)))
+    out["k_only"] = k_only
+    out["k_swapped"], out["a_swapped"], out["b_swapped"] = b.compare_select(a)                 # the k-mers only in B
+np.savez({path!r}, **out)
+"""
+
+
+@functools.lru_cache(maxsize=None)
+def child(aux_form):
+    """the K = 31 pair under SDT_SCAN_BLOCKS = 2: two workgroups take every stride of both tables, so a workgroup's LDS matrix
+    accumulates over many strides and every wavefront closes and reopens chunks of the selection"""
+    path = os.path.join(tempfile.mkdtemp(prefix="table_compare_"), "child.npz")
+    env = dict(os.environ, SDT_TEST_HOOKS="1", SDT_PROFILE_AUX=aux_form, SDT_SCAN_BLOCKS="2")
+    r = subprocess.run([sys.executable, "-c", CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"), path=path)], env=env, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return dict(np.load(path))
+
+
+@pytest.mark.parametrize("aux_form", ["aux", "hash"])
+def test_high_halves_in_both_forms(synth, aux_form):
+    case = tu.pair_case(synth, 31)
+    got = child(aux_form)
+    same((got["m"], got["t"]), tu.compare(case["A"], case["B"], 64, 64), f"{aux_form}, two workgroups, 64 x 64")
+    same((got["m2"], got["t2"]), tu.compare(case["A"], case["B"], 2, 8192), f"{aux_form}, two workgroups, 2 x 8192")
+    p = case["polya"]
+    assert (p, case["A"][p], case["B"][p]) in tu.records(got["k_shared"], got["a_shared"], got["b_shared"])
+
+
+@pytest.mark.parametrize("aux_form", ["aux", "hash"])
+def test_selection(synth, aux_form):
+    case = tu.pair_case(synth, 31)
+    A, B = case["A"], case["B"]
+    got = child(aux_form)
+    for name, rg in RANGES.items():
+        want = tu.select(A, B, *rg)
+        assert int(got["n_" + name][0]) == len(want), name                         # capacity = 0: the exact size
+        assert tu.records(got["k_" + name], got["a_" + name], got["b_" + name]) == want, name
+    assert len(tu.select(A, B, *RANGES["empty"])) == 0 and got["k_empty"].shape == (0, 1)
+    everything = tu.select(A, B, *RANGES["everything"])
+    n = len(everything)
+    assert n == case["nodes_a"] > 2 * 256 * 8                                      # more than two chunks per wavefront of the two workgroups
+    # capacity = n - 3: exactly that many written, all of them members, none twice, nothing past them, n unchanged
+    cap = n - 3
+    assert int(got["cap_n"][0]) == n
+    rec = tu.records(got["cap_k"][:cap], got["cap_a"][:cap], got["cap_b"][:cap])
+    assert len(rec) == cap and rec <= everything
+    assert (got["cap_k"][cap:] == 0xDEAD).all() and (got["cap_a"][cap:] == 0xDEAD).all() and (got["cap_b"][cap:] == 0xDEAD).all()
+    assert set(tu.key_ints(got["k_only"])) == set(A)
+    # the k-mers only in B: the contexts swapped
+    assert tu.records(got["k_swapped"], got["a_swapped"], got["b_swapped"]) == tu.select(B, A) and len(tu.select(B, A)) > 100
+
+
+# ---- 3. symmetries and invariance -------------------------------------------------------------------------------------------------------------
+def test_symmetries_and_invariance(pkg, synth):
+    case = tu.pair_case(synth, 31)
+    A, B = case["A"], case["B"]
+    a, b = pair(pkg, synth, case)
+    with a, b:
+        m, t = pkg.compare_tables(a, b, 64, 32)
+        same((m, t), tu.compare(A, B, 64, 32), "64 x 32")
+        mt, tt = pkg.compare_tables(b, a, 32, 64)
+        assert (mt == m.T).all() and (tt == tu.swapped(t)).all()
+        d, td = pkg.compare_tables(a, a, 64, 64)
+        same((d, td), tu.compare(A, A, 64, 64), "A against itself")
+        assert (d == np.diag(np.diag(d))).all() and td[0] == td[1] == td[2] == case["nodes_a"]
+        # matrix alone, totals alone
+        only_m, only_t = np.zeros((64, 32), dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+        prm = pkg.CmpParams(64, 32)
+        a._check(a.lib.sdt_gpu_compare_tables(a._ctx, b._ctx, ctypes.addressof(prm), pkg._ptr(only_m), None))
+        a._check(a.lib.sdt_gpu_compare_tables(a._ctx, b._ctx, ctypes.addressof(prm), None, pkg._ptr(only_t)))
+        assert (only_m == m).all() and (only_t == t).all()
+        # a B whose table starts far too small (room for 4 096 nodes, as the suite forces growth elsewhere) and is rebuilt while the same
+        # reads are counted: another layout, the same answer
+        with counted(pkg, synth, case["b"], 31, 1 << 12, (case["kmers_b"], case["nodes_b"])) as grown:
+            assert grown.lib.sdt_gpu_table_slots(grown._ctx) != b.lib.sdt_gpu_table_slots(b._ctx)
+            same(pkg.compare_tables(a, grown, 64, 32), (m, t), "B grown from est_distinct = 4096")
+            same(pkg.compare_tables(grown, b, 64, 64), tu.compare(B, B, 64, 64), "B against B in another layout")
+        # every 7th exported key of A: its two counts by search_kmers are its record in the selection, and its cell holds it
+        keys = a.export_nodes()[0][::7]
+        ca, cb = a.search_kmers(keys)[0], b.search_kmers(keys)[0]
+        sel = {k: (x, y) for k, x, y in tu.records(*pkg.compare_select(a, b, 0, tu.U32, 0, tu.U32))}
+        sampled = np.zeros((64, 32), dtype=np.uint64)
+        for k, x, y in zip(tu.key_ints(keys), ca.tolist(), cb.tolist()):
+            assert sel[k] == (x, y) == (A[k], B.get(k, 0))
+            sampled[min(x, 63), min(y, 31)] += 1
+        assert (sampled <= m).all() and sampled.sum() == len(keys) > 1000
+
+
+# ---- 5. nothing is written --------------------------------------------------------------------------------------------------------------------
+def test_nothing_is_written(pkg, synth):
+    import asm_support_util as au
+    case = tu.pair_case(synth, 31)
+
+    def snapshot(g):
+        keys, l, rf, cnt = g.export_nodes()[:4]
+        order = np.lexsort(keys.T[::-1])
+        return [x[order].copy() for x in (keys, l, rf, cnt)]
+
+    a, b = pair(pkg, synth, case)
+    with a, b:
+        before = snapshot(a), snapshot(b)
+        a.asm_begin(dict(min_count=2, rows=64))
+        codes, offs = au.concat([case["a"][0][:400]])
+        a.asm_add(synth.pack_2bit(codes), offs)
+        spec = a.asm_spectrum()
+        same(pkg.compare_tables(a, b, 64, 64), tu.compare(case["A"], case["B"], 64, 64), "with a tally open on A")
+        pkg.compare_tables(b, a, 8, 8)
+        assert len(pkg.compare_select(a, b)[0]) == len(tu.select(case["A"], case["B"]))
+        for was, now in zip(before, (snapshot(a), snapshot(b))):
+            for x, y in zip(was, now):
+                assert x.shape == y.shape and (x == y).all()
+        again = a.asm_spectrum()                                                   # the tally is neither stale nor changed
+        assert (again[0] == spec[0]).all() and (again[1] == spec[1]).all() and spec[0][:, 1:].sum() > 0
+        a.asm_end()
+
+
+# ---- 6. refusals ------------------------------------------------------------------------------------------------------------------------------
+def raises(pkg, code, call, *words):
+    with pytest.raises(pkg.SdtError) as e:
+        call()
+    assert e.value.code == code, str(e.value)
+    for w in words:
+        assert w in str(e.value), str(e.value)
+
+
+def test_refusals(pkg, synth):
+    case = tu.pair_case(synth, 31)
+    words, offs = synth.pack_2bit(case["a"][0]), case["a"][1]
+    with counted(pkg, synth, case["a"], 31, EST_A) as a, counted(pkg, synth, case["b"], 31, EST_A) as b:
+        before = a.kernel_time(reset=True)[1], b.kernel_time(reset=True)[1]
+
+        def tables(x, y, rows=64, cols=64, flags=0, reserved=0):
+            return pkg.compare_tables(x, y, params=pkg.CmpParams(rows, cols, flags, reserved))
+
+        with pkg.PregraphGPU(33, est_distinct=1 << 12) as other:
+            other.finish_count()
+            raises(pkg, pkg.SDT_EINVAL, lambda: tables(a, other), "sdt_gpu_compare_tables", "K = 31", "K = 33")
+            raises(pkg, pkg.SDT_EINVAL, lambda: pkg.compare_select(other, a), "sdt_gpu_compare_select", "K = 33", "K = 31")
+        with pkg.PregraphGPU(31, est_distinct=1 << 12, flags=pkg.SDT_FLAG_CONTIG_INDEX) as ctg:
+            raises(pkg, pkg.SDT_ESTATE, lambda: tables(a, ctg), "sdt_gpu_compare_tables: context B", "SDT_FLAG_CONTIG_INDEX")
+            raises(pkg, pkg.SDT_ESTATE, lambda: tables(ctg, a), "sdt_gpu_compare_tables: context A", "SDT_FLAG_CONTIG_INDEX")
+            raises(pkg, pkg.SDT_ESTATE, lambda: pkg.compare_select(a, ctg), "sdt_gpu_compare_select: context B", "SDT_FLAG_CONTIG_INDEX")
+        with pkg.PregraphGPU(31, est_distinct=1 << 16) as busy:
+            busy.push_reads(words, offs[:101])
+            raises(pkg, pkg.SDT_ESTATE, lambda: tables(a, busy), "context B", "sdt_gpu_finish_count")
+            raises(pkg, pkg.SDT_ESTATE, lambda: pkg.compare_select(busy, a), "context A", "sdt_gpu_finish_count")
+            busy.finish_count()
+            assert tables(busy, busy)[1][1] > 0                                    # drained: it answers
+        raises(pkg, pkg.SDT_EINVAL, lambda: tables(a, b, rows=1), "rows = 1")
+        raises(pkg, pkg.SDT_EINVAL, lambda: tables(a, b, cols=1), "cols = 1")
+        raises(pkg, pkg.SDT_EINVAL, lambda: tables(a, b, rows=5, cols=3277), "16385", "16384")
+        raises(pkg, pkg.SDT_EINVAL, lambda: tables(a, b, flags=4), "flags = 0x4")
+        raises(pkg, pkg.SDT_EINVAL, lambda: tables(a, b, reserved=9), "reserved = 9")
+        raises(pkg, pkg.SDT_EINVAL, lambda: pkg.compare_select(a, b, min_a=5, max_a=4), "min_a = 5", "max_a = 4")
+        raises(pkg, pkg.SDT_EINVAL, lambda: pkg.compare_select(a, b, min_b=2, max_b=1), "min_b = 2", "max_b = 1")
+        prm, rg, n = pkg.CmpParams(), pkg.CmpRange(), ctypes.c_uint64(77)
+        lib = a.lib
+        raises(pkg, pkg.SDT_EINVAL, lambda: a._check(lib.sdt_gpu_compare_tables(a._ctx, b._ctx, ctypes.addressof(prm), None, None)), "matrix and totals are both NULL")
+        raises(pkg, pkg.SDT_EINVAL, lambda: a._check(lib.sdt_gpu_compare_tables(a._ctx, b._ctx, None, None, None)), "sdt_cmp_params is NULL")
+        raises(pkg, pkg.SDT_EINVAL, lambda: a._check(lib.sdt_gpu_compare_tables(a._ctx, None, ctypes.addressof(prm), None, None)), "context B is NULL")
+        raises(pkg, pkg.SDT_EINVAL, lambda: a._check(lib.sdt_gpu_compare_select(a._ctx, b._ctx, ctypes.addressof(rg), None, None, None, 10, ctypes.byref(n))),
+               "capacity = 10", "every array is NULL")
+        assert n.value == 77                                                       # a refused call writes nothing
+        # nothing was launched by any refusal: the two contexts of the pair have booked no kernel since
+        assert (a.kernel_time(reset=False)[1], b.kernel_time(reset=False)[1]) == (0, 0) and before[0] >= 0
