@@ -798,8 +798,10 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  *                   their copies are still queued or they are counted and not yet synchronised.  *nreads = reads decided.  Mates are judged
  *                   independently.  The kept reads are NOT changed.
  * State: the dense forms need a context for its stream only: any state, any kind of context, like dedup_reads.  The kept form
- * follows the rules of sdt_gpu_kept_batches.  nreads == 0: SDT_OK, nothing touched.  There is NO limit on the read length: a
- * wavefront walks a read one window at a time (windows, low, start and len are 32-bit, as in sdt_read_trim).
+ * follows the rules of sdt_gpu_kept_batches and is stricter in one: it alone of the kept forms that need no table also refuses
+ * batches that are counted and not yet synchronised (above), as the forms on the counted table do; the others (fetch_kept_batch,
+ * dedup_, clip_, overlap_, merge_, screen_) refuse only batches whose launch is still queued.  nreads == 0: SDT_OK, nothing
+ * touched.  There is NO limit on the read length: a wavefront walks a read one window at a time (windows, low, start and len are 32-bit, as in sdt_read_trim).
  * SDT_EINVAL, from a check on the host before any launch, with a message that names the field and its value: NULL params; flag bits
  * other than SDT_COMPLEXITY_TRIM; max_score_pct 0 (every window would be low) or > 100; max_low_pct > 100; max_low_pct != 0 under
  * SDT_COMPLEXITY_TRIM.

@@ -3,14 +3,11 @@
 // kept in HBM.  Nothing here writes the table or the kept reads.  What is refused, and the adapters as the kernel takes them, are
 // sdt_read_plan.h's; staging in pieces and the kept batches are sdt_readstage.hpp's.  The records go to sdt_gpu_compact_trimmed as
 // they are: start, len and verdict sit where sdt_read_trim has them.
-#include "sdt_readstage.hpp"
+#include "sdt_compact.hpp"
 #include "sdt_clip_kernels.cuh"
-#include <cstddef>
 
 static_assert(sizeof(sdt_read_clip) == sizeof(ReadClip) && sizeof(sdt_clip_params) == sizeof(ClipParams), "include/sdt_gpu.h and the kernel agree");
-static_assert(offsetof(sdt_read_clip, start) == offsetof(sdt_read_trim, start) && offsetof(sdt_read_clip, len) == offsetof(sdt_read_trim, len) &&
-                  offsetof(sdt_read_clip, verdict) == offsetof(sdt_read_trim, verdict) && sizeof(sdt_read_clip) == sizeof(sdt_read_trim),
-              "sdt_gpu_compact_trimmed takes sdt_read_clip records through a pointer cast");
+static_assert(trim_layout_compatible<sdt_read_clip>(), "sdt_gpu_compact_trimmed takes sdt_read_clip records through a pointer cast");
 static_assert(SDT_CLIP_MAX_ADAPTERS == CLIP_MAX_ADAPTERS && SDT_CLIP_MAX_ADAPTER_LEN == CLIP_MAX_ADAPTER_LEN, "include/sdt_gpu.h and sdt_read_plan.h agree");
 
 // every refusal of the parameters and of the adapter set, before any launch
@@ -75,20 +72,9 @@ struct ClipState {
 static int clip_device(sdt_ctx *c, const ClipState &st, const uint32_t *d_words, const uint64_t *d_offs, uint64_t nreads, ReadClip *d_clip,
                        uint8_t *d_keep, uint64_t *n_kept)
 {
-	unsigned long long *ctr = (unsigned long long *)st.ctr.p, kept = 0;
-	HIPCHK(hipMemsetAsync(ctr, 0, sizeof *ctr, c->stream));
-	EventPair *ev = next_event(c);
-	if (ev) HIPCHK(hipEventRecord(ev->a, c->stream));
-	hipLaunchKernelGGL(k_clip_reads, dim3(wave_grid(c, nreads)), dim3(TPB), 0, c->stream, d_words, d_offs, nreads, st.prm, st.set, d_clip, d_keep, ctr);
-	HIPCHK(hipGetLastError());
-	if (ev) {
-		HIPCHK(hipEventRecord(ev->b, c->stream));
-		ev->kmers = nreads;                                  // (reads, not k-mers: sdt_gpu_kernel_time reports them as they are)
-	}
-	HIPCHK(hipMemcpyAsync(&kept, ctr, sizeof kept, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	if (n_kept) *n_kept += kept;
-	return SDT_OK;
+	return launch_counted(c, st.ctr, nreads, nreads, n_kept, [&](int grid, unsigned long long *ctr) {
+		hipLaunchKernelGGL(k_clip_reads, dim3(grid), dim3(TPB), 0, c->stream, d_words, d_offs, nreads, st.prm, st.set, d_clip, d_keep, ctr);
+	});
 }
 
 extern "C" {
@@ -131,19 +117,10 @@ int sdt_gpu_clip_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwords
 	ClipState st;
 	rc = st.prepare(params, adapters);
 	if (rc != SDT_OK) return rc;
-	DevBuf d_r, d_k;
-	uint64_t kept = 0;
-	rc = for_each_piece(c, packed_words, offsets, nreads, 1, "clip staging", [&](const StagedPiece &p) -> int {
-		int rc = d_r.reserve(p.nr * sizeof(ReadClip), "clip staging");
-		if (rc == SDT_OK) rc = d_k.reserve(p.nr, "clip staging");
-		if (rc == SDT_OK) rc = clip_device(c, st, p.d_words, p.d_offs, p.nr, (ReadClip *)d_r.p, (uint8_t *)d_k.p, &kept);
-		if (rc != SDT_OK) return rc;
-		HIPCHK(hipMemcpy(clip + p.r0, d_r.p, p.nr * sizeof(ReadClip), hipMemcpyDeviceToHost));
-		if (keep) HIPCHK(hipMemcpy(keep + p.r0, d_k.p, p.nr, hipMemcpyDeviceToHost));
-		return SDT_OK;
+	return staged_records<ReadClip>(c, packed_words, offsets, nreads, 1, "clip staging", clip, keep, n_kept,
+	                                [&](const StagedPiece &p, ReadClip *d_r, uint8_t *d_k, uint64_t *kept) {
+		return clip_device(c, st, p.d_words, p.d_offs, p.nr, d_r, d_k, kept);
 	});
-	if (rc == SDT_OK && n_kept) *n_kept = kept;
-	return rc;
 }
 
 int sdt_gpu_clip_kept_reads(sdt_ctx *c, const sdt_clip_params *params, const sdt_adapter_set *adapters, sdt_read_clip *clip,
@@ -157,9 +134,8 @@ int sdt_gpu_clip_kept_reads(sdt_ctx *c, const sdt_clip_params *params, const sdt
 	int rc = args_ok(params, adapters);
 	if (rc != SDT_OK) return rc;
 	rc = kept_ready(c);
+	if (rc == SDT_OK) rc = kept_drained(c, "sdt_gpu_clip_kept_reads", false);
 	if (rc != SDT_OK) return rc;
-	if (c->staged_head < c->staged.size())
-		return fail(SDT_ESTATE, "sdt_gpu_clip_kept_reads: batches were pushed and not drained: call sdt_gpu_finish_count first");
 	uint64_t total, most, npick;
 	rc = kept_span(c, out_capacity, "clip", &total, &most, &npick);
 	if (rc != SDT_OK) return rc;
@@ -170,18 +146,12 @@ int sdt_gpu_clip_kept_reads(sdt_ctx *c, const sdt_clip_params *params, const sdt
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	ClipState st;
 	rc = st.prepare(params, adapters);
-	// batch by batch: dense records on the device, scattered to their ordinals on the host
-	DevBuf d_r;
-	if (rc == SDT_OK) rc = d_r.get(most * sizeof(ReadClip), "clip records");
 	if (rc != SDT_OK) return rc;
-	std::vector<ReadClip> tmp(most);
 	uint64_t kept = 0;
-	for (const auto &kb : c->kept) {
-		if (!kb.nreads) continue;
-		rc = clip_device(c, st, kb.d_words, kb.d_offs, kb.nreads, (ReadClip *)d_r.p, nullptr, &kept);
-		if (rc == SDT_OK) rc = scatter_by_ordinal(clip, kb, d_r, tmp);
-		if (rc != SDT_OK) return rc;
-	}
+	rc = for_each_kept_batch<ReadClip>(c, clip, most, "clip records", [&](const sdt_ctx::KeptBatch &kb, ReadClip *d_r) {
+		return clip_device(c, st, kb.d_words, kb.d_offs, kb.nreads, d_r, nullptr, &kept);
+	});
+	if (rc != SDT_OK) return rc;
 	if (nreads) *nreads = total;
 	if (n_kept) *n_kept = kept;
 	return SDT_OK;

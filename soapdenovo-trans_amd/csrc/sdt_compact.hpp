@@ -1,9 +1,19 @@
 // sdt_compact.hpp -- the host side of the compaction of a 2-bit stream, shared by sdt_select.hip (whole kept reads) and sdt_trim.hip
-// (a kept range per read): two scans, a placement kernel of the caller's, k_compact_words; and the host form around it.
+// (a kept range per read): two scans, a placement kernel of the caller's, k_compact_words; and the host form around it.  And the
+// proof that the 24-byte records of the other stages are records of sdt_trim.hip's compaction.
 #pragma once
 #include "sdt_readstage.hpp"
 #include "sdt_select_kernels.cuh"
 #include <rocprim/rocprim.hpp>
+#include <cstddef>
+
+// the records of another stage go to sdt_gpu_compact_trimmed through a pointer cast: start, len and verdict sit where sdt_read_trim has them
+template <class T>
+constexpr bool trim_layout_compatible()
+{
+	return offsetof(T, start) == offsetof(sdt_read_trim, start) && offsetof(T, len) == offsetof(sdt_read_trim, len) &&
+	       offsetof(T, verdict) == offsetof(sdt_read_trim, verdict) && sizeof(T) == sizeof(sdt_read_trim);
+}
 
 // The compaction of one device-resident stream, checked arguments.  len_of(r) / flag_of(r): the bases read r contributes and whether it
 // contributes any, for r in [0, nreads] (0 at nreads).  place(grid, new_off, rank, src): enqueues the kernel that writes d_out_offs[rank[r]]

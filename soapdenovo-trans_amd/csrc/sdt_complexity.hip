@@ -3,15 +3,12 @@
 // table: the dense forms need the context for its stream only, the kept form for the reads kept in HBM.  Nothing here writes the table
 // or the kept reads.  What is refused and the windows are sdt_read_plan.h's; staging in pieces and the kept batches are
 // sdt_readstage.hpp's.  The records go to sdt_gpu_compact_trimmed as they are: start, len and verdict sit where sdt_read_trim has them.
-#include "sdt_readstage.hpp"
+#include "sdt_compact.hpp"
 #include "sdt_complexity_kernels.cuh"
-#include <cstddef>
 
 static_assert(sizeof(sdt_read_complexity) == sizeof(ReadComplexity) && sizeof(sdt_complexity_params) == sizeof(ComplexityParams),
               "include/sdt_gpu.h and the kernel agree");
-static_assert(offsetof(sdt_read_complexity, start) == offsetof(sdt_read_trim, start) && offsetof(sdt_read_complexity, len) == offsetof(sdt_read_trim, len) &&
-                  offsetof(sdt_read_complexity, verdict) == offsetof(sdt_read_trim, verdict) && sizeof(sdt_read_complexity) == sizeof(sdt_read_trim),
-              "sdt_gpu_compact_trimmed takes sdt_read_complexity records through a pointer cast");
+static_assert(trim_layout_compatible<sdt_read_complexity>(), "sdt_gpu_compact_trimmed takes sdt_read_complexity records through a pointer cast");
 static_assert(SDT_COMPLEXITY_TRIM == COMPLEXITY_TRIM, "include/sdt_gpu.h and sdt_read_plan.h agree");
 
 // every refusal of the parameters, before any launch
@@ -32,25 +29,14 @@ static int args_ok(const sdt_complexity_params *p)
 }
 
 // one dense device-resident batch, checked arguments: the kernel and the wait for its counter (ctr: one 64-bit word on the device)
-static int complexity_device(sdt_ctx *c, const DevBuf &ctr_buf, const uint32_t *d_words, const uint64_t *d_offs, uint64_t nreads,
+static int complexity_device(sdt_ctx *c, const DevBuf &ctr, const uint32_t *d_words, const uint64_t *d_offs, uint64_t nreads,
                              const sdt_complexity_params *p, ReadComplexity *d_cx, uint8_t *d_keep, uint64_t *n_kept)
 {
 	const ComplexityParams prm = {p->max_score_pct, p->max_low_pct, p->min_len, p->flags};
 	const DenseReads reads = {d_words, d_offs, nullptr, nreads};
-	unsigned long long *ctr = (unsigned long long *)ctr_buf.p, kept = 0;
-	HIPCHK(hipMemsetAsync(ctr, 0, sizeof *ctr, c->stream));
-	EventPair *ev = next_event(c);
-	if (ev) HIPCHK(hipEventRecord(ev->a, c->stream));
-	hipLaunchKernelGGL(k_complexity_reads<DenseReads>, dim3(wave_grid(c, nreads)), dim3(TPB), 0, c->stream, reads, prm, d_cx, d_keep, ctr);
-	HIPCHK(hipGetLastError());
-	if (ev) {
-		HIPCHK(hipEventRecord(ev->b, c->stream));
-		ev->kmers = nreads;                                  // (reads, not k-mers: sdt_gpu_kernel_time reports them as they are)
-	}
-	HIPCHK(hipMemcpyAsync(&kept, ctr, sizeof kept, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	if (n_kept) *n_kept += kept;
-	return SDT_OK;
+	return launch_counted(c, ctr, nreads, nreads, n_kept, [&](int grid, unsigned long long *d_ctr) {
+		hipLaunchKernelGGL(k_complexity_reads<DenseReads>, dim3(grid), dim3(TPB), 0, c->stream, reads, prm, d_cx, d_keep, d_ctr);
+	});
 }
 
 extern "C" {
@@ -91,21 +77,13 @@ int sdt_gpu_complexity_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t 
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc != SDT_OK) return rc;
 	SDT_ENTER(c);
-	DevBuf ctr, d_r, d_k;
+	DevBuf ctr;
 	rc = ctr.get(sizeof(unsigned long long), "complexity counter");
 	if (rc != SDT_OK) return rc;
-	uint64_t kept = 0;
-	rc = for_each_piece(c, packed_words, offsets, nreads, 1, "complexity staging", [&](const StagedPiece &p) -> int {
-		int rc = d_r.reserve(p.nr * sizeof(ReadComplexity), "complexity staging");
-		if (rc == SDT_OK) rc = d_k.reserve(p.nr, "complexity staging");
-		if (rc == SDT_OK) rc = complexity_device(c, ctr, p.d_words, p.d_offs, p.nr, params, (ReadComplexity *)d_r.p, (uint8_t *)d_k.p, &kept);
-		if (rc != SDT_OK) return rc;
-		HIPCHK(hipMemcpy(cx + p.r0, d_r.p, p.nr * sizeof(ReadComplexity), hipMemcpyDeviceToHost));
-		if (keep) HIPCHK(hipMemcpy(keep + p.r0, d_k.p, p.nr, hipMemcpyDeviceToHost));
-		return SDT_OK;
+	return staged_records<ReadComplexity>(c, packed_words, offsets, nreads, 1, "complexity staging", cx, keep, n_kept,
+	                                      [&](const StagedPiece &p, ReadComplexity *d_r, uint8_t *d_k, uint64_t *kept) {
+		return complexity_device(c, ctr, p.d_words, p.d_offs, p.nr, params, d_r, d_k, kept);
 	});
-	if (rc == SDT_OK && n_kept) *n_kept = kept;
-	return rc;
 }
 
 int sdt_gpu_complexity_kept_reads(sdt_ctx *c, const sdt_complexity_params *params, sdt_read_complexity *cx, uint64_t out_capacity, uint64_t *nreads,
@@ -119,10 +97,8 @@ int sdt_gpu_complexity_kept_reads(sdt_ctx *c, const sdt_complexity_params *param
 	int rc = args_ok(params);
 	if (rc != SDT_OK) return rc;
 	rc = kept_ready(c);
+	if (rc == SDT_OK) rc = kept_drained(c, "sdt_gpu_complexity_kept_reads", true);       // (as search_ready: stricter than the other table-free forms)
 	if (rc != SDT_OK) return rc;
-	// (what search_ready calls not drained: a batch whose copy is queued, or one that is counted and not yet synchronised)
-	if (c->staged_head < c->staged.size() || c->sk.pending_kmers || c->kmers_since_sync || c->hard_since_sync)
-		return fail(SDT_ESTATE, "sdt_gpu_complexity_kept_reads: batches were pushed and not drained: call sdt_gpu_finish_count first");
 	uint64_t total, most, npick;
 	rc = kept_span(c, out_capacity, "cx", &total, &most, &npick);
 	if (rc != SDT_OK) return rc;
@@ -131,19 +107,14 @@ int sdt_gpu_complexity_kept_reads(sdt_ctx *c, const sdt_complexity_params *param
 	if (!cx)
 		return fail(SDT_EINVAL, "NULL argument");
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
-	// batch by batch: dense records on the device, scattered to their ordinals on the host
-	DevBuf ctr, d_r;
+	DevBuf ctr;
 	rc = ctr.get(sizeof(unsigned long long), "complexity counter");
-	if (rc == SDT_OK) rc = d_r.get(most * sizeof(ReadComplexity), "complexity records");
 	if (rc != SDT_OK) return rc;
-	std::vector<ReadComplexity> tmp(most);
 	uint64_t kept = 0;
-	for (const auto &kb : c->kept) {
-		if (!kb.nreads) continue;
-		rc = complexity_device(c, ctr, kb.d_words, kb.d_offs, kb.nreads, params, (ReadComplexity *)d_r.p, nullptr, &kept);
-		if (rc == SDT_OK) rc = scatter_by_ordinal(cx, kb, d_r, tmp);
-		if (rc != SDT_OK) return rc;
-	}
+	rc = for_each_kept_batch<ReadComplexity>(c, cx, most, "complexity records", [&](const sdt_ctx::KeptBatch &kb, ReadComplexity *d_r) {
+		return complexity_device(c, ctr, kb.d_words, kb.d_offs, kb.nreads, params, d_r, nullptr, &kept);
+	});
+	if (rc != SDT_OK) return rc;
 	if (nreads) *nreads = total;
 	if (n_kept) *n_kept = kept;
 	return SDT_OK;

@@ -156,18 +156,12 @@ int sdt_gpu_correct_kept_reads(sdt_ctx *c, uint32_t min_count, sdt_read_fix *fix
 	if (!fix)
 		return fail(SDT_EINVAL, "NULL argument");
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
-	// batch by batch: dense records on the device, scattered to their ordinals on the host
-	DevBuf d_r, eb;
-	rc = d_r.get(most * sizeof(ReadFix), "correction records");
-	if (rc != SDT_OK) return rc;
-	std::vector<ReadFix> tmp(most);
+	DevBuf eb;
 	std::vector<uint64_t> all;
-	for (const auto &kb : c->kept) {
-		if (!kb.nreads) continue;
-		rc = correct_device_grow(c, kb.d_words, kb.nwords, kb.d_offs, kb.nreads, kb.maxlen, min_count, (ReadFix *)d_r.p, &eb, kb.ord_base, kb.ord_stride, &all);
-		if (rc == SDT_OK) rc = scatter_by_ordinal(fix, kb, d_r, tmp);
-		if (rc != SDT_OK) return rc;
-	}
+	rc = for_each_kept_batch<ReadFix>(c, fix, most, "correction records", [&](const sdt_ctx::KeptBatch &kb, ReadFix *d_r) {
+		return correct_device_grow(c, kb.d_words, kb.nwords, kb.d_offs, kb.nreads, kb.maxlen, min_count, d_r, &eb, kb.ord_base, kb.ord_stride, &all);
+	});
+	if (rc != SDT_OK) return rc;
 	if (nreads) *nreads = total;
 	return hand_over_edits(all, edits, max_edits, n_edits, "sdt_gpu_correct_kept_reads");
 }
@@ -186,12 +180,12 @@ int sdt_gpu_fetch_kept_batch(sdt_ctx *c, uint64_t i, uint64_t info[4], uint32_t 
 	if (!c || !info)
 		return fail(SDT_EINVAL, "NULL argument");
 	SDT_ENTER(c);
-	const int rc = kept_ready(c);
+	int rc = kept_ready(c);
 	if (rc != SDT_OK) return rc;
 	if (i >= c->kept.size())
 		return fail(SDT_EINVAL, "kept batch %llu of %zu", (unsigned long long)i, c->kept.size());
-	if (c->staged_head < c->staged.size())
-		return fail(SDT_ESTATE, "sdt_gpu_fetch_kept_batch: batches were pushed and not drained: call sdt_gpu_finish_count first");
+	rc = kept_drained(c, "sdt_gpu_fetch_kept_batch", false);
+	if (rc != SDT_OK) return rc;
 	const sdt_ctx::KeptBatch &kb = c->kept[i];
 	info[0] = kb.nwords;
 	info[1] = kb.nreads;

@@ -164,22 +164,10 @@ int sdt_gpu_dedup_kept_reads(sdt_ctx *c, const sdt_dedup_params *params, const u
 	if (nreads) *nreads = 0;
 	if (n_kept) *n_kept = 0;
 	int rc = params_ok(params, 0, 0);
+	if (rc == SDT_OK) rc = pair_ranges_ok(pair_ranges, n_ranges);
+	if (rc == SDT_OK) rc = kept_ready(c);
+	if (rc == SDT_OK) rc = kept_drained(c, "sdt_gpu_dedup_kept_reads", false);
 	if (rc != SDT_OK) return rc;
-	if (n_ranges && !pair_ranges)
-		return fail(SDT_EINVAL, "NULL argument");
-	PairRangeFault fault;
-	const uint64_t bad = check_pair_ranges(pair_ranges, n_ranges, &fault);
-	if (fault == PAIR_RANGE_NOT_PAIRS)
-		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) does not hold whole pairs", (unsigned long long)bad,
-		            (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1]);
-	if (fault == PAIR_RANGE_OVERLAPS)
-		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) starts before range %llu ends: ranges are ascending and disjoint",
-		            (unsigned long long)bad, (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1],
-		            (unsigned long long)(bad - 1));
-	rc = kept_ready(c);
-	if (rc != SDT_OK) return rc;
-	if (c->staged_head < c->staged.size())
-		return fail(SDT_ESTATE, "sdt_gpu_dedup_kept_reads: batches were pushed and not drained: call sdt_gpu_finish_count first");
 	uint64_t total, most, nord;
 	rc = kept_span(c, out_capacity, "dup", &total, &most, &nord);
 	if (rc != SDT_OK) return rc;
@@ -188,33 +176,26 @@ int sdt_gpu_dedup_kept_reads(sdt_ctx *c, const sdt_dedup_params *params, const u
 	if (!dup)
 		return fail(SDT_EINVAL, "NULL argument");
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
-	std::vector<UnitStretch> segs(2 * n_ranges + 1);
-	uint64_t units = 0;
-	segs.resize(cut_unit_stretches(pair_ranges, n_ranges, nord, segs.data(), &units));
-	// mates and copies sit in different kept batches: the entries and the records of ALL ordinals are on the device at once, the
-	// records preset to "no read"
+	// mates and copies sit in different kept batches: the entries and the records of ALL ordinals on the device at once
+	// (sdt_readstage.hpp: KeptUnits)
+	KeptUnits ku(pair_ranges, n_ranges, nord);
 	DedupState st;
-	DevBuf d_ent, d_dup, d_segs;
+	DevBuf d_ent, d_dup;
 	rc = d_ent.get(nord * sizeof(DedupEnt), "duplicate entries");
 	if (rc == SDT_OK) rc = d_dup.get(nord * sizeof(ReadDup), "duplicate records");
-	if (rc == SDT_OK) rc = d_segs.get(segs.size() * sizeof(UnitStretch), "duplicate units");
-	if (rc == SDT_OK) rc = st.reserve(units);
+	if (rc == SDT_OK) rc = ku.d_segs.get(ku.bytes(), "duplicate units");
+	if (rc == SDT_OK) rc = st.reserve(ku.units);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipMemsetAsync(d_ent.p, 0, nord * sizeof(DedupEnt), c->stream));
 	HIPCHK(hipMemsetAsync(d_dup.p, 0xFF, nord * sizeof(ReadDup), c->stream));
-	HIPCHK(hipMemcpyAsync(d_segs.p, segs.data(), segs.size() * sizeof(UnitStretch), hipMemcpyHostToDevice, c->stream));
+	rc = ku.upload(c);
+	if (rc != SDT_OK) return rc;
 	EventPair *ev = next_event(c);
 	if (ev) HIPCHK(hipEventRecord(ev->a, c->stream));
-	for (const auto &kb : c->kept) {
-		if (!kb.nreads) continue;
-		rc = launch_read_fp(c, kb.d_words, kb.d_offs, kb.nreads, nullptr, (DedupEnt *)d_ent.p, kb.ord_base, kb.ord_stride);
-		if (rc != SDT_OK) break;
-	}
+	rc = kept_entries(c, nord, d_ent);                       // (its memset of the entries is timed with the kernels)
 	uint64_t kept = 0;
 	if (rc == SDT_OK) {
 		const KeptReads reads = {(const DedupEnt *)d_ent.p, nord};
-		const Units U = {(const UnitStretch *)d_segs.p, (uint32_t)segs.size(), UnitStretch{0, 0, 1}, units};
-		rc = dedup_rounds(c, "sdt_gpu_dedup_kept_reads", st, reads, U, params->flags, (ReadDup *)d_dup.p, nullptr, &kept);
+		rc = dedup_rounds(c, "sdt_gpu_dedup_kept_reads", st, reads, ku.on_device(), params->flags, (ReadDup *)d_dup.p, nullptr, &kept);
 	}
 	if (ev) {
 		HIPCHK(hipEventRecord(ev->b, c->stream));
@@ -222,15 +203,8 @@ int sdt_gpu_dedup_kept_reads(sdt_ctx *c, const sdt_dedup_params *params, const u
 	}
 	HIPCHK(hipStreamSynchronize(c->stream));             // (segs may go)
 	if (rc != SDT_OK) return rc;
-	// back in blocks; the records of ordinals that no kept read has stay as the caller had them
-	const uint64_t block = 1ULL << 22;
-	std::vector<ReadDup> tmp((size_t)(nord < block ? nord : block));
-	for (uint64_t o0 = 0; o0 < nord; o0 += block) {
-		const uint64_t k = nord - o0 < block ? nord - o0 : block;
-		HIPCHK(hipMemcpy(tmp.data(), (const ReadDup *)d_dup.p + o0, k * sizeof(ReadDup), hipMemcpyDeviceToHost));
-		for (uint64_t i = 0; i < k; i++)
-			if (tmp[i].verdict != DUP_ABSENT) memcpy(dup + o0 + i, &tmp[i], sizeof(ReadDup));
-	}
+	rc = fetch_present<ReadDup>(dup, d_dup, nord, DUP_ABSENT);
+	if (rc != SDT_OK) return rc;
 	if (nreads) *nreads = total;
 	if (n_kept) *n_kept = kept;
 	return SDT_OK;

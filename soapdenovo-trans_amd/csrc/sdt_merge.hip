@@ -7,12 +7,9 @@
 // sdt_read_trim has them, and what comes out is the stream of the pairs that did not merge.
 #include "sdt_compact.hpp"
 #include "sdt_merge_kernels.cuh"
-#include <cstddef>
 
 static_assert(sizeof(sdt_read_merge) == sizeof(ReadMerge) && sizeof(sdt_merge_params) == sizeof(MergeParams), "include/sdt_gpu.h and the kernel agree");
-static_assert(offsetof(sdt_read_merge, start) == offsetof(sdt_read_trim, start) && offsetof(sdt_read_merge, len) == offsetof(sdt_read_trim, len) &&
-                  offsetof(sdt_read_merge, verdict) == offsetof(sdt_read_trim, verdict) && sizeof(sdt_read_merge) == sizeof(sdt_read_trim),
-              "sdt_gpu_compact_trimmed takes sdt_read_merge records through a pointer cast");
+static_assert(trim_layout_compatible<sdt_read_merge>(), "sdt_gpu_compact_trimmed takes sdt_read_merge records through a pointer cast");
 static_assert(SDT_MERGE_MERGED == MERGE_MERGED, "include/sdt_gpu.h and the kernel agree");
 
 // every refusal of the parameters, before any launch; dense_reads: 0 for the kept form
@@ -259,22 +256,10 @@ int sdt_gpu_merge_kept_pairs(sdt_ctx *c, const sdt_merge_params *params, const u
 	if (n_merged) *n_merged = 0;
 	if (n_out_words) *n_out_words = 0;
 	int rc = args_ok(params, false, 0);
+	if (rc == SDT_OK) rc = pair_ranges_ok(pair_ranges, n_ranges);
+	if (rc == SDT_OK) rc = kept_ready(c);
+	if (rc == SDT_OK) rc = kept_drained(c, "sdt_gpu_merge_kept_pairs", false);
 	if (rc != SDT_OK) return rc;
-	if (n_ranges && !pair_ranges)
-		return fail(SDT_EINVAL, "NULL argument");
-	PairRangeFault fault;
-	const uint64_t bad = check_pair_ranges(pair_ranges, n_ranges, &fault);
-	if (fault == PAIR_RANGE_NOT_PAIRS)
-		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) does not hold whole pairs", (unsigned long long)bad,
-		            (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1]);
-	if (fault == PAIR_RANGE_OVERLAPS)
-		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) starts before range %llu ends: ranges are ascending and disjoint",
-		            (unsigned long long)bad, (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1],
-		            (unsigned long long)(bad - 1));
-	rc = kept_ready(c);
-	if (rc != SDT_OK) return rc;
-	if (c->staged_head < c->staged.size())
-		return fail(SDT_ESTATE, "sdt_gpu_merge_kept_pairs: batches were pushed and not drained: call sdt_gpu_finish_count first");
 	uint64_t total, most, nord;
 	rc = kept_span(c, out_capacity, "mg", &total, &most, &nord);
 	if (rc != SDT_OK) return rc;
@@ -285,31 +270,23 @@ int sdt_gpu_merge_kept_pairs(sdt_ctx *c, const sdt_merge_params *params, const u
 	if (!ov || !mg || !out_words || !out_offsets)
 		return fail(SDT_EINVAL, "NULL argument");
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
-	std::vector<UnitStretch> segs(2 * n_ranges + 1);
-	uint64_t units = 0;
-	segs.resize(cut_unit_stretches(pair_ranges, n_ranges, nord, segs.data(), &units));
-	// as sdt_gpu_overlap_kept_pairs: the entries and the records of ALL ordinals are on the device at once, the new records preset to
-	// "no read"; the overlap records of ordinals that no kept read has are uploaded and never looked at
-	DevBuf d_ent, d_ov, d_mg, d_segs, d_ow, d_oo;
+	// as sdt_gpu_overlap_kept_pairs: the entries and the records of ALL ordinals on the device at once (sdt_readstage.hpp: KeptUnits);
+	// the overlap records of ordinals that no kept read has are uploaded and never looked at
+	KeptUnits ku(pair_ranges, n_ranges, nord);
+	DevBuf d_ent, d_ov, d_mg, d_ow, d_oo;
 	rc = d_ent.get(nord * sizeof(DedupEnt), "merge entries");
 	if (rc == SDT_OK) rc = d_ov.get(nord * sizeof(ReadOverlap), "merge overlap records");
 	if (rc == SDT_OK) rc = d_mg.get(nord * sizeof(ReadMerge), "merge records");
-	if (rc == SDT_OK) rc = d_segs.get(segs.size() * sizeof(UnitStretch), "merge units");
+	if (rc == SDT_OK) rc = ku.d_segs.get(ku.bytes(), "merge units");
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipMemsetAsync(d_ent.p, 0, nord * sizeof(DedupEnt), c->stream));
 	HIPCHK(hipMemsetAsync(d_mg.p, 0xFF, nord * sizeof(ReadMerge), c->stream));
 	HIPCHK(hipMemcpyAsync(d_ov.p, ov, nord * sizeof(ReadOverlap), hipMemcpyHostToDevice, c->stream));
-	HIPCHK(hipMemcpyAsync(d_segs.p, segs.data(), segs.size() * sizeof(UnitStretch), hipMemcpyHostToDevice, c->stream));
-	for (const auto &kb : c->kept) {
-		if (!kb.nreads) continue;
-		hipLaunchKernelGGL(k_read_fp, dim3(wave_grid(c, kb.nreads)), dim3(TPB), 0, c->stream, kb.d_words, kb.d_offs, kb.nreads, (uint64_t *)nullptr,
-		                   (DedupEnt *)d_ent.p, kb.ord_base, kb.ord_stride);
-		HIPCHK(hipGetLastError());
-	}
+	rc = ku.upload(c);
+	if (rc == SDT_OK) rc = kept_entries(c, nord, d_ent);
 	const KeptReads reads = {(const DedupEnt *)d_ent.p, nord};
-	const Units U = {(const UnitStretch *)d_segs.p, (uint32_t)segs.size(), UnitStretch{0, 0, 1}, units};
+	const Units U = ku.on_device();
 	MergePlan pl;
-	rc = merge_plan(c, reads, U, (const ReadOverlap *)d_ov.p, params, pl);   // (waits: segs may go)
+	if (rc == SDT_OK) rc = merge_plan(c, reads, U, (const ReadOverlap *)d_ov.p, params, pl);   // (waits)
 	if (rc != SDT_OK) return rc;
 	if (pl.first_bad != MERGE_NO_UNIT)
 		return fail(SDT_EINVAL, "the pair at ordinals %llu and %llu: the overlap records say inserts %u and %u: not one overlap of these mates",
@@ -328,15 +305,8 @@ int sdt_gpu_merge_kept_pairs(sdt_ctx *c, const sdt_merge_params *params, const u
 	if (rc != SDT_OK) return rc;
 	HIPCHK(hipMemcpy(out_words, d_ow.p, (pl.words + TAIL_PAD) * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(out_offsets, d_oo.p, (pl.merged + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-	// back in blocks; the records of ordinals that no kept read has stay as the caller had them
-	const uint64_t block = 1ULL << 22;
-	std::vector<ReadMerge> tmp((size_t)(nord < block ? nord : block));
-	for (uint64_t o0 = 0; o0 < nord; o0 += block) {
-		const uint64_t k = nord - o0 < block ? nord - o0 : block;
-		HIPCHK(hipMemcpy(tmp.data(), (const ReadMerge *)d_mg.p + o0, k * sizeof(ReadMerge), hipMemcpyDeviceToHost));
-		for (uint64_t i = 0; i < k; i++)
-			if (tmp[i].verdict != MERGE_ABSENT) memcpy(mg + o0 + i, &tmp[i], sizeof(ReadMerge));
-	}
+	rc = fetch_present<ReadMerge>(mg, d_mg, nord, MERGE_ABSENT);
+	if (rc != SDT_OK) return rc;
 	if (nreads) *nreads = total;
 	return SDT_OK;
 }

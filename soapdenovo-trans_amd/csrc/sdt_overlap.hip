@@ -4,14 +4,11 @@
 // reads.  What is refused, the check of the pair ranges and the cut of the units into stretches are sdt_read_plan.h's; staging in
 // pieces and the kept batches are sdt_readstage.hpp's.  The records go to sdt_gpu_compact_trimmed as they are: start, len and verdict
 // sit where sdt_read_trim has them.
-#include "sdt_readstage.hpp"
+#include "sdt_compact.hpp"
 #include "sdt_overlap_kernels.cuh"
-#include <cstddef>
 
 static_assert(sizeof(sdt_read_overlap) == sizeof(ReadOverlap) && sizeof(sdt_overlap_params) == sizeof(OverlapParams), "include/sdt_gpu.h and the kernel agree");
-static_assert(offsetof(sdt_read_overlap, start) == offsetof(sdt_read_trim, start) && offsetof(sdt_read_overlap, len) == offsetof(sdt_read_trim, len) &&
-                  offsetof(sdt_read_overlap, verdict) == offsetof(sdt_read_trim, verdict) && sizeof(sdt_read_overlap) == sizeof(sdt_read_trim),
-              "sdt_gpu_compact_trimmed takes sdt_read_overlap records through a pointer cast");
+static_assert(trim_layout_compatible<sdt_read_overlap>(), "sdt_gpu_compact_trimmed takes sdt_read_overlap records through a pointer cast");
 
 // every refusal of the parameters, before any launch; dense_reads: 0 for the kept form
 static int args_ok(const sdt_overlap_params *p, uint64_t dense_reads)
@@ -28,26 +25,15 @@ static int args_ok(const sdt_overlap_params *p, uint64_t dense_reads)
 	}
 }
 
-// the kernel over units whose reads are in place, and the wait for its counter (ctr: one zeroed-here 64-bit word on the device)
+// the kernel over units whose reads are in place, and the wait for its counter (ctr: one 64-bit word on the device)
 template <class Reads>
 static int overlap_launch(sdt_ctx *c, const Reads &reads, const Units &U, uint64_t nreads, const sdt_overlap_params *p, ReadOverlap *d_ov,
-                          uint8_t *d_keep, unsigned long long *ctr, uint64_t *n_kept)
+                          uint8_t *d_keep, const DevBuf &ctr, uint64_t *n_kept)
 {
 	const OverlapParams prm = {p->min_overlap, p->max_err_pct, p->min_len, p->flags};
-	unsigned long long kept = 0;
-	HIPCHK(hipMemsetAsync(ctr, 0, sizeof *ctr, c->stream));
-	EventPair *ev = next_event(c);
-	if (ev) HIPCHK(hipEventRecord(ev->a, c->stream));
-	hipLaunchKernelGGL(k_overlap_pairs<Reads>, dim3(wave_grid(c, U.n)), dim3(TPB), 0, c->stream, reads, U, prm, d_ov, d_keep, ctr);
-	HIPCHK(hipGetLastError());
-	if (ev) {
-		HIPCHK(hipEventRecord(ev->b, c->stream));
-		ev->kmers = nreads;                                  // (reads, not k-mers: sdt_gpu_kernel_time reports them as they are)
-	}
-	HIPCHK(hipMemcpyAsync(&kept, ctr, sizeof kept, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	if (n_kept) *n_kept += kept;
-	return SDT_OK;
+	return launch_counted(c, ctr, U.n, nreads, n_kept, [&](int grid, unsigned long long *d_ctr) {
+		hipLaunchKernelGGL(k_overlap_pairs<Reads>, dim3(grid), dim3(TPB), 0, c->stream, reads, U, prm, d_ov, d_keep, d_ctr);
+	});
 }
 
 // one dense device-resident batch of whole pairs, checked arguments
@@ -56,7 +42,7 @@ static int overlap_device(sdt_ctx *c, const DevBuf &ctr, const uint32_t *d_words
 {
 	const DenseReads reads = {d_words, d_offs, nullptr, nreads};
 	const Units U = {nullptr, 0, UnitStretch{0, 0, 2}, nreads / 2};
-	return overlap_launch(c, reads, U, nreads, p, d_ov, d_keep, (unsigned long long *)ctr.p, n_kept);
+	return overlap_launch(c, reads, U, nreads, p, d_ov, d_keep, ctr, n_kept);
 }
 
 extern "C" {
@@ -97,22 +83,14 @@ int sdt_gpu_overlap_pairs(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwo
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc != SDT_OK) return rc;
 	SDT_ENTER(c);
-	DevBuf ctr, d_r, d_k;
+	DevBuf ctr;
 	rc = ctr.get(sizeof(unsigned long long), "overlap counter");
 	if (rc != SDT_OK) return rc;
-	uint64_t kept = 0;
 	// step 2: the mates of a pair are never split between two pieces
-	rc = for_each_piece(c, packed_words, offsets, nreads, 2, "overlap staging", [&](const StagedPiece &p) -> int {
-		int rc = d_r.reserve(p.nr * sizeof(ReadOverlap), "overlap staging");
-		if (rc == SDT_OK) rc = d_k.reserve(p.nr, "overlap staging");
-		if (rc == SDT_OK) rc = overlap_device(c, ctr, p.d_words, p.d_offs, p.nr, params, (ReadOverlap *)d_r.p, (uint8_t *)d_k.p, &kept);
-		if (rc != SDT_OK) return rc;
-		HIPCHK(hipMemcpy(ov + p.r0, d_r.p, p.nr * sizeof(ReadOverlap), hipMemcpyDeviceToHost));
-		if (keep) HIPCHK(hipMemcpy(keep + p.r0, d_k.p, p.nr, hipMemcpyDeviceToHost));
-		return SDT_OK;
+	return staged_records<ReadOverlap>(c, packed_words, offsets, nreads, 2, "overlap staging", ov, keep, n_kept,
+	                                   [&](const StagedPiece &p, ReadOverlap *d_r, uint8_t *d_k, uint64_t *kept) {
+		return overlap_device(c, ctr, p.d_words, p.d_offs, p.nr, params, d_r, d_k, kept);
 	});
-	if (rc == SDT_OK && n_kept) *n_kept = kept;
-	return rc;
 }
 
 int sdt_gpu_overlap_kept_pairs(sdt_ctx *c, const sdt_overlap_params *params, const uint64_t *pair_ranges, uint64_t n_ranges, sdt_read_overlap *ov,
@@ -124,22 +102,10 @@ int sdt_gpu_overlap_kept_pairs(sdt_ctx *c, const sdt_overlap_params *params, con
 	if (nreads) *nreads = 0;
 	if (n_kept) *n_kept = 0;
 	int rc = args_ok(params, 0);
+	if (rc == SDT_OK) rc = pair_ranges_ok(pair_ranges, n_ranges);
+	if (rc == SDT_OK) rc = kept_ready(c);
+	if (rc == SDT_OK) rc = kept_drained(c, "sdt_gpu_overlap_kept_pairs", false);
 	if (rc != SDT_OK) return rc;
-	if (n_ranges && !pair_ranges)
-		return fail(SDT_EINVAL, "NULL argument");
-	PairRangeFault fault;
-	const uint64_t bad = check_pair_ranges(pair_ranges, n_ranges, &fault);
-	if (fault == PAIR_RANGE_NOT_PAIRS)
-		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) does not hold whole pairs", (unsigned long long)bad,
-		            (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1]);
-	if (fault == PAIR_RANGE_OVERLAPS)
-		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) starts before range %llu ends: ranges are ascending and disjoint",
-		            (unsigned long long)bad, (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1],
-		            (unsigned long long)(bad - 1));
-	rc = kept_ready(c);
-	if (rc != SDT_OK) return rc;
-	if (c->staged_head < c->staged.size())
-		return fail(SDT_ESTATE, "sdt_gpu_overlap_kept_pairs: batches were pushed and not drained: call sdt_gpu_finish_count first");
 	uint64_t total, most, nord;
 	rc = kept_span(c, out_capacity, "ov", &total, &most, &nord);
 	if (rc != SDT_OK) return rc;
@@ -148,40 +114,22 @@ int sdt_gpu_overlap_kept_pairs(sdt_ctx *c, const sdt_overlap_params *params, con
 	if (!ov)
 		return fail(SDT_EINVAL, "NULL argument");
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
-	std::vector<UnitStretch> segs(2 * n_ranges + 1);
-	uint64_t units = 0;
-	segs.resize(cut_unit_stretches(pair_ranges, n_ranges, nord, segs.data(), &units));
-	// mates sit in different kept batches: the entries and the records of ALL ordinals are on the device at once, the records preset
-	// to "no read".  The entries are k_read_fp's (sdt_dedup_kernels.cuh): where an ordinal's bases are; the fingerprint in them is not used.
-	DevBuf d_ent, d_ov, d_segs, ctr;
+	// the entries and the records of ALL ordinals on the device at once (sdt_readstage.hpp: KeptUnits); the fingerprint in an entry is not used
+	KeptUnits ku(pair_ranges, n_ranges, nord);
+	DevBuf d_ent, d_ov, ctr;
 	rc = d_ent.get(nord * sizeof(DedupEnt), "overlap entries");
 	if (rc == SDT_OK) rc = d_ov.get(nord * sizeof(ReadOverlap), "overlap records");
-	if (rc == SDT_OK) rc = d_segs.get(segs.size() * sizeof(UnitStretch), "overlap units");
+	if (rc == SDT_OK) rc = ku.d_segs.get(ku.bytes(), "overlap units");
 	if (rc == SDT_OK) rc = ctr.get(sizeof(unsigned long long), "overlap counter");
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipMemsetAsync(d_ent.p, 0, nord * sizeof(DedupEnt), c->stream));
 	HIPCHK(hipMemsetAsync(d_ov.p, 0xFF, nord * sizeof(ReadOverlap), c->stream));
-	HIPCHK(hipMemcpyAsync(d_segs.p, segs.data(), segs.size() * sizeof(UnitStretch), hipMemcpyHostToDevice, c->stream));
-	for (const auto &kb : c->kept) {
-		if (!kb.nreads) continue;
-		hipLaunchKernelGGL(k_read_fp, dim3(wave_grid(c, kb.nreads)), dim3(TPB), 0, c->stream, kb.d_words, kb.d_offs, kb.nreads, (uint64_t *)nullptr,
-		                   (DedupEnt *)d_ent.p, kb.ord_base, kb.ord_stride);
-		HIPCHK(hipGetLastError());
-	}
+	rc = ku.upload(c);
+	if (rc == SDT_OK) rc = kept_entries(c, nord, d_ent);
 	uint64_t kept = 0;
 	const KeptReads reads = {(const DedupEnt *)d_ent.p, nord};
-	const Units U = {(const UnitStretch *)d_segs.p, (uint32_t)segs.size(), UnitStretch{0, 0, 1}, units};
-	rc = overlap_launch(c, reads, U, total, params, (ReadOverlap *)d_ov.p, nullptr, (unsigned long long *)ctr.p, &kept);      // (waits: segs may go)
+	if (rc == SDT_OK) rc = overlap_launch(c, reads, ku.on_device(), total, params, (ReadOverlap *)d_ov.p, nullptr, ctr, &kept);     // (waits)
+	if (rc == SDT_OK) rc = fetch_present<ReadOverlap>(ov, d_ov, nord, OVERLAP_ABSENT);
 	if (rc != SDT_OK) return rc;
-	// back in blocks; the records of ordinals that no kept read has stay as the caller had them
-	const uint64_t block = 1ULL << 22;
-	std::vector<ReadOverlap> tmp((size_t)(nord < block ? nord : block));
-	for (uint64_t o0 = 0; o0 < nord; o0 += block) {
-		const uint64_t k = nord - o0 < block ? nord - o0 : block;
-		HIPCHK(hipMemcpy(tmp.data(), (const ReadOverlap *)d_ov.p + o0, k * sizeof(ReadOverlap), hipMemcpyDeviceToHost));
-		for (uint64_t i = 0; i < k; i++)
-			if (tmp[i].verdict != OVERLAP_ABSENT) memcpy(ov + o0 + i, &tmp[i], sizeof(ReadOverlap));
-	}
 	if (nreads) *nreads = total;
 	if (n_kept) *n_kept = kept;
 	return SDT_OK;

@@ -4,15 +4,12 @@
 // in HBM carry no qualities.  What is refused, the table of expected errors and the cut of a byte stream into pieces are
 // sdt_read_plan.h's; staging the pieces is sdt_readstage.hpp's.  The records go to sdt_gpu_compact_trimmed as they are: start, len
 // and verdict sit where sdt_read_trim has them.
-#include "sdt_readstage.hpp"
+#include "sdt_compact.hpp"
 #include "sdt_quality_kernels.cuh"
-#include <cstddef>
 
 static_assert(sizeof(sdt_read_quality) == sizeof(ReadQuality) && sizeof(sdt_quality_params) == sizeof(QualityParams),
               "include/sdt_gpu.h and the kernel agree");
-static_assert(offsetof(sdt_read_quality, start) == offsetof(sdt_read_trim, start) && offsetof(sdt_read_quality, len) == offsetof(sdt_read_trim, len) &&
-                  offsetof(sdt_read_quality, verdict) == offsetof(sdt_read_trim, verdict) && sizeof(sdt_read_quality) == sizeof(sdt_read_trim),
-              "sdt_gpu_compact_trimmed takes sdt_read_quality records through a pointer cast");
+static_assert(trim_layout_compatible<sdt_read_quality>(), "sdt_gpu_compact_trimmed takes sdt_read_quality records through a pointer cast");
 
 static QualityParams kernel_params(const sdt_quality_params *p)
 {
@@ -36,23 +33,12 @@ static int args_ok(const sdt_quality_params *p)
 }
 
 // one device-resident batch, checked arguments: the kernel and the wait for its counter (ctr: one 64-bit word on the device)
-static int quality_device(sdt_ctx *c, const DevBuf &ctr_buf, const uint8_t *d_quals, const uint64_t *d_offs, uint64_t nreads, const sdt_quality_params *p,
+static int quality_device(sdt_ctx *c, const DevBuf &ctr, const uint8_t *d_quals, const uint64_t *d_offs, uint64_t nreads, const sdt_quality_params *p,
                           ReadQuality *d_out, uint8_t *d_keep, uint64_t *n_kept)
 {
-	unsigned long long *ctr = (unsigned long long *)ctr_buf.p, kept = 0;
-	HIPCHK(hipMemsetAsync(ctr, 0, sizeof *ctr, c->stream));
-	EventPair *ev = next_event(c);
-	if (ev) HIPCHK(hipEventRecord(ev->a, c->stream));
-	hipLaunchKernelGGL(k_quality_reads, dim3(wave_grid(c, nreads)), dim3(TPB), 0, c->stream, d_quals, d_offs, nreads, kernel_params(p), d_out, d_keep, ctr);
-	HIPCHK(hipGetLastError());
-	if (ev) {
-		HIPCHK(hipEventRecord(ev->b, c->stream));
-		ev->kmers = nreads;                                  // (reads, not k-mers: sdt_gpu_kernel_time reports them as they are)
-	}
-	HIPCHK(hipMemcpyAsync(&kept, ctr, sizeof kept, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	if (n_kept) *n_kept += kept;
-	return SDT_OK;
+	return launch_counted(c, ctr, nreads, nreads, n_kept, [&](int grid, unsigned long long *d_ctr) {
+		hipLaunchKernelGGL(k_quality_reads, dim3(grid), dim3(TPB), 0, c->stream, d_quals, d_offs, nreads, kernel_params(p), d_out, d_keep, d_ctr);
+	});
 }
 
 extern "C" {

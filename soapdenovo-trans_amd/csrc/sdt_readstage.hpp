@@ -2,11 +2,14 @@
 // sdt_correct.hip, sdt_select.hip (normalise) and sdt_trim.hip do the same way.  A stage is a strip kernel (one wavefront per read,
 // its k-mers' counts in a strip of LDS) with up to three forms: a device-resident batch, a host batch staged in pieces, and the
 // reads kept in HBM with records by read ordinal.  The decisions themselves are pure functions in sdt_read_plan.h; here they meet
-// the context, the stream and the messages.  Each stage keeps its kernel's own arguments and nothing else of this.
+// the context, the stream and the messages.  Each stage keeps its kernel's own arguments and nothing else of this.  The stages that
+// need no counted table (clip, overlap, complexity, quality, screen, dedup, merge) have the same three forms around a kernel that
+// counts what it keeps: their launch, their staged host form, and the kept form over pairs, are the last section.
 #pragma once
 #include "sdt_ctx.hpp"
 #include "sdt_read_plan.h"
 #include "sdt_search_kernels.cuh"
+#include "sdt_dedup_kernels.cuh"
 #include <type_traits>
 
 // ---- sdt_search.hip ----
@@ -217,6 +220,19 @@ static int kept_span(const sdt_ctx *c, uint64_t out_capacity, const char *array_
 	return SDT_OK;
 }
 
+// The state rule of every kept form, with its one message: no batch whose launch is still queued; also_counted: and none that is
+// counted and not yet synchronised (sdt_gpu_finish_count ends both).  Who passes what today:
+//   true   search_ready, and so the forms on the counted table (profile_, correct_, trim_, select_kept_reads); sdt_gpu_complexity_kept_reads
+//   false  sdt_gpu_dedup_kept_reads, clip_kept_reads, overlap_kept_pairs, merge_kept_pairs, screen_kept_reads, sdt_gpu_fetch_kept_batch
+// The table-free forms read the kept reads only, and those are whole once their copy is; that complexity_ is stricter than its
+// siblings is how it was written, not a need of its kernel.  A change of the rule is a change of these arguments.
+static int kept_drained(const sdt_ctx *c, const char *entry, bool also_counted)
+{
+	if (c->staged_head < c->staged.size() || (also_counted && (c->sk.pending_kmers || c->kmers_since_sync || c->hard_since_sync)))
+		return fail(SDT_ESTATE, "%s: batches were pushed and not drained: call sdt_gpu_finish_count first", entry);
+	return SDT_OK;
+}
+
 // the dense records of one kept batch from the device to their ordinals in out[] (nothing else of out[] is touched)
 template <class Rec>
 static int scatter_by_ordinal(void *out, const sdt_ctx::KeptBatch &kb, const DevBuf &d_rec, std::vector<Rec> &tmp)
@@ -224,5 +240,134 @@ static int scatter_by_ordinal(void *out, const sdt_ctx::KeptBatch &kb, const Dev
 	HIPCHK(hipMemcpy(tmp.data(), d_rec.p, kb.nreads * sizeof(Rec), hipMemcpyDeviceToHost));
 	for (uint64_t i = 0; i < kb.nreads; i++)
 		memcpy((char *)out + (kb.ord_base + i * kb.ord_stride) * sizeof(Rec), &tmp[i], sizeof(Rec));
+	return SDT_OK;
+}
+
+// The kept form, batch by batch: dense records of `most` reads on the device, device_fn(kb, d_rec) runs the stage on one non-empty
+// batch and waits for it, and the records go to their ordinals in out[] on the host.
+template <class Rec, class DeviceFn>
+static int for_each_kept_batch(sdt_ctx *c, void *out, uint64_t most, const char *what, DeviceFn device_fn)
+{
+	DevBuf d_r;
+	int rc = d_r.get(most * sizeof(Rec), what);
+	if (rc != SDT_OK) return rc;
+	std::vector<Rec> tmp(most);
+	for (const auto &kb : c->kept) {
+		if (!kb.nreads) continue;
+		rc = device_fn(kb, (Rec *)d_r.p);
+		if (rc == SDT_OK) rc = scatter_by_ordinal(out, kb, d_r, tmp);
+		if (rc != SDT_OK) return rc;
+	}
+	return SDT_OK;
+}
+
+// ---- the record stages that need no counted table (clip, overlap, complexity, quality, screen, dedup, merge) ----
+// One kernel that counts what it keeps in a 64-bit word on the device: the word zeroed, the launch between the events of
+// sdt_gpu_kernel_time (as timed_reads reads, not k-mers), the word read back, which waits, and added to *n_kept.  fn(grid, counter)
+// issues the one hipLaunchKernelGGL; grid: every wavefront one of grid_items and strides over the rest.
+template <class Fn>
+static int launch_counted(sdt_ctx *c, const DevBuf &ctr_buf, uint64_t grid_items, uint64_t timed_reads, uint64_t *n_kept, Fn fn)
+{
+	unsigned long long *ctr = (unsigned long long *)ctr_buf.p, kept = 0;
+	HIPCHK(hipMemsetAsync(ctr, 0, sizeof *ctr, c->stream));
+	EventPair *ev = next_event(c);
+	if (ev) HIPCHK(hipEventRecord(ev->a, c->stream));
+	fn(wave_grid(c, grid_items), ctr);
+	HIPCHK(hipGetLastError());
+	if (ev) {
+		HIPCHK(hipEventRecord(ev->b, c->stream));
+		ev->kmers = timed_reads;
+	}
+	HIPCHK(hipMemcpyAsync(&kept, ctr, sizeof kept, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	if (n_kept) *n_kept += kept;
+	return SDT_OK;
+}
+
+// The staged host form of a stage with records and a keep mask: device_fn(piece, d_rec, d_keep, &kept) runs the stage on one piece
+// and waits for it; its records go to rec + piece.r0, its mask to keep + piece.r0 (keep may be NULL), the sum of kept to *n_kept.
+template <class Rec, class DeviceFn>
+static int staged_records(sdt_ctx *c, const uint32_t *words, const uint64_t *offsets, uint64_t nreads, uint64_t step, const char *what, void *rec,
+                          uint8_t *keep, uint64_t *n_kept, DeviceFn device_fn)
+{
+	DevBuf d_r, d_k;
+	uint64_t kept = 0;
+	const int rc = for_each_piece(c, words, offsets, nreads, step, what, [&](const StagedPiece &p) -> int {
+		int rc = d_r.reserve(p.nr * sizeof(Rec), what);
+		if (rc == SDT_OK) rc = d_k.reserve(p.nr, what);
+		if (rc == SDT_OK) rc = device_fn(p, (Rec *)d_r.p, (uint8_t *)d_k.p, &kept);
+		if (rc != SDT_OK) return rc;
+		HIPCHK(hipMemcpy((Rec *)rec + p.r0, d_r.p, p.nr * sizeof(Rec), hipMemcpyDeviceToHost));
+		if (keep) HIPCHK(hipMemcpy(keep + p.r0, d_k.p, p.nr, hipMemcpyDeviceToHost));
+		return SDT_OK;
+	});
+	if (rc == SDT_OK && n_kept) *n_kept = kept;
+	return rc;
+}
+
+// the pair ranges of a kept form: ascending, disjoint, whole pairs (sdt_read_plan.h: check_pair_ranges), with the messages
+static int pair_ranges_ok(const uint64_t *pair_ranges, uint64_t n_ranges)
+{
+	if (n_ranges && !pair_ranges)
+		return fail(SDT_EINVAL, "NULL argument");
+	PairRangeFault fault;
+	const uint64_t bad = check_pair_ranges(pair_ranges, n_ranges, &fault);
+	if (fault == PAIR_RANGE_NOT_PAIRS)
+		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) does not hold whole pairs", (unsigned long long)bad,
+		            (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1]);
+	if (fault == PAIR_RANGE_OVERLAPS)
+		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) starts before range %llu ends: ranges are ascending and disjoint",
+		            (unsigned long long)bad, (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1],
+		            (unsigned long long)(bad - 1));
+	return SDT_OK;
+}
+
+// The kept form over pairs: mates sit in different kept batches, so the records of ALL nord ordinals are on the device at once,
+// preset to "no read" (0xFF), and the units are stretches of single reads and of pairs (sdt_read_plan.h: cut_unit_stretches; nord may
+// cut a pair: its first mate is a unit, the kernel finds no second).  The caller reserves d_segs with its other buffers.
+struct KeptUnits {
+	std::vector<UnitStretch> segs;
+	uint64_t units = 0;
+	DevBuf d_segs;
+	KeptUnits(const uint64_t *pair_ranges, uint64_t n_ranges, uint64_t nord) : segs(2 * n_ranges + 1)
+	{
+		segs.resize(cut_unit_stretches(pair_ranges, n_ranges, nord, segs.data(), &units));
+	}
+	size_t bytes() const { return segs.size() * sizeof(UnitStretch); }
+	// (segs has to stay until the stream was waited for)
+	int upload(sdt_ctx *c)
+	{
+		HIPCHK(hipMemcpyAsync(d_segs.p, segs.data(), bytes(), hipMemcpyHostToDevice, c->stream));
+		return SDT_OK;
+	}
+	Units on_device() const { return Units{(const UnitStretch *)d_segs.p, (uint32_t)segs.size(), UnitStretch{0, 0, 1}, units}; }
+};
+
+// where the bases of every ordinal are, and their fingerprint for sdt_dedup.hip: d_ent[nord] zeroed, then k_read_fp
+// (sdt_dedup_kernels.cuh) per kept batch
+static int kept_entries(sdt_ctx *c, uint64_t nord, const DevBuf &d_ent)
+{
+	HIPCHK(hipMemsetAsync(d_ent.p, 0, nord * sizeof(DedupEnt), c->stream));
+	for (const auto &kb : c->kept) {
+		if (!kb.nreads) continue;
+		hipLaunchKernelGGL(k_read_fp, dim3(wave_grid(c, kb.nreads)), dim3(TPB), 0, c->stream, kb.d_words, kb.d_offs, kb.nreads, (uint64_t *)nullptr,
+		                   (DedupEnt *)d_ent.p, kb.ord_base, kb.ord_stride);
+		HIPCHK(hipGetLastError());
+	}
+	return SDT_OK;
+}
+
+// the records by ordinal back in blocks; those of ordinals that no kept read has (verdict == absent) stay as the caller had them
+template <class Rec>
+static int fetch_present(void *out, const DevBuf &d_rec, uint64_t nord, uint32_t absent)
+{
+	const uint64_t block = 1ULL << 22;
+	std::vector<Rec> tmp((size_t)(nord < block ? nord : block));
+	for (uint64_t o0 = 0; o0 < nord; o0 += block) {
+		const uint64_t k = nord - o0 < block ? nord - o0 : block;
+		HIPCHK(hipMemcpy(tmp.data(), (const Rec *)d_rec.p + o0, k * sizeof(Rec), hipMemcpyDeviceToHost));
+		for (uint64_t i = 0; i < k; i++)
+			if (tmp[i].verdict != absent) memcpy((Rec *)out + o0 + i, &tmp[i], sizeof(Rec));
+	}
 	return SDT_OK;
 }

@@ -5,14 +5,11 @@
 // refused, the size of the table and the unit verdicts of the kept form are sdt_read_plan.h's; staging in pieces and the kept batches
 // are sdt_readstage.hpp's.  The records go to sdt_gpu_compact_trimmed as they are: start, len and verdict sit where sdt_read_trim has
 // them.
-#include "sdt_readstage.hpp"
+#include "sdt_compact.hpp"
 #include "sdt_screen_kernels.cuh"
-#include <cstddef>
 
 static_assert(sizeof(sdt_read_screen) == sizeof(ReadScreen) && sizeof(sdt_screen_params) == sizeof(ScreenParams), "include/sdt_gpu.h and the kernel agree");
-static_assert(offsetof(sdt_read_screen, start) == offsetof(sdt_read_trim, start) && offsetof(sdt_read_screen, len) == offsetof(sdt_read_trim, len) &&
-                  offsetof(sdt_read_screen, verdict) == offsetof(sdt_read_trim, verdict) && sizeof(sdt_read_screen) == sizeof(sdt_read_trim),
-              "sdt_gpu_compact_trimmed takes sdt_read_screen records through a pointer cast");
+static_assert(trim_layout_compatible<sdt_read_screen>(), "sdt_gpu_compact_trimmed takes sdt_read_screen records through a pointer cast");
 static_assert(SDT_SCREEN_KEEP_MATCHED == SCREEN_KEEP_MATCHED && SDT_SCREEN_NO_REF == SCREEN_NO_REF, "include/sdt_gpu.h and sdt_read_plan.h agree");
 
 // every refusal of the parameters, before any launch
@@ -41,27 +38,15 @@ static int set_ready(const sdt_ctx *c, const char *what)
 static ScreenTable table_of_set(const sdt_ctx *c) { return ScreenTable{(ScreenSlot *)c->screen.tab, c->screen.slots - 1, c->screen.k}; }
 
 // one dense device-resident batch, checked arguments: the kernel and the wait for its counter (ctr: one 64-bit word on the device)
-static int screen_device(sdt_ctx *c, const DevBuf &ctr_buf, const uint32_t *d_words, const uint64_t *d_offs, uint64_t nreads, int paired,
+static int screen_device(sdt_ctx *c, const DevBuf &ctr, const uint32_t *d_words, const uint64_t *d_offs, uint64_t nreads, int paired,
                          const ScreenParams &prm, ReadScreen *d_out, uint8_t *d_keep, uint64_t *n_kept)
 {
 	const DenseReads reads = {d_words, d_offs, nullptr, nreads};
 	const uint32_t stride = paired ? 2u : 1u;
 	const uint64_t units = nreads / stride;
-	unsigned long long *ctr = (unsigned long long *)ctr_buf.p, kept = 0;
-	HIPCHK(hipMemsetAsync(ctr, 0, sizeof *ctr, c->stream));
-	EventPair *ev = next_event(c);
-	if (ev) HIPCHK(hipEventRecord(ev->a, c->stream));
-	hipLaunchKernelGGL(k_screen_reads, dim3(wave_grid(c, units)), dim3(TPB), 0, c->stream, reads, units, stride, table_of_set(c), prm, d_out, d_keep,
-	                   ctr);
-	HIPCHK(hipGetLastError());
-	if (ev) {
-		HIPCHK(hipEventRecord(ev->b, c->stream));
-		ev->kmers = nreads;                                  // (reads, not k-mers: sdt_gpu_kernel_time reports them as they are)
-	}
-	HIPCHK(hipMemcpyAsync(&kept, ctr, sizeof kept, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	if (n_kept) *n_kept += kept;
-	return SDT_OK;
+	return launch_counted(c, ctr, units, nreads, n_kept, [&](int grid, unsigned long long *d_ctr) {
+		hipLaunchKernelGGL(k_screen_reads, dim3(grid), dim3(TPB), 0, c->stream, reads, units, stride, table_of_set(c), prm, d_out, d_keep, d_ctr);
+	});
 }
 
 static ScreenParams params_of(const sdt_screen_params *p) { return ScreenParams{p->min_hits, p->min_hit_pct, p->flags, p->reserved}; }
@@ -216,22 +201,14 @@ int sdt_gpu_screen_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwor
 	rc = stream_args_ok(offsets, nreads, nwords, &in);
 	if (rc != SDT_OK) return rc;
 	SDT_ENTER(c);
-	DevBuf ctr, d_r, d_k;
+	DevBuf ctr;
 	rc = ctr.get(sizeof(unsigned long long), "screen counter");
 	if (rc != SDT_OK) return rc;
-	uint64_t kept = 0;
 	// (the mates of a pair stay in one piece)
-	rc = for_each_piece(c, packed_words, offsets, nreads, paired ? 2 : 1, "screen staging", [&](const StagedPiece &p) -> int {
-		int rc = d_r.reserve(p.nr * sizeof(ReadScreen), "screen staging");
-		if (rc == SDT_OK) rc = d_k.reserve(p.nr, "screen staging");
-		if (rc == SDT_OK) rc = screen_device(c, ctr, p.d_words, p.d_offs, p.nr, paired, params_of(params), (ReadScreen *)d_r.p, (uint8_t *)d_k.p, &kept);
-		if (rc != SDT_OK) return rc;
-		HIPCHK(hipMemcpy(out + p.r0, d_r.p, p.nr * sizeof(ReadScreen), hipMemcpyDeviceToHost));
-		if (keep) HIPCHK(hipMemcpy(keep + p.r0, d_k.p, p.nr, hipMemcpyDeviceToHost));
-		return SDT_OK;
+	return staged_records<ReadScreen>(c, packed_words, offsets, nreads, paired ? 2 : 1, "screen staging", out, keep, n_kept,
+	                                  [&](const StagedPiece &p, ReadScreen *d_r, uint8_t *d_k, uint64_t *kept) {
+		return screen_device(c, ctr, p.d_words, p.d_offs, p.nr, paired, params_of(params), d_r, d_k, kept);
 	});
-	if (rc == SDT_OK && n_kept) *n_kept = kept;
-	return rc;
 }
 
 int sdt_gpu_screen_kept_reads(sdt_ctx *c, const sdt_screen_params *params, const uint64_t *pair_ranges, uint64_t n_ranges, sdt_read_screen *out,
@@ -243,23 +220,11 @@ int sdt_gpu_screen_kept_reads(sdt_ctx *c, const sdt_screen_params *params, const
 	if (nreads) *nreads = 0;
 	if (n_kept) *n_kept = 0;
 	int rc = args_ok(params, 0, 0);
-	if (rc != SDT_OK) return rc;
-	if (n_ranges && !pair_ranges)
-		return fail(SDT_EINVAL, "NULL argument");
-	PairRangeFault fault;
-	const uint64_t bad = check_pair_ranges(pair_ranges, n_ranges, &fault);
-	if (fault == PAIR_RANGE_NOT_PAIRS)
-		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) does not hold whole pairs", (unsigned long long)bad,
-		            (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1]);
-	if (fault == PAIR_RANGE_OVERLAPS)
-		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) starts before range %llu ends: ranges are ascending and disjoint",
-		            (unsigned long long)bad, (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1],
-		            (unsigned long long)(bad - 1));
-	rc = set_ready(c, "sdt_gpu_screen_kept_reads");
+	if (rc == SDT_OK) rc = pair_ranges_ok(pair_ranges, n_ranges);
+	if (rc == SDT_OK) rc = set_ready(c, "sdt_gpu_screen_kept_reads");
 	if (rc == SDT_OK) rc = kept_ready(c);
+	if (rc == SDT_OK) rc = kept_drained(c, "sdt_gpu_screen_kept_reads", false);
 	if (rc != SDT_OK) return rc;
-	if (c->staged_head < c->staged.size())
-		return fail(SDT_ESTATE, "sdt_gpu_screen_kept_reads: batches were pushed and not drained: call sdt_gpu_finish_count first");
 	uint64_t total, most, nord;
 	rc = kept_span(c, out_capacity, "out", &total, &most, &nord);
 	if (rc != SDT_OK) return rc;
@@ -270,21 +235,18 @@ int sdt_gpu_screen_kept_reads(sdt_ctx *c, const sdt_screen_params *params, const
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	// batch by batch: what every read has on its own, dense on the device, scattered to the ordinals of a copy on the host; mates sit
 	// in different batches, so the unit verdicts are taken there (sdt_read_plan.h) before anything of out[] is written
-	DevBuf ctr, d_r;
+	DevBuf ctr;
 	rc = ctr.get(sizeof(unsigned long long), "screen counter");
-	if (rc == SDT_OK) rc = d_r.get(most * sizeof(ReadScreen), "screen records");
 	if (rc != SDT_OK) return rc;
 	ScreenParams per_read = params_of(params);
 	per_read.flags |= SCREEN_PER_READ;
-	std::vector<ReadScreen> tmp(most), rec(nord);
+	std::vector<ReadScreen> rec(nord);
 	std::vector<uint8_t> present(nord, 0);
-	for (const auto &kb : c->kept) {
-		if (!kb.nreads) continue;
-		rc = screen_device(c, ctr, kb.d_words, kb.d_offs, kb.nreads, 0, per_read, (ReadScreen *)d_r.p, nullptr, nullptr);
-		if (rc == SDT_OK) rc = scatter_by_ordinal(rec.data(), kb, d_r, tmp);
-		if (rc != SDT_OK) return rc;
+	rc = for_each_kept_batch<ReadScreen>(c, rec.data(), most, "screen records", [&](const sdt_ctx::KeptBatch &kb, ReadScreen *d_r) {
 		for (uint64_t i = 0; i < kb.nreads; i++) present[kb.ord_base + i * kb.ord_stride] = 1;
-	}
+		return screen_device(c, ctr, kb.d_words, kb.d_offs, kb.nreads, 0, per_read, d_r, nullptr, nullptr);
+	});
+	if (rc != SDT_OK) return rc;
 	const uint64_t kept = screen_unit_verdicts(rec.data(), present.data(), nord, pair_ranges, n_ranges, params_of(params));
 	for (uint64_t o = 0; o < nord; o++)
 		if (present[o]) memcpy(out + o, &rec[o], sizeof(ReadScreen));

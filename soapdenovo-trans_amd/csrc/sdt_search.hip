@@ -26,9 +26,7 @@ int search_ready(sdt_ctx *c, const char *what)
 		return fail(SDT_ESTATE, "%s: the counters were overwritten by path words (sdt_gpu_load_paths / sdt_gpu_import_paths)", what);
 	if (!c->d_ent || !c->d_aux || c->slots == 0)
 		return fail(SDT_ESTATE, "%s: the node table was released (sdt_gpu_release_table)", what);
-	if (c->staged_head < c->staged.size() || c->sk.pending_kmers || c->kmers_since_sync || c->hard_since_sync)
-		return fail(SDT_ESTATE, "%s: batches were pushed and not drained: call sdt_gpu_finish_count first", what);
-	return SDT_OK;
+	return kept_drained(c, what, true);
 }
 
 int flags_reserve(sdt_ctx *c)
@@ -218,17 +216,10 @@ int sdt_gpu_profile_kept_reads(sdt_ctx *c, uint32_t min_count, sdt_read_cov *out
 		return fail(SDT_EINVAL, "NULL argument");
 	SDT_ENTER(c);
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
-	// batch by batch: dense records on the device, scattered to their ordinals on the host
-	DevBuf d_r;
-	rc = d_r.get(most * sizeof(ReadCov), "profile records");
+	rc = for_each_kept_batch<ReadCov>(c, out, most, "profile records", [&](const sdt_ctx::KeptBatch &kb, ReadCov *d_r) {
+		return profile_device(c, kb.d_words, kb.d_offs, kb.nreads, kb.maxlen, min_count, d_r);
+	});
 	if (rc != SDT_OK) return rc;
-	std::vector<ReadCov> tmp(most);
-	for (const auto &kb : c->kept) {
-		if (!kb.nreads) continue;
-		rc = profile_device(c, kb.d_words, kb.d_offs, kb.nreads, kb.maxlen, min_count, (ReadCov *)d_r.p);
-		if (rc == SDT_OK) rc = scatter_by_ordinal(out, kb, d_r, tmp);
-		if (rc != SDT_OK) return rc;
-	}
 	if (nreads) *nreads = total;
 	return SDT_OK;
 }

@@ -109,19 +109,10 @@ int sdt_gpu_select_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwor
 	if (rc != SDT_OK) return rc;
 	SDT_ENTER(c);
 	// a piece of a paired batch holds whole pairs, and a unit's id in the draw is the index of its first read in the whole batch
-	DevBuf d_r, d_k;
-	uint64_t kept = 0;
-	rc = for_each_piece(c, packed_words, offsets, nreads, paired ? 2 : 1, "selection staging", [&](const StagedPiece &p) -> int {
-		int rc = d_r.reserve(p.nr * sizeof(ReadPick), "selection staging");
-		if (rc == SDT_OK) rc = d_k.reserve(p.nr, "selection staging");
-		if (rc == SDT_OK) rc = select_device(c, p.d_words, p.d_offs, p.nr, p.maxlen, paired, params, (ReadPick *)d_r.p, (uint8_t *)d_k.p, p.r0, &kept);
-		if (rc != SDT_OK) return rc;
-		HIPCHK(hipMemcpy(pick + p.r0, d_r.p, p.nr * sizeof(ReadPick), hipMemcpyDeviceToHost));
-		if (keep) HIPCHK(hipMemcpy(keep + p.r0, d_k.p, p.nr, hipMemcpyDeviceToHost));
-		return SDT_OK;
+	return staged_records<ReadPick>(c, packed_words, offsets, nreads, paired ? 2 : 1, "selection staging", pick, keep, n_kept,
+	                                [&](const StagedPiece &p, ReadPick *d_r, uint8_t *d_k, uint64_t *kept) {
+		return select_device(c, p.d_words, p.d_offs, p.nr, p.maxlen, paired, params, d_r, d_k, p.r0, kept);
 	});
-	if (rc == SDT_OK && n_kept) *n_kept = kept;
-	return rc;
 }
 
 int sdt_gpu_select_kept_reads(sdt_ctx *c, const sdt_norm_params *params, const uint64_t *pair_ranges, uint64_t n_ranges,
@@ -132,19 +123,8 @@ int sdt_gpu_select_kept_reads(sdt_ctx *c, const sdt_norm_params *params, const u
 	if (nreads) *nreads = 0;
 	if (n_kept) *n_kept = 0;
 	int rc = params_ok(params, 0, 0);
-	if (rc != SDT_OK) return rc;
-	if (n_ranges && !pair_ranges)
-		return fail(SDT_EINVAL, "NULL argument");
-	PairRangeFault fault;
-	const uint64_t bad = check_pair_ranges(pair_ranges, n_ranges, &fault);
-	if (fault == PAIR_RANGE_NOT_PAIRS)
-		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) does not hold whole pairs", (unsigned long long)bad,
-		            (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1]);
-	if (fault == PAIR_RANGE_OVERLAPS)
-		return fail(SDT_EINVAL, "pair range %llu = [%llu, %llu) starts before range %llu ends: ranges are ascending and disjoint",
-		            (unsigned long long)bad, (unsigned long long)pair_ranges[2 * bad], (unsigned long long)pair_ranges[2 * bad + 1],
-		            (unsigned long long)(bad - 1));
-	rc = search_ready(c, "sdt_gpu_select_kept_reads");
+	if (rc == SDT_OK) rc = pair_ranges_ok(pair_ranges, n_ranges);
+	if (rc == SDT_OK) rc = search_ready(c, "sdt_gpu_select_kept_reads");
 	if (rc != SDT_OK) return rc;
 	uint64_t total, most, npick;
 	rc = kept_span(c, out_capacity, "pick", &total, &most, &npick);
@@ -156,40 +136,32 @@ int sdt_gpu_select_kept_reads(sdt_ctx *c, const sdt_norm_params *params, const u
 	SDT_ENTER(c);
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
 	// the unit list, as stretches: single reads up to a range, the pairs of the range, and so on up to the last ordinal a read has
-	// (npick may cut a pair: its first mate is a unit, the kernel finds no second)
-	std::vector<UnitSeg> segs(2 * n_ranges + 1);
-	uint64_t units = 0;
-	segs.resize(cut_unit_stretches(pair_ranges, n_ranges, npick, segs.data(), &units));
-	// records by ordinal on the device, preset to "no read": every kept batch fills in its own, then the units are decided
-	DevBuf d_pick, d_segs;
+	// (sdt_readstage.hpp: KeptUnits); records by ordinal on the device, preset to "no read": every kept batch fills in its own, then
+	// the units are decided
+	KeptUnits ku(pair_ranges, n_ranges, npick);
+	DevBuf d_pick;
 	rc = d_pick.get(npick * sizeof(ReadPick), "selection records");
-	if (rc == SDT_OK) rc = d_segs.get(segs.size() * sizeof(UnitSeg), "selection units");
+	if (rc == SDT_OK) rc = ku.d_segs.get(ku.bytes(), "selection units");
 	if (rc != SDT_OK) return rc;
 	HIPCHK(hipMemsetAsync(d_pick.p, 0xFF, npick * sizeof(ReadPick), c->stream));
 	rc = flags_begin(c);
+	if (rc == SDT_OK) rc = ku.upload(c);
 	if (rc != SDT_OK) return rc;
-	HIPCHK(hipMemcpyAsync(d_segs.p, segs.data(), segs.size() * sizeof(UnitSeg), hipMemcpyHostToDevice, c->stream));
 	for (const auto &kb : c->kept) {
 		if (!kb.nreads) continue;
 		rc = launch_pick_stats(c, kb.d_words, kb.d_offs, kb.nreads, kb.maxlen, params->max_cv_pct, (ReadPick *)d_pick.p, kb.ord_base, kb.ord_stride);
 		if (rc != SDT_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
 	}
-	rc = launch_pick_decide(c, (ReadPick *)d_pick.p, npick, (const UnitSeg *)d_segs.p, (uint32_t)segs.size(), UnitSeg{0, 0, 1}, units, 0, params, nullptr);
+	rc = launch_pick_decide(c, (ReadPick *)d_pick.p, npick, (const UnitSeg *)ku.d_segs.p, (uint32_t)ku.segs.size(), UnitSeg{0, 0, 1}, ku.units, 0, params,
+	                        nullptr);
 	unsigned long long fl[3] = {0, 0, 0};
 	if (rc == SDT_OK) HIPCHK(hipMemcpyAsync(fl, c->d_cov_flags, sizeof fl, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));             // (segs may go)
 	if (rc != SDT_OK) return rc;
 	if (fl[0])
 		return fail(SDT_EINVAL, "sdt_gpu_select_kept_reads: %llu kept reads are longer than their batch says", fl[0]);
-	// back in blocks; the records of ordinals that no kept read has stay as the caller had them
-	const uint64_t block = 1ULL << 22;
-	std::vector<ReadPick> tmp((size_t)(npick < block ? npick : block));
-	for (uint64_t o0 = 0; o0 < npick; o0 += block) {
-		const uint64_t k = npick - o0 < block ? npick - o0 : block;
-		HIPCHK(hipMemcpy(tmp.data(), (const ReadPick *)d_pick.p + o0, k * sizeof(ReadPick), hipMemcpyDeviceToHost));
-		for (uint64_t i = 0; i < k; i++)
-			if (tmp[i].verdict != PICK_ABSENT) memcpy(pick + o0 + i, &tmp[i], sizeof(ReadPick));
-	}
+	rc = fetch_present<ReadPick>(pick, d_pick, npick, PICK_ABSENT);
+	if (rc != SDT_OK) return rc;
 	if (nreads) *nreads = total;
 	if (n_kept) *n_kept = fl[2];
 	return SDT_OK;

@@ -88,19 +88,10 @@ int sdt_gpu_trim_reads(sdt_ctx *c, const uint32_t *packed_words, uint64_t nwords
 	if (rc == SDT_OK) rc = strip_plan(c, nreads, in.longest, &geo);      // (the whole call is refused before a piece's records are written)
 	if (rc != SDT_OK) return rc;
 	SDT_ENTER(c);
-	DevBuf d_r, d_k;
-	uint64_t kept = 0;
-	rc = for_each_piece(c, packed_words, offsets, nreads, 1, "trim staging", [&](const StagedPiece &p) -> int {
-		int rc = d_r.reserve(p.nr * sizeof(ReadTrim), "trim staging");
-		if (rc == SDT_OK) rc = d_k.reserve(p.nr, "trim staging");
-		if (rc == SDT_OK) rc = trim_device(c, p.d_words, p.d_offs, p.nr, p.maxlen, params, (ReadTrim *)d_r.p, (uint8_t *)d_k.p, &kept);
-		if (rc != SDT_OK) return rc;
-		HIPCHK(hipMemcpy(trim + p.r0, d_r.p, p.nr * sizeof(ReadTrim), hipMemcpyDeviceToHost));
-		if (keep) HIPCHK(hipMemcpy(keep + p.r0, d_k.p, p.nr, hipMemcpyDeviceToHost));
-		return SDT_OK;
+	return staged_records<ReadTrim>(c, packed_words, offsets, nreads, 1, "trim staging", trim, keep, n_kept,
+	                                [&](const StagedPiece &p, ReadTrim *d_r, uint8_t *d_k, uint64_t *kept) {
+		return trim_device(c, p.d_words, p.d_offs, p.nr, p.maxlen, params, d_r, d_k, kept);
 	});
-	if (rc == SDT_OK && n_kept) *n_kept = kept;
-	return rc;
 }
 
 int sdt_gpu_trim_kept_reads(sdt_ctx *c, const sdt_trim_params *params, sdt_read_trim *trim, uint64_t out_capacity, uint64_t *nreads,
@@ -123,18 +114,11 @@ int sdt_gpu_trim_kept_reads(sdt_ctx *c, const sdt_trim_params *params, sdt_read_
 		return fail(SDT_EINVAL, "NULL argument");
 	SDT_ENTER(c);
 	HIPCHK(hipStreamSynchronize(c->copy_stream));        // (sdt_gpu_keep_reads uploads on the copy stream)
-	// batch by batch: dense records on the device, scattered to their ordinals on the host
-	DevBuf d_r;
-	rc = d_r.get(most * sizeof(ReadTrim), "trim records");
-	if (rc != SDT_OK) return rc;
-	std::vector<ReadTrim> tmp(most);
 	uint64_t kept = 0;
-	for (const auto &kb : c->kept) {
-		if (!kb.nreads) continue;
-		rc = trim_device(c, kb.d_words, kb.d_offs, kb.nreads, kb.maxlen, params, (ReadTrim *)d_r.p, nullptr, &kept);
-		if (rc == SDT_OK) rc = scatter_by_ordinal(trim, kb, d_r, tmp);
-		if (rc != SDT_OK) return rc;
-	}
+	rc = for_each_kept_batch<ReadTrim>(c, trim, most, "trim records", [&](const sdt_ctx::KeptBatch &kb, ReadTrim *d_r) {
+		return trim_device(c, kb.d_words, kb.d_offs, kb.nreads, kb.maxlen, params, d_r, nullptr, &kept);
+	});
+	if (rc != SDT_OK) return rc;
 	if (nreads) *nreads = total;
 	if (n_kept) *n_kept = kept;
 	return SDT_OK;

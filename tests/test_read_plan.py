@@ -35,8 +35,12 @@ def test_the_library_uses_this_plan():
         assert call in layer, f"sdt_readstage.hpp does not call {call})"
     plan = open(os.path.join(CSRC, "sdt_read_plan.h")).read()
     texts = {name: open(os.path.join(CSRC, name)).read() for name in STAGES + ("sdt_compact.hpp",)}
+    # (a stage with records and a keep mask stages through staged_records, which is the layer's own for_each_piece body)
+    assert "for_each_piece(" in layer[layer.index("static int staged_records("):].split("\n}\n", 1)[0]
     for name in STAGES:
-        assert "launch_strip(" in texts[name] and "for_each_piece(" in texts[name], f"{name} launches or stages on its own"
+        assert "launch_strip(" in texts[name] and ("for_each_piece(" in texts[name] or "staged_records<" in texts[name]), \
+            f"{name} launches or stages on its own"
+        assert "next_piece(" not in texts[name], f"{name} cuts its pieces on its own"
     # each decision is written down once: the refusal, the two stream messages, the state of the kept reads, the cut
     everything = layer + plan + "".join(texts.values())
     for once in ("per-wavefront LDS strip", "offsets not monotonic at read", "packed_words too short", "the reads were not kept"):
