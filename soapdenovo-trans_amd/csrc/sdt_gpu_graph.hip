@@ -1,32 +1,30 @@
-// sdt_gpu_graph.hip -- the graph phases of pregraph on the device mirror of the graph (part of libsdt_gpu.so).
+// sdt_gpu_graph.hip -- the graph phases of pregraph on the device mirror of the graph (part of libsdt_gpu.so): the entry points of the
+// ABI, their argument and state checks, and the host side of the layout.
 //
-//   layout      sdt_gpu_layout_sorted_keys / sdt_gpu_layout_apply / sdt_gpu_export_ordered: the reference's visiting order
-//               (graph.c replays only the probing of each set; sort, gather and numbering happen here)
+//   layout      the reference's visiting order.  sdt_gpu_layout_on_device reads as its steps: layout_sort (nodes by set and first
+//               occurrence), the growth schedule of every set (sdt_layout_plan.h, pure host arithmetic), the replay of the probing
+//               (struct Replay: grow = rehash rounds to the fixed point and strip, put, order), layout_publish (numbering).
+//               sdt_gpu_layout_sorted_keys / sdt_gpu_layout_apply are the same two ends around a replay on the host (graph.c).
 //   dry runs    the read-only halves of removeMinorOut / removeSingleTips / removeMinorTips (cutTipPreGraph.c) and of
-//               kmer2edges (node2edge.c), labelled with the connected components the ordered commits may run side by side
-//               (union-find over node indices), sorted by (component, node)
+//               kmer2edges (node2edge.c): by host position, and labelled with the connected components the ordered commits may
+//               run side by side (union-find over node indices), sorted by (component, node)
+// Scratch owns the device buffers of a call, GCHK returns its HIP errors, LAUNCH_NW picks the kernel of the key width.
 // The phases that hold node indices are templates over the index form (sdt_graph_phases.hpp): the 32-bit form is instantiated
 // here, the 64-bit one in sdt_gpu_graph64.hip; the entry points pick the form the numbering fixed.
 // gfx950 only; no CPU fallback.  The context is seen through sdti::GraphView (sdt_internal.hpp).
-#include "sdt_graph_phases.hpp"
+#include <vector>
 
+#include "sdt_graph_phases.hpp"
+#include "sdt_layout_plan.h"
+
+static_assert(sdt::RP_PLAN_DEPTH_BITS == RP_DEPTH_BITS && sdt::RP_PLAN_CHUNK == AP_CH && sdt::RP_PLAN_WAVES == TPB / 64, "sdt_layout_plan.h restates these");
 
 void sdti::graph_ext_free(GraphExt *gx)
 {
 	if (!gx) return;
-	if (gx->d_sval) (void)hipFree(gx->d_sval);
-	if (gx->d_slot_of) (void)hipFree(gx->d_slot_of);
-	if (gx->d_result) (void)hipFree(gx->d_result);
-	if (gx->d_wnode) (void)hipFree(gx->d_wnode);
-	if (gx->d_wl) (void)hipFree(gx->d_wl);
-	if (gx->d_wr) (void)hipFree(gx->d_wr);
-	if (gx->d_skipped) (void)hipFree(gx->d_skipped);
-	if (gx->mo_dirty) (void)hipFree(gx->mo_dirty);
-	if (gx->mo_cnt) (void)hipFree(gx->mo_cnt);
-	if (gx->mo_recidx) (void)hipFree(gx->mo_recidx);
-	if (gx->mo_cstart) (void)hipFree(gx->mo_cstart);
-	if (gx->d_seq) (void)hipFree(gx->d_seq);
-	if (gx->d_pw) (void)hipFree(gx->d_pw);
+	for (void *q : {(void *)gx->d_sval, (void *)gx->d_slot_of, (void *)gx->d_result, (void *)gx->d_wnode, (void *)gx->d_wl, (void *)gx->d_wr, (void *)gx->d_skipped,
+	                (void *)gx->mo_dirty, (void *)gx->mo_cnt, (void *)gx->mo_recidx, (void *)gx->mo_cstart, (void *)gx->d_seq, (void *)gx->d_pw})
+		if (q) (void)hipFree(q);
 	delete gx;
 }
 
@@ -69,7 +67,6 @@ uint64_t *sdti::graph_take_path_words(GraphExt *gx, uint64_t n)
 	return p;
 }
 
-
 // (from ascending, first appearance descending): stable sort by ~first, then stable sort by from
 int sdti::sort_arcs_for_output(hipStream_t stream, int cu_count, uint32_t *d_from, uint32_t *d_to, uint32_t *d_mult, uint64_t *d_first, uint64_t n)
 {
@@ -101,298 +98,311 @@ int sdti::sort_arcs_for_output(hipStream_t stream, int cu_count, uint32_t *d_fro
 	return SDT_OK;
 }
 
-
-// ---- the whole layout on the device: sort, replay of the probing (fixed point per growth), numbering ---------------------
-#include <math.h>
-#include <time.h>
-#include <vector>
-static int rp_prime(uint64_t num)                    // find_next_prime_kh's test (newhash.c:116-158): the bound is (ubyte8)sqrt((float)n)
+// ---- layout: the steps sdt_gpu_layout_on_device shares with sdt_gpu_layout_sorted_keys / sdt_gpu_layout_apply ---------------
+// what both layouts ask of the context and of their arguments
+static int layout_check(const GraphView &v, int p, int nw_variant)
 {
-	if (num < 4) return 1;
-	if (num % 2 == 0) return 0;
-	const uint64_t lim = (uint64_t)sqrt((float)num);
-	for (uint64_t i = 3; i < lim; i += 2)
-		if (num % i == 0) return 0;
-	return 1;
-}
-static uint64_t rp_next_prime(uint64_t n) { if (n % 2 == 0) n++; while (!rp_prime(n)) n += 2; return n; }
-static uint64_t rp_next_size(uint64_t size, double lf, uint64_t count)      // encap_kmerset's growth (newhash.c:318-330)
-{
-	uint64_t n = size;
-	do {
-		n = n < 0xFFFFFFFu ? n << 1 : n + 0xFFFFFFu;
-		n = rp_next_prime(n);
-	} while (n * lf < (double)(count + 1));
-	return n;
-}
-
-extern "C" int sdt_gpu_layout_on_device(sdt_ctx *c, int p, int nw_variant, int small_init, uint64_t *set_start, uint64_t *n_out)
-{
-	if (!c || !n_out || !set_start) return fail(SDT_EINVAL, "NULL argument");
-	const GraphView v0 = sdti::graph_view(c);
-	GRAPH_ENTER(v0);
-	struct timespec ts0_; clock_gettime(CLOCK_MONOTONIC, &ts0_);
-	const double t_call = ts0_.tv_sec * 1e3 + ts0_.tv_nsec * 1e-6;
-	const bool timing = sdt_env("SDT_TIMING") != nullptr;
-	auto tick = [&](const char *what) {              // (SDT_TIMING: where the call's time goes, on stderr)
-		if (!timing) return;
-		struct timespec t_;
-		clock_gettime(CLOCK_MONOTONIC, &t_);
-		fprintf(stderr, "[device]       %s at %.1f ms\n", what, t_.tv_sec * 1e3 + t_.tv_nsec * 1e-6 - t_call);
-	};
-	int rc = sdti::release_pass1(c);
-	if (rc != SDT_OK) return rc;
-	tick("pass 1 released");
-	const GraphView v = sdti::graph_view(c);
-	const uint64_t n = v.h_stats->distinct;
-	*n_out = n;
 	if (!v.d_first) return fail(SDT_ESTATE, "first-occurrence ordinals were not tracked: init with SDT_FLAG_TRACK_FIRST");
 	if (p < 1 || p > 256) return fail(SDT_EINVAL, "layout on the device: 1..256 sets, asked for %d", p);
 	if (nw_variant < v.nw || nw_variant > 4) return fail(SDT_EINVAL, "a %d-word variant cannot hold %d-word keys", nw_variant, v.nw);
-	sdti::GraphExt *gx = ext_of(v);
-	rc = graph_choose_form(gx, n);                           // (the ranks of the numbering below: 32-bit below 2^32 - 16 nodes, else 64-bit)
-	if (rc != SDT_OK) return rc;
-	if (gx->d_sval) { (void)hipFree(gx->d_sval); gx->d_sval = nullptr; gx->n_sorted = 0; }
-	Scratch S;
+	return SDT_OK;
+}
+
+// the n nodes sorted by (set, first occurrence): set_start[0 .. p] on the host; on the device (S owns all of it) the keys in that order
+// and v1s, rank -> table slot.  k1, v0s and, for keys of more than one word, k0 are of no use afterwards: the caller may free them
+struct SortedNodes { uint64_t *k0, *k1, *v0s, *v1s, *d_keys; };
+static int layout_sort(sdt_ctx *c, const GraphView &v, Scratch &S, int p, int nw_variant, uint64_t n, uint64_t *set_start, const CallTimer &T, SortedNodes &o)
+{
 	const uint64_t m = n ? n : 1;
-	// ---- sort by (set, first occurrence), keys gathered in that order (as sdt_gpu_layout_sorted_keys)
-	uint64_t *k0, *k1, *v0s, *v1s, *d_keys, *d_ss;
+	uint64_t *d_ss;
 	unsigned long long *d_cur;
-	GCHK(S.alloc(&k0, m * 8)); GCHK(S.alloc(&k1, m * 8)); GCHK(S.alloc(&v0s, m * 8)); GCHK(S.alloc(&v1s, m * 8));
+	GCHK(S.alloc(&o.k0, m * 8)); GCHK(S.alloc(&o.k1, m * 8)); GCHK(S.alloc(&o.v0s, m * 8)); GCHK(S.alloc(&o.v1s, m * 8));
 	GCHK(S.alloc(&d_cur, 8)); GCHK(S.alloc(&d_ss, (size_t)(p + 1) * 8));
 	GCHK(hipMemsetAsync(d_cur, 0, 8, v.stream));
-	const int g = sdti::scan_grid(v.cu_count, v.slots);
-	LAUNCH_NW(v, k_layout_keys, g, (uint32_t)p, nw_variant, k0, v0s, (unsigned long long)n, d_cur, v.d_stats);
+	LAUNCH_NW(v, k_layout_keys, sdti::scan_grid(v.cu_count, v.slots), (uint32_t)p, nw_variant, o.k0, o.v0s, (unsigned long long)n, d_cur, v.d_stats);
 	GCHK(hipGetLastError());
-	rc = sdti::sync_stats(c);
-	if (rc != SDT_OK) return fail(SDT_ESTATE, "layout: %llu nodes without a usable first-occurrence ordinal", (unsigned long long)v.h_stats->probe_fail);
-	tick("sort keys made");
+	if (sdti::sync_stats(c) != SDT_OK)
+		return fail(SDT_ESTATE, "layout: %llu nodes without a usable first-occurrence ordinal (>= 2^56, or more nodes than counted)", (unsigned long long)v.h_stats->probe_fail);
+	T.tick("sort keys made");
 	unsigned end_bit = 56;
 	for (int q = p - 1; q > 0; q >>= 1) end_bit++;
-	rc = sort_pairs<uint64_t>(v, k0, k1, v0s, v1s, n, end_bit);
+	const int rc = sort_pairs<uint64_t>(v, o.k0, o.k1, o.v0s, o.v1s, n, end_bit);
 	if (rc != SDT_OK) return rc;
-	tick("sorted");
-	hipLaunchKernelGGL(k_layout_set_starts, dim3((p + 1 + 63) / 64), dim3(64), 0, v.stream, k1, n, (uint32_t)p, d_ss);
+	T.tick("sorted");
+	hipLaunchKernelGGL(k_layout_set_starts, dim3((p + 1 + 63) / 64), dim3(64), 0, v.stream, o.k1, n, (uint32_t)p, d_ss);
 	GCHK(hipGetLastError());
 	GCHK(hipMemcpyAsync(set_start, d_ss, (size_t)(p + 1) * 8, hipMemcpyDeviceToHost, v.stream));
-	if (v.nw == 1) d_keys = k0; else GCHK(S.alloc(&d_keys, m * v.nw * 8));
-	LAUNCH_NW(v, k_layout_gather_keys, sdti::scan_grid(v.cu_count, m), v1s, n, d_keys);
+	// k0 is free again: the keys in sorted order go there (NW words each: reuse needs NW * n words)
+	if (v.nw == 1) o.d_keys = o.k0; else GCHK(S.alloc(&o.d_keys, m * v.nw * 8));
+	LAUNCH_NW(v, k_layout_gather_keys, sdti::scan_grid(v.cu_count, m), o.v1s, n, o.d_keys);
 	GCHK(hipGetLastError());
 	GCHK(hipStreamSynchronize(v.stream));
-	tick("keys gathered");
-	(void)hipFree(S.release(k1));                             // (the sorted sort keys are not needed any more)
-	if (v.nw != 1) (void)hipFree(S.release(k0));
-	(void)hipFree(S.release(v0s));
-	// ---- every set's growth schedule (a function of its number of keys only)
-	struct Gen { uint32_t lo, hi, size; };                   // ids [lo, hi) are put into a table of `size` slots (after a growth from the previous size)
-	std::vector<std::vector<Gen>> sched(p);
-	std::vector<RpSet> sets(p);
-	const double lf = (double)0.77f;
-	uint64_t tab_total = 0, max_size = 0;
-	size_t max_gens = 0;
-	for (int s = 0; s < p; s++) {
-		const uint64_t ms = set_start[s + 1] - set_start[s];
-		uint64_t size = (nw_variant != 1 && small_init) ? 3 : rp_next_prime(1024);      // init_kmerset (prlHashReads.c:402-423, newhash.c:163-166)
-		uint64_t max = (uint64_t)(size * 0.77f), lo = 0;
-		for (;;) {
-			const uint64_t hi = ms < max ? ms : max;
-			sched[s].push_back(Gen{(uint32_t)lo, (uint32_t)hi, (uint32_t)size});
-			if (hi >= ms) break;
-			size = rp_next_size(size, lf, max);                // the put of id == max finds count + 1 > max
-			if (size >= 0xFFFFFFFFULL) return fail(SDT_EINVAL, "layout on the device: a set's table passes 2^32 slots");
-			lo = hi;
-			max = (uint64_t)(size * lf);
-		}
-		sets[s].key0 = set_start[s]; sets[s].tab0 = tab_total; sets[s].m = (uint32_t)ms;
-		tab_total += size;
-		if (size > max_size) max_size = size;
-		if (sched[s].size() > max_gens) max_gens = sched[s].size();
-	}
-	// table word of a growth's rounds: time << qbits | q + 1 (q = old slot, time = old slot << RP_DEPTH_BITS | depth); a dirty cluster's
-	// list entry keeps the set in 10 bits
-	int qbits = 1;
-	while ((1ULL << qbits) <= max_size) qbits++;
-	if (2 * qbits + RP_DEPTH_BITS > 64 || p >= 1024) return fail(SDT_ELIMIT, "layout on the device: twice %d slot bits do not fit the table word (or %d sets the list entry)", qbits, p);
-	tick("schedule made");
-	// ---- buffers
-	unsigned long long *tab[2], *d_time, *d_saved, *d_list[2], *d_pre;
-	uint32_t *d_home, *d_occ;
-	RpSet *d_sets;
-	unsigned int *d_flags;
-	RpRound *d_round;
-	GCHK(S.alloc(&tab[0], (tab_total + 1) * 8)); GCHK(S.alloc(&tab[1], (tab_total + 1) * 8));
-	uint32_t *d_home_slot;
-	// per OLD slot of a growth: time and home; per new slot: the word a round took out of it; per entry: the two lists of the rounds
-	// (an entry whose time changed is listed once)
-	// (sdt_append.cuh: the lists are written in chunks of AP_CH entries per wave, the open chunk of every wave has unused slots)
-	// A round lists the entries whose time changed: a fifth of the entries of a growth in round 0 (tools/replay_fixed_point.c), i.e. an
-	// eighth of all keys when the largest set grows; room for a quarter of all keys (past that: SDT_ELIMIT, the caller replays on the host)
-	const unsigned long long list_chunks = (m / 4 + 1) / (AP_CH - 64) + 1 + (unsigned long long)v.cu_count * 8 * (TPB / 64), list_cap = list_chunks * AP_CH;
-	GCHK(S.alloc(&d_time, (tab_total + 1) * 8)); GCHK(S.alloc(&d_home_slot, (tab_total + 1) * 4)); GCHK(S.alloc(&d_saved, (tab_total + 1) * 8));
-	GCHK(S.alloc(&d_list[0], list_cap * 8)); GCHK(S.alloc(&d_list[1], list_cap * 8)); GCHK(S.alloc(&d_round, sizeof(RpRound)));
-	GCHK(S.alloc(&d_home, m * 4)); GCHK(S.alloc(&d_sets, (size_t)p * sizeof(RpSet))); GCHK(S.alloc(&d_pre, (size_t)(p + 1) * 8)); GCHK(S.alloc(&d_flags, 4));
-	GCHK(hipMemsetAsync(tab[0], 0, (tab_total + 1) * 8, v.stream));
-	tick("buffers made");
-	std::vector<unsigned long long> pre(p + 1);
-	auto upload = [&](void) -> int {
-		GCHK(hipStreamSynchronize(v.stream));                  // (kernels in flight read the old copies; the host vectors change right after)
-		GCHK(hipMemcpy(d_sets, sets.data(), (size_t)p * sizeof(RpSet), hipMemcpyHostToDevice));
-		GCHK(hipMemcpy(d_pre, pre.data(), (size_t)(p + 1) * 8, hipMemcpyHostToDevice));
-		return SDT_OK;
-	};
-	auto grid = [&](unsigned long long items) { return dim3(sdti::scan_grid(v.cu_count, items ? items : 1)); };
-	unsigned int h_flags = 0;
-	int cur = 0, total_rounds = 0;
-	auto now_ms = []() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
-	const double t_start = now_ms();
-	double t_rehash = 0, t_put = 0, t_strip = 0;
-	if (timing) fprintf(stderr, "[device]     layout: release + sort + gather + schedule + buffers %.1f ms\n", t_start - t_call);
-	for (size_t gen = 0; gen < max_gens; gen++) {
-		// ---- growth into this generation's size (every set that has a generation `gen`, except the first)
-		if (gen > 0) {
-			unsigned long long old_total = 0, cnt_total = 0;
-			for (int s = 0; s < p; s++) {
-				const bool on = gen < sched[s].size();
-				sets[s].old_size = on ? sched[s][gen - 1].size : 0;
-				sets[s].size = on ? sched[s][gen].size : sets[s].size;
-				sets[s].lo = 0; sets[s].hi = on ? sched[s][gen].lo : 0;            // ids [0, lo) are in the table
-				pre[s] = cnt_total;
-				cnt_total += sets[s].hi;
-			}
-			(void)cnt_total;
-			for (int s = 0; s < p; s++) { pre[s] = old_total; old_total += sets[s].old_size; }
-			pre[p] = old_total;
-			rc = upload(); if (rc != SDT_OK) return rc;
-			const int nxt = cur ^ 1;
-			const double t_g0 = now_ms();
-			const int rounds0 = total_rounds;
-			// time (q, 0) and the home in the new geometry, per old slot
-			if (v.nw == 1) hipLaunchKernelGGL(k_rp_rehash_init<1>, grid(old_total), dim3(TPB), 0, v.stream, d_keys, d_sets, d_pre, p, tab[cur], d_time, d_home_slot);
-			else if (v.nw == 2) hipLaunchKernelGGL(k_rp_rehash_init<2>, grid(old_total), dim3(TPB), 0, v.stream, d_keys, d_sets, d_pre, p, tab[cur], d_time, d_home_slot);
-			else hipLaunchKernelGGL(k_rp_rehash_init<4>, grid(old_total), dim3(TPB), 0, v.stream, d_keys, d_sets, d_pre, p, tab[cur], d_time, d_home_slot);
-			for (int s = 0; s < p; s++)                           // (only the regions of the sets that grow, at their new size: the early growths are tiny)
-				if (sets[s].old_size) GCHK(hipMemsetAsync(tab[nxt] + sets[s].tab0, 0, (size_t)sets[s].size * 8, v.stream));
-			GCHK(hipMemsetAsync(d_round, 0, sizeof(RpRound), v.stream));
-			// round 0: everybody
-			hipLaunchKernelGGL(k_rp_ins_all, grid(old_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, qbits, tab[cur], tab[nxt], d_home_slot, d_time, d_round);
-			hipLaunchKernelGGL(k_rp_eval_all, grid(old_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, qbits, tab[cur], tab[nxt], d_home_slot, d_time,
-			                   d_list[0], list_chunks, d_round);
-			GCHK(hipGetLastError());
-			// (SDT_RP_MAX_ROUNDS: test hook -- a cap that real data passes, so that the caller's other path is exercised)
-			static const int max_rounds = sdt_test_env("SDT_RP_MAX_ROUNDS") ? atoi(sdt_test_env("SDT_RP_MAX_ROUNDS")) : 60;
-			int lc = 0;
-			for (int round = 0;; round++) {
-				RpRound h_round;
-				GCHK(hipMemcpyAsync(&h_round, d_round, sizeof(RpRound), hipMemcpyDeviceToHost, v.stream));
-				GCHK(hipStreamSynchronize(v.stream));
-				total_rounds++;
-				if (h_round.flags) return fail(SDT_ELIMIT, "layout on the device: %s", (h_round.flags & 2u) ? "an insertion found no slot" :
-				                               (h_round.flags & 4u) ? "an eviction chain or a stretch of slots past its field" : "the list of a round is full");
-				if (!h_round.n_next) break;
-				if (round >= max_rounds) return fail(SDT_ELIMIT, "layout on the device: a growth did not settle in %d rounds", max_rounds);
-				// from the home of every changed entry to the end of its cluster: taken out, laid out again, the old slots in there evaluated again
-				const unsigned long long n_list = h_round.n_next * AP_CH;
-				GCHK(hipMemsetAsync(d_round, 0, sizeof(RpRound), v.stream));
-				hipLaunchKernelGGL(k_rp_collect, grid(n_list), dim3(TPB), 0, v.stream, d_sets, tab[nxt], d_saved, d_list[lc], n_list, d_round);
-				hipLaunchKernelGGL(k_rp_ins_list, grid(n_list), dim3(TPB), 0, v.stream, d_sets, d_pre, qbits, tab[nxt], d_saved, d_home_slot, d_time, d_list[lc], n_list, d_round);
-				hipLaunchKernelGGL(k_rp_eval_list, grid(n_list), dim3(TPB), 0, v.stream, d_sets, d_pre, qbits, tab[cur], tab[nxt], d_home_slot, d_time,
-				                   d_list[lc], n_list, d_list[lc ^ 1], list_chunks, d_round);
-				GCHK(hipGetLastError());
-				lc ^= 1;
-			}
-			const double t_g1 = now_ms();
-			t_rehash += t_g1 - t_g0;
-			if (timing && old_total > (1u << 24)) fprintf(stderr, "[device]     growth %zu: %llu old slots, %d rounds, %.1f ms\n", gen, old_total, total_rounds - rounds0, t_g1 - t_g0);
-			// the settled layout without its times is the table of this generation
-			unsigned long long new_total = 0;
-			for (int s = 0; s < p; s++) { pre[s] = new_total; new_total += gen < sched[s].size() ? sets[s].size : 0; }
-			pre[p] = new_total;
-			// (sets without this generation keep their table: copy their region over unchanged)
-			for (int s = 0; s < p; s++)
-				if (gen >= sched[s].size())
-					GCHK(hipMemcpyAsync(tab[nxt] + sets[s].tab0, tab[cur] + sets[s].tab0, (size_t)sets[s].size * 8, hipMemcpyDeviceToDevice, v.stream));
-			rc = upload(); if (rc != SDT_OK) return rc;
-			{
-				// slots of the sets that grew: pre counts only those (others have size 0 in the prefix)
-				std::vector<RpSet> grown = sets;
-				for (int s = 0; s < p; s++) if (gen >= sched[s].size()) grown[s].size = 0;
-				GCHK(hipMemcpy(d_sets, grown.data(), (size_t)p * sizeof(RpSet), hipMemcpyHostToDevice));
-				hipLaunchKernelGGL(k_rp_slots, grid(new_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, 0, qbits, tab[cur], tab[nxt], (uint32_t *)nullptr);
-				GCHK(hipGetLastError());
-				GCHK(hipStreamSynchronize(v.stream));
-			}
-			cur = nxt;
-			t_strip += now_ms() - t_g1;
-		}
-		// ---- the puts of this generation
-		const double t_p0 = now_ms();
-		unsigned long long put_total = 0;
-		for (int s = 0; s < p; s++) {
-			const bool on = gen < sched[s].size();
-			sets[s].lo = on ? sched[s][gen].lo : 0;
-			sets[s].hi = on ? sched[s][gen].hi : 0;
-			if (on) sets[s].size = sched[s][gen].size;
-			pre[s] = put_total;
-			put_total += sets[s].hi - sets[s].lo;
-		}
-		pre[p] = put_total;
-		rc = upload(); if (rc != SDT_OK) return rc;
-		GCHK(hipMemsetAsync(d_flags, 0, 4, v.stream));
-		if (v.nw == 1) hipLaunchKernelGGL(k_rp_home<1>, grid(put_total), dim3(TPB), 0, v.stream, d_keys, d_sets, d_pre, p, 0, d_home);
-		else if (v.nw == 2) hipLaunchKernelGGL(k_rp_home<2>, grid(put_total), dim3(TPB), 0, v.stream, d_keys, d_sets, d_pre, p, 0, d_home);
-		else hipLaunchKernelGGL(k_rp_home<4>, grid(put_total), dim3(TPB), 0, v.stream, d_keys, d_sets, d_pre, p, 0, d_home);
-		hipLaunchKernelGGL(k_rp_put, grid(put_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, d_home, tab[cur], d_flags);
-		GCHK(hipGetLastError());
-		GCHK(hipMemcpyAsync(&h_flags, d_flags, 4, hipMemcpyDeviceToHost, v.stream));
-		GCHK(hipStreamSynchronize(v.stream));
-		if (h_flags) return fail(SDT_ELIMIT, "layout on the device: a put found no slot");
-		t_put += now_ms() - t_p0;
-	}
-	if (timing) fprintf(stderr, "[device]     layout replay so far %.1f ms: rehash rounds %.1f, strip + copies %.1f, puts %.1f ms\n", now_ms() - t_start, t_rehash, t_strip, t_put);
-	// ---- the visiting order: the sets one after the other, every set's slots in order
-	unsigned long long slot_total = 0;
-	for (int s = 0; s < p; s++) { sets[s].size = sched[s].back().size; pre[s] = slot_total; slot_total += sets[s].size; }
-	pre[p] = slot_total;
-	rc = upload(); if (rc != SDT_OK) return rc;
-	// (the buffers of the replay that are free now make room for the flags and their prefix sum)
-	(void)hipFree(S.release(tab[cur ^ 1])); (void)hipFree(S.release(d_time)); (void)hipFree(S.release(d_home_slot));
-	(void)hipFree(S.release(d_saved)); (void)hipFree(S.release(d_list[0])); (void)hipFree(S.release(d_list[1]));
-	uint64_t *d_order;
-	GCHK(S.alloc(&d_occ, (slot_total + 1) * 4)); GCHK(S.alloc(&d_order, m * 8));
-	hipLaunchKernelGGL(k_rp_slots, grid(slot_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, 1, qbits, (const unsigned long long *)nullptr, tab[cur], d_occ);
-	GCHK(hipGetLastError());
-	rc = gx->wide ? sdti::layout_order<Ix64>(v, d_sets, d_pre, p, tab[cur], d_occ, slot_total, d_order)
-	              : sdti::layout_order<Ix32>(v, d_sets, d_pre, p, tab[cur], d_occ, slot_total, d_order);
-	if (rc != SDT_OK) return rc;
-	(void)hipFree(S.release(tab[cur])); (void)hipFree(S.release(d_occ)); (void)hipFree(S.release(d_home));
-	if (timing) fprintf(stderr, "[device]     layout: order extracted at %.1f ms\n", now_ms() - t_call);
-	// ---- number the nodes (as sdt_gpu_layout_apply)
+	T.tick("keys gathered");
+	return SDT_OK;
+}
+
+// number the n nodes: idx[slot of the node at visiting position i] = i, slot_of[i] = that slot (order[i] = its rank in sval), and make
+// that the numbering of the context.  The order is on the device already (d_order), or it is uploaded here from h_order.  first_done:
+// the first-occurrence ordinals have done their work.  not_ranks() is the caller's refusal of an order that is no permutation
+template <class Refusal>
+static int layout_publish(sdt_ctx *c, const GraphView &v, Scratch &S, const uint64_t *sval, uint64_t *d_order, const uint64_t *h_order, uint64_t n, bool first_done,
+                          Refusal not_ranks)
+{
+	sdti::GraphExt *gx = ext_of(v);
 	if (*v.d_idx) { (void)hipFree(*v.d_idx); *v.d_idx = nullptr; }
 	*v.idx_slots = *v.idx_n = 0;
 	if (gx->d_slot_of) { (void)hipFree(gx->d_slot_of); gx->d_slot_of = nullptr; gx->n_nodes = 0; }
-	// the replay is through (every limit it can run into lies behind): the first-occurrence ordinals have done their work, and the
-	// node index is exactly as large -- 8 bytes per table slot that it finds in the arena instead of asking the driver
-	if (!sdt_test_env("SDT_KEEP_FIRST")) { rc = sdti::drop_first(c); if (rc != SDT_OK) return rc; }
+	// after a replay on the device every limit it can run into lies behind: the first-occurrence ordinals go, and the node index is
+	// exactly as large -- 8 bytes per table slot that it finds in the arena instead of asking the driver
+	if (first_done && !sdt_test_env("SDT_KEEP_FIRST")) { const int rc = sdti::drop_first(c); if (rc != SDT_OK) return rc; }
 	uint64_t *d_idx, *d_slot_of;
+	const uint64_t m = n ? n : 1;
+	const bool from_host = !d_order;
+	if (from_host) GCHK(S.alloc(&d_order, m * 8));
 	GCHK(S.alloc(&d_idx, v.slots * 8)); GCHK(S.alloc(&d_slot_of, m * 8));
 	GCHK(hipMemsetAsync(d_idx, 0xFF, v.slots * 8, v.stream));
-	rc = gx->wide ? sdti::layout_number(v, ix64_of(gx), v1s, d_order, n, d_idx, d_slot_of) : sdti::layout_number(v, Ix32(), v1s, d_order, n, d_idx, d_slot_of);
+	int rc = from_host ? sdti::h2d_big(v.copy_stream, d_order, h_order, n * 8) : SDT_OK;
 	if (rc != SDT_OK) return rc;
-	rc = sdti::sync_stats(c);
-	if (rc != SDT_OK) return fail(SDT_ESTATE, "layout on the device: %llu positions of the order are not ranks", (unsigned long long)v.h_stats->probe_fail);
+	rc = gx->wide ? sdti::layout_number(v, ix64_of(gx), sval, d_order, n, d_idx, d_slot_of) : sdti::layout_number(v, Ix32(), sval, d_order, n, d_idx, d_slot_of);
+	if (rc != SDT_OK) return rc;
+	if (sdti::sync_stats(c) != SDT_OK) return not_ranks();
 	*v.d_idx = (uint64_t *)S.release(d_idx);
 	*v.idx_slots = v.slots;
 	*v.idx_n = n;
 	gx->d_slot_of = (uint64_t *)S.release(d_slot_of);
 	gx->n_nodes = n;
-	if (timing) fprintf(stderr, "[device]     layout: whole call %.1f ms\n", now_ms() - t_call);
-	if (sdt_env("SDT_TIMING")) fprintf(stderr, "[device]   layout replay: %zu generations, %d rounds of timed insertion in all, %llu table slots\n", max_gens, total_rounds, (unsigned long long)tab_total);
+	return SDT_OK;
+}
+
+// ---- the replay of the probing: every set's generations side by side (sdt_layout_plan.h), a growth as a fixed point of insertion
+// times (sdt_graph_kernels.cuh; tools/replay_fixed_point.c is the proof on the CPU) ----------------------------------------
+struct Replay {
+	const GraphView &v;
+	const sdt::RpSchedule &sch;
+	const CallTimer &T;
+	const int p;
+	const uint64_t *d_keys;                                   // the keys by rank (layout_sort)
+	std::vector<RpSet> sets;                                  // the sets as the next kernels see them, and the prefix sums of their items
+	std::vector<unsigned long long> pre;
+	// per OLD slot of a growth: time and home; per new slot: the word a round took out of it; per entry: the two lists of the rounds
+	// (an entry whose time changed is listed once); the two table buffers, every set's region at its final size
+	unsigned long long *tab[2], *d_time, *d_saved, *d_list[2], *d_pre, list_chunks;
+	uint32_t *d_home, *d_home_slot;
+	RpSet *d_sets;
+	unsigned int *d_flags;
+	RpRound *d_round;
+	int cur = 0, total_rounds = 0;
+	double t_rehash = 0, t_strip = 0, t_put = 0;              // (SDT_TIMING)
+
+	Replay(const GraphView &v_, const sdt::RpSchedule &sch_, const CallTimer &T_, int p_, const uint64_t *set_start, const uint64_t *d_keys_)
+	    : v(v_), sch(sch_), T(T_), p(p_), d_keys(d_keys_), sets(p_), pre(p_ + 1)
+	{
+		for (int s = 0; s < p; s++) { sets[s].key0 = set_start[s]; sets[s].tab0 = sch.tab0[s]; sets[s].m = (uint32_t)(set_start[s + 1] - set_start[s]); }
+	}
+	dim3 grid(unsigned long long items) const { return dim3(sdti::scan_grid(v.cu_count, items ? items : 1)); }
+	bool has(int s, size_t gen) const { return gen < sch.gens[s].size(); }
+	int alloc(Scratch &S, uint64_t n)
+	{
+		const uint64_t m = n ? n : 1, slots = sch.tab_total + 1;
+		list_chunks = sdt::rp_list_chunks(n, v.cu_count);
+		const unsigned long long list_cap = list_chunks * AP_CH;
+		GCHK(S.alloc(&tab[0], slots * 8)); GCHK(S.alloc(&tab[1], slots * 8));
+		GCHK(S.alloc(&d_time, slots * 8)); GCHK(S.alloc(&d_home_slot, slots * 4)); GCHK(S.alloc(&d_saved, slots * 8));
+		GCHK(S.alloc(&d_list[0], list_cap * 8)); GCHK(S.alloc(&d_list[1], list_cap * 8)); GCHK(S.alloc(&d_round, sizeof(RpRound)));
+		GCHK(S.alloc(&d_home, m * 4)); GCHK(S.alloc(&d_sets, (size_t)p * sizeof(RpSet))); GCHK(S.alloc(&d_pre, (size_t)(p + 1) * 8)); GCHK(S.alloc(&d_flags, 4));
+		GCHK(hipMemsetAsync(tab[0], 0, slots * 8, v.stream));
+		return SDT_OK;
+	}
+	int upload(const std::vector<RpSet> &h_sets)
+	{
+		GCHK(hipStreamSynchronize(v.stream));                  // (kernels in flight read the old copies; the host vectors change right after)
+		GCHK(hipMemcpy(d_sets, h_sets.data(), (size_t)p * sizeof(RpSet), hipMemcpyHostToDevice));
+		GCHK(hipMemcpy(d_pre, pre.data(), (size_t)(p + 1) * 8, hipMemcpyHostToDevice));
+		return SDT_OK;
+	}
+	int grow(size_t gen);
+	int put(size_t gen);
+	int order(Scratch &S, bool wide, uint64_t n, uint64_t **d_order);
+};
+
+// the growth into generation gen's size of every set that has one: rehash init, round 0, rounds to the fixed point, strip
+int Replay::grow(size_t gen)
+{
+	unsigned long long old_total = 0;
+	for (int s = 0; s < p; s++) {
+		sets[s].old_size = has(s, gen) ? sch.gens[s][gen - 1].size : 0;
+		if (has(s, gen)) sets[s].size = sch.gens[s][gen].size;
+		sets[s].lo = 0; sets[s].hi = has(s, gen) ? sch.gens[s][gen].lo : 0;            // ids [0, lo) are in the table
+		pre[s] = old_total;
+		old_total += sets[s].old_size;
+	}
+	pre[p] = old_total;
+	int rc = upload(sets); if (rc != SDT_OK) return rc;
+	const int nxt = cur ^ 1, rounds0 = total_rounds;
+	const double t_g0 = T.ms();
+	// time (q, 0) and the home in the new geometry, per old slot
+	LAUNCH_NW_NOTAB(v, k_rp_rehash_init, grid(old_total), d_keys, d_sets, d_pre, p, tab[cur], d_time, d_home_slot);
+	for (int s = 0; s < p; s++)                           // (only the regions of the sets that grow, at their new size: the early growths are tiny)
+		if (sets[s].old_size) GCHK(hipMemsetAsync(tab[nxt] + sets[s].tab0, 0, (size_t)sets[s].size * 8, v.stream));
+	GCHK(hipMemsetAsync(d_round, 0, sizeof(RpRound), v.stream));
+	// round 0: everybody
+	hipLaunchKernelGGL(k_rp_ins_all, grid(old_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, sch.qbits, tab[cur], tab[nxt], d_home_slot, d_time, d_round);
+	hipLaunchKernelGGL(k_rp_eval_all, grid(old_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, sch.qbits, tab[cur], tab[nxt], d_home_slot, d_time,
+	                   d_list[0], list_chunks, d_round);
+	GCHK(hipGetLastError());
+	// (SDT_RP_MAX_ROUNDS: test hook -- a cap that real data passes, so that the caller's other path is exercised)
+	static const int max_rounds = sdt_test_env("SDT_RP_MAX_ROUNDS") ? atoi(sdt_test_env("SDT_RP_MAX_ROUNDS")) : 60;
+	int lc = 0;
+	for (int round = 0;; round++) {
+		RpRound h_round;
+		GCHK(hipMemcpyAsync(&h_round, d_round, sizeof(RpRound), hipMemcpyDeviceToHost, v.stream));
+		GCHK(hipStreamSynchronize(v.stream));
+		total_rounds++;
+		if (h_round.flags) return fail(SDT_ELIMIT, "layout on the device: %s", (h_round.flags & 2u) ? "an insertion found no slot" :
+		                               (h_round.flags & 4u) ? "an eviction chain or a stretch of slots past its field" : "the list of a round is full");
+		if (!h_round.n_next) break;
+		if (round >= max_rounds) return fail(SDT_ELIMIT, "layout on the device: a growth did not settle in %d rounds", max_rounds);
+		// from the home of every changed entry to the end of its cluster: taken out, laid out again, the old slots in there evaluated again
+		const unsigned long long n_list = h_round.n_next * AP_CH;
+		GCHK(hipMemsetAsync(d_round, 0, sizeof(RpRound), v.stream));
+		hipLaunchKernelGGL(k_rp_collect, grid(n_list), dim3(TPB), 0, v.stream, d_sets, tab[nxt], d_saved, d_list[lc], n_list, d_round);
+		hipLaunchKernelGGL(k_rp_ins_list, grid(n_list), dim3(TPB), 0, v.stream, d_sets, d_pre, sch.qbits, tab[nxt], d_saved, d_home_slot, d_time, d_list[lc], n_list, d_round);
+		hipLaunchKernelGGL(k_rp_eval_list, grid(n_list), dim3(TPB), 0, v.stream, d_sets, d_pre, sch.qbits, tab[cur], tab[nxt], d_home_slot, d_time,
+		                   d_list[lc], n_list, d_list[lc ^ 1], list_chunks, d_round);
+		GCHK(hipGetLastError());
+		lc ^= 1;
+	}
+	const double t_g1 = T.ms();
+	t_rehash += t_g1 - t_g0;
+	if (T.on && old_total > (1u << 24)) fprintf(stderr, "[device]     growth %zu: %llu old slots, %d rounds, %.1f ms\n", gen, old_total, total_rounds - rounds0, t_g1 - t_g0);
+	// the settled layout without its times is the table of this generation
+	unsigned long long new_total = 0;
+	for (int s = 0; s < p; s++) { pre[s] = new_total; new_total += has(s, gen) ? sets[s].size : 0; }
+	pre[p] = new_total;
+	// (sets without this generation keep their table: copy their region over unchanged)
+	for (int s = 0; s < p; s++)
+		if (!has(s, gen)) GCHK(hipMemcpyAsync(tab[nxt] + sets[s].tab0, tab[cur] + sets[s].tab0, (size_t)sets[s].size * 8, hipMemcpyDeviceToDevice, v.stream));
+	rc = upload(sets); if (rc != SDT_OK) return rc;
+	// slots of the sets that grew: pre counts only those (others have size 0 in the prefix)
+	std::vector<RpSet> grown = sets;
+	for (int s = 0; s < p; s++) if (!has(s, gen)) grown[s].size = 0;
+	GCHK(hipMemcpy(d_sets, grown.data(), (size_t)p * sizeof(RpSet), hipMemcpyHostToDevice));
+	hipLaunchKernelGGL(k_rp_slots, grid(new_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, 0, sch.qbits, tab[cur], tab[nxt], (uint32_t *)nullptr);
+	GCHK(hipGetLastError());
+	GCHK(hipStreamSynchronize(v.stream));
+	cur = nxt;
+	t_strip += T.ms() - t_g1;
+	return SDT_OK;
+}
+
+// the puts of generation gen: ids [lo, hi) of every set that has one, into its table as it is
+int Replay::put(size_t gen)
+{
+	const double t_p0 = T.ms();
+	unsigned long long put_total = 0;
+	for (int s = 0; s < p; s++) {
+		sets[s].lo = has(s, gen) ? sch.gens[s][gen].lo : 0;
+		sets[s].hi = has(s, gen) ? sch.gens[s][gen].hi : 0;
+		if (has(s, gen)) sets[s].size = sch.gens[s][gen].size;
+		pre[s] = put_total;
+		put_total += sets[s].hi - sets[s].lo;
+	}
+	pre[p] = put_total;
+	const int rc = upload(sets); if (rc != SDT_OK) return rc;
+	unsigned int h_flags = 0;
+	GCHK(hipMemsetAsync(d_flags, 0, 4, v.stream));
+	LAUNCH_NW_NOTAB(v, k_rp_home, grid(put_total), d_keys, d_sets, d_pre, p, 0, d_home);
+	hipLaunchKernelGGL(k_rp_put, grid(put_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, d_home, tab[cur], d_flags);
+	GCHK(hipGetLastError());
+	GCHK(hipMemcpyAsync(&h_flags, d_flags, 4, hipMemcpyDeviceToHost, v.stream));
+	GCHK(hipStreamSynchronize(v.stream));
+	if (h_flags) return fail(SDT_ELIMIT, "layout on the device: a put found no slot");
+	t_put += T.ms() - t_p0;
+	return SDT_OK;
+}
+
+// the visiting order from the settled tables: the sets one after the other, every set's slots in order; *d_order[i] = rank of the node at
+// visiting position i.  The buffers of the replay go as soon as they are not needed
+int Replay::order(Scratch &S, bool wide, uint64_t n, uint64_t **d_order)
+{
+	unsigned long long slot_total = 0;
+	for (int s = 0; s < p; s++) { sets[s].size = sch.gens[s].back().size; pre[s] = slot_total; slot_total += sets[s].size; }
+	pre[p] = slot_total;
+	int rc = upload(sets); if (rc != SDT_OK) return rc;
+	// (the buffers of the replay that are free now make room for the flags and their prefix sum)
+	for (void *q : {(void *)tab[cur ^ 1], (void *)d_time, (void *)d_home_slot, (void *)d_saved, (void *)d_list[0], (void *)d_list[1]}) (void)hipFree(S.release(q));
+	uint32_t *d_occ;
+	GCHK(S.alloc(&d_occ, (slot_total + 1) * 4)); GCHK(S.alloc(d_order, (n ? n : 1) * 8));
+	hipLaunchKernelGGL(k_rp_slots, grid(slot_total), dim3(TPB), 0, v.stream, d_sets, d_pre, p, 1, sch.qbits, (const unsigned long long *)nullptr, tab[cur], d_occ);
+	GCHK(hipGetLastError());
+	rc = wide ? sdti::layout_order<Ix64>(v, d_sets, d_pre, p, tab[cur], d_occ, slot_total, *d_order)
+	          : sdti::layout_order<Ix32>(v, d_sets, d_pre, p, tab[cur], d_occ, slot_total, *d_order);
+	if (rc != SDT_OK) return rc;
+	(void)hipFree(S.release(tab[cur])); (void)hipFree(S.release(d_occ)); (void)hipFree(S.release(d_home));
 	return SDT_OK;
 }
 
 extern "C" {
 
 // ---- layout ---------------------------------------------------------------------------------------------------------
+int sdt_gpu_layout_on_device(sdt_ctx *c, int p, int nw_variant, int small_init, uint64_t *set_start, uint64_t *n_out)
+{
+	if (!c || !n_out || !set_start) return fail(SDT_EINVAL, "NULL argument");
+	const GraphView v0 = sdti::graph_view(c);
+	GRAPH_ENTER(v0);
+	const CallTimer T;
+	int rc = sdti::release_pass1(c);
+	if (rc != SDT_OK) return rc;
+	T.tick("pass 1 released");
+	const GraphView v = sdti::graph_view(c);
+	const uint64_t n = v.h_stats->distinct;
+	*n_out = n;
+	rc = layout_check(v, p, nw_variant);
+	if (rc != SDT_OK) return rc;
+	sdti::GraphExt *gx = ext_of(v);
+	rc = graph_choose_form(gx, n);                           // (the ranks of the numbering below: 32-bit below 2^32 - 16 nodes, else 64-bit)
+	if (rc != SDT_OK) return rc;
+	if (gx->d_sval) { (void)hipFree(gx->d_sval); gx->d_sval = nullptr; gx->n_sorted = 0; }
+	Scratch S;
+	SortedNodes sorted;
+	rc = layout_sort(c, v, S, p, nw_variant, n, set_start, T, sorted);
+	if (rc != SDT_OK) return rc;
+	(void)hipFree(S.release(sorted.k1));                      // (the sorted sort keys are not needed any more)
+	if (v.nw != 1) (void)hipFree(S.release(sorted.k0));
+	(void)hipFree(S.release(sorted.v0s));
+	// every set's growth schedule (a function of its number of keys only)
+	std::vector<uint64_t> set_size(p);
+	for (int s = 0; s < p; s++) set_size[s] = set_start[s + 1] - set_start[s];
+	sdt::RpSchedule sch;
+	const sdt::RpPlanStatus plan = sdt::rp_schedule(set_size.data(), p, nw_variant, small_init, sch);
+	if (plan == sdt::RP_PLAN_SLOTS) return fail(SDT_EINVAL, "layout on the device: a set's table passes 2^32 slots");
+	if (plan == sdt::RP_PLAN_BITS) return fail(SDT_ELIMIT, "layout on the device: twice %d slot bits do not fit the table word (or %d sets the list entry)", sch.qbits, p);
+	T.tick("schedule made");
+	Replay R(v, sch, T, p, set_start, sorted.d_keys);
+	rc = R.alloc(S, n);
+	if (rc != SDT_OK) return rc;
+	T.tick("buffers made");
+	const double t_start = T.ms();
+	if (T.on) fprintf(stderr, "[device]     layout: release + sort + gather + schedule + buffers %.1f ms\n", t_start);
+	for (size_t gen = 0; gen < sch.max_gens; gen++) {
+		if (gen > 0) { rc = R.grow(gen); if (rc != SDT_OK) return rc; }
+		rc = R.put(gen);
+		if (rc != SDT_OK) return rc;
+	}
+	if (T.on) fprintf(stderr, "[device]     layout replay so far %.1f ms: rehash rounds %.1f, strip + copies %.1f, puts %.1f ms\n", T.ms() - t_start, R.t_rehash, R.t_strip, R.t_put);
+	uint64_t *d_order;
+	rc = R.order(S, gx->wide, n, &d_order);
+	if (rc != SDT_OK) return rc;
+	if (T.on) fprintf(stderr, "[device]     layout: order extracted at %.1f ms\n", T.ms());
+	rc = layout_publish(c, v, S, sorted.v1s, d_order, nullptr, n, true, [&] {
+		return fail(SDT_ESTATE, "layout on the device: %llu positions of the order are not ranks", (unsigned long long)v.h_stats->probe_fail);
+	});
+	if (rc != SDT_OK) return rc;
+	if (T.on) fprintf(stderr, "[device]     layout: whole call %.1f ms\n[device]   layout replay: %zu generations, %d rounds of timed insertion in all, %llu table slots\n", T.ms(),
+	                  sch.max_gens, R.total_rounds, (unsigned long long)sch.tab_total);
+	return SDT_OK;
+}
+
 int sdt_gpu_layout_sorted_keys(sdt_ctx *c, int p, int nw_variant, uint64_t *keys, uint64_t max_nodes, uint64_t *set_start, uint64_t *n_out)
 {
 	if (!c || !n_out) return fail(SDT_EINVAL, "NULL argument");
@@ -405,39 +415,18 @@ int sdt_gpu_layout_sorted_keys(sdt_ctx *c, int p, int nw_variant, uint64_t *keys
 	*n_out = n;
 	if (!keys && !set_start) return SDT_OK;
 	if (!keys || !set_start) return fail(SDT_EINVAL, "NULL argument");
-	if (!v.d_first) return fail(SDT_ESTATE, "first-occurrence ordinals were not tracked: init with SDT_FLAG_TRACK_FIRST");
-	if (p < 1 || p > 256) return fail(SDT_EINVAL, "layout on the device: 1..256 sets, asked for %d", p);
-	if (nw_variant < v.nw || nw_variant > 4) return fail(SDT_EINVAL, "a %d-word variant cannot hold %d-word keys", nw_variant, v.nw);
+	rc = layout_check(v, p, nw_variant);
+	if (rc != SDT_OK) return rc;
 	if (max_nodes < n) return fail(SDT_EINVAL, "key array holds %llu nodes, the table has %llu", (unsigned long long)max_nodes, (unsigned long long)n);
 	sdti::GraphExt *gx = ext_of(v);
 	if (gx->d_sval) { (void)hipFree(gx->d_sval); gx->d_sval = nullptr; gx->n_sorted = 0; }
 	Scratch S;
-	const uint64_t m = n ? n : 1;
-	uint64_t *k0, *k1, *v0s, *v1s, *d_keys, *d_ss;
-	unsigned long long *d_cur;
-	GCHK(S.alloc(&k0, m * 8)); GCHK(S.alloc(&k1, m * 8)); GCHK(S.alloc(&v0s, m * 8)); GCHK(S.alloc(&v1s, m * 8));
-	GCHK(S.alloc(&d_cur, 8)); GCHK(S.alloc(&d_ss, (size_t)(p + 1) * 8));
-	GCHK(hipMemsetAsync(d_cur, 0, 8, v.stream));
-	const int g = sdti::scan_grid(v.cu_count, v.slots);
-	LAUNCH_NW(v, k_layout_keys, g, (uint32_t)p, nw_variant, k0, v0s, (unsigned long long)n, d_cur, v.d_stats);
-	GCHK(hipGetLastError());
-	rc = sdti::sync_stats(c);
-	if (rc != SDT_OK) return fail(SDT_ESTATE, "layout: %llu nodes without a usable first-occurrence ordinal (>= 2^56, or more nodes than counted)", (unsigned long long)v.h_stats->probe_fail);
-	unsigned end_bit = 56;
-	for (int q = p - 1; q > 0; q >>= 1) end_bit++;
-	rc = sort_pairs<uint64_t>(v, k0, k1, v0s, v1s, n, end_bit);
+	SortedNodes sorted;
+	rc = layout_sort(c, v, S, p, nw_variant, n, set_start, CallTimer(false), sorted);
 	if (rc != SDT_OK) return rc;
-	hipLaunchKernelGGL(k_layout_set_starts, dim3((p + 1 + 63) / 64), dim3(64), 0, v.stream, k1, n, (uint32_t)p, d_ss);
-	GCHK(hipGetLastError());
-	GCHK(hipMemcpyAsync(set_start, d_ss, (size_t)(p + 1) * 8, hipMemcpyDeviceToHost, v.stream));
-	// k0 is free again: the keys in sorted order go there (NW words each: reuse needs NW * n words)
-	if (v.nw == 1) d_keys = k0; else GCHK(S.alloc(&d_keys, m * v.nw * 8));
-	LAUNCH_NW(v, k_layout_gather_keys, sdti::scan_grid(v.cu_count, m), v1s, n, d_keys);
-	GCHK(hipGetLastError());
-	GCHK(hipStreamSynchronize(v.stream));
-	rc = sdti::d2h_big(v.copy_stream, keys, d_keys, n * v.nw * 8);
+	rc = sdti::d2h_big(v.copy_stream, keys, sorted.d_keys, n * v.nw * 8);
 	if (rc != SDT_OK) return rc;
-	gx->d_sval = (uint64_t *)S.release(v1s);
+	gx->d_sval = (uint64_t *)S.release(sorted.v1s);
 	gx->n_sorted = n;
 	return SDT_OK;
 }
@@ -451,25 +440,11 @@ int sdt_gpu_layout_apply(sdt_ctx *c, const uint64_t *order, uint64_t n)
 	GRAPH_ENTER(v);
 	int rc = graph_choose_form(gx, n);
 	if (rc != SDT_OK) return rc;
-	if (*v.d_idx) { (void)hipFree(*v.d_idx); *v.d_idx = nullptr; }
-	*v.idx_slots = *v.idx_n = 0;
-	if (gx->d_slot_of) { (void)hipFree(gx->d_slot_of); gx->d_slot_of = nullptr; gx->n_nodes = 0; }
 	Scratch S;
-	uint64_t *d_order, *d_idx, *d_slot_of;
-	const uint64_t m = n ? n : 1;
-	GCHK(S.alloc(&d_order, m * 8)); GCHK(S.alloc(&d_idx, v.slots * 8)); GCHK(S.alloc(&d_slot_of, m * 8));
-	GCHK(hipMemsetAsync(d_idx, 0xFF, v.slots * 8, v.stream));
-	rc = sdti::h2d_big(v.copy_stream, d_order, order, n * 8);
+	rc = layout_publish(c, v, S, gx->d_sval, nullptr, order, n, false, [&] {
+		return fail(SDT_EINVAL, "layout order: %llu entries are not ranks below %llu", (unsigned long long)v.h_stats->probe_fail, (unsigned long long)n);
+	});
 	if (rc != SDT_OK) return rc;
-	rc = gx->wide ? sdti::layout_number(v, ix64_of(gx), gx->d_sval, d_order, n, d_idx, d_slot_of) : sdti::layout_number(v, Ix32(), gx->d_sval, d_order, n, d_idx, d_slot_of);
-	if (rc != SDT_OK) return rc;
-	rc = sdti::sync_stats(c);
-	if (rc != SDT_OK) return fail(SDT_EINVAL, "layout order: %llu entries are not ranks below %llu", (unsigned long long)v.h_stats->probe_fail, (unsigned long long)n);
-	*v.d_idx = (uint64_t *)S.release(d_idx);
-	*v.idx_slots = v.slots;
-	*v.idx_n = n;
-	gx->d_slot_of = (uint64_t *)S.release(d_slot_of);
-	gx->n_nodes = n;
 	(void)hipFree(gx->d_sval);
 	gx->d_sval = nullptr;
 	gx->n_sorted = 0;
@@ -583,7 +558,6 @@ int sdt_gpu_minor_out_commit_begin(sdt_ctx *c, double threshold, uint64_t max_co
 	                : sdti::minor_out_commit_begin(c, Ix32(), threshold, max_component, largest, n_skipped, n_skipped_records);
 }
 
-
 int sdt_gpu_minor_out_commit_finish(sdt_ctx *c, uint64_t *off, uint64_t *linear, uint64_t *n_written)
 {
 	if (!c || !off || !linear || !n_written) return fail(SDT_EINVAL, "NULL argument");
@@ -659,7 +633,6 @@ int sdt_gpu_fetch_written(sdt_ctx *c, uint64_t *node, uint32_t *l_links, uint32_
 	return rc;
 }
 
-
 // ---- kmer2edges on the device (node2edge.c:46-561; sdt_graph_phases.hpp) ------------------------------------------------
 int sdt_gpu_build_edges(sdt_ctx *c, uint64_t *n_edges, uint64_t *num_ed, uint64_t *n_bases)
 {
@@ -703,42 +676,37 @@ int sdt_gpu_fetch_records(sdt_ctx *c, uint64_t *dst, uint64_t nwords)
 	return rc;
 }
 
-// ---- graph-cleaning dry runs on the device mirror of the host graph ---------------------------------------
-static int upload_keys(sdt_ctx *c, const uint64_t *keys, uint64_t n, uint64_t **d_k)
+// ---- graph-cleaning dry runs on the device mirror of the host graph, indexed by host position ---------------------------------
+static int upload_keys(const GraphView &v, Scratch &S, const uint64_t *keys, uint64_t n, uint64_t **d_k)
 {
-	const GraphView v = sdti::graph_view(c);
-	HIPCHK(hipMalloc((void **)d_k, (n ? n : 1) * v.nw * sizeof(uint64_t)));
-	const int rc = sdti::h2d_big(v.copy_stream, *d_k, keys, n * v.nw * sizeof(uint64_t));
-	if (rc != SDT_OK) { (void)hipFree(*d_k); *d_k = nullptr; }
-	return rc;
+	GCHK(S.alloc(d_k, (n ? n : 1) * v.nw * sizeof(uint64_t)));
+	return sdti::h2d_big(v.copy_stream, *d_k, keys, n * v.nw * sizeof(uint64_t));
 }
 
 int sdt_gpu_set_node_index(sdt_ctx *c, const uint64_t *keys, uint64_t n)
 {
 	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
 	const GraphView v = sdti::graph_view(c);
-	if (!c || (n && !keys))
-		return fail(SDT_EINVAL, "NULL argument");
+	if (n && !keys) return fail(SDT_EINVAL, "NULL argument");
 	GRAPH_ENTER(v);
-	HIPCHK(hipStreamSynchronize(v.stream));
-	if ((*v.d_idx)) HIPCHK(hipFree((*v.d_idx)));
-	(*v.d_idx) = nullptr;
-	(*v.idx_slots) = (*v.idx_n) = 0;
-	HIPCHK(hipMalloc((void **)&(*v.d_idx), v.slots * sizeof(uint64_t)));
-	HIPCHK(hipMemsetAsync((*v.d_idx), 0xFF, v.slots * sizeof(uint64_t), v.stream));
+	GCHK(hipStreamSynchronize(v.stream));
+	if (*v.d_idx) GCHK(hipFree(*v.d_idx));
+	*v.d_idx = nullptr;
+	*v.idx_slots = *v.idx_n = 0;
+	GCHK(hipMalloc(v.d_idx, v.slots * sizeof(uint64_t)));
+	GCHK(hipMemsetAsync(*v.d_idx, 0xFF, v.slots * sizeof(uint64_t), v.stream));
 	sdti::GraphExt *gx = ext_of(v);
 	int rc = graph_choose_form(gx, n);
 	if (rc != SDT_OK) return rc;
-	uint64_t *d_k = nullptr;
-	rc = upload_keys(c, keys, n, &d_k);
+	Scratch S;
+	uint64_t *d_k;
+	rc = upload_keys(v, S, keys, n, &d_k);
 	if (rc != SDT_OK) return rc;
 	rc = gx->wide ? sdti::set_index(v, ix64_of(gx), d_k, n) : sdti::set_index(v, Ix32(), d_k, n);
-	if (rc == SDT_OK) rc = sdti::sync_stats(c);
-	(void)hipFree(d_k);
-	if (rc != SDT_OK)
+	if (rc != SDT_OK || sdti::sync_stats(c) != SDT_OK)
 		return fail(SDT_ESTATE, "sdt_gpu_set_node_index: %llu nodes are not in the table", (unsigned long long)v.h_stats->probe_fail);
-	(*v.idx_slots) = v.slots;
-	(*v.idx_n) = n;
+	*v.idx_slots = v.slots;
+	*v.idx_n = n;
 	return SDT_OK;
 }
 
@@ -746,147 +714,150 @@ int sdt_gpu_update_nodes(sdt_ctx *c, const uint64_t *keys, const uint32_t *l_lin
 {
 	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
 	const GraphView v = sdti::graph_view(c);
-	if (!c || (n && (!keys || !l_links || !r_flags)))
-		return fail(SDT_EINVAL, "NULL argument");
-	if (!n)
-		return SDT_OK;
+	if (n && (!keys || !l_links || !r_flags)) return fail(SDT_EINVAL, "NULL argument");
+	if (!n) return SDT_OK;
 	GRAPH_ENTER(v);
-	uint64_t *d_k = nullptr;
-	uint32_t *d_l = nullptr, *d_r = nullptr;
-	int rc = upload_keys(c, keys, n, &d_k);
+	Scratch S;
+	uint64_t *d_k;
+	uint32_t *d_l, *d_r;
+	const int rc = upload_keys(v, S, keys, n, &d_k);
 	if (rc != SDT_OK) return rc;
-	hipError_t e = hipMalloc((void **)&d_l, n * 4);
-	if (e == hipSuccess) e = hipMalloc((void **)&d_r, n * 4);
-	if (e == hipSuccess) e = hipMemcpyAsync(d_l, l_links, n * 4, hipMemcpyHostToDevice, v.stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(d_r, r_flags, n * 4, hipMemcpyHostToDevice, v.stream);
-	if (e == hipSuccess) {
-		const int g = sdti::scan_grid(v.cu_count, n);
-		if (v.nw == 1) hipLaunchKernelGGL(k_update_nodes<1>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<1>(v), d_k, d_l, d_r, n, v.d_stats);
-		else if (v.nw == 2) hipLaunchKernelGGL(k_update_nodes<2>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<2>(v), d_k, d_l, d_r, n, v.d_stats);
-		else hipLaunchKernelGGL(k_update_nodes<4>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<4>(v), d_k, d_l, d_r, n, v.d_stats);
-		e = hipGetLastError();
-	}
-	rc = e == hipSuccess ? sdti::sync_stats(c) : fail(SDT_EHIP, "sdt_gpu_update_nodes: %s", hipGetErrorString(e));
-	(void)hipFree(d_k);
-	if (d_l) (void)hipFree(d_l);
-	if (d_r) (void)hipFree(d_r);
-	if (rc != SDT_OK && e == hipSuccess)
+	GCHK(S.alloc(&d_l, n * 4)); GCHK(S.alloc(&d_r, n * 4));
+	GCHK(hipMemcpyAsync(d_l, l_links, n * 4, hipMemcpyHostToDevice, v.stream));
+	GCHK(hipMemcpyAsync(d_r, r_flags, n * 4, hipMemcpyHostToDevice, v.stream));
+	LAUNCH_NW(v, k_update_nodes, sdti::scan_grid(v.cu_count, n), d_k, d_l, d_r, n, v.d_stats);
+	GCHK(hipGetLastError());
+	if (sdti::sync_stats(c) != SDT_OK)
 		return fail(SDT_ESTATE, "sdt_gpu_update_nodes: %llu nodes are not in the table", (unsigned long long)v.h_stats->probe_fail);
-	return rc;
+	return SDT_OK;
+}
+
+// what the dry runs by host position ask of the context: no node base, a node index (`bad` = the call has a NULL argument)
+static int dry_run_check(const GraphView &v, const char *who, bool bad)
+{
+	if (ext_of(v)->base) return fail(SDT_ESTATE, "%s reads host positions straight from the node index: no node base (SDT_NODE_BASE)", who);
+	if (bad) return fail(SDT_EINVAL, "NULL argument");
+	if (!*v.d_idx || *v.idx_slots != v.slots) return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
+	return SDT_OK;
 }
 
 int sdt_gpu_tip_walks(sdt_ctx *c, int thin, int cut_len, uint64_t *end_idx, uint8_t *info, uint64_t n)
 {
 	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
 	const GraphView v = sdti::graph_view(c);
-	if (ext_of(v)->base) return fail(SDT_ESTATE, "%s reads host positions straight from the node index: no node base (SDT_NODE_BASE)", "sdt_gpu_tip_walks");
-	if (!c || !end_idx || !info)
-		return fail(SDT_EINVAL, "NULL argument");
-	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
-		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
-	if (n != (*v.idx_n))
-		return fail(SDT_EINVAL, "the node index holds %llu nodes, the output arrays %llu", (unsigned long long)(*v.idx_n), (unsigned long long)n);
+	const int rc = dry_run_check(v, "sdt_gpu_tip_walks", !end_idx || !info);
+	if (rc != SDT_OK) return rc;
+	if (n != *v.idx_n)
+		return fail(SDT_EINVAL, "the node index holds %llu nodes, the output arrays %llu", (unsigned long long)*v.idx_n, (unsigned long long)n);
 	GRAPH_ENTER(v);
-	uint64_t *d_e = nullptr;
-	uint8_t *d_i = nullptr;
-	HIPCHK(hipMalloc((void **)&d_e, (n ? n : 1) * sizeof(uint64_t)));
-	hipError_t e = hipMalloc((void **)&d_i, n ? n : 1);
-	if (e == hipSuccess) {
-		const int g = sdti::scan_grid(v.cu_count, v.slots);
-		if (v.nw == 1) hipLaunchKernelGGL(k_tip_walks<1>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<1>(v), (*v.d_idx), v.K, thin, cut_len, d_e, d_i, v.d_stats, (uint64_t *)nullptr, 0ULL, (unsigned long long *)nullptr, 2);
-		else if (v.nw == 2) hipLaunchKernelGGL(k_tip_walks<2>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<2>(v), (*v.d_idx), v.K, thin, cut_len, d_e, d_i, v.d_stats, (uint64_t *)nullptr, 0ULL, (unsigned long long *)nullptr, 2);
-		else hipLaunchKernelGGL(k_tip_walks<4>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<4>(v), (*v.d_idx), v.K, thin, cut_len, d_e, d_i, v.d_stats, (uint64_t *)nullptr, 0ULL, (unsigned long long *)nullptr, 2);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(end_idx, d_e, n * sizeof(uint64_t), hipMemcpyDeviceToHost, v.stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(info, d_i, n, hipMemcpyDeviceToHost, v.stream);
-	int rc = e == hipSuccess ? sdti::sync_stats(c) : fail(SDT_EHIP, "sdt_gpu_tip_walks: %s", hipGetErrorString(e));
-	(void)hipFree(d_e);
-	if (d_i) (void)hipFree(d_i);
-	if (rc != SDT_OK && e == hipSuccess)
-		return fail(SDT_ESTATE, "sdt_gpu_tip_walks: %llu walks left the graph (a link points at a k-mer that is not a node)",
-		            (unsigned long long)v.h_stats->probe_fail);
-	return rc;
+	Scratch S;
+	uint64_t *d_e;
+	uint8_t *d_i;
+	GCHK(S.alloc(&d_e, (n ? n : 1) * sizeof(uint64_t))); GCHK(S.alloc(&d_i, n ? n : 1));
+	LAUNCH_NW(v, k_tip_walks, sdti::scan_grid(v.cu_count, v.slots), *v.d_idx, v.K, thin, cut_len, d_e, d_i, v.d_stats, (uint64_t *)nullptr, 0ULL, (unsigned long long *)nullptr, 2);
+	GCHK(hipGetLastError());
+	GCHK(hipMemcpyAsync(end_idx, d_e, n * sizeof(uint64_t), hipMemcpyDeviceToHost, v.stream));
+	GCHK(hipMemcpyAsync(info, d_i, n, hipMemcpyDeviceToHost, v.stream));
+	if (sdti::sync_stats(c) != SDT_OK)
+		return fail(SDT_ESTATE, "sdt_gpu_tip_walks: %llu walks left the graph (a link points at a k-mer that is not a node)", (unsigned long long)v.h_stats->probe_fail);
+	return SDT_OK;
 }
-
 
 int sdt_gpu_minor_out_dry(sdt_ctx *c, double threshold, uint64_t *records, uint64_t max_records, uint64_t *n_junctions, uint64_t *n_records)
 {
 	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
 	const GraphView v = sdti::graph_view(c);
-	if (ext_of(v)->base) return fail(SDT_ESTATE, "%s reads host positions straight from the node index: no node base (SDT_NODE_BASE)", "sdt_gpu_minor_out_dry");
-	if (!c || (!records && max_records) || !n_junctions || !n_records)
-		return fail(SDT_EINVAL, "NULL argument");
-	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
-		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
+	const int rc = dry_run_check(v, "sdt_gpu_minor_out_dry", (!records && max_records) || !n_junctions || !n_records);
+	if (rc != SDT_OK) return rc;
 	GRAPH_ENTER(v);
-	uint8_t *d_need = nullptr, *d_flag = nullptr;
-	uint64_t *d_rec = nullptr;
-	unsigned long long *d_cur = nullptr;
-	unsigned long long h1 = 0, h2 = 0;
-	int ret = SDT_OK;
-	const uint64_t n = (*v.idx_n) ? (*v.idx_n) : 1, m = max_records ? max_records : 1;
-#define MO_CHK(expr) do { hipError_t e5_ = (expr); if (e5_ != hipSuccess) { ret = fail(e5_ == hipErrorOutOfMemory ? SDT_ENOMEM : SDT_EHIP, "%s: %s", #expr, hipGetErrorString(e5_)); goto done; } } while (0)
-	MO_CHK(hipMalloc((void **)&d_need, n));
-	MO_CHK(hipMalloc((void **)&d_flag, n));
-	MO_CHK(hipMalloc((void **)&d_rec, m * 9 * sizeof(uint64_t)));
-	MO_CHK(hipMalloc((void **)&d_cur, sizeof(unsigned long long)));
-	MO_CHK(hipMemsetAsync(d_need, 0, n, v.stream));
-	MO_CHK(hipMemsetAsync(d_flag, 0, n, v.stream));
-	MO_CHK(hipMemsetAsync(d_cur, 0, sizeof(unsigned long long), v.stream));
-	{
-		const int g = sdti::scan_grid(v.cu_count, v.slots);
-		if (v.nw == 1) hipLaunchKernelGGL(k_minor_out_junctions<1>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<1>(v), (*v.d_idx), v.K, threshold, d_need, d_flag, d_rec, (unsigned long long)max_records, d_cur, v.d_stats, 9);
-		else if (v.nw == 2) hipLaunchKernelGGL(k_minor_out_junctions<2>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<2>(v), (*v.d_idx), v.K, threshold, d_need, d_flag, d_rec, (unsigned long long)max_records, d_cur, v.d_stats, 9);
-		else hipLaunchKernelGGL(k_minor_out_junctions<4>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<4>(v), (*v.d_idx), v.K, threshold, d_need, d_flag, d_rec, (unsigned long long)max_records, d_cur, v.d_stats, 9);
-		MO_CHK(hipGetLastError());
-		MO_CHK(hipMemcpyAsync(&h1, d_cur, sizeof h1, hipMemcpyDeviceToHost, v.stream));
-		if (v.nw == 1) hipLaunchKernelGGL(k_minor_out_candidates<1>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<1>(v), (*v.d_idx), v.K, d_need, d_flag, d_rec, (unsigned long long)max_records, d_cur, v.d_stats, 9);
-		else if (v.nw == 2) hipLaunchKernelGGL(k_minor_out_candidates<2>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<2>(v), (*v.d_idx), v.K, d_need, d_flag, d_rec, (unsigned long long)max_records, d_cur, v.d_stats, 9);
-		else hipLaunchKernelGGL(k_minor_out_candidates<4>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<4>(v), (*v.d_idx), v.K, d_need, d_flag, d_rec, (unsigned long long)max_records, d_cur, v.d_stats, 9);
-		MO_CHK(hipGetLastError());
-		MO_CHK(hipMemcpyAsync(&h2, d_cur, sizeof h2, hipMemcpyDeviceToHost, v.stream));
-	}
-	ret = sdti::sync_stats(c);
-	if (ret != SDT_OK) {
-		ret = fail(SDT_ESTATE, "sdt_gpu_minor_out_dry: %llu links point at k-mers that are not nodes", (unsigned long long)v.h_stats->probe_fail);
-		goto done;
-	}
+	Scratch S;
+	uint8_t *d_need, *d_flag;
+	uint64_t *d_rec;
+	unsigned long long *d_cur, h1 = 0, h2 = 0;
+	const uint64_t n = *v.idx_n ? *v.idx_n : 1, m = max_records ? max_records : 1;
+	GCHK(S.alloc(&d_need, n)); GCHK(S.alloc(&d_flag, n)); GCHK(S.alloc(&d_rec, m * 9 * sizeof(uint64_t))); GCHK(S.alloc(&d_cur, sizeof(unsigned long long)));
+	GCHK(hipMemsetAsync(d_need, 0, n, v.stream));
+	GCHK(hipMemsetAsync(d_flag, 0, n, v.stream));
+	GCHK(hipMemsetAsync(d_cur, 0, sizeof(unsigned long long), v.stream));
+	const int g = sdti::scan_grid(v.cu_count, v.slots);
+	LAUNCH_NW(v, k_minor_out_junctions, g, *v.d_idx, v.K, threshold, d_need, d_flag, d_rec, (unsigned long long)max_records, d_cur, v.d_stats, 9);
+	GCHK(hipGetLastError());
+	GCHK(hipMemcpyAsync(&h1, d_cur, sizeof h1, hipMemcpyDeviceToHost, v.stream));
+	LAUNCH_NW(v, k_minor_out_candidates, g, *v.d_idx, v.K, d_need, d_flag, d_rec, (unsigned long long)max_records, d_cur, v.d_stats, 9);
+	GCHK(hipGetLastError());
+	GCHK(hipMemcpyAsync(&h2, d_cur, sizeof h2, hipMemcpyDeviceToHost, v.stream));
+	if (sdti::sync_stats(c) != SDT_OK)
+		return fail(SDT_ESTATE, "sdt_gpu_minor_out_dry: %llu links point at k-mers that are not nodes", (unsigned long long)v.h_stats->probe_fail);
 	*n_junctions = h1;
 	*n_records = h2;
-	if (h2 > max_records) {
-		ret = fail(SDT_EFULL, "record array holds %llu, the pass needs %llu", (unsigned long long)max_records, h2);
-		goto done;
-	}
-	if (h2) MO_CHK(hipMemcpy(records, d_rec, h2 * 9 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-done:
-#undef MO_CHK
-	if (d_need) (void)hipFree(d_need);
-	if (d_flag) (void)hipFree(d_flag);
-	if (d_rec) (void)hipFree(d_rec);
-	if (d_cur) (void)hipFree(d_cur);
-	return ret;
+	if (h2 > max_records) return fail(SDT_EFULL, "record array holds %llu, the pass needs %llu", (unsigned long long)max_records, h2);
+	if (h2) GCHK(hipMemcpy(records, d_rec, h2 * 9 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	return SDT_OK;
+}
+
+int sdt_gpu_edge_ports(sdt_ctx *c, uint64_t *records, uint64_t max_records, uint64_t *n_records)
+{
+	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
+	const GraphView v = sdti::graph_view(c);
+	const int rc = dry_run_check(v, "sdt_gpu_edge_ports", (!records && max_records) || !n_records);
+	if (rc != SDT_OK) return rc;
+	GRAPH_ENTER(v);
+	Scratch S;
+	uint64_t *d_rec;
+	unsigned long long *d_cur, h = 0;
+	GCHK(S.alloc(&d_rec, (max_records ? max_records : 1) * 17 * sizeof(uint64_t))); GCHK(S.alloc(&d_cur, sizeof(unsigned long long)));
+	GCHK(hipMemsetAsync(d_cur, 0, sizeof(unsigned long long), v.stream));
+	LAUNCH_NW(v, k_edge_ports, sdti::scan_grid(v.cu_count, v.slots), *v.d_idx, v.K, *v.idx_n + 1, d_rec, (unsigned long long)max_records, d_cur, v.d_stats);
+	GCHK(hipGetLastError());
+	GCHK(hipMemcpyAsync(&h, d_cur, sizeof h, hipMemcpyDeviceToHost, v.stream));
+	if (sdti::sync_stats(c) != SDT_OK)
+		return fail(SDT_ESTATE, "sdt_gpu_edge_ports: %llu chains leave the graph or never end", (unsigned long long)v.h_stats->probe_fail);
+	*n_records = h;
+	if (h > max_records) return fail(SDT_EFULL, "record array holds %llu, the graph has %llu non-linear nodes", (unsigned long long)max_records, h);
+	if (h) GCHK(hipMemcpy(records, d_rec, h * 17 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	return SDT_OK;
+}
+
+int sdt_gpu_tip_walks_compact(sdt_ctx *c, int thin, int cut_len, uint64_t *records, uint64_t max_records, uint64_t *n_records)
+{
+	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
+	const GraphView v = sdti::graph_view(c);
+	const int rc = dry_run_check(v, "sdt_gpu_tip_walks_compact", (!records && max_records) || !n_records);
+	if (rc != SDT_OK) return rc;
+	if (*v.idx_n >= (1ULL << 56)) return fail(SDT_EINVAL, "node indices do not fit 56 bits");
+	GRAPH_ENTER(v);
+	Scratch S;
+	uint64_t *d_rec;
+	unsigned long long *d_cur, h = 0;
+	GCHK(S.alloc(&d_rec, (max_records ? max_records : 1) * 2 * sizeof(uint64_t))); GCHK(S.alloc(&d_cur, sizeof(unsigned long long)));
+	GCHK(hipMemsetAsync(d_cur, 0, sizeof(unsigned long long), v.stream));
+	LAUNCH_NW(v, k_tip_walks, sdti::scan_grid(v.cu_count, v.slots), *v.d_idx, v.K, thin, cut_len, (uint64_t *)nullptr, (uint8_t *)nullptr, v.d_stats, d_rec,
+	          (unsigned long long)max_records, d_cur, 2);
+	GCHK(hipGetLastError());
+	GCHK(hipMemcpyAsync(&h, d_cur, sizeof h, hipMemcpyDeviceToHost, v.stream));
+	if (sdti::sync_stats(c) != SDT_OK)
+		return fail(SDT_ESTATE, "sdt_gpu_tip_walks_compact: %llu walks left the graph", (unsigned long long)v.h_stats->probe_fail);
+	*n_records = h;
+	if (h > max_records) return fail(SDT_EFULL, "record array holds %llu, %llu nodes have a walk", (unsigned long long)max_records, h);
+	if (h) GCHK(hipMemcpy(records, d_rec, h * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	return SDT_OK;
 }
 
 }  // extern "C"
 
 // the host's look-up index with entries E (32- or 64-bit), built on the device in the form of the numbering and copied to `index`
 template <class E>
-static int host_index_entries(sdt_ctx *c, const GraphView &v, E *index, uint64_t index_slots)
+static int host_index_entries(const GraphView &v, E *index, uint64_t index_slots)
 {
-	(void)c;
 	sdti::GraphExt *gx = ext_of(v);
-	E *d_index = nullptr;
-	HIPCHK(hipMalloc((void **)&d_index, index_slots * sizeof(E)));
-	hipError_t e = hipMemsetAsync(d_index, 0, index_slots * sizeof(E), v.stream);
-	int rc = SDT_OK;
-	if (e == hipSuccess) rc = gx->wide ? sdti::host_index(v, ix64_of(gx), d_index, index_slots - 1) : sdti::host_index(v, Ix32(), d_index, index_slots - 1);
-	if (e == hipSuccess && rc == SDT_OK) e = hipStreamSynchronize(v.stream);
-	if (e == hipSuccess && rc == SDT_OK) rc = sdti::d2h_big(v.copy_stream, index, d_index, index_slots * sizeof(E));      // (pageable destination of gigabytes: staged copies)
-	(void)hipFree(d_index);
-	if (e != hipSuccess)
-		return fail(SDT_EHIP, "building the host index: %s", hipGetErrorString(e));
-	return rc;
+	Scratch S;
+	E *d_index;
+	GCHK(S.alloc(&d_index, index_slots * sizeof(E)));
+	GCHK(hipMemsetAsync(d_index, 0, index_slots * sizeof(E), v.stream));
+	const int rc = gx->wide ? sdti::host_index(v, ix64_of(gx), d_index, index_slots - 1) : sdti::host_index(v, Ix32(), d_index, index_slots - 1);
+	if (rc != SDT_OK) return rc;
+	GCHK(hipStreamSynchronize(v.stream));
+	return sdti::d2h_big(v.copy_stream, index, d_index, index_slots * sizeof(E));      // (pageable destination of gigabytes: staged copies)
 }
 
 extern "C" {
@@ -895,28 +866,22 @@ int sdt_gpu_build_host_index(sdt_ctx *c, uint32_t *index, uint64_t index_slots)
 {
 	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
 	const GraphView v = sdti::graph_view(c);
-	if (!c || !index)
-		return fail(SDT_EINVAL, "NULL argument");
-	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
-		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
-	if (index_slots < 2 * (*v.idx_n) || (index_slots & (index_slots - 1)))
-		return fail(SDT_EINVAL, "index_slots must be a power of two >= 2 x nodes");
-	if ((*v.idx_n) >= 0xFFFFFFFEULL)
-		return fail(SDT_EINVAL, "%llu nodes do not fit 32-bit index entries", (unsigned long long)(*v.idx_n));
+	if (!index) return fail(SDT_EINVAL, "NULL argument");
+	if (!*v.d_idx || *v.idx_slots != v.slots) return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
+	if (index_slots < 2 * *v.idx_n || (index_slots & (index_slots - 1))) return fail(SDT_EINVAL, "index_slots must be a power of two >= 2 x nodes");
+	if (*v.idx_n >= 0xFFFFFFFEULL) return fail(SDT_EINVAL, "%llu nodes do not fit 32-bit index entries", (unsigned long long)*v.idx_n);
 	GRAPH_ENTER(v);
-	return host_index_entries<unsigned int>(c, v, index, index_slots);
+	return host_index_entries<unsigned int>(v, index, index_slots);
 }
 
 int sdt_gpu_build_host_index64(sdt_ctx *c, uint64_t *index, uint64_t index_slots)
 {
 	if (!c || !index) return fail(SDT_EINVAL, "NULL argument");
 	const GraphView v = sdti::graph_view(c);
-	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
-		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
-	if (index_slots < 2 * (*v.idx_n) || (index_slots & (index_slots - 1)))
-		return fail(SDT_EINVAL, "index_slots must be a power of two >= 2 x nodes");
+	if (!*v.d_idx || *v.idx_slots != v.slots) return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
+	if (index_slots < 2 * *v.idx_n || (index_slots & (index_slots - 1))) return fail(SDT_EINVAL, "index_slots must be a power of two >= 2 x nodes");
 	GRAPH_ENTER(v);
-	return host_index_entries<unsigned long long>(c, v, (unsigned long long *)index, index_slots);
+	return host_index_entries<unsigned long long>(v, (unsigned long long *)index, index_slots);
 }
 
 int sdt_gpu_set_graph_index_bits(sdt_ctx *c, int bits)
@@ -935,82 +900,5 @@ int sdt_gpu_graph_index_bits(const sdt_ctx *c)
 	if (*v.d_idx) return gx->wide ? 64 : 32;                  // (numbered: the form of that numbering; before: the one asked for)
 	return gx->want_bits == 64 ? 64 : 32;
 }
-
-int sdt_gpu_edge_ports(sdt_ctx *c, uint64_t *records, uint64_t max_records, uint64_t *n_records)
-{
-	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
-	const GraphView v = sdti::graph_view(c);
-	if (ext_of(v)->base) return fail(SDT_ESTATE, "%s reads host positions straight from the node index: no node base (SDT_NODE_BASE)", "sdt_gpu_edge_ports");
-	if (!c || (!records && max_records) || !n_records)
-		return fail(SDT_EINVAL, "NULL argument");
-	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
-		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
-	GRAPH_ENTER(v);
-	uint64_t *d_rec = nullptr;
-	unsigned long long *d_cur = nullptr, h = 0;
-	const uint64_t m = max_records ? max_records : 1;
-	HIPCHK(hipMalloc((void **)&d_rec, m * 17 * sizeof(uint64_t)));
-	hipError_t e = hipMalloc((void **)&d_cur, sizeof(unsigned long long));
-	if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, sizeof(unsigned long long), v.stream);
-	if (e == hipSuccess) {
-		const int g = sdti::scan_grid(v.cu_count, v.slots);
-		if (v.nw == 1) hipLaunchKernelGGL(k_edge_ports<1>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<1>(v), (*v.d_idx), v.K, (*v.idx_n) + 1, d_rec, (unsigned long long)max_records, d_cur, v.d_stats);
-		else if (v.nw == 2) hipLaunchKernelGGL(k_edge_ports<2>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<2>(v), (*v.d_idx), v.K, (*v.idx_n) + 1, d_rec, (unsigned long long)max_records, d_cur, v.d_stats);
-		else hipLaunchKernelGGL(k_edge_ports<4>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<4>(v), (*v.d_idx), v.K, (*v.idx_n) + 1, d_rec, (unsigned long long)max_records, d_cur, v.d_stats);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(&h, d_cur, sizeof h, hipMemcpyDeviceToHost, v.stream);
-	int rc = e == hipSuccess ? sdti::sync_stats(c) : fail(SDT_EHIP, "sdt_gpu_edge_ports: %s", hipGetErrorString(e));
-	if (rc != SDT_OK && e == hipSuccess)
-		rc = fail(SDT_ESTATE, "sdt_gpu_edge_ports: %llu chains leave the graph or never end", (unsigned long long)v.h_stats->probe_fail);
-	if (rc == SDT_OK) {
-		*n_records = h;
-		if (h > max_records) rc = fail(SDT_EFULL, "record array holds %llu, the graph has %llu non-linear nodes", (unsigned long long)max_records, h);
-		else if (h && hipMemcpy(records, d_rec, h * 17 * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SDT_EHIP, "edge port records: copy failed");
-	}
-	(void)hipFree(d_rec);
-	if (d_cur) (void)hipFree(d_cur);
-	return rc;
-}
-
-int sdt_gpu_tip_walks_compact(sdt_ctx *c, int thin, int cut_len, uint64_t *records, uint64_t max_records, uint64_t *n_records)
-{
-	if (!c) return fail(SDT_EINVAL, "ctx is NULL");
-	const GraphView v = sdti::graph_view(c);
-	if (ext_of(v)->base) return fail(SDT_ESTATE, "%s reads host positions straight from the node index: no node base (SDT_NODE_BASE)", "sdt_gpu_tip_walks_compact");
-	if (!c || (!records && max_records) || !n_records)
-		return fail(SDT_EINVAL, "NULL argument");
-	if (!(*v.d_idx) || (*v.idx_slots) != v.slots)
-		return fail(SDT_ESTATE, "call sdt_gpu_set_node_index first");
-	if ((*v.idx_n) >= (1ULL << 56))
-		return fail(SDT_EINVAL, "node indices do not fit 56 bits");
-	GRAPH_ENTER(v);
-	uint64_t *d_rec = nullptr;
-	unsigned long long *d_cur = nullptr, h = 0;
-	const uint64_t m = max_records ? max_records : 1;
-	HIPCHK(hipMalloc((void **)&d_rec, m * 2 * sizeof(uint64_t)));
-	hipError_t e = hipMalloc((void **)&d_cur, sizeof(unsigned long long));
-	if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, sizeof(unsigned long long), v.stream);
-	if (e == hipSuccess) {
-		const int g = sdti::scan_grid(v.cu_count, v.slots);
-		if (v.nw == 1) hipLaunchKernelGGL(k_tip_walks<1>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<1>(v), (*v.d_idx), v.K, thin, cut_len, (uint64_t *)nullptr, (uint8_t *)nullptr, v.d_stats, d_rec, (unsigned long long)max_records, d_cur, 2);
-		else if (v.nw == 2) hipLaunchKernelGGL(k_tip_walks<2>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<2>(v), (*v.d_idx), v.K, thin, cut_len, (uint64_t *)nullptr, (uint8_t *)nullptr, v.d_stats, d_rec, (unsigned long long)max_records, d_cur, 2);
-		else hipLaunchKernelGGL(k_tip_walks<4>, dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<4>(v), (*v.d_idx), v.K, thin, cut_len, (uint64_t *)nullptr, (uint8_t *)nullptr, v.d_stats, d_rec, (unsigned long long)max_records, d_cur, 2);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(&h, d_cur, sizeof h, hipMemcpyDeviceToHost, v.stream);
-	int rc = e == hipSuccess ? sdti::sync_stats(c) : fail(SDT_EHIP, "sdt_gpu_tip_walks_compact: %s", hipGetErrorString(e));
-	if (rc != SDT_OK && e == hipSuccess)
-		rc = fail(SDT_ESTATE, "sdt_gpu_tip_walks_compact: %llu walks left the graph", (unsigned long long)v.h_stats->probe_fail);
-	if (rc == SDT_OK) {
-		*n_records = h;
-		if (h > max_records) rc = fail(SDT_EFULL, "record array holds %llu, %llu nodes have a walk", (unsigned long long)max_records, h);
-		else if (h && hipMemcpy(records, d_rec, h * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SDT_EHIP, "tip walk records: copy failed");
-	}
-	(void)hipFree(d_rec);
-	if (d_cur) (void)hipFree(d_cur);
-	return rc;
-}
-
 
 }  // extern "C"

@@ -1,6 +1,7 @@
-// sdt_graph_phases.hpp -- what the two translation units of the graph phases share (sdt_gpu_graph.hip: the ABI entry points and
-// the Ix32 form, sdt_gpu_graph64.hip: the Ix64 form): the unit's state, its device-buffer helpers, and the phases whose node
-// indices take one of the two forms of sdt_graph_kernels.cuh as a template parameter.
+// sdt_graph_phases.hpp -- what the two translation units of the graph phases share (sdt_gpu_graph.hip: the ABI entry points, the
+// host side of the layout and the Ix32 form, sdt_gpu_graph64.hip: the Ix64 form): the unit's state, the idiom of its host code
+// (LAUNCH_NW*: dispatch by key width, Scratch: the device buffers of a call, GCHK: HIP errors, CallTimer: the SDT_TIMING lines),
+// and the phases whose node indices take one of the two forms of sdt_graph_kernels.cuh as a template parameter.
 #pragma once
 #include <stdio.h>
 #include <stdlib.h>
@@ -70,6 +71,25 @@ static sdti::GraphExt *ext_of(const GraphView &v)
 		else if ((v).nw == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<2, IXT>), dim3(grid), dim3(TPB), 0, (v).stream, sdti::table_of<2>(v), __VA_ARGS__); \
 		else hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<4, IXT>), dim3(grid), dim3(TPB), 0, (v).stream, sdti::table_of<4>(v), __VA_ARGS__);                  \
 	} while (0)
+
+// the same for the kernels that are templates over the key words but take no table (the layout replay's k_rp_rehash_init, k_rp_home)
+#define LAUNCH_NW_NOTAB(v, kernel, grid, ...)                                                                                \
+	do {                                                                                                                     \
+		if ((v).nw == 1) hipLaunchKernelGGL(kernel<1>, dim3(grid), dim3(TPB), 0, (v).stream, __VA_ARGS__);                   \
+		else if ((v).nw == 2) hipLaunchKernelGGL(kernel<2>, dim3(grid), dim3(TPB), 0, (v).stream, __VA_ARGS__);              \
+		else hipLaunchKernelGGL(kernel<4>, dim3(grid), dim3(TPB), 0, (v).stream, __VA_ARGS__);                               \
+	} while (0)
+
+// SDT_TIMING: where the time of a call goes, on stderr (tools/e2e_pregraph.py collects the "[device]" lines).  One per call; without
+// SDT_TIMING no clock is read
+struct CallTimer {
+	const bool on;
+	const double t0;
+	explicit CallTimer(bool wanted = true) : on(wanted && sdt_env("SDT_TIMING") != nullptr), t0(on ? now() : 0) {}
+	static double now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
+	double ms() const { return on ? now() - t0 : 0; }          // since the call began
+	void tick(const char *what) const { if (on) fprintf(stderr, "[device]       %s at %.1f ms\n", what, ms()); }
+};
 
 // every device buffer of a call in one place: freed when the call returns, whatever the path
 struct Scratch {
@@ -394,16 +414,8 @@ int minor_out_commit_begin(sdt_ctx *c, IX ix, double threshold, uint64_t max_com
 	sdti::GraphExt *gx = ext_of(v);
 	const uint64_t nn = gx->n_nodes, nj = gx->result_labelled, nr = gx->result_words / 14;
 	*largest = *n_skipped = *n_skipped_records = 0;
-	const bool timing = sdt_env("SDT_TIMING") != nullptr;
-	struct timespec ts0_; clock_gettime(CLOCK_MONOTONIC, &ts0_);
-	const double t_call = ts0_.tv_sec * 1e3 + ts0_.tv_nsec * 1e-6;
-	auto tick = [&](const char *what) {              // (SDT_TIMING: where the call's time goes, on stderr; waits for the stream)
-		if (!timing) return;
-		(void)hipStreamSynchronize(v.stream);
-		struct timespec t_;
-		clock_gettime(CLOCK_MONOTONIC, &t_);
-		fprintf(stderr, "[device]       commit: %s at %.1f ms\n", what, t_.tv_sec * 1e3 + t_.tv_nsec * 1e-6 - t_call);
-	};
+	const CallTimer T;
+	auto tick = [&](const char *what) { if (T.on) { (void)hipStreamSynchronize(v.stream); T.tick(what); } };      // (waits for the stream)
 	if (gx->mo_pending) { (void)hipStreamSynchronize(v.stream); mo_pending_free(gx); }
 	if (gx->d_wnode) { (void)hipFree(gx->d_wnode); gx->d_wnode = nullptr; }
 	if (gx->d_wl) { (void)hipFree(gx->d_wl); gx->d_wl = nullptr; }
@@ -418,7 +430,7 @@ int minor_out_commit_begin(sdt_ctx *c, IX ix, double threshold, uint64_t max_com
 	GCHK(hipMemsetAsync(d_cnt, 0, 5 * 8, v.stream));
 	GCHK(S.alloc(&recidx, (nn + 1) * 4)); GCHK(S.alloc(&dirty, nn + 1));
 	GCHK(hipMemsetAsync(dirty, 0, nn + 1, v.stream));
-	tick("buffers");
+	tick("commit: buffers");
 	if (!nj) {                                                   // nothing to visit: _finish reports zeros
 		GCHK(S.alloc(&cstart, 8));
 		gx->mo_dirty = (uint8_t *)S.release(dirty); gx->mo_cnt = (unsigned long long *)S.release(d_cnt);
@@ -453,7 +465,7 @@ int minor_out_commit_begin(sdt_ctx *c, IX ix, double threshold, uint64_t max_com
 	GCHK(hipGetLastError());
 	GCHK(hipStreamSynchronize(v.stream));
 	*largest = h_largest;
-	tick("components + record index");
+	tick("commit: components + record index");
 	if (h_largest > max_component) {
 		// the records of the components that are left alone: their junction records in order, then the records of the neighbours
 		// they may cut (the host's commit finds the neighbours of a cut node there instead of looking them up)
@@ -486,7 +498,7 @@ int minor_out_commit_begin(sdt_ctx *c, IX ix, double threshold, uint64_t max_com
 		gx->n_skipped = (uint64_t)nsk + nsk2;
 		*n_skipped = nsk;
 		*n_skipped_records = (uint64_t)nsk + nsk2;
-		tick("long components gathered");
+		tick("commit: long components gathered");
 	}
 	}
 	// the visits and the re-marking: launched, not waited for
@@ -611,10 +623,7 @@ int layout_number(const GraphView &v, IX ix, const uint64_t *sval, const uint64_
 template <class IX>
 int set_index(const GraphView &v, IX ix, const uint64_t *d_keys, uint64_t n)
 {
-	const int g = sdti::scan_grid(v.cu_count, n ? n : 1);
-	if (v.nw == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_set_index<1, IX>), dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<1>(v), d_keys, n, *v.d_idx, v.d_stats, ix);
-	else if (v.nw == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_set_index<2, IX>), dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<2>(v), d_keys, n, *v.d_idx, v.d_stats, ix);
-	else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_set_index<4, IX>), dim3(g), dim3(TPB), 0, v.stream, sdti::table_of<4>(v), d_keys, n, *v.d_idx, v.d_stats, ix);
+	LAUNCH_NW_IX(v, k_set_index, IX, sdti::scan_grid(v.cu_count, n ? n : 1), d_keys, n, *v.d_idx, v.d_stats, ix);
 	GCHK(hipGetLastError());
 	return SDT_OK;
 }
