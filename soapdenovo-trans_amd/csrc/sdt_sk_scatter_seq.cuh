@@ -8,6 +8,7 @@
 #include "sdt_table.cuh"
 #include "sdt_superkmer.cuh"
 #include "sdt_clear_plan.h"
+#include "sdt_sk_walk.h"
 
 using namespace sdt;
 
@@ -293,9 +294,9 @@ template <int NW, bool C1> __device__ inline void sk_store_record1(uint64_t *rec
 	}
 }
 
-// cut run [j0, j0 + n) of a read out of the tile and append the record to its level-1 bucket
+// cut run [j0, j0 + n) of a read out of the tile and append the record to its level-1 bucket (last: the tile's last readable word)
 template <int NW, bool C1 = false>
-__device__ inline void sk_emit_run(const uint32_t *words, int rb_r, int len_r, int nk_r, int K, uint64_t read_ord, int j0, int n,
+__device__ inline void sk_emit_run(const uint32_t *words, int last, int rb_r, int len_r, int nk_r, int K, uint64_t read_ord, int j0, int n,
                                    uint32_t fb, unsigned long long *s_cur, unsigned long long *s_blk, const SkPool &pool,
                                    uint32_t *s_cnt, const Table<NW> &tbl, uint32_t &claimed, uint32_t &failed, uint32_t &done,
                                    uint32_t &emitted, const SkFuse &fz, uint32_t &emis, uint32_t &cutv)
@@ -322,17 +323,11 @@ __device__ inline void sk_emit_run(const uint32_t *words, int rb_r, int len_r, i
 		const int len = hp + n + K - 1 + hn, ps = rb_r + j0 - hp;
 		uint64_t rec[RW];
 		rec[0] = C1 ? sk_rec1c_hdr(l2, n, hp, hn, SK_L2BITS) : sk_header(read_ord, (uint32_t)j0, l2, n, hp, hn);
+		uint64_t bases[BW];
+		sk_cut_bases<BW, TAIL_PAD>(words, ps, len, last, bases);     // (sdt_sk_walk.h: every word of the tile read once)
 #pragma unroll
-		for (int k = 0; k < BW; k++) {
-			uint64_t wv = 0;
-			if (32 * k < len) {
-				wv = sk_stream_word(words, ps + 32 * k);
-				const int keep = len - 32 * k;
-				if (keep < 32)
-					wv &= ~0ULL << (64 - 2 * keep);
-			}
-			rec[1 + k] = wv;
-		}
+		for (int k = 0; k < BW; k++)
+			rec[1 + k] = bases[k];
 		sk_store_record1<NW, C1>(pool.recs, chunk, pos, rec);
 		emitted += (uint32_t)n;
 		emis++;
@@ -388,8 +383,7 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 	if (tid == 0 && !replay)
 		s_blk = g_blk[blockIdx.x];
 	const uint64_t ntiles = (nreads + TR - 1) / TR;
-	const uint32_t mmask = (1u << (2 * m)) - 1u;
-	const int topsh = 2 * (m - 1);
+	const int mshift = 32 - 2 * m;
 	uint32_t claimed = 0, failed = 0, done = 0, emitted = 0;
 #ifdef SDT_SK_TICKS
 	unsigned long long cyc[4] = {0, 0, 0, 0}, t0 = wall_clock64(), t1;
@@ -404,6 +398,7 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 		int nwords = (int)(((offs[r0 + nr] + 15) >> 4) - word0) + TAIL_PAD;
 		if (nwords > max_tile_words)
 			nwords = max_tile_words;                     // cannot happen when max_read_len was honoured
+		const int last = nwords - 1;                     // the tile's last readable word
 		// (replay only; loaded in front of the tile's loads so that THEIR wait covers it: behind the clear it would put a wait on the stores)
 		uint32_t emis = 0, cutv = replay && tid < nr ? (uint32_t)fz.redo.cut[r0 + tid] : SK_CUT_NONE;
 		s_rb[tid] = (uint32_t)(offs[r0 + (tid < nr ? tid : nr)] - (word0 << 4));
@@ -425,17 +420,22 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 		uint32_t *runs = s_runs + tid * SK_SEQ_RUNCAP;
 		int nrun = 0;
 		if (nk_r > 0) {
-			const int nhv = len_r - m + 1;               // m-mers of the read; window j covers m-mers [j, j + W)
-			// rolling canonical m-mer: fw holds the last m - 1 bases, rc their reverse complement one base up
-			uint32_t fw = sk_stream_mmer(words, rb_r, m) >> 2;
-			uint32_t rc = (sk_rev2bit32(fw ^ 0xAAAAAAAAu) >> (32 - 2 * (m - 1))) << 2;
-			int pb = rb_r + m - 1;                       // stream index of the next base to enter
+			// rolling canonical m-mer over a register window of the read's bases (sdt_sk_walk.h): no LDS read and no wait in a step.
+			// p counts the steps of ALL lanes alike, so the refill test is scalar; a lane steps on past its read's last m-mer (the
+			// refill clamps its word index).  What it hashes there reaches no window it emits: window j < nk_r covers the m-mers
+			// [j, j + W), and j + W - 1 <= nk_r - 1 + W - 1 = len_r - m is the read's last one.
+			SkRoll roll;
+			sk_roll_init(roll, sk_stream_mmer(words, rb_r, m) >> 2);
+			SkBaseWin win;
+			sk_win_init(win, words, rb_r + m - 1, last);
+			int p = 0;                                   // m-mers hashed so far
 			auto next_hv = [&]() -> uint32_t {
-				const uint32_t b = (words[pb >> 4] >> (30 - 2 * (pb & 15))) & 3u;
-				pb++;
-				fw = ((fw << 2) | b) & mmask;
-				rc = (rc >> 2) | ((b ^ 2u) << topsh);
-				return sk_mmer_hash(fw < rc ? fw : rc);
+				if ((p & (SK_WIN_BASES - 1)) == 0)
+					sk_win_refill(win, words, last);
+				p++;
+				const uint32_t canon = sk_roll_step(roll, win.cur, mshift);
+				sk_win_take(win);
+				return sk_mmer_hash(canon);
 			};
 			int j0 = 0;
 			uint32_t fb0 = 0, pfb = 0;
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 					if (nrun < SK_SEQ_RUNCAP)
 						runs[nrun] = (fb0 << 6) | (uint32_t)(j - j0 - 1);
 					else
-						sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, j0, j - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted, fz, emis, cutv);
+						sk_emit_run<NW, C1>(words, last, rb_r, len_r, nk_r, K, read_ord, j0, j - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted, fz, emis, cutv);
 					nrun++;
 					j0 = j;
 					fb0 = fb;
@@ -459,25 +459,22 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 			uint32_t h[W], nh[W];
 #pragma clang loop unroll(full)
 			for (int i = 0; i < W; i++)
-				h[i] = next_hv();                        // nhv >= W: the read has at least one k-mer
+				h[i] = next_hv();                        // the read has at least one k-mer: W m-mers
 #pragma clang loop unroll(full)
 			for (int i = W - 2; i >= 0; i--)
 				h[i] = h[i] < h[i + 1] ? h[i] : h[i + 1];
-			int p = W;                                   // next m-mer position
 			for (int jb = 0; jb < nk_r; jb += W) {
 				window(jb, h[0]);
 				uint32_t pre = 0xFFFFFFFFu;
 #pragma clang loop unroll(full)
 				for (int i = 1; i < W; i++) {
-					const uint32_t x = p < nhv ? next_hv() : 0xFFFFFFFFu;
-					p++;
+					const uint32_t x = next_hv();
 					nh[i - 1] = x;
 					pre = x < pre ? x : pre;
 					if (jb + i < nk_r)
 						window(jb + i, h[i] < pre ? h[i] : pre);
 				}
-				nh[W - 1] = p < nhv ? next_hv() : 0xFFFFFFFFu;
-				p++;
+				nh[W - 1] = next_hv();
 				h[W - 1] = nh[W - 1];
 #pragma clang loop unroll(full)
 				for (int i = W - 2; i >= 0; i--)
@@ -487,7 +484,7 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 			if (nrun < SK_SEQ_RUNCAP)
 				runs[nrun] = (fb0 << 6) | (uint32_t)(nk_r - j0 - 1);
 			else
-				sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, j0, nk_r - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted, fz, emis, cutv);
+				sk_emit_run<NW, C1>(words, last, rb_r, len_r, nk_r, K, read_ord, j0, nk_r - j0, fb0, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted, fz, emis, cutv);
 			nrun++;
 		}
 		SK_TICK(1);
@@ -495,7 +492,7 @@ __global__ __launch_bounds__(SK_SEQ_TILE, NW == 1 ? 4 : 2) void k_sk_scatter_rea
 		for (int k = 0, jr = 0; k < nlist; k++) {        // (the listed runs are the read's first ones, back to back from k-mer 0)
 			const uint32_t e = runs[k];
 			const int nr = (int)(e & 63u) + 1;
-			sk_emit_run<NW, C1>(words, rb_r, len_r, nk_r, K, read_ord, jr, nr, e >> 6, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted, fz, emis, cutv);
+			sk_emit_run<NW, C1>(words, last, rb_r, len_r, nk_r, K, read_ord, jr, nr, e >> 6, s_cur, &s_blk, pool, s_cnt, tbl, claimed, failed, done, emitted, fz, emis, cutv);
 			jr += nr;
 		}
 		if (fz.mode == SK_FUSE_FUSED && tid < nr)
