@@ -1156,7 +1156,66 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  *                       capacity / 192 + 1 chunks and one per wavefront of the grid -- 8 B per chunk, and the dense copy of what
  *                       was written
  * Out of scope: more than two tables; tables of different K; sharded contexts (refused); sketches; statistics on the counts;
- * scaling by library size (the matrix is raw); a read filter by the selection; a device-pointer form of the selection. */
+ * scaling by library size (the matrix is raw); a read filter by the selection; a device-pointer form of the selection.
+ *
+ * Reads clustered by connected component of the counted k-mer graph.  Every node of the table carries eight link counters, four
+ * to the left and four to the right: the table is a de Bruijn graph, and its connected components split the read set into the
+ * groups that can be assembled, normalised or inspected on their own (what Trinity's Chrysalis and khmer's partition-graph /
+ * annotate-partitions give).  Needs the counted table, and writes nothing to it, to the kept reads or to any cache of the context.
+ * Added without a change of SDT_ABI_VERSION: the seven calls, the three structs and the constant are additions.
+ *     Integers only.  Everything is exact and does not depend on the table's size or layout, on the order in which pass 1 placed
+ *     colliding keys, on the pass-1 kernel family, or on the launch geometry.
+ *     PARAMETERS (sdt_cluster_params): flags must be 0; min_link 1 .. 63; max_count 0 (no upper bound) or >= max(min_count, 1).
+ *     LIVE NODES.  A node is live iff it exists and its deleted flag is clear, its 32-bit count (the one profile_reads sees, with
+ *     the high half) is >= max(min_count, 1), and max_count is 0 or the count is <= max_count.
+ *     EDGES.  For a live node u, a side (0 left, 1 right) and a base b, the link counter is bits 24 * side + 6 * b of the node's
+ *     link word (l_links | r_links << 24, as export_nodes gives them).  If it is >= min_link: the neighbour word is u's k-mer
+ *     shifted right by one base with b in front (left), or shifted left with b behind (right); its canonical strand is looked up;
+ *     if that node v exists and is live, {u, v} is an edge.  One qualifying end is enough; a neighbour that is missing or not live
+ *     gives no edge; u = v is allowed and joins nothing.
+ *     CLUSTERS are the connected components of the live nodes under these edges, numbered 0 .. C - 1 in ascending order of their
+ *     smallest canonical k-mer (numeric on the key words, most significant first).  SDT_CLUSTER_NONE = no cluster.
+ *     READS.  A read of len bases has n = len - K + 1 k-mers (0 for len < K); a k-mer is live iff its canonical node is.  RECORD,
+ *     per read (sdt_read_cluster, 24 bytes):
+ *         kmers  n            live   its live k-mers
+ *         cluster  the id of its first live k-mer, or SDT_CLUSTER_NONE
+ *         split    its live k-mers that lie in another cluster than that one
+ *         unit     a unit is one read or, with paired, reads 2t and 2t + 1: mate 1's cluster unless that is NONE, else mate 2's
+ *         verdict  the first that applies: 4 every read of the unit has n == 0 (short); 3 no read of the unit has a live k-mer
+ *                  (unassigned); 2 this read has no live k-mer, its mate has (assigned through the mate); 1 split > 0 or
+ *                  cluster != unit (assigned, not whole); 0 assigned and whole
+ *     keep[i] = 1 iff pick_lo <= unit <= pick_hi and unit is not SDT_CLUSTER_NONE.
+ *   cluster_begin:      builds the clustering and waits.  info[8]: [0] live nodes  [1] link ends: the triples (u, side, b) that
+ *                       qualified and found a live neighbour  [2] clusters  [3] nodes of the largest cluster  [4] its id (the
+ *                       smallest among equals; 0 without a cluster)  [5] nodes that exist and are not live  [6], [7] 0.  info may be
+ *                       NULL.  A second begin replaces the first.  A table of 2^32 - 1 slots or more is SDT_EINVAL ("the labels
+ *                       are 32-bit"): a 64-bit form does not exist yet.
+ *   cluster_components: per cluster in id order its smallest k-mer (sdt_gpu_key_words words, most significant first) and
+ *                       sdt_cluster_comp { count_sum: the sum of its nodes' counts; nodes }.  Either array may be NULL; *n = C
+ *                       always; SDT_EFULL when C > capacity, with the first capacity written.
+ *   cluster_lookup:     the cluster of n k-mers, keys as for search_kmers, either strand; absent or not live: SDT_CLUSTER_NONE.
+ *   cluster_reads:      a host batch, staged in pieces (a piece never splits a pair); rec nreads records, keep nreads bytes or
+ *                       NULL; *n_kept = reads with keep 1.  Waits.
+ *   cluster_reads_device: buffers already on the device; d_keep may be NULL.  Asynchronous on the context's stream when n_kept is
+ *                       NULL; with n_kept it waits for the count.
+ *   cluster_kept_reads: the reads kept in HBM, records by read ordinal as for select_kept_reads: pair_ranges as there, a pair with
+ *                       only one mate kept is judged on that mate alone, records of ordinals that no kept read has are untouched,
+ *                       SDT_EFULL (nothing written) when a kept read's ordinal is >= out_capacity.  *nreads = the kept reads seen.
+ *   cluster_end:        frees the labels (sdt_gpu_destroy does too).  Without a begin: SDT_OK.
+ * There is NO limit on the length of a read: a wavefront walks a unit 64 k-mer positions at a time and keeps no strip of it.
+ * nreads == 0 (n == 0 for lookup): SDT_OK, nothing touched, whatever the rest says.
+ * SDT_ESTATE: cluster_begin under the state rules of search_kmers, with its messages (a SDT_FLAG_CONTIG_INDEX context, a shard or any
+ * context with a communicator, after load_paths / import_paths, a released table, batches pushed and not drained); every other call
+ * without a begin, after cluster_end, and once the table has changed since cluster_begin (counted into, grown, reset, delow,
+ * imported, released, any call of the graph phases): "the table changed since sdt_gpu_cluster_begin" -- labels are by slot and never read against another table.
+ * SDT_EINVAL, before any launch: NULL params; flags not 0; min_link outside 1 .. 63; max_count below max(min_count, 1) and not 0;
+ * a table of 2^32 - 1 slots or more; an odd nreads with paired; offsets not monotonic or nwords too short (as for reads); a read of
+ * 2^32 bases or more (host form); pair ranges as for select_kept_reads.
+ * Device memory: from cluster_begin to cluster_end 4 B per table slot; during cluster_begin 4 B per slot more and, per cluster,
+ * 8 B x (key words + 2) + 8 B and the sort's scratch; SDT_ENOMEM with nothing left allocated when that does not fit.  The forms
+ * over reads hold what select_reads holds, with records of 24 B.
+ * Out of scope: tables of 2^32 - 1 slots and more; sharded contexts; joining clusters through mate pairs; removing knots beyond
+ * what max_count does. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -1198,6 +1257,10 @@ typedef struct { uint32_t min_count, rows, flags, reserved; } sdt_asm_params;   
 #define SDT_CMP_MAX_CELLS 16384 /* rows * cols: the matrix of a workgroup is 32-bit counters in 64 KiB of LDS */
 typedef struct { uint32_t rows, cols, flags, reserved; } sdt_cmp_params;   /* rows, cols >= 2; flags, reserved: 0 */
 typedef struct { uint32_t min_a, max_a, min_b, max_b; } sdt_cmp_range;
+#define SDT_CLUSTER_NONE 0xFFFFFFFFu /* sdt_read_cluster.cluster / unit, cluster_lookup: no cluster */
+typedef struct { uint32_t min_count, max_count, min_link, flags; } sdt_cluster_params;   /* flags: 0 */
+typedef struct { uint64_t count_sum; uint32_t nodes, reserved; } sdt_cluster_comp;   /* 16 bytes */
+typedef struct { uint32_t kmers, live, split, cluster, unit, verdict; } sdt_read_cluster;   /* 24 bytes */
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -1326,6 +1389,18 @@ int sdt_gpu_asm_end(sdt_ctx *ctx);
 int sdt_gpu_compare_tables(sdt_ctx *a, sdt_ctx *b, const sdt_cmp_params *params, uint64_t *matrix, uint64_t totals[8]);
 int sdt_gpu_compare_select(sdt_ctx *a, sdt_ctx *b, const sdt_cmp_range *range, uint64_t *keys, uint32_t *count_a,
                            uint32_t *count_b, uint64_t capacity, uint64_t *n);
+int sdt_gpu_cluster_begin(sdt_ctx *ctx, const sdt_cluster_params *params, uint64_t info[8]);
+int sdt_gpu_cluster_components(sdt_ctx *ctx, uint64_t *keys, sdt_cluster_comp *out, uint64_t capacity, uint64_t *n);
+int sdt_gpu_cluster_lookup(sdt_ctx *ctx, const uint64_t *keys, uint64_t n, uint32_t *cluster);
+int sdt_gpu_cluster_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                          uint64_t nreads, int paired, uint32_t pick_lo, uint32_t pick_hi, sdt_read_cluster *rec,
+                          uint8_t *keep, uint64_t *n_kept);
+int sdt_gpu_cluster_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                                 int paired, uint32_t pick_lo, uint32_t pick_hi, void *d_rec, void *d_keep, uint64_t *n_kept);
+int sdt_gpu_cluster_kept_reads(sdt_ctx *ctx, const uint64_t *pair_ranges, uint64_t n_ranges, uint32_t pick_lo,
+                               uint32_t pick_hi, sdt_read_cluster *rec, uint64_t out_capacity, uint64_t *nreads,
+                               uint64_t *n_kept);
+int sdt_gpu_cluster_end(sdt_ctx *ctx);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

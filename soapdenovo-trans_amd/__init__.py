@@ -213,6 +213,16 @@ _ABI = [
     ("sdt_gpu_asm_end", _c.c_int, [_c.c_void_p]),
     ("sdt_gpu_compare_tables", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     ("sdt_gpu_compare_select", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
+    ("sdt_gpu_cluster_begin", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_cluster_components", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_cluster_lookup", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
+    ("sdt_gpu_cluster_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_uint32, _c.c_uint32,
+                                         _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_cluster_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int, _c.c_uint32, _c.c_uint32,
+                                                _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_cluster_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_uint64,
+                                              _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_cluster_end", _c.c_int, [_c.c_void_p]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -272,6 +282,12 @@ QC_QUALS, QC_GC_BINS, QC_TOTALS = 94, 101, 8
 SEQ_SUPPORT_DTYPE = np.dtype([("sum", np.uint64)] + [(f, np.uint32) for f in ("kmers", "found", "solid", "gaps", "longest_gap", "longest_at")])
 ASM_CN_COLS, ASM_MAX_ROWS = 8, 1024                      # SDT_ASM_CN_COLS, SDT_ASM_MAX_ROWS
 CMP_MAX_CELLS = 16384                                    # SDT_CMP_MAX_CELLS
+# sdt_read_cluster (include/sdt_gpu.h): one record per read of a clustering; cluster = the id of its first live k-mer, split = its live
+# k-mers in another cluster, unit = the cluster of its unit (a read or a pair); sdt_cluster_comp: one record of 16 bytes per cluster
+READ_CLUSTER_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "live", "split", "cluster", "unit", "verdict")])
+CLUSTER_COMP_DTYPE = np.dtype([("count_sum", np.uint64), ("nodes", np.uint32), ("reserved", np.uint32)])
+CLUSTER_NONE = 0xFFFFFFFF                                # SDT_CLUSTER_NONE
+CLUSTER_WHOLE, CLUSTER_NOT_WHOLE, CLUSTER_THROUGH_MATE, CLUSTER_UNASSIGNED, CLUSTER_SHORT = range(5)
 
 
 class NormParams(_c.Structure):
@@ -357,6 +373,14 @@ class CmpParams(_c.Structure):
 
     def __init__(self, rows=64, cols=64, flags=0, reserved=0):
         super().__init__(rows, cols, flags, reserved)
+
+
+class ClusterParams(_c.Structure):
+    """sdt_cluster_params; the defaults of `sdt-kmers cluster`"""
+    _fields_ = [(f, _c.c_uint32) for f in ("min_count", "max_count", "min_link", "flags")]
+
+    def __init__(self, min_count=2, max_count=0, min_link=1, flags=0):
+        super().__init__(min_count, max_count, min_link, flags)
 
 
 class CmpRange(_c.Structure):
@@ -1280,6 +1304,83 @@ class PregraphGPU:
 
     def asm_end(self):
         self._check(self.lib.sdt_gpu_asm_end(self._ctx))
+
+    # -- reads clustered by connected component of the counted k-mer graph (the rule: include/sdt_gpu.h).  Nothing is written to the
+    # table; the labels (4 bytes per table slot) live from cluster_begin to cluster_end
+    def cluster_begin(self, params=None):
+        """params: ClusterParams or its fields as a dict -> info uint64[8]: live nodes, link ends, clusters, nodes of the largest
+        cluster, its id, nodes that are not live, 0, 0"""
+        prm = params if isinstance(params, ClusterParams) else ClusterParams(**(params or {}))
+        info = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_cluster_begin(self._ctx, ctypes.addressof(prm), _ptr(info)))
+        return info
+
+    def cluster_components(self, capacity: int = None):
+        """-> (keys uint64[C, key_words]: the smallest k-mer of every cluster, in id order; CLUSTER_COMP_DTYPE[C]: count_sum, nodes);
+        capacity: the room to offer (SdtError SDT_EFULL when it is too small: e.needed says how many clusters there are)"""
+        n = ctypes.c_uint64()
+        if capacity is None:
+            rc = self.lib.sdt_gpu_cluster_components(self._ctx, None, None, 0, ctypes.byref(n))
+            if rc != SDT_OK and rc != SDT_EFULL:
+                self._check(rc)
+            capacity = n.value
+        nw = self.nw
+        keys = np.zeros((max(capacity, 1), nw), dtype=np.uint64)
+        comp = np.zeros(max(capacity, 1), dtype=CLUSTER_COMP_DTYPE)
+        rc = self.lib.sdt_gpu_cluster_components(self._ctx, _ptr(keys), _ptr(comp), capacity, ctypes.byref(n))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.needed = n.value
+            raise e
+        return keys[: n.value], comp[: n.value]
+
+    def cluster_lookup(self, keys):
+        """keys: uint64[n, key_words] (or [n] for one word), either strand -> uint32[n]: the cluster, CLUSTER_NONE for an absent or
+        not live k-mer"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        nw = self.nw
+        assert keys.size % nw == 0
+        n = keys.size // nw
+        out = np.full(n, 0xABABABAB, dtype=np.uint32)
+        self._check(self.lib.sdt_gpu_cluster_lookup(self._ctx, _ptr(keys) if n else None, n, _ptr(out) if n else None))
+        return out
+
+    def cluster_reads(self, words, offsets, paired: bool = False, pick_lo: int = 0, pick_hi: int = 0xFFFFFFFE):
+        """-> (READ_CLUSTER_DTYPE[nreads]; keep uint8[nreads]: pick_lo <= unit <= pick_hi; reads kept)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        rec = np.zeros(n, dtype=READ_CLUSTER_DTYPE)
+        keep = np.zeros(n, dtype=np.uint8)
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_cluster_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, int(bool(paired)), pick_lo, pick_hi,
+                                                   _ptr(rec), _ptr(keep), ctypes.byref(kept)))
+        return rec, keep, kept.value
+
+    def cluster_reads_device(self, d_words, d_offsets, nreads: int, d_rec, d_keep=None, paired: bool = False, pick_lo: int = 0,
+                             pick_hi: int = 0xFFFFFFFE, wait: bool = True):
+        """device buffers; d_rec holds nreads records of 24 bytes, d_keep (optional) nreads bytes -> reads kept (waits for the kernel),
+        or None with wait=False (enqueued on the context's stream)"""
+        kept = ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_cluster_reads_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, int(bool(paired)), pick_lo, pick_hi,
+                                                          _ptr(d_rec), _ptr(d_keep), ctypes.byref(kept) if wait else None))
+        return kept.value if wait else None
+
+    def cluster_kept_reads(self, total_reads: int, pair_ranges=(), pick_lo: int = 0, pick_hi: int = 0xFFFFFFFE, out: np.ndarray = None):
+        """the reads kept in HBM; pair_ranges as for select_kept_reads
+        -> (READ_CLUSTER_DTYPE[total_reads] by read ordinal, reads seen, reads kept)"""
+        if out is None:
+            out = np.zeros(total_reads, dtype=READ_CLUSTER_DTYPE)
+        assert out.dtype == READ_CLUSTER_DTYPE and out.flags.c_contiguous and len(out) >= total_reads
+        ranges = np.ascontiguousarray(np.asarray(pair_ranges, dtype=np.uint64).reshape(-1))
+        assert ranges.size % 2 == 0
+        n, kept = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.sdt_gpu_cluster_kept_reads(self._ctx, _ptr(ranges) if ranges.size else None, ranges.size // 2, pick_lo, pick_hi,
+                                                        _ptr(out), total_reads, ctypes.byref(n), ctypes.byref(kept)))
+        return out, n.value, kept.value
+
+    def cluster_end(self):
+        self._check(self.lib.sdt_gpu_cluster_end(self._ctx))
 
     # -- this context's counted table against another's (the rule: include/sdt_gpu.h); nothing is written to either
     def compare(self, other, rows: int = 64, cols: int = 64):

@@ -59,9 +59,14 @@ int sdt_pair_ranges_holds(const sdt_pair_ranges *pr, uint64_t ord, size_t *curso
 
 char *sdt_put_fasta_record(char *p, uint64_t ord, const uint32_t *words, uint64_t start, uint64_t len)
 {
-	static const char letters[4] = {'A', 'C', 'T', 'G'};
 	*p++ = '>';
 	p = sdt_put_dec(p, ord + 1, '\n');
+	return sdt_put_fasta_bases(p, words, start, len);
+}
+
+char *sdt_put_fasta_bases(char *p, const uint32_t *words, uint64_t start, uint64_t len)
+{
+	static const char letters[4] = {'A', 'C', 'T', 'G'};
 	/* base by base up to a word boundary, then whole words without a branch per base, then the rest.  (The bases are most of what the
 	 * read stages' host side does; how fast a loop of one base per round ran depended on where the linker had put it.) */
 	uint64_t g = start;

@@ -25,5 +25,7 @@ int sdt_pair_ranges_holds(const sdt_pair_ranges *pr, uint64_t ord, size_t *curso
 /* ">ordinal + 1\n" and the len bases from base `start` of a 2-bit stream as letters on one line; returns the end of what it wrote
  * (at most len + 23 bytes) */
 char *sdt_put_fasta_record(char *p, uint64_t ord, const uint32_t *words, uint64_t start, uint64_t len);
+/* the sequence line alone: len bases from `start` of words and a newline (len + 1 bytes) */
+char *sdt_put_fasta_bases(char *p, const uint32_t *words, uint64_t start, uint64_t len);
 
 #endif

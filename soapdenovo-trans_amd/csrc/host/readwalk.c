@@ -3,6 +3,7 @@
 #include <string.h>
 #include "readwalk.h"
 #include "trimsplit.h"
+#include "putdec.h"
 
 int ob_open(outbuf *o, const char *path)
 {
@@ -104,8 +105,14 @@ int sdt_walk_reads(const kept_reads *k, const sdt_pair_ranges *pairs, const char
 		tally->kept++;
 		tally->bases_out += len;
 		outbuf *o = to == SDT_TRIM_TO_PAIRS && out[1].f ? &out[1] : &out[2];
-		ob_room(o, (size_t)len + 24);
-		o->p = sdt_put_fasta_record(o->p, ord, w, at + start, len);
+		ob_room(o, (size_t)len + 24 + SDT_WALK_NAME_TAIL_MAX);
+		if (stage->name_tail) {
+			*o->p++ = '>';
+			o->p = stage->name_tail(state, sdt_put_dec(o->p, ord + 1, ' '), ord);
+			o->p = sdt_put_fasta_bases(o->p, w, at + start, len);
+		} else {
+			o->p = sdt_put_fasta_record(o->p, ord, w, at + start, len);
+		}
 	}
 	const int all_written = out[0].ok && (!out[1].f || out[1].ok) && out[2].ok;
 	if ((ob_close(&out[0]) != 0) | (out[1].f && ob_close(&out[1]) != 0) | (ob_close(&out[2]) != 0) || bad) return 1;

@@ -41,7 +41,10 @@ typedef struct {
 	int (*alive)(const void *state, uint64_t ord);                              /* sdt_alive_fn of trimsplit.h: is anything of it kept */
 	/* NULL, or what changes the read (read_len bases from `start` of words) before its FASTA record is written; 0, or -1 */
 	int (*edit)(void *state, uint64_t ord, uint32_t *words, uint64_t start, uint64_t read_len);
+	/* NULL, or what follows "><read number> " in the name line of a FASTA record, newline included; at most SDT_WALK_NAME_TAIL_MAX bytes */
+	char *(*name_tail)(const void *state, char *p, uint64_t ord);
 } sdt_walk_stage;
+enum { SDT_WALK_NAME_TAIL_MAX = 40 };
 
 typedef struct { unsigned long long kept, bases_in, bases_out; } sdt_walk_tally;   /* reads written; bases of all reads; bases written */
 

@@ -112,6 +112,16 @@
  *       prefix.cmpMatrix: the joint spectrum; prefix.cmpKmers (--select): the k-mers of A in the ranges, with both counts
  *       and one line: compare: nodes_a X nodes_b Y shared S solid_a P solid_b Q solid_shared T jaccard_x10000 J contain_a_x10000 U
  *       contain_b_x10000 V braycurtis_x10000 W   (cmpsplit.c, which documents the files and the ratios)
+ *   sdt-kmers cluster -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--max-count M, default 0 = no limit]
+ *                     [--min-link N, default 1] [--pick LO:HI] -o prefix
+ *       the reads split along the connected components of the counted k-mer graph (sdt_gpu_cluster_begin, sdt_gpu_cluster_kept_reads,
+ *       sdt_gpu_cluster_components; the rule: include/sdt_gpu.h).  The two mates of a pair are one unit; pairs as for normalize.  Ids
+ *       are 1-based in every file and 0 means none (clustersplit.c, which documents the files)
+ *       prefix.readCluster: one line per read in stream order:  kmers live split cluster unit verdict
+ *       prefix.clusters: per cluster  id kmer nodes count_sum reads bases,  then  # live L link_ends E clusters C largest N unassigned U
+ *       prefix.cluster.pairs.fa / prefix.cluster.single.fa: the reads, as dedup routes and names them, with " cluster=<id>" behind the
+ *       name; with --pick only the units of the clusters LO .. HI
+ *       and one line: cluster: reads R assigned A whole W through_mate M unassigned U short S clusters C largest_nodes N largest_reads X
  *
  * The query file is read and checked before the device is touched.
  *
@@ -141,6 +151,7 @@
 #include "qcsplit.h"
 #include "asmsplit.h"
 #include "cmpsplit.h"
+#include "clustersplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -316,6 +327,23 @@ static void usage(void)
 	        "           k-mers counted min_count times or more in A, in B, in both; J = floor(10000 S / (X + Y - S)), U = floor(10000 S / X),\n"
 	        "           V = floor(10000 S / Y), W = floor(10000 (sum cA + sum cB - 2 sum min(cA, cB)) / (sum cA + sum cB)); 0 when the\n"
 	        "           divisor is 0)\n"
+	        "       sdt-kmers cluster -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--max-count M, default 0]\n"
+	        "                         [--min-link N, default 1] [--pick LO:HI] -o prefix\n"
+	        "           the reads are split along the connected components of the counted k-mer graph.  A node is live if it is not deleted\n"
+	        "           and counted max(min_count, 1) times or more and, unless M is 0, at most M times (M takes the k-mers of adapters and\n"
+	        "           low-complexity sequence out, which glue unrelated transcripts together); a link counted N times or more (1 to 63)\n"
+	        "           between two live nodes joins them.  Clusters are numbered from 1 in ascending order of their smallest k-mer; a read\n"
+	        "           goes to the cluster of its first live k-mer, a pair to that of mate 1 if it has one, else of mate 2.\n"
+	        "           -> prefix.readCluster (per read in stream order: kmers live split cluster unit verdict; live = its live k-mers, split\n"
+	        "              = those of them in another cluster than its own, unit = the cluster of the read or pair, 0 none; verdict 0 whole,\n"
+	        "              1 assigned but split or apart from its unit, 2 assigned through its mate, 3 unassigned, 4 shorter than K),\n"
+	        "              prefix.clusters (per cluster: id kmer nodes count_sum reads bases, the smallest k-mer in letters; then:\n"
+	        "              # live L link_ends E clusters C largest N unassigned U), prefix.cluster.pairs.fa (read 1 then read 2 of the\n"
+	        "              pairs), prefix.cluster.single.fa (the single reads), every name followed by cluster=<unit>; with --pick only\n"
+	        "              the units of the clusters LO to HI are written\n"
+	        "           and one line: cluster: reads R assigned A whole W through_mate M unassigned U short S clusters C largest_nodes N\n"
+	        "           largest_reads X\n"
+	        "           Pairs are the reads of q1=/q2= and f1=/f2= files; the reads of a p= file are single reads, as for normalize.\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -399,6 +427,9 @@ typedef struct {
 	uint32_t cols, select[4];                                                /* compare: --cols; --select min_a max_a min_b max_b */
 	int select_given;
 	unsigned long long max_list;
+	sdt_cluster_params cluster;
+	uint32_t pick[2];                                                        /* cluster: --pick, as the library takes it */
+	int pick_given;
 	sdt_adapter_list ads;                                                    /* of afile[] */
 	sdt_ref_set refs;                                                        /* of rfile[] */
 	query_set qs;                                                            /* of qfile */
@@ -567,7 +598,7 @@ static int correct_alive(const void *state, uint64_t ord)
 /* `correct`: the records and the edits from the device, the kept batches back from HBM, the edits applied on the way into the one file */
 static int run_correct(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	static const sdt_walk_stage stage = {{".readFix", NULL, ".corrected.fa"}, 4 * 11, 1, correct_note, correct_line, correct_alive, edits_apply};
+	static const sdt_walk_stage stage = {{".readFix", NULL, ".corrected.fa"}, 4 * 11, 1, correct_note, correct_line, correct_alive, edits_apply, NULL};
 	sdt_read_fix *fix = (sdt_read_fix *)records_alloc(reads, sizeof *fix, 0);
 	correct_state st;
 	memset(&st, 0, sizeof st);
@@ -611,7 +642,7 @@ static int norm_alive(const void *state, uint64_t ord) { return (((const norm_st
 /* `normalize`: the verdicts from the device, the kept batches back from HBM, the kept reads into the pairs file or the singles file */
 static int run_normalize(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	static const sdt_walk_stage stage = {{".readPick", ".norm.pairs.fa", ".norm.single.fa"}, 4 * 11, 1, norm_note, norm_line, norm_alive, NULL};
+	static const sdt_walk_stage stage = {{".readPick", ".norm.pairs.fa", ".norm.single.fa"}, 4 * 11, 1, norm_note, norm_line, norm_alive, NULL, NULL};
 	sdt_read_pick *pick = (sdt_read_pick *)records_alloc(reads, sizeof *pick, 0xFF);
 	uint64_t got = 0, n_kept = 0;
 	if (!pick || SDT_CALL(sdt_gpu_select_kept_reads, gpu, &opt->norm, pairs->v, pairs->n, pick, reads, &got, &n_kept)) return 1;
@@ -648,7 +679,7 @@ static int dedup_alive(const void *state, uint64_t ord) { return ((const dedup_s
  * table of duplication levels (dupsplit.c) */
 static int run_dedup(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	static const sdt_walk_stage stage = {{".readDup", ".dedup.pairs.fa", ".dedup.single.fa"}, SDT_DUP_LINE_MAX, 1, dedup_note, dedup_line, dedup_alive, NULL};
+	static const sdt_walk_stage stage = {{".readDup", ".dedup.pairs.fa", ".dedup.single.fa"}, SDT_DUP_LINE_MAX, 1, dedup_note, dedup_line, dedup_alive, NULL, NULL};
 	sdt_read_dup *dup = (sdt_read_dup *)records_alloc(reads, sizeof *dup, 0xFF);
 	uint64_t got = 0, n_kept = 0;
 	if (!dup || SDT_CALL(sdt_gpu_dedup_kept_reads, gpu, &opt->dedup, pairs->v, pairs->n, dup, reads, &got, &n_kept)) return 1;
@@ -700,7 +731,7 @@ static int trim_alive(const void *state, uint64_t ord) { return ((const trim_sta
  * bases of every read into the pairs file (both mates survive) or the singles file (trimsplit.c) */
 static int run_trim(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	sdt_walk_stage stage = {{".readTrim", ".trim.pairs.fa", ".trim.single.fa"}, SDT_TRIM_LINE_MAX, 0, trim_note, trim_line, trim_alive, NULL};
+	sdt_walk_stage stage = {{".readTrim", ".trim.pairs.fa", ".trim.single.fa"}, SDT_TRIM_LINE_MAX, 0, trim_note, trim_line, trim_alive, NULL, NULL};
 	const int correct = (opt->trim.flags & SDT_TRIM_CORRECTED) != 0;
 	opt->trim.min_count = (uint32_t)opt->min_count;
 	sdt_read_trim *trim = (sdt_read_trim *)records_alloc(reads, sizeof *trim, 0);
@@ -749,7 +780,7 @@ static int clip_alive(const void *state, uint64_t ord) { return ((const clip_sta
  * survive) or the singles file, routed as trim routes them; the statistics (clipsplit.c) */
 static int run_clip(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	static const sdt_walk_stage stage = {{".readClip", ".clip.pairs.fa", ".clip.single.fa"}, SDT_CLIP_LINE_MAX, 0, clip_note, clip_line, clip_alive, NULL};
+	static const sdt_walk_stage stage = {{".readClip", ".clip.pairs.fa", ".clip.single.fa"}, SDT_CLIP_LINE_MAX, 0, clip_note, clip_line, clip_alive, NULL, NULL};
 	sdt_read_clip *clip = (sdt_read_clip *)records_alloc(reads, sizeof *clip, 0);
 	clip_state st = {clip, {0}};
 	if (!clip) return 1;
@@ -811,7 +842,7 @@ static int overlap_alive(const void *state, uint64_t ord) { return ((const overl
 static int run_overlap(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
 	static const sdt_walk_stage stage = {{".readOverlap", ".overlap.pairs.fa", ".overlap.single.fa"}, SDT_OVERLAP_LINE_MAX, 0,
-	                                     overlap_note, overlap_line, overlap_alive, NULL};
+	                                     overlap_note, overlap_line, overlap_alive, NULL, NULL};
 	sdt_read_overlap *ov = (sdt_read_overlap *)records_alloc(reads, sizeof *ov, 0);
 	uint64_t got = 0, n_kept = 0;
 	if (!ov || SDT_CALL(sdt_gpu_overlap_kept_pairs, gpu, &opt->overlap, pairs->v, pairs->n, ov, reads, &got, &n_kept)) return 1;
@@ -905,7 +936,7 @@ static int merged_write(const char *prefix, const sdt_pair_ranges *pairs, const 
  * into a file of their own; the histogram of the inserts (overlapsplit.c), the statistics (mergesplit.c) */
 static int run_merge(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	static const sdt_walk_stage stage = {{".readMerge", ".merge.pairs.fa", ".merge.single.fa"}, SDT_MERGE_LINE_MAX, 0, merge_note, merge_line, merge_alive, NULL};
+	static const sdt_walk_stage stage = {{".readMerge", ".merge.pairs.fa", ".merge.single.fa"}, SDT_MERGE_LINE_MAX, 0, merge_note, merge_line, merge_alive, NULL, NULL};
 	sdt_read_overlap *ov = (sdt_read_overlap *)records_alloc(reads, sizeof *ov, 0);
 	sdt_read_merge *mg = (sdt_read_merge *)records_alloc(reads, sizeof *mg, 0);
 	uint64_t got = 0, n_kept = 0, n_merged = 0, n_words = 0;
@@ -972,7 +1003,7 @@ static int cx_alive(const void *state, uint64_t ord) { return ((const cx_state *
  * mates survive) or the singles file, routed as clip routes them; the histogram of the scores (cxsplit.c) */
 static int run_complexity(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	static const sdt_walk_stage stage = {{".readComplexity", ".cx.pairs.fa", ".cx.single.fa"}, SDT_CX_LINE_MAX, 0, cx_note, cx_line, cx_alive, NULL};
+	static const sdt_walk_stage stage = {{".readComplexity", ".cx.pairs.fa", ".cx.single.fa"}, SDT_CX_LINE_MAX, 0, cx_note, cx_line, cx_alive, NULL, NULL};
 	sdt_read_complexity *cx = (sdt_read_complexity *)records_alloc(reads, sizeof *cx, 0);
 	uint64_t got = 0, n_kept = 0;
 	if (!cx || SDT_CALL(sdt_gpu_complexity_kept_reads, gpu, &opt->cx, cx, reads, &got, &n_kept) || !all_reads_came_back(reads, got, "decided")) return 1;
@@ -1016,7 +1047,7 @@ static int screen_alive(const void *state, uint64_t ord) { return ((const screen
 static int run_screen(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
 	static const sdt_walk_stage stage = {{".readScreen", ".screen.pairs.fa", ".screen.single.fa"}, SDT_SCREEN_LINE_MAX, 0,
-	                                     screen_note, screen_line, screen_alive, NULL};
+	                                     screen_note, screen_line, screen_alive, NULL, NULL};
 	const sdt_ref_set *refs = &opt->refs;
 	uint64_t distinct = 0;
 	if (SDT_CALL(sdt_gpu_screen_load, gpu, refs->words, refs->nwords, refs->offsets, refs->nseqs, refs->ref_of_seq, refs->n_refs, opt->screen_k, &distinct)) return 1;
@@ -1110,7 +1141,7 @@ static int qtrim_alive(const void *state, uint64_t ord) { return ((const qtrim_s
  * the singles file, routed as clip routes them; the histogram of the kept lengths (qualsplit.c) */
 static int run_qtrim(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
 {
-	static const sdt_walk_stage stage = {{".readQual", ".qtrim.pairs.fa", ".qtrim.single.fa"}, SDT_QUAL_LINE_MAX, 0, qtrim_note, qtrim_line, qtrim_alive, NULL};
+	static const sdt_walk_stage stage = {{".readQual", ".qtrim.pairs.fa", ".qtrim.single.fa"}, SDT_QUAL_LINE_MAX, 0, qtrim_note, qtrim_line, qtrim_alive, NULL, NULL};
 	qtrim_state *q = opt->qtrim;
 	if (reads > q->cap) { fprintf(stderr, "sdt-kmers: %llu reads streamed, records for %llu\n", reads, (unsigned long long)q->cap); return 1; }
 	sdt_walk_tally t;
@@ -1374,8 +1405,64 @@ static int run_compare(sdt_ctx *a, sdt_ctx *b, const options *opt)
 	return 0;
 }
 
+/* ---- cluster ----------------------------------------------------------------------------------------------------------------------------- */
+typedef struct { const sdt_read_cluster *rec; sdt_cluster_tally tally; const uint32_t *pick; } cluster_state;
+
+static int cluster_note(void *state, uint64_t ord, uint64_t read_len, uint64_t *start, uint64_t *len)
+{
+	cluster_state *s = (cluster_state *)state;
+	const sdt_read_cluster *r = s->rec + ord;
+	(void)start; (void)len;                                                  /* a read is written whole */
+	if (sdt_cluster_tally_note(&s->tally, r, read_len) != 0) {
+		fprintf(stderr, "sdt-kmers: the record of read %llu is %u %u %u %u %u %u\n", (unsigned long long)ord + 1, r->kmers, r->live, r->split, r->cluster, r->unit, r->verdict);
+		return -1;
+	}
+	return 0;
+}
+
+static char *cluster_line(const void *state, char *p, uint64_t ord) { return sdt_put_cluster_line(p, ((const cluster_state *)state)->rec + ord); }
+static char *cluster_name(const void *state, char *p, uint64_t ord) { return sdt_put_cluster_name_tail(p, ((const cluster_state *)state)->rec + ord); }
+static int cluster_alive(const void *state, uint64_t ord)
+{
+	const cluster_state *s = (const cluster_state *)state;
+	return !s->pick || sdt_cluster_picked(s->rec + ord, s->pick);
+}
+
+/* `cluster`: the clustering on the device, the records of the kept reads, the component list; the kept batches back from HBM, every
+ * read (with --pick: of the picked units) into the pairs file or the singles file; the cluster list with the reads of each */
+static int run_cluster(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	static const sdt_walk_stage stage = {{".readCluster", ".cluster.pairs.fa", ".cluster.single.fa"}, SDT_CLUSTER_LINE_MAX, 1, cluster_note, cluster_line,
+	                                     cluster_alive, NULL, cluster_name};
+	uint64_t info[8], got = 0, n_kept = 0, n_comp = 0;
+	opt->cluster.min_count = (uint32_t)opt->min_count;
+	if (SDT_CALL(sdt_gpu_cluster_begin, gpu, &opt->cluster, info)) return 1;
+	sdt_read_cluster *rec = (sdt_read_cluster *)records_alloc(reads, sizeof *rec, 0xFF);
+	if (!rec || SDT_CALL(sdt_gpu_cluster_kept_reads, gpu, pairs->v, pairs->n, opt->pick[0], opt->pick[1], rec, reads, &got, &n_kept)) return 1;
+	if (!all_reads_came_back(reads, got, "clustered")) return 1;
+	const int nw = sdt_gpu_key_words(gpu);
+	uint64_t *keys = (uint64_t *)malloc((info[2] ? info[2] : 1) * (size_t)nw * sizeof(uint64_t));
+	sdt_cluster_comp *comp = (sdt_cluster_comp *)malloc((info[2] ? info[2] : 1) * sizeof *comp);
+	cluster_state st = {rec, {0}, opt->pick_given ? opt->pick : NULL};
+	if (!keys || !comp || sdt_cluster_tally_init(&st.tally, info[2]) != 0) { fprintf(stderr, "sdt-kmers: out of memory for %llu clusters\n", (unsigned long long)info[2]); return 1; }
+	if (SDT_CALL(sdt_gpu_cluster_components, gpu, keys, comp, info[2], &n_comp)) return 1;
+	if (SDT_CALL(sdt_gpu_cluster_end, gpu)) return 1;
+	sdt_walk_tally t;
+	if (fetch_and_walk(gpu, reads, pairs, opt->outname, &stage, &st, opt->pick_given ? n_kept : reads, &t) != 0) return 1;
+	char path[4200], line[SDT_CLUSTER_SUMMARY_MAX];
+	FILE *f = stats_open(path, opt->outname, ".clusters");
+	if (!f) return cannot_write(path);
+	const int bad = sdt_cluster_list_write(f, keys, comp, nw, opt->K, info, &st.tally) != 0;
+	if ((fclose(f) != 0) | bad) { fprintf(stderr, "sdt-kmers: write to %s failed\n", path); return 1; }
+	sdt_cluster_summary(line, info, &st.tally);
+	fputs(line, stdout);
+	sdt_cluster_tally_free(&st.tally);
+	free(keys); free(comp); free(rec);
+	return 0;
+}
+
 /* ---- the command line ------------------------------------------------------------------------------------------------------------------ */
-enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, COMPARE, N_SUBCOMMANDS };
+enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, COMPARE, CLUSTER, N_SUBCOMMANDS };
 
 static const struct {
 	const char *name;
@@ -1392,11 +1479,12 @@ static const struct {
 	[QC] = {"qc", 0, 0, 0, NULL},                           /* (streams on its own and counts nothing: run_qc, from main) */
 	[EVALUATE] = {"evaluate", 0, 0, 2, run_evaluate},
 	[COMPARE] = {"compare", 0, 0, 2, NULL},                 /* (counts two sets of libraries into two contexts: run_compare, from main) */
+	[CLUSTER] = {"cluster", 1, 1, 2, run_cluster},
 };
 
 enum { O_MAX_K = 1000, O_DEVICE, O_TARGET, O_MAX_CV, O_SEED, O_MIN_COV, O_MIN_LEN, O_CORRECT, O_MATE_SWAP, O_TAIL3, O_TAIL5, O_MIN_OVERLAP, O_ERROR_PCT,
        O_MIN_TAIL, O_TAIL_ERROR_PCT, O_MAX_ERR, O_MAX_SCORE, O_MAX_LOW, O_TRIM_LOW, O_PHRED, O_CUT_Q, O_LOW_Q, O_MAX_LOW_BASES, O_MAX_EE, O_SCREEN_K,
-       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED, O_CYCLES, O_FROM_END, O_ASSEMBLY, O_ROWS, O_AGAINST, O_COLS, O_SELECT, O_MAX_LIST };
+       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED, O_CYCLES, O_FROM_END, O_ASSEMBLY, O_ROWS, O_AGAINST, O_COLS, O_SELECT, O_MAX_LIST, O_MAX_COUNT, O_MIN_LINK, O_PICK };
 
 /* the options that belong to some subcommands only: the name as it is printed, who may be given it, what the refusal says after
  * "belongs to" (kept, not derived: --min-overlap names clip alone), and the most its value may be where it takes a whole number */
@@ -1422,6 +1510,8 @@ static const struct { int code; const char *name; unsigned owners; const char *b
 	{O_ASSEMBLY, "--assembly", BIT(EVALUATE), "evaluate", 0}, {O_ROWS, "--rows", BIT(EVALUATE) | BIT(COMPARE), "evaluate", SDT_CMP_MAX_CELLS / 2},
 	{O_AGAINST, "--against", BIT(COMPARE), "compare", 0}, {O_COLS, "--cols", BIT(COMPARE), "compare", SDT_CMP_MAX_CELLS / 2},
 	{O_SELECT, "--select", BIT(COMPARE), "compare", 0}, {O_MAX_LIST, "--max-list", BIT(COMPARE), "compare", 1ULL << 31},
+	{O_MAX_COUNT, "--max-count", BIT(CLUSTER), "cluster", UINT32_MAX}, {O_MIN_LINK, "--min-link", BIT(CLUSTER), "cluster", 63},
+	{O_PICK, "--pick", BIT(CLUSTER), "cluster", 0},
 };
 
 /* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
@@ -1470,6 +1560,8 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 	                                   {"assembly", required_argument, 0, O_ASSEMBLY}, {"rows", required_argument, 0, O_ROWS},
 	                                   {"against", required_argument, 0, O_AGAINST}, {"cols", required_argument, 0, O_COLS},
 	                                   {"select", required_argument, 0, O_SELECT}, {"max-list", required_argument, 0, O_MAX_LIST},
+	                                   {"max-count", required_argument, 0, O_MAX_COUNT}, {"min-link", required_argument, 0, O_MIN_LINK},
+	                                   {"pick", required_argument, 0, O_PICK},
 	                                   {0, 0, 0, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:r:", longopts, NULL)) != -1) {
@@ -1569,6 +1661,18 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 			opt->select_given = 1;
 			break;
 		case O_MAX_LIST: opt->max_list = v; break;
+		case O_MAX_COUNT: opt->cluster.max_count = (uint32_t)v; break;
+		case O_MIN_LINK:
+			if (v == 0) { fprintf(stderr, "sdt-kmers: --min-link must be at least 1\n"); return 255; }
+			opt->cluster.min_link = (uint32_t)v;
+			break;
+		case O_PICK:
+			if (sdt_cluster_parse_pick(optarg, opt->pick) != 0) {
+				fprintf(stderr, "sdt-kmers: --pick %s: LO:HI is expected, two cluster ids from 1 with LO <= HI\n", optarg);
+				return 255;
+			}
+			opt->pick_given = 1;
+			break;
 		default: usage(); return 255;
 		}
 	}
@@ -1592,6 +1696,10 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 	}
 	if (sub == MERGE && opt->merge.max_len != 0 && opt->merge.max_len < (opt->merge.min_len > 1 ? opt->merge.min_len : 1u)) {
 		fprintf(stderr, "sdt-kmers: --max-merged %u is below --min-merged %u: no pair could merge (0: no limit)\n", opt->merge.max_len, opt->merge.min_len);
+		return 255;
+	}
+	if (sub == CLUSTER && opt->cluster.max_count != 0 && opt->cluster.max_count < (opt->min_count > 1 ? opt->min_count : 1ul)) {
+		fprintf(stderr, "sdt-kmers: --max-count %u is below -c %lu: no node could be live (0: no limit)\n", opt->cluster.max_count, opt->min_count);
 		return 255;
 	}
 	if (sub == NORMALIZE && opt->norm.target == 0) { fprintf(stderr, "sdt-kmers: --target must be at least 1\n"); return 255; }
@@ -1706,7 +1814,8 @@ int main(int argc, char **argv)
 	static options opt = {.K = 23, .threads = 8,
 	                      .norm = {50, 10000, 0}, .clip = {5, 10, 0, 10, 20, 0, 0, 0}, .overlap = {30, 10, 0, 0}, .cx = {10, 50, 0, 0},
 	                      .qual = {33, 20, 15, 40, 0, 0, 0, 0}, .screen = {1, 0, 0, 0}, .merge = {0, 0, 33, 0},
-	                      .qc = {1024, 33, 0, 0, 0}, .screen_k = 31, .rows = 256, .cols = 64, .max_list = 1000000};                                   /* bbduk's usual figure: a choice, not a measurement */
+	                      .qc = {1024, 33, 0, 0, 0}, .screen_k = 31, .rows = 256, .cols = 64, .max_list = 1000000,
+	                      .cluster = {2, 0, 1, 0}, .pick = {0, 0xFFFFFFFEu}};                                   /* bbduk's usual figure: a choice, not a measurement */
 	opt.min_count = subcommands[sub].min_count;
 	if (sub == COMPARE) opt.rows = 64;
 	sdt_cfg cfg;

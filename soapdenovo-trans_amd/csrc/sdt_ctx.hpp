@@ -14,6 +14,7 @@
 //   sdt_asm.hip       an assembly scored against the counted table: per-sequence support records, a copy number per node, the spectrum
 //   sdt_compare.hip   two counted tables compared: the joint count spectrum and the k-mers within given ranges of both counts (the one
 //                     unit whose entry points take two contexts)
+//   sdt_cluster.hip   the counted table as a graph: its connected components, one label per slot, and the reads' clusters
 //   sdt_gpu_graph.hip the graph phases (own view of the context: sdt_internal.hpp GraphView)
 // Not part of the ABI: nothing here is visible to a caller of libsdt_gpu.so.
 #pragma once
@@ -192,6 +193,17 @@ struct sdt_ctx {
 		uint32_t min_count = 0, rows = 0;
 		bool open = false, stale = false;
 	} asmt;
+	// the clustering (sdt_cluster.hip): one 32-bit label per table slot, the id of the node's cluster or 0xFFFFFFFF; lives from
+	// cluster_begin to cluster_end / destroy.  The component list is small and stays on the host.  Like the tally it belongs to one
+	// state of the table: search_cache_drop marks it stale, and a stale clustering is refused, not read
+	struct Clustering {
+		uint32_t *label = nullptr;         // slots words
+		uint64_t slots = 0;                // the table's slots at cluster_begin
+		std::vector<uint64_t> keys;        // clusters x nw words: the smallest k-mer of every cluster, in id order
+		std::vector<uint64_t> count_sum;   // per cluster
+		std::vector<uint32_t> nodes;       // per cluster
+		bool open = false, stale = false;
+	} cl;
 	// timing
 	std::vector<EventPair> ev;
 	size_t ev_used = 0;
@@ -229,11 +241,12 @@ inline uint64_t wave_blocks_forced()
 
 
 // the table is about to change (nodes counted, moved or replaced): what sdt_search.hip derived from it is stale, and so is the
-// assembly tally of sdt_asm.hip, which is kept by slot
+// assembly tally of sdt_asm.hip and the clustering of sdt_cluster.hip, which are kept by slot
 inline void search_cache_drop(sdt_ctx *c)
 {
 	c->hi_mode = -1;
 	c->asmt.stale = true;
+	c->cl.stale = true;
 }
 
 inline int env_int(const char *name, int dflt) { const char *v = getenv(name); return v && *v ? atoi(v) : dflt; }

@@ -377,6 +377,7 @@ int sdt_gpu_destroy(sdt_ctx *c)
 	if (c->screen.tab) (void)hipFree(c->screen.tab);
 	if (c->asmt.cn) (void)hipFree(c->asmt.cn);
 	if (c->asmt.totals) (void)hipFree(c->asmt.totals);
+	if (c->cl.label) (void)hipFree(c->cl.label);
 	for (int i = 0; i < 5; i++) if (c->ab[i]) (void)hipFree(c->ab[i]);
 	sk_free(c);
 	shard_free(c);
@@ -829,6 +830,7 @@ int sdt_gpu_delow(sdt_ctx *c, int d, uint64_t *removed)
 		d = 0;       // pregraph.c:159: negative -d becomes 0
 	SDT_ENTER(c);
 	{ const int rcd = drain_staged(c, true); if (rcd != SDT_OK) return rcd; }
+	c->cl.stale = true;          // (deleted flags decide which nodes a clustering of sdt_cluster.hip holds; counts and slots stay: nothing else is stale)
 	HIPCHK(hipMemsetAsync(&c->d_stats->scratch, 0, sizeof(unsigned long long), c->stream));
 	const int g = scan_grid(c, view_slots(c));
 	if (c->nw == 1) hipLaunchKernelGGL(k_delow<1>, dim3(g), dim3(TPB), 0, c->stream, table_of<1>(c), (uint32_t)d, c->d_stats);
@@ -1056,6 +1058,7 @@ int drain_pushes(sdt_ctx *c, bool force) { return drain_staged(c, force); }
 static int graph_enter(sdt_ctx *c)
 {
 	SDT_ENTER(c);
+	c->cl.stale = true;          // (the graph phases may set deleted flags and cut links: a clustering of sdt_cluster.hip is by the state it was begun on)
 	return SDT_OK;
 }
 

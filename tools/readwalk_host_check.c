@@ -47,8 +47,8 @@ static int alive(const void *st, uint64_t ord)
 	return s->by_verdict ? s->r[ord].verdict == 0 : s->r[ord].len != 0;
 }
 
-static const sdt_walk_stage by_range = {{".lines", ".pairs", ".single"}, 3 * 11, 0, note, put_line, alive, NULL};
-static const sdt_walk_stage by_verdict = {{".lines", ".pairs", ".single"}, 3 * 11, 1, note, put_line, alive, NULL};
+static const sdt_walk_stage by_range = {{".lines", ".pairs", ".single"}, 3 * 11, 0, note, put_line, alive, NULL, NULL};
+static const sdt_walk_stage by_verdict = {{".lines", ".pairs", ".single"}, 3 * 11, 1, note, put_line, alive, NULL, NULL};
 
 /* n reads of the letters given as one batch: malloc'ed words and offsets as kept_add takes them (A0 C1 T2 G3) */
 static void make_batch(const char *const *reads, uint64_t n, uint32_t **words, uint64_t **offsets)
@@ -217,7 +217,7 @@ int main(int argc, char **argv)
 		char full[4200], errpath[4200], said[8400];
 		snprintf(full, sizeof full, "%s.full", prefix);
 		snprintf(errpath, sizeof errpath, "%s.stderr", prefix);
-		const sdt_walk_stage to_full = {{".lines", ".full", ".single"}, 3 * 11, 0, note, put_line, alive, NULL};
+		const sdt_walk_stage to_full = {{".lines", ".full", ".single"}, 3 * 11, 0, note, put_line, alive, NULL, NULL};
 		remove(full);
 		CHECK(symlink("/dev/full", full) == 0);
 		st.noted = 0;
