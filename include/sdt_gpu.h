@@ -1215,7 +1215,68 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  * 8 B x (key words + 2) + 8 B and the sort's scratch; SDT_ENOMEM with nothing left allocated when that does not fit.  The forms
  * over reads hold what select_reads holds, with records of 24 B.
  * Out of scope: tables of 2^32 - 1 slots and more; sharded contexts; joining clusters through mate pairs; removing knots beyond
- * what max_count does. */
+ * what max_count does.
+ *
+ * The bubbles of the counted k-mer graph: two non-branching paths that leave one k-mer and meet again.  A substitution (a SNP, a
+ * recurring error) is a bubble with K nodes on each side, an indel one with unequal sides, a skipped exon a short side against a
+ * long one (what KisSplice and DiscoSNP report from a de Bruijn graph) -- the structures that tip cutting and the removal of minor
+ * branches flatten.  Needs the counted table, and writes nothing to it, to the kept reads or to any cache or tally of the context.
+ * Added without a change of SDT_ABI_VERSION: the four calls, the two structs and the constant are additions.
+ *     Integers only.  Everything is exact and does not depend on the table's size or layout, on the pass-1 kernel family, or on
+ *     the launch geometry.
+ *     PARAMETERS (sdt_bubble_params): flags and reserved must be 0; min_link 1 .. 63; max_count 0 (no upper bound) or
+ *     >= max(min_count, 1); max_len 1 .. SDT_BUBBLE_MAX_LEN (2^20).
+ *     LIVE NODES are those of cluster_begin: the node exists, its deleted flag is clear, its 32-bit count (with the high half) is
+ *     >= max(min_count, 1), and max_count is 0 or the count is <= max_count.
+ *     ORIENTED WORDS.  The rule speaks of k-mer words x: K bases, either strand.  The node of x is its canonical strand; x is live
+ *     iff that node is; count(x) is the node's count.  The OUT SIDE of x comes from the node's own link word (l_links |
+ *     r_links << 24): if x is the stored canonical key, the four right counters, base b at bits 24 + 6 b; otherwise the four left
+ *     counters of the canonical key, base b read at bits 6 (b ^ 2).  A palindrome (even K) is its own canonical key, uses the
+ *     right counters, and is one oriented word, not two.
+ *     SUCCESSORS.  succ(x) is the list, in ascending b, of (b, y, link) with link = the out counter of x for b >= min_link,
+ *     y = next(x, b) -- x shifted left by one base, b behind, masked to K bases -- and y live.  outdeg(x) = |succ(x)|,
+ *     indeg(x) = |succ(revcomp(x))|.  Every degree comes from the examined node's own counters and the liveness of the neighbour
+ *     they name; in a table that pass 1 counted both ends of a link carry the same counter.
+ *     BRANCH.  For a source word s with outdeg(s) >= 2 and one (b, y, link) of succ(s): cur = y, len = 0, and repeat:
+ *         1. if indeg(cur) >= 2 the branch REACHES THE SINK cur; stop
+ *         2. else if outdeg(cur) != 1 or len == max_len the branch fails; stop
+ *         3. else cur is an inner node: len += 1, min = min(min, count(cur)), sum += count(cur), cur = its only successor.
+ *     A branch with len == 0 has min = 0 and sum = 0; a branch never has more than max_len inner nodes.  Nothing else is special:
+ *     s may be the sink.
+ *     BUBBLE.  Two branches of the same s, with bases base_a < base_b, that reach the same sink word t.  Three branches that
+ *     meet are three bubbles.  The bubble is REPORTED iff s <= revcomp(t), numeric on the key words, most significant first: a
+ *     bubble of a counted table is found from both of its ends, and this keeps one of them.
+ *     ID.  The reported bubbles are numbered 0 .. N - 1 in ascending order of (s, base_a, base_b).
+ *     RECORD (sdt_bubble, 48 bytes): sum_a, sum_b, len_a, len_b, min_a, min_b of the two branches; src_count = count(s),
+ *     snk_count = count(t); info = base_a | base_b << 2 | link_a << 8 | link_b << 16; reserved 0.  With each record go two
+ *     words, 2 x sdt_gpu_key_words uint64: s, then t, as oriented words, most significant word first.
+ *     PATHS.  Branch a of a bubble is len_a + 1 base codes (A 0, C 1, T 2, G 3, one byte each): the bases appended from s up to
+ *     and including the step that gives t; the first is base_a.  The allele sequence is s followed by them; its last K bases are t.
+ *   bubbles_begin: finds, sorts and numbers the bubbles, keeps the list on the device, and waits.  info[8]: [0] live nodes
+ *                  [1] fork sides: the oriented words with outdeg >= 2  [2] branches walked: the sum of outdeg over the fork sides
+ *                  [3] branches that reached a sink  [4] bubbles N  [5] the sum of len_a + len_b + 2 over the bubbles = the bytes
+ *                  of all paths  [6] the longest branch (len) of a reported bubble  [7] 0.  info may be NULL.  A second begin
+ *                  replaces the first.
+ *   bubbles_fetch: bubbles first .. first + n - 1 in id order: keys n x 2 x sdt_gpu_key_words words, rec n records; either may be
+ *                  NULL.  first + n > N: SDT_EINVAL.
+ *   bubbles_paths: offsets[2 n + 1] = the prefix sums of len + 1 in the order a0, b0, a1, b1, ...; the bytes of branch j at
+ *                  bases[offsets[j]].  SDT_EFULL, with the offsets written and no base written, when offsets[2 n] > capacity.
+ *                  bases == NULL with capacity == 0 asks for the offsets only.  The branches are walked again in the table: no
+ *                  path is stored at begin.
+ *   bubbles_end:   frees the list (sdt_gpu_destroy does too).  Without a begin: SDT_OK.
+ * There is no limit on the length of a branch other than max_len.  n == 0: SDT_OK, nothing touched, whatever the rest says.
+ * SDT_ESTATE: bubbles_begin under the state rules of search_kmers, with its messages (a shard or any context with a communicator
+ * among them); every other call without a begin, after bubbles_end, and once the table has changed since bubbles_begin (counted
+ * into, grown, reset, delow, imported, released, any call of the graph phases): "the table changed since sdt_gpu_bubbles_begin".
+ * SDT_EINVAL, before any launch: NULL params; flags or reserved not 0; min_link outside 1 .. 63; max_count below
+ * max(min_count, 1) and not 0; max_len outside 1 .. 2^20 -- each with the field and its value; a range past N.
+ * Device memory: from bubbles_begin to bubbles_end 48 B + 16 B x key words per bubble.  During bubbles_begin the fork list, 8 B per
+ * fork side in chunks of 256 (a first guess of one per 64 table slots, the exact need on a second scan when that was too small),
+ * the bubbles as they are found, six per fork side at the most at 48 B + 16 B x key words, and per bubble 24 B of sort keys and
+ * order with the sort's scratch.  Nothing is per table slot.  SDT_ENOMEM leaves nothing allocated.  bubbles_paths holds the
+ * offsets and the bytes it returns.
+ * Out of scope: nested or overlapping bubbles (inner nodes are 1-in 1-out); popping or editing anything; allele counts from a
+ * second table; phasing by reads or mates; sharded contexts; 2^32 bubbles and more. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -1261,6 +1322,9 @@ typedef struct { uint32_t min_a, max_a, min_b, max_b; } sdt_cmp_range;
 typedef struct { uint32_t min_count, max_count, min_link, flags; } sdt_cluster_params;   /* flags: 0 */
 typedef struct { uint64_t count_sum; uint32_t nodes, reserved; } sdt_cluster_comp;   /* 16 bytes */
 typedef struct { uint32_t kmers, live, split, cluster, unit, verdict; } sdt_read_cluster;   /* 24 bytes */
+#define SDT_BUBBLE_MAX_LEN (1u << 20) /* sdt_bubble_params.max_len: inner nodes of a branch at the most */
+typedef struct { uint32_t min_count, max_count, min_link, max_len, flags, reserved; } sdt_bubble_params;   /* flags, reserved: 0 */
+typedef struct { uint64_t sum_a, sum_b; uint32_t len_a, len_b, min_a, min_b, src_count, snk_count, info, reserved; } sdt_bubble;   /* 48 bytes */
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -1401,6 +1465,10 @@ int sdt_gpu_cluster_kept_reads(sdt_ctx *ctx, const uint64_t *pair_ranges, uint64
                                uint32_t pick_hi, sdt_read_cluster *rec, uint64_t out_capacity, uint64_t *nreads,
                                uint64_t *n_kept);
 int sdt_gpu_cluster_end(sdt_ctx *ctx);
+int sdt_gpu_bubbles_begin(sdt_ctx *ctx, const sdt_bubble_params *params, uint64_t info[8]);
+int sdt_gpu_bubbles_fetch(sdt_ctx *ctx, uint64_t first, uint64_t n, uint64_t *keys, sdt_bubble *rec);
+int sdt_gpu_bubbles_paths(sdt_ctx *ctx, uint64_t first, uint64_t n, uint8_t *bases, uint64_t capacity, uint64_t *offsets);
+int sdt_gpu_bubbles_end(sdt_ctx *ctx);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

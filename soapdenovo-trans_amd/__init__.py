@@ -223,6 +223,10 @@ _ABI = [
     ("sdt_gpu_cluster_kept_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_uint64,
                                               _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_cluster_end", _c.c_int, [_c.c_void_p]),
+    ("sdt_gpu_bubbles_begin", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_bubbles_fetch", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_bubbles_paths", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
+    ("sdt_gpu_bubbles_end", _c.c_int, [_c.c_void_p]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -288,6 +292,11 @@ READ_CLUSTER_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "live", "split"
 CLUSTER_COMP_DTYPE = np.dtype([("count_sum", np.uint64), ("nodes", np.uint32), ("reserved", np.uint32)])
 CLUSTER_NONE = 0xFFFFFFFF                                # SDT_CLUSTER_NONE
 CLUSTER_WHOLE, CLUSTER_NOT_WHOLE, CLUSTER_THROUGH_MATE, CLUSTER_UNASSIGNED, CLUSTER_SHORT = range(5)
+# sdt_bubble (include/sdt_gpu.h): one record of 48 bytes per bubble of the counted k-mer graph; info = base_a | base_b << 2 |
+# link_a << 8 | link_b << 16
+BUBBLE_DTYPE = np.dtype([("sum_a", np.uint64), ("sum_b", np.uint64)] +
+                        [(f, np.uint32) for f in ("len_a", "len_b", "min_a", "min_b", "src_count", "snk_count", "info", "reserved")])
+BUBBLE_MAX_LEN = 1 << 20                                 # SDT_BUBBLE_MAX_LEN
 
 
 class NormParams(_c.Structure):
@@ -381,6 +390,14 @@ class ClusterParams(_c.Structure):
 
     def __init__(self, min_count=2, max_count=0, min_link=1, flags=0):
         super().__init__(min_count, max_count, min_link, flags)
+
+
+class BubbleParams(_c.Structure):
+    """sdt_bubble_params; the defaults of `sdt-kmers bubbles`"""
+    _fields_ = [(f, _c.c_uint32) for f in ("min_count", "max_count", "min_link", "max_len", "flags", "reserved")]
+
+    def __init__(self, min_count=2, max_count=0, min_link=1, max_len=1000, flags=0, reserved=0):
+        super().__init__(min_count, max_count, min_link, max_len, flags, reserved)
 
 
 class CmpRange(_c.Structure):
@@ -631,6 +648,14 @@ class PregraphGPU:
         if with_first:
             return keys[:k], l_links[:k], r_flags[:k], count[:k], first[:k]
         return keys[:k], l_links[:k], r_flags[:k], count[:k]
+
+    def import_nodes(self, keys, l_links, r_flags, count, first=None):
+        """nodes as export_nodes gives them (keys distinct, canonical and not in the table yet) into this context's table"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, self.nw)
+        l_links, r_flags, count = (np.ascontiguousarray(a, dtype=np.uint32) for a in (l_links, r_flags, count))
+        assert len(l_links) == len(r_flags) == len(count) == len(keys)
+        first = None if first is None else np.ascontiguousarray(first, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_import_nodes(self._ctx, _ptr(keys), _ptr(l_links), _ptr(r_flags), _ptr(count), _ptr(first), len(keys)))
 
     # -- graph-cleaning dry runs on the device mirror (cutTipPreGraph.c)
     def set_node_index(self, keys: np.ndarray):
@@ -1381,6 +1406,44 @@ class PregraphGPU:
 
     def cluster_end(self):
         self._check(self.lib.sdt_gpu_cluster_end(self._ctx))
+
+    # -- the bubbles of the counted k-mer graph (the rule: include/sdt_gpu.h).  Nothing is written to the table; the sorted list lives
+    # on the device from bubbles_begin to bubbles_end
+    def bubbles_begin(self, params=None):
+        """params: BubbleParams or its fields as a dict -> info uint64[8]: live nodes, fork sides, branches walked, branches that
+        reached a sink, bubbles, bytes of all paths, longest branch, 0"""
+        prm = params if isinstance(params, BubbleParams) else BubbleParams(**(params or {}))
+        info = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_bubbles_begin(self._ctx, ctypes.addressof(prm), _ptr(info)))
+        return info
+
+    def bubbles_fetch(self, first: int, n: int):
+        """-> (keys uint64[n, 2, key_words]: source and sink as oriented words; BUBBLE_DTYPE[n]) of bubbles first .. first + n - 1"""
+        keys = np.zeros((n, 2, self.nw), dtype=np.uint64)
+        rec = np.zeros(n, dtype=BUBBLE_DTYPE)
+        self._check(self.lib.sdt_gpu_bubbles_fetch(self._ctx, first, n, _ptr(keys) if n else None, _ptr(rec) if n else None))
+        return keys, rec
+
+    def bubbles_paths(self, first: int, n: int, capacity: int = None):
+        """-> (bases uint8[offsets[2 n]]: A 0, C 1, T 2, G 3; offsets uint64[2 n + 1]: branch a of bubble first + i is
+        bases[offsets[2 i] : offsets[2 i + 1]], branch b the stretch after it).  capacity: the room to offer (default: what is
+        needed, asked for first; SdtError SDT_EFULL when it is too small: e.offsets holds the offsets)"""
+        offsets = np.zeros(2 * n + 1, dtype=np.uint64)
+        if n == 0:
+            return np.zeros(0, dtype=np.uint8), offsets
+        if capacity is None:
+            self._check(self.lib.sdt_gpu_bubbles_paths(self._ctx, first, n, None, 0, _ptr(offsets)))
+            capacity = int(offsets[2 * n])
+        bases = np.zeros(max(capacity, 1), dtype=np.uint8)
+        rc = self.lib.sdt_gpu_bubbles_paths(self._ctx, first, n, _ptr(bases), capacity, _ptr(offsets))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.offsets = offsets
+            raise e
+        return bases[: int(offsets[2 * n])], offsets
+
+    def bubbles_end(self):
+        self._check(self.lib.sdt_gpu_bubbles_end(self._ctx))
 
     # -- this context's counted table against another's (the rule: include/sdt_gpu.h); nothing is written to either
     def compare(self, other, rows: int = 64, cols: int = 64):

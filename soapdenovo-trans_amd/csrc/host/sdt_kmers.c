@@ -122,6 +122,13 @@
  *       prefix.cluster.pairs.fa / prefix.cluster.single.fa: the reads, as dedup routes and names them, with " cluster=<id>" behind the
  *       name; with --pick only the units of the clusters LO .. HI
  *       and one line: cluster: reads R assigned A whole W through_mate M unassigned U short S clusters C largest_nodes N largest_reads X
+ *   sdt-kmers bubbles -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--max-count M, default 0 = no limit]
+ *                     [--min-link N, default 1] [--max-branch L, default 1000] -o prefix
+ *       the bubbles of the counted k-mer graph, the variants that graph cleaning would merge (sdt_gpu_bubbles_begin, sdt_gpu_bubbles_fetch,
+ *       sdt_gpu_bubbles_paths; the rule: include/sdt_gpu.h).  No read is kept.  Ids are 1-based (bubblesplit.c, which documents the files)
+ *       prefix.bubbles: per bubble  id source sink base_a base_b len_a len_b min_a min_b sum_a sum_b link_a link_b kind
+ *       prefix.bubbles.fa: the two alleles of every bubble, >id_a and >id_b
+ *       and one line: bubbles: live L forks F branches B reached R bubbles N kind0 X kind1 Y kind2 Z longest M
  *
  * The query file is read and checked before the device is touched.
  *
@@ -152,6 +159,7 @@
 #include "asmsplit.h"
 #include "cmpsplit.h"
 #include "clustersplit.h"
+#include "bubblesplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -344,6 +352,17 @@ static void usage(void)
 	        "           and one line: cluster: reads R assigned A whole W through_mate M unassigned U short S clusters C largest_nodes N\n"
 	        "           largest_reads X\n"
 	        "           Pairs are the reads of q1=/q2= and f1=/f2= files; the reads of a p= file are single reads, as for normalize.\n"
+	        "       sdt-kmers bubbles -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--max-count M, default 0]\n"
+	        "                         [--min-link N, default 1] [--max-branch L, default 1000] -o prefix\n"
+	        "           the bubbles of the counted k-mer graph: two paths without a branch that leave one k-mer and meet again -- a SNP or a\n"
+	        "           recurring error (K nodes on each side), an indel (unequal sides), a skipped exon (a short side against a long one):\n"
+	        "           what graph cleaning would merge.  Live nodes and links as for cluster; a side has at most L inner nodes (1 to 1048576).\n"
+	        "           -> prefix.bubbles (per bubble: id source sink base_a base_b len_a len_b min_a min_b sum_a sum_b link_a link_b kind;\n"
+	        "              source and sink are k-mers in letters as the bubble is read, base_a < base_b (A C T G) follow the source, len =\n"
+	        "              the inner nodes of a side, min and sum = their counts, link = the counter of the side's first step; kind 0:\n"
+	        "              len_a = len_b = K, 1: other equal lengths, 2: unequal), prefix.bubbles.fa (>id_a len=.. min=.. sum=.. and the\n"
+	        "              allele from source to sink, then the same for b); ids from 1 in ascending order of (source, base_a, base_b)\n"
+	        "           and one line: bubbles: live L forks F branches B reached R bubbles N kind0 X kind1 Y kind2 Z longest M\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -430,6 +449,7 @@ typedef struct {
 	sdt_cluster_params cluster;
 	uint32_t pick[2];                                                        /* cluster: --pick, as the library takes it */
 	int pick_given;
+	uint32_t max_branch;                                                     /* bubbles: --max-branch, the inner nodes of a side at the most */
 	sdt_adapter_list ads;                                                    /* of afile[] */
 	sdt_ref_set refs;                                                        /* of rfile[] */
 	query_set qs;                                                            /* of qfile */
@@ -1461,8 +1481,48 @@ static int run_cluster(sdt_ctx *gpu, unsigned long long reads, options *opt, con
 	return 0;
 }
 
+/* ---- bubbles ----------------------------------------------------------------------------------------------------------------------------- */
+/* `bubbles`: the list on the device, then fetched and written a piece at a time with the paths of that piece (bubblesplit.c) */
+static int run_bubbles(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	(void)reads; (void)pairs;
+	enum { PIECE = 1 << 16 };
+	const sdt_bubble_params prm = {(uint32_t)opt->min_count, opt->cluster.max_count, opt->cluster.min_link, opt->max_branch, 0, 0};
+	uint64_t info[8], kinds[3] = {0, 0, 0}, cap = 0;
+	if (SDT_CALL(sdt_gpu_bubbles_begin, gpu, &prm, info)) return 1;
+	const int nw = sdt_gpu_key_words(gpu);
+	uint64_t *keys = (uint64_t *)malloc((size_t)PIECE * 2 * (size_t)nw * sizeof *keys), *offs = (uint64_t *)malloc((2 * (size_t)PIECE + 1) * sizeof *offs);
+	sdt_bubble *rec = (sdt_bubble *)malloc((size_t)PIECE * sizeof *rec);
+	uint8_t *bases = NULL;
+	if (!keys || !offs || !rec) { fprintf(stderr, "sdt-kmers: out of memory for the bubbles\n"); return 1; }
+	char path[4200], fa_path[4200], line[SDT_BUBBLE_SUMMARY_MAX];
+	FILE *f = stats_open(path, opt->outname, ".bubbles");
+	if (!f) return cannot_write(path);
+	FILE *fa = stats_open(fa_path, opt->outname, ".bubbles.fa");
+	if (!fa) return cannot_write(fa_path);
+	for (uint64_t first = 0; first < info[4]; first += PIECE) {
+		const uint64_t n = info[4] - first < PIECE ? info[4] - first : PIECE;
+		if (SDT_CALL(sdt_gpu_bubbles_fetch, gpu, first, n, keys, rec) || SDT_CALL(sdt_gpu_bubbles_paths, gpu, first, n, NULL, 0, offs)) return 1;
+		if (offs[2 * n] > cap) {
+			free(bases);
+			cap = offs[2 * n];
+			if (!(bases = (uint8_t *)malloc(cap))) { fprintf(stderr, "sdt-kmers: out of memory for %llu bases of paths\n", (unsigned long long)cap); return 1; }
+		}
+		if (SDT_CALL(sdt_gpu_bubbles_paths, gpu, first, n, bases, cap, offs)) return 1;
+		if (sdt_bubble_list_write(f, keys, rec, first, n, nw, opt->K, kinds) != 0) return cannot_write(path);
+		if (sdt_bubble_fasta_write(fa, keys, rec, bases, offs, first, n, nw, opt->K) != 0) return cannot_write(fa_path);
+	}
+	if (fclose(f) != 0) return cannot_write(path);
+	if (fclose(fa) != 0) return cannot_write(fa_path);
+	if (SDT_CALL(sdt_gpu_bubbles_end, gpu)) return 1;
+	sdt_bubble_summary(line, info, kinds);
+	fputs(line, stdout);
+	free(keys); free(offs); free(rec); free(bases);
+	return 0;
+}
+
 /* ---- the command line ------------------------------------------------------------------------------------------------------------------ */
-enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, COMPARE, CLUSTER, N_SUBCOMMANDS };
+enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, COMPARE, CLUSTER, BUBBLES, N_SUBCOMMANDS };
 
 static const struct {
 	const char *name;
@@ -1480,11 +1540,12 @@ static const struct {
 	[EVALUATE] = {"evaluate", 0, 0, 2, run_evaluate},
 	[COMPARE] = {"compare", 0, 0, 2, NULL},                 /* (counts two sets of libraries into two contexts: run_compare, from main) */
 	[CLUSTER] = {"cluster", 1, 1, 2, run_cluster},
+	[BUBBLES] = {"bubbles", 0, 0, 2, run_bubbles},
 };
 
 enum { O_MAX_K = 1000, O_DEVICE, O_TARGET, O_MAX_CV, O_SEED, O_MIN_COV, O_MIN_LEN, O_CORRECT, O_MATE_SWAP, O_TAIL3, O_TAIL5, O_MIN_OVERLAP, O_ERROR_PCT,
        O_MIN_TAIL, O_TAIL_ERROR_PCT, O_MAX_ERR, O_MAX_SCORE, O_MAX_LOW, O_TRIM_LOW, O_PHRED, O_CUT_Q, O_LOW_Q, O_MAX_LOW_BASES, O_MAX_EE, O_SCREEN_K,
-       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED, O_CYCLES, O_FROM_END, O_ASSEMBLY, O_ROWS, O_AGAINST, O_COLS, O_SELECT, O_MAX_LIST, O_MAX_COUNT, O_MIN_LINK, O_PICK };
+       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED, O_CYCLES, O_FROM_END, O_ASSEMBLY, O_ROWS, O_AGAINST, O_COLS, O_SELECT, O_MAX_LIST, O_MAX_COUNT, O_MIN_LINK, O_PICK, O_MAX_BRANCH };
 
 /* the options that belong to some subcommands only: the name as it is printed, who may be given it, what the refusal says after
  * "belongs to" (kept, not derived: --min-overlap names clip alone), and the most its value may be where it takes a whole number */
@@ -1510,8 +1571,8 @@ static const struct { int code; const char *name; unsigned owners; const char *b
 	{O_ASSEMBLY, "--assembly", BIT(EVALUATE), "evaluate", 0}, {O_ROWS, "--rows", BIT(EVALUATE) | BIT(COMPARE), "evaluate", SDT_CMP_MAX_CELLS / 2},
 	{O_AGAINST, "--against", BIT(COMPARE), "compare", 0}, {O_COLS, "--cols", BIT(COMPARE), "compare", SDT_CMP_MAX_CELLS / 2},
 	{O_SELECT, "--select", BIT(COMPARE), "compare", 0}, {O_MAX_LIST, "--max-list", BIT(COMPARE), "compare", 1ULL << 31},
-	{O_MAX_COUNT, "--max-count", BIT(CLUSTER), "cluster", UINT32_MAX}, {O_MIN_LINK, "--min-link", BIT(CLUSTER), "cluster", 63},
-	{O_PICK, "--pick", BIT(CLUSTER), "cluster", 0},
+	{O_MAX_COUNT, "--max-count", BIT(CLUSTER) | BIT(BUBBLES), "cluster", UINT32_MAX}, {O_MIN_LINK, "--min-link", BIT(CLUSTER) | BIT(BUBBLES), "cluster", 63},
+	{O_PICK, "--pick", BIT(CLUSTER), "cluster", 0}, {O_MAX_BRANCH, "--max-branch", BIT(BUBBLES), "bubbles", SDT_BUBBLE_MAX_LEN},
 };
 
 /* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
@@ -1561,7 +1622,7 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 	                                   {"against", required_argument, 0, O_AGAINST}, {"cols", required_argument, 0, O_COLS},
 	                                   {"select", required_argument, 0, O_SELECT}, {"max-list", required_argument, 0, O_MAX_LIST},
 	                                   {"max-count", required_argument, 0, O_MAX_COUNT}, {"min-link", required_argument, 0, O_MIN_LINK},
-	                                   {"pick", required_argument, 0, O_PICK},
+	                                   {"pick", required_argument, 0, O_PICK}, {"max-branch", required_argument, 0, O_MAX_BRANCH},
 	                                   {0, 0, 0, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:r:", longopts, NULL)) != -1) {
@@ -1673,6 +1734,10 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 			}
 			opt->pick_given = 1;
 			break;
+		case O_MAX_BRANCH:
+			if (v == 0) { fprintf(stderr, "sdt-kmers: --max-branch must be at least 1\n"); return 255; }
+			opt->max_branch = (uint32_t)v;
+			break;
 		default: usage(); return 255;
 		}
 	}
@@ -1698,7 +1763,7 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 		fprintf(stderr, "sdt-kmers: --max-merged %u is below --min-merged %u: no pair could merge (0: no limit)\n", opt->merge.max_len, opt->merge.min_len);
 		return 255;
 	}
-	if (sub == CLUSTER && opt->cluster.max_count != 0 && opt->cluster.max_count < (opt->min_count > 1 ? opt->min_count : 1ul)) {
+	if ((sub == CLUSTER || sub == BUBBLES) && opt->cluster.max_count != 0 && opt->cluster.max_count < (opt->min_count > 1 ? opt->min_count : 1ul)) {
 		fprintf(stderr, "sdt-kmers: --max-count %u is below -c %lu: no node could be live (0: no limit)\n", opt->cluster.max_count, opt->min_count);
 		return 255;
 	}
@@ -1815,7 +1880,7 @@ int main(int argc, char **argv)
 	                      .norm = {50, 10000, 0}, .clip = {5, 10, 0, 10, 20, 0, 0, 0}, .overlap = {30, 10, 0, 0}, .cx = {10, 50, 0, 0},
 	                      .qual = {33, 20, 15, 40, 0, 0, 0, 0}, .screen = {1, 0, 0, 0}, .merge = {0, 0, 33, 0},
 	                      .qc = {1024, 33, 0, 0, 0}, .screen_k = 31, .rows = 256, .cols = 64, .max_list = 1000000,
-	                      .cluster = {2, 0, 1, 0}, .pick = {0, 0xFFFFFFFEu}};                                   /* bbduk's usual figure: a choice, not a measurement */
+	                      .cluster = {2, 0, 1, 0}, .pick = {0, 0xFFFFFFFEu}, .max_branch = 1000};                                   /* bbduk's usual figure: a choice, not a measurement */
 	opt.min_count = subcommands[sub].min_count;
 	if (sub == COMPARE) opt.rows = 64;
 	sdt_cfg cfg;

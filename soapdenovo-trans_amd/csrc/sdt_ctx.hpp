@@ -15,6 +15,7 @@
 //   sdt_compare.hip   two counted tables compared: the joint count spectrum and the k-mers within given ranges of both counts (the one
 //                     unit whose entry points take two contexts)
 //   sdt_cluster.hip   the counted table as a graph: its connected components, one label per slot, and the reads' clusters
+//   sdt_bubble.hip    the counted table as a graph again: its bubbles (two non-branching paths between two k-mers), listed and re-walked
 //   sdt_gpu_graph.hip the graph phases (own view of the context: sdt_internal.hpp GraphView)
 // Not part of the ABI: nothing here is visible to a caller of libsdt_gpu.so.
 #pragma once
@@ -204,6 +205,17 @@ struct sdt_ctx {
 		std::vector<uint32_t> nodes;       // per cluster
 		bool open = false, stale = false;
 	} cl;
+	// the bubble list (sdt_bubble.hip): the records and their two words each, sorted, on the device from bubbles_begin to
+	// bubbles_end / destroy; nothing per table slot.  bubbles_paths walks the table again from these, so the list belongs to one state of
+	// the table like the clustering: stale once search_cache_drop, delow or a graph phase has said so
+	struct Bubbles {
+		uint64_t *keys = nullptr;          // n x 2 nw words: s, then t
+		void *rec = nullptr;               // n records of 48 bytes
+		uint64_t n = 0;
+		uint64_t slots = 0;                // the table's slots at bubbles_begin
+		uint32_t min_count = 0, max_count = 0, min_link = 0, max_len = 0;    // the rule of that begin (min_count: already max(min_count, 1))
+		bool open = false, stale = false;
+	} bb;
 	// timing
 	std::vector<EventPair> ev;
 	size_t ev_used = 0;
@@ -241,12 +253,14 @@ inline uint64_t wave_blocks_forced()
 
 
 // the table is about to change (nodes counted, moved or replaced): what sdt_search.hip derived from it is stale, and so is the
-// assembly tally of sdt_asm.hip and the clustering of sdt_cluster.hip, which are kept by slot
+// assembly tally of sdt_asm.hip and the clustering of sdt_cluster.hip, which are kept by slot, and the bubble list of sdt_bubble.hip,
+// whose paths are walked in the table again
 inline void search_cache_drop(sdt_ctx *c)
 {
 	c->hi_mode = -1;
 	c->asmt.stale = true;
 	c->cl.stale = true;
+	c->bb.stale = true;
 }
 
 inline int env_int(const char *name, int dflt) { const char *v = getenv(name); return v && *v ? atoi(v) : dflt; }

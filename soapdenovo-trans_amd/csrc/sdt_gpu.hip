@@ -378,6 +378,8 @@ int sdt_gpu_destroy(sdt_ctx *c)
 	if (c->asmt.cn) (void)hipFree(c->asmt.cn);
 	if (c->asmt.totals) (void)hipFree(c->asmt.totals);
 	if (c->cl.label) (void)hipFree(c->cl.label);
+	if (c->bb.keys) (void)hipFree(c->bb.keys);
+	if (c->bb.rec) (void)hipFree(c->bb.rec);
 	for (int i = 0; i < 5; i++) if (c->ab[i]) (void)hipFree(c->ab[i]);
 	sk_free(c);
 	shard_free(c);
@@ -831,6 +833,7 @@ int sdt_gpu_delow(sdt_ctx *c, int d, uint64_t *removed)
 	SDT_ENTER(c);
 	{ const int rcd = drain_staged(c, true); if (rcd != SDT_OK) return rcd; }
 	c->cl.stale = true;          // (deleted flags decide which nodes a clustering of sdt_cluster.hip holds; counts and slots stay: nothing else is stale)
+	c->bb.stale = true;          // (... and which nodes the bubbles of sdt_bubble.hip walk)
 	HIPCHK(hipMemsetAsync(&c->d_stats->scratch, 0, sizeof(unsigned long long), c->stream));
 	const int g = scan_grid(c, view_slots(c));
 	if (c->nw == 1) hipLaunchKernelGGL(k_delow<1>, dim3(g), dim3(TPB), 0, c->stream, table_of<1>(c), (uint32_t)d, c->d_stats);
@@ -1059,6 +1062,7 @@ static int graph_enter(sdt_ctx *c)
 {
 	SDT_ENTER(c);
 	c->cl.stale = true;          // (the graph phases may set deleted flags and cut links: a clustering of sdt_cluster.hip is by the state it was begun on)
+	c->bb.stale = true;          // (... and so is the bubble list of sdt_bubble.hip)
 	return SDT_OK;
 }
 
