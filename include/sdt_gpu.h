@@ -1276,7 +1276,74 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  * order with the sort's scratch.  Nothing is per table slot.  SDT_ENOMEM leaves nothing allocated.  bubbles_paths holds the
  * offsets and the bytes it returns.
  * Out of scope: nested or overlapping bubbles (inner nodes are 1-in 1-out); popping or editing anything; allele counts from a
- * second table; phasing by reads or mates; sharded contexts; 2^32 bubbles and more. */
+ * second table; phasing by reads or mates; sharded contexts; 2^32 bubbles and more.
+ *
+ * The unitigs of the counted k-mer graph and their links: the compacted de Bruijn graph, before any cleaning -- the maximal
+ * non-branching paths with their abundances and what joins them (what BCALM writes, what an assembler dumps as its graph, what
+ * Bandage draws).  Needs the counted table, and writes nothing to it, to the kept reads or to any cache or tally of the context.
+ * Added without a change of SDT_ABI_VERSION: the five calls and the three structs are additions.
+ *     Integers only.  Everything is exact and does not depend on the table's size or layout, on the pass-1 kernel family, or on
+ *     the launch geometry.
+ *     PARAMETERS (sdt_unitig_params): flags must be 0; min_link 1 .. 63; max_count 0 (no upper bound) or >= max(min_count, 1).
+ *     LIVE NODES, ORIENTED WORDS, SUCCESSORS (succ, outdeg, indeg, next, revcomp) are those of the bubble rule above, word for word.
+ *     JOIN.  For live oriented words x and y, JOIN(x, y) holds iff succ(x) has exactly one element and it is y; succ(revcomp(y))
+ *     has exactly one element and it is revcomp(x); the nodes of x and y differ (this excludes y = x and y = revcomp(x)); and
+ *     neither x nor y is its own reverse complement.  JOIN(x, y) <=> JOIN(revcomp(y), revcomp(x)) by construction, also where the
+ *     two ends of a link carry different counters, which imported tables can.  A word has at most one right and one left join,
+ *     so the oriented words fall into paths and cycles; each has a mirror image that shares no word with it (a shared word would
+ *     need a palindrome or a hairpin join, and both are excluded).
+ *     UNITIG.  A maximal chain x0 .. x(n-1) with JOIN(xi, xi+1).  A linear one is REPORTED in the orientation with
+ *     x0 <= revcomp(x(n-1)), numeric on the key words, most significant first; a palindromic single word is reported once.  A
+ *     cycle (every word has both joins) is reported as circular: of the two mirror cycles the one that holds the smallest word of
+ *     both; that word is a stored canonical key, and it is x0.  Every live node lies in exactly one reported unitig.
+ *     ID.  Ids run 0 .. N - 1 in ascending order of x0 (every word is in one unitig: no ties).
+ *     RECORD (sdt_unitig, 24 bytes): sum, min, max over the counts of the n nodes; nodes = n; info = circular | indeg(x0) << 4 |
+ *     outdeg(x(n-1)) << 8.  With each record go two words, 2 x sdt_gpu_key_words uint64: x0, then x(n-1), most significant word
+ *     first.
+ *     SEQUENCE.  The K bases of x0, then the last base of x1 .. x(n-1): nodes + K - 1 base codes (A 0, C 1, T 2, G 3, one byte
+ *     each).  A circular unitig is written the same way from x0; its last K - 1 bases are NOT its first K - 1: the closing link
+ *     says that it closes.
+ *     LINKS.  For a reported unitig u and an orientation o, the out word w is x(n-1) for o = 0 (+) and revcomp(x0) for o = 1 (-).
+ *     For every (b, y, link) of succ(w), in ascending b: if y is the first word of an oriented unitig (v, o') -- y = x0 of v for
+ *     o' = 0, y = revcomp(x(n-1)) of v for o' = 1 -- one record (sdt_unitig_link, 16 bytes): from = u, to = v, info = o | o' << 1
+ *     | b << 2 | link << 8, reserved 0.  The order is ascending (from, o, b).  A circular unitig gets its closing link
+ *     (u, +) -> (u, +) and the mirror from the same rule.  In a table that pass 1 counted every successor of an out word is such
+ *     a first word and every link appears from both sides; where the two ends of a link disagree, a target that is no first word
+ *     is left out and counted (*n_dangling).
+ *   unitigs_begin: finds, sorts and numbers the unitigs, keeps the list on the device, and waits.  info[8]: [0] live nodes
+ *                  [1] start words found (= 2 x the linear unitigs: a chain is walked from both ends)  [2] unitigs N  [3] circular
+ *                  ones  [4] the sum of nodes over the list: it equals [0], or the call fails with SDT_ESTATE and says so  [5] the
+ *                  bytes of all sequences  [6] the longest unitig, in nodes  [7] 0.  info may be NULL.  A second begin replaces the
+ *                  first.
+ *   unitigs_fetch: unitigs first .. first + n - 1 in id order: keys n x 2 x sdt_gpu_key_words words, rec n records; either may be
+ *                  NULL.  first + n > N: SDT_EINVAL.
+ *   unitigs_seqs:  offsets[n + 1] = the prefix sums of nodes + K - 1; the bytes of unitig first + i at bases[offsets[i]].
+ *                  SDT_EFULL, with the offsets written and no base written, when offsets[n] > capacity.  bases == NULL with
+ *                  capacity == 0 asks for the offsets only.  The chains are walked again in the table: no sequence is stored at
+ *                  begin; a chain that walks otherwise than at begin is counted and the call fails with SDT_ESTATE.
+ *   unitigs_links: the links of the unitigs of the range, *n_links of them; *n_dangling (may be NULL) as above.  SDT_EFULL, with
+ *                  *n_links set and nothing written, when *n_links > capacity.  links == NULL with capacity == 0 asks for the size.
+ *   unitigs_end:   frees the list (sdt_gpu_destroy does too).  Without a begin: SDT_OK.
+ * n == 0: SDT_OK, nothing touched, whatever the rest says.
+ * SDT_ESTATE: unitigs_begin under the state rules of search_kmers, with its messages (a shard or any context with a communicator
+ * among them); every other call without a begin, after unitigs_end, and once the table has changed since unitigs_begin (counted
+ * into, grown, reset, delow, imported, released, any call of the graph phases): "the table changed since sdt_gpu_unitigs_begin".
+ * A clustering, a bubble list and an assembly tally stay valid across these calls, and the list across theirs.
+ * SDT_EINVAL, before any launch: NULL params; flags not 0; min_link outside 1 .. 63; max_count below max(min_count, 1) and not 0
+ * -- each with the field and its value; a range past N.  SDT_ELIMIT: 2^32 unitigs or more (the sort's indices and the ids of a
+ * link are 32-bit); a unitig of 2^32 nodes or more.
+ * Device memory: from unitigs_begin to unitigs_end 24 B + 16 B x key words per unitig, and the index that unitigs_links searches,
+ * 4 B + 8 B x key words per unitig (the reverse complements of the last words, sorted, with their ids; the first words are the
+ * list itself).  During unitigs_begin the list of start words, 8 B each in chunks of 256 (a first guess of one per 16 table slots,
+ * the exact need on a second scan when that was too small), the unitigs as they are found, one per start word at the most at
+ * 24 B + 16 B x key words, and per unitig 24 B + 8 B x key words of sort keys and order with the sort's scratch.  Only if the
+ * chains do not cover the live nodes -- the graph has a cycle without a branch -- also ONE BIT PER TABLE SLOT and a second copy of
+ * the found unitigs; every node on such a cycle then walks it until it meets a smaller key, which is quadratic in the length of
+ * one cycle in the worst case (real ones are a PhiX or a mitochondrion).  SDT_ENOMEM leaves nothing allocated.  unitigs_seqs
+ * and unitigs_links hold the offsets and the bytes they return.
+ * One lane walks one unitig, so a wavefront waits for its longest: accepted for transcripts, whose unitigs are thousands of nodes
+ * long.  Out of scope: a list-ranking formulation for genome-length unitigs (single ones of millions of nodes); a k-mer -> unitig
+ * look-up; read or mate threading; removing tips or popping bubbles; sharded contexts; tables of even K; 2^32 unitigs and more. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -1325,6 +1392,9 @@ typedef struct { uint32_t kmers, live, split, cluster, unit, verdict; } sdt_read
 #define SDT_BUBBLE_MAX_LEN (1u << 20) /* sdt_bubble_params.max_len: inner nodes of a branch at the most */
 typedef struct { uint32_t min_count, max_count, min_link, max_len, flags, reserved; } sdt_bubble_params;   /* flags, reserved: 0 */
 typedef struct { uint64_t sum_a, sum_b; uint32_t len_a, len_b, min_a, min_b, src_count, snk_count, info, reserved; } sdt_bubble;   /* 48 bytes */
+typedef struct { uint32_t min_count, max_count, min_link, flags; } sdt_unitig_params;   /* flags: 0 */
+typedef struct { uint64_t sum; uint32_t nodes, min, max, info; } sdt_unitig;   /* 24 bytes */
+typedef struct { uint32_t from, to, info, reserved; } sdt_unitig_link;   /* 16 bytes */
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -1469,6 +1539,12 @@ int sdt_gpu_bubbles_begin(sdt_ctx *ctx, const sdt_bubble_params *params, uint64_
 int sdt_gpu_bubbles_fetch(sdt_ctx *ctx, uint64_t first, uint64_t n, uint64_t *keys, sdt_bubble *rec);
 int sdt_gpu_bubbles_paths(sdt_ctx *ctx, uint64_t first, uint64_t n, uint8_t *bases, uint64_t capacity, uint64_t *offsets);
 int sdt_gpu_bubbles_end(sdt_ctx *ctx);
+int sdt_gpu_unitigs_begin(sdt_ctx *ctx, const sdt_unitig_params *params, uint64_t info[8]);
+int sdt_gpu_unitigs_fetch(sdt_ctx *ctx, uint64_t first, uint64_t n, uint64_t *keys, sdt_unitig *rec);
+int sdt_gpu_unitigs_seqs(sdt_ctx *ctx, uint64_t first, uint64_t n, uint8_t *bases, uint64_t capacity, uint64_t *offsets);
+int sdt_gpu_unitigs_links(sdt_ctx *ctx, uint64_t first, uint64_t n, sdt_unitig_link *links, uint64_t capacity,
+                          uint64_t *n_links, uint64_t *n_dangling);
+int sdt_gpu_unitigs_end(sdt_ctx *ctx);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

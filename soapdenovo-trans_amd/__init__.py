@@ -227,6 +227,11 @@ _ABI = [
     ("sdt_gpu_bubbles_fetch", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_void_p]),
     ("sdt_gpu_bubbles_paths", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
     ("sdt_gpu_bubbles_end", _c.c_int, [_c.c_void_p]),
+    ("sdt_gpu_unitigs_begin", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_unitigs_fetch", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_unitigs_seqs", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
+    ("sdt_gpu_unitigs_links", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_unitigs_end", _c.c_int, [_c.c_void_p]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -297,6 +302,10 @@ CLUSTER_WHOLE, CLUSTER_NOT_WHOLE, CLUSTER_THROUGH_MATE, CLUSTER_UNASSIGNED, CLUS
 BUBBLE_DTYPE = np.dtype([("sum_a", np.uint64), ("sum_b", np.uint64)] +
                         [(f, np.uint32) for f in ("len_a", "len_b", "min_a", "min_b", "src_count", "snk_count", "info", "reserved")])
 BUBBLE_MAX_LEN = 1 << 20                                 # SDT_BUBBLE_MAX_LEN
+# sdt_unitig (include/sdt_gpu.h): one record of 24 bytes per unitig of the counted k-mer graph; info = circular | indeg(first word) << 4 |
+# outdeg(last word) << 8.  sdt_unitig_link: 16 bytes per link; info = o | o' << 1 | base << 2 | link counter << 8
+UNITIG_DTYPE = np.dtype([("sum", np.uint64)] + [(f, np.uint32) for f in ("nodes", "min", "max", "info")])
+UNITIG_LINK_DTYPE = np.dtype([(f, np.uint32) for f in ("from", "to", "info", "reserved")])
 
 
 class NormParams(_c.Structure):
@@ -398,6 +407,14 @@ class BubbleParams(_c.Structure):
 
     def __init__(self, min_count=2, max_count=0, min_link=1, max_len=1000, flags=0, reserved=0):
         super().__init__(min_count, max_count, min_link, max_len, flags, reserved)
+
+
+class UnitigParams(_c.Structure):
+    """sdt_unitig_params; the defaults of `sdt-kmers unitigs`"""
+    _fields_ = [(f, _c.c_uint32) for f in ("min_count", "max_count", "min_link", "flags")]
+
+    def __init__(self, min_count=2, max_count=0, min_link=1, flags=0):
+        super().__init__(min_count, max_count, min_link, flags)
 
 
 class CmpRange(_c.Structure):
@@ -1444,6 +1461,62 @@ class PregraphGPU:
 
     def bubbles_end(self):
         self._check(self.lib.sdt_gpu_bubbles_end(self._ctx))
+
+    # -- the unitigs of the counted k-mer graph and their links (the rule: include/sdt_gpu.h).  Nothing is written to the table; the
+    # sorted list lives on the device from unitigs_begin to unitigs_end
+    def unitigs_begin(self, params=None):
+        """params: UnitigParams or its fields as a dict -> info uint64[8]: live nodes, start words, unitigs, circular ones, the sum of
+        their nodes (= live nodes), bytes of all sequences, longest unitig in nodes, 0"""
+        prm = params if isinstance(params, UnitigParams) else UnitigParams(**(params or {}))
+        info = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_unitigs_begin(self._ctx, ctypes.addressof(prm), _ptr(info)))
+        return info
+
+    def unitigs_fetch(self, first: int, n: int):
+        """-> (keys uint64[n, 2, key_words]: first and last word as the unitig is read; UNITIG_DTYPE[n]) of unitigs first .. first + n - 1"""
+        keys = np.zeros((n, 2, self.nw), dtype=np.uint64)
+        rec = np.zeros(n, dtype=UNITIG_DTYPE)
+        self._check(self.lib.sdt_gpu_unitigs_fetch(self._ctx, first, n, _ptr(keys) if n else None, _ptr(rec) if n else None))
+        return keys, rec
+
+    def unitigs_seqs(self, first: int, n: int, capacity: int = None):
+        """-> (bases uint8[offsets[n]]: A 0, C 1, T 2, G 3; offsets uint64[n + 1]: unitig first + i is bases[offsets[i] : offsets[i + 1]],
+        nodes + K - 1 of them).  capacity: the room to offer (default: what is needed, asked for first; SdtError SDT_EFULL when it is
+        too small: e.offsets holds the offsets)"""
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        if n == 0:
+            return np.zeros(0, dtype=np.uint8), offsets
+        if capacity is None:
+            self._check(self.lib.sdt_gpu_unitigs_seqs(self._ctx, first, n, None, 0, _ptr(offsets)))
+            capacity = int(offsets[n])
+        bases = np.zeros(max(capacity, 1), dtype=np.uint8)
+        rc = self.lib.sdt_gpu_unitigs_seqs(self._ctx, first, n, _ptr(bases), capacity, _ptr(offsets))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.offsets = offsets
+            raise e
+        return bases[: int(offsets[n])], offsets
+
+    def unitigs_links(self, first: int, n: int, capacity: int = None):
+        """-> (UNITIG_LINK_DTYPE[...]: the links that leave unitigs first .. first + n - 1, by (from, orientation, base); the link ends
+        of the range whose target begins no unitig).  capacity: the room to offer (default: what is needed, asked for first; SdtError
+        SDT_EFULL when it is too small: e.n_links holds the need)"""
+        n_links, n_dangling = _c.c_uint64(0), _c.c_uint64(0)
+        if n == 0:
+            return np.zeros(0, dtype=UNITIG_LINK_DTYPE), 0
+        if capacity is None:
+            self._check(self.lib.sdt_gpu_unitigs_links(self._ctx, first, n, None, 0, ctypes.byref(n_links), ctypes.byref(n_dangling)))
+            capacity = n_links.value
+        links = np.zeros(max(capacity, 1), dtype=UNITIG_LINK_DTYPE)
+        rc = self.lib.sdt_gpu_unitigs_links(self._ctx, first, n, _ptr(links), capacity, ctypes.byref(n_links), ctypes.byref(n_dangling))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.n_links = n_links.value
+            raise e
+        return links[: n_links.value], n_dangling.value
+
+    def unitigs_end(self):
+        self._check(self.lib.sdt_gpu_unitigs_end(self._ctx))
 
     # -- this context's counted table against another's (the rule: include/sdt_gpu.h); nothing is written to either
     def compare(self, other, rows: int = 64, cols: int = 64):

@@ -129,6 +129,15 @@
  *       prefix.bubbles: per bubble  id source sink base_a base_b len_a len_b min_a min_b sum_a sum_b link_a link_b kind
  *       prefix.bubbles.fa: the two alleles of every bubble, >id_a and >id_b
  *       and one line: bubbles: live L forks F branches B reached R bubbles N kind0 X kind1 Y kind2 Z longest M
+ *   sdt-kmers unitigs -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--max-count M, default 0 = no limit]
+ *                     [--min-link N, default 1] -o prefix
+ *       the unitigs of the counted k-mer graph and their links, the compacted graph before any cleaning (sdt_gpu_unitigs_begin,
+ *       sdt_gpu_unitigs_fetch, sdt_gpu_unitigs_seqs, sdt_gpu_unitigs_links; the rule: include/sdt_gpu.h).  No read is kept.  Ids are
+ *       1-based (unitigsplit.c, which documents the files)
+ *       prefix.unitigs: per unitig  id first last nodes bases sum mean_x100 min max in out circular
+ *       prefix.unitigs.fa: >id nodes=.. sum=.. min=.. max=.. circular=.. and the sequence on one line
+ *       prefix.unitigs.gfa: GFA 1: H, an S line per unitig (LN:i: bases, KC:i: sum), an L line per link, written once (lc:i: its counter)
+ *       and one line: unitigs: live L unitigs N circular C isolated I dead_ends D links E bases B longest M n50 X
  *
  * The query file is read and checked before the device is touched.
  *
@@ -160,6 +169,7 @@
 #include "cmpsplit.h"
 #include "clustersplit.h"
 #include "bubblesplit.h"
+#include "unitigsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -363,6 +373,16 @@ static void usage(void)
 	        "              len_a = len_b = K, 1: other equal lengths, 2: unequal), prefix.bubbles.fa (>id_a len=.. min=.. sum=.. and the\n"
 	        "              allele from source to sink, then the same for b); ids from 1 in ascending order of (source, base_a, base_b)\n"
 	        "           and one line: bubbles: live L forks F branches B reached R bubbles N kind0 X kind1 Y kind2 Z longest M\n"
+	        "       sdt-kmers unitigs -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--max-count M, default 0]\n"
+	        "                         [--min-link N, default 1] -o prefix\n"
+	        "           the unitigs of the counted k-mer graph and their links: the maximal paths without a branch, the compacted graph\n"
+	        "           before any cleaning.  Live nodes and links as for cluster.\n"
+	        "           -> prefix.unitigs (per unitig: id first last nodes bases sum mean_x100 min max in out circular; first and last are\n"
+	        "              k-mers in letters as the unitig is read, bases = nodes + K - 1, sum min max and the mean (x 100, a floor) are over\n"
+	        "              the counts of its nodes, in and out the degrees at its ends), prefix.unitigs.fa (>id nodes=.. sum=.. min=.. max=..\n"
+	        "              circular=.. and the sequence), prefix.unitigs.gfa (GFA 1: S id seq LN:i:bases KC:i:sum; L from +/- to +/- <K-1>M\n"
+	        "              lc:i:link, every link once); ids from 1 in ascending order of the first k-mer\n"
+	        "           and one line: unitigs: live L unitigs N circular C isolated I dead_ends D links E bases B longest M n50 X\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -1521,8 +1541,67 @@ static int run_bubbles(sdt_ctx *gpu, unsigned long long reads, options *opt, con
 	return 0;
 }
 
+/* ---- unitigs ----------------------------------------------------------------------------------------------------------------------------- */
+/* `unitigs`: the list on the device, then fetched and written a piece at a time with the sequences of that piece, then the links of
+ * every piece behind the S lines (unitigsplit.c) */
+static int run_unitigs(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	(void)reads; (void)pairs;
+	enum { PIECE = 1 << 16 };
+	const sdt_unitig_params prm = {(uint32_t)opt->min_count, opt->cluster.max_count, opt->cluster.min_link, 0};
+	uint64_t info[8], cap = 0, link_cap = 0;
+	if (SDT_CALL(sdt_gpu_unitigs_begin, gpu, &prm, info)) return 1;
+	const int nw = sdt_gpu_key_words(gpu);
+	uint64_t *keys = (uint64_t *)malloc((size_t)PIECE * 2 * (size_t)nw * sizeof *keys), *offs = (uint64_t *)malloc(((size_t)PIECE + 1) * sizeof *offs);
+	sdt_unitig *rec = (sdt_unitig *)malloc((size_t)PIECE * sizeof *rec);
+	sdt_unitig_tally tally = {0, 0, 0, 0, (uint32_t *)malloc((size_t)(info[2] ? info[2] : 1) * sizeof(uint32_t))};
+	uint8_t *bases = NULL;
+	sdt_unitig_link *links = NULL;
+	if (!keys || !offs || !rec || !tally.nodes) { fprintf(stderr, "sdt-kmers: out of memory for the unitigs\n"); return 1; }
+	char path[4200], fa_path[4200], gfa_path[4200], line[SDT_UNITIG_SUMMARY_MAX];
+	FILE *f = stats_open(path, opt->outname, ".unitigs");
+	if (!f) return cannot_write(path);
+	FILE *fa = stats_open(fa_path, opt->outname, ".unitigs.fa");
+	if (!fa) return cannot_write(fa_path);
+	FILE *gfa = stats_open(gfa_path, opt->outname, ".unitigs.gfa");
+	if (!gfa || sdt_unitig_gfa_header(gfa) != 0) return cannot_write(gfa_path);
+	for (uint64_t first = 0; first < info[2]; first += PIECE) {
+		const uint64_t n = info[2] - first < PIECE ? info[2] - first : PIECE;
+		if (SDT_CALL(sdt_gpu_unitigs_fetch, gpu, first, n, keys, rec) || SDT_CALL(sdt_gpu_unitigs_seqs, gpu, first, n, NULL, 0, offs)) return 1;
+		if (offs[n] > cap) {
+			free(bases);
+			cap = offs[n];
+			if (!(bases = (uint8_t *)malloc(cap))) { fprintf(stderr, "sdt-kmers: out of memory for %llu bases of unitigs\n", (unsigned long long)cap); return 1; }
+		}
+		if (SDT_CALL(sdt_gpu_unitigs_seqs, gpu, first, n, bases, cap, offs)) return 1;
+		if (sdt_unitig_list_write(f, keys, rec, first, n, nw, opt->K, &tally) != 0) return cannot_write(path);
+		if (sdt_unitig_fasta_write(fa, rec, bases, offs, first, n) != 0) return cannot_write(fa_path);
+		if (sdt_unitig_gfa_segments(gfa, rec, bases, offs, first, n) != 0) return cannot_write(gfa_path);
+	}
+	for (uint64_t first = 0; first < info[2]; first += PIECE) {
+		const uint64_t n = info[2] - first < PIECE ? info[2] - first : PIECE;
+		uint64_t n_links = 0, n_dangling = 0;
+		if (SDT_CALL(sdt_gpu_unitigs_links, gpu, first, n, NULL, 0, &n_links, &n_dangling)) return 1;
+		if (n_links > link_cap) {
+			free(links);
+			link_cap = n_links;
+			if (!(links = (sdt_unitig_link *)malloc((size_t)link_cap * sizeof *links))) { fprintf(stderr, "sdt-kmers: out of memory for %llu links\n", (unsigned long long)link_cap); return 1; }
+		}
+		if (n_links && SDT_CALL(sdt_gpu_unitigs_links, gpu, first, n, links, link_cap, &n_links, &n_dangling)) return 1;
+		if (sdt_unitig_gfa_links(gfa, links, n_links, opt->K, &tally) != 0) return cannot_write(gfa_path);
+	}
+	if (fclose(f) != 0) return cannot_write(path);
+	if (fclose(fa) != 0) return cannot_write(fa_path);
+	if (fclose(gfa) != 0) return cannot_write(gfa_path);
+	if (SDT_CALL(sdt_gpu_unitigs_end, gpu)) return 1;
+	sdt_unitig_summary(line, info, &tally, opt->K);
+	fputs(line, stdout);
+	free(keys); free(offs); free(rec); free(bases); free(links); free(tally.nodes);
+	return 0;
+}
+
 /* ---- the command line ------------------------------------------------------------------------------------------------------------------ */
-enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, COMPARE, CLUSTER, BUBBLES, N_SUBCOMMANDS };
+enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, COMPARE, CLUSTER, BUBBLES, UNITIGS, N_SUBCOMMANDS };
 
 static const struct {
 	const char *name;
@@ -1541,6 +1620,7 @@ static const struct {
 	[COMPARE] = {"compare", 0, 0, 2, NULL},                 /* (counts two sets of libraries into two contexts: run_compare, from main) */
 	[CLUSTER] = {"cluster", 1, 1, 2, run_cluster},
 	[BUBBLES] = {"bubbles", 0, 0, 2, run_bubbles},
+	[UNITIGS] = {"unitigs", 0, 0, 2, run_unitigs},
 };
 
 enum { O_MAX_K = 1000, O_DEVICE, O_TARGET, O_MAX_CV, O_SEED, O_MIN_COV, O_MIN_LEN, O_CORRECT, O_MATE_SWAP, O_TAIL3, O_TAIL5, O_MIN_OVERLAP, O_ERROR_PCT,
@@ -1571,7 +1651,8 @@ static const struct { int code; const char *name; unsigned owners; const char *b
 	{O_ASSEMBLY, "--assembly", BIT(EVALUATE), "evaluate", 0}, {O_ROWS, "--rows", BIT(EVALUATE) | BIT(COMPARE), "evaluate", SDT_CMP_MAX_CELLS / 2},
 	{O_AGAINST, "--against", BIT(COMPARE), "compare", 0}, {O_COLS, "--cols", BIT(COMPARE), "compare", SDT_CMP_MAX_CELLS / 2},
 	{O_SELECT, "--select", BIT(COMPARE), "compare", 0}, {O_MAX_LIST, "--max-list", BIT(COMPARE), "compare", 1ULL << 31},
-	{O_MAX_COUNT, "--max-count", BIT(CLUSTER) | BIT(BUBBLES), "cluster", UINT32_MAX}, {O_MIN_LINK, "--min-link", BIT(CLUSTER) | BIT(BUBBLES), "cluster", 63},
+	{O_MAX_COUNT, "--max-count", BIT(CLUSTER) | BIT(BUBBLES) | BIT(UNITIGS), "cluster", UINT32_MAX},
+	{O_MIN_LINK, "--min-link", BIT(CLUSTER) | BIT(BUBBLES) | BIT(UNITIGS), "cluster", 63},
 	{O_PICK, "--pick", BIT(CLUSTER), "cluster", 0}, {O_MAX_BRANCH, "--max-branch", BIT(BUBBLES), "bubbles", SDT_BUBBLE_MAX_LEN},
 };
 
@@ -1763,7 +1844,7 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 		fprintf(stderr, "sdt-kmers: --max-merged %u is below --min-merged %u: no pair could merge (0: no limit)\n", opt->merge.max_len, opt->merge.min_len);
 		return 255;
 	}
-	if ((sub == CLUSTER || sub == BUBBLES) && opt->cluster.max_count != 0 && opt->cluster.max_count < (opt->min_count > 1 ? opt->min_count : 1ul)) {
+	if ((sub == CLUSTER || sub == BUBBLES || sub == UNITIGS) && opt->cluster.max_count != 0 && opt->cluster.max_count < (opt->min_count > 1 ? opt->min_count : 1ul)) {
 		fprintf(stderr, "sdt-kmers: --max-count %u is below -c %lu: no node could be live (0: no limit)\n", opt->cluster.max_count, opt->min_count);
 		return 255;
 	}

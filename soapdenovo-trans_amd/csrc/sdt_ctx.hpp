@@ -216,6 +216,19 @@ struct sdt_ctx {
 		uint32_t min_count = 0, max_count = 0, min_link = 0, max_len = 0;    // the rule of that begin (min_count: already max(min_count, 1))
 		bool open = false, stale = false;
 	} bb;
+	// the unitig list (sdt_unitig.hip): the records and their two words each, sorted by the first word, and the second order by the
+	// reverse complement of the last word that unitigs_links searches, on the device from unitigs_begin to unitigs_end / destroy; nothing
+	// per table slot.  unitigs_seqs and unitigs_links read the table again, so the list goes stale where the bubble list does
+	struct Unitigs {
+		uint64_t *keys = nullptr;          // n x 2 nw words: x0, then the last word
+		void *rec = nullptr;               // n records of 24 bytes
+		uint64_t *idx_keys = nullptr;      // n x nw words: revcomp(last), ascending
+		uint32_t *idx_id = nullptr;        // ... and the unitig of each
+		uint64_t n = 0;
+		uint64_t slots = 0;                // the table's slots at unitigs_begin
+		uint32_t min_count = 0, max_count = 0, min_link = 0;    // the rule of that begin (min_count: already max(min_count, 1))
+		bool open = false, stale = false;
+	} ug;
 	// timing
 	std::vector<EventPair> ev;
 	size_t ev_used = 0;
@@ -253,14 +266,15 @@ inline uint64_t wave_blocks_forced()
 
 
 // the table is about to change (nodes counted, moved or replaced): what sdt_search.hip derived from it is stale, and so is the
-// assembly tally of sdt_asm.hip and the clustering of sdt_cluster.hip, which are kept by slot, and the bubble list of sdt_bubble.hip,
-// whose paths are walked in the table again
+// assembly tally of sdt_asm.hip and the clustering of sdt_cluster.hip, which are kept by slot, and the bubble list of sdt_bubble.hip
+// and the unitig list of sdt_unitig.hip, whose paths are walked in the table again
 inline void search_cache_drop(sdt_ctx *c)
 {
 	c->hi_mode = -1;
 	c->asmt.stale = true;
 	c->cl.stale = true;
 	c->bb.stale = true;
+	c->ug.stale = true;
 }
 
 inline int env_int(const char *name, int dflt) { const char *v = getenv(name); return v && *v ? atoi(v) : dflt; }

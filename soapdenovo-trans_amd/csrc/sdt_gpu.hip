@@ -380,6 +380,10 @@ int sdt_gpu_destroy(sdt_ctx *c)
 	if (c->cl.label) (void)hipFree(c->cl.label);
 	if (c->bb.keys) (void)hipFree(c->bb.keys);
 	if (c->bb.rec) (void)hipFree(c->bb.rec);
+	if (c->ug.keys) (void)hipFree(c->ug.keys);
+	if (c->ug.rec) (void)hipFree(c->ug.rec);
+	if (c->ug.idx_keys) (void)hipFree(c->ug.idx_keys);
+	if (c->ug.idx_id) (void)hipFree(c->ug.idx_id);
 	for (int i = 0; i < 5; i++) if (c->ab[i]) (void)hipFree(c->ab[i]);
 	sk_free(c);
 	shard_free(c);
@@ -834,6 +838,7 @@ int sdt_gpu_delow(sdt_ctx *c, int d, uint64_t *removed)
 	{ const int rcd = drain_staged(c, true); if (rcd != SDT_OK) return rcd; }
 	c->cl.stale = true;          // (deleted flags decide which nodes a clustering of sdt_cluster.hip holds; counts and slots stay: nothing else is stale)
 	c->bb.stale = true;          // (... and which nodes the bubbles of sdt_bubble.hip walk)
+	c->ug.stale = true;          // (... and the unitigs of sdt_unitig.hip)
 	HIPCHK(hipMemsetAsync(&c->d_stats->scratch, 0, sizeof(unsigned long long), c->stream));
 	const int g = scan_grid(c, view_slots(c));
 	if (c->nw == 1) hipLaunchKernelGGL(k_delow<1>, dim3(g), dim3(TPB), 0, c->stream, table_of<1>(c), (uint32_t)d, c->d_stats);
@@ -1063,6 +1068,7 @@ static int graph_enter(sdt_ctx *c)
 	SDT_ENTER(c);
 	c->cl.stale = true;          // (the graph phases may set deleted flags and cut links: a clustering of sdt_cluster.hip is by the state it was begun on)
 	c->bb.stale = true;          // (... and so is the bubble list of sdt_bubble.hip)
+	c->ug.stale = true;          // (... and the unitig list of sdt_unitig.hip)
 	return SDT_OK;
 }
 
