@@ -90,6 +90,11 @@ CASES = [
     # nothing longer can have a reference golden.  Transcripts of at least 1 000 bases (tx_lo), so that no read is cut short.
     dict(name="se1000_k31_p4", variant=31, K=31, p=4, d=0, n=250, L=1000, T=5, kind="se", tx_lo=1000),
     dict(name="se1000_k63_p3_127mer", variant=127, K=63, p=3, d=0, n=250, L=1000, T=5, kind="se", tx_lo=1000),
+    # the first K of each key width: the top base of a K-mer sits at bit 0 of a key word, so the highest word in use holds
+    # 2 bits, and at K = 97 w[0] of a 4-word key is non-zero for the first time
+    dict(name="se100_k33_p4_63mer", variant=63, K=33, p=4, d=0, n=1500, L=100, T=20, kind="se"),
+    dict(name="se150_k65_p3_127mer", variant=127, K=65, p=3, d=0, n=1500, L=150, T=20, kind="se"),
+    dict(name="se200_k97_p5_127mer_d1", variant=127, K=97, p=5, d=1, n=1500, L=200, T=20, kind="se"),
 ]
 
 

@@ -38,7 +38,7 @@ def check(pkg, synth, g, case, min_count, rows, what):
 
 
 # ---- 1. records, totals and matrix equal the model -----------------------------------------------------------------------------------
-@pytest.mark.parametrize("K,flags", [(23, 0), (24, 0), (31, 1), (31, 2), (47, 0), (63, 0), (95, 0), (127, 0)])
+@pytest.mark.parametrize("K,flags", [(23, 0), (24, 0), (31, 1), (31, 2), (47, 0), (63, 0), (95, 0), (127, 0), (33, 0), (65, 0), (97, 0)])
 def test_records_totals_and_matrix_equal_the_model(pkg, synth, K, flags):
     """1, 2 and 4 key words, both pass-1 kernel families at K = 31 (SDT_FLAG_DIRECT, SDT_FLAG_PARTITION).  K = 24: the library takes odd
     K only (sdt_gpu_init refuses an even one before any table exists), so the one thing an even K adds to the rule -- a palindrome is

@@ -41,7 +41,7 @@ def raises(pkg, code, call, *words):
 
 
 # ---- 1. the model, per key width ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K,flags", [(23, 0), (31, 1), (31, 2), (47, 0), (63, 0), (95, 0), (127, 0)])
+@pytest.mark.parametrize("K,flags", [(23, 0), (31, 1), (31, 2), (47, 0), (63, 0), (95, 0), (127, 0), (33, 0), (65, 0), (97, 0)])
 def test_bubbles_equal_the_model(pkg, synth, K, flags):
     """1, 2 and 4 key words, both pass-1 kernel families at K = 31; min_count 2 and 1, max_len at the longest side and one below"""
     case = bu.built_case(K)

@@ -42,7 +42,7 @@ def test_header_library_and_binding_agree(pkg):
 
 
 # ---- the restatement on its cases ----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K", [23, 24, 31, 47, 63, 95])
+@pytest.mark.parametrize("K", [23, 24, 31, 47, 63, 95, 33, 65, 97])
 def test_the_cases_hold_what_they_are_built_for(K):
     """the builder asserts every property on the model (bubble_util.built_case): a case that lost one fails here.  Also: the list is the
     same after every read was reverse-complemented; every reported bubble has s <= revcomp(t), and its mirror is found and dropped"""

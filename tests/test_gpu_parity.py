@@ -63,7 +63,7 @@ def test_golden_case_kmerfreq_bit_identical(pkg, name, mode):
 
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("K,L,ragged", [(13, 60, True), (23, 100, False), (23, 150, True), (31, 150, True), (31, 158, False), (31, 250, True), (21, 250, True), (33, 150, True),
-                                        (63, 250, False), (65, 200, True), (127, 250, True),
+                                        (63, 250, False), (65, 200, True), (97, 250, True), (127, 250, True),
                                         # reads of more than 256 k-mers leave the one-lane-per-read scatter for the strip kernel: its strips
                                         # (window <= 49 m-mers) with 1-word keys, its sparse table of window minima (longer windows) with 2- and 4-word keys
                                         (31, 330, True), (63, 400, True), (95, 420, False)])
@@ -263,7 +263,7 @@ def test_device_resident_batch_and_properties(pkg, synth, mode):
 
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("K,stride,base", [(21, 1, 0), (35, 2, 1), (71, 2, 0)])
+@pytest.mark.parametrize("K,stride,base", [(21, 1, 0), (35, 2, 1), (71, 2, 0), (33, 1, 0), (65, 2, 1), (97, 2, 0)])
 def test_first_occurrence_ordinals(pkg, synth, K, stride, base, mode):
     """SDT_FLAG_TRACK_FIRST: per node, the smallest (read ordinal << 16 | position) over its occurrences --
     the order the reference's table layout is a function of"""
@@ -328,7 +328,7 @@ def test_async_and_fixed_length_pushes_equal_one_push(pkg, synth, K, L, mode):
             assert table(g) == want, f"fixed={fixed}"
 
 
-@pytest.mark.parametrize("K", [63, 127])
+@pytest.mark.parametrize("K", [63, 97, 127])
 def test_wide_key_publication_stress(pkg, synth, K):
     """multi-word keys are claimed with a CAS on the first word and published without a release fence
     (csrc/sdt_table.cuh): a lost or duplicated node would change the node count / histogram.  ~100 M occurrences,
@@ -354,7 +354,7 @@ def test_wide_key_publication_stress(pkg, synth, K):
 
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("K", [95, 127])
+@pytest.mark.parametrize("K", [95, 97, 127])
 def test_wide_key_poly_g_tails(pkg, synth, K, mode):
     """4-word keys whose LOW words are all ones (64+ trailing G's, the NextSeq poly-G tail) equal the cleared-slot
     sentinel in key[2..3]: the plain-load fast path must not take a half-published entry for them (csrc/sdt_table.cuh).
@@ -450,7 +450,7 @@ def py_tip_walks(keys_int, l, rf, cnt, K, thin, cut_len):
     return out
 
 
-@pytest.mark.parametrize("K,L", [(21, 100), (31, 100), (41, 150), (63, 150), (75, 200), (127, 250)])
+@pytest.mark.parametrize("K,L", [(21, 100), (31, 100), (41, 150), (63, 150), (75, 200), (127, 250), (33, 120), (65, 200), (97, 250)])
 def test_tip_walks_equal_reference_walk(pkg, synth, K, L):
     """the device dry run of removeSingleTips / removeMinorTips: every node's walk == the restated walk, on the
     table as counted and again after the host 'writes' nodes (update_nodes: deletions, cleared linear flags,
@@ -765,7 +765,7 @@ def py_minor_out_dry(keys_int, l, rf, cnt, K, threshold):
     return junc, need, nbrs
 
 
-@pytest.mark.parametrize("K,L", [(21, 100), (31, 150), (47, 150), (75, 200)])
+@pytest.mark.parametrize("K,L", [(21, 100), (31, 150), (47, 150), (75, 200), (33, 120), (65, 200), (97, 250)])
 def test_minor_out_dry_run_equals_reference_rule(pkg, synth, K, L):
     """the device dry run of removeMinorOut: the set of junctions that would cut, the neighbours to cut, and the
     neighbour tables of both == the restated rule, on an arbitrary host order"""
@@ -845,7 +845,7 @@ def py_edge_ports(keys_int, l, rf, K):
     return out
 
 
-@pytest.mark.parametrize("K,L", [(21, 100), (31, 120), (47, 150), (75, 200)])
+@pytest.mark.parametrize("K,L", [(21, 100), (31, 120), (47, 150), (75, 200), (33, 120), (65, 200), (97, 250)])
 def test_edge_port_walks_equal_reference_rule(pkg, synth, K, L):
     """the device dry run of kmer2edges: every port of every non-linear node -- far node, arrival port, length and
     the palindrome flag (decided from 4 k-mers on the device, from the whole list here); reads that spell X + rc(X)
@@ -898,7 +898,7 @@ def test_edge_port_walks_equal_reference_rule(pkg, synth, K, L):
         assert palins > 0
 
 
-@pytest.mark.parametrize("K,L", [(21, 90), (45, 160), (81, 300)])
+@pytest.mark.parametrize("K,L", [(21, 90), (45, 160), (81, 300), (33, 120), (65, 200), (97, 250)])
 def test_map_stage_randomised_vs_oracle(pkg, synth, K, L):
     """random contigs that share stretches (repeated k-mers = 'deleted'), reads that hop between contigs and
     strands, reads shorter than K+1, lengths that need several 64-k-mer rounds per wavefront; 1-, 2- and 4-word keys"""
@@ -936,6 +936,16 @@ def test_map_stage_randomised_vs_oracle(pkg, synth, K, L):
         flips = rng.random(len(r)) < 0.01
         r[flips] = (r[flips] + 1) & 3
         reads.append(r)
+    # reads across a junction: the end of one contig, then the start of another on either strand, L / 2 bases (more than K) of each.
+    # The pieces above are too short to give a read two hits once K nears L / 2 (none of the 600 has two at K = 97, L = 250).  A
+    # generator of their own, so that the 600 reads above and their align_len are what they were before these were added
+    rng2 = np.random.default_rng(K * 11 + L)
+    for _ in range(40):
+        a, b = rng2.choice(nctg, size=2, replace=False)
+        tail, head = ctgs[a][-(L // 2):], ctgs[b][:L - L // 2]
+        if rng2.random() < 0.5:
+            head = (head[::-1] ^ 2).astype(np.uint8)
+        reads.append(np.concatenate([tail, head]))
     roffs = np.zeros(len(reads) + 1, dtype=np.uint64)
     roffs[1:] = np.cumsum([len(r) for r in reads])
     rcodes = np.concatenate(reads)
@@ -946,7 +956,7 @@ def test_map_stage_randomised_vs_oracle(pkg, synth, K, L):
         g.set_contig_table(length, twin)
         kmers, nodes = g.finish_count()
         assert (nodes, kmers) == o.counts()
-        al = rng.integers(K, K + 40, size=len(reads)).astype(np.int32)
+        al = np.concatenate([rng.integers(K, K + 40, size=600), rng2.integers(K, K + 40, size=40)]).astype(np.int32)
         info_w, hits = g.align_reads(synth.pack_2bit(rcodes), roffs, align_len=al)
         multi = 0
         for r in range(len(reads)):
@@ -1040,7 +1050,8 @@ def _uf_labels(n, edges):
     return [find(i) for i in range(n)]
 
 
-@pytest.mark.parametrize("K,L,variant,p", [(23, 100, 1, 8), (31, 150, 1, 3), (31, 150, 2, 16), (47, 150, 2, 5), (75, 200, 4, 8), (25, 100, 4, 1)])
+@pytest.mark.parametrize("K,L,variant,p", [(23, 100, 1, 8), (31, 150, 1, 3), (31, 150, 2, 16), (47, 150, 2, 5), (75, 200, 4, 8), (25, 100, 4, 1),
+                                           (33, 120, 2, 4), (65, 200, 4, 3), (97, 250, 4, 5)])
 def test_layout_on_device_sorts_by_set_and_first_occurrence(pkg, synth, K, L, variant, p):
     """sdt_gpu_layout_sorted_keys: the nodes grouped by hash_kmer % p (the oracle's pinned restatement of hashFunction.c:83-122,
     over the bytes of the emulated variant's Kmer) and ordered by first occurrence inside a set; layout_apply + export_ordered:
@@ -1085,7 +1096,7 @@ def test_layout_on_device_sorts_by_set_and_first_occurrence(pkg, synth, K, L, va
         assert (k4 == k2).all() and (l4 == l3).all() and ((r4 & 0x3FFFFFF) == (r3 & 0x3FFFFFF)).all() and (c4 == c2).all()
 
 
-@pytest.mark.parametrize("K,L", [(21, 100), (31, 150), (63, 150), (75, 200)])
+@pytest.mark.parametrize("K,L", [(21, 100), (31, 150), (63, 150), (75, 200), (33, 120), (65, 200), (97, 250)])
 def test_labelled_walks_and_their_components(pkg, synth, K, L):
     """sdt_gpu_tip_walks_labelled: the walks of tip_walks_compact, each with the component of its node -- removeSingleTips: the
     connected components of (tip, end node); removeMinorTips: of the non-linear nodes joined by chains of <= cut_len linear
@@ -1122,7 +1133,7 @@ def test_labelled_walks_and_their_components(pkg, synth, K, L):
                 assert len(set(labs)) < len(labs), "some component holds more than one walk"
 
 
-@pytest.mark.parametrize("K,L", [(21, 100), (31, 150), (47, 150)])
+@pytest.mark.parametrize("K,L", [(21, 100), (31, 150), (47, 150), (33, 120), (65, 200), (97, 250)])
 def test_labelled_junction_records_and_their_components(pkg, synth, K, L):
     """sdt_gpu_minor_out_labelled: the records of minor_out_dry with the component of their node (every record's node united
     with its eight neighbours), the junction records sorted by (label, node)"""
@@ -1220,7 +1231,8 @@ def py_minor_out_commit(rec, nj, keys_int, l, rf, K, thr):
     return ll, rr, lin, dele, off, marked, touched
 
 
-@pytest.mark.parametrize("K,L,thr", [(21, 100, 0.05), (31, 150, 0.3), (31, 150, 0.05), (47, 150, 0.3), (75, 200, 0.2)])
+@pytest.mark.parametrize("K,L,thr", [(21, 100, 0.05), (31, 150, 0.3), (31, 150, 0.05), (47, 150, 0.3), (75, 200, 0.2),
+                                     (33, 120, 0.3), (65, 200, 0.2), (97, 250, 0.2)])
 def test_minor_out_commit_on_the_device_equals_the_sequential_commit(pkg, synth, K, L, thr):
     """sdt_gpu_minor_out_commit (one lane per component, the visits of a component in record order) against the sequential sweep over
     the junctions in node order: kmers off, newly linear nodes, the set of written nodes, and every node's links and flags afterwards"""
@@ -1344,7 +1356,7 @@ def py_build_edges(keys_int, l, rf, cnt, K):
     return edges, num_ed, stamp
 
 
-@pytest.mark.parametrize("K,L,p", [(21, 100, 8), (31, 120, 3), (47, 150, 16), (75, 200, 5)])
+@pytest.mark.parametrize("K,L,p", [(21, 100, 8), (31, 120, 3), (47, 150, 16), (75, 200, 5), (33, 120, 4), (65, 200, 3), (97, 250, 5)])
 def test_edges_built_on_the_device_equal_the_sequential_rule(pkg, synth, K, L, p):
     """sdt_gpu_build_edges: edge records in id order (length, bal_edge, cvg with the palindrome quirk, id, end k-mers), the bases
     of every edge and the number of ids == kmer2edges restated sequentially over the nodes in the order the host asked for;
@@ -1409,7 +1421,8 @@ def test_read_ordinals_continue_from_device_batches_into_pushed_ones(pkg, synth,
 
 
 @pytest.mark.parametrize("K,L,variant,p,small,n_reads", [(23, 100, 1, 8, False, 6000), (31, 150, 1, 1, False, 20000), (31, 150, 2, 3, True, 8000),
-                                                         (47, 150, 2, 5, False, 6000), (75, 200, 4, 2, True, 5000), (31, 100, 4, 16, False, 30000)])
+                                                         (47, 150, 2, 5, False, 6000), (75, 200, 4, 2, True, 5000), (31, 100, 4, 16, False, 30000),
+                                                         (33, 120, 2, 4, True, 6000), (65, 200, 4, 3, False, 5000), (97, 250, 4, 5, True, 5000)])
 def test_layout_replay_on_the_device_equals_the_reference_table(pkg, synth, K, L, variant, p, small, n_reads):
     """sdt_gpu_layout_on_device: the visiting order it numbers the nodes in == the slot order of the oracle's KmerSet (pinned to
     the reference's newhash.c by the unit vectors: growth sizes and final slots) after the set's distinct keys went in in

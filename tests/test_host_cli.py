@@ -235,9 +235,13 @@ def test_cli_multi_process_all_files_identical(pkg, tmp_path, name, gpus, second
                                                        # pipeline takes, and the longest read pass 1 counts at all (include/sdt_gpu.h:
                                                        # SDT_PASS1_MAX_READ_LEN).  The reference itself does not survive such reads: these
                                                        # rows have the oracle only
-                                                       (31, 4, 0, 2000, 31, 12, 1), (63, 3, 0, 4059, 63, 13, 1)])
+                                                       (31, 4, 0, 2000, 31, 12, 1), (63, 3, 0, 4059, 63, 13, 1),
+                                                       # the first K of each key width (the top base of a K-mer at bit 0 of a key word; at 97
+                                                       # w[0] of a 4-word key is non-zero for the first time): one GPU, the pipeline forced, sharded
+                                                       (33, 4, 1, 120, 63, 14, 1), (65, 3, 0, 200, 127, 15, 1), (97, 5, 0, 250, 127, 16, 0),
+                                                       (65, 2, 0, 200, 127, 17, 2), (97, 3, 2, 250, 127, 18, 1)])
 def test_cli_against_oracle_on_fresh_inputs(pkg, synth, tmp_path, K, p, d, L, variant, seed, gpus):
-    """beyond the 12 fixtures: seeded synthetic reads (ragged, with errors, a few hairpins) through `sdt-pregraph` on the GPU
+    """beyond the 17 fixtures: seeded synthetic reads (ragged, with errors, a few hairpins) through `sdt-pregraph` on the GPU
     (two configurations with 2 and 3 ranks, bucket sharded; gpus = 0: one GPU with the locality pipeline forced) and through the C oracle's restatement of the WHOLE of pregraph (pass 1, -d, the three cleaning passes, kmer2edges, the
     second read pass) -- the oracle is pinned file by file against the reference on the fixtures
     (tests/test_oracle_vs_reference.py), so agreement here is agreement with the reference on inputs it never saw"""

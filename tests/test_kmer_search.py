@@ -53,7 +53,7 @@ def revcomp_int(v, K):
 
 def test_revcomp_helper_is_an_involution_and_matches_the_definition():
     rng = np.random.default_rng(1)
-    for K in (13, 21, 31, 33, 63, 95, 127):
+    for K in (13, 21, 31, 33, 63, 65, 95, 97, 127):
         bases = rng.integers(0, 4, size=K).tolist()
         v = 0
         for c in bases:
@@ -175,7 +175,7 @@ def check_search(g, K, nodes, seed):
 
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("K,L", [(13, 60), (31, 150), (33, 150), (63, 250), (95, 420), (127, 250)])
+@pytest.mark.parametrize("K,L", [(13, 60), (31, 150), (33, 150), (63, 250), (65, 200), (95, 420), (97, 250), (127, 250)])
 def test_search_equals_oracle(pkg, synth, K, L, mode):
     """every oracle node as stored, the reverse complement of every node, k-mers verified to be absent, one query 200 times; batches of
     0, 1, 63, 65 and all; count, l_links, r_links and the linear / deleted / single bits -- and once more after delow(2) + mark"""
@@ -226,7 +226,7 @@ def test_search_device_form_equals_host_form(pkg, synth):
 
 
 # ---- 3. profile equals numpy ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K", [21, 31, 63, 95])
+@pytest.mark.parametrize("K", [21, 31, 63, 95, 65, 97])
 def test_profile_equals_numpy(pkg, synth, K):
     """ragged reads of the counted workload, hand-made reads of K - 1, K and K + 1 bases and of more than 256 k-mers, reads of another
     seed that hold k-mers the table does not have; min_count 0, 1, 2, 50; all six fields of every read"""
@@ -269,7 +269,7 @@ def test_profile_equals_numpy(pkg, synth, K):
 
 
 @pytest.mark.parametrize("aux_form", ["", "hash", "aux"])
-@pytest.mark.parametrize("K", [21, 31, 63, 95])
+@pytest.mark.parametrize("K", [21, 31, 63, 95, 65, 97])
 def test_profile_counts_past_65535(pkg, synth, monkeypatch, K, aux_form):
     """1 000 poly-A reads: one node counted tens of thousands of times, so min, median and max of those reads need the high half of
     the count -- through the small hash of such nodes (the default), and through aux itself (test hook)"""

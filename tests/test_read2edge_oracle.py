@@ -10,7 +10,7 @@ import oracle_binding as ob
 import read2edge_util as ru
 
 
-@pytest.mark.parametrize("K", [25, 45, 127])
+@pytest.mark.parametrize("K", [25, 45, 127, 33, 97])
 def test_setters_reproduce_a_natural_state(synth, tmp_path, K):
     L, d = (250 if K > 90 else 100), 1
     # isoforms that share exons: junction vertices, short edges, (K+1)-mer patches and arcs in number, which transcripts of
@@ -82,7 +82,7 @@ def test_canonical_kplus1_has_the_128mer_quirk():
     assert key == (0, 0, 0, min(v, rc)) and ps == (v < rc)
 
 
-@pytest.mark.parametrize("K,L,E", [(21, 100, 6), (63, 250, 5000), (127, 250, 6)])
+@pytest.mark.parametrize("K,L,E", [(21, 100, 6), (63, 250, 5000), (127, 250, 6), (33, 100, 5000), (97, 250, 6)])
 def test_python_walk_pairs_kmers_as_the_oracle_does(synth, tmp_path, K, L, E):
     s = ru.Scenario(synth, tmp_path, K, L, E, seed=1000 + K, n_reads=1200)
     assert s.walk_arcs == s.arcs

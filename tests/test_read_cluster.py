@@ -57,7 +57,7 @@ def check_all(pkg, synth, g, case, name, what):
 
 
 # ---- 1. the model, per key width ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K,flags", [(23, 0), (31, 1), (31, 2), (47, 0), (63, 0), (95, 0), (127, 0)])
+@pytest.mark.parametrize("K,flags", [(23, 0), (31, 1), (31, 2), (47, 0), (63, 0), (95, 0), (127, 0), (33, 0), (65, 0), (97, 0)])
 def test_clustering_equals_the_model(pkg, synth, K, flags):
     """1, 2 and 4 key words, both pass-1 kernel families at K = 31; the four parameter sets the case is built around"""
     case = cu.built_case(K)

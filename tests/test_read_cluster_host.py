@@ -188,7 +188,7 @@ def test_symmetries_on_the_model():
     assert (base.records(shuffled, paired=True)[0] == rec.reshape(-1, 2)[perm].reshape(-1)).all()
 
 
-@pytest.mark.parametrize("K", [23, 31, 47, 63, 95, 127])
+@pytest.mark.parametrize("K", [23, 31, 47, 63, 95, 127, 33, 65, 97])
 def test_the_cases_hold_what_they_are_built_for(K):
     """the builder asserts every property on the model (read_cluster_util.built_case): a case that lost one fails here"""
     case = cu.built_case(K)

@@ -117,7 +117,7 @@ def assert_outputs(pkg, synth, got, want, codes, offs, what):
 
 
 # ---- 1. the rule ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K,mode", [(21, 0), (31, 1), (31, 2), (33, 0), (63, 0), (95, 0)])
+@pytest.mark.parametrize("K,mode", [(21, 0), (31, 1), (31, 2), (33, 0), (63, 0), (95, 0), (65, 0), (97, 0)])
 def test_correct_equals_the_rule(pkg, synth, K, mode):
     """6 000 ragged reads with errors and the hand-made reads (errors at the boundary positions, runs across k-mer 63 / 64, two runs,
     reads of K - 1, K, K + 1 bases, more than 256 k-mers, nothing solid, an ambiguous site, two edits in one word); min_count 0, 1, 2,

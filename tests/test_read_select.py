@@ -73,7 +73,7 @@ def assert_select(pkg, got, want, what):
 
 # ---- 1. the rule ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("paired", [False, True])
-@pytest.mark.parametrize("K", [21, 31, 33, 63, 95])
+@pytest.mark.parametrize("K", [21, 31, 33, 63, 95, 65, 97])
 def test_select_equals_the_rule(pkg, synth, K, paired):
     c = case(K)
     words = synth.pack_2bit(c["batch"])
@@ -105,7 +105,7 @@ def test_select_equals_the_rule(pkg, synth, K, paired):
 
 
 # ---- 2. counts past 65 535 --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K", [21, 63, 95])
+@pytest.mark.parametrize("K", [21, 63, 95, 65, 97])
 def test_select_counts_past_65535(pkg, synth, K):
     """the poly-A reads of test_profile_counts_past_65535: medians past 65 535, and a read that is half poly-A, half tandem repeat,
     at a max_cv_pct where the saturated counts say "not aberrant" and the counts as they are would say "aberrant" """

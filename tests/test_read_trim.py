@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 COPIES = (1, 3, 8, 64)
 LONG_COPIES = 4
 PIECE = 3000                                            # the long transcript is counted in pieces that pass 1 takes: PIECE + K - 1 bases
-assert PIECE + 95 - 1 <= 4059                           # ... at every K of this file (SDT_PASS1_MAX_READ_LEN)
+assert PIECE + 97 - 1 <= 4059                           # ... at every K of this file (SDT_PASS1_MAX_READ_LEN)
 
 
 def settings(K):
@@ -115,7 +115,7 @@ def assert_trim(pkg, got, want, what):
 
 
 # ---- 1. the rule ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K", [21, 31, 33, 63, 95])
+@pytest.mark.parametrize("K", [21, 31, 33, 63, 95, 65, 97])
 def test_trim_equals_the_rule(pkg, synth, K):
     c = case(K)
     words = synth.pack_2bit(c["batch"])
@@ -153,7 +153,7 @@ def test_trim_equals_the_rule(pkg, synth, K):
 
 
 # ---- 2. counts past 65 535 --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K", [21, 63, 95])
+@pytest.mark.parametrize("K", [21, 63, 95, 65, 97])
 def test_trim_counts_past_65535(pkg, synth, K):
     """the poly-A and tandem-repeat reads of test_profile_counts_past_65535 and a read that is half one, half the other: with min_count
     between the two counts and above 65 535 it is cut to its poly-A half -- counts saturated at 65 535 would call every k-mer weak"""

@@ -48,7 +48,7 @@ def test_kmer_owner_is_strand_symmetric():
     import oracle_binding as ob
     pkg = ge.load_package()
     rng = np.random.default_rng(5)
-    for K in (21, 31, 47, 63, 95, 127):
+    for K in (21, 31, 33, 47, 63, 65, 95, 97, 127):
         nw = 1 if K <= 31 else (2 if K <= 63 else 4)
         for _ in range(40):
             codes = rng.integers(0, 4, size=K, dtype=np.uint8)

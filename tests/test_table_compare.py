@@ -42,7 +42,7 @@ def same(got, want, what):
 
 
 # ---- 1. the model, per key width ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K,flags", [(23, 0), (31, 1), (31, 2), (47, 0), (63, 0), (95, 0), (127, 0)])
+@pytest.mark.parametrize("K,flags", [(23, 0), (31, 1), (31, 2), (47, 0), (63, 0), (95, 0), (127, 0), (33, 0), (65, 0), (97, 0)])
 def test_matrix_and_totals_equal_the_model(pkg, synth, K, flags):
     """1, 2 and 4 key words, both pass-1 kernel families at K = 31 (SDT_FLAG_DIRECT = 1, SDT_FLAG_PARTITION = 2).  64 x 64, and 2 x 8192:
     the cell cap exactly, where the workgroup's matrix fills 64 KiB of LDS.  Named cells: the B-only k-mers (row 0: a kernel without its

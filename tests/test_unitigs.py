@@ -55,7 +55,7 @@ def whole_list(g, info):
 
 
 # ---- 1. the model, per key width ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K,flags", [(23, 0), (31, 1), (31, 2), (47, 0), (63, 0), (95, 0), (127, 0)])
+@pytest.mark.parametrize("K,flags", [(23, 0), (31, 1), (31, 2), (47, 0), (63, 0), (95, 0), (127, 0), (33, 0), (65, 0), (97, 0)])
 def test_unitigs_equal_the_model(pkg, synth, K, flags):
     """1, 2 and 4 key words, both pass-1 kernel families at K = 31; min_count 2 and 1, and an upper bound with min_link 3"""
     case = bu.built_case(K)

@@ -58,7 +58,7 @@ def check_model(m):
     uu.assert_overlaps(m)
 
 
-@pytest.mark.parametrize("K", [23, 31])
+@pytest.mark.parametrize("K", [23, 31, 33, 65, 97])
 def test_the_cases_hold_what_they_are_built_for(K):
     """the figures of the built cases, so that a case that lost its point fails without a GPU; every link is seen from both sides; every
     inner stretch of a bubble side is exactly one unitig; the list is the same after every read was reverse-complemented"""
@@ -68,7 +68,7 @@ def test_the_cases_hold_what_they_are_built_for(K):
         m = uu.Unitigs(case["nodes"], K, min_count=min_count)
         check_model(m)
         assert m.info[2] == n and m.info[1] == 2 * n and m.info[3] == 0 and m.dangling == 0
-        assert m.info[6] == case["longest"] == {23: 3022, 31: 3030}[K]      # the long side of the detour is one unitig
+        assert m.info[6] == case["longest"] == {23: 3022, 31: 3030, 33: 3032, 65: 3064, 97: 3096}[K]      # the long side of the detour is one unitig
         seen = {(u, o, v, o2) for u, v, o, o2, _, _ in m.links}
         assert all((v, 1 - o2, u, 1 - o) in seen for u, o, v, o2 in seen)
         # a bubble side with inner nodes: the first of them starts a unitig (or ends its mirror) with the same nodes, min and sum

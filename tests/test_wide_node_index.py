@@ -123,7 +123,7 @@ def _same_records(ra, rb, nj):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("K,L,variant,p", [(31, 150, 1, 4), (47, 150, 2, 5), (75, 200, 4, 3)])
+@pytest.mark.parametrize("K,L,variant,p", [(31, 150, 1, 4), (47, 150, 2, 5), (75, 200, 4, 3), (97, 250, 4, 5)])
 def test_wide_form_equals_the_narrow_one(pkg, synth, monkeypatch, K, L, variant, p):
     """two contexts on the same reads, the default form and the 64-bit one with the nodes numbered from 2^32 + 12345: layout, labelled
     walks, labelled junctions, the minor-out commit, the edges and the host's look-up index agree"""
