@@ -1342,8 +1342,61 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  * one cycle in the worst case (real ones are a PhiX or a mitochondrion).  SDT_ENOMEM leaves nothing allocated.  unitigs_seqs
  * and unitigs_links hold the offsets and the bytes they return.
  * One lane walks one unitig, so a wavefront waits for its longest: accepted for transcripts, whose unitigs are thousands of nodes
- * long.  Out of scope: a list-ranking formulation for genome-length unitigs (single ones of millions of nodes); a k-mer -> unitig
- * look-up; read or mate threading; removing tips or popping bubbles; sharded contexts; tables of even K; 2^32 unitigs and more. */
+ * long.  Out of scope: a list-ranking formulation for genome-length unitigs (single ones of millions of nodes); mate threading
+ * (the k-mer -> unitig look-up and read threading are the block below); removing tips or popping bubbles; sharded contexts; tables
+ * of even K; 2^32 unitigs and more.
+ *
+ * Reads threaded through the unitig list: a k-mer -> unitig index over the list of unitigs_begin, and every read laid on the list as
+ * a path of segments -- what quantifies unitigs by reads, phases a bubble by the reads that cross both of its ends, shows which
+ * links one read traverses in a row, and what a GAF line says on the GFA of the list.  Needs the counted table and a list begun with
+ * sdt_gpu_unitigs_begin, and writes nothing to the table, to the kept reads or to any cache or tally of the context.  Added without
+ * a change of SDT_ABI_VERSION: the four calls, the three structs and the constant are additions.
+ *     Integers only.  Everything is exact and does not depend on the table's size or layout, on the pass-1 kernel family, on the
+ *     launch geometry, or on how a host batch is cut into pieces.
+ *     LIVE NODES, ORIENTED WORDS, SUCCESSORS, JOIN, UNITIG and ID are those of the unitig rule above, word for word.
+ *     LABEL.  Every live node with stored canonical key c lies in one reported unitig u at one position i, counted from 0 in the
+ *     reported orientation x0 .. x(n-1): s = 0 if x_i = c, s = 1 if x_i = revcomp(c).
+ *     PLACEMENT.  A k-mer word w, as given, whose node is live has place(w) = (u, i, o): o = 0 when w = x_i -- the read runs along
+ *     the reported orientation -- and o = 1 when w = revcomp(x_i).
+ *     READS.  A read of len bases has n = max(len - K + 1, 0) k-mers w_0 .. w_(n-1), forward as read.  Position p CONTINUES p - 1
+ *     iff both k-mers are live, they lie in the same unitig with the same o, and i_p = i_(p-1) + 1 for o = 0 or i_p = i_(p-1) - 1
+ *     for o = 1.  There is no modular arithmetic: going round a circular unitig is NOT a continuation, it is the closing link.  A
+ *     SEGMENT is a maximal run of live positions in which each position continues the one before.  The join of a segment that
+ *     starts at p: 0 if p = 0 or w_(p-1) is not live (the first segment, or one after a gap); 1 if the out counter of w_(p-1)
+ *     towards the last base of w_p is >= min_link -- the out side of the bubble rule, read from w_(p-1)'s own node: the transition
+ *     is LINKED; 2 otherwise: the k-mers are adjacent in the read, and that is no edge of this graph.
+ *     SEGMENT RECORD (sdt_path_seg, 24 bytes): unitig; info = o | join << 1; read_pos = p; unitig_pos = i of its FIRST k-mer;
+ *     kmers; reserved 0.  For o = 1 the segment covers positions unitig_pos down to unitig_pos - kmers + 1.
+ *     READ RECORD (sdt_read_path, 24 bytes): kmers = n; live = the live k-mers of the read; segs = its segments; breaks = the
+ *     segments after the first whose join != 1; first, last = the unitig of the first and of the last segment, or SDT_UNITIG_NONE.
+ *     What follows: the kmers of a read's segments sum to live.  In a table that pass 1 counted, a segment with join 1 starts at
+ *     the in end of its oriented unitig (v, o') -- unitig_pos 0 for o' = 0, nodes - 1 for o' = 1 -- the segment before it ends at
+ *     the out end of (u, o), and (u, o, v, o', the last base of w_p) is a record of sdt_gpu_unitigs_links.
+ *   unitigs_index:  labels the table slot of every live node, 8 bytes per slot (the unitig; pos << 1 | s; all ones elsewhere), and
+ *                   waits.  info[4]: [0] nodes labelled  [1] unitigs  [2] bytes held  [3] 0; info may be NULL.  The labelled nodes
+ *                   are the live nodes of begin, or the call fails with SDT_ESTATE as unitigs_seqs does.  A second index rebuilds.
+ *                   The index goes with the list: unitigs_end, a second unitigs_begin and sdt_gpu_destroy free it, and what makes
+ *                   the list stale makes it stale.  No limit of 2^32 slots.
+ *   unitigs_lookup: the place of n k-mers, keys as for search_kmers, either strand: sdt_unitig_pos { unitig, pos, info = o of the
+ *                   word AS GIVEN, reserved 0 }; absent or not live: unitig SDT_UNITIG_NONE, the rest 0.
+ *   unitigs_reads:  a host batch, staged in pieces like cluster_reads: rec nreads records; seg_offsets[nreads + 1] the prefix sums
+ *                   of rec[].segs; the segments of read r at segs[seg_offsets[r]] in ascending read_pos; *n_segs the total.
+ *                   segs == NULL with capacity == 0 asks for the records and the offsets only.  SDT_EFULL when the total exceeds
+ *                   capacity: rec, seg_offsets and *n_segs are complete, what segs holds is unspecified.  Waits.
+ *   unitigs_reads_device: the same with every buffer on the device (d_segs may be NULL with capacity 0); waits for the total.
+ * There is NO limit on the length of a read: a wavefront walks a read 64 k-mer positions at a time and keeps no strip of it (a
+ * segment that is open at the end of a step is carried in registers).  nreads == 0 (n == 0 for lookup): SDT_OK, nothing touched.
+ * SDT_ESTATE: under the state rules of search_kmers with their messages; without a list, after unitigs_end and once the table has
+ * changed, with the messages of the unitig calls; lookup and the reads forms without an index: "no sdt_gpu_unitigs_index of this
+ * unitig list".  SDT_EINVAL, before any launch: NULL arguments; offsets not monotonic or nwords too short (as for reads); a read
+ * of 2^32 bases or more (host form).  SDT_ELIMIT: a unitig of 2^31 nodes or more (a position and its strand share 32 bits).
+ * Device memory: from unitigs_index to unitigs_end 8 B per table slot; SDT_ENOMEM leaves nothing of it allocated and the list as
+ * it was.  The forms over reads hold 8 B per read of segment counts and the scan's scratch, and the host form what cluster_reads
+ * holds with records of 24 B, 8 B per read of offsets and the segments of one piece.  Every read is walked twice, first for its
+ * record and the number of its segments, then, after an exclusive scan on the device, for the segments at their offsets.  A
+ * clustering, a bubble list and an assembly tally stay valid across these calls.
+ * Out of scope: a form over the reads kept in HBM (there is no kept form and there are no keep bytes); mate links between unitigs;
+ * accumulating per-unitig support on the device; aligning through the stretches that are not live; sharded contexts; even K. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -1395,6 +1448,10 @@ typedef struct { uint64_t sum_a, sum_b; uint32_t len_a, len_b, min_a, min_b, src
 typedef struct { uint32_t min_count, max_count, min_link, flags; } sdt_unitig_params;   /* flags: 0 */
 typedef struct { uint64_t sum; uint32_t nodes, min, max, info; } sdt_unitig;   /* 24 bytes */
 typedef struct { uint32_t from, to, info, reserved; } sdt_unitig_link;   /* 16 bytes */
+#define SDT_UNITIG_NONE 0xFFFFFFFFu  /* sdt_unitig_pos.unitig, sdt_read_path.first / last: no unitig */
+typedef struct { uint32_t unitig, pos, info, reserved; } sdt_unitig_pos;   /* 16 bytes */
+typedef struct { uint32_t kmers, live, segs, breaks, first, last; } sdt_read_path;   /* 24 bytes */
+typedef struct { uint32_t unitig, info, read_pos, unitig_pos, kmers, reserved; } sdt_path_seg;   /* 24 bytes */
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -1545,6 +1602,13 @@ int sdt_gpu_unitigs_seqs(sdt_ctx *ctx, uint64_t first, uint64_t n, uint8_t *base
 int sdt_gpu_unitigs_links(sdt_ctx *ctx, uint64_t first, uint64_t n, sdt_unitig_link *links, uint64_t capacity,
                           uint64_t *n_links, uint64_t *n_dangling);
 int sdt_gpu_unitigs_end(sdt_ctx *ctx);
+int sdt_gpu_unitigs_index(sdt_ctx *ctx, uint64_t info[4]);
+int sdt_gpu_unitigs_lookup(sdt_ctx *ctx, const uint64_t *keys, uint64_t n, sdt_unitig_pos *out);
+int sdt_gpu_unitigs_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                          uint64_t nreads, sdt_read_path *rec, uint64_t *seg_offsets, sdt_path_seg *segs,
+                          uint64_t capacity, uint64_t *n_segs);
+int sdt_gpu_unitigs_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                                 void *d_rec, void *d_seg_offsets, void *d_segs, uint64_t capacity, uint64_t *n_segs);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

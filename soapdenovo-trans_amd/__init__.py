@@ -232,6 +232,12 @@ _ABI = [
     ("sdt_gpu_unitigs_seqs", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
     ("sdt_gpu_unitigs_links", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_unitigs_end", _c.c_int, [_c.c_void_p]),
+    ("sdt_gpu_unitigs_index", _c.c_int, [_c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_unitigs_lookup", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p]),
+    ("sdt_gpu_unitigs_reads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                         _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_unitigs_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                                _c.POINTER(_c.c_uint64)]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -306,6 +312,12 @@ BUBBLE_MAX_LEN = 1 << 20                                 # SDT_BUBBLE_MAX_LEN
 # outdeg(last word) << 8.  sdt_unitig_link: 16 bytes per link; info = o | o' << 1 | base << 2 | link counter << 8
 UNITIG_DTYPE = np.dtype([("sum", np.uint64)] + [(f, np.uint32) for f in ("nodes", "min", "max", "info")])
 UNITIG_LINK_DTYPE = np.dtype([(f, np.uint32) for f in ("from", "to", "info", "reserved")])
+# reads threaded through the unitig list (include/sdt_gpu.h).  sdt_unitig_pos: the place of a k-mer, info = o of the word as given.
+# sdt_read_path: one record of 24 bytes per read.  sdt_path_seg: one of 24 bytes per segment; info = o | join << 1
+UNITIG_NONE = 0xFFFFFFFF                                 # SDT_UNITIG_NONE
+UNITIG_POS_DTYPE = np.dtype([(f, np.uint32) for f in ("unitig", "pos", "info", "reserved")])
+READ_PATH_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "live", "segs", "breaks", "first", "last")])
+PATH_SEG_DTYPE = np.dtype([(f, np.uint32) for f in ("unitig", "info", "read_pos", "unitig_pos", "kmers", "reserved")])
 
 
 class NormParams(_c.Structure):
@@ -1517,6 +1529,62 @@ class PregraphGPU:
 
     def unitigs_end(self):
         self._check(self.lib.sdt_gpu_unitigs_end(self._ctx))
+
+    # -- reads threaded through that list (the rule: include/sdt_gpu.h): a label per table slot from unitigs_index to unitigs_end
+    def unitigs_index(self):
+        """-> info uint64[4]: nodes labelled (= the live nodes), unitigs, bytes held (8 per table slot), 0"""
+        info = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_unitigs_index(self._ctx, _ptr(info)))
+        return info
+
+    def unitigs_lookup(self, keys):
+        """keys: uint64[n, key_words] (or [n] for one word), either strand -> UNITIG_POS_DTYPE[n]: unitig, position and o of the word
+        as given; UNITIG_NONE and zeros for an absent or not live k-mer"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        nw = self.nw
+        assert keys.size % nw == 0
+        n = keys.size // nw
+        out = np.full(4 * n, 0xABABABAB, dtype=np.uint32).view(UNITIG_POS_DTYPE)
+        self._check(self.lib.sdt_gpu_unitigs_lookup(self._ctx, _ptr(keys) if n else None, n, _ptr(out) if n else None))
+        return out
+
+    def unitigs_reads(self, words, offsets, capacity: int = None, segments: bool = True):
+        """-> (READ_PATH_DTYPE[nreads]; seg_offsets uint64[nreads + 1]; PATH_SEG_DTYPE[seg_offsets[nreads]]: the segments of read r are
+        segs[seg_offsets[r] : seg_offsets[r + 1]]).  segments=False: the records and the offsets only (segs is None).  capacity: the
+        room to offer (default: what is needed, asked for first; SdtError SDT_EFULL when it is too small: e.rec, e.seg_offsets and
+        e.n_segs are complete)"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        rec = np.zeros(n, dtype=READ_PATH_DTYPE)
+        seg_offsets = np.zeros(n + 1, dtype=np.uint64)
+        total = ctypes.c_uint64()
+        if not segments or capacity is None:
+            self._check(self.lib.sdt_gpu_unitigs_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, _ptr(rec), _ptr(seg_offsets), None, 0,
+                                                       ctypes.byref(total)))
+            if not segments:
+                return rec, seg_offsets, None
+            capacity = total.value
+        segs = np.zeros(max(capacity, 1), dtype=PATH_SEG_DTYPE)
+        rc = self.lib.sdt_gpu_unitigs_reads(self._ctx, _ptr(words), words.size, _ptr(offsets), n, _ptr(rec), _ptr(seg_offsets), _ptr(segs), capacity,
+                                            ctypes.byref(total))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.rec, e.seg_offsets, e.n_segs = rec, seg_offsets, total.value
+            raise e
+        return rec, seg_offsets, segs[: total.value]
+
+    def unitigs_reads_device(self, d_words, d_offsets, nreads: int, d_rec, d_seg_offsets, d_segs=None, capacity: int = 0):
+        """device buffers; d_rec holds nreads records of 24 bytes, d_seg_offsets nreads + 1 uint64, d_segs (optional) capacity records of
+        24 bytes -> the segments of all reads (waits for the total; SdtError SDT_EFULL with e.n_segs when d_segs is too small)"""
+        total = ctypes.c_uint64()
+        rc = self.lib.sdt_gpu_unitigs_reads_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, _ptr(d_rec), _ptr(d_seg_offsets), _ptr(d_segs), capacity,
+                                                   ctypes.byref(total))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.n_segs = total.value
+            raise e
+        return total.value
 
     # -- this context's counted table against another's (the rule: include/sdt_gpu.h); nothing is written to either
     def compare(self, other, rows: int = 64, cols: int = 64):

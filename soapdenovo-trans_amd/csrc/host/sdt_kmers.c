@@ -138,6 +138,15 @@
  *       prefix.unitigs.fa: >id nodes=.. sum=.. min=.. max=.. circular=.. and the sequence on one line
  *       prefix.unitigs.gfa: GFA 1: H, an S line per unitig (LN:i: bases, KC:i: sum), an L line per link, written once (lc:i: its counter)
  *       and one line: unitigs: live L unitigs N circular C isolated I dead_ends D links E bases B longest M n50 X
+ *   sdt-kmers thread -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--max-count M, default 0 = no limit]
+ *                    [--min-link L, default 1] -o prefix
+ *       every read as a path over the unitig list (sdt_gpu_unitigs_begin, sdt_gpu_unitigs_index, sdt_gpu_unitigs_reads; the rule:
+ *       include/sdt_gpu.h).  No read is kept: the libraries are streamed a second time, in the same ordinals.  Ids are 1-based
+ *       (threadsplit.c, which documents the files)
+ *       prefix.readPaths: per read in stream order  kmers live segs breaks path
+ *       prefix.unitigReads: per unitig  id reads segments kmers
+ *       prefix.unitigs, prefix.unitigs.fa, prefix.unitigs.gfa: as `unitigs` writes them
+ *       and one line: thread: reads R placed P whole W broken B unplaced U short S segments G linked L unlinked X
  *
  * The query file is read and checked before the device is touched.
  *
@@ -170,6 +179,7 @@
 #include "clustersplit.h"
 #include "bubblesplit.h"
 #include "unitigsplit.h"
+#include "threadsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -383,6 +393,15 @@ static void usage(void)
 	        "              circular=.. and the sequence), prefix.unitigs.gfa (GFA 1: S id seq LN:i:bases KC:i:sum; L from +/- to +/- <K-1>M\n"
 	        "              lc:i:link, every link once); ids from 1 in ascending order of the first k-mer\n"
 	        "           and one line: unitigs: live L unitigs N circular C isolated I dead_ends D links E bases B longest M n50 X\n"
+	        "       sdt-kmers thread -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--max-count M, default 0]\n"
+	        "                        [--min-link L, default 1] -o prefix\n"
+	        "           every read laid on the unitig list as a path: the unitigs as `unitigs` finds and writes them, a k-mer -> unitig index\n"
+	        "           on the device, and the libraries streamed a second time through it\n"
+	        "           -> prefix.readPaths (per read in stream order: kmers live segs breaks path; path = * or the read's segments, each\n"
+	        "              <sep><dir><id>:<unitig_pos>+<kmers> with sep none for the first, - over a link of the graph, ~ adjacent in the read\n"
+	        "              without such a link, / after k-mers that are not in the graph, and dir > along the unitig, < against it),\n"
+	        "              prefix.unitigReads (per unitig: id reads segments kmers), prefix.unitigs, .unitigs.fa and .unitigs.gfa as above\n"
+	        "           and one line: thread: reads R placed P whole W broken B unplaced U short S segments G linked L unlinked X\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -474,6 +493,7 @@ typedef struct {
 	sdt_ref_set refs;                                                        /* of rfile[] */
 	query_set qs;                                                            /* of qfile */
 	qtrim_state *qtrim;                                                      /* qtrim's records, taken while the reads streamed */
+	const sdt_cfg *cfg;                                                      /* thread: the libraries, for its second pass over them */
 } options;
 
 /* ---- the device half that every read stage shares ------------------------------------------------------------------------------------ */
@@ -1544,12 +1564,12 @@ static int run_bubbles(sdt_ctx *gpu, unsigned long long reads, options *opt, con
 /* ---- unitigs ----------------------------------------------------------------------------------------------------------------------------- */
 /* `unitigs`: the list on the device, then fetched and written a piece at a time with the sequences of that piece, then the links of
  * every piece behind the S lines (unitigsplit.c) */
-static int run_unitigs(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+/* sdt_gpu_unitigs_begin and the three files; the list stays open, line: the summary */
+static int unitigs_files(sdt_ctx *gpu, options *opt, uint64_t info[8], char line[SDT_UNITIG_SUMMARY_MAX])
 {
-	(void)reads; (void)pairs;
 	enum { PIECE = 1 << 16 };
 	const sdt_unitig_params prm = {(uint32_t)opt->min_count, opt->cluster.max_count, opt->cluster.min_link, 0};
-	uint64_t info[8], cap = 0, link_cap = 0;
+	uint64_t cap = 0, link_cap = 0;
 	if (SDT_CALL(sdt_gpu_unitigs_begin, gpu, &prm, info)) return 1;
 	const int nw = sdt_gpu_key_words(gpu);
 	uint64_t *keys = (uint64_t *)malloc((size_t)PIECE * 2 * (size_t)nw * sizeof *keys), *offs = (uint64_t *)malloc(((size_t)PIECE + 1) * sizeof *offs);
@@ -1558,7 +1578,7 @@ static int run_unitigs(sdt_ctx *gpu, unsigned long long reads, options *opt, con
 	uint8_t *bases = NULL;
 	sdt_unitig_link *links = NULL;
 	if (!keys || !offs || !rec || !tally.nodes) { fprintf(stderr, "sdt-kmers: out of memory for the unitigs\n"); return 1; }
-	char path[4200], fa_path[4200], gfa_path[4200], line[SDT_UNITIG_SUMMARY_MAX];
+	char path[4200], fa_path[4200], gfa_path[4200];
 	FILE *f = stats_open(path, opt->outname, ".unitigs");
 	if (!f) return cannot_write(path);
 	FILE *fa = stats_open(fa_path, opt->outname, ".unitigs.fa");
@@ -1593,15 +1613,113 @@ static int run_unitigs(sdt_ctx *gpu, unsigned long long reads, options *opt, con
 	if (fclose(f) != 0) return cannot_write(path);
 	if (fclose(fa) != 0) return cannot_write(fa_path);
 	if (fclose(gfa) != 0) return cannot_write(gfa_path);
-	if (SDT_CALL(sdt_gpu_unitigs_end, gpu)) return 1;
 	sdt_unitig_summary(line, info, &tally, opt->K);
-	fputs(line, stdout);
 	free(keys); free(offs); free(rec); free(bases); free(links); free(tally.nodes);
 	return 0;
 }
 
+static int run_unitigs(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	(void)reads; (void)pairs;
+	uint64_t info[8];
+	char line[SDT_UNITIG_SUMMARY_MAX];
+	if (unitigs_files(gpu, opt, info, line) != 0 || SDT_CALL(sdt_gpu_unitigs_end, gpu)) return 1;
+	fputs(line, stdout);
+	return 0;
+}
+
+/* ---- thread ------------------------------------------------------------------------------------------------------------------------------ */
+/* `thread`: the unitig list and its files as `unitigs` writes them, the index, then the libraries once more through
+ * sdt_gpu_unitigs_reads, batch by batch as they are parsed: the records by read ordinal, the segments in the order the batches came
+ * with every read's place among them; then one walk over the ordinals writes the lines (threadsplit.c) */
+typedef struct {
+	sdt_ctx *gpu;
+	uint64_t reads;                                                          /* the ordinals: what pass 1 streamed */
+	sdt_read_path *rec;                                                      /* by ordinal; kmers 0xFFFFFFFF: no read */
+	uint64_t *seg_at;                                                        /* by ordinal: its first segment in segs */
+	sdt_path_seg *segs;
+	uint64_t n_segs, cap_segs, seen;
+	sdt_read_path *b_rec;                                                    /* of one batch */
+	uint64_t *b_offs, b_cap;
+} thread_state;
+
+static int thread_batch(void *user, const sdt_batch *b, uint64_t ord_base, uint64_t ord_stride)
+{
+	thread_state *st = (thread_state *)user;
+	if (!b->nreads) return 0;
+	if (ord_base + (b->nreads - 1) * ord_stride >= st->reads) {
+		fprintf(stderr, "sdt-kmers: the second pass over the libraries holds read %llu, the first held %llu reads\n",
+		        (unsigned long long)(ord_base + (b->nreads - 1) * ord_stride) + 1, (unsigned long long)st->reads);
+		return -1;
+	}
+	if (b->nreads > st->b_cap) {
+		free(st->b_rec); free(st->b_offs);
+		st->b_cap = b->nreads;
+		st->b_rec = (sdt_read_path *)malloc((size_t)st->b_cap * sizeof *st->b_rec);
+		st->b_offs = (uint64_t *)malloc(((size_t)st->b_cap + 1) * sizeof *st->b_offs);
+		if (!st->b_rec || !st->b_offs) { fprintf(stderr, "sdt-kmers: out of memory for the paths of %llu reads\n", (unsigned long long)b->nreads); return -1; }
+	}
+	uint64_t n = 0;
+	/* into the room behind the segments so far; where that is too small the call says how many there are, and runs once more */
+	int rc = sdt_gpu_unitigs_reads(st->gpu, b->words, b->nwords, b->offsets, b->nreads, st->b_rec, st->b_offs, st->segs ? st->segs + st->n_segs : NULL,
+	                               st->segs ? st->cap_segs - st->n_segs : 0, &n);
+	if (rc == SDT_EFULL || (rc == SDT_OK && !st->segs && n)) {
+		const uint64_t cap = 2 * (st->n_segs + n);
+		sdt_path_seg *more = (sdt_path_seg *)realloc(st->segs, (size_t)cap * sizeof *more);
+		if (!more) { fprintf(stderr, "sdt-kmers: out of memory for %llu path segments\n", (unsigned long long)cap); return -1; }
+		st->segs = more;
+		st->cap_segs = cap;
+		rc = sdt_gpu_unitigs_reads(st->gpu, b->words, b->nwords, b->offsets, b->nreads, st->b_rec, st->b_offs, st->segs + st->n_segs, st->cap_segs - st->n_segs, &n);
+	}
+	if (rc != SDT_OK) { gpu_fail("sdt_gpu_unitigs_reads"); return -1; }
+	for (uint64_t i = 0; i < b->nreads; i++) {
+		const uint64_t ord = ord_base + i * ord_stride;
+		st->rec[ord] = st->b_rec[i];
+		st->seg_at[ord] = st->n_segs + st->b_offs[i];
+	}
+	st->n_segs += n;
+	st->seen += b->nreads;
+	return 0;
+}
+
+static int run_thread(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	(void)pairs;
+	uint64_t info[8], iinfo[4];
+	char uline[SDT_UNITIG_SUMMARY_MAX], line[SDT_THREAD_SUMMARY_MAX], path[4200];
+	if (unitigs_files(gpu, opt, info, uline) != 0 || SDT_CALL(sdt_gpu_unitigs_index, gpu, iinfo)) return 1;
+	thread_state st = {gpu, reads, (sdt_read_path *)records_alloc(reads, sizeof(sdt_read_path), 0xFF), (uint64_t *)records_alloc(reads, sizeof(uint64_t), 0),
+	                   NULL, 0, 0, 0, NULL, NULL, 0};
+	sdt_thread_tally tally;
+	if (!st.rec || !st.seg_at) return 1;
+	if (sdt_thread_tally_init(&tally, info[2]) != 0) { fprintf(stderr, "sdt-kmers: out of memory for %llu unitigs\n", (unsigned long long)info[2]); return 1; }
+	const sdt_cfg *cfg = opt->cfg;
+	const int max_read_len = cfg->max_rd_len ? cfg->max_rd_len : 100;
+	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
+	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : opt->threads;
+	if (sdt_stream_reads(cfg, max_read_len, parse_threads > 0 ? parse_threads : 1, chunk, 0, thread_batch, &st, NULL) != 0) return 1;
+	if (!all_reads_came_back(reads, st.seen, "threaded")) return 1;
+	if (SDT_CALL(sdt_gpu_unitigs_end, gpu)) return 1;
+	FILE *f = stats_open(path, opt->outname, ".readPaths");
+	if (!f) return cannot_write(path);
+	for (uint64_t ord = 0; ord < reads; ord++) {
+		if (st.rec[ord].kmers == 0xFFFFFFFFu) continue;                      /* (an ordinal that no read has) */
+		const int rc = sdt_thread_read_write(f, st.rec + ord, st.segs ? st.segs + st.seg_at[ord] : NULL, &tally);
+		if (rc == -2) { fprintf(stderr, "sdt-kmers: the path of read %llu does not add up\n", (unsigned long long)ord + 1); return 1; }
+		if (rc != 0) return cannot_write(path);
+	}
+	if (fclose(f) != 0) return cannot_write(path);
+	f = stats_open(path, opt->outname, ".unitigReads");
+	if (!f || (sdt_thread_unitig_reads_write(f, &tally) != 0) | (fclose(f) != 0)) return cannot_write(path);
+	sdt_thread_summary(line, &tally);
+	fputs(line, stdout);
+	sdt_thread_tally_free(&tally);
+	free(st.rec); free(st.seg_at); free(st.segs); free(st.b_rec); free(st.b_offs);
+	return 0;
+}
+
 /* ---- the command line ------------------------------------------------------------------------------------------------------------------ */
-enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, COMPARE, CLUSTER, BUBBLES, UNITIGS, N_SUBCOMMANDS };
+enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, COMPARE, CLUSTER, BUBBLES, UNITIGS, THREAD, N_SUBCOMMANDS };
 
 static const struct {
 	const char *name;
@@ -1621,6 +1739,7 @@ static const struct {
 	[CLUSTER] = {"cluster", 1, 1, 2, run_cluster},
 	[BUBBLES] = {"bubbles", 0, 0, 2, run_bubbles},
 	[UNITIGS] = {"unitigs", 0, 0, 2, run_unitigs},
+	[THREAD] = {"thread", 0, 0, 2, run_thread},            /* (streams the libraries a second time on its own: no read is kept) */
 };
 
 enum { O_MAX_K = 1000, O_DEVICE, O_TARGET, O_MAX_CV, O_SEED, O_MIN_COV, O_MIN_LEN, O_CORRECT, O_MATE_SWAP, O_TAIL3, O_TAIL5, O_MIN_OVERLAP, O_ERROR_PCT,
@@ -1651,8 +1770,8 @@ static const struct { int code; const char *name; unsigned owners; const char *b
 	{O_ASSEMBLY, "--assembly", BIT(EVALUATE), "evaluate", 0}, {O_ROWS, "--rows", BIT(EVALUATE) | BIT(COMPARE), "evaluate", SDT_CMP_MAX_CELLS / 2},
 	{O_AGAINST, "--against", BIT(COMPARE), "compare", 0}, {O_COLS, "--cols", BIT(COMPARE), "compare", SDT_CMP_MAX_CELLS / 2},
 	{O_SELECT, "--select", BIT(COMPARE), "compare", 0}, {O_MAX_LIST, "--max-list", BIT(COMPARE), "compare", 1ULL << 31},
-	{O_MAX_COUNT, "--max-count", BIT(CLUSTER) | BIT(BUBBLES) | BIT(UNITIGS), "cluster", UINT32_MAX},
-	{O_MIN_LINK, "--min-link", BIT(CLUSTER) | BIT(BUBBLES) | BIT(UNITIGS), "cluster", 63},
+	{O_MAX_COUNT, "--max-count", BIT(CLUSTER) | BIT(BUBBLES) | BIT(UNITIGS) | BIT(THREAD), "cluster", UINT32_MAX},
+	{O_MIN_LINK, "--min-link", BIT(CLUSTER) | BIT(BUBBLES) | BIT(UNITIGS) | BIT(THREAD), "cluster", 63},
 	{O_PICK, "--pick", BIT(CLUSTER), "cluster", 0}, {O_MAX_BRANCH, "--max-branch", BIT(BUBBLES), "bubbles", SDT_BUBBLE_MAX_LEN},
 };
 
@@ -1844,7 +1963,7 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 		fprintf(stderr, "sdt-kmers: --max-merged %u is below --min-merged %u: no pair could merge (0: no limit)\n", opt->merge.max_len, opt->merge.min_len);
 		return 255;
 	}
-	if ((sub == CLUSTER || sub == BUBBLES || sub == UNITIGS) && opt->cluster.max_count != 0 && opt->cluster.max_count < (opt->min_count > 1 ? opt->min_count : 1ul)) {
+	if ((sub == CLUSTER || sub == BUBBLES || sub == UNITIGS || sub == THREAD) && opt->cluster.max_count != 0 && opt->cluster.max_count < (opt->min_count > 1 ? opt->min_count : 1ul)) {
 		fprintf(stderr, "sdt-kmers: --max-count %u is below -c %lu: no node could be live (0: no limit)\n", opt->cluster.max_count, opt->min_count);
 		return 255;
 	}
@@ -1980,6 +2099,7 @@ int main(int argc, char **argv)
 	memset(&pairs, 0, sizeof pairs);
 	static qtrim_state qst;
 	opt.qtrim = &qst;
+	opt.cfg = &cfg;
 	unsigned long long reads = 0;
 	if (sub == COMPARE) {
 		/* A is counted and drained before B's libraries stream; both contexts then live side by side on the device */

@@ -224,7 +224,9 @@ struct sdt_ctx {
 		void *rec = nullptr;               // n records of 24 bytes
 		uint64_t *idx_keys = nullptr;      // n x nw words: revcomp(last), ascending
 		uint32_t *idx_id = nullptr;        // ... and the unitig of each
+		void *lab = nullptr;               // unitigs_index (sdt_thread.hip): 8 B per table slot, (unitig, pos << 1 | s) or all ones; goes with the list
 		uint64_t n = 0;
+		uint64_t live = 0;                 // the live nodes of unitigs_begin (= the sum of the records' nodes)
 		uint64_t slots = 0;                // the table's slots at unitigs_begin
 		uint32_t min_count = 0, max_count = 0, min_link = 0;    // the rule of that begin (min_count: already max(min_count, 1))
 		bool open = false, stale = false;

@@ -5,6 +5,7 @@
 // the table, the kept reads or a cache of the context.  What the context keeps from unitigs_begin to unitigs_end is the sorted list -- N
 // records and their two words each -- and that second order, and nothing per table slot; it is tied to the state of the table it was found
 // on as the bubble list is (search_cache_drop, delow, the graph phases mark it stale).  State rules are those of the read stages.
+// (sdt_thread.hip adds its index to this state when asked: 8 B per slot, freed where the list is.)
 #include "sdt_readstage.hpp"
 #include "sdt_unitig_kernels.cuh"
 #include <rocprim/rocprim.hpp>
@@ -29,6 +30,7 @@ static void unitigs_free(sdt_ctx *c)
 	if (c->ug.rec) (void)hipFree(c->ug.rec);
 	if (c->ug.idx_keys) (void)hipFree(c->ug.idx_keys);
 	if (c->ug.idx_id) (void)hipFree(c->ug.idx_id);
+	if (c->ug.lab) (void)hipFree(c->ug.lab);                 // (the index of sdt_thread.hip goes with the list)
 	c->ug = sdt_ctx::Unitigs();
 }
 
@@ -207,6 +209,7 @@ static int unitigs_build(sdt_ctx *c, const ClusterRule &rule, uint64_t info[8])
 		if (rc != SDT_OK) return rc;
 	}
 	c->ug.n = n;
+	c->ug.live = n_live;
 	if (ev) {
 		HIPCHK(hipEventRecord(ev->b, c->stream));
 		ev->kmers = slots;                                   // (slots scanned, not k-mers)
