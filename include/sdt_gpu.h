@@ -1395,8 +1395,81 @@ int sdt_gpu_align_reads_device(sdt_ctx *ctx, const void *d_packed_words, const v
  * holds with records of 24 B, 8 B per read of offsets and the segments of one piece.  Every read is walked twice, first for its
  * record and the number of its segments, then, after an exclusive scan on the device, for the segments at their offsets.  A
  * clustering, a bubble list and an assembly tally stay valid across these calls.
- * Out of scope: a form over the reads kept in HBM (there is no kept form and there are no keep bytes); mate links between unitigs;
- * accumulating per-unitig support on the device; aligning through the stretches that are not live; sharded contexts; even K. */
+ * Out of scope: a form over the reads kept in HBM (there is no kept form and there are no keep bytes); aligning through the
+ * stretches that are not live; sharded contexts; even K.  (What the reads support of the list is the block below.)
+ *
+ * Read support tallied on the unitig list: how many segments and k-mers of the added reads lie in every unitig, how many reads
+ * traverse every link, which way into a unitig goes with which way out (junctions), and mate links between unitigs: which unitigs a
+ * read pair bridges -- what picks paths through the graph, separates isoforms at a shared exon and joins unitigs that no single read
+ * joins, without taking the segments of sdt_gpu_unitigs_reads to the host.  Needs the counted table, a list begun with
+ * sdt_gpu_unitigs_begin and its sdt_gpu_unitigs_index, and writes nothing to the table, to the kept reads, to the index or to any
+ * other cache or tally of the context.  Added without a change of SDT_ABI_VERSION: the nine calls and the five structs are additions.
+ *     Integers only.  Everything is exact and does not depend on the order of the reads, on their split over add calls, on how a
+ *     host batch is cut into pieces (pairs stay together), on the launch geometry, or on the table's size or layout.
+ *     LIVE NODES, ORIENTED WORDS, SUCCESSORS, JOIN, UNITIG, ID, LABEL, PLACEMENT, READS, CONTINUES, SEGMENT and join are those of
+ *     the threading rule above, word for word.
+ *     ORIENTED UNITIG.  The 32-bit number ou = unitig << 1 | o; its mirror is ou ^ 1.
+ *     PER UNITIG (sdt_unitig_support, 16 bytes): segs = the segments of all added reads in the unitig; kmers = the sum of their
+ *     kmers.  (The number of DISTINCT READS per unitig stays on the host, in `sdt-kmers thread`: an exact set of reads per unitig
+ *     has no bounded form on the device.)
+ *     PER LINK (sdt_link_support, 16 bytes), parallel to the records of sdt_gpu_unitigs_links for the same range, record by record.
+ *     A segment with join 1 that starts at position p is one TRAVERSAL of (the ou of the segment before it, b = the last base of
+ *     w_p).  along of a record (from, o, b) = the traversals of (from << 1 | o, b).  against = the along of the record's MIRROR, the
+ *     one record that leaves (to, o' ^ 1) for (from, o ^ 1) -- it may be the record itself; its base is the complement of the first
+ *     base of the record's out word.  The closing link of a circular unitig is a link like any other.  A traversal that matches no
+ *     record of the list is counted in the totals only (imported tables whose link ends disagree).
+ *     JUNCTIONS (sdt_unitig_junction, 24 bytes: from, via, to oriented unitigs; reserved 0; count).  Two consecutive segments of one
+ *     read that both have join 1 pass through the unitig of the first of them: with f the ou of the segment before it, v its own and
+ *     t that of the second, one PASSAGE (f, v, t).  A passage and its mirror (t ^ 1, v ^ 1, f ^ 1) are the same junction, reported
+ *     in the form whose via has o = 0.  The list is ascending by (via, from, to) and holds the junctions with count > 0.  (The set
+ *     is keyed by the unitig of via and the two bases with which via is left at either end; in a table whose link ends disagree,
+ *     passages that share those share a junction, reported with the ends of the first of them that came.)
+ *     MATE LINKS (sdt_mate_link, 16 bytes: from, to oriented unitigs; pairs).  paired: reads 2r and 2r + 1 are mates, as for
+ *     cluster_reads; forward/reverse libraries only.  If both mates have a segment, with (a, oa) the LAST segment of mate 1 and
+ *     (b, ob) the LAST segment of mate 2 -- mate 2 is read against the fragment, so its last segment is the one nearest mate 1 --
+ *     the link is from = a << 1 | oa, to = b << 1 | (ob ^ 1).  from == to: the pair lies within one unitig, counted in the totals
+ *     only.  Otherwise (from, to) and (to ^ 1, from ^ 1) are one link, reported in the form with the smaller (from, to); the list
+ *     is ascending by (from, to).
+ *     TOTALS, uint64_t[12]: [0] reads  [1] reads with a segment  [2] segments  [3] live k-mers  [4] traversals  [5] traversals
+ *     without a record  [6] passages  [7] pairs  [8] pairs with both mates placed  [9] pairs within one unitig  [10] pairs tallied
+ *     as mate links  [11] entries dropped for want of room.
+ *   unitigs_support_begin:     a cleared tally for the list, kept on the device; a second begin replaces the first.  params:
+ *                              junction_capacity and mate_capacity = the DISTINCT junctions / mate links the two sets may hold, 0 =
+ *                              that list is not kept (its passages and pairs are still counted in the totals) and its fetch gives
+ *                              SDT_EINVAL; flags and reserved 0.
+ *   unitigs_support_add:       a host batch, staged in pieces like cluster_reads (a piece of a paired batch holds whole pairs);
+ *                              ADDS to the tally and waits.
+ *   unitigs_support_add_device: the same for a batch on the device.
+ *   unitigs_support_unitigs:   the tallies of unitigs first .. first + n - 1.
+ *   unitigs_support_links:     the tallies of the link records of that range, *n_links of them, in the order of unitigs_links;
+ *                              SDT_EFULL with *n_links set when capacity is too small; out == NULL with capacity == 0: the size.
+ *   unitigs_support_junctions, unitigs_support_mates: the list, *n entries; SDT_EFULL with *n set when capacity is too small; out ==
+ *                              NULL with capacity == 0: the size only.  The lists are put in order on the host.
+ *   unitigs_support_totals:    the twelve totals.  [5] is made here from the link records of the whole list.
+ *   unitigs_support_end:       frees the tally; without a begin SDT_OK.  The tally is part of the list's state: unitigs_end, a second
+ *                              unitigs_begin and sdt_gpu_destroy free it; what makes the list or the index stale makes it stale; a
+ *                              second unitigs_index leaves it valid, because the labels are a function of the list.
+ * WHEN A SET FILLS UP -- more distinct entries than its capacity -- the add call returns SDT_EFULL, and so does every add after it
+ * and every fetch of that set; totals[11] counts the entries that found no room (their number, unlike all else, depends on the
+ * order of arrival).  The tallies per unitig and per link, the other set and the other totals stay exact.  The slots of a set are
+ * the next power of two of twice its capacity, 64 at the least.
+ * There is no limit on the length of a read.  nreads == 0 (n == 0): SDT_OK, nothing touched.
+ * SDT_ESTATE: under the state rules of search_kmers with their messages; without a list, once the table has changed and without an
+ * index with the messages of the threading calls; every call but begin and end without a begin:
+ * "no sdt_gpu_unitigs_support_begin of this unitig list".  SDT_EINVAL, before any launch and with nothing added: NULL arguments;
+ * non-zero flags or reserved; a capacity above 2^36; paired with an odd nreads; offsets not monotonic or nwords too short; a read of
+ * 2^32 bases or more (host form); a range past N.  SDT_ELIMIT at begin: 2^31 - 1 unitigs or more (an oriented unitig is 32 bits,
+ * and all ones is no unitig).
+ * Device memory, from support_begin to support_end / unitigs_end: 16 B per unitig of tallies, 8 x 8 B per unitig of link slots
+ * (two orientations x four bases), 24 B per slot of the junction set and 16 B per slot of the mate-link set, and 384 B of
+ * counters; SDT_ENOMEM leaves nothing of it allocated.  unitigs_support_links holds the records and the tallies of its range,
+ * 32 B per link; the host form of add holds what cluster_reads stages.  ON THE HOST a fetch of a list holds a copy of that set's
+ * whole slot array (24 B or 16 B per slot, whatever it holds), and unitigs_support_totals the link records of the whole list and the
+ * link slots, 8 x 8 B per unitig: ask for them once, after the last add.  One wavefront walks one read or one pair, once; every
+ * count is a 64-bit atomic add at the memory side, the totals are summed per wavefront first.  A clustering, a bubble list and an
+ * assembly tally stay valid across these calls.
+ * Out of scope: the distinct reads per unitig on the device; gap or insert-size estimates on mate links; reverse/forward or
+ * same-strand libraries; a form over the reads kept in HBM; sharded contexts; even K. */
 typedef struct { uint32_t kmers, found, solid, min, median, max; } sdt_read_cov;
 typedef struct { uint32_t kmers, weak, runs, fixed; } sdt_read_fix;
 typedef struct { uint32_t kmers, median, cov, verdict; } sdt_read_pick;
@@ -1452,6 +1525,11 @@ typedef struct { uint32_t from, to, info, reserved; } sdt_unitig_link;   /* 16 b
 typedef struct { uint32_t unitig, pos, info, reserved; } sdt_unitig_pos;   /* 16 bytes */
 typedef struct { uint32_t kmers, live, segs, breaks, first, last; } sdt_read_path;   /* 24 bytes */
 typedef struct { uint32_t unitig, info, read_pos, unitig_pos, kmers, reserved; } sdt_path_seg;   /* 24 bytes */
+typedef struct { uint64_t junction_capacity, mate_capacity; uint32_t flags, reserved; } sdt_support_params;   /* flags, reserved: 0 */
+typedef struct { uint64_t segs, kmers; } sdt_unitig_support;   /* 16 bytes */
+typedef struct { uint64_t along, against; } sdt_link_support;   /* 16 bytes */
+typedef struct { uint32_t from, via, to, reserved; uint64_t count; } sdt_unitig_junction;   /* 24 bytes */
+typedef struct { uint32_t from, to; uint64_t pairs; } sdt_mate_link;   /* 16 bytes */
 int sdt_gpu_search_kmers(sdt_ctx *ctx, const uint64_t *keys, uint64_t n,
                          uint32_t *count, uint32_t *l_links, uint32_t *r_flags, uint8_t *status);
 int sdt_gpu_search_kmers_device(sdt_ctx *ctx, const void *d_keys, uint64_t n,
@@ -1609,6 +1687,18 @@ int sdt_gpu_unitigs_reads(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t n
                           uint64_t capacity, uint64_t *n_segs);
 int sdt_gpu_unitigs_reads_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
                                  void *d_rec, void *d_seg_offsets, void *d_segs, uint64_t capacity, uint64_t *n_segs);
+int sdt_gpu_unitigs_support_begin(sdt_ctx *ctx, const sdt_support_params *params);
+int sdt_gpu_unitigs_support_add(sdt_ctx *ctx, const uint32_t *packed_words, uint64_t nwords, const uint64_t *offsets,
+                                uint64_t nreads, int paired);
+int sdt_gpu_unitigs_support_add_device(sdt_ctx *ctx, const void *d_packed_words, const void *d_offsets, uint64_t nreads,
+                                       int paired);
+int sdt_gpu_unitigs_support_unitigs(sdt_ctx *ctx, uint64_t first, uint64_t n, sdt_unitig_support *out);
+int sdt_gpu_unitigs_support_links(sdt_ctx *ctx, uint64_t first, uint64_t n, sdt_link_support *out, uint64_t capacity,
+                                  uint64_t *n_links);
+int sdt_gpu_unitigs_support_junctions(sdt_ctx *ctx, sdt_unitig_junction *out, uint64_t capacity, uint64_t *n);
+int sdt_gpu_unitigs_support_mates(sdt_ctx *ctx, sdt_mate_link *out, uint64_t capacity, uint64_t *n);
+int sdt_gpu_unitigs_support_totals(sdt_ctx *ctx, uint64_t totals[12]);
+int sdt_gpu_unitigs_support_end(sdt_ctx *ctx);
 
 /* ---- introspection / measurement --------------------------------------------------------------- */
 int sdt_gpu_key_words(const sdt_ctx *ctx);         /* 1 (K<=31), 2 (K<=63), 4 (K<=127) */

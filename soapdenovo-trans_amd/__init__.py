@@ -238,6 +238,15 @@ _ABI = [
                                          _c.POINTER(_c.c_uint64)]),
     ("sdt_gpu_unitigs_reads_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,
                                                 _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_unitigs_support_begin", _c.c_int, [_c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_unitigs_support_add", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    ("sdt_gpu_unitigs_support_add_device", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int]),
+    ("sdt_gpu_unitigs_support_unitigs", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p]),
+    ("sdt_gpu_unitigs_support_links", _c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_unitigs_support_junctions", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_unitigs_support_mates", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    ("sdt_gpu_unitigs_support_totals", _c.c_int, [_c.c_void_p, _c.c_void_p]),
+    ("sdt_gpu_unitigs_support_end", _c.c_int, [_c.c_void_p]),
 ]
 ABI_SYMBOLS = [n for n, _, _ in _ABI]
 
@@ -318,6 +327,14 @@ UNITIG_NONE = 0xFFFFFFFF                                 # SDT_UNITIG_NONE
 UNITIG_POS_DTYPE = np.dtype([(f, np.uint32) for f in ("unitig", "pos", "info", "reserved")])
 READ_PATH_DTYPE = np.dtype([(f, np.uint32) for f in ("kmers", "live", "segs", "breaks", "first", "last")])
 PATH_SEG_DTYPE = np.dtype([(f, np.uint32) for f in ("unitig", "info", "read_pos", "unitig_pos", "kmers", "reserved")])
+# read support tallied on the unitig list (include/sdt_gpu.h).  An oriented unitig is unitig << 1 | o.  sdt_unitig_support: 16 bytes per
+# unitig; sdt_link_support: 16 per link record of unitigs_links; sdt_unitig_junction: 24 per junction; sdt_mate_link: 16 per mate link
+UNITIG_SUPPORT_DTYPE = np.dtype([("segs", np.uint64), ("kmers", np.uint64)])
+LINK_SUPPORT_DTYPE = np.dtype([("along", np.uint64), ("against", np.uint64)])
+UNITIG_JUNCTION_DTYPE = np.dtype([(f, np.uint32) for f in ("from", "via", "to", "reserved")] + [("count", np.uint64)])
+MATE_LINK_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("pairs", np.uint64)])
+SUPPORT_TOTALS = ("reads", "placed", "segments", "live", "traversals", "no_record", "passages", "pairs", "pairs_placed", "pairs_within", "pairs_linked",
+                  "dropped")
 
 
 class NormParams(_c.Structure):
@@ -427,6 +444,14 @@ class UnitigParams(_c.Structure):
 
     def __init__(self, min_count=2, max_count=0, min_link=1, flags=0):
         super().__init__(min_count, max_count, min_link, flags)
+
+
+class SupportParams(_c.Structure):
+    """sdt_support_params; a capacity of 0: that list is not kept"""
+    _fields_ = [("junction_capacity", _c.c_uint64), ("mate_capacity", _c.c_uint64), ("flags", _c.c_uint32), ("reserved", _c.c_uint32)]
+
+    def __init__(self, junction_capacity=0, mate_capacity=0, flags=0, reserved=0):
+        super().__init__(junction_capacity, mate_capacity, flags, reserved)
 
 
 class CmpRange(_c.Structure):
@@ -1585,6 +1610,75 @@ class PregraphGPU:
             e.n_segs = total.value
             raise e
         return total.value
+
+    # -- what the reads support of that list (the rule: include/sdt_gpu.h): a tally on the device from unitigs_support_begin to
+    # unitigs_support_end / unitigs_end; the add forms ADD
+    def unitigs_support_begin(self, params=None):
+        """params: SupportParams or its fields as a dict (junction_capacity, mate_capacity: the distinct entries the two sets may hold)"""
+        prm = params if isinstance(params, SupportParams) else SupportParams(**(params or {}))
+        self._check(self.lib.sdt_gpu_unitigs_support_begin(self._ctx, ctypes.addressof(prm)))
+
+    def unitigs_support_add(self, words, offsets, paired: bool = False):
+        """a host batch; paired: reads 2r and 2r + 1 are mates.  SdtError SDT_EFULL when a set has filled up"""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_unitigs_support_add(self._ctx, _ptr(words), words.size, _ptr(offsets), len(offsets) - 1, int(paired)))
+
+    def unitigs_support_add_device(self, d_words, d_offsets, nreads: int, paired: bool = False):
+        self._check(self.lib.sdt_gpu_unitigs_support_add_device(self._ctx, _ptr(d_words), _ptr(d_offsets), nreads, int(paired)))
+
+    def unitigs_support_unitigs(self, first: int, n: int):
+        """-> UNITIG_SUPPORT_DTYPE[n]: the segments and their k-mers in unitigs first .. first + n - 1"""
+        out = np.zeros(n, dtype=UNITIG_SUPPORT_DTYPE)
+        self._check(self.lib.sdt_gpu_unitigs_support_unitigs(self._ctx, first, n, _ptr(out) if n else None))
+        return out
+
+    def unitigs_support_links(self, first: int, n: int, capacity: int = None):
+        """-> LINK_SUPPORT_DTYPE[...] parallel to unitigs_links(first, n).  capacity: the room to offer (default: what is needed, asked
+        for first; SdtError SDT_EFULL when it is too small: e.n_links holds the need)"""
+        n_links = _c.c_uint64(0)
+        if n == 0:
+            return np.zeros(0, dtype=LINK_SUPPORT_DTYPE)
+        if capacity is None:
+            self._check(self.lib.sdt_gpu_unitigs_support_links(self._ctx, first, n, None, 0, ctypes.byref(n_links)))
+            capacity = n_links.value
+        out = np.zeros(max(capacity, 1), dtype=LINK_SUPPORT_DTYPE)
+        rc = self.lib.sdt_gpu_unitigs_support_links(self._ctx, first, n, _ptr(out), capacity, ctypes.byref(n_links))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.n_links = n_links.value
+            raise e
+        return out[: n_links.value]
+
+    def _support_list(self, fn, dtype, capacity):
+        n = _c.c_uint64(0)
+        if capacity is None:
+            self._check(fn(self._ctx, None, 0, ctypes.byref(n)))
+            capacity = n.value
+        out = np.zeros(max(capacity, 1), dtype=dtype)
+        rc = fn(self._ctx, _ptr(out), capacity, ctypes.byref(n))
+        if rc != SDT_OK:
+            e = SdtError(rc, self.lib.sdt_gpu_last_error().decode())
+            e.n = n.value
+            raise e
+        return out[: n.value]
+
+    def unitigs_support_junctions(self, capacity: int = None):
+        """-> UNITIG_JUNCTION_DTYPE[...], ascending by (via, from, to); SdtError SDT_EFULL when the set filled up or capacity is too small"""
+        return self._support_list(self.lib.sdt_gpu_unitigs_support_junctions, UNITIG_JUNCTION_DTYPE, capacity)
+
+    def unitigs_support_mates(self, capacity: int = None):
+        """-> MATE_LINK_DTYPE[...], ascending by (from, to)"""
+        return self._support_list(self.lib.sdt_gpu_unitigs_support_mates, MATE_LINK_DTYPE, capacity)
+
+    def unitigs_support_totals(self):
+        """-> uint64[12], named by SUPPORT_TOTALS"""
+        totals = np.zeros(12, dtype=np.uint64)
+        self._check(self.lib.sdt_gpu_unitigs_support_totals(self._ctx, _ptr(totals)))
+        return totals
+
+    def unitigs_support_end(self):
+        self._check(self.lib.sdt_gpu_unitigs_support_end(self._ctx))
 
     # -- this context's counted table against another's (the rule: include/sdt_gpu.h); nothing is written to either
     def compare(self, other, rows: int = 64, cols: int = 64):

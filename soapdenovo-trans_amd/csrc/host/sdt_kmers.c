@@ -147,6 +147,17 @@
  *       prefix.unitigReads: per unitig  id reads segments kmers
  *       prefix.unitigs, prefix.unitigs.fa, prefix.unitigs.gfa: as `unitigs` writes them
  *       and one line: thread: reads R placed P whole W broken B unplaced U short S segments G linked L unlinked X
+ *   sdt-kmers support -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--max-count M, default 0 = no limit]
+ *                     [--min-link L, default 1] [--max-junctions J, default 4194304] -o prefix
+ *       what the reads support of the unitig list, tallied on the device (sdt_gpu_unitigs_support_*; the rule: include/sdt_gpu.h).  No
+ *       read is kept and no segment comes to the host: the libraries are streamed a second time.  Ids are 1-based, an oriented unitig
+ *       is <id><+|-> (supportsplit.c, which documents the files).  The mates of a library in two files come in different batches, so
+ *       every batch is added as single reads and no mate link is tallied: those are for the callers of the library
+ *       prefix.unitigSupport: per unitig  id segments kmers cov_x100
+ *       prefix.linkSupport: per link that the GFA writes  from o to o' along against
+ *       prefix.junctions: from via to count
+ *       prefix.unitigs, prefix.unitigs.fa, prefix.unitigs.gfa: as `unitigs` writes them
+ *       and one line: support: reads R placed P segments G kmers L traversals T no_record N passages X junctions J dropped Z
  *
  * The query file is read and checked before the device is touched.
  *
@@ -180,6 +191,7 @@
 #include "bubblesplit.h"
 #include "unitigsplit.h"
 #include "threadsplit.h"
+#include "supportsplit.h"
 #include "../../../include/sdt_gpu.h"
 
 #define SDT_MAX_K 127
@@ -402,6 +414,12 @@ static void usage(void)
 	        "              without such a link, / after k-mers that are not in the graph, and dir > along the unitig, < against it),\n"
 	        "              prefix.unitigReads (per unitig: id reads segments kmers), prefix.unitigs, .unitigs.fa and .unitigs.gfa as above\n"
 	        "           and one line: thread: reads R placed P whole W broken B unplaced U short S segments G linked L unlinked X\n"
+	        "       sdt-kmers support -s lib.cfg -K k [-p threads] [-d d] [-c min_count, default 2] [--max-count M, default 0]\n"
+	        "                         [--min-link L, default 1] [--max-junctions J, default 4194304] -o prefix\n"
+	        "           what the reads support of the unitig list, tallied on the device; every batch is added as single reads\n"
+	        "           prefix.unitigSupport: id segments kmers cov_x100    prefix.linkSupport: from o to o' along against\n"
+	        "           prefix.junctions: from via to count    and the files of `unitigs`\n"
+	        "           and one line: support: reads R placed P segments G kmers L traversals T no_record N passages X junctions J dropped Z\n"
 	        "       (--device n: HIP device ordinal; --max-k 31|63|127: the variant whose K limit applies, default by K)\n");
 }
 
@@ -488,6 +506,7 @@ typedef struct {
 	sdt_cluster_params cluster;
 	uint32_t pick[2];                                                        /* cluster: --pick, as the library takes it */
 	int pick_given;
+	uint64_t max_junctions;                                                  /* support: the distinct junctions its set may hold */
 	uint32_t max_branch;                                                     /* bubbles: --max-branch, the inner nodes of a side at the most */
 	sdt_adapter_list ads;                                                    /* of afile[] */
 	sdt_ref_set refs;                                                        /* of rfile[] */
@@ -1718,8 +1737,88 @@ static int run_thread(sdt_ctx *gpu, unsigned long long reads, options *opt, cons
 	return 0;
 }
 
+/* ---- support ----------------------------------------------------------------------------------------------------------------------------- */
+/* `support`: the unitig list and its files as `unitigs` writes them, the index, a cleared tally, then the libraries once more through
+ * sdt_gpu_unitigs_support_add, batch by batch as they are parsed; then the tallies are fetched a piece at a time and written
+ * (supportsplit.c).  Nothing per read or per segment comes to the host */
+typedef struct { sdt_ctx *gpu; uint64_t seen; } support_state;
+
+static int support_batch(void *user, const sdt_batch *b, uint64_t ord_base, uint64_t ord_stride)
+{
+	support_state *st = (support_state *)user;
+	(void)ord_base; (void)ord_stride;
+	if (!b->nreads) return 0;
+	/* (single reads: the mates of two files are in different batches) */
+	if (sdt_gpu_unitigs_support_add(st->gpu, b->words, b->nwords, b->offsets, b->nreads, 0) != SDT_OK) { gpu_fail("sdt_gpu_unitigs_support_add"); return -1; }
+	st->seen += b->nreads;
+	return 0;
+}
+
+static int run_support(sdt_ctx *gpu, unsigned long long reads, options *opt, const sdt_pair_ranges *pairs)
+{
+	(void)pairs;
+	enum { PIECE = 1 << 16 };
+	uint64_t info[8], iinfo[4], totals[12], nj = 0, link_cap = 0;
+	char uline[SDT_UNITIG_SUMMARY_MAX], line[SDT_SUPPORT_SUMMARY_MAX], path[4200];
+	const sdt_support_params prm = {opt->max_junctions, 0, 0, 0};           /* (no mate links: see support_batch) */
+	if (unitigs_files(gpu, opt, info, uline) != 0 || SDT_CALL(sdt_gpu_unitigs_index, gpu, iinfo) || SDT_CALL(sdt_gpu_unitigs_support_begin, gpu, &prm)) return 1;
+	support_state st = {gpu, 0};
+	const sdt_cfg *cfg = opt->cfg;
+	const int max_read_len = cfg->max_rd_len ? cfg->max_rd_len : 100;
+	const size_t chunk = sdt_test_env("SDT_CHUNK_BYTES") ? (size_t)strtoull(sdt_test_env("SDT_CHUNK_BYTES"), NULL, 10) : (size_t)(32u << 20);
+	const int parse_threads = sdt_env("SDT_PARSE_THREADS") ? atoi(sdt_env("SDT_PARSE_THREADS")) : opt->threads;
+	if (sdt_stream_reads(cfg, max_read_len, parse_threads > 0 ? parse_threads : 1, chunk, 0, support_batch, &st, NULL) != 0) return 1;
+	if (!all_reads_came_back(reads, st.seen, "tallied")) return 1;
+	sdt_unitig *rec = (sdt_unitig *)malloc((size_t)PIECE * sizeof *rec);
+	sdt_unitig_support *us = (sdt_unitig_support *)malloc((size_t)PIECE * sizeof *us);
+	sdt_unitig_link *links = NULL;
+	sdt_link_support *ls = NULL;
+	if (!rec || !us) { fprintf(stderr, "sdt-kmers: out of memory for the tallies\n"); return 1; }
+	FILE *f = stats_open(path, opt->outname, ".unitigSupport");
+	if (!f) return cannot_write(path);
+	for (uint64_t first = 0; first < info[2]; first += PIECE) {
+		const uint64_t n = info[2] - first < PIECE ? info[2] - first : PIECE;
+		if (SDT_CALL(sdt_gpu_unitigs_fetch, gpu, first, n, NULL, rec) || SDT_CALL(sdt_gpu_unitigs_support_unitigs, gpu, first, n, us)) return 1;
+		if (sdt_support_unitigs_write(f, rec, us, first, n) != 0) return cannot_write(path);
+	}
+	if (fclose(f) != 0) return cannot_write(path);
+	f = stats_open(path, opt->outname, ".linkSupport");
+	if (!f) return cannot_write(path);
+	for (uint64_t first = 0; first < info[2]; first += PIECE) {
+		const uint64_t n = info[2] - first < PIECE ? info[2] - first : PIECE;
+		uint64_t n_links = 0;
+		if (SDT_CALL(sdt_gpu_unitigs_links, gpu, first, n, NULL, 0, &n_links, NULL)) return 1;
+		if (n_links > link_cap) {
+			free(links); free(ls);
+			link_cap = n_links;
+			links = (sdt_unitig_link *)malloc((size_t)link_cap * sizeof *links);
+			ls = (sdt_link_support *)malloc((size_t)link_cap * sizeof *ls);
+			if (!links || !ls) { fprintf(stderr, "sdt-kmers: out of memory for %llu links\n", (unsigned long long)link_cap); return 1; }
+		}
+		if (!n_links) continue;
+		if (SDT_CALL(sdt_gpu_unitigs_links, gpu, first, n, links, link_cap, &n_links, NULL) || SDT_CALL(sdt_gpu_unitigs_support_links, gpu, first, n, ls, link_cap, &n_links))
+			return 1;
+		if (sdt_support_links_write(f, links, ls, n_links) != 0) return cannot_write(path);
+	}
+	if (fclose(f) != 0) return cannot_write(path);
+	/* the junctions; a set that is not kept (a capacity of 0) leaves an empty file */
+	sdt_unitig_junction *jn = NULL;
+	if (opt->max_junctions) {
+		if (SDT_CALL(sdt_gpu_unitigs_support_junctions, gpu, NULL, 0, &nj)) return 1;
+		if (!(jn = (sdt_unitig_junction *)malloc((size_t)(nj ? nj : 1) * sizeof *jn))) { fprintf(stderr, "sdt-kmers: out of memory for %llu junctions\n", (unsigned long long)nj); return 1; }
+		if (SDT_CALL(sdt_gpu_unitigs_support_junctions, gpu, jn, nj, &nj)) return 1;
+	}
+	f = stats_open(path, opt->outname, ".junctions");
+	if (!f || (sdt_support_junctions_write(f, jn, nj) != 0) | (fclose(f) != 0)) return cannot_write(path);
+	if (SDT_CALL(sdt_gpu_unitigs_support_totals, gpu, totals) || SDT_CALL(sdt_gpu_unitigs_support_end, gpu) || SDT_CALL(sdt_gpu_unitigs_end, gpu)) return 1;
+	sdt_support_summary(line, totals, nj);
+	fputs(line, stdout);
+	free(rec); free(us); free(links); free(ls); free(jn);
+	return 0;
+}
+
 /* ---- the command line ------------------------------------------------------------------------------------------------------------------ */
-enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, COMPARE, CLUSTER, BUBBLES, UNITIGS, THREAD, N_SUBCOMMANDS };
+enum { PROFILE, QUERY, CORRECT, NORMALIZE, TRIM, DEDUP, CLIP, OVERLAP, COMPLEXITY, QTRIM, SCREEN, MERGE, QC, EVALUATE, COMPARE, CLUSTER, BUBBLES, UNITIGS, THREAD, SUPPORT, N_SUBCOMMANDS };
 
 static const struct {
 	const char *name;
@@ -1740,11 +1839,12 @@ static const struct {
 	[BUBBLES] = {"bubbles", 0, 0, 2, run_bubbles},
 	[UNITIGS] = {"unitigs", 0, 0, 2, run_unitigs},
 	[THREAD] = {"thread", 0, 0, 2, run_thread},            /* (streams the libraries a second time on its own: no read is kept) */
+	[SUPPORT] = {"support", 0, 0, 2, run_support},         /* (the same) */
 };
 
 enum { O_MAX_K = 1000, O_DEVICE, O_TARGET, O_MAX_CV, O_SEED, O_MIN_COV, O_MIN_LEN, O_CORRECT, O_MATE_SWAP, O_TAIL3, O_TAIL5, O_MIN_OVERLAP, O_ERROR_PCT,
        O_MIN_TAIL, O_TAIL_ERROR_PCT, O_MAX_ERR, O_MAX_SCORE, O_MAX_LOW, O_TRIM_LOW, O_PHRED, O_CUT_Q, O_LOW_Q, O_MAX_LOW_BASES, O_MAX_EE, O_SCREEN_K,
-       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED, O_CYCLES, O_FROM_END, O_ASSEMBLY, O_ROWS, O_AGAINST, O_COLS, O_SELECT, O_MAX_LIST, O_MAX_COUNT, O_MIN_LINK, O_PICK, O_MAX_BRANCH };
+       O_MIN_HITS, O_MIN_HIT_PCT, O_KEEP_MATCHED, O_MIN_MERGED, O_MAX_MERGED, O_CYCLES, O_FROM_END, O_ASSEMBLY, O_ROWS, O_AGAINST, O_COLS, O_SELECT, O_MAX_LIST, O_MAX_COUNT, O_MIN_LINK, O_PICK, O_MAX_BRANCH, O_MAX_JUNCTIONS };
 
 /* the options that belong to some subcommands only: the name as it is printed, who may be given it, what the refusal says after
  * "belongs to" (kept, not derived: --min-overlap names clip alone), and the most its value may be where it takes a whole number */
@@ -1770,9 +1870,10 @@ static const struct { int code; const char *name; unsigned owners; const char *b
 	{O_ASSEMBLY, "--assembly", BIT(EVALUATE), "evaluate", 0}, {O_ROWS, "--rows", BIT(EVALUATE) | BIT(COMPARE), "evaluate", SDT_CMP_MAX_CELLS / 2},
 	{O_AGAINST, "--against", BIT(COMPARE), "compare", 0}, {O_COLS, "--cols", BIT(COMPARE), "compare", SDT_CMP_MAX_CELLS / 2},
 	{O_SELECT, "--select", BIT(COMPARE), "compare", 0}, {O_MAX_LIST, "--max-list", BIT(COMPARE), "compare", 1ULL << 31},
-	{O_MAX_COUNT, "--max-count", BIT(CLUSTER) | BIT(BUBBLES) | BIT(UNITIGS) | BIT(THREAD), "cluster", UINT32_MAX},
-	{O_MIN_LINK, "--min-link", BIT(CLUSTER) | BIT(BUBBLES) | BIT(UNITIGS) | BIT(THREAD), "cluster", 63},
+	{O_MAX_COUNT, "--max-count", BIT(CLUSTER) | BIT(BUBBLES) | BIT(UNITIGS) | BIT(THREAD) | BIT(SUPPORT), "cluster", UINT32_MAX},
+	{O_MIN_LINK, "--min-link", BIT(CLUSTER) | BIT(BUBBLES) | BIT(UNITIGS) | BIT(THREAD) | BIT(SUPPORT), "cluster", 63},
 	{O_PICK, "--pick", BIT(CLUSTER), "cluster", 0}, {O_MAX_BRANCH, "--max-branch", BIT(BUBBLES), "bubbles", SDT_BUBBLE_MAX_LEN},
+	{O_MAX_JUNCTIONS, "--max-junctions", BIT(SUPPORT), "support", 1ULL << 36},
 };
 
 /* the letters of a tail option as a mask of base codes (A0 C1 T2 G3), or -1 */
@@ -1822,7 +1923,7 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 	                                   {"against", required_argument, 0, O_AGAINST}, {"cols", required_argument, 0, O_COLS},
 	                                   {"select", required_argument, 0, O_SELECT}, {"max-list", required_argument, 0, O_MAX_LIST},
 	                                   {"max-count", required_argument, 0, O_MAX_COUNT}, {"min-link", required_argument, 0, O_MIN_LINK},
-	                                   {"pick", required_argument, 0, O_PICK}, {"max-branch", required_argument, 0, O_MAX_BRANCH},
+	                                   {"pick", required_argument, 0, O_PICK}, {"max-branch", required_argument, 0, O_MAX_BRANCH}, {"max-junctions", required_argument, 0, O_MAX_JUNCTIONS},
 	                                   {0, 0, 0, 0}};
 	int c;
 	while ((c = getopt_long(argc, argv, "s:K:p:d:c:o:q:a:g:r:", longopts, NULL)) != -1) {
@@ -1938,6 +2039,7 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 			if (v == 0) { fprintf(stderr, "sdt-kmers: --max-branch must be at least 1\n"); return 255; }
 			opt->max_branch = (uint32_t)v;
 			break;
+		case O_MAX_JUNCTIONS: opt->max_junctions = v; break;
 		default: usage(); return 255;
 		}
 	}
@@ -1963,7 +2065,7 @@ static int parse_options(int argc, char **argv, int sub, options *opt)
 		fprintf(stderr, "sdt-kmers: --max-merged %u is below --min-merged %u: no pair could merge (0: no limit)\n", opt->merge.max_len, opt->merge.min_len);
 		return 255;
 	}
-	if ((sub == CLUSTER || sub == BUBBLES || sub == UNITIGS || sub == THREAD) && opt->cluster.max_count != 0 && opt->cluster.max_count < (opt->min_count > 1 ? opt->min_count : 1ul)) {
+	if ((sub == CLUSTER || sub == BUBBLES || sub == UNITIGS || sub == THREAD || sub == SUPPORT) && opt->cluster.max_count != 0 && opt->cluster.max_count < (opt->min_count > 1 ? opt->min_count : 1ul)) {
 		fprintf(stderr, "sdt-kmers: --max-count %u is below -c %lu: no node could be live (0: no limit)\n", opt->cluster.max_count, opt->min_count);
 		return 255;
 	}
@@ -2080,7 +2182,7 @@ int main(int argc, char **argv)
 	                      .norm = {50, 10000, 0}, .clip = {5, 10, 0, 10, 20, 0, 0, 0}, .overlap = {30, 10, 0, 0}, .cx = {10, 50, 0, 0},
 	                      .qual = {33, 20, 15, 40, 0, 0, 0, 0}, .screen = {1, 0, 0, 0}, .merge = {0, 0, 33, 0},
 	                      .qc = {1024, 33, 0, 0, 0}, .screen_k = 31, .rows = 256, .cols = 64, .max_list = 1000000,
-	                      .cluster = {2, 0, 1, 0}, .pick = {0, 0xFFFFFFFEu}, .max_branch = 1000};                                   /* bbduk's usual figure: a choice, not a measurement */
+	                      .cluster = {2, 0, 1, 0}, .pick = {0, 0xFFFFFFFEu}, .max_branch = 1000, .max_junctions = 1u << 22};                                   /* bbduk's usual figure: a choice, not a measurement */
 	opt.min_count = subcommands[sub].min_count;
 	if (sub == COMPARE) opt.rows = 64;
 	sdt_cfg cfg;

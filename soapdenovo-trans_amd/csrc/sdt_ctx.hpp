@@ -15,6 +15,7 @@
 //   sdt_compare.hip   two counted tables compared: the joint count spectrum and the k-mers within given ranges of both counts (the one
 //                     unit whose entry points take two contexts)
 //   sdt_cluster.hip   the counted table as a graph: its connected components, one label per slot, and the reads' clusters
+//   sdt_unitig.hip    its unitigs and their links; sdt_thread.hip the reads as paths over them; sdt_support.hip what the reads support of them
 //   sdt_bubble.hip    the counted table as a graph again: its bubbles (two non-branching paths between two k-mers), listed and re-walked
 //   sdt_gpu_graph.hip the graph phases (own view of the context: sdt_internal.hpp GraphView)
 // Not part of the ABI: nothing here is visible to a caller of libsdt_gpu.so.
@@ -225,6 +226,10 @@ struct sdt_ctx {
 		uint64_t *idx_keys = nullptr;      // n x nw words: revcomp(last), ascending
 		uint32_t *idx_id = nullptr;        // ... and the unitig of each
 		void *lab = nullptr;               // unitigs_index (sdt_thread.hip): 8 B per table slot, (unitig, pos << 1 | s) or all ones; goes with the list
+		// unitigs_support_begin (sdt_support.hip): one block -- 48 counters, 16 B per unitig of (segs, kmers), 8 x 8 B per unitig of link
+		// slots, the junction set at 24 B and the mate set at 16 B per slot; goes with the list, stays across a second unitigs_index
+		void *sup = nullptr;
+		uint64_t sup_jn_slots = 0, sup_jn_cap = 0, sup_mt_slots = 0, sup_mt_cap = 0;      // slots: a power of two, or 0 = not kept
 		uint64_t n = 0;
 		uint64_t live = 0;                 // the live nodes of unitigs_begin (= the sum of the records' nodes)
 		uint64_t slots = 0;                // the table's slots at unitigs_begin

@@ -385,6 +385,7 @@ int sdt_gpu_destroy(sdt_ctx *c)
 	if (c->ug.idx_keys) (void)hipFree(c->ug.idx_keys);
 	if (c->ug.idx_id) (void)hipFree(c->ug.idx_id);
 	if (c->ug.lab) (void)hipFree(c->ug.lab);
+	if (c->ug.sup) (void)hipFree(c->ug.sup);
 	for (int i = 0; i < 5; i++) if (c->ab[i]) (void)hipFree(c->ab[i]);
 	sk_free(c);
 	shard_free(c);

@@ -31,6 +31,7 @@ static void unitigs_free(sdt_ctx *c)
 	if (c->ug.idx_keys) (void)hipFree(c->ug.idx_keys);
 	if (c->ug.idx_id) (void)hipFree(c->ug.idx_id);
 	if (c->ug.lab) (void)hipFree(c->ug.lab);                 // (the index of sdt_thread.hip goes with the list)
+	if (c->ug.sup) (void)hipFree(c->ug.sup);                 // (... and the tally of sdt_support.hip)
 	c->ug = sdt_ctx::Unitigs();
 }
 
